@@ -19,7 +19,12 @@ the WEAK regime (100,000 rows per rank) under the key `weak`.  Every candidate i
 past --mode-budget-s or past what is left of --total-budget-s; a watchdog ends a run that hangs in a collective after
 --wall-limit-s (480 s: below the 600 s the round-end driver gives a run).
 
-Prints ONE JSON line (rank 0).  `roofline` describes the kernel that takes the most time per step (its `elbo_fwd_kernel`
+Prints ONE JSON line (rank 0).  A plain run sets up, settles, warms up, times --steps steps and prints the headline
+(`value`, `ms_per_step`); every other figure below is measured only with --full (its keys are null otherwise).
+--dump-outputs DIR writes what the last timed step gave its caller (loss, predictions, updated parameters; a fixed seeded
+sample of the rows of a big table) as DIR/<name>.npy: the timed steps start from the initial state, so the same arguments
+give the same arrays from run to run and two builds can be compared output for output.
+With --full: `roofline` describes the kernel that takes the most time per step (its `elbo_fwd_kernel`
 entry is the fused forward ELBO kernel; `frac_fwd_8d` / `frac_K_8d` are SURVEY 8(d)'s own figures against the 0.60
 target); `kernels` lists all of them (HIP events on every 5th step of the timed region); `sustained` = 2,000
 more steps without events; `streamed` = the regime of a caller that cannot keep plans (streamed / shuffled batches): every
@@ -69,11 +74,12 @@ def main():
                     help="N=1.  resident (default): plans are built once per batch before the timed region and reused (the "
                          "reference's loader does not shuffle, vfm-torch.py:121-122); stream: the timed region builds every plan "
                          "it uses, a few steps ahead (VFM.plan_prefetch_depth) on side streams -- the regime of a caller that streams or shuffles batches. "
-                         "Whatever this says, the line carries both figures (`ms_per_step` / `streamed`).")
+                         "Whatever this says, a --full line carries both figures (`ms_per_step` / `streamed`).")
     ap.add_argument("--streamed-steps", type=int, default=400, help="steps of the extra `streamed` region (0: none)")
-    ap.add_argument("--scaling", default="both", choices=["both", "strong", "weak"],
+    ap.add_argument("--scaling", default=None, choices=["both", "strong", "weak"],
                     help="N>1: strong = the workload's global batch split by rows over the ranks (SURVEY cfg4; the headline), "
-                         "weak = that many rows PER rank; both = the two in one run (weak under the key `weak`)")
+                         "weak = that many rows PER rank; both = the two in one run (weak under the key `weak`).  "
+                         "Default: strong, both with --full")
     ap.add_argument("--strong", action="store_true", help="same as --scaling strong")
     ap.add_argument("--mode-budget-s", type=float, default=90.0,
                     help="N>1: a candidate whose 3-step probe projects more than this many seconds for warm-up + timed steps "
@@ -120,9 +126,17 @@ def main():
                          "trajectory); auto: when a batch touches less than 35 %% of the table")
     ap.add_argument("--plain-moments", action="store_true",
                     help="A/B: keep the Adam moments in the plain form (no VFM_FLAG_SCALED_MOMENTS)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel HIP events + roofline, the copy-rate probe, "
+                         "settle.cold, sustained, streamed, regions, cpu_baseline, the rebuilt-plan timing, and (N>1) both "
+                         "scaling regimes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, predictions, updated parameters) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.strong:
         args.scaling = "strong"
+    if args.scaling is None:
+        args.scaling = "both" if args.full else "strong"
     args.event_every = max(1, min(args.event_every, args.steps // 5))       # (at least five sampled steps in a short region)
 
     import threading
@@ -290,7 +304,7 @@ def main():
                         p_.lookahead_rows(ps[(i_ + 1) % len(ps)])
             torch.cuda.synchronize()
             self.plan_build[key] = (time.perf_counter() - t0) / nbt * 1e3
-            if not multi:       # the same once more (discarded): the allocator now has the buffers -- what a loop that
+            if not multi and args.full:       # the same once more (discarded): the allocator now has the buffers -- what a loop that
                 t0 = time.perf_counter()                 # rebuilds its plans every epoch (shuffled batches) pays per batch
                 again = [model.plan(xb, yb, B_global=B * world, process_group=pg, defer_readback=True) for xb, yb in batches]
                 for p_ in again:
@@ -303,6 +317,7 @@ def main():
             return self.plans[key]
 
     step_no = [0]                     # batches are cycled through in order across warm-up and timed regions
+    last_ret = [None]                 # what the last train_step returned: (loss3, pred)
 
     def run_streamed(setup, n):
         """n steps of a caller that keeps NO plan: the plan of batch t + depth (index, normalisers) is built on a side stream
@@ -318,7 +333,8 @@ def main():
         for i in range(n):       # D plans in hand: this batch's, the next one's (named to the step), the ones being built
             s = step_no[0]
             step_no[0] += 1
-            model.train_step(q[0], next_plan=q[1], fused=not args.unfused, prefetch=bt[(s + D) % nbt] + (False,))   # (resident data: no fork)
+            last_ret[0] = model.train_step(q[0], next_plan=q[1], fused=not args.unfused,
+                                           prefetch=bt[(s + D) % nbt] + (False,))   # (resident data: no fork)
             q.pop(0)
             q.append(model.prefetched)
             if trace and i % 50 == 49:
@@ -354,14 +370,16 @@ def main():
                     e = event_pool.pop() if event_pool else torch.cuda.Event(enable_timing=True)
                     e.record()
                     ev[name] = e
-            model.train_step(plans[s % nbt], process_group=pg, mark=mark, fused=not args.unfused, eps=eps_tables,
-                             next_plan=plans[(s + 1) % nbt] if (not multi or model.exchange == "rows") else None)
+            last_ret[0] = model.train_step(plans[s % nbt], process_group=pg, mark=mark, fused=not args.unfused, eps=eps_tables,
+                                           next_plan=plans[(s + 1) % nbt] if (not multi or model.exchange == "rows") else None)
             if args.sync_each_step:
                 torch.cuda.synchronize()
 
-    def measure(setup, mode, steps, warmup, with_events, streamed=False, probe=False, settle=0):
+    def measure(setup, mode, steps, warmup, with_events, streamed=False, probe=False, settle=0, fresh=False):
         """warm-up, then `steps` timed steps bracketed by barrier + synchronize on both sides, MAX over ranks.  With
-        `probe`, three steps are timed first and the candidate is dropped if it projects past --mode-budget-s."""
+        `probe`, three steps are timed first and the candidate is dropped if it projects past --mode-budget-s.  With
+        `fresh`, the model is put back to its initial state and batch 0 after the probe / settling steps, so that the
+        warm-up and the timed steps compute the same values in every run (what --dump-outputs writes)."""
         doing[0] = f"measure {mode} B={setup.B}"
         model.exchange = mode
         plans, uniq = setup.build_plans(mode)
@@ -384,14 +402,15 @@ def main():
             # duration (tools/transient_probe.py: 163 -> 151 us over the first 60-260 steps, again after 0.3 s of
             # idleness, not after a reload of the same values without one).  A commanded region of 20 steps is 4 ms,
             # so it is preceded by untimed settling steps -- real training steps, like the warm-up's -- and the same
-            # region WITHOUT them is timed first and reported beside the headline as `settle.cold_ms_per_step`.
-            kc = min(steps, 20)
-            run(plans, warmup, None, stm)
-            barrier()
-            t0 = time.perf_counter()
-            run(plans, kc, None, stm)
-            barrier()
-            cold = {"steps": kc, "ms_per_step": max_over_ranks(time.perf_counter() - t0) / kc * 1e3}
+            # region WITHOUT them is timed first (--full) and reported beside the headline as `settle.cold_ms_per_step`.
+            if args.full:
+                kc = min(steps, 20)
+                run(plans, warmup, None, stm)
+                barrier()
+                t0 = time.perf_counter()
+                run(plans, kc, None, stm)
+                barrier()
+                cold = {"steps": kc, "ms_per_step": max_over_ranks(time.perf_counter() - t0) / kc * 1e3}
             done, t0 = 0, time.perf_counter()
             while done < settle:
                 run(plans, 50, None, stm)
@@ -399,7 +418,11 @@ def main():
                 torch.cuda.synchronize()
                 if max_over_ranks(time.perf_counter() - t0) >= args.settle_max_s:     # (every rank takes the same decision)
                     break
-            cold["settle_steps"] = done
+            if cold is not None:
+                cold["settle_steps"] = done
+        if fresh:        # (the settling steps are bounded in wall time: how many ran must not change what is computed)
+            reset_state()
+            step_no[0] = 0
         if with_events:
             fill_event_pool(6 * (steps // max(1, args.event_every) + 2))
         run(plans, warmup, None, stm)
@@ -416,8 +439,10 @@ def main():
         if multi:      # what ONE step's exchange carried (the last step's; bytes per rank into the all-reduce)
             xbytes = {"stats": 4 * int(model._exchanged_floats), "grads": 4 * int(model._gflat.numel()),
                       "rows": 4 * int(model._exchanged_floats)}.get(mode)
+        outputs = step_outputs(model, last_ret[0]) if (fresh and args.dump_outputs) else None
         return {"dt": dt, "t_host": t_host, "events": events, "lazy_kind": lazy_kind, "plans": plans, "cold": cold,
-                "U": sum(uniq) / len(uniq), "B": setup.B, "steps": steps, "mode": mode, "exchange_bytes": xbytes}
+                "U": sum(uniq) / len(uniq), "B": setup.B, "steps": steps, "mode": mode, "exchange_bytes": xbytes,
+                "outputs": outputs}
 
     # ------------------------------------------------------------------ what to run
     exchange_note = None
@@ -446,7 +471,7 @@ def main():
 
     # the box's streaming rate (device-to-device copies of 1 GiB) -- measured before the timed regions, it touches
     # nothing of the model
-    copy_gbs = stream_copy_rate(dev)
+    copy_gbs = stream_copy_rate(dev) if args.full else None
     results = {}          # regime -> {mode: measurement}
     head = None           # the headline measurement: first regime, fastest north-star candidate
     for reg, B in regimes:
@@ -458,8 +483,9 @@ def main():
             reset_state()
             try:
                 stream_head = not multi and args.plans == "stream"
-                m = measure(setup, mode, args.steps, args.warmup, with_events=not args.no_events and not stream_head,
-                            streamed=stream_head, probe=multi, settle=args.settle_steps)
+                m = measure(setup, mode, args.steps, args.warmup,
+                            with_events=args.full and not args.no_events and not stream_head,
+                            streamed=stream_head, probe=multi, settle=args.settle_steps, fresh=True)
             except Exception as exc:      # communication-pattern fallback only (never a compute fallback)
                 if len(use) == 1:
                     raise
@@ -475,6 +501,8 @@ def main():
     model.exchange = head["mode"] if multi else model.exchange
     setup, B, U, dt, plans = head["setup"], head["B"], head["U"], head["dt"], head["plans"]
     events, lazy_kind, t_host = head["events"], head["lazy_kind"], head["t_host"]
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, head["outputs"])
     loss = float(model._gflat[model._n_flat].item())
     nan_params = int(torch.isnan(model._flat).sum().item())
 
@@ -498,7 +526,7 @@ def main():
         return {"steps": args.sustained_steps, "ms_per_step": round(m["dt"] / args.sustained_steps * 1e3, 4),
                 "triples_per_s": round(args.sustained_steps * B / m["dt"], 1),
                 "host_enqueue_ms_per_step": round(m["t_host"] / args.sustained_steps * 1e3, 4)}
-    if not multi and args.sustained_steps > 0:
+    if args.full and not multi and args.sustained_steps > 0:
         sustained = aux("sustained", sustained_region)
 
     def streamed_region():
@@ -521,9 +549,9 @@ def main():
                 "note": "every step builds the plan of the batch `prefetch_depth` steps ahead (inverted index + batch normalisers; the look-ahead "
                         "kernel classifies the table rows itself) on a side stream inside the timed region; nothing of a plan is reused; "
                         "plan_build_gpu_us_alone = max(GPU time, host enqueue time) of one build with nothing beside it"}
-    if not multi and args.streamed_steps > 0 and not args.unfused and eps_tables is None:
+    if args.full and not multi and args.streamed_steps > 0 and not args.unfused and eps_tables is None:
         streamed = aux("streamed", streamed_region)
-    if not multi and events is None and not args.no_events:
+    if args.full and not multi and events is None and not args.no_events:
         # (--plans stream: the headline region carries no per-kernel events) per-kernel durations from a resident-plans pass
         m = measure(setup, "single", min(100, args.steps), 4, with_events=True)
         events, lazy_kind = m["events"], m["lazy_kind"]
@@ -531,7 +559,7 @@ def main():
     # ---- per-kernel durations from the HIP events recorded inside the timed region + the roofline object
     args._plans = plans
     kern, roof = kernel_report(events, model, args, world if not forced else 2, B, d, F, U, lazy_kind)
-    if roof is not None:
+    if roof is not None and copy_gbs:
         roof["box_stream_copy_GBs"] = round(copy_gbs, 1)
         roof["frac_of_box_stream_copy"] = round(roof["achieved"] / copy_gbs, 4)
 
@@ -579,12 +607,12 @@ def main():
             roof["bytes_fwd_8d"], roof["bytes_K_8d"] = int(b_fwd), int(b_K)
             roof["target_8d"] = 0.60
         return regions_
-    if not multi and kern and not args.unfused and not args.no_regions:
+    if args.full and not multi and kern and not args.unfused and not args.no_regions:
         regions = aux("regions", regions_region)
 
     # ---- CPU baseline (rank 0, N=1): reference-shaped restatement on the host cores
     cpu = None
-    if rank == 0 and not multi and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not multi and not args.no_cpu_baseline:
         cpu = aux("cpu_baseline", lambda: cpu_baseline(sizes, d, B, nb_train, output, plans[0], setup.occ, args.cpu_seconds))
 
     if rank == 0:
@@ -616,7 +644,7 @@ def main():
             "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
             "host_enqueue_ms_per_step": round(t_host / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": head_reg if multi else "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
+            "data": "synthetic", "full": bool(args.full),
             "config": {"workload": args.workload, "fields": F, "entities": model.T, "d": d,
                        "batch_per_gpu": B, "global_batch": B * world, "nb_train": nb_train,
                        "ids": "int32" if args.id32 else "int64",
@@ -806,6 +834,45 @@ def stream_copy_rate(dev):
     copy_gbs = 10 * 2 * src.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
     del src, dst
     return copy_gbs
+
+
+DUMP_ROW_BYTES = {"entity_params": 24 << 20, "bias_params": 4 << 20, "pred": 4 << 20}    # per array; 64 MB in all at most
+
+
+def _dump_rows(t, limit, seed):
+    """t (rows first) on the host as float32, whole if it fits in `limit` bytes, else a fixed seeded sample of its rows in
+    row order; and the sampled row numbers as float64 (None: whole)."""
+    t = t.detach().float()
+    n = t.shape[0]
+    per_row = 4 * (t[0].numel() if n else 1)
+    if n * per_row <= limit:
+        return t.cpu().numpy(), None
+    import torch
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[: max(1, limit // per_row)].sort().values
+    return t[idx.to(t.device)].cpu().numpy(), idx.double().numpy()
+
+
+def step_outputs(model, ret):
+    """What the last timed step gave its caller: train_step's (loss3 = [loss, nll, kl], pred) and the parameters it
+    updated (read after the timed region's sync_lazy: every row current).  Host copies, taken before anything else runs."""
+    loss3, pred = ret
+    ent, bia, scal = model._views(model._flat)
+    arrays = {"loss": loss3.detach().float().cpu().numpy(), "scalars": scal.detach().float().cpu().numpy()}
+    for seed, (name, t) in enumerate((("entity_params", ent), ("bias_params", bia), ("pred", pred.reshape(-1)))):
+        arrays[name], rows = _dump_rows(t, DUMP_ROW_BYTES[name], seed)
+        if rows is not None:
+            arrays[name + "_rows"] = rows
+    return arrays
+
+
+def write_outputs(out_dir, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"[bench] wrote {len(arrays)} arrays ({total} bytes) to {out_dir}", file=sys.stderr)
 
 
 def cpu_baseline(sizes, d, B, nb_train, output, plan, occ, budget_s):

@@ -1,4 +1,5 @@
 """Helpers to read the golden fixtures written by tools/make_golden.py."""
+import glob
 import os
 
 import numpy as np
@@ -15,12 +16,32 @@ VARIANT_CASES = ["multi_reg_d8_s3", "softplus_reg_d8", "softplus_multi_class_d8_
 PARAM_KEYS = ("alpha", "global_bias_mean", "global_bias_scale", "bias_params", "entity_params")
 
 
+class _Fixture(dict):
+    """The arrays of one fixture (the `files` / item interface of np.load's NpzFile)."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
+def load_fixture(name):
+    """<name>.npz together with its parts <name>.<tag>.npz, if it was written in parts (tools/make_golden.py save_case:
+    a fixture is split where one file would pass the size limit for a committed file)."""
+    z = _Fixture()
+    for path in [os.path.join(GOLDEN, name + ".npz")] + sorted(glob.glob(os.path.join(GOLDEN, name + ".*.npz"))):
+        with np.load(path) as f:
+            for k in f.files:
+                assert k not in z, (path, k)
+                z[k] = f[k]
+    return z
+
+
 class Case:
     """One single-step fixture with dense tables rebuilt (fixtures of big tables
     only store the rows the batch touches)."""
 
     def __init__(self, name):
-        z = np.load(os.path.join(GOLDEN, name + ".npz"))
+        z = load_fixture(name)
         self.z = z
         self.name = name
         self.N, self.M, self.d = int(z["N"]), int(z["M"]), int(z["d"])

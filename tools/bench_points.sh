@@ -17,7 +17,7 @@ run() {  # label, env assignments (may be empty), bench args...
   local label=$1; shift
   local envs=$1; shift
   echo "[points] $label" >&2
-  env $envs python3 $R/bench.py "$@" --no-cpu-baseline 2>> $R/gpurun_out/points_$TAG.err | python3 -c "
+  env $envs python3 $R/bench.py --full "$@" --no-cpu-baseline 2>> ${OUT%.jsonl}.err | python3 -c "
 import json,sys
 j=json.loads(sys.stdin.readline()); j['point']='$label'; print(json.dumps(j))" >> $OUT || echo "{\"point\": \"$label\", \"error\": true}" >> $OUT
 }

@@ -6,6 +6,7 @@ set -o pipefail
 #   tools/final_measure.sh r04 ranks      gloo rehearsals of `bench.py --gpus N` (2 and 5 ranks on the one card) + host probes
 TAG=${1:-r04}; STAGE=${2:-profiles1}
 R=${GRAFT_REPO_ROOT:-/root/repo}
+BENCH_LINE_DIR=${BENCH_LINE_DIR:-$R/bench_out}      # where the points stage writes the default bench line (--full)
 cd $R
 mkdir -p gpurun_out/fin
 case $STAGE in
@@ -20,7 +21,8 @@ profiles2)
   EXTRA_ARGS="--workload criteo_d256 --lazy-adam on" bash tools/profile_round.sh ${TAG}cfg5list > gpurun_out/fin/prof_${TAG}cfg5list.log 2>&1
   ;;
 points)
-  python bench.py > gpurun_out/fin/bench_default.json 2> gpurun_out/fin/bench_default.err
+  mkdir -p "$BENCH_LINE_DIR"
+  python bench.py --full > "$BENCH_LINE_DIR/bench_default.json" 2> "$BENCH_LINE_DIR/bench_default.err"
   bash tools/bench_points.sh $TAG > gpurun_out/fin/points.log 2>&1
   tail -3 gpurun_out/fin/points.log
   ;;

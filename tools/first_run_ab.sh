@@ -7,7 +7,7 @@ OUT=$1; shift
 i=0
 for a in "$@"; do
   i=$((i + 1))
-  python3 $R/bench.py --no-cpu-baseline --sustained-steps 500 --streamed-steps 0 --no-regions $a 2>/dev/null | python3 -c "
+  python3 $R/bench.py --full --no-cpu-baseline --sustained-steps 500 --streamed-steps 0 --no-regions $a 2>/dev/null | python3 -c "
 import json,sys
 j=json.loads(sys.stdin.readline())
 print('run $i [$a]: ms/step', j['ms_per_step'], 'host', j['host_enqueue_ms_per_step'], 'cold', j['settle']['cold_ms_per_step'] if j.get('settle') else None, 'sustained', j['sustained']['ms_per_step'], 'kernels', {k: v['avg_us'] for k, v in (j.get('kernels') or {}).items()})" >> $OUT

@@ -6,7 +6,7 @@ OUT=$1; shift
 for e in "$@"; do
   envs=$e; [ "$e" = "-" ] && envs=""
   for pt in "--user-order --zipf 1.1 --n-batches 160 --steps 320 --warmup 20" "--zipf 1.1 --steps 200 --warmup 20"; do
-    env $envs python3 $R/bench.py $pt --no-regions --no-cpu-baseline --sustained-steps 0 --streamed-steps 0 2>/dev/null | python3 -c "
+    env $envs python3 $R/bench.py --full $pt --no-regions --no-cpu-baseline --sustained-steps 0 --streamed-steps 0 2>/dev/null | python3 -c "
 import json,sys
 j=json.loads(sys.stdin.readline())
 print('[$e] [$pt]: ms/step', j['ms_per_step'], {k: v['avg_us'] for k, v in j['kernels'].items()})" >> $OUT

@@ -16,6 +16,7 @@ Usage:  python tools/make_golden.py [--only name1,name2]     (writes tests/golde
 fixture only on purpose: `--only` limits the run to the named cases)
 """
 import ast
+import glob
 import os
 import sys
 
@@ -132,6 +133,26 @@ def closed_form_case(name, group_sizes, d, B, nb_train, seed):
     print(f"{name}: lifted CF of vfm-tomasrch.py lines {span}, G={G} B={B} loss={float(loss)}")
 
 
+MAX_FIXTURE_BYTES = 1 << 20       # the repository's limit for one committed file
+
+
+def save_case(name, rec):
+    """<name>.npz; a fixture past MAX_FIXTURE_BYTES is written in parts instead: <name>.npz (inputs and parameters) and
+    <name>.<tag>.npz (the expected values of one precision), which tests/golden_util.Case reads back as one."""
+    for f in glob.glob(os.path.join(OUT, name + ".*.npz")):
+        os.remove(f)
+    path = os.path.join(OUT, name + ".npz")
+    np.savez_compressed(path, **rec)
+    if os.path.getsize(path) <= MAX_FIXTURE_BYTES:
+        return
+    tags = sorted({k.split("_", 1)[0] for k in rec if k.startswith(("f32_", "f64_"))})
+    for tag in tags:
+        np.savez_compressed(os.path.join(OUT, f"{name}.{tag}.npz"), **{k: v for k, v in rec.items() if k.startswith(tag + "_")})
+    np.savez_compressed(path, **{k: v for k, v in rec.items() if not k.startswith(tuple(t + "_" for t in tags))})
+    for f in [path] + [os.path.join(OUT, f"{name}.{t}.npz") for t in tags]:
+        assert os.path.getsize(f) <= MAX_FIXTURE_BYTES, f
+
+
 LINKS = {"abs": torch.abs, "softplus": nn.functional.softplus}     # vfm-torch.py:126 / :125
 ONLY = None
 
@@ -245,7 +266,7 @@ def single_case(ns, CF, name, N, M, d, x, y, nb_train, nb_occ, output,
         rec["sparse_rows"] = np.array(1)
     for k, v in p.items():
         rec[f"p_{k}"] = v
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), **rec)
+    save_case(name, rec)
     print(f"{name}: B={len(y)} U={len(rec['uniq'])} loss_f32={rec['f32_loss']}",
           f"loss_f64={rec.get('f64_loss')}")
 
