@@ -1,0 +1,73 @@
+/*
+ * vfm_rank.h -- C ABI of the preference-elicitation kernels of libvfm_hip.so (gfx950): closed-form predictive
+ * moments of the mean-field posterior, and a fused catalog ranking (scores by fp32 MFMA, exclusion lists, top k).
+ *
+ * The caller of the posterior in the reference is select_next_question / predict_proba (vfm.py:1024-1057): it scores
+ * (user, item) pairs by the mean probability or the logit variance over S posterior samples.  These entry points give
+ * the exact S -> infinity limit of those estimates in one pass.
+ *
+ * Conventions: those of vfm_hip.h.  Every pointer is DEVICE memory owned by the caller; launch-only, no host
+ * synchronisation; the caller owns the workspace (vfm_rank_workspace_bytes); 0 on success, a negative VFM_E_* code or a
+ * positive hipError_t otherwise; arguments are checked before any HIP call; vfm_last_error() (vfm_hip.h) describes the
+ * last failure on the calling thread.  Tables as in vfm_hip.h: entity_params [T, 2d] = [mu | s],
+ * bias_params [T, 2] = [mu_w, s_w], scalars [3] = alpha, global_bias_mean, global_bias_scale; sigma = link(s),
+ * link = |.|, or softplus with VFM_FLAG_LINK_SOFTPLUS.
+ *
+ * Closed form (a_f ~ N(m_f, s_f^2) independent per coordinate k):
+ *   E[pred]   = m0 + sum_f mu_w,f + sum_k sum_{f<g} m_f m_g
+ *   Var[pred] = sigma0^2 + sum_f sigma_w,f^2 + sum_k [ sum_{f<g} s_f^2 s_g^2 + sum_f s_f^2 (sum_{g!=f} m_g)^2 ]
+ * For two fields (u, i) the pair term is sum_k (mu_u^2 sigma_i^2 + sigma_u^2 (mu_i^2 + sigma_i^2)).
+ */
+#ifndef VFM_RANK_H
+#define VFM_RANK_H
+
+#include <stdint.h>
+
+#include "vfm_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* scoring strategies (the reference's select_next_question strategies, plus plain top-k) */
+#define VFM_RANK_TOP 0      /* score = E[pred]                                                         */
+#define VFM_RANK_VARIANCE 1 /* score = Var[pred] (the logit variance of predict_proba)                */
+#define VFM_RANK_MEAN 2     /* score = -|E| / sqrt(1 + pi Var / 8): the probit form of -|p_bar - 0.5|  */
+#define VFM_RANK_RANDOM 3   /* score = Philox uniform in [0,1) keyed on (seed, user id, item id)     */
+#define VFM_RANK_MAX_K 128
+#define VFM_RANK_MAX_SPLITS 64
+
+/* Closed-form logit mean and variance of rows x [B, F] (int64 or int32 ids by id_bits), any F <= VFM_MAX_FIELDS.
+ * flags: 0 or VFM_FLAG_LINK_SOFTPLUS.  score: NULL, or [B] written with the ranking score of `strategy` (for
+ * VFM_RANK_RANDOM keyed on (seed, x[r,0], x[r,1]); F == 2 for VFM_RANK_RANDOM).  For F == 2 the three outputs are
+ * bitwise those vfm_rank_items_f32 forms for the same pair.  A row with an id outside [0, T) gets NaN outputs. */
+int vfm_predictive_moments_f32(int64_t B, int32_t F, int32_t d, int64_t T, int32_t id_bits, int32_t flags,
+                               const void* x, const float* entity_params, const float* bias_params,
+                               const float* scalars, int32_t strategy, uint64_t seed, float* logit_mean,
+                               float* logit_var, float* score, void* stream);
+
+/* Workspace of vfm_rank_items_f32, in bytes (n_splits = 0: the automatic split count).  Negative on bad arguments. */
+int64_t vfm_rank_workspace_bytes(int64_t U, int64_t n_cand, int32_t d, int32_t k, int32_t strategy, int32_t n_splits);
+
+/* Top k candidate items of each query user, two-field model (F must be 2).
+ *  users [U] int64 entity ids of the users; candidates: cand [n_cand] int64 entity ids, STRICTLY ASCENDING, or
+ *  cand == NULL for the range [item_lo, item_lo + n_cand).  n_cand < 2^31.
+ *  Exclusion: excl_ptr [U+1] int64 offsets into excl_items [n_excl] (int64 entity ids, ascending per user); both NULL
+ *  (and n_excl 0) for none.  The walk over a user's list advances with the candidates: cost O(list length).
+ *  Order: score descending, then item id ascending; NaN scores are never returned.  Bitwise deterministic and
+ *  independent of n_splits (1 .. VFM_RANK_MAX_SPLITS, 0 = automatic): every pair's score is one k-ordered fp32 fma
+ *  chain (the fp32-input MFMA).
+ *  Outputs [U, k]: out_items (entity ids), out_score, out_mean, out_var (the winners' closed-form moments).  Fewer than
+ *  k candidates: item -1, score -inf, NaN moments.  flags: 0 or VFM_FLAG_LINK_SOFTPLUS. */
+int vfm_rank_items_f32(int64_t U, const int64_t* users, int64_t n_cand, const int64_t* cand, int64_t item_lo,
+                       int64_t T, int32_t F, int32_t d, int32_t k, int32_t strategy, int32_t flags, uint64_t seed,
+                       int32_t n_splits, const int64_t* excl_ptr, const int64_t* excl_items, int64_t n_excl,
+                       const float* entity_params, const float* bias_params, const float* scalars, void* workspace,
+                       int64_t workspace_bytes, int64_t* out_items, float* out_score, float* out_mean,
+                       float* out_var, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* VFM_RANK_H */

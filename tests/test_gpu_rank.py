@@ -1,0 +1,361 @@
+"""GPU: preference elicitation (include/vfm_rank.h) -- the closed-form predictive moments against the fp64 closed form,
+the deterministic forward and the sampled predictive; the fused top-k ranking against an fp64 oracle for every strategy
+(tie-aware), its determinism, padding, exclusion and candidate sets, and at the ML-20M shape against a torch fp32
+composition."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from golden_util import Case, rel_err
+from test_rank_cpu import closed_form
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+
+
+def _model(N, M, d, output="reg", link="abs", seed=0, scale=0.5):
+    from vae_amd.model import VFM
+    torch.manual_seed(seed)
+    m = VFM(N, M, d, output=output, link=link, device=DEV)
+    g = torch.Generator().manual_seed(seed)
+    m.entity_params.weight.data.copy_(torch.randn(m.T, 2 * d, generator=g) * scale)
+    m.bias_params.weight.data.copy_(torch.randn(m.T, 2, generator=g) * scale)
+    m._flat[m._off_scal: m._off_scal + 3] = torch.tensor([0.7, 0.2, 0.3], device=DEV)
+    return m
+
+
+def _tables_np(m):
+    return (m.entity_params.weight.detach().cpu().numpy(), m.bias_params.weight.detach().cpu().numpy(),
+            m._scalars().cpu().numpy())
+
+
+def _link_t(s, link):
+    return s.abs() if link == "abs" else torch.nn.functional.softplus(s)
+
+
+def philox_uniform_np(seed, user, item):
+    """The kernels' Philox4x32-10 uniform keyed on (seed, user id, item id), in numpy."""
+    M32 = np.uint64(0xFFFFFFFF)
+    user, item = np.asarray(user, np.int64).astype(np.uint64), np.asarray(item, np.int64).astype(np.uint64)
+    c0, c1, c2, c3 = item & M32, item >> np.uint64(32), user & M32, user >> np.uint64(32)
+    c0, c1, c2, c3 = np.broadcast_arrays(c0, c1, c2, c3)
+    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF)
+    for _ in range(10):
+        p0 = np.uint64(0xD2511F53) * c0
+        p1 = np.uint64(0xCD9E8D57) * c2
+        n0 = (p1 >> np.uint64(32)) ^ c1 ^ k0
+        n2 = (p0 >> np.uint64(32)) ^ c3 ^ k1
+        c1, c3, c0, c2 = p1 & M32, p0 & M32, n0, n2
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M32, (k1 + np.uint64(0xBB67AE85)) & M32
+    return (c0 >> np.uint64(8)).astype(np.float64) * 2.0 ** -24
+
+
+def oracle(m, users, cand, strategy, seed=0):
+    """fp64 (score, mean, var) [U, C] of every (user, candidate) pair."""
+    d, link = m.d, m.link
+    ent, bia = m.entity_params.weight.detach().double(), m.bias_params.weight.detach().double()
+    scal = m._scalars().double()
+    u, c = torch.as_tensor(users, device=DEV), torch.as_tensor(cand, device=DEV)
+    mu_u, s_u = ent[u, :d], _link_t(ent[u, d:], link)
+    mu_i, s_i = ent[c, :d], _link_t(ent[c, d:], link)
+    mean = scal[1] + bia[u, 0][:, None] + bia[c, 0][None, :] + mu_u @ mu_i.T
+    var = (_link_t(scal[2], link) ** 2 + (_link_t(bia[u, 1], link) ** 2)[:, None] + (_link_t(bia[c, 1], link) ** 2)[None, :]
+           + (mu_u ** 2) @ (s_i ** 2).T + (s_u ** 2) @ (mu_i ** 2 + s_i ** 2).T)
+    mean, var = mean.cpu().numpy(), var.cpu().numpy()
+    if strategy == "top":
+        sc = mean
+    elif strategy == "variance":
+        sc = var
+    elif strategy == "mean":
+        sc = -np.abs(mean) / np.sqrt(1 + math.pi * var / 8)
+    else:
+        sc = philox_uniform_np(seed, np.asarray(users)[:, None], np.asarray(cand)[None, :])
+    return sc, mean, var
+
+
+def check_ranking(out, cand, S, Mo, Vo, excluded, k, tol, tol_mv):
+    """Tie-aware: returned scores match the oracle's, nothing excluded or repeated, every oracle item that beats the
+    returned k-th score by more than `tol` is returned, padding as specified."""
+    items, sc = out["items"].cpu().numpy(), out["score"].cpu().numpy()
+    lm, lv = out["logit_mean"].cpu().numpy(), out["logit_var"].cpu().numpy()
+    cand = np.asarray(cand)
+    for q in range(items.shape[0]):
+        avail = ~excluded[q]
+        n = min(k, int(avail.sum()))
+        valid = items[q] >= 0
+        assert valid.sum() == n and valid[:n].all(), (q, items[q])
+        it = items[q][:n]
+        assert len(set(it.tolist())) == n
+        j = np.searchsorted(cand, it)
+        assert (j < len(cand)).all() and (cand[np.minimum(j, len(cand) - 1)] == it).all()
+        assert not excluded[q, j].any()
+        assert np.all(np.abs(sc[q][:n] - S[q, j]) <= tol), (q, sc[q][:n], S[q, j])
+        assert np.all(np.abs(lm[q][:n] - Mo[q, j]) <= tol_mv[0]) and np.all(np.abs(lv[q][:n] - Vo[q, j]) <= tol_mv[1])
+        assert np.all(np.diff(sc[q][:n]) <= 0)
+        kth = sc[q][n - 1] if n == k else -np.inf
+        must = cand[avail & (S[q] > kth + tol)]
+        assert set(must.tolist()) <= set(it.tolist()), q
+        assert np.all(np.isneginf(sc[q][n:])) and np.isnan(lm[q][n:]).all() and np.isnan(lv[q][n:]).all()
+
+
+# ---------------------------------------------------------------------------------------------------- moments
+@pytest.mark.parametrize("name", ["quirk_reg_d8", "fraction_class_d5", "ml100k_reg_d20", "softplus_reg_d8"])
+@pytest.mark.parametrize("id_dtype", [torch.int64, torch.int32])
+def test_moments_golden_cases(name, id_dtype):
+    from vae_amd.model import VFM
+    from vae_amd import ops
+    c = Case(name)
+    P = c.params()
+    m = VFM(c.N, c.M, c.d, output=c.output, link=c.link, device=DEV)
+    m.entity_params.weight.data.copy_(torch.tensor(P["entity_params"]))
+    m.bias_params.weight.data.copy_(torch.tensor(P["bias_params"]))
+    m._flat[m._off_scal: m._off_scal + 3] = torch.tensor(
+        np.concatenate([P["alpha"], P["global_bias_mean"], P["global_bias_scale"]]), device=DEV)
+    x = torch.tensor(c.x, device=DEV).to(id_dtype)
+    mean, var = m.predictive_moments(x)
+    rm, rv = closed_form(*_tables_np(m), c.x, c.link)
+    assert np.abs(mean.cpu().numpy() - rm).max() <= 2e-6 * np.abs(rm).max()
+    assert np.abs(var.cpu().numpy() - rv).max() <= 2e-6 * np.abs(rv).max()
+    det = m._mean_logits(m.plan(x.to(torch.int64)), m._flat)          # VFM_FLAG_EPS_ZERO forward
+    assert rel_err(mean.cpu().numpy(), det.cpu().numpy()) < 1e-6
+    assert ops.FLAG_EPS_ZERO == 2
+
+
+@pytest.mark.parametrize("F", [2, 3, 8])
+@pytest.mark.parametrize("d", [5, 8, 20, 128])
+@pytest.mark.parametrize("link", ["abs", "softplus"])
+def test_moments_general_fields(F, d, link):
+    from vae_amd.model import VFM
+    sizes = [40 + 7 * f for f in range(F)]
+    torch.manual_seed(F * 100 + d)
+    m = VFM(field_sizes=sizes, embedding_size=d, link=link, device=DEV)
+    with torch.no_grad():
+        m._flat.mul_(0.5)
+    off = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    rng = np.random.default_rng(d)
+    xn = (rng.integers(0, min(sizes), size=(700, F)) + off[None, :]).astype(np.int64)
+    rm, rv = closed_form(*_tables_np(m), xn, link)
+    for dt in (torch.int64, torch.int32):
+        mean, var = m.predictive_moments(torch.tensor(xn, device=DEV).to(dt))
+        assert np.abs(mean.cpu().numpy() - rm).max() <= 2e-6 * np.abs(rm).max()
+        assert np.abs(var.cpu().numpy() - rv).max() <= 2e-6 * np.abs(rv).max()
+
+
+def test_moments_match_sampled_predictive():
+    from scipy.stats import chi2
+    m = _model(60, 80, 8, seed=5)
+    rng = np.random.default_rng(1)
+    x = torch.tensor(np.stack([rng.integers(0, 60, 300), 60 + rng.integers(0, 80, 300)], 1), device=DEV)
+    mean, var = m.predictive_moments(x)
+    S = 4096
+    s = m.predict_samples(x, n_samples=S)
+    mean, var = mean.double().cpu().numpy(), var.double().cpu().numpy()
+    mc_m, mc_v = s["logits_mean"].double().cpu().numpy(), s["logits_var"].double().cpu().numpy()
+    assert np.all(np.abs(mc_m - mean) <= 5 * np.sqrt(var / S))
+    lo, hi = chi2.ppf(0.5e-6, S - 1) / (S - 1), chi2.ppf(1 - 0.5e-6, S - 1) / (S - 1)
+    ratio = mc_v / var
+    assert np.all((ratio > lo) & (ratio < hi)), (ratio.min(), ratio.max(), lo, hi)
+
+
+# ---------------------------------------------------------------------------------------------------- ranking
+def _exclusions(users, cand_all, rng, frac=0.2):
+    rows = []
+    for u in users:
+        pick = cand_all[rng.random(len(cand_all)) < frac]
+        rows += [(u, i) for i in pick]
+    rows += [(int(users.max()) + 1, int(cand_all[0]))]                # a row of a user that is not queried
+    return np.array(rows, np.int64)
+
+
+def _excluded_mask(users, cand, ex):
+    s = set(map(tuple, ex.tolist())) if ex is not None else set()
+    return np.array([[(u, i) in s for i in cand] for u in users], bool)
+
+
+@pytest.mark.parametrize("output", ["reg", "class"])
+@pytest.mark.parametrize("link", ["abs", "softplus"])
+@pytest.mark.parametrize("d", [5, 20, 128])
+def test_rank_items_matches_fp64_oracle(output, link, d):
+    N, M = 2000, 3000
+    m = _model(N, M, d, output=output, link=link, seed=d)
+    rng = np.random.default_rng(d)
+    users = np.sort(rng.choice(N - 1, 48, replace=False)).astype(np.int64)
+    all_items = np.arange(N, N + M, dtype=np.int64)
+    ex = _exclusions(users, all_items, rng)
+    sub = rng.choice(all_items, 700, replace=False)                    # (unsorted: the library sorts)
+    strategies = ["top", "variance", "random"] + (["mean"] if output == "class" else [])
+    for strategy in strategies:
+        S_all, M_all, V_all = oracle(m, users, all_items, strategy, seed=9)
+        scale = np.abs(S_all).max() + 1
+        tol = 0.0 if strategy == "random" else 3e-6 * scale * (1 + d / 16)
+        tol_mv = (3e-6 * (np.abs(M_all).max() + 1) * (1 + d / 16), 3e-6 * (np.abs(V_all).max() + 1) * (1 + d / 16))
+        for items in (None, sub):
+            cand = all_items if items is None else np.sort(sub)
+            cols = cand - N
+            for exclude in (None, ex):
+                excl = _excluded_mask(users, cand, exclude) if exclude is not None else np.zeros((len(users), len(cand)), bool)
+                for k in (1, 10, 128):
+                    out = m.rank_items(torch.tensor(users), k=k, strategy=strategy,
+                                       items=None if items is None else torch.tensor(items),
+                                       exclude=None if exclude is None else torch.tensor(exclude), seed=9)
+                    check_ranking(out, cand, S_all[:, cols], M_all[:, cols], V_all[:, cols], excl, k, tol, tol_mv)
+
+
+def test_rank_mean_strategy_refuses_reg_models_and_bad_arguments():
+    m = _model(50, 60, 8)
+    with pytest.raises(ValueError):
+        m.rank_items([0, 1], strategy="mean")
+    for kw in (dict(k=0), dict(k=129), dict(items=[50, 50]), dict(items=[10]), dict(exclude=torch.tensor([[0, 5]])),
+               dict(strategy="best")):
+        with pytest.raises(ValueError):
+            m.rank_items([0, 1], **kw)
+    with pytest.raises(ValueError):
+        m.rank_items([50])                                             # a user id past N
+    from vae_amd.model import VFM
+    with pytest.raises(ValueError):
+        VFM(field_sizes=[10, 10, 10], embedding_size=4, device=DEV).rank_items([0])
+
+
+def test_rank_is_bitwise_deterministic_across_calls_splits_and_streams():
+    N, M = 3000, 5000
+    for strategy, output in (("top", "reg"), ("variance", "reg"), ("mean", "class"), ("random", "reg")):
+        m = _model(N, M, 20, output=output, seed=3)
+        users = torch.arange(0, 600, 2)
+        rng = np.random.default_rng(0)
+        ex = torch.tensor(_exclusions(users.numpy(), np.arange(N, N + M), rng, 0.05))
+        ref = m.rank_items(users, k=10, strategy=strategy, exclude=ex, seed=4)
+        for n_splits in (0, 1, 7, 64):
+            out = m.rank_items(users, k=10, strategy=strategy, exclude=ex, seed=4, n_splits=n_splits)
+            for key in ref:
+                assert torch.equal(ref[key], out[key]), (strategy, n_splits, key)
+        s = torch.cuda.Stream()
+        with torch.cuda.stream(s):
+            out = m.rank_items(users, k=10, strategy=strategy, exclude=ex, seed=4)
+        s.synchronize()
+        for key in ref:
+            assert torch.equal(ref[key], out[key])
+
+
+def test_rank_scores_are_the_moments_kernel_scores_bitwise():
+    """For two fields the score of a returned pair is the k_moments score of that pair, bit for bit (one fma chain)."""
+    m = _model(500, 900, 20, output="class", seed=8)
+    users = torch.arange(0, 500, 5)
+    for strategy in ("top", "variance", "mean"):
+        out = m.rank_items(users, k=16, strategy=strategy)
+        pairs = torch.stack([users.to(DEV)[:, None].expand(-1, 16).reshape(-1), out["items"].reshape(-1)], 1)
+        mean, var = m.predictive_moments(pairs)
+        assert torch.equal(out["logit_mean"].reshape(-1), mean) and torch.equal(out["logit_var"].reshape(-1), var)
+        want = {"top": mean, "variance": var}.get(strategy)
+        if want is not None:
+            assert torch.equal(out["score"].reshape(-1), want)
+
+
+def test_duplicated_items_tie_to_the_lower_id_and_short_lists_are_padded():
+    N, M = 100, 200
+    m = _model(N, M, 8, seed=1)
+    with torch.no_grad():
+        w = m.entity_params.weight
+        b = m.bias_params.weight
+        w[N + 150] = w[N + 40]
+        b[N + 150] = b[N + 40]
+        w[N + 40, :8] = 3.0                                             # make the pair stand out for user 0
+        w[N + 150] = w[N + 40]
+        w[0, :8] = 3.0
+    out = m.rank_items([0], k=2, strategy="top")
+    assert out["items"][0].tolist() == [N + 40, N + 150]
+    assert out["score"][0, 0] == out["score"][0, 1]
+    out = m.rank_items([0, 3], k=5, items=[N + 7, N + 9], exclude=torch.tensor([[3, N + 9]]))
+    assert out["items"][0, 2:].tolist() == [-1, -1, -1] and out["items"][1].tolist() == [N + 7, -1, -1, -1, -1]
+    assert torch.isneginf(out["score"][1, 1:]).all() and torch.isnan(out["logit_mean"][1, 1:]).all()
+    assert torch.isnan(out["logit_var"][0, 2:]).all() and not torch.isnan(out["logit_var"][0, :2]).any()
+    out = m.rank_items([0], k=3, items=[])
+    assert out["items"][0].tolist() == [-1, -1, -1]
+
+
+@pytest.mark.parametrize("strategy,output", [("variance", "reg"), ("top", "reg"), ("mean", "class"), ("random", "class")])
+def test_select_next_questions_picks_what_rank_items_ranks(strategy, output):
+    N, M, n = 40, 300, 5
+    m = _model(N, M, 12, output=output, seed=2)
+    rng = np.random.default_rng(3)
+    users = np.arange(N)
+    ex = _exclusions(users[:-1], np.arange(N, N + M), rng, 0.3)
+    ex = ex[ex[:, 0] < N]
+    excl = set(map(tuple, ex.tolist()))
+    pool = np.array([(u, i) for u in users for i in range(N, N + M) if (u, i) not in excl], np.int64)
+    pool = pool[rng.permutation(len(pool))]                            # any row order
+    su, rows = m.select_next_questions(torch.tensor(pool), n=n, strategy=strategy, seed=6)
+    assert su.tolist() == users.tolist()
+    picked = torch.tensor(pool, device=DEV)[rows.clamp(min=0)][:, :, 1]
+    out = m.rank_items(torch.tensor(users), k=n, strategy=strategy, exclude=torch.tensor(ex), seed=6)
+    # same scores (one score function), so the same picks up to ties; ties go to the lower row resp. item id
+    from vae_amd.rank import predictive_moments
+    pool_sc = {}
+    _, _, sc = predictive_moments(torch.tensor(pool, device=DEV), *m._views(m._flat), m.link, strategy, 6)
+    for (u, i), s in zip(pool.tolist(), sc.cpu().tolist()):
+        pool_sc[(u, i)] = s
+    for q, u in enumerate(users.tolist()):
+        a = [pool_sc[(u, i)] for i in picked[q].tolist()]
+        assert a == out["score"][q].cpu().tolist(), (u, a, out["score"][q])
+        top = out["score"][q, -1].item()
+        assert {i for i, s in zip(out["items"][q].tolist(), out["score"][q].tolist()) if s > top} <= set(picked[q].tolist())
+
+
+def test_rank_after_lazy_fit_equals_rank_after_sync():
+    from vae_amd.model import VFM
+    from vae_amd.data import synthetic_triples
+
+    def trained():
+        torch.manual_seed(3)
+        m = VFM(900, 1100, 16, device=DEV, rng_seed=11)
+        m.lazy_adam, m.pipeline = True, False
+        X, y = synthetic_triples([900, 1100], 12 * 48, seed=4, device=DEV)
+        m.set_training_data(X, nb_train=X.shape[0])
+        plans = [m.plan(X[i * 48:(i + 1) * 48], y[i * 48:(i + 1) * 48]) for i in range(12)]
+        for s in range(40):
+            m.train_step(plans[s % 12], lr=0.05)
+        return m, X
+    a, X = trained()
+    b, _ = trained()
+    assert a._lazy_dirty and b._lazy_dirty                             # rows are lagging
+    b.sync_lazy()
+    users = torch.arange(0, 900, 3)
+    for strategy in ("top", "variance"):
+        ra = a.rank_items(users, k=10, strategy=strategy, exclude=X)
+        rb = b.rank_items(users, k=10, strategy=strategy, exclude=X)
+        for key in ra:
+            assert torch.equal(ra[key], rb[key])
+    assert not a._lazy_dirty and torch.equal(a._flat, b._flat)
+
+
+@pytest.mark.parametrize("strategy", ["top", "variance"])
+def test_full_size_ml20m_shape_matches_torch_composition(strategy):
+    N, M, d, U, k = 138_493, 26_744, 128, 4096, 10
+    m = _model(N, M, d, seed=20, scale=0.3)
+    g = torch.Generator(device=DEV).manual_seed(1)
+    users = torch.randperm(N, device=DEV, generator=g)[:U].sort().values
+    ex_items = N + torch.randint(0, M, (U, 100), device=DEV, generator=g)
+    ex = torch.stack([users[:, None].expand(-1, 100).reshape(-1), ex_items.reshape(-1)], 1)
+    out = m.rank_items(users, k=k, strategy=strategy, exclude=ex)
+    # torch fp32 composition: two mm + masking + topk
+    ent, bia, scal = m._views(m._flat)
+    mu, sg = ent[:, :d], ent[:, d:].abs()
+    if strategy == "top":
+        S = mu[users] @ mu[N:].T + (scal[1] + bia[users, 0])[:, None] + bia[N:, 0][None, :]
+    else:
+        S = ((mu[users] ** 2) @ (sg[N:] ** 2).T + (sg[users] ** 2) @ (mu[N:] ** 2 + sg[N:] ** 2).T
+             + (scal[2].abs() ** 2 + bia[users, 1] ** 2)[:, None] + (bia[N:, 1] ** 2)[None, :])
+    S[torch.arange(U, device=DEV)[:, None].expand(-1, 100), ex_items - N] = -float("inf")
+    tv, ti = torch.topk(S, k, dim=1)
+    tol = 2e-5 * float(S[torch.isfinite(S)].abs().max())
+    got = out["score"]
+    # every returned pair: not excluded, scored like the composition; the composition's clear winners are returned
+    gathered = S.gather(1, out["items"] - N)
+    assert torch.isfinite(gathered).all()
+    assert (gathered - got).abs().max().item() <= tol
+    assert ((tv - got).abs().max().item()) <= tol                      # same k-th scores up to rounding
+    kth = got[:, -1:]
+    clear = (tv > kth + tol)
+    hit = (ti[:, :, None] + N == out["items"][:, None, :]).any(2)
+    assert bool((hit | ~clear).all())

@@ -50,7 +50,27 @@ _UNITS = [("vfm_abi.hip", "", _EXACT), ("vfm_index.hip", "", []), ("vfm_variants
           ("vfm_bwd.hip", "0_abs", ["-DVFM_LINK=0", "-DVFM_BWD_PART=0"] + _EXACT),
           ("vfm_bwd.hip", "1_abs", ["-DVFM_LINK=0", "-DVFM_BWD_PART=1"] + _EXACT),
           ("vfm_bwd.hip", "0_softplus", ["-DVFM_LINK=1", "-DVFM_BWD_PART=0"] + _EXACT),
-          ("vfm_bwd.hip", "1_softplus", ["-DVFM_LINK=1", "-DVFM_BWD_PART=1"] + _EXACT)]
+          ("vfm_bwd.hip", "1_softplus", ["-DVFM_LINK=1", "-DVFM_BWD_PART=1"] + _EXACT),
+          # preference elicitation (include/vfm_rank.h): kept out of csrc/ so that sources_digest() -- the training
+          # kernels the committed traffic profile was measured on -- does not move with it.  Contraction off: the explicit
+          # fmaf chains of the pair moments are the MFMA chains of the ranking kernel, bit for bit.
+          ("csrc_rank/vfm_rank.hip", "", ["-ffp-contract=off"])]
+RANK_DIR = os.path.join(HERE, "csrc_rank")
+RANK_HDR = os.path.join(ROOT, "include", "vfm_rank.h")
+RANK_OPS = os.path.join(RANK_DIR, "vfm_rank_ops.cpp")
+
+
+def _unit_path(src):
+    """A unit named by a bare file name lives in csrc/, one with a directory part relative to the package."""
+    return os.path.join(HERE, src) if "/" in src else os.path.join(HERE, "csrc", src)
+
+
+def _unit_obj(objdir, src, suffix):
+    return os.path.join(objdir, os.path.splitext(os.path.basename(src))[0] + suffix + ".o")
+
+
+def _rank_sources():
+    return [RANK_HDR] + sorted(os.path.join(RANK_DIR, f) for f in os.listdir(RANK_DIR) if f.endswith((".hip", ".hpp")))
 
 
 def build_hip_library(force=False, verbose=False):
@@ -58,7 +78,7 @@ def build_hip_library(force=False, verbose=False):
     compiled in parallel (hipcc -c) and linked into one shared object."""
     csrc = os.path.join(HERE, "csrc")
     hdr = os.path.join(ROOT, "include", "vfm_hip.h")
-    parts = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))]
+    parts = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hpp", ".hip"))] + _rank_sources()
     out = os.path.join(HERE, "libvfm_hip.so")
     if not force and not _stale(out, [hdr, os.path.abspath(__file__)] + parts):      # (this file holds the compile flags)
         return out
@@ -67,13 +87,13 @@ def build_hip_library(force=False, verbose=False):
     common = [HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-fvisibility-inlines-hidden",
               "-I" + os.path.join(ROOT, "include"), "-I" + csrc]
     jobs, objs = [], []
-    shared = [hdr, os.path.abspath(__file__)] + [f for f in parts if f.endswith(".hpp")]      # what every unit depends on
+    shared = [hdr, RANK_HDR, os.path.abspath(__file__)] + [f for f in parts if f.endswith(".hpp")]      # what every unit depends on
     for src, suffix, extra in _UNITS:
-        obj = os.path.join(objdir, os.path.splitext(src)[0] + suffix + ".o")
+        obj = _unit_obj(objdir, src, suffix)
         objs.append(obj)
-        if not force and not _stale(obj, shared + [os.path.join(csrc, src)]):
+        if not force and not _stale(obj, shared + [_unit_path(src)]):
             continue                      # (a change to one .hip recompiles that unit only)
-        cmd = common + extra + ["-c", os.path.join(csrc, src), "-o", obj]
+        cmd = common + extra + ["-c", _unit_path(src), "-o", obj]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         jobs.append((cmd, subprocess.Popen(cmd)))
@@ -95,13 +115,14 @@ def build_hip_library(force=False, verbose=False):
 
 
 def build_torch_ops(force=False, verbose=False):
-    """libvfm_torch_ops.so: TORCH_LIBRARY shim `torch.ops.vfm_hip.*` over the C ABI (host C++ only)."""
+    """libvfm_torch_ops.so: TORCH_LIBRARY shim `torch.ops.vfm_hip.*` over the C ABI (host C++ only); the ranking ops are a
+    TORCH_LIBRARY_FRAGMENT of their own source (csrc_rank/vfm_rank_ops.cpp) linked into the same shim."""
     import torch
     src = os.path.join(HERE, "csrc", "vfm_torch_ops.cpp")
     hdr = os.path.join(ROOT, "include", "vfm_hip.h")
     out = os.path.join(HERE, "libvfm_torch_ops.so")
     lib = os.path.join(HERE, "libvfm_hip.so")
-    if not force and not _stale(out, [src, hdr, lib]):
+    if not force and not _stale(out, [src, hdr, lib, RANK_OPS, RANK_HDR]):
         return out
     ti = os.path.dirname(torch.__file__)
     rocm = os.environ.get("ROCM_HOME", "/opt/rocm")
@@ -109,7 +130,7 @@ def build_torch_ops(force=False, verbose=False):
            "-D_GLIBCXX_USE_CXX11_ABI=%d" % int(torch._C._GLIBCXX_USE_CXX11_ABI),
            "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ti, "include"),
            "-I" + os.path.join(ti, "include", "torch", "csrc", "api", "include"),
-           "-I" + os.path.join(rocm, "include"), "-o", out, src,
+           "-I" + os.path.join(rocm, "include"), "-o", out, src, RANK_OPS,
            "-L" + os.path.join(ti, "lib"), "-ltorch", "-ltorch_cpu", "-lc10", "-lc10_hip", "-ltorch_hip",
            "-L" + HERE, "-lvfm_hip", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(ti, "lib")]
     if verbose:
@@ -135,7 +156,8 @@ def build_sanitized(force=False, verbose=False):
     outdir = os.path.join(HERE, "build", "san")
     os.makedirs(outdir, exist_ok=True)
     stamp = os.path.join(outdir, "digest.txt")
-    digest = sources_digest()
+    import hashlib
+    digest = sources_digest() + hashlib.sha1(b"".join(open(f, "rb").read() for f in _rank_sources() + [RANK_OPS])).hexdigest()
     out = os.path.join(outdir, "libvfm_hip.so")
     out_ops = os.path.join(outdir, "libvfm_torch_ops.so")
     if (not force and os.path.exists(out) and os.path.exists(out_ops) and os.path.exists(stamp)
@@ -147,8 +169,8 @@ def build_sanitized(force=False, verbose=False):
               "-I" + os.path.join(ROOT, "include"), "-I" + csrc] + san
     jobs, objs = [], []
     for src, suffix, extra in _UNITS:
-        obj = os.path.join(outdir, os.path.splitext(src)[0] + suffix + ".o")
-        cmd = common + extra + ["-c", os.path.join(csrc, src), "-o", obj]
+        obj = _unit_obj(outdir, src, suffix)
+        cmd = common + extra + ["-c", _unit_path(src), "-o", obj]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         jobs.append((cmd, subprocess.Popen(cmd)))
@@ -168,7 +190,7 @@ def build_sanitized(force=False, verbose=False):
            "-D_GLIBCXX_USE_CXX11_ABI=%d" % int(torch._C._GLIBCXX_USE_CXX11_ABI),
            "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ti, "include"),
            "-I" + os.path.join(ti, "include", "torch", "csrc", "api", "include"),
-           "-I" + os.path.join(rocm, "include"), "-o", out_ops, os.path.join(csrc, "vfm_torch_ops.cpp"),
+           "-I" + os.path.join(rocm, "include"), "-o", out_ops, os.path.join(csrc, "vfm_torch_ops.cpp"), RANK_OPS,
            "-L" + os.path.join(ti, "lib"), "-ltorch", "-ltorch_cpu", "-lc10", "-lc10_hip", "-ltorch_hip",
            "-L" + outdir, "-lvfm_hip", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(ti, "lib")]
     if verbose:

@@ -1,0 +1,118 @@
+// vfm_rank_ops.cpp -- torch.ops.vfm_hip.{predictive_moments, rank_items, rank_workspace_bytes}: the TORCH_LIBRARY
+// fragment over include/vfm_rank.h.  Like vfm_torch_ops.cpp it only validates tensors, takes the current HIP stream
+// of the tensors' device and forwards raw pointers; all arithmetic is in the HIP kernels.
+#include <ATen/ATen.h>
+#include <c10/hip/HIPGuard.h>
+#include <c10/hip/HIPStream.h>
+#include <torch/library.h>
+
+#include <string.h>
+
+#include "vfm_rank.h"
+
+namespace {
+
+using at::Tensor;
+using c10::optional;
+
+void check(int rc, const char* what) {
+  TORCH_CHECK(rc == 0, what, " failed (code ", rc, "): ", vfm_last_error());
+}
+
+const Tensor& dev_tensor(const Tensor& t, at::ScalarType dt, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on the GPU (vae_amd has no CPU fallback)");
+  TORCH_CHECK(t.scalar_type() == dt, name, " has the wrong dtype");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  return t;
+}
+
+void* stream_of(const Tensor& t) { return (void*)c10::hip::getCurrentHIPStream(t.get_device()).stream(); }
+
+void tables(const Tensor& entity, const Tensor& bias, const Tensor& scalars) {
+  dev_tensor(entity, at::kFloat, "entity_params"); dev_tensor(bias, at::kFloat, "bias_params");
+  dev_tensor(scalars, at::kFloat, "scalars");
+  TORCH_CHECK(entity.dim() == 2 && bias.dim() == 2 && bias.size(1) == 2 && bias.size(0) == entity.size(0) &&
+              entity.size(1) % 2 == 0 && scalars.numel() >= 3, "table shapes");
+}
+
+void predictive_moments(const Tensor& x, const Tensor& entity, const Tensor& bias, const Tensor& scalars,
+                        Tensor logit_mean, Tensor logit_var, const optional<Tensor>& score, int64_t flags,
+                        int64_t strategy, int64_t seed) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2, "x must be a contiguous [B,F] GPU tensor");
+  TORCH_CHECK(x.scalar_type() == at::kLong || x.scalar_type() == at::kInt, "x must be int64 or int32");
+  tables(entity, bias, scalars);
+  const int64_t B = x.size(0);
+  dev_tensor(logit_mean, at::kFloat, "logit_mean"); dev_tensor(logit_var, at::kFloat, "logit_var");
+  TORCH_CHECK(logit_mean.numel() >= B && logit_var.numel() >= B, "output sizes");
+  float* sp = nullptr;
+  if (score.has_value() && score->defined()) {
+    TORCH_CHECK(dev_tensor(*score, at::kFloat, "score").numel() >= B, "score too small");
+    sp = score->data_ptr<float>();
+  }
+  c10::hip::HIPGuard guard(x.get_device());
+  check(vfm_predictive_moments_f32(B, (int32_t)x.size(1), (int32_t)(entity.size(1) / 2), entity.size(0),
+                                   x.scalar_type() == at::kLong ? 64 : 32, (int32_t)flags, x.data_ptr(),
+                                   entity.data_ptr<float>(), bias.data_ptr<float>(), scalars.data_ptr<float>(),
+                                   (int32_t)strategy, (uint64_t)seed, logit_mean.data_ptr<float>(),
+                                   logit_var.data_ptr<float>(), sp, stream_of(x)),
+        "vfm_predictive_moments_f32");
+}
+
+int64_t rank_workspace_bytes(int64_t U, int64_t n_cand, int64_t d, int64_t k, int64_t strategy, int64_t n_splits) {
+  const int64_t b = vfm_rank_workspace_bytes(U, n_cand, (int32_t)d, (int32_t)k, (int32_t)strategy, (int32_t)n_splits);
+  TORCH_CHECK(b >= 0, "vfm_rank_workspace_bytes: bad arguments");
+  return b;
+}
+
+void rank_items(const Tensor& users, const optional<Tensor>& cand, int64_t n_cand, int64_t item_lo,
+                const optional<Tensor>& excl_ptr, const optional<Tensor>& excl_items, const Tensor& entity,
+                const Tensor& bias, const Tensor& scalars, Tensor workspace, Tensor items, Tensor score,
+                Tensor logit_mean, Tensor logit_var, int64_t F, int64_t k, int64_t strategy, int64_t flags,
+                int64_t seed, int64_t n_splits) {
+  dev_tensor(users, at::kLong, "users");
+  tables(entity, bias, scalars);
+  const int64_t U = users.numel();
+  const int64_t* cp = nullptr;
+  if (cand.has_value() && cand->defined()) {
+    TORCH_CHECK(dev_tensor(*cand, at::kLong, "cand").numel() == n_cand, "cand must hold n_cand ids");
+    cp = cand->data_ptr<int64_t>();
+  }
+  const int64_t *ep = nullptr, *ei = nullptr;
+  int64_t n_excl = 0;
+  if (excl_ptr.has_value() && excl_ptr->defined()) {
+    TORCH_CHECK(dev_tensor(*excl_ptr, at::kLong, "excl_ptr").numel() == U + 1, "excl_ptr needs U + 1 offsets");
+    TORCH_CHECK(excl_items.has_value() && excl_items->defined(), "excl_ptr without excl_items");
+    ep = excl_ptr->data_ptr<int64_t>();
+    n_excl = dev_tensor(*excl_items, at::kLong, "excl_items").numel();
+    ei = n_excl > 0 ? excl_items->data_ptr<int64_t>() : nullptr;
+  }
+  dev_tensor(workspace, at::kByte, "workspace");
+  dev_tensor(items, at::kLong, "items"); dev_tensor(score, at::kFloat, "score");
+  dev_tensor(logit_mean, at::kFloat, "logit_mean"); dev_tensor(logit_var, at::kFloat, "logit_var");
+  TORCH_CHECK(items.numel() >= U * k && score.numel() >= U * k && logit_mean.numel() >= U * k &&
+              logit_var.numel() >= U * k, "output sizes");
+  c10::hip::HIPGuard guard(users.get_device());
+  check(vfm_rank_items_f32(U, users.data_ptr<int64_t>(), n_cand, cp, item_lo, entity.size(0), (int32_t)F,
+                           (int32_t)(entity.size(1) / 2), (int32_t)k, (int32_t)strategy, (int32_t)flags,
+                           (uint64_t)seed, (int32_t)n_splits, ep, ei, n_excl, entity.data_ptr<float>(),
+                           bias.data_ptr<float>(), scalars.data_ptr<float>(), workspace.data_ptr(), workspace.numel(),
+                           items.data_ptr<int64_t>(), score.data_ptr<float>(), logit_mean.data_ptr<float>(),
+                           logit_var.data_ptr<float>(), stream_of(users)),
+        "vfm_rank_items_f32");
+}
+
+}  // namespace
+
+TORCH_LIBRARY_FRAGMENT(vfm_hip, m) {
+  m.def("predictive_moments(Tensor x, Tensor entity_params, Tensor bias_params, Tensor scalars, "
+        "Tensor(a!) logit_mean, Tensor(b!) logit_var, Tensor(c!)? score=None, int flags=0, int strategy=0, "
+        "int seed=0) -> ()",
+        &predictive_moments);
+  m.def("rank_workspace_bytes(int U, int n_cand, int d, int k, int strategy, int n_splits) -> int",
+        &rank_workspace_bytes);
+  m.def("rank_items(Tensor users, Tensor? cand, int n_cand, int item_lo, Tensor? excl_ptr, Tensor? excl_items, "
+        "Tensor entity_params, Tensor bias_params, Tensor scalars, Tensor(a!) workspace, Tensor(b!) items, "
+        "Tensor(c!) score, Tensor(d!) logit_mean, Tensor(e!) logit_var, int F, int k, int strategy, int flags, "
+        "int seed, int n_splits) -> ()",
+        &rank_items);
+}

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _lib, ops
+from . import _lib, ops, rank
 from .dist import shard_rows, allreduce_flat, prior_terms_flag
 
 
@@ -1009,6 +1009,38 @@ class VFM(nn.Module):
         var = m2 / max(n - 1, 1)
         pm = pmean / n
         return {"mean": pm, "var": var if self.output == "reg" else None, "logits_mean": mean, "logits_var": var}
+
+    # ------------------------------------------------------------------ preference elicitation (vae_amd/rank.py)
+    @torch.no_grad()
+    def predictive_moments(self, X):
+        """Closed-form logit mean and variance of the rows X [B, F] under the mean-field posterior: the exact limit of
+        what predict_samples estimates by sampling (include/vfm_rank.h).  Returns (logit_mean [B], logit_var [B])."""
+        self._fresh_params()
+        x = torch.as_tensor(X).to(self.device)
+        if x.dim() != 2 or x.shape[1] != self.F:
+            raise ValueError(f"X must be [B, {self.F}]")
+        ent, bia, scal = self._views(self._flat)
+        m, v, _ = rank.predictive_moments(x, ent, bia, scal, self.link)
+        return m, v
+
+    @torch.no_grad()
+    def rank_items(self, users, k: int = 10, strategy: str = "top", items=None, exclude=None, seed: int = 0,
+                   n_splits: int = 0):
+        """The k best items of each user (two-field model) in one fused kernel.  users: user ids [U] (as in X[:, 0]);
+        items: candidate item entity ids (as in X[:, 1]; default: all M items); exclude: [R, 2] (user, item) rows never
+        returned (e.g. X_train); strategy: "top" (largest logit mean), "variance" (largest logit variance), "mean"
+        ('class' only: probability closest to 0.5, -|mu| / sqrt(1 + pi var / 8)) or "random" (Philox keyed on seed,
+        user, item).  Order: score descending, then item id ascending; bitwise deterministic.  n_splits: item splits
+        of the kernel (0 = automatic; the result does not depend on it).  Returns dict(items [U, k] int64, score,
+        logit_mean, logit_var [U, k]); a user with fewer than k candidates gets item -1, score -inf, NaN moments."""
+        return rank.rank_items(self, users, k, strategy, items, exclude, seed, n_splits)
+
+    @torch.no_grad()
+    def select_next_questions(self, pool, n: int = 1, strategy: str = "variance", seed: int = 0):
+        """The reference's select_next_question (vfm.py:1024-1057) on a pool [P, 2] of (user, item) rows: per user of
+        the pool, the indices of its n best rows under `strategy` (the scores of rank_items).  Returns (users [U'],
+        rows [U', n] int64, -1 padded)."""
+        return rank.select_next_questions(self, pool, n, strategy, seed)
 
     @torch.no_grad()
     def evaluate(self, X_test, y_test):
