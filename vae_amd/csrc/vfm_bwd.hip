@@ -53,10 +53,16 @@ int launch_bwd_t(KArgs& a, const BwdArgs& b, const AdamArgs& ad, hipStream_t st)
     }
   }
   if (b.zrec != nullptr) return fail(VFM_E_UNSUPPORTED, "pipelined step: fused Adam, Philox eps, d % 4 == 0, |.| link only");
+  // VFM_BWD_PREFETCH=1: the fused Philox step fetches each row's index one row ahead (k_bwd<PF>; A/B, tests).  Off by
+  // default: bitwise the same step, but not faster at cfg3
+  const bool pf = env_int("VFM_BWD_PREFETCH", 0) != 0;
   if constexpr (STAGE == STAGE_FULL && ADAM == 1 && EPS == EPS_PHILOX) {
     if (b.last_step != nullptr) {     // look-ahead lazy Adam
       if (a.S > 1) return fail(VFM_E_UNSUPPORTED, "look-ahead lazy Adam: one variational sample");
-      hipLaunchKernelGGL((k_bwd<LPE, CPL, VEC, EPS, ADAM, STAGE, LINK, false, false, true>), dim3((unsigned)nb), dim3(BLOCK), 0, st, a, b, ad);
+      if (pf)
+        hipLaunchKernelGGL((k_bwd<LPE, CPL, VEC, EPS, ADAM, STAGE, LINK, false, false, true, true>), dim3((unsigned)nb), dim3(BLOCK), 0, st, a, b, ad);
+      else
+        hipLaunchKernelGGL((k_bwd<LPE, CPL, VEC, EPS, ADAM, STAGE, LINK, false, false, true>), dim3((unsigned)nb), dim3(BLOCK), 0, st, a, b, ad);
       return 0;
     }
   }
@@ -64,6 +70,12 @@ int launch_bwd_t(KArgs& a, const BwdArgs& b, const AdamArgs& ad, hipStream_t st)
   if constexpr (STAGE == STAGE_FULL) {
     if (a.S > 1) {       // variational samples: the instance with the per-sample walk
       hipLaunchKernelGGL((k_bwd<LPE, CPL, VEC, EPS, ADAM, STAGE, LINK, true>), dim3((unsigned)nb), dim3(BLOCK), 0, st, a, b, ad);
+      return 0;
+    }
+  }
+  if constexpr (STAGE == STAGE_FULL && ADAM == 1 && EPS == EPS_PHILOX) {
+    if (pf) {
+      hipLaunchKernelGGL((k_bwd<LPE, CPL, VEC, EPS, ADAM, STAGE, LINK, false, false, false, true>), dim3((unsigned)nb), dim3(BLOCK), 0, st, a, b, ad);
       return 0;
     }
   }

@@ -61,7 +61,12 @@ __device__ __forceinline__ float replay_one(float p, float m, float r, float2 c,
   return fmaf(-c.x * m, __builtin_amdgcn_rcpf(fmaf(r, c.y, eps)), p);
 }
 
-template <int LPE, int CPL, int VEC, int EPS, int ADAM, int STAGE, int LINK, bool MULTI, bool PIPE = false, bool LA = false>
+// PF (fused dense step, one sample, not pipelined): the index of the NEXT row a lane group visits is fetched one row
+// ahead, under this row's epilogue -- the first two row numbers of its list and (LA) whether it is in the next batch --
+// so that a row's walk starts with the grow / sumz loads: one dependent load less per row.  Same loads, same sums, same
+// order; PF = false is the row-serial form (the default; VFM_BWD_PREFETCH=1 selects PF).
+template <int LPE, int CPL, int VEC, int EPS, int ADAM, int STAGE, int LINK, bool MULTI, bool PIPE = false, bool LA = false,
+          bool PF = false>
 __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const KArgs a, const BwdArgs b, const AdamArgs ad_in) {
   constexpr int GPB = BLOCK / LPE;
   // step-dependent values: from the kernel arguments, or (replayable step, a.dev) from device memory
@@ -73,6 +78,7 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
                   blockIdx.x == 0 && threadIdx.x == 0 && a.row_filter != 3 && a.e_hi == a.T);
   static_assert(!PIPE || (ADAM == 1 && STAGE == STAGE_FULL && !MULTI), "the pipelined step is the fused single-sample one");
   static_assert(!LA || (ADAM == 1 && STAGE == STAGE_FULL && !MULTI), "look-ahead lazy Adam is a form of the fused dense step");
+  static_assert(!PF || (ADAM == 1 && STAGE == STAGE_FULL && !MULTI && !PIPE), "the index prefetch serves the fused single-sample step");
   __shared__ float sh_cs[VFM_MAX_FIELDS];
   __shared__ float sh_cs_next[PIPE ? VFM_MAX_FIELDS : 1];
   __shared__ int64_t sh_hi[VFM_MAX_FIELDS];
@@ -186,8 +192,23 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
   if (listed && li < li_end) e_cur = ent_ok(b.row_ids[li]);
   int2 pq = make_int2(0, 0);
   if (STAGE != STAGE_APPLY && li < li_end) pq = span_ok(make_int2(b.occ_ptr[e_cur], b.occ_ptr[e_cur + 1]));
+  // PF: nr = occ_rows[pq.x], occ_rows[pq.x + 1] and nn = "e_cur is in the next batch" (LA), for the row pq / e_cur describe
+  int2 nr = make_int2(0, 0);
+  bool nn = false;
+  auto fetch_next = [&](bool more) {
+    if constexpr (PF) {
+      if (more) {
+        if (pq.y > pq.x) nr.x = b.occ_rows[pq.x];
+        if (pq.y > pq.x + 1) nr.y = b.occ_rows[pq.x + 1];
+        if constexpr (LA) nn = b.next_occ_ptr[e_cur + 1] != b.next_occ_ptr[e_cur];
+      }
+    }
+  };
+  fetch_next(li < li_end);
   for (; li < li_end; li += stride) {
     const int64_t e = listed ? e_cur : li;
+    const int2 rr = nr;           // PF: this row's first two row numbers
+    const bool in_nb = nn;        // PF + LA: this row is in the next batch
     const int64_t rec = (listed && !b.rec_by_slot) ? e : li;      // where this row's statistics record sits (multi-rank stages)
     int beg = pq.x, end = pq.y;
     const int64_t en = li + stride;
@@ -211,13 +232,17 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
     float* grow_e = (ADAM || STAGE == STAGE_ACC) ? nullptr : b.g_entity + (size_t)e * (2 * (size_t)d);
     const bool touched = (STAGE == STAGE_APPLY) ? gc.y > 0.f : beg != end;
     const float cntf = (STAGE == STAGE_APPLY) ? gc.y : (float)(end - beg);
+    const bool more = en < li_end;         // PF: the lane group has a next row (its index goes out before a `continue`)
     int la_gap = 0;                        // LA: skipped zero-gradient steps this row applies before this step's update
     if constexpr (LA) {
-      if (!touched && b.next_occ_ptr[e + 1] == b.next_occ_ptr[e]) continue;     // in neither batch: the row waits
+      if (!touched && !(PF ? in_nb : b.next_occ_ptr[e + 1] != b.next_occ_ptr[e])) {     // in neither batch: the row waits
+        fetch_next(more);
+        continue;
+      }
       la_gap = (la_step - 1) - b.last_step[e];
     }
     if (ADAM == 2 && !touched) continue;   // opt-in row-sparse Adam: rows not in the batch stay as they are
-    if (ADAM == 1 && STAGE == STAGE_FULL && a.row_filter == 2 && !touched) continue;
+    if (ADAM == 1 && STAGE == STAGE_FULL && a.row_filter == 2 && !touched) { fetch_next(more); continue; }
 
     // loads that do not depend on the index chain
     Chunk<VEC> mu[CPL], s[CPL], ep[CPL], mm[CPL], ms[CPL], vm[CPL], vs[CPL];
@@ -256,7 +281,7 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
     int hslot = -1;
     if (STAGE != STAGE_APPLY && b.n_heavy > 0 && end - beg > VFM_HEAVY_MIN)
       hslot = heavy_slot_of(b.heavy_ids, b.n_heavy, (int)e);
-    if (ADAM == 1 && STAGE == STAGE_FULL && a.row_filter == 4 && hslot >= 0) continue;   // (the heavy-only launch takes it)
+    if (ADAM == 1 && STAGE == STAGE_FULL && a.row_filter == 4 && hslot >= 0) { fetch_next(more); continue; }   // (the heavy-only launch takes it)
     auto walk = [&](const float* __restrict__ sz, const float* __restrict__ hacc, Chunk<VEC>(&A)[CPL], float& gs) {
 #pragma unroll
       for (int i = 0; i < CPL; ++i)
@@ -297,8 +322,8 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
         if constexpr (PIPE) return b.zrec + (size_t)ent_ok(b.occ_other[oo]) * xs + 4;
         return sz + (size_t)r * d;
       };
-      for (; o + 1 < end; o += 2) {       // two occurrences in flight
-        const int r0 = row_ok(b.occ_rows[o]), r1 = row_ok(b.occ_rows[o + 1]);
+      auto pair = [&](int o, int r0, int r1) {      // two occurrences in flight
+        r0 = row_ok(r0); r1 = row_ok(r1);
         const float g0 = b.grow[r0], g1 = b.grow[r1];
         const float* p0 = src(o, r0);
         const float* p1 = src(o + 1, r1);
@@ -313,9 +338,15 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
             for (int t = 0; t < VEC; ++t) A[i].v[t] = fmaf(g1, s1v.v[t], fmaf(g0, s0v.v[t], A[i].v[t]));
           }
         }
+      };
+      int rt = -1;                         // PF: the tail's row number when the list has one entry (prefetched)
+      if constexpr (PF) {
+        if (o + 1 < end) { pair(o, rr.x, rr.y); o += 2; }
+        else if (o < end) rt = rr.x;
       }
+      for (; o + 1 < end; o += 2) pair(o, b.occ_rows[o], b.occ_rows[o + 1]);
       if (o < end) {
-        const int r0 = row_ok(b.occ_rows[o]);
+        const int r0 = row_ok(rt >= 0 ? rt : b.occ_rows[o]);
         const float g0 = b.grow[r0];
         const float* p0 = src(o, r0);
         gs += g0;
@@ -333,6 +364,7 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
     Chunk<VEC> A[CPL];
     float gs;
     walk(b.sumz, b.heavy_acc, A, gs);
+    fetch_next(more);
 
     if constexpr (STAGE == STAGE_ACC) {   // store the statistics (dense: zeros for rows not in this shard)
 #pragma unroll

@@ -64,14 +64,21 @@ __device__ __forceinline__ void normal8b(const RngKey& k, uint32_t e, uint32_t p
 // eps of chunk j (VEC coordinates from j*VEC) for the lane that owns it, plus the bias eps
 template <int VEC>
 __device__ __forceinline__ void eps_of_chunk(const RngKey& k, uint32_t e, int j, float (&ep)[VEC], float& nb) {
-  float n[8];
   if constexpr (VEC == 4) {
+    // the two 26-bit fields of this chunk's half (normal8b's pairs 0, 1 or 2, 3) are picked by parity BEFORE
+    // Box-Muller: two pairs + the nb pair per lane instead of five; the same bits in, the same floats out
     const uint32_t jg = (uint32_t)j + k.chunk_off;      // global chunk (chunk_off is even: same parity)
-    normal8b(k, e, jg >> 1, n, nb);
+    uint32_t o[4];
+    philox4x32_10(jg >> 1, e, k.step_lo, k.step_hi, k.seed_lo, k.seed_hi, o);
     const bool odd = j & 1;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) ep[t] = odd ? n[4 + t] : n[t];
+    const uint32_t f0 = odd ? __builtin_amdgcn_alignbit(o[2], o[1], 20) : o[0];
+    const uint32_t f1 = odd ? __builtin_amdgcn_alignbit(o[3], o[2], 14) : __builtin_amdgcn_alignbit(o[1], o[0], 26);
+    box_muller_bits<16, 10>(f0, ep[0], ep[1]);
+    box_muller_bits<16, 10>(f1, ep[2], ep[3]);
+    float unused;
+    box_muller_bits<16, 8>(o[3] >> 8, nb, unused);
   } else {
+    float n[8];
     normal8b(k, e, (uint32_t)j >> 3, n, nb);
     float v = n[0];
 #pragma unroll
