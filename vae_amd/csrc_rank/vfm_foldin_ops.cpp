@@ -1,0 +1,86 @@
+// vfm_foldin_ops.cpp -- torch.ops.vfm_hip.{foldin, foldin_workspace_bytes}: the TORCH_LIBRARY fragment over
+// include/vfm_foldin.h.  Like vfm_rank_ops.cpp it only validates tensors, takes the current HIP stream of the tensors'
+// device and forwards raw pointers; all arithmetic is in the HIP kernels.
+#include <ATen/ATen.h>
+#include <c10/hip/HIPGuard.h>
+#include <c10/hip/HIPStream.h>
+#include <torch/library.h>
+
+#include <string.h>
+
+#include "vfm_foldin.h"
+
+namespace {
+
+using at::Tensor;
+using c10::optional;
+
+const Tensor& dev_tensor(const Tensor& t, at::ScalarType dt, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on the GPU (vae_amd has no CPU fallback)");
+  TORCH_CHECK(t.scalar_type() == dt, name, " has the wrong dtype");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  return t;
+}
+
+int64_t foldin_workspace_bytes(int64_t n_ops, int64_t d, int64_t objective) {
+  const int64_t b = vfm_foldin_workspace_bytes(n_ops, (int32_t)d, (int32_t)objective);
+  TORCH_CHECK(b >= 0, "vfm_foldin_workspace_bytes: bad arguments");
+  return b;
+}
+
+void foldin(const Tensor& entities, const Tensor& row_ptr, const Tensor& x, const Tensor& y,
+            const optional<Tensor>& op_x, const optional<Tensor>& row_op, Tensor entity, Tensor bias,
+            const Tensor& scalars, const optional<Tensor>& workspace, Tensor loss, const optional<Tensor>& grad,
+            int64_t col, int64_t objective, int64_t likelihood, int64_t flags, int64_t mode, int64_t n_steps,
+            int64_t n_samples, int64_t reset, int64_t lds_rows, double lr, double kl_weight, int64_t seed, int64_t t0) {
+  dev_tensor(entities, at::kLong, "entities"); dev_tensor(row_ptr, at::kLong, "row_ptr");
+  dev_tensor(x, at::kLong, "x"); dev_tensor(y, at::kFloat, "y");
+  dev_tensor(entity, at::kFloat, "entity_params"); dev_tensor(bias, at::kFloat, "bias_params");
+  dev_tensor(scalars, at::kFloat, "scalars"); dev_tensor(loss, at::kFloat, "loss");
+  TORCH_CHECK(entity.dim() == 2 && bias.dim() == 2 && bias.size(1) == 2 && bias.size(0) == entity.size(0) &&
+              entity.size(1) % 2 == 0 && scalars.numel() >= 3, "table shapes");
+  TORCH_CHECK(x.dim() == 2 && y.numel() == x.size(0), "x must be [R, F] with y [R]");
+  const int64_t E = entities.numel();
+  TORCH_CHECK(row_ptr.numel() == E + 1 && loss.numel() >= E, "row_ptr [E + 1], loss [E]");
+  vfm_foldin_t p;
+  memset(&p, 0, sizeof(p));
+  p.E = E; p.R = x.size(0); p.T = entity.size(0); p.F = (int32_t)x.size(1); p.d = (int32_t)(entity.size(1) / 2);
+  p.col = (int32_t)col; p.objective = (int32_t)objective; p.likelihood = (int32_t)likelihood; p.flags = (int32_t)flags;
+  p.mode = (int32_t)mode; p.n_steps = (int32_t)n_steps; p.n_samples = (int32_t)n_samples; p.reset = (int32_t)reset;
+  p.lds_rows = (int32_t)lds_rows; p.lr = (float)lr; p.kl_weight = (float)kl_weight; p.seed = (uint64_t)seed; p.t0 = t0;
+  p.entities = entities.data_ptr<int64_t>(); p.row_ptr = row_ptr.data_ptr<int64_t>();
+  p.x = x.data_ptr<int64_t>(); p.y = y.data_ptr<float>();
+  if (op_x.has_value() && op_x->defined()) {
+    TORCH_CHECK(dev_tensor(*op_x, at::kLong, "op_x").dim() == 2 && op_x->size(1) == x.size(1), "op_x must be [n_ops, F]");
+    TORCH_CHECK(row_op.has_value() && row_op->defined() && dev_tensor(*row_op, at::kLong, "row_op").numel() == p.R,
+                "row_op must hold one operand per row");
+    p.n_ops = op_x->size(0);
+    p.op_x = op_x->data_ptr<int64_t>();
+    p.row_op = row_op->data_ptr<int64_t>();
+  }
+  if (workspace.has_value() && workspace->defined()) {
+    dev_tensor(*workspace, at::kByte, "workspace");
+    p.workspace = workspace->data_ptr();
+    p.workspace_bytes = workspace->numel();
+  }
+  p.entity_params = entity.data_ptr<float>(); p.bias_params = bias.data_ptr<float>();
+  p.scalars = scalars.data_ptr<float>(); p.out_loss = loss.data_ptr<float>();
+  if (grad.has_value() && grad->defined()) {
+    TORCH_CHECK(dev_tensor(*grad, at::kFloat, "grad").numel() >= E * (2 * (int64_t)p.d + 2), "grad must be [E, 2d + 2]");
+    p.out_grad = grad->data_ptr<float>();
+  }
+  c10::hip::HIPGuard guard(x.get_device());
+  const int rc = vfm_foldin_f32(&p, (void*)c10::hip::getCurrentHIPStream(x.get_device()).stream());
+  TORCH_CHECK(rc == 0, "vfm_foldin_f32 failed (code ", rc, "): ", vfm_last_error());
+}
+
+}  // namespace
+
+TORCH_LIBRARY_FRAGMENT(vfm_hip, m) {
+  m.def("foldin_workspace_bytes(int n_ops, int d, int objective) -> int", &foldin_workspace_bytes);
+  m.def("foldin(Tensor entities, Tensor row_ptr, Tensor x, Tensor y, Tensor? op_x, Tensor? row_op, "
+        "Tensor(a!) entity_params, Tensor(b!) bias_params, Tensor scalars, Tensor(c!)? workspace, Tensor(d!) loss, "
+        "Tensor(e!)? grad, int col, int objective, int likelihood, int flags, int mode, int n_steps, int n_samples, "
+        "int reset, int lds_rows, float lr, float kl_weight, int seed, int t0) -> ()",
+        &foldin);
+}

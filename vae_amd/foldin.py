@@ -1,0 +1,128 @@
+"""Fold-in: fit chosen entities' posteriors with the rest of the model frozen (include/vfm_foldin.h).
+
+With every parameter but one entity's variational factors frozen, the mean-field ELBO splits into independent
+per-entity problems ("Fold-in").  This module checks the arguments, sorts the rows by the folded id
+(stable), builds the per-entity row lists and, for the closed form, the distinct frozen-partner tuples; the fit itself
+is one HIP launch (plus the operand prep) through torch.ops.vfm_hip.foldin.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+
+from . import _lib, ops
+from .rank import _seed64
+
+OBJECTIVES = {"sampled": _lib._gen.VFM_OBJ_SAMPLED, "closed_form": _lib._gen.VFM_OBJ_CLOSED_FORM}
+MAX_D = 512
+MAX_SAMPLES = 4
+MODE_FIT, MODE_OBJECTIVE = 0, 1
+
+
+def prior_s(link: str) -> float:
+    """The scale parameter whose sigma = link(s) is 1: 1 for |.|, log(e - 1) for softplus."""
+    return 1.0 if link == "abs" else math.log(math.e - 1.0)
+
+
+def field_range(model, field: int):
+    lo = sum(model.field_sizes[:field])
+    return lo, lo + model.field_sizes[field]
+
+
+def check_args(model, X, y, field, objective, n_samples, n_steps=0, lr=0.0, kl_weight=1.0):
+    """Validate a fold-in call (no GPU needed).  Returns (x [R, F] int64, y [R] fp32, objective name) on the model's
+    device."""
+    if isinstance(field, bool) or not isinstance(field, int) or not 0 <= field < model.F:
+        raise ValueError(f"field must be an int in [0, {model.F})")
+    if objective is None:
+        objective = "closed_form" if model.output == "reg" else "sampled"
+    if objective not in OBJECTIVES:
+        raise ValueError(f"objective must be one of {sorted(OBJECTIVES)}, not {objective!r}")
+    if objective == "closed_form" and model.output != "reg":
+        raise ValueError("the closed-form objective needs a 'reg' model (Gaussian likelihood); use 'sampled'")
+    if not 1 <= int(n_samples) <= MAX_SAMPLES:
+        raise ValueError(f"n_samples must lie in [1, {MAX_SAMPLES}]")
+    if int(n_steps) < 0:
+        raise ValueError("n_steps must be >= 0")
+    if not float(lr) >= 0.0 or not float(kl_weight) >= 0.0:
+        raise ValueError("lr and kl_weight must be >= 0")
+    if model.d > MAX_D:
+        raise ValueError(f"fold-in supports embedding sizes up to {MAX_D}")
+    dev = model.device
+    x = torch.as_tensor(X)
+    if x.dtype.is_floating_point or x.dtype == torch.bool:
+        raise ValueError("X must hold integer ids")
+    x = x.to(dev, torch.int64)
+    if x.dim() != 2 or x.shape[1] != model.F:
+        raise ValueError(f"X must be [R, {model.F}]")
+    y = torch.as_tensor(y).to(dev, torch.float32).reshape(-1)
+    if y.numel() != x.shape[0]:
+        raise ValueError(f"y must hold one value per row of X ({x.shape[0]}), not {y.numel()}")
+    if x.shape[0]:
+        lo, hi = field_range(model, field)
+        f = x[:, field]
+        if int(f.min()) < lo or int(f.max()) >= hi:
+            raise ValueError(f"folded ids (column {field}) must lie in the field's range [{lo}, {hi})")
+        if model.F > 1:
+            p = torch.cat([x[:, :field], x[:, field + 1:]], 1)
+            if int(p.min()) < 0 or int(p.max()) >= model.T:
+                raise ValueError(f"partner ids must lie in [0, {model.T})")
+            if bool(((p >= lo) & (p < hi)).any()):
+                raise ValueError(f"partner columns hold ids of the folded field's range [{lo}, {hi}): they would not be frozen")
+    return x.contiguous(), y.contiguous(), objective
+
+
+def row_lists(x, y, field):
+    """Stable sort of the rows by the folded id: (xs, ys, entities [E] ascending, row_ptr [E + 1], rows [E])."""
+    order = torch.sort(x[:, field], stable=True).indices
+    xs, ys = x[order].contiguous(), y[order].contiguous()
+    ents, counts = torch.unique_consecutive(xs[:, field], return_counts=True)
+    ptr = torch.zeros(ents.numel() + 1, dtype=torch.int64, device=x.device)
+    torch.cumsum(counts, 0, out=ptr[1:])
+    return xs, ys, ents.contiguous(), ptr, counts
+
+
+def partner_tuples(xs, field):
+    """The distinct frozen-partner tuples (the folded column zeroed) and each row's tuple: (op_x [n_ops, F], row_op [R])."""
+    xp = xs.clone()
+    xp[:, field] = 0
+    if xp.shape[1] == 1:
+        return xp[:1].contiguous(), torch.zeros(xp.shape[0], dtype=torch.int64, device=xs.device)
+    if xp.shape[1] == 2:                   # (one partner column: a 1-D unique)
+        pc = xp[:, 1 - field]
+        u, inv = torch.unique(pc, return_inverse=True)
+        op_x = torch.zeros(u.numel(), 2, dtype=torch.int64, device=xs.device)
+        op_x[:, 1 - field] = u
+        return op_x, inv.contiguous()
+    u, inv = torch.unique(xp, dim=0, return_inverse=True)
+    return u.contiguous(), inv.contiguous()
+
+
+def run(model, X, y, field=0, objective=None, n_samples=1, seed=0, kl_weight=1.0, mode=MODE_FIT, n_steps=0, lr=0.0,
+        reset=False, t0=0, lds_rows=-1):
+    """One fold-in launch.  Returns (entities [E], loss [E], rows [E], grad [E, 2d + 2] or None)."""
+    x, y, objective = check_args(model, X, y, field, objective, n_samples, n_steps, lr, kl_weight)
+    ops._need_cuda(model._flat, "the model's parameters")
+    dev, d = model.device, model.d
+    xs, ys, ents, ptr, counts = row_lists(x, y, field)
+    E = ents.numel()
+    loss = torch.empty(E, dtype=torch.float32, device=dev)
+    grad = torch.empty(E, 2 * d + 2, dtype=torch.float32, device=dev) if mode == MODE_OBJECTIVE else None
+    if E == 0:
+        return ents, loss, counts, grad
+    code = OBJECTIVES[objective]
+    o = _lib.ops()
+    op_x = row_op = ws = None
+    if objective == "closed_form":
+        op_x, row_op = partner_tuples(xs, field)
+        ws = torch.empty(max(o.foldin_workspace_bytes(op_x.shape[0], d, code), 1), dtype=torch.uint8, device=dev)
+    model._fresh_params()
+    ent, bia, scal = model._views(model._flat)
+    lik = _lib.LIK_NORMAL if model.output == "reg" else _lib.LIK_BERNOULLI
+    o.foldin(ents, ptr, xs, ys, op_x, row_op, ent, bia, scal, ws, loss, grad, int(field), code, lik,
+             ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, int(mode), int(n_steps), int(n_samples),
+             int(bool(reset)), int(lds_rows), float(lr), float(kl_weight), _seed64(seed), int(t0))
+    if mode == MODE_FIT:
+        model.params_changed()          # (rows written outside the step kernels: derived caches are stale)
+    return ents, loss, counts, grad

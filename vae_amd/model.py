@@ -8,6 +8,7 @@ What maps to what
   loop body   (:351-370)                  -> VFM.train_step(plan)   fwd + bwd + Adam, no autograd
   training loop / eval (:337-422)         -> VFM.fit(...)
   eval block  (:402-417) + save_weights   -> VFM.predict(X)
+  interactive loop refit (vfm.py:1236-1251) -> VFM.fold_in(X, y)   the answering entities only, model frozen
 All arithmetic of forward / backward / Adam runs in libvfm_hip.so; torch provides device memory,
 streams, (optionally) autograd and torch.distributed.
 """
@@ -1041,6 +1042,46 @@ class VFM(nn.Module):
         the pool, the indices of its n best rows under `strategy` (the scores of rank_items).  Returns (users [U'],
         rows [U', n] int64, -1 padded)."""
         return rank.select_next_questions(self, pool, n, strategy, seed)
+
+    # ------------------------------------------------------------------ fold-in (vae_amd/foldin.py)
+    @torch.no_grad()
+    def fold_in(self, X, y, field: int = 0, n_steps: int = 200, lr: float = 0.05, objective: Optional[str] = None,
+                n_samples: int = 1, seed: int = 0, kl_weight: float = 1.0, reset: bool = False):
+        """Fit the posteriors of the entities in X[:, field] with every other parameter frozen: the answer of a new
+        rating or a cold-start user taken into account without retraining (include/vfm_foldin.h).
+
+        Folded entities: the sorted distinct ids of X[:, field], all in that field's id range ([0, N) for field 0 of an
+        (N, M) model; the consecutive range of field_sizes[field]) -- else ValueError.  The other columns are the frozen
+        partners (ids outside the folded field's range); duplicate rows count twice; an empty X does nothing.
+        Objective per entity e:  L_e = sum_{rows of e} E_q[nll(y, pred)] + kl_weight (KL(q(w_e)) + sum_k KL(q(z_e,k))),
+        nll = the model's likelihood (Normal with precision link(alpha), i.e. sigma_y = sqrt(1/|alpha|) under |.|; or
+        Bernoulli with logits).  objective "closed_form" ('reg' only, its default): E[(y - pred)^2] = (y - E pred)^2 +
+        Var pred over all random variables of the row, deterministic.  "sampled" (the default for 'class'): the mean
+        over n_samples (1-4) reparameterised draws of every random variable of the row; draw s of iteration t uses the
+        eps of ops.philox_eps(spec with n_samples=1, seed, step=t * n_samples + s).  Rows are summed in the order of a
+        stable sort of X by the folded id: bitwise deterministic, independent of which other entities are folded.
+        Optimiser: Adam (torch.optim.Adam defaults, constant lr, fresh moments), n_steps updates.  reset=True starts
+        from the prior (mu = 0, sigma = 1) instead of the current rows.
+        Only the folded rows of entity_params / bias_params change: every other row, the scalars, the training Adam
+        state and the save_weights snapshots stay as they are, bit for bit.
+        Returns dict(entities [E] int64, loss [E] fp32 = L_e at the returned parameters (draw key t = n_steps),
+        rows [E] int64)."""
+        from . import foldin
+        ents, loss, rows, _ = foldin.run(self, X, y, field, objective, n_samples, seed, kl_weight,
+                                         mode=foldin.MODE_FIT, n_steps=n_steps, lr=lr, reset=reset)
+        return {"entities": ents, "loss": loss, "rows": rows}
+
+    @torch.no_grad()
+    def fold_in_objective(self, X, y, field: int = 0, objective: Optional[str] = None, n_samples: int = 1,
+                          seed: int = 0, step: int = 0, kl_weight: float = 1.0):
+        """fold_in's objective L_e and its gradient at the current parameters, nothing updated (tests, diagnostics).
+        step: the draw key t of the sampled objective.  Returns (loss [E], grads) with grads = dict(entities [E],
+        entity [E, 2d] = dL/d[mu | s], bias [E, 2] = dL/d[mu_w, s_w])."""
+        from . import foldin
+        ents, loss, _, g = foldin.run(self, X, y, field, objective, n_samples, seed, kl_weight,
+                                      mode=foldin.MODE_OBJECTIVE, t0=int(step))
+        d = self.d
+        return loss, {"entities": ents, "entity": g[:, :2 * d], "bias": g[:, 2 * d:]}
 
     @torch.no_grad()
     def evaluate(self, X_test, y_test):
