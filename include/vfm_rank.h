@@ -66,6 +66,33 @@ int vfm_rank_items_f32(int64_t U, const int64_t* users, int64_t n_cand, const in
                        int64_t workspace_bytes, int64_t* out_items, float* out_score, float* out_mean,
                        float* out_var, void* stream);
 
+/* Workspace of vfm_rank_heldout_f32, in bytes (n_splits = 0: the automatic split count): the packed operands of
+ * vfm_rank_items_f32 plus O(n_splits (U + n_pos)), never O(U n_cand).  Negative on bad arguments. */
+int64_t vfm_rank_eval_workspace_bytes(int64_t U, int64_t n_cand, int64_t n_pos, int32_t d, int32_t strategy,
+                                      int32_t n_splits);
+
+/* Held-out ranking evaluation, two-field model (F must be 2): where each user's held-out positives land in the user's
+ * full ranking of the candidates, in the order of vfm_rank_items_f32 (c beats i: score_c > score_i, or equal scores and
+ * id_c < id_i; the scores bitwise those of vfm_predictive_moments_f32 for the strategy).
+ *  users, cand / item_lo, n_cand, exclusions, strategy, seed, n_splits, flags: as vfm_rank_items_f32.  The eligible
+ *  candidates of user u, E_u: the candidates not excluded for u.
+ *  Positives: pos_ptr [U+1] int64 offsets into pos_items [n_pos] (int64 entity ids, STRICTLY ASCENDING per user); P_u
+ *  the positives of u.  Every positive should lie in E_u (the caller checks: the Python layer raises otherwise).
+ *  Outputs, int64: per positive p of u (aligned with pos_items) out_rank[p] = #{c in E_u : c beats p} (p's 0-based
+ *  position in u's ranking), out_rank_neg[p] = #{c in E_u \ P_u : c beats p}; per user out_n_eligible[u] = |E_u|,
+ *  out_n_neg[u] = |E_u \ P_u|.  Integer counts: bitwise deterministic and independent of n_splits, the grid and the
+ *  stream.  A positive with rank < k is item [rank] of vfm_rank_items_f32's list for k; one with rank >= k is not in it.
+ *  Scores are assumed finite (a NaN score -- non-finite parameters -- compares false with everything).  Cost: the
+ *  ranking's score tiles and scan, a positive compare per candidate, a binary search over P_u for the candidates that
+ *  beat u's last positive; O(|P_u|^2) to sort P_u. */
+int vfm_rank_heldout_f32(int64_t U, const int64_t* users, int64_t n_cand, const int64_t* cand, int64_t item_lo,
+                         int64_t T, int32_t F, int32_t d, int32_t strategy, int32_t flags, uint64_t seed,
+                         int32_t n_splits, const int64_t* excl_ptr, const int64_t* excl_items, int64_t n_excl,
+                         const int64_t* pos_ptr, const int64_t* pos_items, int64_t n_pos,
+                         const float* entity_params, const float* bias_params, const float* scalars, void* workspace,
+                         int64_t workspace_bytes, int64_t* out_rank, int64_t* out_rank_neg, int64_t* out_n_eligible,
+                         int64_t* out_n_neg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1043,6 +1043,49 @@ class VFM(nn.Module):
         rows [U', n] int64, -1 padded)."""
         return rank.select_next_questions(self, pool, n, strategy, seed)
 
+    @torch.no_grad()
+    def rank_heldout(self, pos, exclude=None, items=None, strategy: str = "top", seed: int = 0, n_splits: int = 0):
+        """Where held-out positives land in their users' full rankings (two-field model; include/vfm_rank.h).
+        pos: [P, 2] (user, item) rows, duplicates dropped; items, exclude, strategy, seed, n_splits: as rank_items.  The
+        eligible candidates E_u of user u are the candidates not excluded for u; every positive must lie in E_u (else
+        ValueError, e.g. a test item that is also in the training exclusions).  "c beats i" is rank_items' order: larger
+        score, or equal scores and the lower item id.
+        Returns dict(users [U] ascending (the users of pos), ptr [U+1], items [n] (the positives, ascending per user),
+        user_index [n], rank [n] = #{c in E_u : c beats i} (i's 0-based position in u's ranking: item [rank] of
+        rank_items(u, k) whenever rank < k), rank_neg [n] = #{c in E_u \\ Pos_u : c beats i}, n_eligible [U] = |E_u|,
+        n_neg [U] = |E_u \\ Pos_u|), all int64 and bitwise deterministic (independent of n_splits)."""
+        return rank.rank_heldout(self, pos, exclude, items, strategy, seed, n_splits)
+
+    @torch.no_grad()
+    def evaluate_ranking(self, X_test, y_test, ks=(10,), exclude=None, items=None, threshold: Optional[float] = None,
+                         per_user: bool = False):
+        """Held-out top-k ranking metrics over the full catalog (two-field model): each user's relevant test items
+        are ranked against every eligible candidate (the candidates `items`, default all M, minus the user's rows of
+        `exclude`, e.g. X_train) by the logit mean, in rank_items' order.  Relevant: y >= threshold for 'reg' (default
+        4.0, the reference's binarisation), y == 1 for 'class'; the other test rows are ordinary negatives.
+        Metrics (vae_amd.rank.ranking_metrics): hit@k, precision@k, recall@k, ndcg@k for each k of ks, mrr, and auc =
+        the fraction of (relevant, eligible negative) pairs ranked right -- ties broken by item id, never counted 1/2.
+        Returns {metric: mean over users with a relevant item (auc: and a negative)}, plus "n_users"; with per_user=True
+        also "per_user": {"users": [U], metric: [U] float64}."""
+        if self.F != 2:
+            raise ValueError("evaluate_ranking ranks (user, item) pairs: two-field models only")
+        ks = [int(k) for k in ks]
+        if not ks or any(k <= 0 for k in ks):
+            raise ValueError("ks must be a non-empty list of positive ints")
+        X = torch.as_tensor(X_test).to(self.device, torch.int64)
+        y = torch.as_tensor(y_test).to(self.device).reshape(-1)
+        if X.dim() != 2 or X.shape[1] != 2 or X.shape[0] != y.numel():
+            raise ValueError("X_test must be [B, 2] with one y_test value per row")
+        if self.output == "reg":
+            relevant = y >= (4.0 if threshold is None else float(threshold))
+        else:
+            relevant = y == 1
+        r = rank.rank_heldout(self, X[relevant], exclude, items, "top")
+        means, per = rank.ranking_metrics(r["rank"], r["rank_neg"], r["ptr"], r["n_neg"], ks)
+        if per_user:
+            means["per_user"] = dict(users=r["users"], **per)
+        return means
+
     # ------------------------------------------------------------------ fold-in (vae_amd/foldin.py)
     @torch.no_grad()
     def fold_in(self, X, y, field: int = 0, n_steps: int = 200, lr: float = 0.05, objective: Optional[str] = None,

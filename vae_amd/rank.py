@@ -150,3 +150,135 @@ def select_next_questions(model, pool, n: int = 1, strategy: str = "variance", s
     rows = torch.full((users.numel(), n), -1, dtype=torch.int64, device=dev)
     rows[grp[keep], rank[keep]] = order[keep]
     return users, rows
+
+
+def _candidates(model, items):
+    """(cand sorted int64 or None, n_cand) of rank_items' `items` argument."""
+    N, M, T = model.N, model.M, model.T
+    if items is None:
+        return None, M
+    cand = torch.as_tensor(items).to(model.device, torch.int64).reshape(-1)
+    if cand.numel() and (int(cand.min()) < N or int(cand.max()) >= T):
+        raise ValueError(f"item ids must lie in [{N}, {T})")
+    cand = torch.sort(cand).values
+    if cand.numel() > 1 and bool((cand[1:] == cand[:-1]).any()):
+        raise ValueError("duplicate candidate items")
+    return cand, cand.numel()
+
+
+def _pair_rows(x, name, N, T, dev):
+    x = torch.as_tensor(x).to(dev, torch.int64)
+    if x.dim() != 2 or x.shape[1] != 2:
+        raise ValueError(f"{name} must be an [R, 2] tensor of (user, item) rows")
+    if x.numel() and (int(x[:, 0].min()) < 0 or int(x[:, 0].max()) >= N or int(x[:, 1].min()) < N
+                      or int(x[:, 1].max()) >= T):
+        raise ValueError(f"{name} holds ids outside the user / item ranges")
+    return x
+
+
+def rank_heldout(model, pos, exclude=None, items=None, strategy: str = "top", seed: int = 0, n_splits: int = 0):
+    """Exact full-catalog positions of held-out positives (model.rank_heldout documents the arguments and outputs)."""
+    ops._need_cuda(model._flat, "the model's parameters")
+    code = strategy_code(strategy)
+    if model.F != 2:
+        raise ValueError("rank_heldout ranks (user, item) pairs: two-field models only")
+    if strategy == "mean" and model.output != "class":
+        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
+    if not 0 <= int(n_splits) <= MAX_SPLITS:
+        raise ValueError(f"n_splits must lie in [0, {MAX_SPLITS}]")
+    dev = model.device
+    N, T = model.N, model.T
+    pos = _pair_rows(pos, "pos", N, T, dev)
+    users = torch.unique(pos[:, 0])                          # sorted: every user with a positive
+    pptr, pitems = exclusion_csr(users, pos, T)              # (ascending per user, duplicates dropped)
+    cand, n_cand = _candidates(model, items)
+    U = users.numel()
+    counts = pptr[1:] - pptr[:-1]
+    puser = torch.repeat_interleave(torch.arange(U, device=dev), counts)
+    # eligibility (torch, on the device): every positive is a candidate and not excluded
+    bad = torch.zeros(pitems.numel(), dtype=torch.bool, device=dev)
+    if cand is not None:
+        j = torch.searchsorted(cand, pitems).clamp_(max=max(n_cand - 1, 0))
+        bad |= (cand[j] != pitems) if n_cand > 0 else torch.ones_like(bad)
+    eptr = ex_items = None
+    if exclude is not None:
+        ex = _pair_rows(exclude, "exclude", N, T, dev)
+        eptr, ex_items = exclusion_csr(users, ex, T)
+        ekey = torch.repeat_interleave(torch.arange(U, device=dev), eptr[1:] - eptr[:-1]) * T + ex_items   # sorted
+        pkey = puser * T + pitems
+        if ekey.numel():
+            j = torch.searchsorted(ekey, pkey).clamp_(max=ekey.numel() - 1)
+            bad |= ekey[j] == pkey
+    if bool(bad.any()):
+        q = int(torch.nonzero(bad)[0, 0])
+        raise ValueError(f"positive (user {int(users[puser[q]])}, item {int(pitems[q])}) is not an eligible candidate "
+                         "(excluded, or outside `items`)")
+    model._fresh_params()
+    ent, bia, scal = model._views(model._flat)
+    n_pos = pitems.numel()
+    i64 = dict(dtype=torch.int64, device=dev)
+    out = {"users": users, "ptr": pptr, "items": pitems, "user_index": puser, "rank": torch.empty(n_pos, **i64),
+           "rank_neg": torch.empty(n_pos, **i64), "n_eligible": torch.empty(U, **i64), "n_neg": torch.empty(U, **i64)}
+    o = _lib.ops()
+    ws = torch.empty(max(o.rank_eval_workspace_bytes(U, n_cand, n_pos, model.d, code, int(n_splits)), 1),
+                     dtype=torch.uint8, device=dev)
+    o.rank_heldout(users, cand, n_cand, N, eptr, ex_items, pptr, pitems, ent, bia, scal, ws, out["rank"],
+                   out["rank_neg"], out["n_eligible"], out["n_neg"], 2, code,
+                   ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, _seed64(seed), int(n_splits))
+    return out
+
+
+def ranking_metrics(rank, rank_neg, ptr, n_neg, ks=(10,)):
+    """Per-user top-k metrics from exact ranks (pure torch, any device).
+
+    rank, rank_neg [P]: per positive, the number of eligible candidates resp. eligible negatives ranked above it (ties
+    broken by item id, as rank_items orders them -- never counted 1/2); ptr [U+1]: the positives of user u are
+    [ptr[u], ptr[u+1]); n_neg [U]: the user's eligible negatives.  Per user with at least one positive, for each k:
+    hit@k (any positive in the top k), precision@k = hits / k, recall@k = hits / |Pos|,
+    ndcg@k = sum_{rank < k} 1 / log2(rank + 2) / sum_{j < min(k, |Pos|)} 1 / log2(j + 2); and mrr = 1 / (1 + best rank),
+    auc = 1 - mean_p rank_neg_p / n_neg (the fraction of (positive, negative) pairs ordered right; NaN if n_neg == 0).
+    Returns (means, per_user): means = {metric: float}, the mean over users with a positive (auc: and a negative), plus
+    "n_users"; per_user = {metric: [U] float64, NaN where the metric is undefined}."""
+    ks = [int(k) for k in ks]
+    if not ks or any(k <= 0 for k in ks):
+        raise ValueError("ks must be a non-empty list of positive ints")
+    rank = torch.as_tensor(rank).to(torch.int64).reshape(-1)
+    dev = rank.device
+    rank_neg = torch.as_tensor(rank_neg, device=dev).to(torch.int64).reshape(-1)
+    ptr = torch.as_tensor(ptr, device=dev).to(torch.int64).reshape(-1)
+    n_neg = torch.as_tensor(n_neg, device=dev).to(torch.int64).reshape(-1)
+    U = ptr.numel() - 1
+    counts = ptr[1:] - ptr[:-1]
+    seg = torch.repeat_interleave(torch.arange(U, device=dev), counts)
+    f64 = dict(dtype=torch.float64, device=dev)
+    has = counts > 0
+    nan = torch.full((U,), float("nan"), **f64)
+    npos = counts.to(torch.float64)
+
+    def seg_sum(v):
+        return torch.zeros(U, **f64).index_add_(0, seg, v.to(torch.float64))
+
+    per = {}
+    disc = 1.0 / torch.log2(rank.to(torch.float64) + 2.0)
+    kmax = max(ks)
+    ideal = torch.cumsum(1.0 / torch.log2(torch.arange(kmax, **f64) + 2.0), 0)        # ideal[j] = sum_{i <= j}
+    for k in ks:
+        inside = rank < k
+        hits = torch.zeros(U, dtype=torch.int64, device=dev).index_add_(0, seg, inside.to(torch.int64)).to(torch.float64)
+        dcg = seg_sum(torch.where(inside, disc, torch.zeros_like(disc)))
+        idcg = ideal[(torch.clamp(counts, max=k) - 1).clamp(min=0)]
+        per[f"hit@{k}"] = torch.where(has, (hits > 0).to(torch.float64), nan)
+        per[f"precision@{k}"] = torch.where(has, hits / k, nan)
+        per[f"recall@{k}"] = torch.where(has, hits / npos.clamp(min=1), nan)
+        per[f"ndcg@{k}"] = torch.where(has, dcg / idcg, nan)
+    best = torch.full((U,), torch.iinfo(torch.int64).max, dtype=torch.int64, device=dev)
+    best = best.scatter_reduce(0, seg, rank, reduce="amin")
+    per["mrr"] = torch.where(has, 1.0 / (1.0 + best.to(torch.float64)), nan)
+    frac = seg_sum(rank_neg) / npos.clamp(min=1)
+    per["auc"] = torch.where(has & (n_neg > 0), 1.0 - frac / n_neg.to(torch.float64).clamp(min=1), nan)
+    means = {}
+    for key, v in per.items():
+        ok = ~torch.isnan(v)
+        means[key] = float(v[ok].mean()) if bool(ok.any()) else float("nan")
+    means["n_users"] = int(has.sum())
+    return means, per
