@@ -94,7 +94,9 @@ def test_objective_and_gradient_match_fp64_autograd(objective, output, link, siz
     assert rel_err(grads["bias"].cpu().numpy(), gb) <= 1e-5
 
 
-@pytest.mark.parametrize("objective,output,link,sizes,field,d,S", [CASES[1], CASES[4], CASES[6]])
+# d = 512: k_foldin <64, 8> (vfm_foldin.hip shape_of), LDS cap 5 rows per entity
+@pytest.mark.parametrize("objective,output,link,sizes,field,d,S", [CASES[1], CASES[4], CASES[6],
+                                                                   ("closed_form", "reg", "abs", (20, 30, 25), 2, 512, 1)])
 def test_trajectory_matches_fp64_adam(objective, output, link, sizes, field, d, S):
     m = _model(sizes, d, output, link, seed=3)
     X, y = _rows(m, field, 5, 40, seed=9, output=output)

@@ -51,8 +51,10 @@ def test_records_and_record_forward_match_the_tables():
     assert rel_err(zrec[ids, 0].cpu().numpy(), w_want.cpu().numpy()) < 1e-6
 
 
+# d = 300 / 512: k_bwd <64, 2, 4> with 75 of 128 chunks filled / full (vfm_abi.hip pick_shape); k_fwd2 <64, false / true>
 @pytest.mark.parametrize("cfg", [dict(), dict(d=128, sizes=(2000, 300), B=1500), dict(zipf=1.3, B=3000, sizes=(400, 60)),
-                                 dict(output="class", link="softplus", d=20)])
+                                 dict(output="class", link="softplus", d=20), dict(d=300, sizes=(2000, 300), B=900, nb=5),
+                                 dict(d=512, sizes=(2000, 300), B=900, nb=5)])
 def test_pipelined_trajectory_equals_plain(cfg):
     """40 steps: pipelined (next batch named, records written by the backward) vs plain fused steps.  Every step's
     loss, the final parameters and moments agree to fp32 summation-order accuracy; heavy lists (zipf) included."""
@@ -141,8 +143,10 @@ def test_auto_pipelines_a_small_part_of_the_table_only_in_the_look_ahead_form():
             assert (m._lazy_kind == "la") == (lookahead and not covers), (covers, lookahead, m._lazy_kind)
 
 
+# d = 300 / 512: k_bwd <64, 2, 4> with 75 of 128 chunks filled / full (vfm_abi.hip pick_shape)
 @pytest.mark.parametrize("cfg", [dict(sizes=(3000, 1200), B=300, nb=8), dict(d=128, sizes=(2000, 300), B=900, nb=5),
-                                 dict(zipf=1.3, B=2000, sizes=(4000, 600), nb=6)])
+                                 dict(zipf=1.3, B=2000, sizes=(4000, 600), nb=6), dict(d=300, sizes=(2000, 300), B=900, nb=5),
+                                 dict(d=512, sizes=(2000, 300), B=900, nb=5)])
 def test_pipelined_look_ahead_form_is_bitwise_the_pipelined_dense_form(cfg):
     """k_bwd<PIPE, LA>: the pipelined step visiting only the rows of this batch and of the next one (a skipped row replays
     its zero-gradient updates when it is next visited, or at the period's end) against the pipelined step that updates

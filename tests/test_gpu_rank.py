@@ -238,9 +238,9 @@ def test_rank_is_bitwise_deterministic_across_calls_splits_and_streams():
             assert torch.equal(ref[key], out[key])
 
 
-def test_rank_scores_are_the_moments_kernel_scores_bitwise():
+def test_rank_scores_are_the_moments_kernel_scores_bitwise(d=20):
     """For two fields the score of a returned pair is the k_moments score of that pair, bit for bit (one fma chain)."""
-    m = _model(500, 900, 20, output="class", seed=8)
+    m = _model(500, 900, d, output="class", seed=8)
     users = torch.arange(0, 500, 5)
     for strategy in ("top", "variance", "mean"):
         out = m.rank_items(users, k=16, strategy=strategy)
@@ -250,6 +250,12 @@ def test_rank_scores_are_the_moments_kernel_scores_bitwise():
         want = {"top": mean, "variance": var}.get(strategy)
         if want is not None:
             assert torch.equal(out["score"].reshape(-1), want)
+
+
+# d -> padded depths (KA, KB) of vfm_rank_tile.hpp: 1:(16,16) 17:(32,48) 1024:(1024,2048) (above: 20:(32,48))
+@pytest.mark.parametrize("d", [1, 17, 1024])
+def test_rank_scores_are_the_moments_kernel_scores_bitwise_at_padded_depths(d):
+    test_rank_scores_are_the_moments_kernel_scores_bitwise(d)
 
 
 def test_duplicated_items_tie_to_the_lower_id_and_short_lists_are_padded():

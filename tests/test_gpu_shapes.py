@@ -171,7 +171,8 @@ def test_large_batch_properties():
     assert torch.allclose(p1, st.pred, rtol=1e-5, atol=1e-4)                    # predict mode == train mode pred
 
 
-@pytest.mark.parametrize("d", [16, 128])
+# d -> k_heavy / k_bwd (LPE, CPL, VEC): 16:(4,1,4) 128:(32,1,4) 300:(64,2,4) 75/128 chunks 1024:(64,4,4)
+@pytest.mark.parametrize("d", [16, 128, 300, 1024])
 def test_skewed_batch_heavy_lists(d):
     """A few entities own most of the rows (lists far longer than VFM_HEAVY_LIST): the pre-reduced
     heavy path must give the oracle's gradients, through all three backward entry points."""
