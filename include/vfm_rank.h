@@ -93,6 +93,51 @@ int vfm_rank_heldout_f32(int64_t U, const int64_t* users, int64_t n_cand, const 
                          int64_t workspace_bytes, int64_t* out_rank, int64_t* out_rank_neg, int64_t* out_n_eligible,
                          int64_t* out_n_neg, void* stream);
 
+/* ---- One field's catalog ranked for models with any number of fields (the field form) --------------------------------
+ * A query is a context: one entity of every field but `field`; c is a candidate entity of `field`.  With S the sum of
+ * the context's embeddings and P their pair term, per coordinate k (sums over the context columns q):
+ *   M = E S,  A = Var S = sum_q sigma_q^2,  C = 2 Cov(S, P) = 2 sum_q sigma_q^2 (M - mu_q),
+ *   c_mean = m0 + sum_q mu_w,q + sum_k E P,  c_var = sigma0^2 + sum_q sigma_w,q^2 + sum_k Var P
+ *   E pred   = c_mean + mu_w,c + sum_k mu_c M
+ *   Var pred = c_var + sigma_w,c^2 + sum_k [ mu_c^2 A + sigma_c^2 (A + M^2) + mu_c C ]
+ * (the closed form above with the context's part separated; Var P is its context-only part).  Over a catalog these are
+ * two GEMMs: query [M] . candidate [mu] (K = d), query [A | A + M^2 | C] . candidate [mu^2 | sigma^2 | mu] (K = 3d).
+ *
+ * Rounding, the bitwise definition of a field-form score: M, A, A + M^2, C per coordinate and c_mean, c_var are formed
+ * in fp64 -- sums over the context columns in column order, then for the two constants over the coordinates in k order --
+ * and each rounded to fp32 once; the two dot products are fp32 fma chains in k order (the variance chain over
+ * [mu^2 | sigma^2 | mu] in that order); mean = (chain + c_mean) + mu_w,c, var = (chain + c_var) + sigma_w,c^2. */
+
+/* Field-form moments of rows x [B, F] (int64 or int32 ids by id_bits): column `field` is the candidate, the other
+ * columns its context; 2 <= F <= VFM_MAX_FIELDS.  score: NULL, or [B] written with the ranking score of `strategy`; for
+ * VFM_RANK_RANDOM the Philox uniform keyed on (seed, qkey[r], x[r, field]); qkey [B] int64, NULL: the row's position r.
+ * The three outputs are bitwise those vfm_rank_field_f32 returns for the same (context, candidate).  A row with an id
+ * outside [0, T) gets NaN outputs.  flags: 0 or VFM_FLAG_LINK_SOFTPLUS. */
+int vfm_field_moments_f32(int64_t B, int32_t F, int32_t d, int64_t T, int32_t id_bits, int32_t flags, const void* x,
+                          int32_t field, const float* entity_params, const float* bias_params, const float* scalars,
+                          int32_t strategy, uint64_t seed, const int64_t* qkey, float* logit_mean, float* logit_var,
+                          float* score, void* stream);
+
+/* Workspace of vfm_rank_field_f32, in bytes (n_splits = 0: the automatic split count).  Negative on bad arguments. */
+int64_t vfm_rank_field_workspace_bytes(int64_t Q, int64_t n_cand, int32_t F, int32_t d, int32_t k, int32_t strategy,
+                                       int32_t n_splits);
+
+/* Top k candidates of field `field` for each query context.
+ *  ctx [Q, F] int64 entity ids; column `field` is ignored.  qkey [Q] int64: the query's key of VFM_RANK_RANDOM (score =
+ *  Philox uniform keyed on (seed, qkey[q], candidate id)); NULL: the query's position q.
+ *  cand / cand_lo / n_cand, excl_ptr [Q+1] / excl_items / n_excl, k, the order (score descending, then candidate id
+ *  ascending), padding, NaN handling (a context or candidate id outside [0, T): NaN scores, never returned), n_splits:
+ *  as the users, items and exclusions of vfm_rank_items_f32.  2 <= F <= VFM_MAX_FIELDS.
+ *  Outputs [Q, k]: out_items, out_score, out_mean, out_var: each returned score, mean and variance is bitwise
+ *  vfm_field_moments_f32 of the row (context, candidate).  Bitwise deterministic and independent of n_splits, the grid
+ *  and the stream. */
+int vfm_rank_field_f32(int64_t Q, const int64_t* ctx, int32_t field, const int64_t* qkey, int64_t n_cand,
+                       const int64_t* cand, int64_t cand_lo, int64_t T, int32_t F, int32_t d, int32_t k,
+                       int32_t strategy, int32_t flags, uint64_t seed, int32_t n_splits, const int64_t* excl_ptr,
+                       const int64_t* excl_items, int64_t n_excl, const float* entity_params, const float* bias_params,
+                       const float* scalars, void* workspace, int64_t workspace_bytes, int64_t* out_items,
+                       float* out_score, float* out_mean, float* out_var, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,6 +57,8 @@ _UNITS = [("vfm_abi.hip", "", _EXACT), ("vfm_index.hip", "", []), ("vfm_variants
           ("csrc_rank/vfm_rank.hip", "", ["-ffp-contract=off"]),
           # held-out ranking evaluation: the same score tiles (csrc_rank/vfm_rank_tile.hpp), hence the same flag
           ("csrc_rank/vfm_rank_eval.hip", "", ["-ffp-contract=off"]),
+          # field-form ranking (any number of fields): operands of its own for the same tiles and scan, the same flag
+          ("csrc_rank/vfm_rank_field.hip", "", ["-ffp-contract=off"]),
           # fold-in (include/vfm_foldin.h): outside csrc/ for the same reason; it includes csrc/'s Philox stream and link
           # helpers, so its draws and links are those of the training kernels
           ("csrc_rank/vfm_foldin.hip", "", _EXACT)]

@@ -1,5 +1,6 @@
 // vfm_rank.hip -- preference elicitation (include/vfm_rank.h): closed-form predictive moments (k_moments) and the
-// fused catalog ranking (k_rank_prep -> k_rank -> k_rank_merge).
+// fused catalog ranking (k_rank_prep -> k_rank -> k_rank_merge).  The scan k_rank is instantiated here only; the
+// field-form ranking (vfm_rank_field.hip) launches it through vfm::launch_rank_scan with operands of its own.
 //
 // Compiled with -ffp-contract=off: every fused multiply-add below is an explicit fmaf, so the pair moments of
 // k_moments, the MFMA chains of k_rank and the recomputation in k_rank_merge round the same way, bit for bit.
@@ -11,11 +12,11 @@
 
 #include "vfm_rank.h"
 #include "vfm_rank_tile.hpp"        // pair scores, operand packing (k_rank_prep), the MFMA score tile
+#include "vfm_rank_scan.hpp"        // the scan launch other operand forms share, k_rank_merge, the list workspace
 
 namespace {
 
 constexpr int KR = 16;        // k <= KR: the running top k is kept in registers (branch-free insertion)
-constexpr int MERGE_BLOCK = 256;
 
 // ---------------------------------------------------------------------------------------------------------------------
 // k_moments: one thread per row.  F == 2: the pair chains above; general F: per coordinate in fp64
@@ -173,80 +174,54 @@ __global__ __launch_bounds__(256, 2) void k_rank(RankArgs a) {
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// k_rank_merge: one workgroup per user.  Each list entry's final rank = its position in its own list + the number of
-// entries of the other lists that beat it (binary search: every list is sorted); entries of rank < k are written with
-// their moments recomputed from the tables, the rest of the k slots padded.
-// ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(MERGE_BLOCK) void k_rank_merge(int64_t U, int k, int S, const float* __restrict__ ls,
-                                                            const int* __restrict__ lc, const int64_t* __restrict__ users,
-                                                            const int64_t* __restrict__ cand, int64_t item_lo, int64_t T,
-                                                            int d, bool sp, const float* __restrict__ ent,
-                                                            const float* __restrict__ bias, const float* __restrict__ scal,
-                                                            int64_t* __restrict__ out_items, float* __restrict__ out_score,
-                                                            float* __restrict__ out_m, float* __restrict__ out_v) {
-  __shared__ int n_valid;
-  const int64_t u = blockIdx.x;
-  if (threadIdx.x == 0) n_valid = 0;
-  __syncthreads();
-  const int64_t uid = users[u];
-  const bool uok = uid >= 0 && uid < T;
-  for (int e = threadIdx.x; e < S * k; e += MERGE_BLOCK) {
-    const int s = e / k, p = e - s * k;
-    const float sc = ls[((int64_t)s * U + u) * k + p];
-    const int c = lc[((int64_t)s * U + u) * k + p];
-    if (c == INT32_MAX) continue;
-    atomicAdd(&n_valid, 1);
-    int rank = p;
-    for (int s2 = 0; s2 < S && rank < k; ++s2) {
-      if (s2 == s) continue;
-      const float* L2s = ls + ((int64_t)s2 * U + u) * k;
-      const int* L2c = lc + ((int64_t)s2 * U + u) * k;
-      int lo = 0, hi = k;              // first position whose entry does not beat (sc, c)
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (beats(L2s[mid], L2c[mid], sc, c)) lo = mid + 1;
-        else hi = mid;
-      }
-      rank += lo;
-    }
-    if (rank >= k) continue;
-    const int64_t iid = cand ? cand[c] : item_lo + c;
-    float m = __builtin_nanf(""), v = __builtin_nanf("");
-    if (uok && iid >= 0 && iid < T)
+// The winners' moments of k_rank_merge (vfm_rank_scan.hpp) for two fields: pair_moments straight from the tables
+struct PairMoments {
+  const int64_t* users;
+  int64_t T;
+  int d;
+  bool sp;
+  const float *ent, *bias, *scal;
+  __device__ void operator()(int64_t u, int64_t iid, float& m, float& v) const {
+    const int64_t uid = users[u];
+    if (uid >= 0 && uid < T && iid >= 0 && iid < T)
       pair_moments(ent + uid * 2 * d, ent + iid * 2 * d, bias + uid * 2, bias + iid * 2, scal[1], link_of(scal[2], sp), d,
                    sp, m, v);
-    out_items[u * k + rank] = iid;
-    out_score[u * k + rank] = sc;
-    out_m[u * k + rank] = m;
-    out_v[u * k + rank] = v;
   }
-  __syncthreads();
-  for (int p = min(n_valid, k) + threadIdx.x; p < k; p += MERGE_BLOCK) {
-    out_items[u * k + p] = -1;
-    out_score[u * k + p] = -INFINITY;
-    out_m[u * k + p] = __builtin_nanf("");
-    out_v[u * k + p] = __builtin_nanf("");
-  }
-}
+};
 
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-struct Layout : OpLayout {
-  int64_t off_ls, off_lc, bytes;
-};
+struct Layout : OpLayout, ListLayout {};
 
 Layout layout_of(int64_t U, int64_t n_cand, int d, int k, int strategy, int n_splits) {
   Layout L;
   static_cast<OpLayout&>(L) = op_layout_of(U, n_cand, d, strategy, n_splits);
-  L.off_ls = L.end;
-  L.off_lc = L.off_ls + round_up((int64_t)L.S * U * k * 4, 256);
-  L.bytes = L.off_lc + round_up((int64_t)L.S * U * k * 4, 256);
+  static_cast<ListLayout&>(L) = list_layout_of(L.end, L.S, U, k);
   return L;
 }
 
+int launch_scan(const RankArgs& a, int strategy, dim3 grid, hipStream_t st) {
+  switch (strategy) {
+    case VFM_RANK_TOP: hipLaunchKernelGGL(k_rank<VFM_RANK_TOP>, grid, dim3(256), 0, st, a); break;
+    case VFM_RANK_VARIANCE: hipLaunchKernelGGL(k_rank<VFM_RANK_VARIANCE>, grid, dim3(256), 0, st, a); break;
+    case VFM_RANK_MEAN: hipLaunchKernelGGL(k_rank<VFM_RANK_MEAN>, grid, dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL(k_rank<VFM_RANK_RANDOM>, grid, dim3(256), 0, st, a); break;
+  }
+  return launch_status("k_rank");
+}
+
 }  // namespace
+
+int vfm::launch_rank_scan(const RankScan& r, int strategy, unsigned n_query_tiles, hipStream_t st) {
+  RankArgs a;
+  a.U = r.U; a.n_cand = r.n_cand; a.item_lo = r.item_lo; a.n_excl = r.n_excl;
+  a.users = r.keys; a.cand = r.cand; a.excl_ptr = r.excl_ptr; a.excl_items = r.excl_items;
+  a.ops = TileOps{r.uop, r.iop, r.ucon, r.icon, r.Kp, r.KA, r.KB};
+  a.ls = r.ls; a.lc = r.lc;
+  a.k = r.k; a.n_tiles = r.n_tiles; a.S = r.S; a.seed = r.seed;
+  return launch_scan(a, strategy, dim3(n_query_tiles, (unsigned)r.S), st);
+}
 
 extern "C" {
 
@@ -318,16 +293,10 @@ int vfm_rank_items_f32(int64_t U, const int64_t* users, int64_t n_cand, const in
     if (int rc = launch_rank_prep(L, ws, U, users, n_cand, cand, item_lo, T, d, sp, entity_params, bias_params, scalars,
                                   st))
       return rc;
-  const dim3 grid((unsigned)(L.U_pad / UT), (unsigned)L.S);
-  switch (strategy) {
-    case VFM_RANK_TOP: hipLaunchKernelGGL(k_rank<VFM_RANK_TOP>, grid, dim3(256), 0, st, a); break;
-    case VFM_RANK_VARIANCE: hipLaunchKernelGGL(k_rank<VFM_RANK_VARIANCE>, grid, dim3(256), 0, st, a); break;
-    case VFM_RANK_MEAN: hipLaunchKernelGGL(k_rank<VFM_RANK_MEAN>, grid, dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL(k_rank<VFM_RANK_RANDOM>, grid, dim3(256), 0, st, a); break;
-  }
-  if (int rc = launch_status("k_rank")) return rc;
-  hipLaunchKernelGGL(k_rank_merge, dim3((unsigned)U), dim3(MERGE_BLOCK), 0, st, U, k, L.S, a.ls, a.lc, users, cand,
-                     item_lo, T, d, sp, entity_params, bias_params, scalars, out_items, out_score, out_mean, out_var);
+  if (int rc = launch_scan(a, strategy, dim3((unsigned)(L.U_pad / UT), (unsigned)L.S), st)) return rc;
+  hipLaunchKernelGGL(k_rank_merge<PairMoments>, dim3((unsigned)U), dim3(MERGE_BLOCK), 0, st, U, k, L.S, a.ls, a.lc, cand,
+                     item_lo, PairMoments{users, T, d, sp, entity_params, bias_params, scalars}, out_items, out_score,
+                     out_mean, out_var);
   return launch_status("k_rank_merge");
 }
 

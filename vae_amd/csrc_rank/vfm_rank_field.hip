@@ -1,0 +1,390 @@
+// vfm_rank_field.hip -- ranking one field's catalog for models with any number of fields (include/vfm_rank.h:
+// vfm_field_moments_f32, vfm_rank_field_f32).
+//
+// With every field of a row but one fixed (the query's context), the row's closed-form moments are linear resp.
+// quadratic in the free entity c (include/vfm_foldin.h):
+//   E pred   = c_mean + mu_w,c + sum_k mu_c M
+//   Var pred = c_var + sigma_w,c^2 + sum_k [ mu_c^2 A + sigma_c^2 (A + M^2) + mu_c C ]
+// so over a catalog they are GEMMs again: query [M] . candidate [mu] (K = d) and query [A | A + M^2 | C] . candidate
+// [mu^2 | sigma^2 | mu] (K = 3d).  Only the operands are new:
+//   k_field_ctx_prep   a wave per query, lanes over coordinates: fp64 sums over the context columns -> the packed row
+//   k_field_cand_prep  the candidates' rows
+// The score tiles, the scan with the exclusion cursor, the top k and the split merge are those of the two-field ranking
+// (vfm_rank_tile.hpp, vfm_rank_scan.hpp, k_rank of vfm_rank.hip).  Both parts are always packed (the merge recomputes the
+// winners' two moments from the query's packed row, whatever the strategy scored).
+//
+// Compiled with -ffp-contract=off: field_pair_moments' explicit fmaf chains are the MFMA chains of the tile, and the fp64
+// operand arithmetic (ctx_coord) rounds the same in k_field_ctx_prep and k_field_moments, bit for bit.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "vfm_rank.h"
+#include "vfm_rank_tile.hpp"
+#include "vfm_rank_scan.hpp"
+
+namespace {
+
+constexpr int WAVE = 64;
+constexpr int PREP_BLOCK = 256;       // k_field_ctx_prep: four queries per workgroup
+
+// Coordinate k of a context (the columns f != field of xr), in fp64, sums in column order.  With S the sum of the
+// context embeddings and P their pair term:  M = E S,  A = Var S,  C = 2 Cov(S, P) = 2 sum_q sigma_q^2 (M - mu_q),
+// ep = E P = ((sum mu)^2 - sum mu^2) / 2,  vp = Var P = sum_{q<r} sigma_q^2 sigma_r^2 + sum_q sigma_q^2 (M - mu_q)^2
+// (the context-only part of the variance of vfm_rank.h), the sums over q expanded so that one pass over the rows serves.
+struct CtxCoord {
+  double M, A, C, ep, vp;
+};
+
+template <typename ID>
+__device__ __forceinline__ CtxCoord ctx_coord(const ID* xr, int F, int field, int k, int d, bool sp,
+                                              const float* __restrict__ ent) {
+  double s1 = 0., smm = 0., ss = 0., sss = 0., ssm = 0., ssmm = 0.;
+  for (int f = 0; f < F; ++f) {
+    if (f == field) continue;
+    const float* row = ent + (int64_t)xr[f] * 2 * d;
+    const double m = row[k], s = link_of(row[d + k], sp), s2 = s * s;
+    s1 += m; smm += m * m; ss += s2; sss += s2 * s2; ssm += s2 * m; ssmm += s2 * (m * m);
+  }
+  CtxCoord c;
+  c.M = s1;
+  c.A = ss;
+  c.C = 2. * (s1 * ss - ssm);
+  c.ep = 0.5 * (s1 * s1 - smm);
+  c.vp = 0.5 * (ss * ss - sss) + ((s1 * s1) * ss - 2. * s1 * ssm + ssmm);
+  return c;
+}
+
+// The stored (fp32, rounded once) query operands of a coordinate: mean part [M], variance part [A | A + M^2 | C]
+__device__ __forceinline__ float ctx_op_var(const CtxCoord& c, int part) {
+  return part == 0 ? (float)c.A : part == 1 ? (float)(c.A + c.M * c.M) : (float)c.C;
+}
+
+// The context's constants before the coordinates are added: (m0 + sum_q mu_w,q, sigma0^2 + sum_q sigma_w,q^2)
+template <typename ID>
+__device__ __forceinline__ void ctx_consts(const ID* xr, int F, int field, bool sp, const float* __restrict__ bias,
+                                           const float* __restrict__ scal, double& cm, double& cv) {
+  const double sg0 = (double)link_of(scal[2], sp);
+  cm = (double)scal[1];
+  cv = sg0 * sg0;
+  for (int f = 0; f < F; ++f) {
+    if (f == field) continue;
+    const int64_t e = (int64_t)xr[f];
+    const double sw = (double)link_of(bias[e * 2 + 1], sp);
+    cm += (double)bias[e * 2];
+    cv += sw * sw;
+  }
+}
+
+template <typename ID>
+__device__ __forceinline__ bool ctx_valid(const ID* xr, int F, int field, int64_t T) {
+  bool ok = true;
+  for (int f = 0; f < F; ++f) ok = ok && (f == field || ((int64_t)xr[f] >= 0 && (int64_t)xr[f] < T));
+  return ok;
+}
+
+// The candidate's operands: mean part [mu], variance part [mu^2 | sigma^2 | mu]
+__device__ __forceinline__ float cand_op_var(const float* row, int kb, int d, bool sp) {
+  if (kb < d) return row[kb] * row[kb];
+  if (kb < 2 * d) {
+    const float s = link_of(row[kb], sp);        // (row[d + (kb - d)])
+    return s * s;
+  }
+  return row[kb - 2 * d];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// field_pair_moments: the moments of (context, candidate) from the query's operands q (q.mean_op(k), q.var_op(kb)) and
+// the candidate's table rows: the same fp32 chains, in the same k order, as the MFMA accumulation of the tile, and the
+// tile's epilogue (accumulator + query constant) + candidate constant.
+// ---------------------------------------------------------------------------------------------------------------------
+template <typename QOP>
+__device__ void field_pair_moments(const QOP& q, const float* ec, const float* bc, float c_mean, float c_var, int d,
+                                   bool sp, float& mean, float& var) {
+  float am = 0.f, av = 0.f;
+  for (int k = 0; k < d; ++k) am = fmaf(op_mean(ec, k), q.mean_op(k), am);
+  for (int kb = 0; kb < 3 * d; ++kb) av = fmaf(cand_op_var(ec, kb, d, sp), q.var_op(kb), av);
+  const float sw = link_of(bc[1], sp);
+  mean = (am + c_mean) + bc[0];
+  var = (av + c_var) + sw * sw;
+}
+
+// A query's operands read from its packed row (the ranking's workspace)
+struct StoredOp {
+  const float* row;
+  int KA;
+  __device__ float mean_op(int k) const { return row[k]; }
+  __device__ float var_op(int kb) const { return row[KA + kb]; }
+};
+
+// A query's operands formed on the fly from the tables (k_field_moments: no workspace)
+template <typename ID>
+struct TableOp {
+  const ID* xr;
+  int F, field, d;
+  bool sp;
+  const float* ent;
+  __device__ float mean_op(int k) const { return (float)ctx_coord(xr, F, field, k, d, sp, ent).M; }
+  __device__ float var_op(int kb) const {
+    const int part = kb / d;
+    return ctx_op_var(ctx_coord(xr, F, field, kb - part * d, d, sp, ent), part);
+  }
+};
+
+// ---------------------------------------------------------------------------------------------------------------------
+// k_field_moments: one thread per row x [B, F]; column `field` is the free entity, the others its context.
+// ---------------------------------------------------------------------------------------------------------------------
+template <typename ID>
+__global__ __launch_bounds__(256) void k_field_moments(int64_t B, int F, int field, int d, int64_t T, bool sp,
+                                                       const ID* __restrict__ x, const float* __restrict__ ent,
+                                                       const float* __restrict__ bias, const float* __restrict__ scal,
+                                                       int strat, uint64_t seed, const int64_t* __restrict__ qkey,
+                                                       float* __restrict__ out_m, float* __restrict__ out_v,
+                                                       float* __restrict__ out_s) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= B) return;
+  const ID* xr = x + r * F;
+  const int64_t c = (int64_t)xr[field];
+  float mean = __builtin_nanf(""), var = __builtin_nanf(""), sc = __builtin_nanf("");
+  if (ctx_valid(xr, F, field, T) && c >= 0 && c < T) {
+    double cm, cv;
+    ctx_consts(xr, F, field, sp, bias, scal, cm, cv);
+    for (int k = 0; k < d; ++k) {                 // (in k order, as the prep's ordered lane sum)
+      const CtxCoord cc = ctx_coord(xr, F, field, k, d, sp, ent);
+      cm += cc.ep;
+      cv += cc.vp;
+    }
+    field_pair_moments(TableOp<ID>{xr, F, field, d, sp, ent}, ent + c * 2 * d, bias + c * 2, (float)cm, (float)cv, d, sp,
+                       mean, var);
+    sc = strat == VFM_RANK_RANDOM ? philox_uniform(seed, qkey ? qkey[r] : r, c) : score_of(strat, mean, var);
+  }
+  out_m[r] = mean;
+  out_v[r] = var;
+  if (out_s) out_s[r] = sc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// k_field_ctx_prep: a wave per query row (rows past Q: zero padding), lanes over coordinates, so every gather of a
+// context entity's 8d bytes is coalesced.  Writes the packed row [M .. 0 | A | A + M^2 | C .. 0], the constants
+// (c_mean, c_var) -- the coordinates' E P and Var P added in k order: an ordered sum over the lanes of each chunk of 64 --
+// and, without caller keys, the query's position as its Philox key.  A context id outside [0, T): a NaN row.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(PREP_BLOCK) void k_field_ctx_prep(int64_t Q_pad, int64_t Q, const int64_t* __restrict__ ctx,
+                                                               int F, int field, int64_t T, int Kp, int KA, int KB,
+                                                               int d, bool sp, const float* __restrict__ ent,
+                                                               const float* __restrict__ bias,
+                                                               const float* __restrict__ scal, float* __restrict__ op,
+                                                               float* __restrict__ con, int64_t* __restrict__ key_out) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int64_t r = (int64_t)blockIdx.x * (PREP_BLOCK / WAVE) + (threadIdx.x >> 6);
+  if (r >= Q_pad) return;                                   // (wave-uniform)
+  float* row = op + r * Kp;
+  const int64_t* xr = ctx + r * F;
+  const bool live = r < Q;
+  const bool ok = live && ctx_valid(xr, F, field, T);
+  if (!ok) {
+    const float fill = live ? __builtin_nanf("") : 0.f;
+    for (int k = lane; k < Kp; k += WAVE) row[k] = fill;
+    if (lane < 2) con[r * 2 + lane] = fill;
+  } else {
+    double cm, cv;
+    ctx_consts(xr, F, field, sp, bias, scal, cm, cv);
+    for (int k0 = 0; k0 < d; k0 += WAVE) {
+      const int k = k0 + lane;
+      CtxCoord cc = {0., 0., 0., 0., 0.};
+      if (k < d) {
+        cc = ctx_coord(xr, F, field, k, d, sp, ent);
+        row[k] = (float)cc.M;
+        row[KA + k] = ctx_op_var(cc, 0);
+        row[KA + d + k] = ctx_op_var(cc, 1);
+        row[KA + 2 * d + k] = ctx_op_var(cc, 2);
+      }
+      const int n = min(WAVE, d - k0);
+      for (int j = 0; j < n; ++j) {
+        cm += __shfl(cc.ep, j);
+        cv += __shfl(cc.vp, j);
+      }
+    }
+    for (int k = d + lane; k < KA; k += WAVE) row[k] = 0.f;
+    for (int kb = 3 * d + lane; kb < KB; kb += WAVE) row[KA + kb] = 0.f;
+    if (lane == 0) {
+      con[r * 2] = (float)cm;
+      con[r * 2 + 1] = (float)cv;
+    }
+  }
+  if (key_out && live && lane == 0) key_out[r] = r;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// k_field_cand_prep: the candidates' packed rows [rows_pad, Kp] = [mu .. 0 | mu^2 | sigma^2 | mu .. 0] (zero rows past
+// n_cand) and constants (mu_w, sigma_w^2); one thread per value, as k_rank_prep.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_field_cand_prep(int64_t rows_pad, int64_t rows, const int64_t* __restrict__ ids,
+                                                         int64_t lo, int64_t T, int Kp, int KA, int d, bool sp,
+                                                         const float* __restrict__ ent, const float* __restrict__ bias,
+                                                         float* __restrict__ op, float* __restrict__ con) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int W = Kp + 2;
+  if (idx >= rows_pad * W) return;
+  const int64_t r = idx / W;
+  const int k = (int)(idx - r * W);
+  float v = 0.f;
+  if (r < rows) {
+    const int64_t e = ids ? ids[r] : lo + r;
+    if (e < 0 || e >= T) {
+      v = __builtin_nanf("");
+    } else if (k < KA) {
+      v = k < d ? op_mean(ent + e * 2 * d, k) : 0.f;
+    } else if (k < Kp) {
+      const int kb = k - KA;
+      v = kb < 3 * d ? cand_op_var(ent + e * 2 * d, kb, d, sp) : 0.f;
+    } else if (k == Kp) {
+      v = bias[e * 2];
+    } else {
+      const float sw = link_of(bias[e * 2 + 1], sp);
+      v = sw * sw;
+    }
+  }
+  if (k < Kp) op[r * Kp + k] = v;
+  else con[r * 2 + (k - Kp)] = v;
+}
+
+// The winners' moments of k_rank_merge: the query's packed row and constants against the candidate's table rows
+struct FieldMoments {
+  const float *uop, *ucon;
+  int Kp, KA;
+  int64_t T;
+  int d;
+  bool sp;
+  const float *ent, *bias;
+  __device__ void operator()(int64_t u, int64_t iid, float& m, float& v) const {
+    if (iid >= 0 && iid < T)
+      field_pair_moments(StoredOp{uop + u * Kp, KA}, ent + iid * 2 * d, bias + iid * 2, ucon[u * 2], ucon[u * 2 + 1], d,
+                         sp, m, v);
+  }
+};
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------------
+// The workspace: both operand parts for every strategy (no candidate block for VFM_RANK_RANDOM: no tile runs), the
+// position keys, the split lists.  Padding, tiles and the split count: op_layout_of.
+struct FieldLayout : ListLayout {
+  int KA, KB, Kp, S, n_tiles;
+  int64_t U_pad, C_pad, off_uop, off_iop, off_ucon, off_icon, off_key;
+};
+
+FieldLayout field_layout_of(int64_t Q, int64_t n_cand, int d, int k, int strategy, int n_splits) {
+  const OpLayout B = op_layout_of(Q, n_cand, d, strategy, n_splits);
+  FieldLayout L;
+  L.KA = (int)round_up(d, KS);
+  L.KB = (int)round_up(3 * (int64_t)d, KS);
+  L.Kp = L.KA + L.KB;
+  L.S = B.S; L.n_tiles = B.n_tiles; L.U_pad = B.U_pad; L.C_pad = B.C_pad;
+  const int64_t c_rows = strategy == VFM_RANK_RANDOM ? 0 : L.C_pad;
+  L.off_uop = 0;
+  L.off_iop = L.off_uop + round_up(L.U_pad * L.Kp * 4, 256);
+  L.off_ucon = L.off_iop + round_up(c_rows * L.Kp * 4, 256);
+  L.off_icon = L.off_ucon + round_up(L.U_pad * 2 * 4, 256);
+  L.off_key = L.off_icon + round_up(c_rows * 2 * 4, 256);
+  static_cast<ListLayout&>(L) = list_layout_of(L.off_key + round_up(Q * 8, 256), L.S, Q, k);
+  return L;
+}
+
+int check_fields(int32_t F, int32_t field) {
+  if (F < 2 || F > VFM_MAX_FIELDS) return vfm::fail(VFM_E_INVALID, "F out of range [2,64]");
+  if (field < 0 || field >= F) return vfm::fail(VFM_E_INVALID, "field out of range [0,F)");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vfm_field_moments_f32(int64_t B, int32_t F, int32_t d, int64_t T, int32_t id_bits, int32_t flags, const void* x,
+                          int32_t field, const float* entity_params, const float* bias_params, const float* scalars,
+                          int32_t strategy, uint64_t seed, const int64_t* qkey, float* logit_mean, float* logit_var,
+                          float* score, void* stream) {
+  if (int rc = check_common(T, d, flags, strategy)) return rc;
+  if (int rc = check_fields(F, field)) return rc;
+  if (B < 0) return vfm::fail(VFM_E_INVALID, "B < 0");
+  if (id_bits != 32 && id_bits != 64) return vfm::fail(VFM_E_INVALID, "id_bits must be 32 or 64");
+  if (B == 0) return 0;
+  if (!x || !entity_params || !bias_params || !scalars || !logit_mean || !logit_var)
+    return vfm::fail(VFM_E_INVALID, "null pointer");
+  const hipStream_t st = (hipStream_t)stream;
+  const bool sp = (flags & VFM_FLAG_LINK_SOFTPLUS) != 0;
+  const unsigned nb = (unsigned)((B + 255) / 256);
+  if (id_bits == 64)
+    hipLaunchKernelGGL(k_field_moments<int64_t>, dim3(nb), dim3(256), 0, st, B, F, field, d, T, sp, (const int64_t*)x,
+                       entity_params, bias_params, scalars, strategy, seed, qkey, logit_mean, logit_var, score);
+  else
+    hipLaunchKernelGGL(k_field_moments<int32_t>, dim3(nb), dim3(256), 0, st, B, F, field, d, T, sp, (const int32_t*)x,
+                       entity_params, bias_params, scalars, strategy, seed, qkey, logit_mean, logit_var, score);
+  return launch_status("k_field_moments");
+}
+
+int64_t vfm_rank_field_workspace_bytes(int64_t Q, int64_t n_cand, int32_t F, int32_t d, int32_t k, int32_t strategy,
+                                       int32_t n_splits) {
+  if (Q < 0 || n_cand < 0 || n_cand >= ((int64_t)1 << 31) || F < 2 || F > VFM_MAX_FIELDS || d < 1 || d > 4096 || k < 1 ||
+      k > VFM_RANK_MAX_K || strategy < VFM_RANK_TOP || strategy > VFM_RANK_RANDOM || n_splits < 0 ||
+      n_splits > VFM_RANK_MAX_SPLITS)
+    return VFM_E_INVALID;
+  return field_layout_of(Q, n_cand, d, k, strategy, n_splits).bytes;
+}
+
+int vfm_rank_field_f32(int64_t Q, const int64_t* ctx, int32_t field, const int64_t* qkey, int64_t n_cand,
+                       const int64_t* cand, int64_t cand_lo, int64_t T, int32_t F, int32_t d, int32_t k,
+                       int32_t strategy, int32_t flags, uint64_t seed, int32_t n_splits, const int64_t* excl_ptr,
+                       const int64_t* excl_items, int64_t n_excl, const float* entity_params, const float* bias_params,
+                       const float* scalars, void* workspace, int64_t workspace_bytes, int64_t* out_items,
+                       float* out_score, float* out_mean, float* out_var, void* stream) {
+  if (int rc = check_common(T, d, flags, strategy)) return rc;
+  if (int rc = check_fields(F, field)) return rc;
+  if (k < 1 || k > VFM_RANK_MAX_K) return vfm::fail(VFM_E_INVALID, "k out of range [1,128]");
+  if (Q < 0) return vfm::fail(VFM_E_INVALID, "Q < 0");
+  if (n_cand < 0 || n_cand >= ((int64_t)1 << 31)) return vfm::fail(VFM_E_INVALID, "n_cand out of range [0,2^31)");
+  if (n_splits < 0 || n_splits > VFM_RANK_MAX_SPLITS) return vfm::fail(VFM_E_INVALID, "n_splits out of range [0,64]");
+  if (!cand && (cand_lo < 0 || cand_lo + n_cand > T)) return vfm::fail(VFM_E_INVALID, "candidate range outside [0,T)");
+  if (n_excl < 0 || (n_excl > 0 && (!excl_ptr || !excl_items)))
+    return vfm::fail(VFM_E_INVALID, "exclusion lists: excl_ptr and excl_items together, n_excl >= 0");
+  if (Q == 0) return 0;
+  if (!ctx || !entity_params || !bias_params || !scalars || !workspace || !out_items || !out_score || !out_mean ||
+      !out_var)
+    return vfm::fail(VFM_E_INVALID, "null pointer");
+  const FieldLayout L = field_layout_of(Q, n_cand, d, k, strategy, n_splits);
+  if (workspace_bytes < L.bytes)
+    return vfm::fail(VFM_E_INVALID, "workspace too small (vfm_rank_field_workspace_bytes)");
+  if (((uintptr_t)workspace) & 255) return vfm::fail(VFM_E_INVALID, "workspace must be 256-byte aligned");
+
+  const hipStream_t st = (hipStream_t)stream;
+  const bool sp = (flags & VFM_FLAG_LINK_SOFTPLUS) != 0;
+  char* ws = (char*)workspace;
+  float *uop = (float*)(ws + L.off_uop), *iop = (float*)(ws + L.off_iop), *ucon = (float*)(ws + L.off_ucon),
+        *icon = (float*)(ws + L.off_icon);
+  int64_t* keys = (int64_t*)(ws + L.off_key);
+  hipLaunchKernelGGL(k_field_ctx_prep, dim3((unsigned)((L.U_pad + PREP_BLOCK / WAVE - 1) / (PREP_BLOCK / WAVE))),
+                     dim3(PREP_BLOCK), 0, st, L.U_pad, Q, ctx, F, field, T, L.Kp, L.KA, L.KB, d, sp, entity_params,
+                     bias_params, scalars, uop, ucon, qkey ? (int64_t*)nullptr : keys);
+  if (int rc = launch_status("k_field_ctx_prep")) return rc;
+  const int64_t ni = L.C_pad * (L.Kp + 2);
+  if (strategy != VFM_RANK_RANDOM && ni > 0) {
+    hipLaunchKernelGGL(k_field_cand_prep, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, st, L.C_pad, n_cand, cand,
+                       cand_lo, T, L.Kp, L.KA, d, sp, entity_params, bias_params, iop, icon);
+    if (int rc = launch_status("k_field_cand_prep")) return rc;
+  }
+  vfm::RankScan a;
+  a.U = Q; a.n_cand = n_cand; a.item_lo = cand_lo; a.n_excl = excl_ptr ? n_excl : 0;
+  a.keys = qkey ? qkey : keys; a.cand = cand; a.excl_ptr = excl_ptr; a.excl_items = excl_items;
+  a.uop = uop; a.iop = iop; a.ucon = ucon; a.icon = icon;
+  a.Kp = L.Kp; a.KA = L.KA; a.KB = L.KB;
+  a.ls = (float*)(ws + L.off_ls); a.lc = (int*)(ws + L.off_lc);
+  a.k = k; a.n_tiles = L.n_tiles; a.S = L.S; a.seed = seed;
+  if (int rc = vfm::launch_rank_scan(a, strategy, (unsigned)(L.U_pad / UT), st)) return rc;
+  hipLaunchKernelGGL(k_rank_merge<FieldMoments>, dim3((unsigned)Q), dim3(MERGE_BLOCK), 0, st, Q, k, L.S, a.ls, a.lc, cand,
+                     cand_lo, FieldMoments{uop, ucon, L.Kp, L.KA, T, d, sp, entity_params, bias_params}, out_items,
+                     out_score, out_mean, out_var);
+  return launch_status("k_rank_merge");
+}
+
+}  // extern "C"

@@ -1057,6 +1057,30 @@ class VFM(nn.Module):
         return rank.rank_heldout(self, pos, exclude, items, strategy, seed, n_splits)
 
     @torch.no_grad()
+    def rank_field(self, contexts, field: int, k: int = 10, strategy: str = "top", candidates=None, exclude=None,
+                   match_fields=None, key_field: Optional[int] = None, seed: int = 0, n_splits: int = 0):
+        """The k best entities of one field for each context, any number of fields (>= 2): "which k items for this user
+        in this format?".  contexts: [Q, F] rows of entity ids, column `field` ignored; a context column holding ids of
+        the ranked field's range raises.  candidates: entity ids of the field's range (default: the whole range);
+        exclude: [R, F] rows (e.g. X_train): candidate c is never returned for query q when a row holds c in column
+        `field` and agrees with q on the columns `match_fields` (default: every context column; (0,) = "anything this
+        user has seen, in any format").  strategy, k, seed, n_splits, the order, padding and determinism: as rank_items;
+        "random" is keyed on (seed, the context's id in column key_field -- default: the lowest context column --,
+        candidate id).  Duplicate contexts are ranked once.  Returns dict(items [Q, k] int64, score, logit_mean,
+        logit_var [Q, k]), one row per row of `contexts`; every score, mean and variance is bitwise field_moments of the
+        row (context, returned candidate)."""
+        return rank.rank_field(self, contexts, field, k, strategy, candidates, exclude, match_fields, key_field, seed,
+                               n_splits)
+
+    @torch.no_grad()
+    def field_moments(self, X, field: int, strategy: Optional[str] = None, seed: int = 0,
+                      key_field: Optional[int] = None):
+        """Closed-form logit mean and variance of the rows X [B, F] in the field form of rank_field (column `field` the
+        candidate, the others its context: include/vfm_rank.h), and the ranking score of `strategy` (None: no score).
+        Equal to predictive_moments up to fp32 rounding; bitwise what rank_field returns.  Returns (mean, var, score)."""
+        return rank.field_moments(self, X, field, strategy, seed, key_field)
+
+    @torch.no_grad()
     def evaluate_ranking(self, X_test, y_test, ks=(10,), exclude=None, items=None, threshold: Optional[float] = None,
                          per_user: bool = False):
         """Held-out top-k ranking metrics over the full catalog (two-field model): each user's relevant test items

@@ -152,6 +152,154 @@ def select_next_questions(model, pool, n: int = 1, strategy: str = "variance", s
     return users, rows
 
 
+def field_exclusion_csr(ctx: torch.Tensor, exclude: torch.Tensor, field: int, match_fields, T: int):
+    """CSR of rank_field's exclusions over the query contexts ctx [Q, F] (any order): candidate c is excluded for query q
+    when a row of `exclude` [R, F] holds c in column `field` and agrees with q on the columns `match_fields`.  Returns
+    (ptr [Q+1] int64, items [n] int64 ascending per query, duplicates dropped).  The distinct keys are numbered by one
+    `unique` over the key columns of queries and rows together; the per-key lists are exclusion_csr's, and every query
+    takes a copy of its key's list."""
+    dev, Q = ctx.device, ctx.shape[0]
+    ex = exclude.to(dev, torch.int64)
+    cols = list(match_fields)
+    if cols:
+        keys = torch.cat([ctx[:, cols], ex[:, cols]], 0)
+        g = torch.unique(keys, dim=0, return_inverse=True)[1].reshape(-1)
+    else:                                                                    # (no key column: every row matches every query)
+        g = torch.zeros(Q + ex.shape[0], dtype=torch.int64, device=dev)
+    gq, ge = g[:Q], g[Q:]
+    ug, ginv = torch.unique(gq, return_inverse=True)                         # the keys the queries hold
+    gptr, gitems = exclusion_csr(ug, torch.stack([ge, ex[:, field]], 1), T)
+    counts = (gptr[1:] - gptr[:-1])[ginv]
+    ptr = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=ptr[1:])
+    qi = torch.repeat_interleave(torch.arange(Q, device=dev), counts)
+    src = gptr[ginv[qi]] + (torch.arange(qi.numel(), device=dev) - ptr[qi])
+    return ptr, gitems[src].contiguous()
+
+
+def _field_arg(model, field):
+    if isinstance(field, bool) or not isinstance(field, int) or not 0 <= field < model.F:
+        raise ValueError(f"field must be an int in [0, {model.F})")
+    if model.F < 2:
+        raise ValueError("the field form needs a model with at least two fields")
+    return field
+
+
+def _key_field(model, field, key_field):
+    ctx_cols = [f for f in range(model.F) if f != field]
+    if key_field is None:
+        return ctx_cols[0]
+    if isinstance(key_field, bool) or not isinstance(key_field, int) or key_field not in ctx_cols:
+        raise ValueError(f"key_field must be a context column, one of {ctx_cols}")
+    return key_field
+
+
+def _context_rows(model, x, name, field, check_field_column=False):
+    """x [R, F] int64 on the model's device: context ids inside [0, T) and outside the ranked field's range (they would
+    be candidates, not context), and -- for full rows -- column `field` inside that range."""
+    from .foldin import field_range
+    x = torch.as_tensor(x)
+    if x.dtype.is_floating_point or x.dtype == torch.bool:
+        raise ValueError(f"{name} must hold integer ids")
+    x = x.to(model.device, torch.int64)
+    if x.dim() != 2 or x.shape[1] != model.F:
+        raise ValueError(f"{name} must be [R, {model.F}]")
+    if x.shape[0]:
+        lo, hi = field_range(model, field)
+        p = torch.cat([x[:, :field], x[:, field + 1:]], 1)
+        if int(p.min()) < 0 or int(p.max()) >= model.T:
+            raise ValueError(f"{name}: context ids must lie in [0, {model.T})")
+        if bool(((p >= lo) & (p < hi)).any()):
+            raise ValueError(f"{name}: context columns hold ids of the ranked field's range [{lo}, {hi})")
+        if check_field_column and (int(x[:, field].min()) < lo or int(x[:, field].max()) >= hi):
+            raise ValueError(f"{name}: column {field} must lie in the field's range [{lo}, {hi})")
+    return x
+
+
+def field_moments(model, X, field, strategy: Optional[str] = None, seed: int = 0, key_field=None):
+    """(logit_mean [B], logit_var [B], score [B] or None) of the rows X [B, F] in the field form: the bitwise definition
+    of what rank_field returns (model.field_moments documents the arguments)."""
+    field = _field_arg(model, field)
+    kf = _key_field(model, field, key_field)
+    code = strategy_code(strategy) if strategy is not None else 0
+    if strategy == "mean" and model.output != "class":
+        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
+    x = torch.as_tensor(X)
+    if x.dim() != 2 or x.shape[1] != model.F:
+        raise ValueError(f"X must be [B, {model.F}]")
+    ops._need_cuda(model._flat, "the model's parameters")
+    x = x.to(model.device)
+    x = (x if x.dtype in (torch.int32, torch.int64) else x.to(torch.int64)).contiguous()
+    model._fresh_params()
+    ent, bia, scal = model._views(model._flat)
+    B = x.shape[0]
+    m = torch.empty(B, dtype=torch.float32, device=x.device)
+    v = torch.empty_like(m)
+    sc = torch.empty_like(m) if strategy is not None else None
+    qkey = x[:, kf].to(torch.int64).contiguous()
+    _lib.ops().field_moments(x, field, qkey, ent, bia, scal, m, v, sc,
+                             ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, code, _seed64(seed))
+    return m, v, sc
+
+
+def rank_field(model, contexts, field, k: int = 10, strategy: str = "top", candidates=None, exclude=None,
+               match_fields=None, key_field=None, seed: int = 0, n_splits: int = 0):
+    """The k best entities of `field` for each context row (model.rank_field documents the arguments)."""
+    from .foldin import field_range
+    field = _field_arg(model, field)
+    code = strategy_code(strategy)
+    if strategy == "mean" and model.output != "class":
+        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
+    if not 1 <= int(k) <= MAX_K:
+        raise ValueError(f"k must lie in [1, {MAX_K}]")
+    if not 0 <= int(n_splits) <= MAX_SPLITS:
+        raise ValueError(f"n_splits must lie in [0, {MAX_SPLITS}]")
+    k = int(k)
+    kf = _key_field(model, field, key_field)
+    ctx_cols = [f for f in range(model.F) if f != field]
+    if match_fields is None:
+        match = ctx_cols
+    else:
+        match = sorted({int(f) for f in match_fields})
+        if any(f not in ctx_cols for f in match):
+            raise ValueError(f"match_fields must be context columns, a subset of {ctx_cols}")
+    dev, T = model.device, model.T
+    lo, hi = field_range(model, field)
+    ctx = _context_rows(model, contexts, "contexts", field).clone()
+    ctx[:, field] = 0                                          # (ignored by the kernels; zeroed so that duplicates meet)
+    cand, n_cand = None, hi - lo
+    if candidates is not None:
+        cand = torch.as_tensor(candidates).to(dev, torch.int64).reshape(-1)
+        if cand.numel() and (int(cand.min()) < lo or int(cand.max()) >= hi):
+            raise ValueError(f"candidate ids must lie in the field's range [{lo}, {hi})")
+        cand = torch.sort(cand).values
+        if cand.numel() > 1 and bool((cand[1:] == cand[:-1]).any()):
+            raise ValueError("duplicate candidates")
+        n_cand = cand.numel()
+    ex = _context_rows(model, exclude, "exclude", field, check_field_column=True) if exclude is not None else None
+    ops._need_cuda(model._flat, "the model's parameters")
+    uq, inv = torch.unique(ctx, dim=0, return_inverse=True)    # (each distinct context ranked once)
+    inv = inv.reshape(-1)
+    ptr = ex_items = None
+    if ex is not None:
+        ptr, ex_items = field_exclusion_csr(uq, ex, field, match, T)
+    model._fresh_params()
+    ent, bia, scal = model._views(model._flat)
+    Q = uq.shape[0]
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = {"items": torch.empty(Q, k, dtype=torch.int64, device=dev), "score": torch.empty(Q, k, **f32),
+           "logit_mean": torch.empty(Q, k, **f32), "logit_var": torch.empty(Q, k, **f32)}
+    o = _lib.ops()
+    ws = torch.empty(max(o.rank_field_workspace_bytes(Q, n_cand, model.F, model.d, k, code, int(n_splits)), 1),
+                     dtype=torch.uint8, device=dev)
+    o.rank_field(uq.contiguous(), field, uq[:, kf].contiguous(), cand, n_cand, lo, ptr, ex_items, ent, bia, scal, ws,
+                 out["items"], out["score"], out["logit_mean"], out["logit_var"], k, code,
+                 ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, _seed64(seed), int(n_splits))
+    if Q != ctx.shape[0] or not bool((uq == ctx).all()):
+        out = {key: val[inv] for key, val in out.items()}
+    return out
+
+
 def _candidates(model, items):
     """(cand sorted int64 or None, n_cand) of rank_items' `items` argument."""
     N, M, T = model.N, model.M, model.T
