@@ -1,0 +1,38 @@
+#!/usr/bin/env python3
+"""The reference's interactive experiment (vfm.py:1236-1251) on the `fraction` data set, as elicitation sessions: the
+students of the test rows are treated as a cold-start population (their posteriors start from the prior), every one of
+them is asked up to 15 questions picked by a strategy from the student's current posterior, and after each answer the
+student's posterior alone is refitted -- all rounds of all students in one launch per strategy (`VFM.elicit`).  Prints
+the test AUC on the questions still unasked after every round, once per strategy:
+
+    python examples/elicit_session.py [questions] [epochs]     (needs an MI355X; vae_amd has no CPU fallback)
+"""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch
+from vae_amd.model import VFM
+from vae_amd.data import load_fraction
+
+
+def main():
+    questions = int(sys.argv[1]) if len(sys.argv) > 1 else 15
+    epochs = int(sys.argv[2]) if len(sys.argv) > 2 else 60
+    N, M, X_train, X_test, y_train, y_test = load_fraction(os.path.join(ROOT, "tests", "golden", "fraction"))
+    X_train, X_test = torch.as_tensor(X_train), torch.as_tensor(X_test)
+    y_train, y_test = torch.as_tensor(y_train), torch.as_tensor(y_test)
+    torch.manual_seed(42)
+    model = VFM(N, M, embedding_size=5, output="class", device="cuda")
+    model.fit(X_train, y_train, n_epochs=epochs, batch_size=100000, verbose=False)
+    strategies = ("mean", "random", "variance")
+    curve = model.elicitation_curve(X_test, y_test, questions, strategies, n_steps=200, lr=0.05, reset=True, seed=1)
+    print(f"{len(torch.unique(X_test[:, 0]))} students, {len(X_test)} questions in the pool")
+    print("asked  " + "  ".join(f"{s:>16}" for s in strategies))
+    for q in range(questions + 1):
+        print(f"{q:5d}  " + "  ".join(f"{curve[s][q]:8.4f} ({curve['n_unasked'][s][q]:5d})" for s in strategies))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,104 @@
+/*
+ * vfm_elicit.h -- C ABI of the elicitation session of libvfm_hip.so (gfx950): an adaptive questionnaire -- ask, fold
+ * in, ask again -- for many users in one launch.
+ *
+ * The reference's last act (vfm.py:1236-1251, --interactive) asks every test user N_QUESTIONS_ASKED questions: pick the
+ * next question by a strategy, take the answer, refit the user's parameters alone.  With the items frozen the users are
+ * independent, and every round of a user's session depends on that user's own posterior only, so a whole session runs
+ * where a whole fold-in runs (vfm_foldin.h): one lane group per user, theta_u in registers over all rounds, the user's
+ * rows in LDS.
+ *
+ * Per user u independently, for round q = 0 .. n_rounds - 1:
+ *  1. Score.  Every pool row of u not asked yet gets the closed-form (mean, var, score) of the pair (u, item) under u's
+ *     CURRENT posterior (round 0: the table row, or the prior mu = 0, sigma = 1 with `reset`) and the frozen item rows:
+ *     bitwise what vfm_predictive_moments_f32 (vfm_rank.h) returns for the pair if u's table row held that posterior;
+ *     VFM_RANK_RANDOM: the Philox uniform keyed on (seed + q, u, item).
+ *  2. Choose.  The best score; ties go to the lower pool position; a NaN score is never chosen.  Nothing left to ask:
+ *     out_row = -1, out_score = out_loss = NaN, and nothing more is folded for u.
+ *  3. Fold in.  u's rows are now the history in its given order followed by the asked rows in the order asked: n_steps
+ *     Adam updates from the current posterior with fresh moments, bitwise what vfm_foldin_f32 gives for E = 1 on exactly
+ *     those rows (the sampled objective with t0 + q (n_steps + 1) as its t0).  The result is round q + 1's posterior.
+ *
+ * Two-field models: column 0 the users, column 1 the items; the items' rows are frozen (an id of `users` must not
+ * appear among the items).  A user's result does not depend on the other users of the launch, the grid or the stream.
+ * Launches: one operand pass over op_x (closed form only) and the session kernel, whatever n_rounds.
+ *
+ * Conventions: those of vfm_hip.h / vfm_foldin.h.  Every pointer is DEVICE memory owned by the caller; launch-only, no
+ * host synchronisation; the caller owns the workspace (vfm_elicit_workspace_bytes, 256-byte aligned); 0 on success, a
+ * negative VFM_E_* code or a positive hipError_t otherwise; arguments are checked before any HIP call;
+ * vfm_last_error() describes the last failure on the calling thread.
+ */
+#ifndef VFM_ELICIT_H
+#define VFM_ELICIT_H
+
+#include <stdint.h>
+
+#include "vfm_foldin.h"
+#include "vfm_hip.h"
+#include "vfm_rank.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define VFM_ELICIT_MAX_ROUNDS 4096
+
+typedef struct vfm_elicit_t {
+  uint32_t struct_size; /* sizeof(vfm_elicit_t) of the caller's build; checked (VFM_STRUCT_INIT)                     */
+  uint32_t abi_version; /* VFM_ABI_VERSION of the caller's build                                                     */
+  int64_t U;            /* users                                                                                     */
+  int64_t P;            /* pool rows of all users                                                                    */
+  int64_t H;            /* history rows of all users (0: none)                                                       */
+  int64_t T;            /* table rows                                                                                */
+  int64_t n_ops;        /* closed form: distinct items of pool and history (row operands); 0 for the sampled form    */
+  int32_t F, d;         /* fields (must be 2), embedding size (1 .. VFM_FOLDIN_MAX_D)                                */
+  int32_t n_rounds;     /* Q, 0 .. VFM_ELICIT_MAX_ROUNDS                                                             */
+  int32_t strategy;     /* VFM_RANK_TOP / VARIANCE / MEAN / RANDOM                                                   */
+  int32_t objective;    /* VFM_OBJ_CLOSED_FORM (VFM_LIK_NORMAL only) or VFM_OBJ_SAMPLED                              */
+  int32_t likelihood;   /* VFM_LIK_NORMAL / VFM_LIK_BERNOULLI                                                        */
+  int32_t flags;        /* 0 or VFM_FLAG_LINK_SOFTPLUS                                                               */
+  int32_t n_steps;      /* Adam updates per round (>= 0)                                                             */
+  int32_t n_samples;    /* sampled objective: draws per iteration, 1 .. VFM_FOLDIN_MAX_SAMPLES                       */
+  int32_t reset;        /* 1: round 0 starts from the prior instead of the users' table rows                         */
+  int32_t write;        /* 1: the users' table rows get the final posterior; 0: no table byte changes                */
+  int32_t lds_rows;     /* -1: as many fold rows per user staged in LDS as fit; >= 0: at most that many (tests)      */
+  float lr, kl_weight;
+  uint64_t seed;        /* Philox key: the strategy's uniforms (seed + q) and the sampled objective's draws          */
+  int64_t t0;           /* sampled: the draw key of round 0's first iteration                                        */
+  const int64_t* users;      /* [U] user ids, ascending                                                              */
+  const int64_t* pool_ptr;   /* [U + 1] offsets of each user's pool rows                                             */
+  const int64_t* pool_items; /* [P] item ids, in the caller's pool order per user                                    */
+  const float* pool_y;       /* [P] the answer each question would receive                                           */
+  const int64_t* hist_ptr;   /* [U + 1] offsets of each user's history rows, or NULL (H = 0)                         */
+  const int64_t* hist_items; /* [H]                                                                                  */
+  const float* hist_y;       /* [H]                                                                                  */
+  const int64_t* op_x;       /* closed form: [n_ops, 2] the distinct items in column 1 (column 0 is ignored)         */
+  const int64_t* pool_op;    /* closed form: [P] operand of each pool row                                            */
+  const int64_t* hist_op;    /* closed form: [H] operand of each history row                                         */
+  float* entity_params;      /* [T, 2d]: read; the rows of `users` are written when `write`                          */
+  float* bias_params;        /* [T, 2]                                                                               */
+  const float* scalars;      /* [3]                                                                                  */
+  int64_t* out_row;          /* [U, Q] the pool row asked (an index into pool_items), or -1                          */
+  float* out_score;          /* [U, Q] its score                                                                     */
+  float* out_loss;           /* [U, Q] the fold-in's out_loss after the round                                        */
+  float* out_theta;          /* NULL, or [U, Q, 2d + 2] = [mu | s | mu_w | s_w] after each round                     */
+  float* out_mean;           /* NULL, or [Q + 1, P]: the logit mean of every pool row as scored before round q; row   */
+  float* out_var;            /*   Q is one more scoring pass after the last fold (both or neither).  Rows already     */
+                             /*   asked keep being written: the caller masks them with out_row.                      */
+  void* workspace;
+  int64_t workspace_bytes;
+} vfm_elicit_t;
+
+/* Workspace of vfm_elicit_f32 in bytes: the asked flags [P] and, for the closed form, the row operands.  Negative on
+ * bad arguments. */
+int64_t vfm_elicit_workspace_bytes(int64_t P, int64_t n_ops, int32_t d, int32_t objective);
+
+/* Run the sessions of p.  A user id outside [0, T) asks nothing (every out_row -1); a pool item outside [0, T) has NaN
+ * moments and is never asked. */
+int vfm_elicit_f32(const vfm_elicit_t* p, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* VFM_ELICIT_H */

@@ -1,0 +1,311 @@
+"""CPU: elicitation sessions (include/vfm_elicit.h) -- the library exports the header's functions and lays out
+vfm_elicit_t as the ctypes mirror does; the argument checks of VFM.elicit / elicitation_curve raise before anything needs
+a GPU; the list helpers keep the pool's order and map rows back to the caller's indices; the fp64 restatement of the
+session (elicit_restatement.py) agrees with a literal loop over its single-round pieces."""
+import ctypes as C
+import math
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import elicit_restatement as R
+
+HDR = os.path.join(ROOT, "include", "vfm_elicit.h")
+
+
+def test_library_exports_every_declared_function():
+    from vae_amd import _lib
+    text = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
+    declared = sorted(set(re.findall(r"\b(vfm_elicit\w*)\s*\(", text)))
+    assert declared == sorted(_lib.ELICIT_EXPORTS)
+    lib = _lib.load()
+    for name in declared:
+        getattr(lib, name)                                  # AttributeError: not exported
+    assert lib.vfm_elicit_workspace_bytes(100, 7, 5, _lib.OBJ_SAMPLED) == 256
+    assert lib.vfm_elicit_workspace_bytes(100, 7, 5, _lib.OBJ_CLOSED_FORM) == 256 + 768 + 256
+    assert lib.vfm_elicit_workspace_bytes(100, 7, 513, _lib.OBJ_SAMPLED) < 0
+
+
+def test_struct_mirror_matches_gcc(tmp_path):
+    from vae_amd import _lib
+    text = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
+    body = re.search(r"typedef struct vfm_elicit_t \{(.*?)\} vfm_elicit_t;", text, re.S).group(1)
+    fields = []
+    for decl in body.split(";"):
+        decl = decl.strip()
+        if decl:
+            names = decl.split(",")
+            fields.append(re.findall(r"\w+", names[0])[-1])
+            fields += [re.findall(r"\w+", n)[-1] for n in names[1:]]
+    assert fields == [n for n, _ in _lib.Elicit._fields_]  # every field, in order
+    src = tmp_path / "layout.c"
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "vfm_elicit.h"', "int main(void) {",
+             'printf("S %zu\\n", sizeof(vfm_elicit_t));']
+    lines += [f'printf("F {n} %zu\\n", offsetof(vfm_elicit_t, {n}));' for n in fields]
+    lines += [f'printf("M {n} %d\\n", (int){n});' for n in ("VFM_ELICIT_MAX_ROUNDS", "VFM_ABI_VERSION")]
+    lines += ["return 0; }"]
+    src.write_text("\n".join(lines))
+    exe = tmp_path / "layout"
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    got = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split("\n")
+    for ln in got:
+        t = ln.split()
+        if not t:
+            continue
+        if t[0] == "S":
+            assert C.sizeof(_lib.Elicit) == int(t[1])
+        elif t[0] == "F":
+            assert getattr(_lib.Elicit, t[1]).offset == int(t[2]), t[1]
+        elif t[1] == "VFM_ELICIT_MAX_ROUNDS":
+            assert _lib.ELICIT_MAX_ROUNDS == int(t[2])
+        else:
+            assert _lib.ABI_VERSION == int(t[2])
+    e = _lib.Elicit()
+    assert (e.struct_size, e.abi_version) == (C.sizeof(_lib.Elicit), _lib.ABI_VERSION)
+    with pytest.raises(AttributeError):
+        e.n_round = 3                                       # a misspelt field
+
+
+def test_library_checks_arguments_before_any_hip_call():
+    from vae_amd import _lib
+    lib = _lib.load()
+    e = _lib.Elicit()
+    e.T, e.F, e.d, e.U, e.n_samples = 10, 3, 4, 1, 1
+    assert lib.vfm_elicit_f32(C.byref(e), None) == -1 and b"two-field" in lib.vfm_last_error()
+    e.F = 2
+    e.struct_size -= 8
+    assert lib.vfm_elicit_f32(C.byref(e), None) == -1 and b"struct_size" in lib.vfm_last_error()
+    e.struct_size += 8
+    e.strategy = 4
+    assert lib.vfm_elicit_f32(C.byref(e), None) == -1 and b"strategy" in lib.vfm_last_error()
+    e.strategy, e.objective, e.likelihood = 1, _lib.OBJ_CLOSED_FORM, _lib.LIK_BERNOULLI
+    assert lib.vfm_elicit_f32(C.byref(e), None) == -1 and b"Normal" in lib.vfm_last_error()
+    e.objective, e.n_rounds = _lib.OBJ_SAMPLED, 5000
+    assert lib.vfm_elicit_f32(C.byref(e), None) == -1 and b"n_rounds" in lib.vfm_last_error()
+    e.n_rounds = 3
+    assert lib.vfm_elicit_f32(C.byref(e), None) == -1 and b"null pointer" in lib.vfm_last_error()
+    e.U = 0
+    assert lib.vfm_elicit_f32(C.byref(e), None) == 0        # nothing to do, nothing launched
+
+
+def _cpu_model(output="reg", sizes=(6, 4)):
+    from vae_amd.model import VFM
+    return VFM(field_sizes=list(sizes), embedding_size=4, output=output, device="cpu")
+
+
+@pytest.mark.parametrize("call", ["elicit", "elicitation_curve"])
+def test_argument_checks_raise_value_error(call):
+    m = _cpu_model()
+    fn = getattr(m, call)
+    pool = torch.tensor([[0, 6], [1, 7], [0, 9]])
+    y = torch.tensor([1.0, 2.0, 3.0])
+    kw = dict(strategies=("variance",)) if call == "elicitation_curve" else {}
+    with pytest.raises(ValueError, match="n_questions"):
+        fn(pool, y, -1, **kw)
+    with pytest.raises(ValueError, match="n_questions"):
+        fn(pool, y, 4097, **kw)
+    with pytest.raises(ValueError, match=r"\[P, 2\]"):
+        fn(torch.tensor([0, 1]), y[:2], 2, **kw)
+    with pytest.raises(ValueError, match="range"):
+        fn(torch.tensor([[6, 7]]), y[:1], 2, **kw)          # an item id in the user column
+    with pytest.raises(ValueError, match="lie in"):
+        fn(torch.tensor([[0, 10]]), y[:1], 2, **kw)         # item id past T
+    with pytest.raises(ValueError, match="frozen"):
+        fn(torch.tensor([[0, 3]]), y[:1], 2, **kw)          # a user id as the item: it would not be frozen
+    with pytest.raises(ValueError, match="one value"):
+        fn(pool, y[:2], 2, **kw)
+    with pytest.raises(ValueError, match="n_samples"):
+        fn(pool, y, 2, objective="sampled", n_samples=5, **kw)
+    with pytest.raises(ValueError, match="objective"):
+        fn(pool, y, 2, objective="exact", **kw)
+    with pytest.raises(ValueError, match="n_steps"):
+        fn(pool, y, 2, n_steps=-1, **kw)
+    with pytest.raises(ValueError, match="lr"):
+        fn(pool, y, 2, lr=-0.1, **kw)
+    with pytest.raises(ValueError, match="history"):
+        fn(pool, y, 2, history=torch.tensor([[0, 6]]), **kw)
+    with pytest.raises(ValueError, match="without a pool row"):
+        fn(pool, y, 2, history=(torch.tensor([[2, 6]]), torch.tensor([1.0])), **kw)
+    with pytest.raises(ValueError, match="one value"):
+        fn(pool, y, 2, history=(torch.tensor([[0, 8]]), torch.tensor([1.0, 2.0])), **kw)
+    if call == "elicit":
+        with pytest.raises(ValueError, match="strategy"):
+            fn(pool, y, 2, strategy="thompson")
+        with pytest.raises(ValueError, match="class"):
+            fn(pool, y, 2, strategy="mean")                 # 'mean' on a 'reg' model
+    else:
+        with pytest.raises(ValueError, match="strategy"):
+            fn(pool, y, 2, strategies=("variance", "thompson"))
+        with pytest.raises(ValueError, match="class"):
+            fn(pool, y, 2)                                  # the default strategies hold 'mean'
+        with pytest.raises(ValueError, match="write"):
+            fn(pool, y, 2, strategies=("variance",), write=True)
+    with pytest.raises(ValueError, match="closed-form"):
+        getattr(_cpu_model("class"), call)(pool, torch.tensor([1.0, 0.0, 1.0]), 2, objective="closed_form", **kw)
+    with pytest.raises(ValueError, match="two-field"):
+        getattr(_cpu_model(sizes=(3, 4, 5)), call)(torch.tensor([[0, 3, 8]]), y[:1], 2, **kw)
+
+
+def test_cpu_model_fails_loudly():
+    from vae_amd._lib import VfmLibraryError
+    m = _cpu_model()
+    pool, y = torch.tensor([[0, 6], [1, 7]]), torch.tensor([1.0, 2.0])
+    with pytest.raises(VfmLibraryError, match="MI355X"):
+        m.elicit(pool, y, 2)
+    with pytest.raises(VfmLibraryError, match="MI355X"):
+        m.elicitation_curve(pool, y, 2, strategies=("variance",))
+
+
+def test_list_helpers_keep_pool_order_and_map_rows_back():
+    from vae_amd import elicit as E
+    g = torch.Generator().manual_seed(3)
+    users = torch.tensor([5, 2, 9, 2, 5, 5, 0, 9, 2, 5])
+    pool = torch.stack([users, 20 + torch.randperm(10, generator=g)], 1)
+    order, us, ptr = E.pool_lists(pool)
+    assert us.tolist() == [0, 2, 5, 9] and ptr.tolist() == [0, 1, 4, 8, 10]
+    for i, u in enumerate(us.tolist()):
+        seg = order[ptr[i]:ptr[i + 1]].tolist()
+        assert seg == [r for r in range(10) if int(users[r]) == u]       # the caller's order kept within a user
+    # sorted-pool positions back to caller indices, -1 kept
+    out_row = torch.tensor([[0, -1, -1], [3, 1, 2], [7, 4, 5], [9, 8, -1]])
+    rows = E.rows_to_caller(out_row, order)
+    assert rows.tolist() == [[6, -1, -1], [8, 1, 3], [9, 0, 4], [7, 2, -1]]
+    assert all(int(pool[r, 0]) == u for u, rr in zip(us.tolist(), rows.tolist()) for r in rr if r >= 0)
+    v = torch.arange(20.0).reshape(2, 10)
+    back = E.to_caller_order(v, order)
+    assert torch.equal(back[:, order], v)
+    when = E.asked_round(rows, 10)
+    assert when.tolist() == [1, 1, 1, 2, 2, 3, 0, 0, 0, 0]               # 3 = never asked (Q)
+    hx = torch.tensor([[5, 30], [0, 31], [5, 32], [9, 33]])
+    horder, hptr = E.history_lists(us, hx)
+    assert hptr.tolist() == [0, 1, 1, 3, 4] and horder.tolist() == [1, 0, 2, 3]
+    # a shuffled pool with the same rows: each user's asked row maps to the same (user, item) pair
+    perm = torch.randperm(10, generator=g)
+    o2, u2, p2 = E.pool_lists(pool[perm])
+    assert torch.equal(u2, us) and torch.equal(p2, ptr)
+
+
+def test_metric_helpers():
+    from vae_amd import elicit as E
+    y = torch.tensor([1.0, 0.0, 1.0, 0.0, 1.0])
+    s = torch.tensor([0.9, 0.1, 0.4, 0.4, 0.8])
+    assert abs(E.auc(s, y) - (2 + 2 + 1 + 0.5) / 6) < 1e-12              # the tie counts 1/2
+    assert math.isnan(E.auc(s, torch.ones(5)))
+    mean, var = torch.tensor([1.0, 2.0, float("nan")]), torch.tensor([0.5, 0.5, 0.5])
+    assert abs(E.metric("reg", mean, var, torch.tensor([2.0, 2.0, 9.0])) - math.sqrt(0.5)) < 1e-12
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the fp64 restatement: the session against a literal loop over the single-round pieces
+# ---------------------------------------------------------------------------------------------------------------------
+def _tables(T, d, seed):
+    g = np.random.default_rng(seed)
+    return g.normal(size=(T, 2 * d)) * 0.6, g.normal(size=(T, 2)) * 0.5, np.array([1.3, 0.2, 0.4])
+
+
+def _uniform(seed):
+    return lambda q, item: float(np.random.default_rng([seed, q, item]).random())
+
+
+def _eps(T, d, seed):
+    def f(t):
+        g = np.random.default_rng([seed, t])
+        return g.normal(size=(T, d)), g.normal(size=T), g.normal()
+    return f
+
+
+@pytest.mark.parametrize("strategy,output,objective,kind,reset,n_hist", [
+    ("variance", "reg", "closed_form", "abs", False, 3), ("top", "reg", "closed_form", "softplus", True, 0),
+    ("random", "reg", "sampled", "abs", False, 2), ("mean", "class", "sampled", "softplus", False, 0),
+    ("variance", "class", "sampled", "abs", True, 4)])
+def test_session_equals_loop_over_single_rounds(strategy, output, objective, kind, reset, n_hist):
+    d, N, M, P, Q = 3, 4, 12, 5, 7                                       # Q > P: the pool runs out
+    ent, bia, scal = _tables(N + M, d, 7)
+    g = np.random.default_rng(1)
+    u = 2
+    items = N + g.permutation(M)
+    pool_items, hist_items = items[:P], items[P:P + n_hist]
+    yv = (lambda n: g.normal(size=n) + 1.0) if output == "reg" else (lambda n: (g.random(n) < 0.5).astype(np.float64))
+    pool_y, hist_y = yv(P), yv(n_hist)
+    kw = dict(kind=kind, output=output, objective=objective, n_steps=6, lr=0.05, klw=0.8)
+    s = R.session(u, pool_items, pool_y, Q, strategy, ent, bia, scal, hist_items=hist_items, hist_y=hist_y, reset=reset,
+                  eps=_eps(N + M, d, 5), t0=3, uniform=_uniform(9), **kw)
+    theta = R.prior_theta(d, kind) if reset else R.table_theta(ent, bia, u)
+    asked = np.zeros(P, dtype=bool)
+    f_items, f_y = list(hist_items), list(hist_y)
+    for q in range(Q):
+        mean, var = R.moments(theta, ent, bia, scal, pool_items, kind)
+        np.testing.assert_allclose(s["mean"][q], mean, rtol=1e-12)
+        np.testing.assert_allclose(s["var"][q], var, rtol=1e-12)
+        best, _ = R.choose(R.score(strategy, mean, var, q, pool_items, _uniform(9)), asked)
+        assert s["rows"][q] == best
+        if best < 0:
+            assert q >= P and math.isnan(s["loss"][q]) and math.isnan(s["score"][q])
+            continue
+        asked[best] = True
+        f_items.append(pool_items[best])
+        f_y.append(pool_y[best])
+        theta, loss = R.fold(theta, u, f_items, f_y, ent, bia, scal, kind, output, objective, 6, 0.05, 0.8,
+                             _eps(N + M, d, 5), 3 + q * 7)
+        assert abs(s["loss"][q] - loss) <= 1e-10 * abs(loss)
+        for a, b in zip(s["theta"][q], theta):
+            np.testing.assert_allclose(a, b, rtol=1e-9, atol=1e-12)
+    assert sorted(r for r in s["rows"] if r >= 0) == list(range(P)) and s["rows"][P:] == [-1] * (Q - P)
+
+
+def test_restatement_gradients_match_finite_differences():
+    d, N, M = 3, 2, 6
+    ent, bia, scal = _tables(N + M, d, 2)
+    items, y = np.array([3, 5, 4]), np.array([1.0, 0.0, 1.0])
+    for objective, output in (("closed_form", "reg"), ("sampled", "class"), ("sampled", "reg")):
+        th = R.table_theta(ent, bia, 1)
+        f = lambda t: R.fold(t, 1, items, y, ent, bia, scal, "softplus", output, objective, 0, 0.0, 0.7,
+                             _eps(N + M, d, 1), 2)[1]
+        # one Adam step of size lr moves every parameter by -lr sign(g): recover the signs from finite differences
+        stepped, _ = R.fold(th, 1, items, y, ent, bia, scal, "softplus", output, objective, 1, 1e-3, 0.7,
+                            _eps(N + M, d, 1), 2)
+        flat = lambda t: np.concatenate([t[0], t[1], [t[2], t[3]]])
+        p0 = flat(th)
+        for k in range(2 * d + 2):
+            e = np.zeros(2 * d + 2)
+            e[k] = 1e-6
+            unflat = lambda p: (p[:d], p[d:2 * d], p[2 * d], p[2 * d + 1])
+            fd = (f(unflat(p0 + e)) - f(unflat(p0 - e))) / 2e-6
+            assert np.sign(fd) == -np.sign(flat(stepped)[k] - p0[k]), (objective, k)
+
+
+def test_planted_generator_is_well_conditioned_in_fp32():
+    """The inputs of test_gpu_elicit.py::test_against_the_fp64_restatement_on_a_planted_model (its generator): at lr = 0.01 a numpy fp32 transcription of the folds stays 10x inside the 1e-4 tolerance of the fp64
+    thetas, at lr = 0.05 fp32 rounding alone breaks it -- the reason the GPU test runs at lr = 0.01."""
+    N, M, d, Q, n_steps = 32, 300, 8, 8, 20
+    g = torch.Generator().manual_seed(2)
+    mu = torch.randn(N + M, d, generator=g)
+    ent = torch.cat([mu, torch.full((N + M, d), 0.05)], 1)
+    bia = torch.stack([torch.randn(N + M, generator=g) * 0.1, torch.full((N + M,), 0.05)], 1)
+    pool = torch.stack([torch.arange(N).repeat_interleave(40),
+                        torch.cat([N + torch.randperm(M, generator=g)[:40] for _ in range(N)])], 1)
+    truth = (mu[pool[:, 0]] * mu[pool[:, 1]]).sum(1) + bia[pool[:, 0], 0] + bia[pool[:, 1], 0]
+    y_pool = truth + 0.5 * torch.randn(pool.shape[0], generator=g)
+    E, B = ent.numpy().astype(np.float64), bia.numpy().astype(np.float64)
+    S = np.array([4.0, 0.0, 0.05], dtype=np.float32).astype(np.float64)
+    worst = {0.01: 0.0, 0.05: 0.0}
+    for lr in worst:
+        for u in range(N):
+            sel = (pool[:, 0] == u).nonzero().reshape(-1)
+            items, ys = pool[sel, 1].numpy(), y_pool[sel].numpy()
+            s = R.session(u, items, ys, Q, "variance", E, B, S, n_steps=n_steps, lr=lr, reset=True)
+            assert min(s["gap"]) > 1e-5
+            for th, t32 in zip(s["theta"], R.closed_form_thetas_fp32(s["rows"], items, ys, E, B, S, n_steps, lr)):
+                for a, b in ((t32[0], th[0]), (t32[1], th[1]), (t32[2], np.array(th[2:]))):
+                    worst[lr] = max(worst[lr], float(np.abs(a - b).max() / np.abs(b).max()))
+    assert worst[0.01] < 1e-5, worst
+    assert worst[0.05] > 1e-4, worst

@@ -64,7 +64,37 @@ class Pipe(_Strict, _gen.Pipe):
 
 
 StepConsts, DevStep = _gen.StepConsts, _gen.DevStep
-for _c in (Problem, Index, Pipe):
+
+# ---- elicitation sessions (include/vfm_elicit.h): constants and the mirror of vfm_elicit_t, field for field
+ELICIT_MAX_ROUNDS = 4096
+ELICIT_EXPORTS = ("vfm_elicit_f32", "vfm_elicit_workspace_bytes")
+
+
+class Elicit(_Strict, C.Structure):
+    """`vfm_elicit_t` (tests/test_elicit_cpu.py checks the layout against gcc's)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("abi_version", C.c_uint32),
+        ("U", C.c_int64), ("P", C.c_int64), ("H", C.c_int64), ("T", C.c_int64), ("n_ops", C.c_int64),
+        ("F", C.c_int32), ("d", C.c_int32), ("n_rounds", C.c_int32), ("strategy", C.c_int32),
+        ("objective", C.c_int32), ("likelihood", C.c_int32), ("flags", C.c_int32), ("n_steps", C.c_int32),
+        ("n_samples", C.c_int32), ("reset", C.c_int32), ("write", C.c_int32), ("lds_rows", C.c_int32),
+        ("lr", C.c_float), ("kl_weight", C.c_float),
+        ("seed", C.c_uint64), ("t0", C.c_int64),
+        ("users", C.c_void_p), ("pool_ptr", C.c_void_p), ("pool_items", C.c_void_p), ("pool_y", C.c_void_p),
+        ("hist_ptr", C.c_void_p), ("hist_items", C.c_void_p), ("hist_y", C.c_void_p),
+        ("op_x", C.c_void_p), ("pool_op", C.c_void_p), ("hist_op", C.c_void_p),
+        ("entity_params", C.c_void_p), ("bias_params", C.c_void_p), ("scalars", C.c_void_p),
+        ("out_row", C.c_void_p), ("out_score", C.c_void_p), ("out_loss", C.c_void_p), ("out_theta", C.c_void_p),
+        ("out_mean", C.c_void_p), ("out_var", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size, self.abi_version = C.sizeof(type(self)), ABI_VERSION      # (VFM_STRUCT_INIT)
+
+
+for _c in (Problem, Index, Pipe, Elicit):
     _c._names = frozenset(n for n, _ in _c._fields_)
 
 
@@ -134,6 +164,10 @@ def load():
     lib.vfm_union_rows.argtypes = [i64] + [vp] * 7
     lib.vfm_variant_workspace_elems.argtypes = [i64, i32, i32]
     lib.vfm_variant_workspace_elems.restype = i64
+    lib.vfm_elicit_f32.argtypes = [C.POINTER(Elicit), vp]
+    lib.vfm_elicit_f32.restype = C.c_int
+    lib.vfm_elicit_workspace_bytes.argtypes = [i64, i64, i32, i32]
+    lib.vfm_elicit_workspace_bytes.restype = i64
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name != "vfm_last_error":

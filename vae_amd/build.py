@@ -61,12 +61,18 @@ _UNITS = [("vfm_abi.hip", "", _EXACT), ("vfm_index.hip", "", []), ("vfm_variants
           ("csrc_rank/vfm_rank_field.hip", "", ["-ffp-contract=off"]),
           # fold-in (include/vfm_foldin.h): outside csrc/ for the same reason; it includes csrc/'s Philox stream and link
           # helpers, so its draws and links are those of the training kernels
-          ("csrc_rank/vfm_foldin.hip", "", _EXACT)]
+          ("csrc_rank/vfm_foldin.hip", "", _EXACT),
+          # elicitation sessions (include/vfm_elicit.h): the fold-in's body (csrc_rank/vfm_foldin_body.hpp) and the pair
+          # scores of vfm_rank_tile.hpp in one kernel.  The fold-in's flag: its body is defined under contraction `on`;
+          # the pair functions pin `off` with a pragma of their own, so the scores stay those of vfm_rank.hip bit for bit
+          ("csrc_rank/vfm_elicit.hip", "", _EXACT)]
 RANK_DIR = os.path.join(HERE, "csrc_rank")
 RANK_HDR = os.path.join(ROOT, "include", "vfm_rank.h")
 RANK_OPS = os.path.join(RANK_DIR, "vfm_rank_ops.cpp")
 FOLDIN_HDR = os.path.join(ROOT, "include", "vfm_foldin.h")
 FOLDIN_OPS = os.path.join(RANK_DIR, "vfm_foldin_ops.cpp")
+ELICIT_HDR = os.path.join(ROOT, "include", "vfm_elicit.h")
+ELICIT_OPS = os.path.join(RANK_DIR, "vfm_elicit_ops.cpp")
 
 
 def _unit_path(src):
@@ -79,7 +85,7 @@ def _unit_obj(objdir, src, suffix):
 
 
 def _rank_sources():
-    return [RANK_HDR, FOLDIN_HDR] + sorted(os.path.join(RANK_DIR, f) for f in os.listdir(RANK_DIR) if f.endswith((".hip", ".hpp")))
+    return [RANK_HDR, FOLDIN_HDR, ELICIT_HDR] + sorted(os.path.join(RANK_DIR, f) for f in os.listdir(RANK_DIR) if f.endswith((".hip", ".hpp")))
 
 
 def build_hip_library(force=False, verbose=False):
@@ -96,7 +102,7 @@ def build_hip_library(force=False, verbose=False):
     common = [HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-fvisibility-inlines-hidden",
               "-I" + os.path.join(ROOT, "include"), "-I" + csrc]
     jobs, objs = [], []
-    shared = [hdr, RANK_HDR, FOLDIN_HDR, os.path.abspath(__file__)] + [f for f in parts if f.endswith(".hpp")]      # what every unit depends on
+    shared = [hdr, RANK_HDR, FOLDIN_HDR, ELICIT_HDR, os.path.abspath(__file__)] + [f for f in parts if f.endswith(".hpp")]      # what every unit depends on
     for src, suffix, extra in _UNITS:
         obj = _unit_obj(objdir, src, suffix)
         objs.append(obj)
@@ -125,14 +131,14 @@ def build_hip_library(force=False, verbose=False):
 
 def build_torch_ops(force=False, verbose=False):
     """libvfm_torch_ops.so: TORCH_LIBRARY shim `torch.ops.vfm_hip.*` over the C ABI (host C++ only); the ranking and
-    fold-in ops are TORCH_LIBRARY_FRAGMENTs of their own sources (csrc_rank/vfm_rank_ops.cpp, vfm_foldin_ops.cpp) linked
+    fold-in and session ops are TORCH_LIBRARY_FRAGMENTs of their own sources (csrc_rank/vfm_{rank,foldin,elicit}_ops.cpp) linked
     into the same shim."""
     import torch
     src = os.path.join(HERE, "csrc", "vfm_torch_ops.cpp")
     hdr = os.path.join(ROOT, "include", "vfm_hip.h")
     out = os.path.join(HERE, "libvfm_torch_ops.so")
     lib = os.path.join(HERE, "libvfm_hip.so")
-    if not force and not _stale(out, [src, hdr, lib, RANK_OPS, RANK_HDR, FOLDIN_OPS, FOLDIN_HDR]):
+    if not force and not _stale(out, [src, hdr, lib, RANK_OPS, RANK_HDR, FOLDIN_OPS, FOLDIN_HDR, ELICIT_OPS, ELICIT_HDR]):
         return out
     ti = os.path.dirname(torch.__file__)
     rocm = os.environ.get("ROCM_HOME", "/opt/rocm")
@@ -140,7 +146,7 @@ def build_torch_ops(force=False, verbose=False):
            "-D_GLIBCXX_USE_CXX11_ABI=%d" % int(torch._C._GLIBCXX_USE_CXX11_ABI),
            "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ti, "include"),
            "-I" + os.path.join(ti, "include", "torch", "csrc", "api", "include"),
-           "-I" + os.path.join(rocm, "include"), "-o", out, src, RANK_OPS, FOLDIN_OPS,
+           "-I" + os.path.join(rocm, "include"), "-o", out, src, RANK_OPS, FOLDIN_OPS, ELICIT_OPS,
            "-L" + os.path.join(ti, "lib"), "-ltorch", "-ltorch_cpu", "-lc10", "-lc10_hip", "-ltorch_hip",
            "-L" + HERE, "-lvfm_hip", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(ti, "lib")]
     if verbose:
@@ -167,7 +173,7 @@ def build_sanitized(force=False, verbose=False):
     os.makedirs(outdir, exist_ok=True)
     stamp = os.path.join(outdir, "digest.txt")
     import hashlib
-    digest = sources_digest() + hashlib.sha1(b"".join(open(f, "rb").read() for f in _rank_sources() + [RANK_OPS, FOLDIN_OPS])).hexdigest()
+    digest = sources_digest() + hashlib.sha1(b"".join(open(f, "rb").read() for f in _rank_sources() + [RANK_OPS, FOLDIN_OPS, ELICIT_OPS])).hexdigest()
     out = os.path.join(outdir, "libvfm_hip.so")
     out_ops = os.path.join(outdir, "libvfm_torch_ops.so")
     if (not force and os.path.exists(out) and os.path.exists(out_ops) and os.path.exists(stamp)
@@ -200,7 +206,7 @@ def build_sanitized(force=False, verbose=False):
            "-D_GLIBCXX_USE_CXX11_ABI=%d" % int(torch._C._GLIBCXX_USE_CXX11_ABI),
            "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ti, "include"),
            "-I" + os.path.join(ti, "include", "torch", "csrc", "api", "include"),
-           "-I" + os.path.join(rocm, "include"), "-o", out_ops, os.path.join(csrc, "vfm_torch_ops.cpp"), RANK_OPS, FOLDIN_OPS,
+           "-I" + os.path.join(rocm, "include"), "-o", out_ops, os.path.join(csrc, "vfm_torch_ops.cpp"), RANK_OPS, FOLDIN_OPS, ELICIT_OPS,
            "-L" + os.path.join(ti, "lib"), "-ltorch", "-ltorch_cpu", "-lc10", "-lc10_hip", "-ltorch_hip",
            "-L" + outdir, "-lvfm_hip", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(ti, "lib")]
     if verbose:

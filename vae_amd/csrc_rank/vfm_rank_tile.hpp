@@ -1,7 +1,9 @@
 // vfm_rank_tile.hpp -- what the catalog ranking (vfm_rank.hip: k_rank) and the held-out evaluation
 // (vfm_rank_eval.hip: k_rank_eval) share: the pair score functions, the operand packing (k_rank_prep) and the 256-user x
 // 64-item MFMA score tile.  Both units are compiled with -ffp-contract=off, so a pair's score is one k-ordered fp32 fma
-// chain whichever unit, tile, split or grid forms it, and equals the k_moments score of the pair bit for bit.
+// chain whichever unit, tile, split or grid forms it, and equals the k_moments score of the pair bit for bit.  The pair
+// functions pin that mode themselves (#pragma clang fp contract(off)): the elicitation session (vfm_elicit.hip) inlines
+// them next to the fold-in's arithmetic, which is defined under contraction `on`.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -30,6 +32,7 @@ __device__ __forceinline__ float link_of(float s, bool softplus) {
 }
 
 __device__ __forceinline__ float score_of(int strat, float m, float v) {
+#pragma clang fp contract(off)
   if (strat == VFM_RANK_TOP) return m;
   if (strat == VFM_RANK_VARIANCE) return v;
   return -fabsf(m) / sqrtf(1.0f + PI_OVER_8 * v);
@@ -60,6 +63,7 @@ __device__ __forceinline__ float philox_uniform(uint64_t seed, int64_t user, int
 //   variance part: user [mu_u^2 | sigma_u^2]           item [sigma_i^2 | mu_i^2 + sigma_i^2]
 __device__ __forceinline__ float op_mean(const float* row, int k) { return row[k]; }
 __device__ __forceinline__ float op_var(const float* row, int kb, int d, bool item, bool sp) {
+#pragma clang fp contract(off)
   const int k = kb < d ? kb : kb - d;
   const float m = row[k], s = link_of(row[d + k], sp);
   if (!item) return kb < d ? m * m : s * s;
@@ -69,6 +73,7 @@ __device__ __forceinline__ float op_var(const float* row, int kb, int d, bool it
 // Closed-form moments of the pair (u, i): the same fp32 chains, in the same k order, as the MFMA accumulation of the tile
 __device__ void pair_moments(const float* eu, const float* ei, const float* bu, const float* bi, float m0, float sg0,
                              int d, bool sp, float& mean, float& var) {
+#pragma clang fp contract(off)
   float am = 0.f, av = 0.f;
   for (int k = 0; k < d; ++k) am = fmaf(op_mean(eu, k), op_mean(ei, k), am);
   for (int kb = 0; kb < 2 * d; ++kb) av = fmaf(op_var(eu, kb, d, false, sp), op_var(ei, kb, d, true, sp), av);

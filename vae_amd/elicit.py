@@ -1,0 +1,195 @@
+"""Elicitation sessions: ask, fold in and ask again, every round of every user in one launch (include/vfm_elicit.h).
+
+The reference's interactive experiment (vfm.py:1236-1251) asks every test user a number of questions: the next question
+is picked by a strategy from the user's current posterior, the answer is taken, and the user's parameters alone are
+refitted.  `VFM.select_next_questions` and `VFM.fold_in` are the two halves; this module runs the whole loop for all
+users inside one kernel ("Elicitation sessions").  It checks the arguments, builds the per-user lists of
+the pool and of the history once (stable sorts: the caller's order is kept within a user) and maps the results back to
+the caller's pool order; the sessions themselves are one HIP launch (plus one operand pass for the closed form)
+through torch.ops.vfm_hip.elicit.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+
+from . import _lib, foldin, ops
+from .rank import _seed64, strategy_code
+
+MAX_ROUNDS = _lib.ELICIT_MAX_ROUNDS
+
+
+def check_args(model, pool, y_pool, n_questions, strategy, history, n_steps, lr, objective, n_samples, kl_weight):
+    """Validate a session call (no GPU needed).  Returns (pool [P, 2] int64, y_pool [P] fp32, hist_x [H, 2] or None,
+    hist_y [H] or None, objective name, strategy code) on the model's device."""
+    code = strategy_code(strategy)
+    if model.F != 2:
+        raise ValueError("elicit: two-field models only")
+    if strategy == "mean" and model.output != "class":
+        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
+    if isinstance(n_questions, bool) or not isinstance(n_questions, int) or not 0 <= n_questions <= MAX_ROUNDS:
+        raise ValueError(f"n_questions must be an int in [0, {MAX_ROUNDS}]")
+    pool = torch.as_tensor(pool)
+    if pool.dim() != 2 or pool.shape[1] != 2:
+        raise ValueError("pool must be an [P, 2] tensor of (user, item) rows")
+    x, y, objective = foldin.check_args(model, pool, y_pool, 0, objective, n_samples, n_steps, lr, kl_weight)
+    hx = hy = None
+    if history is not None:
+        if not isinstance(history, (tuple, list)) or len(history) != 2:
+            raise ValueError("history must be a pair (X [H, 2], y [H])")
+        hx = torch.as_tensor(history[0])
+        if hx.dim() != 2 or hx.shape[1] != 2:
+            raise ValueError("history X must be an [H, 2] tensor of (user, item) rows")
+        hx, hy, _ = foldin.check_args(model, hx, history[1], 0, objective, n_samples, n_steps, lr, kl_weight)
+        if hx.shape[0] and not bool(torch.isin(hx[:, 0], x[:, 0]).all()):
+            raise ValueError("history holds users without a pool row")
+    return x, y, hx, hy, objective, code
+
+
+def pool_lists(pool):
+    """Stable sort of the pool rows by user: (order [P] -- position in the sorted pool -> caller's row index --,
+    users [U] ascending, ptr [U + 1])."""
+    order = torch.sort(pool[:, 0], stable=True).indices
+    users, counts = torch.unique_consecutive(pool[order, 0], return_counts=True)
+    ptr = torch.zeros(users.numel() + 1, dtype=torch.int64, device=pool.device)
+    torch.cumsum(counts, 0, out=ptr[1:])
+    return order, users.contiguous(), ptr
+
+
+def history_lists(users, hx):
+    """The history rows grouped by the session users (stable: given order kept per user): (order [H], ptr [U + 1])."""
+    order = torch.sort(hx[:, 0], stable=True).indices
+    pos = torch.searchsorted(users, hx[order, 0].contiguous())
+    counts = torch.bincount(pos, minlength=users.numel())
+    ptr = torch.zeros(users.numel() + 1, dtype=torch.int64, device=hx.device)
+    torch.cumsum(counts, 0, out=ptr[1:])
+    return order, ptr
+
+
+def rows_to_caller(out_row, order):
+    """out_row [U, Q] (positions in the sorted pool, -1 padded) as indices into the caller's pool."""
+    if order.numel() == 0:
+        return out_row.clone()
+    return torch.where(out_row >= 0, order[out_row.clamp(min=0)], out_row)
+
+
+def to_caller_order(v, order):
+    """v [.., P] over the sorted pool -> the same over the caller's pool."""
+    out = torch.empty_like(v)
+    out[..., order] = v
+    return out
+
+
+def run(model, pool, y_pool, n_questions, strategy="variance", history=None, n_steps=200, lr=0.05, objective=None,
+        n_samples=1, seed=0, kl_weight=1.0, reset=False, write=False, return_moments=False, return_theta=False, t0=0,
+        lds_rows=-1):
+    """The sessions of every user of the pool (VFM.elicit documents the arguments and the result)."""
+    x, y, hx, hy, objective, code = check_args(model, pool, y_pool, n_questions, strategy, history, n_steps, lr,
+                                               objective, n_samples, kl_weight)
+    ops._need_cuda(model._flat, "the model's parameters")
+    dev, d, Q = model.device, model.d, int(n_questions)
+    order, users, ptr = pool_lists(x)
+    items, ys = x[order, 1].contiguous(), y[order].contiguous()
+    U, P = users.numel(), items.numel()
+    hptr = hitems = hys = None
+    if hx is not None and hx.shape[0]:
+        horder, hptr = history_lists(users, hx)
+        hitems, hys = hx[horder, 1].contiguous(), hy[horder].contiguous()
+    f32 = dict(dtype=torch.float32, device=dev)
+    out_row = torch.full((U, Q), -1, dtype=torch.int64, device=dev)
+    score, loss = torch.full((U, Q), float("nan"), **f32), torch.full((U, Q), float("nan"), **f32)
+    theta = torch.empty(U, Q, 2 * d + 2, **f32) if return_theta else None
+    mean = torch.empty(Q + 1, P, **f32) if return_moments else None
+    var = torch.empty(Q + 1, P, **f32) if return_moments else None
+    res = {"users": users}
+    if U:
+        o = _lib.ops()
+        obj = foldin.OBJECTIVES[objective]
+        op_x = pool_op = hist_op = None
+        n_ops = 0
+        if objective == "closed_form":     # one operand per DISTINCT item of pool and history: the items are frozen
+            allit = items if hitems is None else torch.cat([items, hitems])
+            uq, inv = torch.unique(allit, return_inverse=True)
+            op_x = torch.zeros(uq.numel(), 2, dtype=torch.int64, device=dev)
+            op_x[:, 1] = uq
+            pool_op = inv[:P].contiguous()
+            hist_op = inv[P:].contiguous() if hitems is not None else None
+            n_ops = uq.numel()
+        ws = torch.empty(max(o.elicit_workspace_bytes(P, n_ops, d, obj), 1), dtype=torch.uint8, device=dev)
+        model._fresh_params()
+        ent, bia, scal = model._views(model._flat)
+        lik = _lib.LIK_NORMAL if model.output == "reg" else _lib.LIK_BERNOULLI
+        o.elicit(users, ptr, items, ys, hptr, hitems, hys, op_x, pool_op, hist_op, ent, bia, scal, ws, out_row, score,
+                 loss, theta, mean, var, Q, code, obj, lik, ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0,
+                 int(n_steps), int(n_samples), int(bool(reset)), int(bool(write)), int(lds_rows), float(lr),
+                 float(kl_weight), _seed64(seed), int(t0))
+        if write:
+            model.params_changed()      # (rows written outside the step kernels: derived caches are stale)
+    res.update(rows=rows_to_caller(out_row, order), score=score, loss=loss)
+    if return_theta:
+        res["theta"] = theta
+    if return_moments:
+        res["logit_mean"], res["logit_var"] = to_caller_order(mean, order), to_caller_order(var, order)
+    return res
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the curve of quality against questions asked (torch; any device)
+# ---------------------------------------------------------------------------------------------------------------------
+def asked_round(rows, P):
+    """[P] the round in which each pool row was asked (rows [U, Q], -1 padded); Q for a row never asked."""
+    U, Q = rows.shape
+    out = torch.full((P,), Q, dtype=torch.int64, device=rows.device)
+    q = torch.arange(Q, device=rows.device).expand(U, Q)
+    hit = rows >= 0
+    out[rows[hit]] = q[hit]
+    return out
+
+
+def auc(score, y):
+    """Area under the ROC curve of `score` for the labels y in {0, 1} (ties count 1/2); NaN with one class only."""
+    pos = y > 0.5
+    n1 = int(pos.sum())
+    n0 = int(y.numel()) - n1
+    if n1 == 0 or n0 == 0:
+        return float("nan")
+    _, inv, cnt = torch.unique(score.to(torch.float64), return_inverse=True, return_counts=True)
+    cum = torch.cumsum(cnt, 0).to(torch.float64)
+    rank = (cum - (cnt.to(torch.float64) - 1.0) / 2.0)[inv]              # 1-based, ties averaged
+    return float((rank[pos].sum() - n1 * (n1 + 1) / 2.0) / (float(n1) * float(n0)))
+
+
+def metric(output, mean, var, y):
+    """The reference's test metric from closed-form moments: 'class' the AUC of the probit mean probability
+    sigmoid(mean / sqrt(1 + pi var / 8)), 'reg' the RMSE of the mean.  Rows with NaN moments are left out."""
+    ok = ~(torch.isnan(mean) | torch.isnan(var))
+    mean, var, y = mean[ok].to(torch.float64), var[ok].to(torch.float64), y[ok].to(torch.float64)
+    if mean.numel() == 0:
+        return float("nan")
+    if output == "reg":
+        return float(torch.sqrt(torch.mean((mean - y) ** 2)))
+    return auc(torch.sigmoid(mean / torch.sqrt(1.0 + math.pi / 8.0 * var)), y)
+
+
+def curve(model, pool, y_pool, n_questions, strategies=("mean", "random", "variance"), **kw):
+    """VFM.elicitation_curve: {strategy: [metric before round 0, .., metric after round Q - 1]} on the rows still
+    unasked, plus "n_unasked": {strategy: [Q + 1] ints}.  The model is left untouched."""
+    for key in ("write", "return_moments", "return_theta"):
+        if key in kw:
+            raise ValueError(f"elicitation_curve sets {key} itself")
+    strategies = list(strategies)
+    for s in strategies:
+        strategy_code(s)
+    out, left = {}, {}
+    for s in strategies:
+        r = run(model, pool, y_pool, n_questions, strategy=s, write=False, return_moments=True, **kw)
+        y = torch.as_tensor(y_pool).to(model.device, torch.float32).reshape(-1)
+        when = asked_round(r["rows"], y.numel())
+        out[s], left[s] = [], []
+        for q in range(int(n_questions) + 1):
+            keep = when >= q
+            out[s].append(metric(model.output, r["logit_mean"][q][keep], r["logit_var"][q][keep], y[keep]))
+            left[s].append(int(keep.sum()))
+    out["n_unasked"] = left
+    return out

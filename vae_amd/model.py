@@ -1150,6 +1150,44 @@ class VFM(nn.Module):
         d = self.d
         return loss, {"entities": ents, "entity": g[:, :2 * d], "bias": g[:, 2 * d:]}
 
+    # ------------------------------------------------------------------ elicitation sessions (vae_amd/elicit.py)
+    @torch.no_grad()
+    def elicit(self, pool, y_pool, n_questions: int, strategy: str = "variance", history=None, n_steps: int = 200,
+               lr: float = 0.05, objective: Optional[str] = None, n_samples: int = 1, seed: int = 0,
+               kl_weight: float = 1.0, reset: bool = False, write: bool = False, return_moments: bool = False,
+               return_theta: bool = False):
+        """An adaptive questionnaire for every user of the pool in one launch (two-field model; include/vfm_elicit.h,
+        DESIGN.md §4): n_questions rounds of select_next_questions(n=1) followed by fold_in of the answering user,
+        bitwise what that loop computes.
+
+        pool: [P, 2] (user, item) rows in any order, y_pool [P] the answer each question would receive; history:
+        (X [H, 2], y [H]) answers already given (users of the pool only).  Per user and round q: every row of the user
+        not asked yet is scored from the user's CURRENT posterior (the scores of select_next_questions with seed + q),
+        the best is asked (ties: the lower pool row), and the user's posterior is refitted on the history followed by
+        the rows asked so far -- fold_in's objective, optimiser and options (n_steps, lr, objective, n_samples,
+        kl_weight; the sampled objective draws with key q (n_steps + 1) + iteration).  reset=True starts round 0 from
+        the prior instead of the users' rows.  write=False leaves the model untouched, bit for bit; write=True stores
+        the final posteriors in the users' rows (nothing else changes).
+        Returns dict(users [U] ascending, rows [U, Q] int64 indices into `pool` in the order asked (-1 once a user has
+        nothing left to ask), score [U, Q] the asked rows' scores, loss [U, Q] fold_in's loss after each round; with
+        return_theta: theta [U, Q, 2d + 2] = [mu | s | mu_w | s_w] after each round; with return_moments: logit_mean,
+        logit_var [Q + 1, P] in the caller's pool order: every pool row's closed-form moments as scored before round q
+        (row Q: after the last round; rows already asked are still filled in))."""
+        from . import elicit
+        return elicit.run(self, pool, y_pool, n_questions, strategy, history, n_steps, lr, objective, n_samples, seed,
+                          kl_weight, reset, write, return_moments, return_theta)
+
+    @torch.no_grad()
+    def elicitation_curve(self, pool, y_pool, n_questions: int, strategies=("mean", "random", "variance"), **kw):
+        """Quality against questions asked, the curve the reference's interactive experiment prints: for each strategy
+        one elicit(write=False) session over the pool and, per round q = 0 .. n_questions, the test metric on the pool
+        rows still unasked before round q -- 'class': the AUC of the probit mean probability sigmoid(mean / sqrt(1 +
+        pi var / 8)); 'reg': the RMSE of the mean -- from the closed-form moments under the users' posteriors of that
+        round.  kw: elicit's other options (history, n_steps, lr, objective, n_samples, seed, kl_weight, reset).
+        Returns {strategy: [Q + 1 floats], "n_unasked": {strategy: [Q + 1 ints]}}.  The model is left untouched."""
+        from . import elicit
+        return elicit.curve(self, pool, y_pool, n_questions, strategies, **kw)
+
     @torch.no_grad()
     def evaluate(self, X_test, y_test):
         """Test metrics of vfm-torch.py:410-422."""
