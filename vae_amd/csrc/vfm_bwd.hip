@@ -31,17 +31,19 @@ constexpr int LINK = VFM_LINK;
 
 template <int LPE, int CPL, int VEC, int EPS, int ADAM, int STAGE = STAGE_FULL>
 int launch_bwd_t(KArgs& a, const BwdArgs& b, const AdamArgs& ad, hipStream_t st) {
-  constexpr int GPB = BLOCK / LPE;
   const int per_cu = env_int("VFM_BWD_BLOCKS_PER_CU", 8);
-  int64_t nb = (a.e_hi - a.e_lo + GPB - 1) / GPB;
-  if (ADAM != 0 && b.row_ids) nb = (b.n_rows + GPB - 1) / GPB;     // the listed rows only
-  const int64_t cap = 256LL * per_cu;
-  if (nb > cap) nb = cap;
-  // VFM_FLAG_SHARE_GPU: 15/16 of the 1,024 workgroups the chip holds (126 VGPRs: four per CU), so that another stream's small
-  // kernels (256 threads, <= 128 VGPRs: csrc/vfm_index.hip) find a free slot on 64 CUs while this one runs
-  { const int share = env_int("VFM_SHARE_CAP", 960); if ((a.flags & VFM_FLAG_SHARE_GPU) && share > 0 && nb > share) nb = share; }
-  { const int forced = env_int("VFM_BWD_GRID", 0); if (forced > 0 && nb > forced) nb = forced; }      // (A/B runs)
-  if (nb < 1) nb = 1;
+  auto grid_of = [&](int gpb) -> int64_t {      // workgroups for lane groups of BLOCK / gpb lanes
+    int64_t nb = (a.e_hi - a.e_lo + gpb - 1) / gpb;
+    if (ADAM != 0 && b.row_ids) nb = (b.n_rows + gpb - 1) / gpb;     // the listed rows only
+    const int64_t cap = 256LL * per_cu;
+    if (nb > cap) nb = cap;
+    // VFM_FLAG_SHARE_GPU: 15/16 of the 1,024 workgroups the chip holds (126 VGPRs: four per CU), so that another stream's small
+    // kernels (256 threads, <= 128 VGPRs: csrc/vfm_index.hip) find a free slot on 64 CUs while this one runs
+    { const int share = env_int("VFM_SHARE_CAP", 960); if ((a.flags & VFM_FLAG_SHARE_GPU) && share > 0 && nb > share) nb = share; }
+    { const int forced = env_int("VFM_BWD_GRID", 0); if (forced > 0 && nb > forced) nb = forced; }      // (A/B runs)
+    return nb < 1 ? 1 : nb;
+  };
+  const int64_t nb = grid_of(BLOCK / LPE);
   if constexpr (STAGE == STAGE_FULL && ADAM == 1 && EPS == EPS_PHILOX && VEC == 4 && LINK == LINK_ABS) {
     if (b.zrec != nullptr) {      // software-pipelined step: gathers samples, writes the next step's records
       if (a.S > 1) return fail(VFM_E_UNSUPPORTED, "pipelined step: one variational sample");
@@ -56,6 +58,19 @@ int launch_bwd_t(KArgs& a, const BwdArgs& b, const AdamArgs& ad, hipStream_t st)
   // VFM_BWD_PREFETCH=1: the fused Philox step fetches each row's index one row ahead (k_bwd<PF>; A/B, tests).  Off by
   // default: bitwise the same step, but not faster at cfg3
   const bool pf = env_int("VFM_BWD_PREFETCH", 0) != 0;
+  // VFM_BWD_LANES8=1: at d = 128 the fused single-sample Philox step (dense and look-ahead forms, scan and listed, |.| link)
+  // runs k_bwd<16, 2, ..., ADJ>: 8 adjacent coordinates and one Philox call per lane, four table rows per wave.  Bitwise the
+  // same step (tests/test_gpu_bwd_lanes8.py).  Every other d, and the prefetch form, keep the shape of the table.
+  if constexpr (STAGE == STAGE_FULL && ADAM == 1 && EPS == EPS_PHILOX && LPE == 32 && CPL == 1 && VEC == 4 && LINK == LINK_ABS) {
+    if (a.d == 128 && a.S == 1 && !pf && env_int("VFM_BWD_LANES8", 0) != 0) {
+      const int64_t nb8 = grid_of(BLOCK / 16);
+      if (b.last_step != nullptr)
+        hipLaunchKernelGGL((k_bwd<16, 2, 4, EPS, ADAM, STAGE, LINK, false, false, true, false, true>), dim3((unsigned)nb8), dim3(BLOCK), 0, st, a, b, ad);
+      else
+        hipLaunchKernelGGL((k_bwd<16, 2, 4, EPS, ADAM, STAGE, LINK, false, false, false, false, true>), dim3((unsigned)nb8), dim3(BLOCK), 0, st, a, b, ad);
+      return 0;
+    }
+  }
   if constexpr (STAGE == STAGE_FULL && ADAM == 1 && EPS == EPS_PHILOX) {
     if (b.last_step != nullptr) {     // look-ahead lazy Adam
       if (a.S > 1) return fail(VFM_E_UNSUPPORTED, "look-ahead lazy Adam: one variational sample");

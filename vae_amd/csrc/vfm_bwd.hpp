@@ -25,6 +25,20 @@
 //   ms += (1-b1) g / b1^k,  vs += (1-b2) g^2 / b2^k,  m = ms b1^k,  v = vs b2^k,  p -= lr_t m / (sqrt(v)/.. + eps)
 // At the end of a period of VFM_MOMENT_PERIOD steps the true m, v are written for every row (k restarts),
 // which bounds 1 / b1^k (0.9^-128 = 7e5).
+// The scaled form in its two halves (adam_update below runs them back to back): the moments take the gradient, then the
+// parameter moves given r = sqrt(stored second moment).  The look-ahead instances call the halves themselves: a replayed
+// row without gradient already holds that root (its second moment does not change), so it is taken once, not twice.
+__device__ __forceinline__ void adam_accum(float g, float& m, float& v, const AdamArgs& ad) {
+  m = fmaf(ad.c1, g, m);
+  v = fmaf(ad.c2 * g, g, v);
+}
+__device__ __forceinline__ float adam_apply(float p, float& m, float& v, float r, const AdamArgs& ad) {
+  const float denom = fmaf(r, ad.q2, ad.eps);
+  const float pn = fmaf(-ad.a1 * m, __builtin_amdgcn_rcpf(denom), p);
+  if (ad.store_true) { m = m * ad.s1; v = v * ad.s2; }
+  return pn;
+}
+
 __device__ __forceinline__ float adam_update(float p, float g, float& m, float& v, const AdamArgs& ad) {
   if (ad.scaled) {                     // uniform
     // (this form is not bitwise torch's anyway: hardware sqrt / rcp, 1 ulp each, instead of the IEEE
@@ -33,12 +47,8 @@ __device__ __forceinline__ float adam_update(float p, float g, float& m, float& 
     // p -= step_size m_t / (sqrt(v_t) / sqrt(bc2) + eps) with m_t = ms b1^k, v_t = vs b2^k, the per-step factors folded
     // into two scalars (a1, q2): sqrt is taken of the STORED second moment, so a row without gradient needs it once
     // however many steps are replayed (k_adam_catchup runs exactly these operations)
-    m = fmaf(ad.c1, g, m);
-    v = fmaf(ad.c2 * g, g, v);
-    const float denom = fmaf(__builtin_amdgcn_sqrtf(v), ad.q2, ad.eps);
-    const float pn = fmaf(-ad.a1 * m, __builtin_amdgcn_rcpf(denom), p);
-    if (ad.store_true) { m = m * ad.s1; v = v * ad.s2; }
-    return pn;
+    adam_accum(g, m, v, ad);
+    return adam_apply(p, m, v, __builtin_amdgcn_sqrtf(v), ad);
   }
   m = m + (g - m) * (1.0f - ad.b1);
   v = v * ad.b2 + ((1.0f - ad.b2) * g) * g;
@@ -65,10 +75,16 @@ __device__ __forceinline__ float replay_one(float p, float m, float r, float2 c,
 // ahead, under this row's epilogue -- the first two row numbers of its list and (LA) whether it is in the next batch --
 // so that a row's walk starts with the grow / sumz loads: one dependent load less per row.  Same loads, same sums, same
 // order; PF = false is the row-serial form (the default; VFM_BWD_PREFETCH=1 selects PF).
+// ADJ (fused dense step, one sample, not pipelined, Philox eps, CPL = 2): a lane owns the two ADJACENT chunks 2 lig and
+// 2 lig + 1 -- 8 coordinates in one 32-byte stretch, the eps of all of them from ONE Philox call (eps_of_chunk_pair), where
+// the strided mapping j = lig + i LPE spends a call per chunk.  Which lane holds a coordinate changes, what is computed for
+// it does not: same expressions, same sums, same order.  At d = 128 a lane group is 16 lanes and a wave carries four rows.
 template <int LPE, int CPL, int VEC, int EPS, int ADAM, int STAGE, int LINK, bool MULTI, bool PIPE = false, bool LA = false,
-          bool PF = false>
+          bool PF = false, bool ADJ = false>
 __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const KArgs a, const BwdArgs b, const AdamArgs ad_in) {
   constexpr int GPB = BLOCK / LPE;
+  static_assert(!ADJ || (CPL == 2 && VEC == 4 && EPS == EPS_PHILOX && ADAM == 1 && STAGE == STAGE_FULL && !MULTI && !PIPE),
+                "adjacent chunks per lane: the fused single-sample Philox step with two chunks per lane");
   // step-dependent values: from the kernel arguments, or (replayable step, a.dev) from device memory
   AdamArgs ad = ad_in;
   RngKey key = a.key, next_key = b.next_key;
@@ -86,6 +102,7 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
   __shared__ float2 sh_tab[LA ? VFM_MOMENT_PERIOD + 1 : 1];      // LA: (a1, q2) of the period's earlier steps, for replays
   const int tid = threadIdx.x;
   const int lig = tid % LPE;
+  auto chunk_of = [&](int i) -> int { return ADJ ? CPL * lig + i : lig + i * LPE; };      // the i-th chunk of this lane
   const int d = a.d;
   const int C = (d + VEC - 1) / VEC;
   if (STAGE != STAGE_ACC && tid < a.G) {
@@ -251,7 +268,7 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
     if (STAGE != STAGE_ACC && (ADAM || touched)) {
 #pragma unroll
       for (int i = 0; i < CPL; ++i) {
-        const int j = lig + i * LPE;
+        const int j = chunk_of(i);
         if (j < C) {
           mu[i] = ld_chunk<VEC>(prow + (size_t)j * VEC);
           s[i] = ld_chunk<VEC>(prow + d + (size_t)j * VEC);
@@ -299,7 +316,7 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
             gs += ir[0];
 #pragma unroll
             for (int i = 0; i < CPL; ++i) {
-              const int j = lig + i * LPE;
+              const int j = chunk_of(i);
               if (j < C) {
                 const Chunk<VEC> t4 = ld_chunk<VEC>(ir + 4 + (size_t)j * VEC);
 #pragma unroll
@@ -311,7 +328,7 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
           gs = __int_as_float(hd.x);
 #pragma unroll
           for (int i = 0; i < CPL; ++i) {
-            const int j = lig + i * LPE;
+            const int j = chunk_of(i);
             if (j < C) A[i] = ld_chunk<VEC>(rec + 4 + (size_t)j * VEC);
           }
         }
@@ -330,7 +347,7 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
         gs += g0 + g1;
 #pragma unroll
         for (int i = 0; i < CPL; ++i) {
-          const int j = lig + i * LPE;
+          const int j = chunk_of(i);
           if (j < C) {
             const Chunk<VEC> s0v = ld_chunk<VEC>(p0 + (size_t)j * VEC);
             const Chunk<VEC> s1v = ld_chunk<VEC>(p1 + (size_t)j * VEC);
@@ -352,7 +369,7 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
         gs += g0;
 #pragma unroll
         for (int i = 0; i < CPL; ++i) {
-          const int j = lig + i * LPE;
+          const int j = chunk_of(i);
           if (j < C) {
             const Chunk<VEC> s0v = ld_chunk<VEC>(p0 + (size_t)j * VEC);
 #pragma unroll
@@ -369,7 +386,7 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
     if constexpr (STAGE == STAGE_ACC) {   // store the statistics (dense: zeros for rows not in this shard)
 #pragma unroll
       for (int i = 0; i < CPL; ++i) {
-        const int j = lig + i * LPE;
+        const int j = chunk_of(i);
         if (j < C) st_chunk<VEC>(b.acc + (size_t)rec * xs + 4 + (size_t)j * VEC, A[i]);
       }
       if (lig == 0) *reinterpret_cast<float4*>(b.acc + (size_t)rec * xs) = make_float4(gs, cntf, 0.f, 0.f);
@@ -380,7 +397,7 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
       if (touched) {
 #pragma unroll
         for (int i = 0; i < CPL; ++i) {
-          const int j = lig + i * LPE;
+          const int j = chunk_of(i);
           if (j < C) A[i] = ld_chunk<VEC>(b.acc + (size_t)rec * xs + 4 + (size_t)j * VEC);
         }
       }
@@ -392,7 +409,7 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
       for (int t = 0; t < VEC; ++t) zc.v[t] = 0.f;
 #pragma unroll
       for (int i = 0; i < CPL; ++i) {
-        const int j = lig + i * LPE;
+        const int j = chunk_of(i);
         if (j < C) {
           st_chunk_nt<VEC>(grow_e + (size_t)j * VEC, zc);
           st_chunk_nt<VEC>(grow_e + d + (size_t)j * VEC, zc);
@@ -423,7 +440,7 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
         const RngKey ks = key_of_sample(key, sm);
 #pragma unroll
         for (int i = 0; i < CPL; ++i) {
-          const int j = lig + i * LPE;
+          const int j = chunk_of(i);
           if (j < C) {
             Chunk<VEC> epc;
             if constexpr (EPS == EPS_TABLE) {
@@ -453,9 +470,13 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
 #pragma unroll
         for (int t = 0; t < VEC; ++t) { g1s[i].v[t] *= a.inv_S; g2s[i].v[t] *= a.inv_S; }
     }
+    Chunk<VEC> epp[ADJ ? CPL : 1];      // ADJ: the eps of both chunks, from the lane's one Philox call
+    if constexpr (ADJ) {
+      if (touched) eps_of_chunk_pair(key, (uint32_t)e, lig, epp[0].v, epp[1].v, nb_eps);
+    }
 #pragma unroll
     for (int i = 0; i < CPL; ++i) {
-      const int j = lig + i * LPE;
+      const int j = chunk_of(i);
       if (j < C) {
         Chunk<VEC> gm, gv;
         if (touched && multi) {
@@ -472,6 +493,8 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
           } else if constexpr (EPS == EPS_ZERO) {
 #pragma unroll
             for (int t = 0; t < VEC; ++t) epc.v[t] = 0.f;
+          } else if constexpr (ADJ) {
+            epc = epp[i];
           } else {
             float nb;
             eps_of_chunk<VEC>(key, (uint32_t)e, j, epc.v, nb);
@@ -490,9 +513,9 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
 #pragma unroll
           for (int t = 0; t < VEC; ++t) { gm.v[t] = 0.f; gv.v[t] = 0.f; }
         }
+        float rm[VEC], rs[VEC];        // LA: sqrt of the stored second moments
         if constexpr (LA) {
           if (la_gap > 0) {            // (uniform over the lane group) bring the row up to the step before this one
-            float rm[VEC], rs[VEC];
 #pragma unroll
             for (int t = 0; t < VEC; ++t) { rm[t] = __builtin_amdgcn_sqrtf(vm[i].v[t]); rs[t] = __builtin_amdgcn_sqrtf(vs[i].v[t]); }
             for (int k = la_k - la_gap; k < la_k; ++k) {
@@ -507,10 +530,28 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
         }
         if constexpr (ADAM) {
           Chunk<VEC> pm, ps;
+          if constexpr (LA) {          // (always the scaled form) adam_update in its halves
 #pragma unroll
-          for (int t = 0; t < VEC; ++t) {
-            pm.v[t] = adam_update(mu[i].v[t], gm.v[t], mm[i].v[t], vm[i].v[t], ad);
-            ps.v[t] = adam_update(s[i].v[t], gv.v[t], ms[i].v[t], vs[i].v[t], ad);
+            for (int t = 0; t < VEC; ++t) {
+              adam_accum(gm.v[t], mm[i].v[t], vm[i].v[t], ad);
+              adam_accum(gv.v[t], ms[i].v[t], vs[i].v[t], ad);
+            }
+            // a replayed row without gradient: vm / vs are what they were (fma(c2 0, 0, v) = v), rm / rs are their roots
+            if (!(la_gap > 0 && !touched)) {
+#pragma unroll
+              for (int t = 0; t < VEC; ++t) { rm[t] = __builtin_amdgcn_sqrtf(vm[i].v[t]); rs[t] = __builtin_amdgcn_sqrtf(vs[i].v[t]); }
+            }
+#pragma unroll
+            for (int t = 0; t < VEC; ++t) {
+              pm.v[t] = adam_apply(mu[i].v[t], mm[i].v[t], vm[i].v[t], rm[t], ad);
+              ps.v[t] = adam_apply(s[i].v[t], ms[i].v[t], vs[i].v[t], rs[t], ad);
+            }
+          } else {
+#pragma unroll
+            for (int t = 0; t < VEC; ++t) {
+              pm.v[t] = adam_update(mu[i].v[t], gm.v[t], mm[i].v[t], vm[i].v[t], ad);
+              ps.v[t] = adam_update(s[i].v[t], gv.v[t], ms[i].v[t], vs[i].v[t], ad);
+            }
           }
           const size_t o2 = (size_t)e * (2 * (size_t)d) + (size_t)j * VEC;
           st_chunk<VEC>(prow + (size_t)j * VEC, pm);
@@ -550,9 +591,10 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
         g0 = gout * (gs + c * th.x);
         g1 = gout * dlink_f<LINK>(th.y) * (gs * nb_eps + c * (sg - inv_sigma(sg)));
       }
+      float r0, r1;                  // LA: sqrt of the stored second moments of (mu_w, s_w)
       if constexpr (LA) {
         if (la_gap > 0) {
-          const float r0 = __builtin_amdgcn_sqrtf(vb.x), r1 = __builtin_amdgcn_sqrtf(vb.y);
+          r0 = __builtin_amdgcn_sqrtf(vb.x); r1 = __builtin_amdgcn_sqrtf(vb.y);
           for (int k = la_k - la_gap; k < la_k; ++k) {
             const float2 c = sh_tab[k];
             th.x = replay_one(th.x, mb.x, r0, c, ad.eps);
@@ -563,8 +605,16 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
       }
       if constexpr (ADAM) {
         float2 pn;
-        pn.x = adam_update(th.x, g0, mb.x, vb.x, ad);
-        pn.y = adam_update(th.y, g1, mb.y, vb.y, ad);
+        if constexpr (LA) {            // the halves of adam_update, the roots handed over as for the embedding row
+          adam_accum(g0, mb.x, vb.x, ad);
+          adam_accum(g1, mb.y, vb.y, ad);
+          if (!(la_gap > 0 && !touched)) { r0 = __builtin_amdgcn_sqrtf(vb.x); r1 = __builtin_amdgcn_sqrtf(vb.y); }
+          pn.x = adam_apply(th.x, mb.x, vb.x, r0, ad);
+          pn.y = adam_apply(th.y, mb.y, vb.y, r1, ad);
+        } else {
+          pn.x = adam_update(th.x, g0, mb.x, vb.x, ad);
+          pn.y = adam_update(th.y, g1, mb.y, vb.y, ad);
+        }
         *reinterpret_cast<float2*>(const_cast<float*>(a.bias) + 2 * (size_t)e) = pn;
         if (a.wrec) *reinterpret_cast<float2*>(a.wrec + 4 * (size_t)e) = pn;      // packed first-order record: (mu_w, s_w | 1/occ, 0)
         if constexpr (PIPE) {
