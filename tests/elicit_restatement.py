@@ -19,14 +19,20 @@ import numpy as np
 LOG_2PI_HALF = 0.5 * math.log(2 * math.pi)
 
 
-def link(s, kind):
-    s = np.asarray(s, dtype=np.float64)
+def link(s, kind, dtype=np.float64):
+    s = np.asarray(s, dtype=dtype)
     return np.abs(s) if kind == "abs" else np.logaddexp(0.0, s)
 
 
-def dlink(s, kind):
-    s = np.asarray(s, dtype=np.float64)
-    return np.where(s < 0, -1.0, 1.0) if kind == "abs" else 1.0 / (1.0 + np.exp(-s))
+def dlink(s, kind, dtype=np.float64):
+    s = np.asarray(s, dtype=dtype)
+    return np.where(s < 0, -1.0, 1.0).astype(dtype) if kind == "abs" else 1.0 / (1.0 + np.exp(-s))
+
+
+def _scalar_of(dtype):
+    """The scalar constructor of a working precision: float for float64 (the arithmetic of every caller that names no
+    dtype, unchanged), the numpy scalar type otherwise (a Python float would carry scalar products in fp64)."""
+    return float if np.dtype(dtype) == np.float64 else np.dtype(dtype).type
 
 
 def prior_theta(d, kind):
@@ -81,8 +87,8 @@ def choose(sc, asked):
     return best, (sc[best] - sc[second]) / den
 
 
-def _adam(theta, grad_fn, n_steps, lr):
-    p = np.concatenate([theta[0], theta[1], [theta[2], theta[3]]]).astype(np.float64)
+def _adam(theta, grad_fn, n_steps, lr, dtype=np.float64):
+    p = np.concatenate([theta[0], theta[1], [theta[2], theta[3]]]).astype(dtype)
     d = theta[0].shape[0]
     m, v = np.zeros_like(p), np.zeros_like(p)
     unpack = lambda p: (p[:d], p[d:2 * d], p[2 * d], p[2 * d + 1])
@@ -97,31 +103,35 @@ def _adam(theta, grad_fn, n_steps, lr):
     return (th[0].copy(), th[1].copy(), float(th[2]), float(th[3])), float(loss)
 
 
-def _kl(theta, kind, klw):
+def _kl(theta, kind, klw, dtype=np.float64):
+    f = _scalar_of(dtype)
     mu, s, mw, sw = theta
-    sg, sgw = link(s, kind), float(link(sw, kind))
+    sg, sgw = link(s, kind, dtype), f(link(sw, kind, dtype))
     kl = np.sum(0.5 * (sg * sg + mu * mu - 1.0) - np.log(sg)) + 0.5 * (sgw * sgw + mw * mw - 1.0) - math.log(sgw)
-    g = np.concatenate([klw * mu, klw * (sg - 1.0 / sg) * dlink(s, kind),
-                        [klw * mw, klw * (sgw - 1.0 / sgw) * float(dlink(sw, kind))]])
+    g = np.concatenate([klw * mu, klw * (sg - 1.0 / sg) * dlink(s, kind, dtype),
+                        [klw * mw, klw * (sgw - 1.0 / sgw) * f(dlink(sw, kind, dtype))]])
     return klw * kl, g
 
 
-def fold(theta, u, items, y, ent, bia, scal, kind, output, objective, n_steps, lr, klw=1.0, eps=None, t0=0):
+def fold(theta, u, items, y, ent, bia, scal, kind, output, objective, n_steps, lr, klw=1.0, eps=None, t0=0,
+         dtype=np.float64):
     """n_steps Adam updates (fresh moments) of the user's theta on the rows (items [n], y [n]); every quantity is
-    recomputed from the rows at every step.  Returns (theta, loss at the final parameters)."""
+    recomputed from the rows at every step.  Returns (theta, loss at the final parameters).  dtype: the working
+    precision of every array and scalar (float32: what rounding alone does to the fold, no kernel involved)."""
+    f = _scalar_of(dtype)
     items = np.asarray(items, dtype=np.int64)
-    y = np.asarray(y, dtype=np.float64)
+    y = np.asarray(y, dtype=dtype)
     d = theta[0].shape[0]
-    prec = float(link(scal[0], kind))
-    m0, sg0 = float(scal[1]), float(link(scal[2], kind))
-    mi = ent[items, :d].astype(np.float64)
-    si = link(ent[items, d:], kind)
-    bi, sbi = bia[items, 0].astype(np.float64), link(bia[items, 1], kind)
+    prec = f(link(scal[0], kind, dtype))
+    m0, sg0 = f(scal[1]), f(link(scal[2], kind, dtype))
+    mi = ent[items, :d].astype(dtype)
+    si = link(ent[items, d:], kind, dtype)
+    bi, sbi = bia[items, 0].astype(dtype), link(bia[items, 1], kind, dtype)
     n = len(items)
 
     def grad_fn(th, it):
         mu, s, mw, sw = th
-        sg, sgw = link(s, kind), float(link(sw, kind))
+        sg, sgw = link(s, kind, dtype), f(link(sw, kind, dtype))
         if objective == "closed_form":
             A = si * si
             Ep = m0 + bi + mw + mi @ mu
@@ -132,10 +142,10 @@ def fold(theta, u, items, y, ent, bia, scal, kind, output, objective, n_steps, l
             gsg = prec * sg * (A + mi * mi).sum(0)
             gmw, gsw = prec * res.sum(), prec * n * sgw
         else:
-            ee, eb, eg = eps(t0 + it)
+            ee, eb, eg = (np.asarray(a, dtype=dtype) for a in eps(t0 + it))
             zu = mu + sg * ee[u]
             zi = mi + si * ee[items]
-            pred = (m0 + sg0 * float(eg)) + (mw + sgw * eb[u]) + (bi + sbi * eb[items]) + zi @ zu
+            pred = (m0 + sg0 * f(eg)) + (mw + sgw * eb[u]) + (bi + sbi * eb[items]) + zi @ zu
             if output == "reg":
                 L = np.sum(0.5 * prec * (y - pred) ** 2) + n * (LOG_2PI_HALF - 0.5 * math.log(prec))
                 gp = prec * (pred - y)
@@ -145,11 +155,11 @@ def fold(theta, u, items, y, ent, bia, scal, kind, output, objective, n_steps, l
             acc = gp @ zi
             gmu, gsg = acc, acc * ee[u]
             gmw, gsw = gp.sum(), gp.sum() * eb[u]
-        kl, gk = _kl(th, kind, klw)
-        g = np.concatenate([gmu, gsg * dlink(s, kind), [gmw, gsw * float(dlink(sw, kind))]]) + gk
+        kl, gk = _kl(th, kind, klw, dtype)
+        g = np.concatenate([gmu, gsg * dlink(s, kind, dtype), [gmw, gsw * f(dlink(sw, kind, dtype))]]) + gk
         return L + kl, g
 
-    return _adam(theta, grad_fn, n_steps, lr)
+    return _adam(theta, grad_fn, n_steps, lr, dtype)
 
 
 def session(u, pool_items, pool_y, n_rounds, strategy, ent, bia, scal, kind="abs", output="reg",
@@ -256,4 +266,78 @@ def closed_form_thetas_fp32(rows, pool_items, pool_y, ent, bia, scal, n_steps, l
             den = np.sqrt(v) / f(math.sqrt(1.0 - 0.999 ** t)) + f(1e-8)
             p = (p + (-f(lr / (1.0 - 0.9 ** t)) * m) / den).astype(f)
         out.append((p[:d].copy(), p[d:2 * d].copy(), p[2 * d:].copy()))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the per-round fp64 check of test_gpu_elicit_shapes.py: its three generators and the walk along given selections
+# ---------------------------------------------------------------------------------------------------------------------
+FP64_CASES = {  # name: output, objective, link, strategy, reset, history rows per user, d
+    "sampled_class_softplus_history_mean_d33": ("class", "sampled", "softplus", "mean", False, 12, 33),
+    "sampled_reg_abs_reset_variance_d300": ("reg", "sampled", "abs", "variance", True, 0, 300),
+    "closed_form_reg_softplus_history_top_d129": ("reg", "closed_form", "softplus", "top", False, 12, 129),
+}
+FP64_USERS, FP64_ITEMS, FP64_POOL, FP64_ROUNDS, FP64_STEPS, FP64_LR = 16, 120, 30, 5, 20, 0.01
+
+
+def planted_case(name):
+    """The inputs of one case of FP64_CASES (numpy only, so that the CPU conditioning test and the GPU test share
+    them): 16 users, 120 items, 30-row pools, planted item means of norm about 1 at every d (N(0, 1 / d) coordinates:
+    logits of unit scale), user means N(0, 1) with sigma 0.3, item sigmas 0.05, noise sd 0.5 (precision 4).  Returns
+    dict(ent [T, 2d], bia [T, 2], scal [3] fp32 tables, pool [P, 2], y_pool [P], hist_x [H, 2], hist_y [H])."""
+    output, objective, kind, strategy, reset, n_hist, d = FP64_CASES[name]
+    N, M, P = FP64_USERS, FP64_ITEMS, FP64_POOL
+    g = np.random.default_rng(100 + sorted(FP64_CASES).index(name))
+    s_of = (lambda sig: sig) if kind == "abs" else (lambda sig: math.log(math.expm1(sig)))
+    mu = g.normal(size=(N + M, d))
+    mu[N:] /= math.sqrt(d)
+    s = np.full((N + M, d), s_of(0.05))
+    s[:N] = s_of(0.3)
+    ent = np.concatenate([mu, s], 1).astype(np.float32)
+    bia = np.stack([g.normal(size=N + M) * 0.1, np.full(N + M, s_of(0.05))], 1).astype(np.float32)
+    bia[:N, 1] = s_of(0.3)
+    scal = np.array([s_of(4.0), 0.0, s_of(0.05)], dtype=np.float32)
+    pool, hist = [], []
+    for u in range(N):
+        it = N + g.permutation(M)
+        pool.append(np.stack([np.full(P, u), it[:P]], 1))
+        hist.append(np.stack([np.full(n_hist, u), it[P:P + n_hist]], 1))
+    pool, hist = np.concatenate(pool).astype(np.int64), np.concatenate(hist).astype(np.int64)
+
+    def answers(x):
+        truth = (mu[x[:, 0]] * mu[x[:, 1]]).sum(1) + bia[x[:, 0], 0] + bia[x[:, 1], 0]
+        if output == "reg":
+            return (truth + 0.5 * g.normal(size=len(x))).astype(np.float32)
+        return (g.random(len(x)) < 1.0 / (1.0 + np.exp(-truth))).astype(np.float32)
+
+    return dict(ent=ent, bia=bia, scal=scal, pool=pool, y_pool=answers(pool), hist_x=hist, hist_y=answers(hist))
+
+
+def rounds_along(name, case, u, rows, theta_before, eps, dtype=np.float64):
+    """User u's session of `case` taken round by round along GIVEN selections, with no feedback between the rounds:
+    rows [Q] positions in u's pool slice (-1: nothing asked), theta_before(q) -> the theta tuple round q starts from.
+    Per round q with a row asked: (q, mean, var, score [n_pool] from theta_before(q), the unasked mask before the
+    choice, theta after the fold of the history followed by rows[:q + 1] with t0 = q (n_steps + 1), its loss)."""
+    output, objective, kind, strategy, reset, n_hist, d = FP64_CASES[name]
+    E, B, S = (case[k].astype(np.float64) for k in ("ent", "bia", "scal"))
+    sel = np.nonzero(case["pool"][:, 0] == u)[0]
+    items, ys = case["pool"][sel, 1], case["y_pool"][sel]
+    hs = np.nonzero(case["hist_x"][:, 0] == u)[0]
+    f_items, f_y = list(case["hist_x"][hs, 1]), list(case["hist_y"][hs])
+    unasked = np.ones(len(sel), dtype=bool)
+    out = []
+    for q, r in enumerate(rows):
+        if r < 0:
+            break
+        th = theta_before(q)
+        mean, var = moments(th, E, B, S, items, kind)
+        sc = score(strategy, mean, var)
+        mask = unasked.copy()
+        unasked[r] = False
+        f_items.append(items[r])
+        f_y.append(ys[r])
+        th_d = (th[0].astype(dtype), th[1].astype(dtype), th[2], th[3])
+        th1, loss = fold(th_d, u, f_items, f_y, E, B, S, kind, output, objective, FP64_STEPS, FP64_LR, 1.0, eps,
+                         q * (FP64_STEPS + 1), dtype=dtype)
+        out.append((q, mean, var, sc, mask, th1, loss))
     return out

@@ -309,3 +309,70 @@ def test_planted_generator_is_well_conditioned_in_fp32():
                     worst[lr] = max(worst[lr], float(np.abs(a - b).max() / np.abs(b).max()))
     assert worst[0.01] < 1e-5, worst
     assert worst[0.05] > 1e-4, worst
+
+
+def test_per_round_generators_are_well_conditioned_in_fp32():
+    """The inputs of test_gpu_elicit_shapes.py::test_rounds_against_the_fp64_restatement (R.FP64_CASES, built by
+    R.planted_case: 16 users, 30-row pools, 5 rounds of 20 Adam steps at lr = 0.01, one draw per iteration).  The GPU test
+    compares every round on its own -- R.fold from the theta the round starts from, on the history followed by the rows
+    asked so far -- with the 1e-4 of test_trajectory_matches_fp64_adam, which bounds fp32 rounding and so means
+    something only where a plain fp32 run of the same fold stays well inside it.  Here: the fp64 session's selections
+    and starting thetas (rounded to fp32, as the kernel's are), each round folded by R.fold in fp32 and in fp64; the
+    condition is 1e-5, 10x inside the tolerance.  The draws are numpy normals keyed on the iteration (the kernel's Philox
+    stream needs a GPU; the condition is one on the inputs, not on the stream).  Largest distance over users, rounds
+    and theta parts (max |fp32 - fp64| / max |fp64|), and of the loss:
+      sampled, class, softplus, 12 history rows, 'mean', d = 33:      theta 7.3e-7, loss 1.8e-7
+      sampled, reg, |.|, cold start (reset), 'variance', d = 300:     theta 5.4e-7, loss 7.6e-7
+      closed form, reg, softplus, 12 history rows, 'top', d = 129:    theta 1.1e-6, loss 2.3e-7
+    None of the three needed a change (item means of norm 1 at every d keep a one-row cold-start fold from
+    overshooting)."""
+    def eps_of(T, d):
+        cache = {}
+
+        def f(t):
+            if t not in cache:
+                g = np.random.default_rng([7, t])
+                cache[t] = (g.normal(size=(T, d)).astype(np.float32), g.normal(size=T).astype(np.float32),
+                            np.float32(g.normal()))
+            return cache[t]
+        return f
+
+    f32 = lambda th: (th[0].astype(np.float32).astype(np.float64), th[1].astype(np.float32).astype(np.float64),
+                      float(np.float32(th[2])), float(np.float32(th[3])))
+    for name, (output, objective, kind, strategy, reset, n_hist, d) in R.FP64_CASES.items():
+        c = R.planted_case(name)
+        E, B, S = (c[k].astype(np.float64) for k in ("ent", "bia", "scal"))
+        eps = eps_of(E.shape[0], d)
+        worst, worst_loss, n_rounds = 0.0, 0.0, 0
+        for u in range(R.FP64_USERS):
+            sel, hs = np.nonzero(c["pool"][:, 0] == u)[0], np.nonzero(c["hist_x"][:, 0] == u)[0]
+            assert len(sel) == R.FP64_POOL and len(hs) == n_hist
+            s = R.session(u, c["pool"][sel, 1], c["y_pool"][sel], R.FP64_ROUNDS, strategy, E, B, S, kind=kind,
+                          output=output, objective=objective, hist_items=c["hist_x"][hs, 1], hist_y=c["hist_y"][hs],
+                          n_steps=R.FP64_STEPS, lr=R.FP64_LR, reset=reset, eps=eps)
+            start = R.prior_theta(d, kind) if reset else R.table_theta(E, B, u)
+            before = lambda q: f32(start if q == 0 else s["theta"][q - 1])
+            r64 = R.rounds_along(name, c, u, s["rows"], before, eps)
+            r32 = R.rounds_along(name, c, u, s["rows"], before, eps, dtype=np.float32)
+            for a, b in zip(r64, r32):
+                assert b[5][0].dtype == np.float32 and b[5][1].dtype == np.float32   # (nothing was promoted on the way)
+                for x, y in ((b[5][0], a[5][0]), (b[5][1], a[5][1]), (np.array(b[5][2:]), np.array(a[5][2:]))):
+                    worst = max(worst, float(np.abs(x - y).max() / np.abs(y).max()))
+                worst_loss = max(worst_loss, abs(b[6] - a[6]) / abs(a[6]))
+                n_rounds += 1
+        assert n_rounds == R.FP64_USERS * R.FP64_ROUNDS
+        assert worst < 1e-5 and worst_loss < 1e-5, (name, worst, worst_loss)
+
+
+def test_fold_dtype_argument_leaves_fp64_callers_alone():
+    """R.fold with no dtype, with dtype=float64 and as session's own round give the same numbers."""
+    d, N, M = 3, 2, 6
+    ent, bia, scal = _tables(N + M, d, 2)
+    items, y = np.array([3, 5, 4]), np.array([1.0, 0.0, 1.0])
+    for objective, output, kind in (("closed_form", "reg", "abs"), ("sampled", "class", "softplus")):
+        args = (R.table_theta(ent, bia, 1), 1, items, y, ent, bia, scal, kind, output, objective, 5, 0.05, 0.7,
+                _eps(N + M, d, 1), 2)
+        (a, la), (b, lb) = R.fold(*args), R.fold(*args, dtype=np.float64)
+        assert la == lb and all(np.array_equal(x, z) for x, z in zip(a, b))
+        (c, lc) = R.fold(*args, dtype=np.float32)
+        assert c[0].dtype == np.float32 and abs(lc - la) < 1e-4 * abs(la) and lc != la
