@@ -138,6 +138,37 @@ int vfm_rank_field_f32(int64_t Q, const int64_t* ctx, int32_t field, const int64
                        const float* scalars, void* workspace, int64_t workspace_bytes, int64_t* out_items,
                        float* out_score, float* out_mean, float* out_var, void* stream);
 
+/* Workspace of vfm_rank_heldout_field_f32, in bytes (n_splits = 0: the automatic split count): the packed operands of
+ * vfm_rank_field_f32 (both parts, no top-k lists) plus O(n_splits (Q + n_pos)), never O(Q n_cand).  Negative on bad
+ * arguments. */
+int64_t vfm_rank_eval_field_workspace_bytes(int64_t Q, int64_t n_cand, int64_t n_pos, int32_t F, int32_t d,
+                                            int32_t strategy, int32_t n_splits);
+
+/* Held-out ranking evaluation in the field form, 2 <= F <= VFM_MAX_FIELDS: where each query context's held-out
+ * positives land in the query's full ranking of the candidates of `field`, in the order of vfm_rank_field_f32 (c beats
+ * i: score_c > score_i, or equal scores and id_c < id_i; the scores bitwise those of vfm_field_moments_f32 of the row
+ * (context, candidate) for the strategy).
+ *  ctx [Q, F], field, qkey, cand / cand_lo / n_cand, the exclusion CSR over the queries, strategy, seed, n_splits, flags:
+ *  as vfm_rank_field_f32.  The eligible candidates of query q, E_q: the candidates not excluded for q.
+ *  Positives: pos_ptr [Q+1] int64 offsets into pos_items [n_pos] (int64 entity ids of `field`, STRICTLY ASCENDING per
+ *  query); P_q the positives of q.  Every positive should lie in E_q (the caller checks: the Python layer raises or
+ *  drops).
+ *  Outputs, int64: per positive p of q (aligned with pos_items) out_rank[p] = #{c in E_q : c beats p},
+ *  out_rank_neg[p] = #{c in E_q \ P_q : c beats p}; per query out_n_eligible[q] = |E_q|, out_n_neg[q] = |E_q \ P_q|.
+ *  Integer counts: bitwise deterministic and independent of n_splits, the grid, the stream and the other queries of the
+ *  call.  A positive with rank < k is item [rank] of vfm_rank_field_f32's list for k; one with rank >= k is not in it.
+ *  A context or candidate id outside [0, T) gives a NaN score, which compares false with everything.  Q == 0: returns
+ *  0, nothing is launched.  Cost: the operand packing and score tiles of vfm_rank_field_f32, one 4d-long fp32 chain per
+ *  positive, and the scan, sort and merge of vfm_rank_heldout_f32. */
+int vfm_rank_heldout_field_f32(int64_t Q, const int64_t* ctx, int32_t field, const int64_t* qkey, int64_t n_cand,
+                               const int64_t* cand, int64_t cand_lo, int64_t T, int32_t F, int32_t d, int32_t strategy,
+                               int32_t flags, uint64_t seed, int32_t n_splits, const int64_t* excl_ptr,
+                               const int64_t* excl_items, int64_t n_excl, const int64_t* pos_ptr,
+                               const int64_t* pos_items, int64_t n_pos, const float* entity_params,
+                               const float* bias_params, const float* scalars, void* workspace, int64_t workspace_bytes,
+                               int64_t* out_rank, int64_t* out_rank_neg, int64_t* out_n_eligible, int64_t* out_n_neg,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,8 @@
 //   k_eval_pos_score -> k_eval_pos_sort:  each user's positives, scored and sorted best first
 //   k_rank_prep -> k_rank_eval:           the score tiles of k_rank, scanned into per-(split, user) histograms
 //   k_rank_eval_merge:                    splits summed, prefix sums -> rank, rank_neg; n_eligible, n_neg
+// The sort, the scan and the merge are instantiated here only; the field form (vfm_rank_field.hip) scores its positives
+// and packs its operands itself and launches the three through vfm::launch_rank_eval (vfm_rank_eval.hpp).
 //
 // Compiled with -ffp-contract=off (as vfm_rank.hip): the positives' scores (pair_moments) and the tile scores (MFMA) are
 // the same k-ordered fp32 fma chains, so a candidate compares with a positive exactly as rank_items orders them.
@@ -13,17 +15,11 @@
 
 #include "vfm_rank.h"
 #include "vfm_rank_tile.hpp"        // pair scores, operand packing (k_rank_prep), the MFMA score tile
+#include "vfm_rank_eval.hpp"        // the launch other operand forms share, the eval tail, segment_of, pos_row_of
 
 namespace {
 
-constexpr int POS_BLOCK = 256;      // per-positive kernels
 constexpr int MERGE_WAVE = 64;      // k_rank_eval_merge: one wave per user
-
-// The clamped CSR segment [lo, hi) of row u (a malformed ptr array gives wrong counts, never an access out of range)
-__device__ __forceinline__ void segment_of(const int64_t* ptr, int64_t u, int64_t n, int64_t& lo, int64_t& hi) {
-  lo = min(max(ptr[u], (int64_t)0), n);
-  hi = min(max(ptr[u + 1], lo), n);
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // k_eval_pos_score: one thread per positive p: its user (the row of pos_ptr holding p) and the strategy's score of the
@@ -39,15 +35,9 @@ __global__ __launch_bounds__(POS_BLOCK) void k_eval_pos_score(int64_t U, int64_t
                                                               int64_t* __restrict__ pusr) {
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n_pos) return;
-  int64_t lo = 0, hi = U - 1;              // the last row whose offset is <= p
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (pos_ptr[mid] <= p) lo = mid;
-    else hi = mid - 1;
-  }
-  int64_t s0, s1;
-  segment_of(pos_ptr, lo, n_pos, s0, s1);
-  pusr[p] = (p >= s0 && p < s1) ? lo : -1;
+  int64_t row;
+  const int64_t lo = pos_row_of(pos_ptr, U, n_pos, p, row);
+  pusr[p] = row;
   const int64_t uid = users[lo], iid = pos_items[p];
   float sc = __builtin_nanf("");
   if (uid >= 0 && uid < T && iid >= 0 && iid < T) {
@@ -253,33 +243,46 @@ __global__ __launch_bounds__(MERGE_WAVE) void k_rank_eval_merge(int64_t U, int S
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-struct EvalLayout : OpLayout {
-  int64_t off_pscore, off_pid, off_raw, off_pusr, off_slot, off_ha, off_hn, off_cel, off_cpos, bytes;
-};
+struct EvalLayout : OpLayout, EvalTail {};
 
 EvalLayout eval_layout_of(int64_t U, int64_t n_cand, int64_t n_pos, int d, int strategy, int n_splits) {
   EvalLayout L;
   static_cast<OpLayout&>(L) = op_layout_of(U, n_cand, d, strategy, n_splits);
-  int64_t off = L.end;
-  auto take = [&](int64_t bytes) { const int64_t o = off; off += round_up(bytes, 256); return o; };
-  L.off_pscore = take(n_pos * 4);
-  L.off_pid = take(n_pos * 8);
-  L.off_raw = take(n_pos * 4);
-  L.off_pusr = take(n_pos * 8);
-  L.off_slot = take(n_pos * 8);
-  L.off_ha = take((int64_t)L.S * n_pos * 4);
-  L.off_hn = take((int64_t)L.S * n_pos * 4);
-  L.off_cel = take((int64_t)L.S * U * 4);
-  L.off_cpos = take((int64_t)L.S * U * 4);
-  L.bytes = off;
+  static_cast<EvalTail&>(L) = eval_tail_of(L.end, L.S, U, n_pos);
   return L;
 }
 
-bool eval_sizes_ok(int64_t U, int64_t n_cand, int64_t n_pos) {
-  return U >= 0 && n_cand >= 0 && n_cand < ((int64_t)1 << 31) && n_pos >= 0 && n_pos < ((int64_t)1 << 40);
-}
-
 }  // namespace
+
+int vfm::launch_rank_eval(const RankEval& r, int strategy, unsigned n_query_tiles, hipStream_t st) {
+  if (r.n_pos > 0) {
+    const unsigned nb = (unsigned)((r.n_pos + POS_BLOCK - 1) / POS_BLOCK);
+    hipLaunchKernelGGL(k_eval_pos_sort, dim3(nb), dim3(POS_BLOCK), 0, st, r.n_pos, r.pos_ptr, r.pos_items, r.raw, r.pusr,
+                       r.pscore, r.pid, r.slot);
+    if (int rc = launch_status("k_eval_pos_sort")) return rc;
+  }
+  EvalArgs a;
+  a.U = r.U; a.n_cand = r.n_cand; a.item_lo = r.item_lo; a.n_excl = r.n_excl; a.n_pos = r.n_pos;
+  a.users = r.keys; a.cand = r.cand; a.excl_ptr = r.excl_ptr; a.excl_items = r.excl_items;
+  a.pos_ptr = r.pos_ptr; a.pos_items = r.pos_items;
+  a.pscore = r.pscore; a.pid = r.pid;
+  a.hist_all = r.hist_all; a.hist_neg = r.hist_neg;
+  a.cnt_el = r.cnt_el; a.cnt_pos = r.cnt_pos;
+  a.ops = TileOps{r.uop, r.iop, r.ucon, r.icon, r.Kp, r.KA, r.KB};
+  a.n_tiles = r.n_tiles; a.S = r.S; a.seed = r.seed;
+  const dim3 grid(n_query_tiles, (unsigned)r.S);
+  switch (strategy) {
+    case VFM_RANK_TOP: hipLaunchKernelGGL(k_rank_eval<VFM_RANK_TOP>, grid, dim3(256), 0, st, a); break;
+    case VFM_RANK_VARIANCE: hipLaunchKernelGGL(k_rank_eval<VFM_RANK_VARIANCE>, grid, dim3(256), 0, st, a); break;
+    case VFM_RANK_MEAN: hipLaunchKernelGGL(k_rank_eval<VFM_RANK_MEAN>, grid, dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL(k_rank_eval<VFM_RANK_RANDOM>, grid, dim3(256), 0, st, a); break;
+  }
+  if (int rc = launch_status("k_rank_eval")) return rc;
+  hipLaunchKernelGGL(k_rank_eval_merge, dim3((unsigned)r.U), dim3(MERGE_WAVE), 0, st, r.U, r.S, r.n_pos, r.pos_ptr,
+                     r.hist_all, r.hist_neg, r.cnt_el, r.cnt_pos, r.slot, r.out_rank, r.out_rank_neg, r.out_n_eligible,
+                     r.out_n_neg);
+  return launch_status("k_rank_eval_merge");
+}
 
 extern "C" {
 
@@ -324,37 +327,23 @@ int vfm_rank_heldout_f32(int64_t U, const int64_t* users, int64_t n_cand, const 
     hipLaunchKernelGGL(k_eval_pos_score, dim3(nb), dim3(POS_BLOCK), 0, st, U, n_pos, users, pos_ptr, pos_items, T, d, sp,
                        strategy, seed, entity_params, bias_params, scalars, (float*)(ws + L.off_raw),
                        (int64_t*)(ws + L.off_pusr));
-    hipLaunchKernelGGL(k_eval_pos_sort, dim3(nb), dim3(POS_BLOCK), 0, st, n_pos, pos_ptr, pos_items,
-                       (const float*)(ws + L.off_raw), (const int64_t*)(ws + L.off_pusr), (float*)(ws + L.off_pscore),
-                       (int64_t*)(ws + L.off_pid), (int64_t*)(ws + L.off_slot));
-    if (int rc = launch_status("k_eval_pos_sort")) return rc;
+    if (int rc = launch_status("k_eval_pos_score")) return rc;
   }
   if (strategy != VFM_RANK_RANDOM)
     if (int rc = launch_rank_prep(L, ws, U, users, n_cand, cand, item_lo, T, d, sp, entity_params, bias_params, scalars,
                                   st))
       return rc;
-  EvalArgs a;
+  vfm::RankEval a;
   a.U = U; a.n_cand = n_cand; a.item_lo = item_lo; a.n_excl = excl_ptr ? n_excl : 0; a.n_pos = n_pos;
-  a.users = users; a.cand = cand; a.excl_ptr = excl_ptr; a.excl_items = excl_items;
+  a.keys = users; a.cand = cand; a.excl_ptr = excl_ptr; a.excl_items = excl_items;
   a.pos_ptr = pos_ptr; a.pos_items = pos_items;
-  a.pscore = (const float*)(ws + L.off_pscore); a.pid = (const int64_t*)(ws + L.off_pid);
-  a.hist_all = (int*)(ws + L.off_ha); a.hist_neg = (int*)(ws + L.off_hn);
-  a.cnt_el = (int*)(ws + L.off_cel); a.cnt_pos = (int*)(ws + L.off_cpos);
-  a.ops = TileOps{(const float*)(ws + L.off_uop), (const float*)(ws + L.off_iop), (const float*)(ws + L.off_ucon),
-                  (const float*)(ws + L.off_icon), L.Kp, L.KA, L.KB};
+  a.uop = (const float*)(ws + L.off_uop); a.iop = (const float*)(ws + L.off_iop);
+  a.ucon = (const float*)(ws + L.off_ucon); a.icon = (const float*)(ws + L.off_icon);
+  a.Kp = L.Kp; a.KA = L.KA; a.KB = L.KB;
+  eval_tail_into(a, ws, L);
   a.n_tiles = L.n_tiles; a.S = L.S; a.seed = seed;
-  const dim3 grid((unsigned)(L.U_pad / UT), (unsigned)L.S);
-  switch (strategy) {
-    case VFM_RANK_TOP: hipLaunchKernelGGL(k_rank_eval<VFM_RANK_TOP>, grid, dim3(256), 0, st, a); break;
-    case VFM_RANK_VARIANCE: hipLaunchKernelGGL(k_rank_eval<VFM_RANK_VARIANCE>, grid, dim3(256), 0, st, a); break;
-    case VFM_RANK_MEAN: hipLaunchKernelGGL(k_rank_eval<VFM_RANK_MEAN>, grid, dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL(k_rank_eval<VFM_RANK_RANDOM>, grid, dim3(256), 0, st, a); break;
-  }
-  if (int rc = launch_status("k_rank_eval")) return rc;
-  hipLaunchKernelGGL(k_rank_eval_merge, dim3((unsigned)U), dim3(MERGE_WAVE), 0, st, U, L.S, n_pos, pos_ptr, a.hist_all,
-                     a.hist_neg, a.cnt_el, a.cnt_pos, (const int64_t*)(ws + L.off_slot), out_rank, out_rank_neg,
-                     out_n_eligible, out_n_neg);
-  return launch_status("k_rank_eval_merge");
+  a.out_rank = out_rank; a.out_rank_neg = out_rank_neg; a.out_n_eligible = out_n_eligible; a.out_n_neg = out_n_neg;
+  return vfm::launch_rank_eval(a, strategy, (unsigned)(L.U_pad / UT), st);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // vfm_rank_field.hip -- ranking one field's catalog for models with any number of fields (include/vfm_rank.h:
-// vfm_field_moments_f32, vfm_rank_field_f32).
+// vfm_field_moments_f32, vfm_rank_field_f32) and its held-out evaluation (vfm_rank_heldout_field_f32).
 //
 // With every field of a row but one fixed (the query's context), the row's closed-form moments are linear resp.
 // quadratic in the free entity c (include/vfm_foldin.h):
@@ -13,6 +13,10 @@
 // (vfm_rank_tile.hpp, vfm_rank_scan.hpp, k_rank of vfm_rank.hip).  Both parts are always packed (the merge recomputes the
 // winners' two moments from the query's packed row, whatever the strategy scored).
 //
+// The held-out evaluation packs the same operands, scores every positive from its query's packed row
+// (k_field_pos_score: field_pair_moments again) and hands over to the sort, scan and merge of the two-field evaluation
+// (vfm_rank_eval.hpp: vfm::launch_rank_eval, k_rank_eval of vfm_rank_eval.hip).
+//
 // Compiled with -ffp-contract=off: field_pair_moments' explicit fmaf chains are the MFMA chains of the tile, and the fp64
 // operand arithmetic (ctx_coord) rounds the same in k_field_ctx_prep and k_field_moments, bit for bit.
 #include <hip/hip_runtime.h>
@@ -22,6 +26,7 @@
 #include "vfm_rank.h"
 #include "vfm_rank_tile.hpp"
 #include "vfm_rank_scan.hpp"
+#include "vfm_rank_eval.hpp"
 
 namespace {
 
@@ -265,18 +270,53 @@ struct FieldMoments {
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
+// k_field_pos_score: one thread per held-out positive p: its query (the row of pos_ptr holding p) and the strategy's
+// score of (the query's context, p) from the query's packed row -- the chains of k_rank_merge<FieldMoments>, hence bit
+// for bit the tile's score and k_field_moments' score.  NaN for a context or candidate id outside [0, T).
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(POS_BLOCK) void k_field_pos_score(int64_t Q, int64_t n_pos, const int64_t* __restrict__ ctx,
+                                                               int F, int field, const int64_t* __restrict__ keys,
+                                                               const int64_t* __restrict__ pos_ptr,
+                                                               const int64_t* __restrict__ pos_items, int64_t T, int d,
+                                                               bool sp, int strat, uint64_t seed,
+                                                               const float* __restrict__ uop,
+                                                               const float* __restrict__ ucon, int Kp, int KA,
+                                                               const float* __restrict__ ent,
+                                                               const float* __restrict__ bias, float* __restrict__ raw,
+                                                               int64_t* __restrict__ pusr) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_pos) return;
+  int64_t row;
+  const int64_t q = pos_row_of(pos_ptr, Q, n_pos, p, row);
+  pusr[p] = row;
+  const int64_t iid = pos_items[p];
+  float sc = __builtin_nanf("");
+  if (iid >= 0 && iid < T && ctx_valid(ctx + q * F, F, field, T)) {
+    if (strat == VFM_RANK_RANDOM) {
+      sc = philox_uniform(seed, keys[q], iid);
+    } else {
+      float m, v;
+      field_pair_moments(StoredOp{uop + q * Kp, KA}, ent + iid * 2 * d, bias + iid * 2, ucon[q * 2], ucon[q * 2 + 1], d,
+                         sp, m, v);
+      sc = score_of(strat, m, v);
+    }
+  }
+  raw[p] = sc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-// The workspace: both operand parts for every strategy (no candidate block for VFM_RANK_RANDOM: no tile runs), the
-// position keys, the split lists.  Padding, tiles and the split count: op_layout_of.
-struct FieldLayout : ListLayout {
+// The operand part of a workspace: both operand parts for every strategy (no candidate block for VFM_RANK_RANDOM: no
+// tile runs) and the position keys.  Padding, tiles and the split count: op_layout_of.
+struct FieldOps {
   int KA, KB, Kp, S, n_tiles;
-  int64_t U_pad, C_pad, off_uop, off_iop, off_ucon, off_icon, off_key;
+  int64_t U_pad, C_pad, off_uop, off_iop, off_ucon, off_icon, off_key, end;
 };
 
-FieldLayout field_layout_of(int64_t Q, int64_t n_cand, int d, int k, int strategy, int n_splits) {
+FieldOps field_ops_of(int64_t Q, int64_t n_cand, int d, int strategy, int n_splits) {
   const OpLayout B = op_layout_of(Q, n_cand, d, strategy, n_splits);
-  FieldLayout L;
+  FieldOps L;
   L.KA = (int)round_up(d, KS);
   L.KB = (int)round_up(3 * (int64_t)d, KS);
   L.Kp = L.KA + L.KB;
@@ -287,8 +327,50 @@ FieldLayout field_layout_of(int64_t Q, int64_t n_cand, int d, int k, int strateg
   L.off_ucon = L.off_iop + round_up(c_rows * L.Kp * 4, 256);
   L.off_icon = L.off_ucon + round_up(L.U_pad * 2 * 4, 256);
   L.off_key = L.off_icon + round_up(c_rows * 2 * 4, 256);
-  static_cast<ListLayout&>(L) = list_layout_of(L.off_key + round_up(Q * 8, 256), L.S, Q, k);
+  L.end = L.off_key + round_up(Q * 8, 256);
   return L;
+}
+
+// The ranking's workspace: the operands, then the split lists
+struct FieldLayout : FieldOps, ListLayout {};
+
+FieldLayout field_layout_of(int64_t Q, int64_t n_cand, int d, int k, int strategy, int n_splits) {
+  FieldLayout L;
+  static_cast<FieldOps&>(L) = field_ops_of(Q, n_cand, d, strategy, n_splits);
+  static_cast<ListLayout&>(L) = list_layout_of(L.end, L.S, Q, k);
+  return L;
+}
+
+// The evaluation's workspace: the operands, then the eval tail
+struct FieldEvalLayout : FieldOps, EvalTail {};
+
+FieldEvalLayout field_eval_layout_of(int64_t Q, int64_t n_cand, int64_t n_pos, int d, int strategy, int n_splits) {
+  FieldEvalLayout L;
+  static_cast<FieldOps&>(L) = field_ops_of(Q, n_cand, d, strategy, n_splits);
+  static_cast<EvalTail&>(L) = eval_tail_of(L.end, L.S, Q, n_pos);
+  return L;
+}
+
+// k_field_ctx_prep and k_field_cand_prep into the operand blocks of L.  VFM_RANK_RANDOM: no tile runs, so the candidates
+// are never packed; the contexts only where their position keys are needed (ctx_rows false: the caller reads neither the
+// packed rows nor, with keys of its own, the position keys)
+int launch_field_prep(const FieldOps& L, char* ws, int64_t Q, const int64_t* ctx, int F, int field, const int64_t* qkey,
+                      int64_t n_cand, const int64_t* cand, int64_t cand_lo, int64_t T, int d, bool sp, int strategy,
+                      bool ctx_rows, const float* ent, const float* bias, const float* scal, hipStream_t st) {
+  if (ctx_rows || !qkey) {
+    hipLaunchKernelGGL(k_field_ctx_prep, dim3((unsigned)((L.U_pad + PREP_BLOCK / WAVE - 1) / (PREP_BLOCK / WAVE))),
+                       dim3(PREP_BLOCK), 0, st, L.U_pad, Q, ctx, F, field, T, L.Kp, L.KA, L.KB, d, sp, ent, bias, scal,
+                       (float*)(ws + L.off_uop), (float*)(ws + L.off_ucon),
+                       qkey ? (int64_t*)nullptr : (int64_t*)(ws + L.off_key));
+    if (int rc = launch_status("k_field_ctx_prep")) return rc;
+  }
+  const int64_t ni = L.C_pad * (L.Kp + 2);
+  if (strategy != VFM_RANK_RANDOM && ni > 0) {
+    hipLaunchKernelGGL(k_field_cand_prep, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, st, L.C_pad, n_cand, cand,
+                       cand_lo, T, L.Kp, L.KA, d, sp, ent, bias, (float*)(ws + L.off_iop), (float*)(ws + L.off_icon));
+    if (int rc = launch_status("k_field_cand_prep")) return rc;
+  }
+  return 0;
 }
 
 int check_fields(int32_t F, int32_t field) {
@@ -363,16 +445,9 @@ int vfm_rank_field_f32(int64_t Q, const int64_t* ctx, int32_t field, const int64
   float *uop = (float*)(ws + L.off_uop), *iop = (float*)(ws + L.off_iop), *ucon = (float*)(ws + L.off_ucon),
         *icon = (float*)(ws + L.off_icon);
   int64_t* keys = (int64_t*)(ws + L.off_key);
-  hipLaunchKernelGGL(k_field_ctx_prep, dim3((unsigned)((L.U_pad + PREP_BLOCK / WAVE - 1) / (PREP_BLOCK / WAVE))),
-                     dim3(PREP_BLOCK), 0, st, L.U_pad, Q, ctx, F, field, T, L.Kp, L.KA, L.KB, d, sp, entity_params,
-                     bias_params, scalars, uop, ucon, qkey ? (int64_t*)nullptr : keys);
-  if (int rc = launch_status("k_field_ctx_prep")) return rc;
-  const int64_t ni = L.C_pad * (L.Kp + 2);
-  if (strategy != VFM_RANK_RANDOM && ni > 0) {
-    hipLaunchKernelGGL(k_field_cand_prep, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, st, L.C_pad, n_cand, cand,
-                       cand_lo, T, L.Kp, L.KA, d, sp, entity_params, bias_params, iop, icon);
-    if (int rc = launch_status("k_field_cand_prep")) return rc;
-  }
+  if (int rc = launch_field_prep(L, ws, Q, ctx, F, field, qkey, n_cand, cand, cand_lo, T, d, sp, strategy, true,
+                                 entity_params, bias_params, scalars, st))
+    return rc;
   vfm::RankScan a;
   a.U = Q; a.n_cand = n_cand; a.item_lo = cand_lo; a.n_excl = excl_ptr ? n_excl : 0;
   a.keys = qkey ? qkey : keys; a.cand = cand; a.excl_ptr = excl_ptr; a.excl_items = excl_items;
@@ -385,6 +460,67 @@ int vfm_rank_field_f32(int64_t Q, const int64_t* ctx, int32_t field, const int64
                      cand_lo, FieldMoments{uop, ucon, L.Kp, L.KA, T, d, sp, entity_params, bias_params}, out_items,
                      out_score, out_mean, out_var);
   return launch_status("k_rank_merge");
+}
+
+int64_t vfm_rank_eval_field_workspace_bytes(int64_t Q, int64_t n_cand, int64_t n_pos, int32_t F, int32_t d,
+                                            int32_t strategy, int32_t n_splits) {
+  if (!eval_sizes_ok(Q, n_cand, n_pos) || F < 2 || F > VFM_MAX_FIELDS || d < 1 || d > 4096 ||
+      strategy < VFM_RANK_TOP || strategy > VFM_RANK_RANDOM || n_splits < 0 || n_splits > VFM_RANK_MAX_SPLITS)
+    return VFM_E_INVALID;
+  return field_eval_layout_of(Q, n_cand, n_pos, d, strategy, n_splits).bytes;
+}
+
+int vfm_rank_heldout_field_f32(int64_t Q, const int64_t* ctx, int32_t field, const int64_t* qkey, int64_t n_cand,
+                               const int64_t* cand, int64_t cand_lo, int64_t T, int32_t F, int32_t d, int32_t strategy,
+                               int32_t flags, uint64_t seed, int32_t n_splits, const int64_t* excl_ptr,
+                               const int64_t* excl_items, int64_t n_excl, const int64_t* pos_ptr,
+                               const int64_t* pos_items, int64_t n_pos, const float* entity_params,
+                               const float* bias_params, const float* scalars, void* workspace, int64_t workspace_bytes,
+                               int64_t* out_rank, int64_t* out_rank_neg, int64_t* out_n_eligible, int64_t* out_n_neg,
+                               void* stream) {
+  if (int rc = check_common(T, d, flags, strategy)) return rc;
+  if (int rc = check_fields(F, field)) return rc;
+  if (Q < 0) return vfm::fail(VFM_E_INVALID, "Q < 0");
+  if (n_cand < 0 || n_cand >= ((int64_t)1 << 31)) return vfm::fail(VFM_E_INVALID, "n_cand out of range [0,2^31)");
+  if (n_pos < 0 || n_pos >= ((int64_t)1 << 40)) return vfm::fail(VFM_E_INVALID, "n_pos out of range [0,2^40)");
+  if (n_splits < 0 || n_splits > VFM_RANK_MAX_SPLITS) return vfm::fail(VFM_E_INVALID, "n_splits out of range [0,64]");
+  if (!cand && (cand_lo < 0 || cand_lo + n_cand > T)) return vfm::fail(VFM_E_INVALID, "candidate range outside [0,T)");
+  if (n_excl < 0 || (n_excl > 0 && (!excl_ptr || !excl_items)))
+    return vfm::fail(VFM_E_INVALID, "exclusion lists: excl_ptr and excl_items together, n_excl >= 0");
+  if (n_pos > 0 && !pos_items) return vfm::fail(VFM_E_INVALID, "null pointer: pos_items");
+  if (Q == 0) return 0;
+  if (!ctx || !pos_ptr || !entity_params || !bias_params || !scalars || !workspace || !out_n_eligible || !out_n_neg ||
+      (n_pos > 0 && (!out_rank || !out_rank_neg)))
+    return vfm::fail(VFM_E_INVALID, "null pointer");
+  const FieldEvalLayout L = field_eval_layout_of(Q, n_cand, n_pos, d, strategy, n_splits);
+  if (workspace_bytes < L.bytes)
+    return vfm::fail(VFM_E_INVALID, "workspace too small (vfm_rank_eval_field_workspace_bytes)");
+  if (((uintptr_t)workspace) & 255) return vfm::fail(VFM_E_INVALID, "workspace must be 256-byte aligned");
+
+  const hipStream_t st = (hipStream_t)stream;
+  const bool sp = (flags & VFM_FLAG_LINK_SOFTPLUS) != 0;
+  char* ws = (char*)workspace;
+  if (int rc = launch_field_prep(L, ws, Q, ctx, F, field, qkey, n_cand, cand, cand_lo, T, d, sp, strategy,
+                                 strategy != VFM_RANK_RANDOM, entity_params, bias_params, scalars, st))
+    return rc;
+  vfm::RankEval a;
+  a.U = Q; a.n_cand = n_cand; a.item_lo = cand_lo; a.n_excl = excl_ptr ? n_excl : 0; a.n_pos = n_pos;
+  a.keys = qkey ? qkey : (const int64_t*)(ws + L.off_key); a.cand = cand; a.excl_ptr = excl_ptr;
+  a.excl_items = excl_items; a.pos_ptr = pos_ptr; a.pos_items = pos_items;
+  a.uop = (const float*)(ws + L.off_uop); a.iop = (const float*)(ws + L.off_iop);
+  a.ucon = (const float*)(ws + L.off_ucon); a.icon = (const float*)(ws + L.off_icon);
+  a.Kp = L.Kp; a.KA = L.KA; a.KB = L.KB;
+  eval_tail_into(a, ws, L);
+  a.n_tiles = L.n_tiles; a.S = L.S; a.seed = seed;
+  a.out_rank = out_rank; a.out_rank_neg = out_rank_neg; a.out_n_eligible = out_n_eligible; a.out_n_neg = out_n_neg;
+  if (n_pos > 0) {
+    hipLaunchKernelGGL(k_field_pos_score, dim3((unsigned)((n_pos + POS_BLOCK - 1) / POS_BLOCK)), dim3(POS_BLOCK), 0, st,
+                       Q, n_pos, ctx, (int)F, (int)field, a.keys, pos_ptr, pos_items, T, (int)d, sp, (int)strategy, seed,
+                       a.uop, a.ucon, L.Kp, L.KA, entity_params, bias_params, (float*)(ws + L.off_raw),
+                       (int64_t*)(ws + L.off_pusr));
+    if (int rc = launch_status("k_field_pos_score")) return rc;
+  }
+  return vfm::launch_rank_eval(a, strategy, (unsigned)(L.U_pad / UT), st);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // vfm_rank_ops.cpp -- torch.ops.vfm_hip.{predictive_moments, rank_items, rank_workspace_bytes, rank_heldout,
-// rank_eval_workspace_bytes, field_moments, rank_field, rank_field_workspace_bytes}: the TORCH_LIBRARY fragment over include/vfm_rank.h.  Like vfm_torch_ops.cpp it only validates tensors, takes the current HIP stream
+// rank_eval_workspace_bytes, field_moments, rank_field, rank_field_workspace_bytes, rank_heldout_field,
+// rank_eval_field_workspace_bytes}: the TORCH_LIBRARY fragment over include/vfm_rank.h.  Like vfm_torch_ops.cpp it only validates tensors, takes the current HIP stream
 // of the tensors' device and forwards raw pointers; all arithmetic is in the HIP kernels.
 #include <ATen/ATen.h>
 #include <c10/hip/HIPGuard.h>
@@ -226,6 +227,61 @@ void rank_field(const Tensor& ctx, int64_t field, const optional<Tensor>& qkey, 
         "vfm_rank_field_f32");
 }
 
+int64_t rank_eval_field_workspace_bytes(int64_t Q, int64_t n_cand, int64_t n_pos, int64_t F, int64_t d, int64_t strategy,
+                                        int64_t n_splits) {
+  const int64_t b = vfm_rank_eval_field_workspace_bytes(Q, n_cand, n_pos, (int32_t)F, (int32_t)d, (int32_t)strategy,
+                                                        (int32_t)n_splits);
+  TORCH_CHECK(b >= 0, "vfm_rank_eval_field_workspace_bytes: bad arguments");
+  return b;
+}
+
+void rank_heldout_field(const Tensor& ctx, int64_t field, const optional<Tensor>& qkey, const optional<Tensor>& cand,
+                        int64_t n_cand, int64_t cand_lo, const optional<Tensor>& excl_ptr,
+                        const optional<Tensor>& excl_items, const Tensor& pos_ptr, const Tensor& pos_items,
+                        const Tensor& entity, const Tensor& bias, const Tensor& scalars, Tensor workspace, Tensor rank,
+                        Tensor rank_neg, Tensor n_eligible, Tensor n_neg, int64_t strategy, int64_t flags, int64_t seed,
+                        int64_t n_splits) {
+  dev_tensor(ctx, at::kLong, "ctx");
+  TORCH_CHECK(ctx.dim() == 2, "ctx must be [Q,F]");
+  tables(entity, bias, scalars);
+  const int64_t Q = ctx.size(0);
+  const int64_t *kp = nullptr, *cp = nullptr;
+  if (qkey.has_value() && qkey->defined()) {
+    TORCH_CHECK(dev_tensor(*qkey, at::kLong, "qkey").numel() == Q, "qkey must hold one key per query");
+    kp = qkey->data_ptr<int64_t>();
+  }
+  if (cand.has_value() && cand->defined()) {
+    TORCH_CHECK(dev_tensor(*cand, at::kLong, "cand").numel() == n_cand, "cand must hold n_cand ids");
+    cp = cand->data_ptr<int64_t>();
+  }
+  const int64_t *ep = nullptr, *ei = nullptr;
+  int64_t n_excl = 0;
+  if (excl_ptr.has_value() && excl_ptr->defined()) {
+    TORCH_CHECK(dev_tensor(*excl_ptr, at::kLong, "excl_ptr").numel() == Q + 1, "excl_ptr needs Q + 1 offsets");
+    TORCH_CHECK(excl_items.has_value() && excl_items->defined(), "excl_ptr without excl_items");
+    ep = excl_ptr->data_ptr<int64_t>();
+    n_excl = dev_tensor(*excl_items, at::kLong, "excl_items").numel();
+    ei = n_excl > 0 ? excl_items->data_ptr<int64_t>() : nullptr;
+  }
+  TORCH_CHECK(dev_tensor(pos_ptr, at::kLong, "pos_ptr").numel() == Q + 1, "pos_ptr needs Q + 1 offsets");
+  const int64_t n_pos = dev_tensor(pos_items, at::kLong, "pos_items").numel();
+  dev_tensor(workspace, at::kByte, "workspace");
+  dev_tensor(rank, at::kLong, "rank"); dev_tensor(rank_neg, at::kLong, "rank_neg");
+  dev_tensor(n_eligible, at::kLong, "n_eligible"); dev_tensor(n_neg, at::kLong, "n_neg");
+  TORCH_CHECK(rank.numel() >= n_pos && rank_neg.numel() >= n_pos && n_eligible.numel() >= Q && n_neg.numel() >= Q,
+              "output sizes");
+  c10::hip::HIPGuard guard(ctx.get_device());
+  check(vfm_rank_heldout_field_f32(Q, ctx.data_ptr<int64_t>(), (int32_t)field, kp, n_cand, cp, cand_lo, entity.size(0),
+                                   (int32_t)ctx.size(1), (int32_t)(entity.size(1) / 2), (int32_t)strategy,
+                                   (int32_t)flags, (uint64_t)seed, (int32_t)n_splits, ep, ei, n_excl,
+                                   pos_ptr.data_ptr<int64_t>(), n_pos > 0 ? pos_items.data_ptr<int64_t>() : nullptr,
+                                   n_pos, entity.data_ptr<float>(), bias.data_ptr<float>(), scalars.data_ptr<float>(),
+                                   workspace.data_ptr(), workspace.numel(), rank.data_ptr<int64_t>(),
+                                   rank_neg.data_ptr<int64_t>(), n_eligible.data_ptr<int64_t>(),
+                                   n_neg.data_ptr<int64_t>(), stream_of(ctx)),
+        "vfm_rank_heldout_field_f32");
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(vfm_hip, m) {
@@ -258,4 +314,11 @@ TORCH_LIBRARY_FRAGMENT(vfm_hip, m) {
         "Tensor(b!) items, Tensor(c!) score, Tensor(d!) logit_mean, Tensor(e!) logit_var, int k, int strategy, "
         "int flags, int seed, int n_splits) -> ()",
         &rank_field);
+  m.def("rank_eval_field_workspace_bytes(int Q, int n_cand, int n_pos, int F, int d, int strategy, int n_splits) -> int",
+        &rank_eval_field_workspace_bytes);
+  m.def("rank_heldout_field(Tensor ctx, int field, Tensor? qkey, Tensor? cand, int n_cand, int cand_lo, "
+        "Tensor? excl_ptr, Tensor? excl_items, Tensor pos_ptr, Tensor pos_items, Tensor entity_params, "
+        "Tensor bias_params, Tensor scalars, Tensor(a!) workspace, Tensor(b!) rank, Tensor(c!) rank_neg, "
+        "Tensor(d!) n_eligible, Tensor(e!) n_neg, int strategy, int flags, int seed, int n_splits) -> ()",
+        &rank_heldout_field);
 }

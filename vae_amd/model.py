@@ -1110,6 +1110,56 @@ class VFM(nn.Module):
             means["per_user"] = dict(users=r["users"], **per)
         return means
 
+    @torch.no_grad()
+    def rank_heldout_field(self, pos, field: int, exclude=None, candidates=None, match_fields=None,
+                           key_field: Optional[int] = None, strategy: str = "top", seed: int = 0, n_splits: int = 0,
+                           ineligible: str = "raise"):
+        """Where held-out positives land in their contexts' full rankings of one field, any number of fields (>= 2):
+        the field form of rank_heldout (include/vfm_rank.h).  pos: [P, F] full rows -- column `field` the held-out
+        positive, the other columns its context; a query is a distinct context, duplicate rows are dropped.  candidates,
+        exclude, match_fields, key_field, strategy, seed, n_splits: as rank_field.  The eligible candidates E_q of query
+        q are the candidates minus q's exclusions; "c beats i" is rank_field's order (larger score, or equal scores and
+        the lower id), the scores bitwise field_moments of the row.  Every positive must lie in E_q: ineligible="raise"
+        (default) raises ValueError naming the first such row, "drop" removes those rows before the launch and counts
+        them in n_dropped (with match_fields=(0,) a test row whose user saw the item in another format during training
+        is excluded by design).
+        Returns dict(contexts [Q, F] (column `field` zeroed, sorted rows), ptr [Q+1], items [n] (the positives, ascending
+        per query), query_index [n], rank [n] = #{c in E_q : c beats i} (item [rank] of rank_field(contexts, k) whenever
+        rank < k), rank_neg [n] = #{c in E_q \\ Pos_q : c beats i}, n_eligible [Q] = |E_q|, n_neg [Q] = |E_q \\ Pos_q|,
+        n_dropped), the tensors int64 and bitwise deterministic (independent of n_splits and of the other queries)."""
+        return rank.rank_heldout_field(self, pos, field, exclude, candidates, match_fields, key_field, strategy, seed,
+                                       n_splits, ineligible)
+
+    @torch.no_grad()
+    def evaluate_ranking_field(self, X_test, y_test, field: int, ks=(10,), exclude=None, candidates=None,
+                               match_fields=None, threshold: Optional[float] = None, per_query: bool = False,
+                               ineligible: str = "raise"):
+        """Held-out top-k ranking metrics over one field's full catalog, any number of fields (>= 2): the field form of
+        evaluate_ranking.  X_test [B, F] full rows; a query is a distinct context (a row with column `field` ignored);
+        its relevant test entities of `field` are ranked against every eligible candidate (`candidates`, default the
+        field's whole range, minus the exclusions of rank_field: `exclude`, `match_fields`) by the logit mean.  Relevant:
+        y >= threshold for 'reg' (default 4.0), y == 1 for 'class'.  ineligible: as rank_heldout_field.  Metrics: those of
+        evaluate_ranking (vae_amd.rank.ranking_metrics).  Returns {metric: mean over the queries with a relevant row
+        (auc: and a negative)}, plus "n_users", which here counts QUERIES (distinct contexts with a relevant row), not
+        users; with per_query=True also "per_query": {"contexts": [Q, F], metric: [Q] float64}."""
+        ks = [int(k) for k in ks]
+        if not ks or any(k <= 0 for k in ks):
+            raise ValueError("ks must be a non-empty list of positive ints")
+        X = torch.as_tensor(X_test)
+        y = torch.as_tensor(y_test).reshape(-1)
+        if X.dim() != 2 or X.shape[1] != self.F or X.shape[0] != y.numel():
+            raise ValueError(f"X_test must be [B, {self.F}] with one y_test value per row")
+        if self.output == "reg":
+            relevant = y >= (4.0 if threshold is None else float(threshold))
+        else:
+            relevant = y == 1
+        r = rank.rank_heldout_field(self, X[relevant.to(X.device)], field, exclude, candidates, match_fields, None, "top",
+                                    0, 0, ineligible)
+        means, per = rank.ranking_metrics(r["rank"], r["rank_neg"], r["ptr"], r["n_neg"], ks)
+        if per_query:
+            means["per_query"] = dict(contexts=r["contexts"], **per)
+        return means
+
     # ------------------------------------------------------------------ fold-in (vae_amd/foldin.py)
     @torch.no_grad()
     def fold_in(self, X, y, field: int = 0, n_steps: int = 200, lr: float = 0.05, objective: Optional[str] = None,

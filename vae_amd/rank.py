@@ -300,6 +300,102 @@ def rank_field(model, contexts, field, k: int = 10, strategy: str = "top", candi
     return out
 
 
+def field_positive_csr(rows: torch.Tensor, field: int, T: int):
+    """The positives of rank_heldout_field grouped by query: rows [P, F] int64 full rows (column `field` the positive
+    candidate, the other columns its context; any device).  Returns (contexts [Q, F] -- the distinct contexts with column
+    `field` zeroed, in the row order of torch.unique(dim=0) --, ptr [Q+1] int64, items [n] int64 ascending per query,
+    duplicate rows dropped)."""
+    x = rows.to(torch.int64)
+    if x.shape[0] == 0:
+        return x.clone(), torch.zeros(1, dtype=torch.int64, device=x.device), x.new_zeros(0)
+    ids = x[:, field].clone()
+    ctx = x.clone()
+    ctx[:, field] = 0
+    uq, inv = torch.unique(ctx, dim=0, return_inverse=True)
+    q = torch.arange(uq.shape[0], device=x.device)
+    ptr, items = exclusion_csr(q, torch.stack([inv.reshape(-1), ids], 1), T)
+    return uq, ptr, items
+
+
+def rank_heldout_field(model, pos, field, exclude=None, candidates=None, match_fields=None, key_field=None,
+                       strategy: str = "top", seed: int = 0, n_splits: int = 0, ineligible: str = "raise"):
+    """Exact positions of held-out positives in their contexts' full rankings of one field (model.rank_heldout_field
+    documents the arguments and outputs)."""
+    from .foldin import field_range
+    field = _field_arg(model, field)
+    code = strategy_code(strategy)
+    if strategy == "mean" and model.output != "class":
+        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
+    if not 0 <= int(n_splits) <= MAX_SPLITS:
+        raise ValueError(f"n_splits must lie in [0, {MAX_SPLITS}]")
+    if ineligible not in ("raise", "drop"):
+        raise ValueError(f"ineligible must be 'raise' or 'drop', not {ineligible!r}")
+    kf = _key_field(model, field, key_field)
+    ctx_cols = [f for f in range(model.F) if f != field]
+    if match_fields is None:
+        match = ctx_cols
+    else:
+        match = sorted({int(f) for f in match_fields})
+        if any(f not in ctx_cols for f in match):
+            raise ValueError(f"match_fields must be context columns, a subset of {ctx_cols}")
+    dev, T = model.device, model.T
+    lo, hi = field_range(model, field)
+    pos = _context_rows(model, pos, "pos", field, check_field_column=True)
+    cand, n_cand = None, hi - lo
+    if candidates is not None:
+        cand = torch.as_tensor(candidates).to(dev, torch.int64).reshape(-1)
+        if cand.numel() and (int(cand.min()) < lo or int(cand.max()) >= hi):
+            raise ValueError(f"candidate ids must lie in the field's range [{lo}, {hi})")
+        cand = torch.sort(cand).values
+        if cand.numel() > 1 and bool((cand[1:] == cand[:-1]).any()):
+            raise ValueError("duplicate candidates")
+        n_cand = cand.numel()
+    ex = _context_rows(model, exclude, "exclude", field, check_field_column=True) if exclude is not None else None
+    ops._need_cuda(model._flat, "the model's parameters")
+    uq, pptr, pitems = field_positive_csr(pos, field, T)
+    Q = uq.shape[0]
+    pq = torch.repeat_interleave(torch.arange(Q, device=dev), pptr[1:] - pptr[:-1])
+    # eligibility (torch, on the device): every positive is a candidate and not excluded
+    bad = torch.zeros(pitems.numel(), dtype=torch.bool, device=dev)
+    if cand is not None:
+        j = torch.searchsorted(cand, pitems).clamp_(max=max(n_cand - 1, 0))
+        bad |= (cand[j] != pitems) if n_cand > 0 else torch.ones_like(bad)
+    eptr = ex_items = None
+    if ex is not None:
+        eptr, ex_items = field_exclusion_csr(uq, ex, field, match, T)
+        ekey = torch.repeat_interleave(torch.arange(Q, device=dev), eptr[1:] - eptr[:-1]) * T + ex_items   # sorted
+        if ekey.numel():
+            pkey = pq * T + pitems
+            j = torch.searchsorted(ekey, pkey).clamp_(max=ekey.numel() - 1)
+            bad |= ekey[j] == pkey
+    n_dropped = int(bad.sum())
+    if n_dropped:
+        if ineligible == "raise":
+            j = int(torch.nonzero(bad)[0, 0])
+            row = uq[pq[j]].clone()
+            row[field] = pitems[j]
+            raise ValueError(f"positive row {row.tolist()} is not an eligible candidate of its context (excluded, or "
+                             "outside `candidates`); ineligible='drop' removes such rows")
+        keep = ~bad
+        pitems, pq = pitems[keep].contiguous(), pq[keep]
+        pptr = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(torch.bincount(pq, minlength=Q), 0, out=pptr[1:])
+    model._fresh_params()
+    ent, bia, scal = model._views(model._flat)
+    n_pos = pitems.numel()
+    i64 = dict(dtype=torch.int64, device=dev)
+    out = {"contexts": uq, "ptr": pptr, "items": pitems, "query_index": pq, "rank": torch.empty(n_pos, **i64),
+           "rank_neg": torch.empty(n_pos, **i64), "n_eligible": torch.empty(Q, **i64), "n_neg": torch.empty(Q, **i64),
+           "n_dropped": n_dropped}
+    o = _lib.ops()
+    ws = torch.empty(max(o.rank_eval_field_workspace_bytes(Q, n_cand, n_pos, model.F, model.d, code, int(n_splits)), 1),
+                     dtype=torch.uint8, device=dev)
+    o.rank_heldout_field(uq.contiguous(), field, uq[:, kf].contiguous(), cand, n_cand, lo, eptr, ex_items, pptr, pitems,
+                         ent, bia, scal, ws, out["rank"], out["rank_neg"], out["n_eligible"], out["n_neg"], code,
+                         ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, _seed64(seed), int(n_splits))
+    return out
+
+
 def _candidates(model, items):
     """(cand sorted int64 or None, n_cand) of rank_items' `items` argument."""
     N, M, T = model.N, model.M, model.T
