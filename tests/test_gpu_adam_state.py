@@ -49,8 +49,6 @@ Measured on an MI355X, worst error / bound over the cases of an entry point (m',
   small table, one launch        scaled  0.009  0.381  0.454   0.005  0.298  0.470   0.003  0.218  0.435
   small table, three launches    as the one-launch rows, digit for digit
   heavy lists                    scaled  0.008  0.341  0.473   0.007  0.319  0.472   0.003  0.086  0.431
-  prefetch / 8 lanes             plain   0.005  0.204  0.455   0.003  0.191  0.467   0.001  0.211  0.436
-  prefetch / 8 lanes             scaled  0.009  0.381  0.454   0.004  0.280  0.466   0.003  0.218  0.435
   lazy (catch-up + touched)      scaled  0.659  0.387  0.456   0.701  0.350  0.437   0.068  0.170  0.480
   look-ahead, listed and scan    scaled  0.009  0.361  0.458   0.008  0.354  0.459   0.013  0.264  0.308
   acc + apply, two chunks        plain   0.004  0.204  0.455   0.003  0.184  0.470   0.001  0.111  0.436
@@ -328,17 +326,6 @@ def test_heavy_lists_step(d):
         assert c.plan.heavy is not None and c.plan.heavy[0].numel() >= 4
         _dense(c)
     _case("heavy", pb, 57, "scaled", run=run)
-
-
-# ------------------------------------------------------------------------------------------------ d. prefetch, 8 lanes
-@pytest.mark.parametrize("env,d", [("VFM_BWD_PREFETCH", 32), ("VFM_BWD_PREFETCH", 128), ("VFM_BWD_LANES8", 128)])
-@pytest.mark.parametrize("form", ["plain", "scaled"])
-def test_prefetch_and_eight_lane_instances(env, d, form, monkeypatch):
-    """k_bwd<PF> / k_bwd<16, 2, 4, ADJ> (Philox, one sample, the three-launch path so that k_bwd runs at these sizes)."""
-    monkeypatch.setenv("VFM_BWD_SMALL", "0")
-    monkeypatch.setenv(env, "1")
-    pb = build_problem(2, d, "reg", seed=300 + d)
-    _case(env, pb, 57, form, eps="philox", run=_dense)
 
 
 # ------------------------------------------------------------------------------------------------ e. lazy exact Adam

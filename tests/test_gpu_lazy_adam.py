@@ -144,3 +144,86 @@ def test_lazy_forms_with_heavy_lists_are_bitwise_the_dense_trajectory(form):
     lz.sync_lazy()
     assert torch.equal(dense._flat, lz._flat)
     assert torch.equal(dense._adam_m, lz._adam_m) and torch.equal(dense._adam_v, lz._adam_v)
+
+
+# ---- hand-placed lists: what the sparse synthetic batches above do not hold at d = 128
+SIZES = (200, 100)          # T = 300 table rows: users 0..199, items 200..299
+B, NB, STEPS = 400, 6, 140  # six batches in turn; 140 steps cross the moment-period boundary at step 128
+ONCE, TWICE, RARE = 0, 1, 2            # users: a list of length 1, of length 2 (batch 1); in batch 0 only (replay gap 4)
+HEAVY, HEAVIER = 200, 201              # items of batch 1: 12 rows (2 work items of 8), 80 rows (10 > VFM_HEAVY_DIRECT)
+HEAVY_MIN, HEAVY_DIRECT = 8, 8         # include/vfm_hip.h; a table this small cuts its lists in work items of 8
+
+
+def _batches(device):
+    """Six batches of B rows over T = 300.  Batch b draws from the 60 % of the users and of the items with (id + b) % 5 >= 2,
+    so a step has rows in both batches, rows in the next batch only and rows in neither; the special ids are placed by hand."""
+    g = torch.Generator().manual_seed(33)
+    special_u, special_i = (ONCE, TWICE, RARE), (HEAVY, HEAVIER)
+    xs = []
+    for b in range(NB):
+        users = torch.tensor([u for u in range(SIZES[0]) if (u + b) % 5 >= 2 and u not in special_u])
+        items = torch.tensor([i for i in range(SIZES[0], sum(SIZES)) if (i + b) % 5 >= 2 and i not in special_i])
+        x = torch.stack([users[torch.randint(0, len(users), (B,), generator=g)],
+                         items[torch.randint(0, len(items), (B,), generator=g)]], 1)
+        if b == 0:
+            x[7, 0] = RARE
+            x[250, 0] = RARE
+        if b == 1:
+            x[5, 0] = ONCE
+            x[40, 0] = TWICE
+            x[399, 0] = TWICE
+            x[100:112, 1] = HEAVY
+            x[200:280, 1] = HEAVIER
+        xs.append(x)
+    X = torch.cat(xs).to(device)
+    y = torch.randint(1, 6, (NB * B,), generator=g).to(torch.float32).to(device)
+    return X, y
+
+
+def _check_shape_of_data(X):
+    """What the cases are there for, checked on the data itself."""
+    T = sum(SIZES)
+    cnt = [torch.bincount(X[b * B:(b + 1) * B].reshape(-1), minlength=T) for b in range(NB)]
+    assert cnt[1][ONCE] == 1 and cnt[1][TWICE] == 2
+    assert HEAVY_MIN < cnt[1][HEAVY] <= HEAVY_MIN * HEAVY_DIRECT and cnt[1][HEAVIER] > HEAVY_MIN * HEAVY_DIRECT
+    assert cnt[0][RARE] > 0 and all(cnt[b][RARE] == 0 for b in range(1, NB))      # replays NB - 2 = 4 steps when batch 0 is next
+    for b in range(NB):
+        cur, nxt = cnt[b] > 0, cnt[(b + 1) % NB] > 0
+        assert (cur & nxt).any() and (cur & ~nxt).any() and (~cur & nxt).any() and (~cur & ~nxt).any()
+
+
+def _run_placed(X, y, attrs):
+    from vae_amd.model import VFM
+    torch.manual_seed(4)
+    m = VFM(field_sizes=list(SIZES), embedding_size=128, device="cuda", rng_seed=6)
+    m.pipeline = False
+    for k_, v_ in attrs.items():
+        setattr(m, k_, v_)
+    m.set_training_data(X, nb_train=NB * B)
+    plans = [m.plan(X[i * B:(i + 1) * B], y[i * B:(i + 1) * B]) for i in range(NB)]
+    losses = []
+    for s in range(STEPS):
+        nxt = {"next_plan": plans[(s + 1) % NB]} if m.lookahead else {}
+        losses.append(m.train_step(plans[s % NB], lr=0.03 if s % 5 else 0.01, **nxt)[0].clone())
+    for pl in plans:
+        pl.check_status()
+    if m.lookahead:
+        assert m._lazy_dirty and (m._lazy_last < STEPS - 2).any()      # rows do lag at the end: the look-ahead form ran
+        m.sync_lazy()
+    out = {"loss": torch.stack(losses), "flat": m._flat.clone(), "m": m._adam_m.clone(), "v": m._adam_v.clone()}
+    assert not torch.isnan(out["flat"]).any()
+    return out
+
+
+@pytest.mark.parametrize("listed", [True, False], ids=["listed", "scan"])
+def test_lookahead_on_hand_placed_lists_is_bitwise_the_dense_trajectory(listed, monkeypatch):
+    """d = 128, T = 300 under B = 400: losses, parameters and both moments BIT FOR BIT over 140 steps, the look-ahead step
+    against the dense one on the same plans -- lists of length 1 and 2, a pre-reduced list added in the kernel and one added
+    by k_heavy_sum, rows in both batches / the next only / neither, a row that replays four steps."""
+    monkeypatch.setenv("VFM_BWD_SMALL", "0")      # the period-end / dense steps of this small table through k_bwd as well
+    X, y = _batches("cuda")
+    _check_shape_of_data(X)
+    la = _run_placed(X, y, dict(lookahead=True, lookahead_list=listed))
+    dense = _run_placed(X, y, dict(lookahead=False))
+    for k_ in dense:
+        assert torch.equal(la[k_], dense[k_]), k_

@@ -16,12 +16,12 @@ WANT = [
     ("vfm_fwd2.hip", [], "k_fwd2<16, true, 0, 1, true, 0, true>", "cfg3 forward (d = 128, Philox, training, int64 ids, |.| link, packed records)"),
     ("vfm_fwd2.hip", [], "k_fwd2<4, false, 0, 1, true, 0, true>", "cfg2 forward (d = 20)"),
     ("vfm_fwdg.hip", [], "k_fwdg<32, true, 0, 1, true, 0, true>", "cfg5 forward (F = 32, d = 256: fields split over lane groups)"),
-    ("vfm_bwd.hip", ["-ffp-contract=on", "-DVFM_BWD_PART=1"], "k_bwd<32, 1, 4, 0, 1, 0, 0, false, false, true, false>", "cfg3 fused backward + dense Adam, look-ahead form"),
-    ("vfm_bwd.hip", ["-ffp-contract=on", "-DVFM_BWD_PART=1"], "k_bwd<64, 1, 4, 0, 1, 0, 0, false, false, true, false>", "cfg5 fused backward + dense Adam, look-ahead form"),
-    ("vfm_bwd.hip", ["-ffp-contract=on", "-DVFM_BWD_PART=1"], "k_bwd<32, 1, 4, 0, 1, 0, 0, false, false, true, true>", "the same with the index fetched one row ahead (VFM_BWD_PREFETCH=1)"),
-    ("vfm_bwd.hip", ["-ffp-contract=on", "-DVFM_BWD_PART=1"], "k_bwd<32, 1, 4, 0, 1, 0, 0, false, true, true, false>", "pipelined step's backward in the look-ahead form (data-file-order batches; the rows exchange)"),
+    ("vfm_bwd.hip", ["-ffp-contract=on", "-DVFM_BWD_PART=1"], "k_bwd<32, 1, 4, 0, 1, 0, 0, false, false, true>", "cfg3 fused backward + dense Adam, look-ahead form"),
+    ("vfm_bwd.hip", ["-ffp-contract=on", "-DVFM_BWD_PART=1"], "k_bwd<64, 1, 4, 0, 1, 0, 0, false, false, true>", "cfg5 fused backward + dense Adam, look-ahead form"),
+    ("vfm_bwd.hip", ["-ffp-contract=on", "-DVFM_BWD_PART=1"], "k_bwd<32, 1, 4, 0, 1, 0, 0, false, true, true>", "pipelined step's backward in the look-ahead form (data-file-order batches; the rows exchange)"),
     ("vfm_bwd.hip", ["-ffp-contract=on", "-DVFM_BWD_PART=1"], "k_bwd_small<8, 0>", "cfg2 one-launch backward + dense Adam (a wave per table row)"),
-    ("vfm_bwd.hip", ["-ffp-contract=on", "-DVFM_BWD_PART=1"], "k_bwd<32, 1, 4, 0, 1, 2, 0, false, false, false, false>", "multi-rank apply stage (epilogue + Adam from the summed statistics)"),
+    ("vfm_bwd.hip", ["-ffp-contract=on", "-DVFM_BWD_PART=1"], "k_bwd_small<32, 0>", "the same at d = 128"),
+    ("vfm_bwd.hip", ["-ffp-contract=on", "-DVFM_BWD_PART=1"], "k_bwd<32, 1, 4, 0, 1, 2, 0, false, false, false>", "multi-rank apply stage (epilogue + Adam from the summed statistics)"),
     ("vfm_abi.hip", ["-ffp-contract=on"], "k_heavy<32, 1, 4>", "pre-reduction of the long lists' work items (eight occurrences in flight, the next eight's row numbers fetched under them)"),
     ("vfm_index.hip", [], "k_index_keys", "index build: ids -> keys, first digit counts, batch normalisers"),
     ("vfm_index.hip", [], "k_radix_scatter<true>", "index build: last radix pass (writes occ_rows / occ_other)"),

@@ -6,6 +6,8 @@
 // gfx950 only, wave = 64.  See vfm_args.hpp for how libvfm_hip.so is split into translation units.
 #include <math.h>
 
+#include <type_traits>
+
 #include "vfm_args.hpp"
 
 #ifndef VFM_LINK
@@ -32,70 +34,42 @@ constexpr int LINK = VFM_LINK;
 template <int LPE, int CPL, int VEC, int EPS, int ADAM, int STAGE = STAGE_FULL>
 int launch_bwd_t(KArgs& a, const BwdArgs& b, const AdamArgs& ad, hipStream_t st) {
   const int per_cu = env_int("VFM_BWD_BLOCKS_PER_CU", 8);
-  auto grid_of = [&](int gpb) -> int64_t {      // workgroups for lane groups of BLOCK / gpb lanes
-    int64_t nb = (a.e_hi - a.e_lo + gpb - 1) / gpb;
-    if (ADAM != 0 && b.row_ids) nb = (b.n_rows + gpb - 1) / gpb;     // the listed rows only
-    const int64_t cap = 256LL * per_cu;
-    if (nb > cap) nb = cap;
-    // VFM_FLAG_SHARE_GPU: 15/16 of the 1,024 workgroups the chip holds (126 VGPRs: four per CU), so that another stream's small
-    // kernels (256 threads, <= 128 VGPRs: csrc/vfm_index.hip) find a free slot on 64 CUs while this one runs
-    { const int share = env_int("VFM_SHARE_CAP", 960); if ((a.flags & VFM_FLAG_SHARE_GPU) && share > 0 && nb > share) nb = share; }
-    { const int forced = env_int("VFM_BWD_GRID", 0); if (forced > 0 && nb > forced) nb = forced; }      // (A/B runs)
-    return nb < 1 ? 1 : nb;
+  constexpr int GPB = BLOCK / LPE;               // lane groups (table rows) per workgroup
+  int64_t nb = (a.e_hi - a.e_lo + GPB - 1) / GPB;
+  if (ADAM != 0 && b.row_ids) nb = (b.n_rows + GPB - 1) / GPB;     // the listed rows only
+  const int64_t cap = 256LL * per_cu;
+  if (nb > cap) nb = cap;
+  // VFM_FLAG_SHARE_GPU: 15/16 of the 1,024 workgroups the chip holds (126 VGPRs: four per CU), so that another stream's small
+  // kernels (256 threads, <= 128 VGPRs: csrc/vfm_index.hip) find a free slot on 64 CUs while this one runs
+  { const int share = env_int("VFM_SHARE_CAP", 960); if ((a.flags & VFM_FLAG_SHARE_GPU) && share > 0 && nb > share) nb = share; }
+  { const int forced = env_int("VFM_BWD_GRID", 0); if (forced > 0 && nb > forced) nb = forced; }      // (A/B runs)
+  if (nb < 1) nb = 1;
+  // the forms of the fused single-sample Philox step, and what this instance family has of them
+  constexpr bool FUSED = STAGE == STAGE_FULL && ADAM == 1 && EPS == EPS_PHILOX;      // look-ahead lazy Adam
+  constexpr bool PIPED = FUSED && VEC == 4 && LINK == LINK_ABS;                       // software-pipelined step
+  const bool pipe = b.zrec != nullptr;      // gathers samples, writes the next step's records
+  const bool la = b.last_step != nullptr;   // rows in neither this batch nor the next are skipped
+  if (pipe && !PIPED) return fail(VFM_E_UNSUPPORTED, "pipelined step: fused Adam, Philox eps, d % 4 == 0, |.| link only");
+  if (pipe && a.S > 1) return fail(VFM_E_UNSUPPORTED, "pipelined step: one variational sample");
+  if (la && !FUSED) return fail(VFM_E_UNSUPPORTED, "look-ahead lazy Adam: fused Adam with Philox eps only");
+  if (la && a.S > 1) return fail(VFM_E_UNSUPPORTED, "look-ahead lazy Adam: one variational sample");
+  auto launch = [&](auto multi, auto piped, auto ahead) {
+    hipLaunchKernelGGL((k_bwd<LPE, CPL, VEC, EPS, ADAM, STAGE, LINK, decltype(multi)::value, decltype(piped)::value, decltype(ahead)::value>),
+                       dim3((unsigned)nb), dim3(BLOCK), 0, st, a, b, ad);
+    return 0;
   };
-  const int64_t nb = grid_of(BLOCK / LPE);
-  if constexpr (STAGE == STAGE_FULL && ADAM == 1 && EPS == EPS_PHILOX && VEC == 4 && LINK == LINK_ABS) {
-    if (b.zrec != nullptr) {      // software-pipelined step: gathers samples, writes the next step's records
-      if (a.S > 1) return fail(VFM_E_UNSUPPORTED, "pipelined step: one variational sample");
-      if (b.last_step != nullptr)     // ... in the look-ahead form: rows in neither this batch nor the next are skipped
-        hipLaunchKernelGGL((k_bwd<LPE, CPL, VEC, EPS, ADAM, STAGE, LINK, false, true, true>), dim3((unsigned)nb), dim3(BLOCK), 0, st, a, b, ad);
-      else
-        hipLaunchKernelGGL((k_bwd<LPE, CPL, VEC, EPS, ADAM, STAGE, LINK, false, true>), dim3((unsigned)nb), dim3(BLOCK), 0, st, a, b, ad);
-      return 0;
-    }
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  if constexpr (PIPED) {
+    if (pipe) return la ? launch(no, yes, yes) : launch(no, yes, no);
   }
-  if (b.zrec != nullptr) return fail(VFM_E_UNSUPPORTED, "pipelined step: fused Adam, Philox eps, d % 4 == 0, |.| link only");
-  // VFM_BWD_PREFETCH=1: the fused Philox step fetches each row's index one row ahead (k_bwd<PF>; A/B, tests).  Off by
-  // default: bitwise the same step, but not faster at cfg3
-  const bool pf = env_int("VFM_BWD_PREFETCH", 0) != 0;
-  // VFM_BWD_LANES8=1: at d = 128 the fused single-sample Philox step (dense and look-ahead forms, scan and listed, |.| link)
-  // runs k_bwd<16, 2, ..., ADJ>: 8 adjacent coordinates and one Philox call per lane, four table rows per wave.  Bitwise the
-  // same step (tests/test_gpu_bwd_lanes8.py).  Every other d, and the prefetch form, keep the shape of the table.
-  if constexpr (STAGE == STAGE_FULL && ADAM == 1 && EPS == EPS_PHILOX && LPE == 32 && CPL == 1 && VEC == 4 && LINK == LINK_ABS) {
-    if (a.d == 128 && a.S == 1 && !pf && env_int("VFM_BWD_LANES8", 0) != 0) {
-      const int64_t nb8 = grid_of(BLOCK / 16);
-      if (b.last_step != nullptr)
-        hipLaunchKernelGGL((k_bwd<16, 2, 4, EPS, ADAM, STAGE, LINK, false, false, true, false, true>), dim3((unsigned)nb8), dim3(BLOCK), 0, st, a, b, ad);
-      else
-        hipLaunchKernelGGL((k_bwd<16, 2, 4, EPS, ADAM, STAGE, LINK, false, false, false, false, true>), dim3((unsigned)nb8), dim3(BLOCK), 0, st, a, b, ad);
-      return 0;
-    }
+  if constexpr (FUSED) {
+    if (la) return launch(no, no, yes);
   }
-  if constexpr (STAGE == STAGE_FULL && ADAM == 1 && EPS == EPS_PHILOX) {
-    if (b.last_step != nullptr) {     // look-ahead lazy Adam
-      if (a.S > 1) return fail(VFM_E_UNSUPPORTED, "look-ahead lazy Adam: one variational sample");
-      if (pf)
-        hipLaunchKernelGGL((k_bwd<LPE, CPL, VEC, EPS, ADAM, STAGE, LINK, false, false, true, true>), dim3((unsigned)nb), dim3(BLOCK), 0, st, a, b, ad);
-      else
-        hipLaunchKernelGGL((k_bwd<LPE, CPL, VEC, EPS, ADAM, STAGE, LINK, false, false, true>), dim3((unsigned)nb), dim3(BLOCK), 0, st, a, b, ad);
-      return 0;
-    }
-  }
-  if (b.last_step != nullptr) return fail(VFM_E_UNSUPPORTED, "look-ahead lazy Adam: fused Adam with Philox eps only");
   if constexpr (STAGE == STAGE_FULL) {
-    if (a.S > 1) {       // variational samples: the instance with the per-sample walk
-      hipLaunchKernelGGL((k_bwd<LPE, CPL, VEC, EPS, ADAM, STAGE, LINK, true>), dim3((unsigned)nb), dim3(BLOCK), 0, st, a, b, ad);
-      return 0;
-    }
+    if (a.S > 1) return launch(yes, no, no);      // variational samples: the instance with the per-sample walk
   }
-  if constexpr (STAGE == STAGE_FULL && ADAM == 1 && EPS == EPS_PHILOX) {
-    if (pf) {
-      hipLaunchKernelGGL((k_bwd<LPE, CPL, VEC, EPS, ADAM, STAGE, LINK, false, false, false, true>), dim3((unsigned)nb), dim3(BLOCK), 0, st, a, b, ad);
-      return 0;
-    }
-  }
-  hipLaunchKernelGGL((k_bwd<LPE, CPL, VEC, EPS, ADAM, STAGE, LINK, false>), dim3((unsigned)nb), dim3(BLOCK), 0, st, a, b, ad);
-  return 0;
+  return launch(no, no, no);
 }
 
 // adam: 0 gradients, 1 dense Adam fused, 2 row-sparse Adam fused, 10 statistics (STAGE_ACC), 11 apply (STAGE_APPLY)

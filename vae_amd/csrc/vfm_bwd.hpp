@@ -70,60 +70,59 @@ __device__ __forceinline__ int heavy_slot_of(const int32_t* ids, int n, int e) {
 __device__ __forceinline__ float replay_one(float p, float m, float r, float2 c, float eps) {
   return fmaf(-c.x * m, __builtin_amdgcn_rcpf(fmaf(r, c.y, eps)), p);
 }
+// ---------------------------------------------------------------------------------------
+// The phases of a row's update.  k_bwd's loop body below is a sequence of them, and k_bwd_small (vfm_bwd_small.hpp) calls
+// the same functions: its step is specified as bitwise the three-launch one, and under -ffp-contract=on equal source
+// expressions give equal bits.  Every arithmetic expression of the update lives here, once.
+// ---------------------------------------------------------------------------------------
 
-// PF (fused dense step, one sample, not pipelined): the index of the NEXT row a lane group visits is fetched one row
-// ahead, under this row's epilogue -- the first two row numbers of its list and (LA) whether it is in the next batch --
-// so that a row's walk starts with the grow / sumz loads: one dependent load less per row.  Same loads, same sums, same
-// order; PF = false is the row-serial form (the default; VFM_BWD_PREFETCH=1 selects PF).
-// ADJ (fused dense step, one sample, not pipelined, Philox eps, CPL = 2): a lane owns the two ADJACENT chunks 2 lig and
-// 2 lig + 1 -- 8 coordinates in one 32-byte stretch, the eps of all of them from ONE Philox call (eps_of_chunk_pair), where
-// the strided mapping j = lig + i LPE spends a call per chunk.  Which lane holds a coordinate changes, what is computed for
-// it does not: same expressions, same sums, same order.  At d = 128 a lane group is 16 lanes and a wave carries four rows.
-template <int LPE, int CPL, int VEC, int EPS, int ADAM, int STAGE, int LINK, bool MULTI, bool PIPE = false, bool LA = false,
-          bool PF = false, bool ADJ = false>
-__global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const KArgs a, const BwdArgs b, const AdamArgs ad_in) {
-  constexpr int GPB = BLOCK / LPE;
-  static_assert(!ADJ || (CPL == 2 && VEC == 4 && EPS == EPS_PHILOX && ADAM == 1 && STAGE == STAGE_FULL && !MULTI && !PIPE),
-                "adjacent chunks per lane: the fused single-sample Philox step with two chunks per lane");
-  // step-dependent values: from the kernel arguments, or (replayable step, a.dev) from device memory
-  AdamArgs ad = ad_in;
-  RngKey key = a.key, next_key = b.next_key;
-  int32_t la_step = b.la_step, la_k = b.la_k;
-  if constexpr (ADAM == 1 && STAGE == STAGE_FULL)
-    load_dev_step(a, key, ad, la_step, la_k, next_key,
-                  blockIdx.x == 0 && threadIdx.x == 0 && a.row_filter != 3 && a.e_hi == a.T);
-  static_assert(!PIPE || (ADAM == 1 && STAGE == STAGE_FULL && !MULTI), "the pipelined step is the fused single-sample one");
-  static_assert(!LA || (ADAM == 1 && STAGE == STAGE_FULL && !MULTI), "look-ahead lazy Adam is a form of the fused dense step");
-  static_assert(!PF || (ADAM == 1 && STAGE == STAGE_FULL && !MULTI && !PIPE), "the index prefetch serves the fused single-sample step");
-  __shared__ float sh_cs[VFM_MAX_FIELDS];
-  __shared__ float sh_cs_next[PIPE ? VFM_MAX_FIELDS : 1];
-  __shared__ int64_t sh_hi[VFM_MAX_FIELDS];
-  __shared__ double sh_fin[7][BLOCK / 64];
-  __shared__ float2 sh_tab[LA ? VFM_MOMENT_PERIOD + 1 : 1];      // LA: (a1, q2) of the period's earlier steps, for replays
+// the i-th chunk of lane `lig` of a lane group of LPE lanes
+template <int LPE>
+__device__ __forceinline__ int chunk_of(int lig, int i) { return lig + i * LPE; }
+
+// Index guard.  A corrupted index is clamped, never followed: list offsets to [0, n_occ], row numbers to [0, B), listed
+// entities to [0, T); every clamp that fires is counted for b.status (vfm_index_t.status), the caller's next look.
+struct IndexGuard {
+  int n_occ, Bm1;
+  int64_t T;
+  int nclamp;
+  __device__ __forceinline__ IndexGuard(const KArgs& a, const BwdArgs& b)
+      : n_occ(b.n_occ), Bm1(a.B > 0 ? (int)a.B - 1 : 0), T(a.T), nclamp(0) {}
+  __device__ __forceinline__ int64_t ent_ok(int64_t v) {
+    const bool ok = v >= 0 && v < T;
+    nclamp += ok ? 0 : 1;
+    return ok ? v : 0;
+  }
+  __device__ __forceinline__ int2 span_ok(int2 v) {
+    const bool ok = v.x >= 0 && v.y >= v.x && v.y <= n_occ;
+    nclamp += ok ? 0 : 1;
+    return ok ? v : make_int2(0, 0);
+  }
+  // (live = false: a padding slot of a batch of loads, clamped without being counted)
+  __device__ __forceinline__ int row_ok(int v, bool live = true) {
+    const bool ok = (unsigned)v <= (unsigned)Bm1;
+    nclamp += (ok || !live) ? 0 : 1;
+    return ok ? v : 0;
+  }
+  __device__ __forceinline__ void report(int32_t* status) const {
+    if (nclamp != 0 && status) atomicAdd(status, nclamp);       // (integer: the total does not depend on the order)
+  }
+};
+
+// Scalars and loss: the duties of workgroup 0.  `duty`: this launch forms the loss and moves the scalars; `last`: it is
+// the last chunk of a chunked run.
+__device__ __forceinline__ void adam_scalar(int i, float g, const KArgs& a, const AdamArgs& ad) {
+  float* sc = const_cast<float*>(a.scalars);
+  float m = ad.m_scal[i], v = ad.v_scal[i];
+  sc[i] = adam_update(sc[i], g, m, v, ad);
+  ad.m_scal[i] = m; ad.v_scal[i] = v;
+}
+
+template <int EPS, int ADAM, int STAGE, int LINK, bool MULTI>
+__device__ __forceinline__ void scalars_and_loss(const KArgs& a, const BwdArgs& b, const AdamArgs& ad, const RngKey& key, float gout,
+                                                 bool duty, bool last, double (*sh_fin)[BLOCK / 64]) {
   const int tid = threadIdx.x;
-  const int lig = tid % LPE;
-  auto chunk_of = [&](int i) -> int { return ADJ ? CPL * lig + i : lig + i * LPE; };      // the i-th chunk of this lane
-  const int d = a.d;
-  const int C = (d + VEC - 1) / VEC;
-  if (STAGE != STAGE_ACC && tid < a.G) {
-    sh_cs[tid] = (float)(a.group_n[tid] / a.W[tid]);
-    sh_hi[tid] = a.group_hi[tid];
-    if constexpr (PIPE) sh_cs_next[tid] = b.zrec_next ? (float)(a.group_n[tid] / b.next_W[tid]) : 0.f;
-  }
-  if constexpr (LA) {
-    for (int k = tid; k < la_k; k += BLOCK) sh_tab[k] = b.step_tab[k];
-  }
-  __syncthreads();
-  if constexpr (LA) {
-    if (blockIdx.x == 0 && tid == 0) b.step_tab[la_k] = make_float2(ad.a1, ad.q2);     // for later replays of this step
-  }
-  const float gout = (ADAM || STAGE == STAGE_ACC) ? 1.0f : b.grad_out[0];
-
   double fin[6] = {0, 0, 0, 0, 0, 0};
-  // a.row_filter (fused Adam, STAGE_FULL): 0 = every row; 2 = only the rows of the batch (+ the scalars and the loss);
-  // 3 / 4 (the long-list pre-reduction overlapped with this kernel, vfm_abi.hip): 4 = every row but the heavy
-  // entities (+ the scalars and the loss), 3 = the heavy entities only, listed
-  const bool duty = a.row_filter != 3;      // this launch forms the loss and moves the scalars
   const bool fold = STAGE == STAGE_FULL && b.loss != nullptr && duty;   // uniform: fold vfm_elbo_finalize_f32 in
   if (blockIdx.x == 0 && fold)
     reduce_slots_and_loss(b.partials, a.scalars, a.ll_scale_d, a.flags, b.loss, sh_fin, fin);
@@ -133,7 +132,7 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
     b.sums[0] = reduced ? (float)b.partials[VFM_P_G] : __builtin_nanf("");   // this rank's row sums, to be summed over ranks
     b.sums[1] = reduced ? (float)b.partials[VFM_P_ALPHA] : __builtin_nanf("");
   }
-  if (STAGE != STAGE_ACC && blockIdx.x == 0 && tid == 0 && a.e_hi == a.T && duty) {   // (last chunk of a chunked run)
+  if (STAGE != STAGE_ACC && blockIdx.x == 0 && tid == 0 && last && duty) {
     const float alpha = a.scalars[0], m0 = a.scalars[1], s0 = a.scalars[2];
     // (no fold and the forward's slots never reduced -- vfm_elbo_finalize_f32 skipped --: NaN, not stale sums)
     const bool stale = STAGE == STAGE_FULL && !fold && b.partials[VFM_P_REDUCED] != 1.0;
@@ -157,425 +156,557 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
     const float ge0 = MULTI ? (float)(fold ? fin[VFM_P_GE0] : b.partials[VFM_P_GE0]) : e0 * sum_g;
     const float gs = gout * dlink_f<LINK>(s0) * (ge0 + prior * (as0 - inv_sigma(as0)));
     if constexpr (ADAM) {
-      float* sc = const_cast<float*>(a.scalars);
-      auto upd = [&](int i, float g) {
-        float m = ad.m_scal[i], v = ad.v_scal[i];
-        sc[i] = adam_update(sc[i], g, m, v, ad);
-        ad.m_scal[i] = m; ad.v_scal[i] = v;
-      };
       // alpha has no gradient under the Bernoulli likelihood (reference: grad None, Adam skips it)
-      if (a.lik == VFM_LIK_NORMAL) upd(0, ga);
-      upd(1, gm);
-      upd(2, gs);
+      if (a.lik == VFM_LIK_NORMAL) adam_scalar(0, ga, a, ad);
+      adam_scalar(1, gm, a, ad);
+      adam_scalar(2, gs, a, ad);
     } else {
       b.g_scalars[0] = ga; b.g_scalars[1] = gm; b.g_scalars[2] = gs;
     }
   }
+}
+
+// Row cursor: the entity of position `at` (of the row list, or of the table scan) and its occ_ptr pair, fetched one
+// iteration before the row is visited.  STAGE_APPLY reads no lists: its pair stays (0, 0).
+template <int STAGE>
+__device__ __forceinline__ void fetch_row(const BwdArgs& b, bool listed, int64_t at, int64_t li_end, IndexGuard& ig,
+                                          int64_t& e_cur, int2& pq) {
+  if (at >= li_end) return;
+  e_cur = listed ? ig.ent_ok(b.row_ids[at]) : at;
+  if constexpr (STAGE != STAGE_APPLY) pq = ig.span_ok(make_int2(b.occ_ptr[e_cur], b.occ_ptr[e_cur + 1]));
+}
+
+// Own-row loads: what does not depend on the index chain -- parameters, moments, table eps, the first-order pair and
+// 1 / occurrences.  `active`: this lane group holds the row (k_bwd_small: the wave's first one).
+template <int VEC, int CPL>
+struct RowRegs {
+  Chunk<VEC> mu[CPL], s[CPL], ep[CPL], mm[CPL], ms[CPL], vm[CPL], vs[CPL];
+  float2 th = make_float2(0.f, 1.f), mb = make_float2(0.f, 0.f), vb = make_float2(0.f, 0.f);
+  float io = 0.f, epw = 0.f;
+};
+
+template <int LPE, int CPL, int VEC, int EPS, int ADAM>
+__device__ __forceinline__ void load_own_row(const KArgs& a, const AdamArgs& ad, int64_t e, int d, int C, int lig, bool active,
+                                             bool touched, bool want_io, RowRegs<VEC, CPL>& r) {
+  const float* prow = a.entity + (size_t)e * (2 * (size_t)d);
+#pragma unroll
+  for (int i = 0; i < CPL; ++i) {
+    const int j = chunk_of<LPE>(lig, i);
+    if (active && j < C) {
+      r.mu[i] = ld_chunk<VEC>(prow + (size_t)j * VEC);
+      r.s[i] = ld_chunk<VEC>(prow + d + (size_t)j * VEC);
+      if constexpr (ADAM) {
+        const size_t o = (size_t)e * (2 * (size_t)d) + (size_t)j * VEC;
+        r.mm[i] = ld_chunk_nt<VEC>(ad.m_entity + o); r.ms[i] = ld_chunk_nt<VEC>(ad.m_entity + o + d);
+        r.vm[i] = ld_chunk_nt<VEC>(ad.v_entity + o); r.vs[i] = ld_chunk_nt<VEC>(ad.v_entity + o + d);
+      }
+      if constexpr (EPS == EPS_TABLE)
+        if (touched) r.ep[i] = ld_chunk<VEC>(a.eps_entity + (size_t)e * d + (size_t)j * VEC);
+    }
+  }
+  if (active && lig == 0) {
+    r.th = *reinterpret_cast<const float2*>(a.bias + 2 * (size_t)e);
+    if constexpr (ADAM) {
+      r.mb = *reinterpret_cast<const float2*>(ad.m_bias + 2 * (size_t)e);
+      r.vb = *reinterpret_cast<const float2*>(ad.v_bias + 2 * (size_t)e);
+    }
+  }
+  if (active && want_io) {
+    r.io = a.inv_occ[e];
+    if constexpr (EPS == EPS_TABLE) r.epw = a.eps_bias[e];
+  }
+}
+
+// List walk, heavy part: a list pre-reduced by k_heavy -- read the record(s) instead of walking
+template <int LPE, int CPL, int VEC>
+__device__ __forceinline__ void read_heavy(const BwdArgs& b, const float* __restrict__ hacc, int hslot, int64_t xs, int C, int lig,
+                                           IndexGuard& ig, Chunk<VEC> (&A)[CPL], float& gs) {
+  const float* rec = hacc + (size_t)hslot * xs;
+  int4 hd = *reinterpret_cast<const int4*>(rec);      // (sum grow, count, first item, last item + 1)
+  if (hd.z < 0 || hd.w < hd.z || hd.w > b.heavy_stride - b.n_heavy) { hd.z = hd.w = 0; ++ig.nclamp; }
+  if (hd.w - hd.z <= VFM_HEAVY_DIRECT) {      // few work items: add their records here, in item order
+    for (int it = hd.z; it < hd.w; ++it) {
+      const float* ir = hacc + ((size_t)b.n_heavy + (size_t)it) * xs;
+      gs += ir[0];
+#pragma unroll
+      for (int i = 0; i < CPL; ++i) {
+        const int j = chunk_of<LPE>(lig, i);
+        if (j < C) {
+          const Chunk<VEC> t4 = ld_chunk<VEC>(ir + 4 + (size_t)j * VEC);
+#pragma unroll
+          for (int t = 0; t < VEC; ++t) A[i].v[t] += t4.v[t];
+        }
+      }
+    }
+  } else {                                    // k_heavy_sum added them into the entity's record
+    gs = __int_as_float(hd.x);
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+      const int j = chunk_of<LPE>(lig, i);
+      if (j < C) A[i] = ld_chunk<VEC>(rec + 4 + (size_t)j * VEC);
+    }
+  }
+}
+
+// List walk, the walk itself: A += sum_r g_r * sumz_r, gs += sum_r g_r over occurrences [o, end), two in flight.
+// PIPE: the sample of the OTHER entity of the row (this step's records) stands in for the sumz row.
+template <bool PIPE>
+__device__ __forceinline__ const float* walk_source(const BwdArgs& b, const float* __restrict__ sz, int oo, int r, int d, int64_t xs,
+                                                    IndexGuard& ig) {
+  if constexpr (PIPE) return b.zrec + (size_t)ig.ent_ok(b.occ_other[oo]) * xs + 4;
+  return sz + (size_t)r * d;
+}
+
+template <int LPE, int CPL, int VEC, bool PIPE>
+__device__ __forceinline__ void walk_pairs(const BwdArgs& b, const float* __restrict__ sz, int o, int end, int d, int C, int64_t xs,
+                                           int lig, IndexGuard& ig, Chunk<VEC> (&A)[CPL], float& gs) {
+  for (; o + 1 < end; o += 2) {      // two occurrences in flight
+    const int r0 = ig.row_ok(b.occ_rows[o]), r1 = ig.row_ok(b.occ_rows[o + 1]);
+    const float g0 = b.grow[r0], g1 = b.grow[r1];
+    const float* p0 = walk_source<PIPE>(b, sz, o, r0, d, xs, ig);
+    const float* p1 = walk_source<PIPE>(b, sz, o + 1, r1, d, xs, ig);
+    gs += g0 + g1;
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+      const int j = chunk_of<LPE>(lig, i);
+      if (j < C) {
+        const Chunk<VEC> s0v = ld_chunk<VEC>(p0 + (size_t)j * VEC);
+        const Chunk<VEC> s1v = ld_chunk<VEC>(p1 + (size_t)j * VEC);
+#pragma unroll
+        for (int t = 0; t < VEC; ++t) A[i].v[t] = fmaf(g1, s1v.v[t], fmaf(g0, s0v.v[t], A[i].v[t]));
+      }
+    }
+  }
+  if (o < end) {
+    const int r0 = ig.row_ok(b.occ_rows[o]);
+    const float g0 = b.grow[r0];
+    const float* p0 = walk_source<PIPE>(b, sz, o, r0, d, xs, ig);
+    gs += g0;
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+      const int j = chunk_of<LPE>(lig, i);
+      if (j < C) {
+        const Chunk<VEC> s0v = ld_chunk<VEC>(p0 + (size_t)j * VEC);
+#pragma unroll
+        for (int t = 0; t < VEC; ++t) A[i].v[t] = fmaf(g0, s0v.v[t], A[i].v[t]);
+      }
+    }
+  }
+}
+
+// the whole list of one sample (sz / hacc: the sample's blocks)
+template <int LPE, int CPL, int VEC, bool PIPE>
+__device__ __forceinline__ void walk_list(const BwdArgs& b, const float* __restrict__ sz, const float* __restrict__ hacc, int hslot,
+                                          int beg, int end, int d, int C, int64_t xs, int lig, IndexGuard& ig, Chunk<VEC> (&A)[CPL],
+                                          float& gs) {
+#pragma unroll
+  for (int i = 0; i < CPL; ++i)
+#pragma unroll
+    for (int t = 0; t < VEC; ++t) A[i].v[t] = 0.f;
+  gs = 0.f;
+  if (hslot >= 0) read_heavy<LPE, CPL, VEC>(b, hacc, hslot, xs, C, lig, ig, A, gs);
+  else walk_pairs<LPE, CPL, VEC, PIPE>(b, sz, beg, end, d, C, xs, lig, ig, A, gs);
+}
+
+// weight of the row's KL part
+__device__ __forceinline__ float kl_weight(const float* sh_cs, const int64_t* sh_hi, int G, int64_t e, float io, float cntf) {
+  return sh_cs[group_index(sh_hi, G, e)] * io * cntf;
+}
+
+// eps of chunk j of entity e: the table's (`tab`, loaded by the caller), zero, or regenerated (nb: the first-order eps)
+template <int VEC, int EPS>
+__device__ __forceinline__ void chunk_eps(const RngKey& key, int64_t e, int j, const Chunk<VEC>& tab, Chunk<VEC>& epc, float& nb) {
+  nb = 0.f;
+  if constexpr (EPS == EPS_TABLE) {
+    epc = tab;
+  } else if constexpr (EPS == EPS_ZERO) {
+#pragma unroll
+    for (int t = 0; t < VEC; ++t) epc.v[t] = 0.f;
+  } else {
+    eps_of_chunk<VEC>(key, (uint32_t)e, j, epc.v, nb);
+  }
+}
+
+// Chunk gradient, one sample: (mu, s, eps, A, gs, c, gout) -> (gm, gv)
+template <int VEC, int LINK, bool PIPE>
+__device__ __forceinline__ void chunk_grad(const Chunk<VEC>& mu, const Chunk<VEC>& s, const Chunk<VEC>& epc, const Chunk<VEC>& A,
+                                           float gs, float c, float gout, Chunk<VEC>& gm, Chunk<VEC>& gv) {
+#pragma unroll
+  for (int t = 0; t < VEC; ++t) {
+    const float sg = link_f<LINK>(s.v[t]);
+    const float z = fmaf(sg, epc.v[t], mu.v[t]);
+    // sum_r g_r (sumz_rk - z_ek); PIPE: A already sums the other entity's z alone
+    const float gz = PIPE ? A.v[t] : A.v[t] - z * gs;
+    gm.v[t] = gout * (gz + c * mu.v[t]);
+    gv.v[t] = gout * dlink_f<LINK>(s.v[t]) * (gz * epc.v[t] + c * (sg - inv_sigma(sg)));
+  }
+}
+
+// Chunk gradient, S > 1: one sample's share of g1s = sum_s (A^s - z^s gs), g2s = sum_s eps^s (A^s - z^s gs) ...
+template <int VEC, int LINK>
+__device__ __forceinline__ void chunk_grad_sample(const Chunk<VEC>& mu, const Chunk<VEC>& s, const Chunk<VEC>& epc,
+                                                  const Chunk<VEC>& A, float gs, Chunk<VEC>& g1s, Chunk<VEC>& g2s) {
+#pragma unroll
+  for (int t = 0; t < VEC; ++t) {
+    const float z = fmaf(link_f<LINK>(s.v[t]), epc.v[t], mu.v[t]);
+    const float gz = A.v[t] - z * gs;
+    g1s.v[t] += gz;
+    g2s.v[t] = fmaf(gz, epc.v[t], g2s.v[t]);
+  }
+}
+// ... and the gradient from the sample means
+template <int VEC, int LINK>
+__device__ __forceinline__ void chunk_grad_multi(const Chunk<VEC>& mu, const Chunk<VEC>& s, const Chunk<VEC>& g1s,
+                                                 const Chunk<VEC>& g2s, float c, float gout, Chunk<VEC>& gm, Chunk<VEC>& gv) {
+#pragma unroll
+  for (int t = 0; t < VEC; ++t) {
+    const float sg = link_f<LINK>(s.v[t]);
+    gm.v[t] = gout * (g1s.v[t] + c * mu.v[t]);
+    gv.v[t] = gout * dlink_f<LINK>(s.v[t]) * (g2s.v[t] + c * (sg - inv_sigma(sg)));
+  }
+}
+
+// S > 1 (uniform): the list is walked once per sample (A, gs hold the first sample's walk on entry, the last one's on
+// return); g1s, g2s = the means over the samples, nb_eps = mean_s eps_w^s
+template <int LPE, int CPL, int VEC, int EPS, int LINK>
+__device__ __forceinline__ void sample_means(const KArgs& a, const BwdArgs& b, const RngKey& key, int64_t e, int hslot, int beg,
+                                             int end, int d, int C, int64_t xs, int lig, IndexGuard& ig,
+                                             const RowRegs<VEC, CPL>& r, Chunk<VEC> (&A)[CPL], float& gs, Chunk<VEC> (&g1s)[CPL],
+                                             Chunk<VEC> (&g2s)[CPL], float& nb_eps) {
+#pragma unroll
+  for (int i = 0; i < CPL; ++i)
+#pragma unroll
+    for (int t = 0; t < VEC; ++t) { g1s[i].v[t] = 0.f; g2s[i].v[t] = 0.f; }
+  for (int sm = 0; sm < a.S; ++sm) {
+    if (sm > 0)
+      walk_list<LPE, CPL, VEC, false>(b, b.sumz + (size_t)sm * (size_t)a.B * d,
+                                      b.heavy_acc + (size_t)sm * (size_t)b.heavy_stride * xs, hslot, beg, end, d, C, xs, lig, ig, A, gs);
+    const RngKey ks = key_of_sample(key, sm);
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+      const int j = chunk_of<LPE>(lig, i);
+      if (j < C) {
+        Chunk<VEC> tab, epc;
+        float nb;
+        if constexpr (EPS == EPS_TABLE)
+          tab = ld_chunk<VEC>(a.eps_entity + ((size_t)sm * (size_t)a.T + (size_t)e) * d + (size_t)j * VEC);
+        chunk_eps<VEC, EPS>(ks, e, j, tab, epc, nb);
+        if (EPS == EPS_PHILOX && i == 0) nb_eps += nb;
+        chunk_grad_sample<VEC, LINK>(r.mu[i], r.s[i], epc, A[i], gs, g1s[i], g2s[i]);
+      }
+    }
+    if constexpr (EPS == EPS_TABLE) nb_eps += a.eps_bias[(size_t)sm * (size_t)a.T + (size_t)e];
+  }
+  nb_eps *= a.inv_S;
+#pragma unroll
+  for (int i = 0; i < CPL; ++i)
+#pragma unroll
+    for (int t = 0; t < VEC; ++t) { g1s[i].v[t] *= a.inv_S; g2s[i].v[t] *= a.inv_S; }
+}
+
+// First-order gradient: (th, gs, nb_eps, c, gout) -> (g0, g1)
+template <int LINK>
+__device__ __forceinline__ void first_order_grad(float2 th, float gs, float nb_eps, float c, float gout, float& g0, float& g1) {
+  const float sg = link_f<LINK>(th.y);
+  g0 = gout * (gs + c * th.x);
+  g1 = gout * dlink_f<LINK>(th.y) * (gs * nb_eps + c * (sg - inv_sigma(sg)));
+}
+
+// Adam step of 2 N parameters (a chunk's mu | s, or the first-order pair): p -> q, moments in place.
+// LA (always the scaled form): the row first replays the la_gap zero-gradient steps it skipped ((a1, q2) of the period's
+// steps in `tab`), then takes adam_update in its halves -- a replayed row without gradient keeps its second moments
+// (fma(c2 0, 0, v) = v), so the roots taken for the replay are handed over to this step's update.
+template <int N, bool LA>
+__device__ __forceinline__ void adam_row_step(float (&p0)[N], float (&p1)[N], float (&m0)[N], float (&m1)[N], float (&v0)[N],
+                                              float (&v1)[N], const float (&g0)[N], const float (&g1)[N], int la_gap, int la_k,
+                                              const float2* tab, bool touched, const AdamArgs& ad, float (&q0)[N], float (&q1)[N]) {
+  if constexpr (LA) {
+    float r0[N], r1[N];          // sqrt of the stored second moments
+    if (la_gap > 0) {            // (uniform over the lane group) bring the row up to the step before this one
+#pragma unroll
+      for (int t = 0; t < N; ++t) { r0[t] = __builtin_amdgcn_sqrtf(v0[t]); r1[t] = __builtin_amdgcn_sqrtf(v1[t]); }
+      for (int k = la_k - la_gap; k < la_k; ++k) {
+        const float2 c = tab[k];
+#pragma unroll
+        for (int t = 0; t < N; ++t) {
+          p0[t] = replay_one(p0[t], m0[t], r0[t], c, ad.eps);
+          p1[t] = replay_one(p1[t], m1[t], r1[t], c, ad.eps);
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < N; ++t) {
+      adam_accum(g0[t], m0[t], v0[t], ad);
+      adam_accum(g1[t], m1[t], v1[t], ad);
+    }
+    if (!(la_gap > 0 && !touched)) {
+#pragma unroll
+      for (int t = 0; t < N; ++t) { r0[t] = __builtin_amdgcn_sqrtf(v0[t]); r1[t] = __builtin_amdgcn_sqrtf(v1[t]); }
+    }
+#pragma unroll
+    for (int t = 0; t < N; ++t) {
+      q0[t] = adam_apply(p0[t], m0[t], v0[t], r0[t], ad);
+      q1[t] = adam_apply(p1[t], m1[t], v1[t], r1[t], ad);
+    }
+  } else {
+#pragma unroll
+    for (int t = 0; t < N; ++t) {
+      q0[t] = adam_update(p0[t], g0[t], m0[t], v0[t], ad);
+      q1[t] = adam_update(p1[t], g1[t], m1[t], v1[t], ad);
+    }
+  }
+}
+
+// the same for the first-order pair (mu_w, s_w)
+template <bool LA>
+__device__ __forceinline__ float2 adam_pair_step(float2 th, float2& mb, float2& vb, float g0, float g1, int la_gap, int la_k,
+                                                 const float2* tab, bool touched, const AdamArgs& ad) {
+  float p0[1] = {th.x}, p1[1] = {th.y}, m0[1] = {mb.x}, m1[1] = {mb.y}, v0[1] = {vb.x}, v1[1] = {vb.y};
+  const float ga[1] = {g0}, gb[1] = {g1};
+  float q0[1], q1[1];
+  adam_row_step<1, LA>(p0, p1, m0, m1, v0, v1, ga, gb, la_gap, la_k, tab, touched, ad, q0, q1);
+  mb = make_float2(m0[0], m1[0]);
+  vb = make_float2(v0[0], v1[0]);
+  return make_float2(q0[0], q1[0]);
+}
+
+// Moment write-back rule (scaled form: rows without gradient keep ms, vs -- their decay is implicit) ...
+__device__ __forceinline__ bool moments_written(const AdamArgs& ad, bool touched) {
+  return !ad.scaled || touched || ad.store_true;
+}
+// ... and the stores of an updated chunk / first-order pair
+template <int VEC>
+__device__ __forceinline__ void store_row_chunk(const KArgs& a, const AdamArgs& ad, int64_t e, int d, int j, bool touched,
+                                                const Chunk<VEC>& pm, const Chunk<VEC>& ps, const Chunk<VEC>& mm,
+                                                const Chunk<VEC>& ms, const Chunk<VEC>& vm, const Chunk<VEC>& vs) {
+  float* prow = const_cast<float*>(a.entity) + (size_t)e * (2 * (size_t)d);
+  const size_t o2 = (size_t)e * (2 * (size_t)d) + (size_t)j * VEC;
+  st_chunk<VEC>(prow + (size_t)j * VEC, pm);
+  st_chunk<VEC>(prow + d + (size_t)j * VEC, ps);
+  if (moments_written(ad, touched)) {
+    st_chunk_nt<VEC>(ad.m_entity + o2, mm); st_chunk_nt<VEC>(ad.m_entity + o2 + d, ms);
+    st_chunk_nt<VEC>(ad.v_entity + o2, vm); st_chunk_nt<VEC>(ad.v_entity + o2 + d, vs);
+  }
+}
+__device__ __forceinline__ void store_first_order(const KArgs& a, const AdamArgs& ad, int64_t e, bool touched, float2 pn, float2 mb,
+                                                  float2 vb) {
+  *reinterpret_cast<float2*>(const_cast<float*>(a.bias) + 2 * (size_t)e) = pn;
+  if (a.wrec) *reinterpret_cast<float2*>(a.wrec + 4 * (size_t)e) = pn;      // packed first-order record: (mu_w, s_w | 1/occ, 0)
+  if (moments_written(ad, touched)) {
+    *reinterpret_cast<float2*>(ad.m_bias + 2 * (size_t)e) = mb;
+    *reinterpret_cast<float2*>(ad.v_bias + 2 * (size_t)e) = vb;
+  }
+}
+
+// Next-step record of PIPE: the updated row is in registers -- sample it for the next step right here.  A chunk ...
+template <int VEC, int LINK>
+__device__ __forceinline__ void next_record_chunk(const BwdArgs& b, const RngKey& next_key, int64_t e, int j, int64_t xs,
+                                                  const Chunk<VEC>& pm, const Chunk<VEC>& ps, bool first, float& nb_next,
+                                                  float& kl_next) {
+  Chunk<VEC> ep2, zn;
+  float nb2;
+  eps_of_chunk<VEC>(next_key, (uint32_t)e, j, ep2.v, nb2);
+  if (first) nb_next = nb2;
+#pragma unroll
+  for (int t = 0; t < VEC; ++t) {
+    const float sg2 = link_f<LINK>(ps.v[t]);
+    zn.v[t] = fmaf(sg2, ep2.v[t], pm.v[t]);
+    kl_next += kl_std_normal(pm.v[t], sg2);
+  }
+  st_chunk<VEC>(b.zrec_next + (size_t)e * xs + 4 + (size_t)j * VEC, zn);
+}
+// ... the sampled first-order weight ...
+template <int LINK>
+__device__ __forceinline__ void next_record_weight(float2 pn, float nb_next, float& w_next, float& kl_next) {
+  const float sgw2 = link_f<LINK>(pn.y);
+  w_next = fmaf(sgw2, nb_next, pn.x);
+  kl_next += kl_std_normal(pn.x, sgw2);
+}
+// ... and (uniform over the lane group) the header of the record: (w, weighted KL, 0, 0)
+template <int LPE>
+__device__ __forceinline__ void next_record_header(const BwdArgs& b, int64_t e, int64_t xs, int lig, float w_next, float kl_next,
+                                                   float cs_next, float io) {
+  kl_next = group_sum<LPE>(kl_next);
+  if (lig == 0)
+    *reinterpret_cast<float4*>(b.zrec_next + (size_t)e * xs) = make_float4(w_next, kl_next * (cs_next * io), 0.f, 0.f);
+}
+
+// STAGE_ACC: store the statistics (dense: zeros for rows not in this shard); STAGE_APPLY: read the summed ones
+template <int LPE, int CPL, int VEC>
+__device__ __forceinline__ void store_statistics(float* rec, int C, int lig, const Chunk<VEC> (&A)[CPL], float gs, float cntf) {
+#pragma unroll
+  for (int i = 0; i < CPL; ++i) {
+    const int j = chunk_of<LPE>(lig, i);
+    if (j < C) st_chunk<VEC>(rec + 4 + (size_t)j * VEC, A[i]);
+  }
+  if (lig == 0) *reinterpret_cast<float4*>(rec) = make_float4(gs, cntf, 0.f, 0.f);
+}
+template <int LPE, int CPL, int VEC>
+__device__ __forceinline__ void load_statistics(const float* rec, int C, int lig, Chunk<VEC> (&A)[CPL]) {
+#pragma unroll
+  for (int i = 0; i < CPL; ++i) {
+    const int j = chunk_of<LPE>(lig, i);
+    if (j < C) A[i] = ld_chunk<VEC>(rec + 4 + (size_t)j * VEC);
+  }
+}
+// gradient form, entity not in the batch: the dense zero row
+template <int LPE, int CPL, int VEC>
+__device__ __forceinline__ void store_zero_row(float* grow_e, float* g_bias_e, int d, int C, int lig) {
+  Chunk<VEC> zc;
+#pragma unroll
+  for (int t = 0; t < VEC; ++t) zc.v[t] = 0.f;
+#pragma unroll
+  for (int i = 0; i < CPL; ++i) {
+    const int j = chunk_of<LPE>(lig, i);
+    if (j < C) {
+      st_chunk_nt<VEC>(grow_e + (size_t)j * VEC, zc);
+      st_chunk_nt<VEC>(grow_e + d + (size_t)j * VEC, zc);
+    }
+  }
+  if (lig == 0) *reinterpret_cast<float2*>(g_bias_e) = make_float2(0.f, 0.f);
+}
+
+// ---------------------------------------------------------------------------------------
+// k_bwd.  Template parameters: the lane-group shape (LPE lanes per row, CPL chunks of VEC coordinates per lane), the eps
+// source, ADAM 0 gradients / 1 dense Adam fused / 2 row-sparse Adam fused, the multi-rank STAGE, the link, and the forms
+// of the fused single-sample dense step: MULTI (S > 1), PIPE (software-pipelined), LA (look-ahead lazy Adam).
+// ---------------------------------------------------------------------------------------
+template <int LPE, int CPL, int VEC, int EPS, int ADAM, int STAGE, int LINK, bool MULTI, bool PIPE = false, bool LA = false>
+__global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const KArgs a, const BwdArgs b, const AdamArgs ad_in) {
+  constexpr int GPB = BLOCK / LPE;
+  static_assert(!PIPE || (ADAM == 1 && STAGE == STAGE_FULL && !MULTI), "the pipelined step is the fused single-sample one");
+  static_assert(!LA || (ADAM == 1 && STAGE == STAGE_FULL && !MULTI), "look-ahead lazy Adam is a form of the fused dense step");
+  // step-dependent values: from the kernel arguments, or (replayable step, a.dev) from device memory
+  AdamArgs ad = ad_in;
+  RngKey key = a.key, next_key = b.next_key;
+  int32_t la_step = b.la_step, la_k = b.la_k;
+  if constexpr (ADAM == 1 && STAGE == STAGE_FULL)
+    load_dev_step(a, key, ad, la_step, la_k, next_key,
+                  blockIdx.x == 0 && threadIdx.x == 0 && a.row_filter != 3 && a.e_hi == a.T);
+  __shared__ float sh_cs[VFM_MAX_FIELDS];
+  __shared__ float sh_cs_next[PIPE ? VFM_MAX_FIELDS : 1];
+  __shared__ int64_t sh_hi[VFM_MAX_FIELDS];
+  __shared__ double sh_fin[7][BLOCK / 64];
+  __shared__ float2 sh_tab[LA ? VFM_MOMENT_PERIOD + 1 : 1];      // LA: (a1, q2) of the period's earlier steps, for replays
+  const int tid = threadIdx.x;
+  const int lig = tid % LPE;
+  const int d = a.d;
+  const int C = (d + VEC - 1) / VEC;
+  if (STAGE != STAGE_ACC && tid < a.G) {
+    sh_cs[tid] = (float)(a.group_n[tid] / a.W[tid]);
+    sh_hi[tid] = a.group_hi[tid];
+    if constexpr (PIPE) sh_cs_next[tid] = b.zrec_next ? (float)(a.group_n[tid] / b.next_W[tid]) : 0.f;
+  }
+  if constexpr (LA) {
+    for (int k = tid; k < la_k; k += BLOCK) sh_tab[k] = b.step_tab[k];
+  }
+  __syncthreads();
+  if constexpr (LA) {
+    if (blockIdx.x == 0 && tid == 0) b.step_tab[la_k] = make_float2(ad.a1, ad.q2);     // for later replays of this step
+  }
+  const float gout = (ADAM || STAGE == STAGE_ACC) ? 1.0f : b.grad_out[0];
+
+  // a.row_filter (fused Adam, STAGE_FULL): 0 = every row; 2 = only the rows of the batch (+ the scalars and the loss);
+  // 3 / 4 (the long-list pre-reduction overlapped with this kernel, vfm_abi.hip): 4 = every row but the heavy
+  // entities (+ the scalars and the loss), 3 = the heavy entities only, listed
+  scalars_and_loss<EPS, ADAM, STAGE, LINK, MULTI>(a, b, ad, key, gout, a.row_filter != 3, a.e_hi == a.T, sh_fin);
 
   const int64_t stride = (int64_t)gridDim.x * GPB;
   const int64_t xs = 4 + (((int64_t)d + 3) & ~(int64_t)3);          // floats per exchange record
   // fused Adam with a row list (the lazy exact-Adam step): li runs over the list (the batch's entities), not over
   // the table.  The SAME instance serves the dense step, so the two agree bit for bit on the rows they share
   // (different template instances are compiled with different fma contractions).
-  // (STAGE_APPLY with a list -- vfm_elbo_apply_adam_rows_f32: the multi-rank step's lazy exact form -- visits the
-  // listed rows only; their records sit in the DENSE statistics table, at the entity's own index)
   // (the multi-rank stages take a list too -- vfm_elbo_bwd_acc_rows_f32 / vfm_elbo_apply_adam_rows_f32: the rows some
   // rank's shard contains; their records sit in the DENSE statistics table at the entity's own index, or, with
   // b.rec_by_slot, in a COMPACT buffer at the row's position in the list)
   const bool listed = b.row_ids != nullptr && (STAGE == STAGE_FULL ? ADAM != 0 : true);
-  // a corrupted index is clamped, never followed: list offsets to [0, n_occ], row numbers to [0, B), listed entities to
-  // [0, T); every clamp that fires is counted in b.status (vfm_index_t.status) for the caller's next look
-  int nclamp = 0;
-  const int n_occ = b.n_occ;
-  const int Bm1 = a.B > 0 ? (int)a.B - 1 : 0;
-  auto ent_ok = [&](int64_t v) -> int64_t {
-    const bool ok = v >= 0 && v < a.T;
-    nclamp += ok ? 0 : 1;
-    return ok ? v : 0;
-  };
-  auto span_ok = [&](int2 v) -> int2 {
-    const bool ok = v.x >= 0 && v.y >= v.x && v.y <= n_occ;
-    nclamp += ok ? 0 : 1;
-    return ok ? v : make_int2(0, 0);
-  };
-  auto row_ok = [&](int v) -> int {
-    const bool ok = (unsigned)v <= (unsigned)Bm1;
-    nclamp += ok ? 0 : 1;
-    return ok ? v : 0;
-  };
+  IndexGuard ig(a, b);
   const int64_t li_end = listed ? b.n_rows : a.e_hi;
   int64_t li = (listed ? 0 : a.e_lo) + (int64_t)blockIdx.x * GPB + tid / LPE;
   int64_t e_cur = li;
-  if (listed && li < li_end) e_cur = ent_ok(b.row_ids[li]);
   int2 pq = make_int2(0, 0);
-  if (STAGE != STAGE_APPLY && li < li_end) pq = span_ok(make_int2(b.occ_ptr[e_cur], b.occ_ptr[e_cur + 1]));
-  // PF: nr = occ_rows[pq.x], occ_rows[pq.x + 1] and nn = "e_cur is in the next batch" (LA), for the row pq / e_cur describe
-  int2 nr = make_int2(0, 0);
-  bool nn = false;
-  auto fetch_next = [&](bool more) {
-    if constexpr (PF) {
-      if (more) {
-        if (pq.y > pq.x) nr.x = b.occ_rows[pq.x];
-        if (pq.y > pq.x + 1) nr.y = b.occ_rows[pq.x + 1];
-        if constexpr (LA) nn = b.next_occ_ptr[e_cur + 1] != b.next_occ_ptr[e_cur];
-      }
-    }
-  };
-  fetch_next(li < li_end);
+  fetch_row<STAGE>(b, listed, li, li_end, ig, e_cur, pq);
   for (; li < li_end; li += stride) {
     const int64_t e = listed ? e_cur : li;
-    const int2 rr = nr;           // PF: this row's first two row numbers
-    const bool in_nb = nn;        // PF + LA: this row is in the next batch
     const int64_t rec = (listed && !b.rec_by_slot) ? e : li;      // where this row's statistics record sits (multi-rank stages)
-    int beg = pq.x, end = pq.y;
-    const int64_t en = li + stride;
-    float2 gc = make_float2(0.f, 0.f);
-    if constexpr (STAGE == STAGE_APPLY) {
-      gc = *reinterpret_cast<const float2*>(b.acc + (size_t)rec * xs);   // (sum of grow, occurrences) over ALL ranks
-      if (listed && en < li_end) e_cur = ent_ok(b.row_ids[en]);
-      beg = 0; end = 0;
-    } else {
-      if (en < li_end) {                                                    // next entity's offsets, early
-        const int64_t e_next = listed ? ent_ok(b.row_ids[en]) : en;
-        e_cur = e_next;
-        pq = span_ok(make_int2(b.occ_ptr[e_next], b.occ_ptr[e_next + 1]));
-      }
-    }
+    const int beg = pq.x, end = pq.y;
+    float2 gc = make_float2(0.f, 0.f);                             // STAGE_APPLY: (sum of grow, occurrences) over ALL ranks
+    if constexpr (STAGE == STAGE_APPLY) gc = *reinterpret_cast<const float2*>(b.acc + (size_t)rec * xs);
+    fetch_row<STAGE>(b, listed, li + stride, li_end, ig, e_cur, pq);      // next entity's offsets, early
     bool in_next = false;          // PIPE: e is in the next batch -> its next-step record is written below
     if constexpr (PIPE) {
       if (b.zrec_next) in_next = b.next_occ_ptr[e + 1] != b.next_occ_ptr[e];
     }
-    float* prow = const_cast<float*>(a.entity) + (size_t)e * (2 * (size_t)d);
-    float* grow_e = (ADAM || STAGE == STAGE_ACC) ? nullptr : b.g_entity + (size_t)e * (2 * (size_t)d);
     const bool touched = (STAGE == STAGE_APPLY) ? gc.y > 0.f : beg != end;
     const float cntf = (STAGE == STAGE_APPLY) ? gc.y : (float)(end - beg);
-    const bool more = en < li_end;         // PF: the lane group has a next row (its index goes out before a `continue`)
     int la_gap = 0;                        // LA: skipped zero-gradient steps this row applies before this step's update
     if constexpr (LA) {
-      if (!touched && !(PF ? in_nb : b.next_occ_ptr[e + 1] != b.next_occ_ptr[e])) {     // in neither batch: the row waits
-        fetch_next(more);
-        continue;
-      }
+      if (!touched && !(b.next_occ_ptr[e + 1] != b.next_occ_ptr[e])) continue;      // in neither batch: the row waits
       la_gap = (la_step - 1) - b.last_step[e];
     }
     if (ADAM == 2 && !touched) continue;   // opt-in row-sparse Adam: rows not in the batch stay as they are
-    if (ADAM == 1 && STAGE == STAGE_FULL && a.row_filter == 2 && !touched) { fetch_next(more); continue; }
+    if (ADAM == 1 && STAGE == STAGE_FULL && a.row_filter == 2 && !touched) continue;
 
-    // loads that do not depend on the index chain
-    Chunk<VEC> mu[CPL], s[CPL], ep[CPL], mm[CPL], ms[CPL], vm[CPL], vs[CPL];
-    float2 th = make_float2(0.f, 1.f), mb = make_float2(0.f, 0.f), vb = make_float2(0.f, 0.f);
-    float io = 0.f, epw = 0.f;
-    if (STAGE != STAGE_ACC && (ADAM || touched)) {
-#pragma unroll
-      for (int i = 0; i < CPL; ++i) {
-        const int j = chunk_of(i);
-        if (j < C) {
-          mu[i] = ld_chunk<VEC>(prow + (size_t)j * VEC);
-          s[i] = ld_chunk<VEC>(prow + d + (size_t)j * VEC);
-          if constexpr (ADAM) {
-            const size_t o = (size_t)e * (2 * (size_t)d) + (size_t)j * VEC;
-            mm[i] = ld_chunk_nt<VEC>(ad.m_entity + o); ms[i] = ld_chunk_nt<VEC>(ad.m_entity + o + d);
-            vm[i] = ld_chunk_nt<VEC>(ad.v_entity + o); vs[i] = ld_chunk_nt<VEC>(ad.v_entity + o + d);
-          }
-          if constexpr (EPS == EPS_TABLE)
-            if (touched) ep[i] = ld_chunk<VEC>(a.eps_entity + (size_t)e * d + (size_t)j * VEC);
-        }
-      }
-      if (lig == 0) {
-        th = *reinterpret_cast<const float2*>(a.bias + 2 * (size_t)e);
-        if constexpr (ADAM) {
-          mb = *reinterpret_cast<const float2*>(ad.m_bias + 2 * (size_t)e);
-          vb = *reinterpret_cast<const float2*>(ad.v_bias + 2 * (size_t)e);
-        }
-      }
-      if (touched || (PIPE && in_next)) {
-        io = a.inv_occ[e];
-        if constexpr (EPS == EPS_TABLE) epw = a.eps_bias[e];
-      }
-    }
+    RowRegs<VEC, CPL> r;
+    if (STAGE != STAGE_ACC && (ADAM || touched))
+      load_own_row<LPE, CPL, VEC, EPS, ADAM>(a, ad, e, d, C, lig, true, touched, touched || (PIPE && in_next), r);
 
-    // walk the inverted index: A = sum_r g_r * sumz_r, gs = sum_r g_r  (sz / hacc: the sample's blocks)
+    // walk the inverted index: A = sum_r g_r * sumz_r, gs = sum_r g_r
     int hslot = -1;
     if (STAGE != STAGE_APPLY && b.n_heavy > 0 && end - beg > VFM_HEAVY_MIN)
       hslot = heavy_slot_of(b.heavy_ids, b.n_heavy, (int)e);
-    if (ADAM == 1 && STAGE == STAGE_FULL && a.row_filter == 4 && hslot >= 0) { fetch_next(more); continue; }   // (the heavy-only launch takes it)
-    auto walk = [&](const float* __restrict__ sz, const float* __restrict__ hacc, Chunk<VEC>(&A)[CPL], float& gs) {
-#pragma unroll
-      for (int i = 0; i < CPL; ++i)
-#pragma unroll
-        for (int t = 0; t < VEC; ++t) A[i].v[t] = 0.f;
-      gs = 0.f;
-      int o = beg;
-      if (hslot >= 0) {      // pre-reduced by k_heavy: read the record(s), skip the walk
-        const float* rec = hacc + (size_t)hslot * xs;
-        int4 hd = *reinterpret_cast<const int4*>(rec);      // (sum grow, count, first item, last item + 1)
-        if (hd.z < 0 || hd.w < hd.z || hd.w > b.heavy_stride - b.n_heavy) { hd.z = hd.w = 0; ++nclamp; }
-        if (hd.w - hd.z <= VFM_HEAVY_DIRECT) {      // few work items: add their records here, in item order
-          for (int it = hd.z; it < hd.w; ++it) {
-            const float* ir = hacc + ((size_t)b.n_heavy + (size_t)it) * xs;
-            gs += ir[0];
-#pragma unroll
-            for (int i = 0; i < CPL; ++i) {
-              const int j = chunk_of(i);
-              if (j < C) {
-                const Chunk<VEC> t4 = ld_chunk<VEC>(ir + 4 + (size_t)j * VEC);
-#pragma unroll
-                for (int t = 0; t < VEC; ++t) A[i].v[t] += t4.v[t];
-              }
-            }
-          }
-        } else {                                    // k_heavy_sum added them into the entity's record
-          gs = __int_as_float(hd.x);
-#pragma unroll
-          for (int i = 0; i < CPL; ++i) {
-            const int j = chunk_of(i);
-            if (j < C) A[i] = ld_chunk<VEC>(rec + 4 + (size_t)j * VEC);
-          }
-        }
-        o = end;
-      }
-      // PIPE: the sample of the OTHER entity of the row (this step's records) stands in for the sumz row
-      auto src = [&](int oo, int r) -> const float* {
-        if constexpr (PIPE) return b.zrec + (size_t)ent_ok(b.occ_other[oo]) * xs + 4;
-        return sz + (size_t)r * d;
-      };
-      auto pair = [&](int o, int r0, int r1) {      // two occurrences in flight
-        r0 = row_ok(r0); r1 = row_ok(r1);
-        const float g0 = b.grow[r0], g1 = b.grow[r1];
-        const float* p0 = src(o, r0);
-        const float* p1 = src(o + 1, r1);
-        gs += g0 + g1;
-#pragma unroll
-        for (int i = 0; i < CPL; ++i) {
-          const int j = chunk_of(i);
-          if (j < C) {
-            const Chunk<VEC> s0v = ld_chunk<VEC>(p0 + (size_t)j * VEC);
-            const Chunk<VEC> s1v = ld_chunk<VEC>(p1 + (size_t)j * VEC);
-#pragma unroll
-            for (int t = 0; t < VEC; ++t) A[i].v[t] = fmaf(g1, s1v.v[t], fmaf(g0, s0v.v[t], A[i].v[t]));
-          }
-        }
-      };
-      int rt = -1;                         // PF: the tail's row number when the list has one entry (prefetched)
-      if constexpr (PF) {
-        if (o + 1 < end) { pair(o, rr.x, rr.y); o += 2; }
-        else if (o < end) rt = rr.x;
-      }
-      for (; o + 1 < end; o += 2) pair(o, b.occ_rows[o], b.occ_rows[o + 1]);
-      if (o < end) {
-        const int r0 = row_ok(rt >= 0 ? rt : b.occ_rows[o]);
-        const float g0 = b.grow[r0];
-        const float* p0 = src(o, r0);
-        gs += g0;
-#pragma unroll
-        for (int i = 0; i < CPL; ++i) {
-          const int j = chunk_of(i);
-          if (j < C) {
-            const Chunk<VEC> s0v = ld_chunk<VEC>(p0 + (size_t)j * VEC);
-#pragma unroll
-            for (int t = 0; t < VEC; ++t) A[i].v[t] = fmaf(g0, s0v.v[t], A[i].v[t]);
-          }
-        }
-      }
-    };
+    if (ADAM == 1 && STAGE == STAGE_FULL && a.row_filter == 4 && hslot >= 0) continue;   // (the heavy-only launch takes it)
     Chunk<VEC> A[CPL];
     float gs;
-    walk(b.sumz, b.heavy_acc, A, gs);
-    fetch_next(more);
+    walk_list<LPE, CPL, VEC, PIPE>(b, b.sumz, b.heavy_acc, hslot, beg, end, d, C, xs, lig, ig, A, gs);
 
-    if constexpr (STAGE == STAGE_ACC) {   // store the statistics (dense: zeros for rows not in this shard)
-#pragma unroll
-      for (int i = 0; i < CPL; ++i) {
-        const int j = chunk_of(i);
-        if (j < C) st_chunk<VEC>(b.acc + (size_t)rec * xs + 4 + (size_t)j * VEC, A[i]);
-      }
-      if (lig == 0) *reinterpret_cast<float4*>(b.acc + (size_t)rec * xs) = make_float4(gs, cntf, 0.f, 0.f);
+    if constexpr (STAGE == STAGE_ACC) {
+      store_statistics<LPE, CPL, VEC>(b.acc + (size_t)rec * xs, C, lig, A, gs, cntf);
       continue;
     }
     if constexpr (STAGE == STAGE_APPLY) {
       gs = gc.x;
-      if (touched) {
-#pragma unroll
-        for (int i = 0; i < CPL; ++i) {
-          const int j = chunk_of(i);
-          if (j < C) A[i] = ld_chunk<VEC>(b.acc + (size_t)rec * xs + 4 + (size_t)j * VEC);
-        }
-      }
+      if (touched) load_statistics<LPE, CPL, VEC>(b.acc + (size_t)rec * xs, C, lig, A);
     }
-
-    if (!touched && !ADAM) {   // entity not in the batch: dense zero row
-      Chunk<VEC> zc;
-#pragma unroll
-      for (int t = 0; t < VEC; ++t) zc.v[t] = 0.f;
-#pragma unroll
-      for (int i = 0; i < CPL; ++i) {
-        const int j = chunk_of(i);
-        if (j < C) {
-          st_chunk_nt<VEC>(grow_e + (size_t)j * VEC, zc);
-          st_chunk_nt<VEC>(grow_e + d + (size_t)j * VEC, zc);
-        }
-      }
-      if (lig == 0) *reinterpret_cast<float2*>(b.g_bias + 2 * (size_t)e) = make_float2(0.f, 0.f);
+    float* grow_e = ADAM ? nullptr : b.g_entity + (size_t)e * (2 * (size_t)d);
+    if (!touched && !ADAM) {
+      store_zero_row<LPE, CPL, VEC>(grow_e, b.g_bias + 2 * (size_t)e, d, C, lig);
       continue;
     }
 
-    float c = 0.f;
-    if (touched) {
-      c = sh_cs[group_index(sh_hi, a.G, e)] * io * cntf;
-    }
+    const float c = touched ? kl_weight(sh_cs, sh_hi, a.G, e, r.io, cntf) : 0.f;
     float nb_eps = 0.f;
     float nb_next = 0.f, kl_next = 0.f, w_next = 0.f;      // PIPE: the next step's first-order eps / KL / sampled weight
-    // S > 1 (uniform): g1s = 1/S sum_s (A^s - z^s gs), g2s = 1/S sum_s eps^s (A^s - z^s gs), nb_eps = mean_s eps_w^s
     // (MULTI is a template parameter so that the S = 1 instances carry none of this: registers, occupancy)
     constexpr bool multi = MULTI && STAGE == STAGE_FULL;
     Chunk<VEC> g1s[CPL], g2s[CPL];
-    if (multi && touched) {
-#pragma unroll
-      for (int i = 0; i < CPL; ++i)
-#pragma unroll
-        for (int t = 0; t < VEC; ++t) { g1s[i].v[t] = 0.f; g2s[i].v[t] = 0.f; }
-      for (int sm = 0; sm < a.S; ++sm) {
-        if (sm > 0)
-          walk(b.sumz + (size_t)sm * (size_t)a.B * d, b.heavy_acc + (size_t)sm * (size_t)b.heavy_stride * xs, A, gs);
-        const RngKey ks = key_of_sample(key, sm);
-#pragma unroll
-        for (int i = 0; i < CPL; ++i) {
-          const int j = chunk_of(i);
-          if (j < C) {
-            Chunk<VEC> epc;
-            if constexpr (EPS == EPS_TABLE) {
-              epc = ld_chunk<VEC>(a.eps_entity + ((size_t)sm * (size_t)a.T + (size_t)e) * d + (size_t)j * VEC);
-            } else if constexpr (EPS == EPS_ZERO) {
-#pragma unroll
-              for (int t = 0; t < VEC; ++t) epc.v[t] = 0.f;
-            } else {
-              float nb;
-              eps_of_chunk<VEC>(ks, (uint32_t)e, j, epc.v, nb);
-              if (i == 0) nb_eps += nb;
-            }
-#pragma unroll
-            for (int t = 0; t < VEC; ++t) {
-              const float z = fmaf(link_f<LINK>(s[i].v[t]), epc.v[t], mu[i].v[t]);
-              const float gz = A[i].v[t] - z * gs;
-              g1s[i].v[t] += gz;
-              g2s[i].v[t] = fmaf(gz, epc.v[t], g2s[i].v[t]);
-            }
-          }
-        }
-        if constexpr (EPS == EPS_TABLE) nb_eps += a.eps_bias[(size_t)sm * (size_t)a.T + (size_t)e];
-      }
-      nb_eps *= a.inv_S;
-#pragma unroll
-      for (int i = 0; i < CPL; ++i)
-#pragma unroll
-        for (int t = 0; t < VEC; ++t) { g1s[i].v[t] *= a.inv_S; g2s[i].v[t] *= a.inv_S; }
-    }
-    Chunk<VEC> epp[ADJ ? CPL : 1];      // ADJ: the eps of both chunks, from the lane's one Philox call
-    if constexpr (ADJ) {
-      if (touched) eps_of_chunk_pair(key, (uint32_t)e, lig, epp[0].v, epp[1].v, nb_eps);
-    }
+    if (multi && touched)
+      sample_means<LPE, CPL, VEC, EPS, LINK>(a, b, key, e, hslot, beg, end, d, C, xs, lig, ig, r, A, gs, g1s, g2s, nb_eps);
 #pragma unroll
     for (int i = 0; i < CPL; ++i) {
-      const int j = chunk_of(i);
+      const int j = chunk_of<LPE>(lig, i);
       if (j < C) {
         Chunk<VEC> gm, gv;
         if (touched && multi) {
-#pragma unroll
-          for (int t = 0; t < VEC; ++t) {
-            const float sg = link_f<LINK>(s[i].v[t]);
-            gm.v[t] = gout * (g1s[i].v[t] + c * mu[i].v[t]);
-            gv.v[t] = gout * dlink_f<LINK>(s[i].v[t]) * (g2s[i].v[t] + c * (sg - inv_sigma(sg)));
-          }
+          chunk_grad_multi<VEC, LINK>(r.mu[i], r.s[i], g1s[i], g2s[i], c, gout, gm, gv);
         } else if (touched) {
           Chunk<VEC> epc;
-          if constexpr (EPS == EPS_TABLE) {
-            epc = ep[i];
-          } else if constexpr (EPS == EPS_ZERO) {
-#pragma unroll
-            for (int t = 0; t < VEC; ++t) epc.v[t] = 0.f;
-          } else if constexpr (ADJ) {
-            epc = epp[i];
-          } else {
-            float nb;
-            eps_of_chunk<VEC>(key, (uint32_t)e, j, epc.v, nb);
-            if (i == 0) nb_eps = nb;
-          }
-#pragma unroll
-          for (int t = 0; t < VEC; ++t) {
-            const float sg = link_f<LINK>(s[i].v[t]);
-            const float z = fmaf(sg, epc.v[t], mu[i].v[t]);
-            // sum_r g_r (sumz_rk - z_ek); PIPE: A already sums the other entity's z alone
-            const float gz = PIPE ? A[i].v[t] : A[i].v[t] - z * gs;
-            gm.v[t] = gout * (gz + c * mu[i].v[t]);
-            gv.v[t] = gout * dlink_f<LINK>(s[i].v[t]) * (gz * epc.v[t] + c * (sg - inv_sigma(sg)));
-          }
+          float nb;
+          chunk_eps<VEC, EPS>(key, e, j, r.ep[i], epc, nb);
+          if (EPS == EPS_PHILOX && i == 0) nb_eps = nb;
+          chunk_grad<VEC, LINK, PIPE>(r.mu[i], r.s[i], epc, A[i], gs, c, gout, gm, gv);
         } else {
 #pragma unroll
           for (int t = 0; t < VEC; ++t) { gm.v[t] = 0.f; gv.v[t] = 0.f; }
         }
-        float rm[VEC], rs[VEC];        // LA: sqrt of the stored second moments
-        if constexpr (LA) {
-          if (la_gap > 0) {            // (uniform over the lane group) bring the row up to the step before this one
-#pragma unroll
-            for (int t = 0; t < VEC; ++t) { rm[t] = __builtin_amdgcn_sqrtf(vm[i].v[t]); rs[t] = __builtin_amdgcn_sqrtf(vs[i].v[t]); }
-            for (int k = la_k - la_gap; k < la_k; ++k) {
-              const float2 c = sh_tab[k];
-#pragma unroll
-              for (int t = 0; t < VEC; ++t) {
-                mu[i].v[t] = replay_one(mu[i].v[t], mm[i].v[t], rm[t], c, ad.eps);
-                s[i].v[t] = replay_one(s[i].v[t], ms[i].v[t], rs[t], c, ad.eps);
-              }
-            }
-          }
-        }
         if constexpr (ADAM) {
           Chunk<VEC> pm, ps;
-          if constexpr (LA) {          // (always the scaled form) adam_update in its halves
-#pragma unroll
-            for (int t = 0; t < VEC; ++t) {
-              adam_accum(gm.v[t], mm[i].v[t], vm[i].v[t], ad);
-              adam_accum(gv.v[t], ms[i].v[t], vs[i].v[t], ad);
-            }
-            // a replayed row without gradient: vm / vs are what they were (fma(c2 0, 0, v) = v), rm / rs are their roots
-            if (!(la_gap > 0 && !touched)) {
-#pragma unroll
-              for (int t = 0; t < VEC; ++t) { rm[t] = __builtin_amdgcn_sqrtf(vm[i].v[t]); rs[t] = __builtin_amdgcn_sqrtf(vs[i].v[t]); }
-            }
-#pragma unroll
-            for (int t = 0; t < VEC; ++t) {
-              pm.v[t] = adam_apply(mu[i].v[t], mm[i].v[t], vm[i].v[t], rm[t], ad);
-              ps.v[t] = adam_apply(s[i].v[t], ms[i].v[t], vs[i].v[t], rs[t], ad);
-            }
-          } else {
-#pragma unroll
-            for (int t = 0; t < VEC; ++t) {
-              pm.v[t] = adam_update(mu[i].v[t], gm.v[t], mm[i].v[t], vm[i].v[t], ad);
-              ps.v[t] = adam_update(s[i].v[t], gv.v[t], ms[i].v[t], vs[i].v[t], ad);
-            }
-          }
-          const size_t o2 = (size_t)e * (2 * (size_t)d) + (size_t)j * VEC;
-          st_chunk<VEC>(prow + (size_t)j * VEC, pm);
-          st_chunk<VEC>(prow + d + (size_t)j * VEC, ps);
-          if (!ad.scaled || touched || ad.store_true) {     // (scaled: rows without gradient keep ms, vs)
-            st_chunk_nt<VEC>(ad.m_entity + o2, mm[i]); st_chunk_nt<VEC>(ad.m_entity + o2 + d, ms[i]);
-            st_chunk_nt<VEC>(ad.v_entity + o2, vm[i]); st_chunk_nt<VEC>(ad.v_entity + o2 + d, vs[i]);
-          }
+          adam_row_step<VEC, LA>(r.mu[i].v, r.s[i].v, r.mm[i].v, r.ms[i].v, r.vm[i].v, r.vs[i].v, gm.v, gv.v, la_gap, la_k, sh_tab,
+                                 touched, ad, pm.v, ps.v);
+          store_row_chunk<VEC>(a, ad, e, d, j, touched, pm, ps, r.mm[i], r.ms[i], r.vm[i], r.vs[i]);
           if constexpr (PIPE) {
-            if (in_next) {     // the updated row is in registers: sample it for the next step right here
-              Chunk<VEC> ep2, zn;
-              float nb2;
-              eps_of_chunk<VEC>(next_key, (uint32_t)e, j, ep2.v, nb2);
-              if (i == 0) nb_next = nb2;
-#pragma unroll
-              for (int t = 0; t < VEC; ++t) {
-                const float sg2 = link_f<LINK>(ps.v[t]);
-                zn.v[t] = fmaf(sg2, ep2.v[t], pm.v[t]);
-                kl_next += kl_std_normal(pm.v[t], sg2);
-              }
-              st_chunk<VEC>(b.zrec_next + (size_t)e * xs + 4 + (size_t)j * VEC, zn);
-            }
+            if (in_next) next_record_chunk<VEC, LINK>(b, next_key, e, j, xs, pm, ps, i == 0, nb_next, kl_next);
           }
-
         } else {
           st_chunk_nt<VEC>(grow_e + (size_t)j * VEC, gm);
           st_chunk_nt<VEC>(grow_e + d + (size_t)j * VEC, gv);
@@ -586,60 +717,23 @@ __global__ __launch_bounds__(BLOCK, (PIPE && CPL == 1) ? 4 : 1) void k_bwd(const
       float g0 = 0.f, g1 = 0.f;
       if (touched) {
         if constexpr (EPS == EPS_TABLE)
-          if (!multi) nb_eps = epw;
-        const float sg = link_f<LINK>(th.y);
-        g0 = gout * (gs + c * th.x);
-        g1 = gout * dlink_f<LINK>(th.y) * (gs * nb_eps + c * (sg - inv_sigma(sg)));
+          if (!multi) nb_eps = r.epw;
+        first_order_grad<LINK>(r.th, gs, nb_eps, c, gout, g0, g1);
       }
-      float r0, r1;                  // LA: sqrt of the stored second moments of (mu_w, s_w)
-      if constexpr (LA) {
-        if (la_gap > 0) {
-          r0 = __builtin_amdgcn_sqrtf(vb.x); r1 = __builtin_amdgcn_sqrtf(vb.y);
-          for (int k = la_k - la_gap; k < la_k; ++k) {
-            const float2 c = sh_tab[k];
-            th.x = replay_one(th.x, mb.x, r0, c, ad.eps);
-            th.y = replay_one(th.y, mb.y, r1, c, ad.eps);
-          }
-        }
-        b.last_step[e] = la_step;
-      }
+      if constexpr (LA) b.last_step[e] = la_step;
       if constexpr (ADAM) {
-        float2 pn;
-        if constexpr (LA) {            // the halves of adam_update, the roots handed over as for the embedding row
-          adam_accum(g0, mb.x, vb.x, ad);
-          adam_accum(g1, mb.y, vb.y, ad);
-          if (!(la_gap > 0 && !touched)) { r0 = __builtin_amdgcn_sqrtf(vb.x); r1 = __builtin_amdgcn_sqrtf(vb.y); }
-          pn.x = adam_apply(th.x, mb.x, vb.x, r0, ad);
-          pn.y = adam_apply(th.y, mb.y, vb.y, r1, ad);
-        } else {
-          pn.x = adam_update(th.x, g0, mb.x, vb.x, ad);
-          pn.y = adam_update(th.y, g1, mb.y, vb.y, ad);
-        }
-        *reinterpret_cast<float2*>(const_cast<float*>(a.bias) + 2 * (size_t)e) = pn;
-        if (a.wrec) *reinterpret_cast<float2*>(a.wrec + 4 * (size_t)e) = pn;      // packed first-order record: (mu_w, s_w | 1/occ, 0)
+        const float2 pn = adam_pair_step<LA>(r.th, r.mb, r.vb, g0, g1, la_gap, la_k, sh_tab, touched, ad);
+        store_first_order(a, ad, e, touched, pn, r.mb, r.vb);
         if constexpr (PIPE) {
-          if (in_next) {
-            const float sgw2 = link_f<LINK>(pn.y);
-            w_next = fmaf(sgw2, nb_next, pn.x);
-            kl_next += kl_std_normal(pn.x, sgw2);
-          }
-        }
-        if (!ad.scaled || touched || ad.store_true) {
-          *reinterpret_cast<float2*>(ad.m_bias + 2 * (size_t)e) = mb;
-          *reinterpret_cast<float2*>(ad.v_bias + 2 * (size_t)e) = vb;
+          if (in_next) next_record_weight<LINK>(pn, nb_next, w_next, kl_next);
         }
       } else {
         *reinterpret_cast<float2*>(b.g_bias + 2 * (size_t)e) = make_float2(g0, g1);
       }
     }
     if constexpr (PIPE) {
-      if (in_next) {           // (uniform over the lane group) header of the next-step record: (w, weighted KL, 0, 0)
-        kl_next = group_sum<LPE>(kl_next);
-        if (lig == 0)
-          *reinterpret_cast<float4*>(b.zrec_next + (size_t)e * xs) =
-              make_float4(w_next, kl_next * (sh_cs_next[group_index(sh_hi, a.G, e)] * io), 0.f, 0.f);
-      }
+      if (in_next) next_record_header<LPE>(b, e, xs, lig, w_next, kl_next, sh_cs_next[group_index(sh_hi, a.G, e)], r.io);
     }
   }
-  if (nclamp != 0 && b.status) atomicAdd(b.status, nclamp);       // (integer: the total does not depend on the order)
+  ig.report(b.status);
 }

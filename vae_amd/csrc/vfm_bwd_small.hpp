@@ -19,9 +19,10 @@
 //                     groups), then P_0 + P_1 + ... in order; with at most VFM_HEAVY_DIRECT items k_bwd adds the items in
 //                     order itself -- here: VFM_HEAVY_DIRECT partial sums of one item each (0 + x = x)
 //   a short list:     k_bwd's own walk: A = fma(g1, s1, fma(g0, s0, A)) two occurrences at a time, gs += g0 + g1
-// -- and the epilogue (eps regeneration, KL part, link, Adam) is k_bwd's, expression for expression (the unit is compiled
-// with -ffp-contract=on: fusion follows the source expression, so equal source gives equal bits).  tests/test_gpu_model.py
-// runs both paths side by side (VFM_BWD_SMALL=0 forces the three-launch path).
+// -- and the scalars, the short walk and the epilogue (eps regeneration, KL part, link, Adam, stores) are k_bwd's own
+// functions (vfm_bwd.hpp; the unit is compiled with -ffp-contract=on: fusion follows the source expression, so the same
+// function gives the same bits in both kernels).  What is written out here is this kernel's alone: the per-item partial
+// sums in LDS.  tests/test_gpu_model.py runs both paths side by side (VFM_BWD_SMALL=0 forces the three-launch path).
 // Serves: STAGE_FULL, fused dense Adam (scaled or plain moments), Philox eps, one sample, every row, d % 4 == 0, d <= 256.
 template <int LPE, int LINK>
 __global__ __launch_bounds__(BLOCK) void k_bwd_small(const KArgs a, const BwdArgs b, const AdamArgs ad_in, int L, int THR) {
@@ -52,75 +53,22 @@ __global__ __launch_bounds__(BLOCK) void k_bwd_small(const KArgs a, const BwdArg
   const float gout = 1.0f;
 
   // ---- loss + the three scalars: workgroup 0, as in k_bwd
-  double fin[6] = {0, 0, 0, 0, 0, 0};
-  const bool fold = b.loss != nullptr;
-  if (blockIdx.x == 0 && fold)
-    reduce_slots_and_loss(b.partials, a.scalars, a.ll_scale_d, a.flags, b.loss, sh_fin, fin);
-  if (blockIdx.x == 0 && tid == 0) {
-    const float alpha = a.scalars[0], m0 = a.scalars[1], s0 = a.scalars[2];
-    const bool stale = !fold && b.partials[VFM_P_REDUCED] != 1.0;
-    const float sum_g = stale ? __builtin_nanf("") : (float)(fold ? fin[VFM_P_G] : b.partials[VFM_P_G]);
-    const float sum_a = (float)(fold ? fin[VFM_P_ALPHA] : b.partials[VFM_P_ALPHA]);
-    float e0 = 0.f;
-    {
-      float n[8], nb;
-      normal8b(key, 0xFFFFFFFFu, 0u, n, nb);
-      e0 = n[0];
-    }
-    const float as0 = link_f<LINK>(s0);
-    const float prior = (a.flags & VFM_FLAG_NO_PRIOR_TERMS) ? 0.f : 1.f;
-    const float ga = (a.lik == VFM_LIK_NORMAL)
-                         ? gout * dlink_f<LINK>(alpha) * a.ll_scale * sum_a : 0.f;
-    const float gm = gout * (sum_g + prior * m0);
-    const float ge0 = e0 * sum_g;
-    const float gs = gout * dlink_f<LINK>(s0) * (ge0 + prior * (as0 - inv_sigma(as0)));
-    float* sc = const_cast<float*>(a.scalars);
-    auto upd = [&](int i, float g) {
-      float m = ad.m_scal[i], v = ad.v_scal[i];
-      sc[i] = adam_update(sc[i], g, m, v, ad);
-      ad.m_scal[i] = m; ad.v_scal[i] = v;
-    };
-    if (a.lik == VFM_LIK_NORMAL) upd(0, ga);
-    upd(1, gm);
-    upd(2, gs);
-  }
+  scalars_and_loss<EPS_PHILOX, 1, STAGE_FULL, LINK, false>(a, b, ad, key, gout, true, true, sh_fin);
 
   // ---- the table rows: one wave each
-  int nclamp = 0;
-  const int n_occ = b.n_occ;
-  const int Bm1 = a.B > 0 ? (int)a.B - 1 : 0;
-  auto row_ok = [&](int v, bool live = true) -> int {
-    const bool ok = (unsigned)v <= (unsigned)Bm1;
-    nclamp += (ok || !live) ? 0 : 1;
-    return ok ? v : 0;
-  };
+  IndexGuard ig(a, b);
   float(*P)[4 * LPE + 4] = sh_P[wave];
   for (int64_t e = (int64_t)blockIdx.x * WPB + wave; e < a.T; e += (int64_t)gridDim.x * WPB) {
-    int beg = b.occ_ptr[e], end = b.occ_ptr[e + 1];
-    if (beg < 0 || end < beg || end > n_occ) { beg = end = 0; ++nclamp; }
+    const int2 pq = ig.span_ok(make_int2(b.occ_ptr[e], b.occ_ptr[e + 1]));
+    const int beg = pq.x, end = pq.y;
     const bool touched = beg != end;
     const float cntf = (float)(end - beg);
-    float* prow = const_cast<float*>(a.entity) + (size_t)e * (2 * (size_t)d);
     // the row's own parameters and moments: issued before the list is walked (first lane group of the wave)
-    Chunk<VEC> mu, s, mm, ms, vm, vs;
-    float2 th = make_float2(0.f, 1.f), mb = make_float2(0.f, 0.f), vb = make_float2(0.f, 0.f);
-    float io = 0.f;
-    const bool mine = lg == 0 && lig < C;
-    if (mine) {
-      mu = ld_chunk<VEC>(prow + (size_t)lig * VEC);
-      s = ld_chunk<VEC>(prow + d + (size_t)lig * VEC);
-      const size_t o = (size_t)e * (2 * (size_t)d) + (size_t)lig * VEC;
-      mm = ld_chunk_nt<VEC>(ad.m_entity + o); ms = ld_chunk_nt<VEC>(ad.m_entity + o + d);
-      vm = ld_chunk_nt<VEC>(ad.v_entity + o); vs = ld_chunk_nt<VEC>(ad.v_entity + o + d);
-    }
-    if (lane == 0) {
-      th = *reinterpret_cast<const float2*>(a.bias + 2 * (size_t)e);
-      mb = *reinterpret_cast<const float2*>(ad.m_bias + 2 * (size_t)e);
-      vb = *reinterpret_cast<const float2*>(ad.v_bias + 2 * (size_t)e);
-    }
-    if (touched && lg == 0) io = a.inv_occ[e];
+    RowRegs<VEC, 1> own;
+    load_own_row<LPE, 1, VEC, EPS_PHILOX, 1>(a, ad, e, d, C, lig, lg == 0, touched, touched, own);
 
-    Chunk<VEC> A;
+    Chunk<VEC> A1[1];
+    Chunk<VEC>& A = A1[0];
 #pragma unroll
     for (int t = 0; t < VEC; ++t) A.v[t] = 0.f;
     float gs = 0.f;
@@ -154,7 +102,7 @@ __global__ __launch_bounds__(BLOCK) void k_bwd_small(const KArgs a, const BwdArg
             float g[U];
             Chunk<VEC> sv[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) r[u] = row_ok(rn[u], o + u < ie);
+            for (int u = 0; u < U; ++u) r[u] = ig.row_ok(rn[u], o + u < ie);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
               g[u] = b.grow[r[u]];
@@ -190,87 +138,33 @@ __global__ __launch_bounds__(BLOCK) void k_bwd_small(const KArgs a, const BwdArg
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");      // (... and the reads before the next row's writes)
       __builtin_amdgcn_wave_barrier();
     } else if (lg == 0) {
-      // a short list: k_bwd's own walk, two occurrences in flight
-      int o = beg;
-      for (; o + 1 < end; o += 2) {
-        const int r0 = row_ok(b.occ_rows[o]), r1 = row_ok(b.occ_rows[o + 1]);
-        const float g0 = b.grow[r0], g1 = b.grow[r1];
-        gs += g0 + g1;
-        if (lig < C) {
-          const Chunk<VEC> s0v = ld_chunk<VEC>(b.sumz + (size_t)r0 * d + (size_t)lig * VEC);
-          const Chunk<VEC> s1v = ld_chunk<VEC>(b.sumz + (size_t)r1 * d + (size_t)lig * VEC);
-#pragma unroll
-          for (int t = 0; t < VEC; ++t) A.v[t] = fmaf(g1, s1v.v[t], fmaf(g0, s0v.v[t], A.v[t]));
-        }
-      }
-      if (o < end) {
-        const int r0 = row_ok(b.occ_rows[o]);
-        const float g0 = b.grow[r0];
-        gs += g0;
-        if (lig < C) {
-          const Chunk<VEC> s0v = ld_chunk<VEC>(b.sumz + (size_t)r0 * d + (size_t)lig * VEC);
-#pragma unroll
-          for (int t = 0; t < VEC; ++t) A.v[t] = fmaf(g0, s0v.v[t], A.v[t]);
-        }
-      }
+      walk_pairs<LPE, 1, VEC, false>(b, b.sumz, beg, end, d, C, 0, lig, ig, A1, gs);      // a short list: k_bwd's own walk
     }
-    if (lg != 0) continue;                           // (the row's epilogue: the wave's first lane group)
+    if (lg != 0) continue;                           // (the row's epilogue, k_bwd's: the wave's first lane group)
 
-    float c = 0.f;
-    if (touched) {
-      c = sh_cs[group_index(sh_hi, a.G, e)] * io * cntf;
-    }
+    const float c = touched ? kl_weight(sh_cs, sh_hi, a.G, e, own.io, cntf) : 0.f;
     float nb_eps = 0.f;
     if (lig < C) {
       Chunk<VEC> gm, gv;
       if (touched) {
         Chunk<VEC> epc;
-        float nb;
-        eps_of_chunk<VEC>(key, (uint32_t)e, lig, epc.v, nb);
-        nb_eps = nb;
-#pragma unroll
-        for (int t = 0; t < VEC; ++t) {
-          const float sg = link_f<LINK>(s.v[t]);
-          const float z = fmaf(sg, epc.v[t], mu.v[t]);
-          const float gz = A.v[t] - z * gs;
-          gm.v[t] = gout * (gz + c * mu.v[t]);
-          gv.v[t] = gout * dlink_f<LINK>(s.v[t]) * (gz * epc.v[t] + c * (sg - inv_sigma(sg)));
-        }
+        chunk_eps<VEC, EPS_PHILOX>(key, e, lig, own.ep[0], epc, nb_eps);
+        chunk_grad<VEC, LINK, false>(own.mu[0], own.s[0], epc, A, gs, c, gout, gm, gv);
       } else {
 #pragma unroll
         for (int t = 0; t < VEC; ++t) { gm.v[t] = 0.f; gv.v[t] = 0.f; }
       }
       Chunk<VEC> pm, ps;
-#pragma unroll
-      for (int t = 0; t < VEC; ++t) {
-        pm.v[t] = adam_update(mu.v[t], gm.v[t], mm.v[t], vm.v[t], ad);
-        ps.v[t] = adam_update(s.v[t], gv.v[t], ms.v[t], vs.v[t], ad);
-      }
-      const size_t o2 = (size_t)e * (2 * (size_t)d) + (size_t)lig * VEC;
-      st_chunk<VEC>(prow + (size_t)lig * VEC, pm);
-      st_chunk<VEC>(prow + d + (size_t)lig * VEC, ps);
-      if (!ad.scaled || touched || ad.store_true) {     // (scaled: rows without gradient keep ms, vs)
-        st_chunk_nt<VEC>(ad.m_entity + o2, mm); st_chunk_nt<VEC>(ad.m_entity + o2 + d, ms);
-        st_chunk_nt<VEC>(ad.v_entity + o2, vm); st_chunk_nt<VEC>(ad.v_entity + o2 + d, vs);
-      }
+      adam_row_step<VEC, false>(own.mu[0].v, own.s[0].v, own.mm[0].v, own.ms[0].v, own.vm[0].v, own.vs[0].v, gm.v, gv.v, 0, 0, nullptr, touched,
+                                ad, pm.v, ps.v);
+      store_row_chunk<VEC>(a, ad, e, d, lig, touched, pm, ps, own.mm[0], own.ms[0], own.vm[0], own.vs[0]);
     }
     if (lig == 0) {
       float g0 = 0.f, g1 = 0.f;
-      if (touched) {
-        const float sg = link_f<LINK>(th.y);
-        g0 = gout * (gs + c * th.x);
-        g1 = gout * dlink_f<LINK>(th.y) * (gs * nb_eps + c * (sg - inv_sigma(sg)));
-      }
-      float2 pn;
-      pn.x = adam_update(th.x, g0, mb.x, vb.x, ad);
-      pn.y = adam_update(th.y, g1, mb.y, vb.y, ad);
-      *reinterpret_cast<float2*>(const_cast<float*>(a.bias) + 2 * (size_t)e) = pn;
-      if (a.wrec) *reinterpret_cast<float2*>(a.wrec + 4 * (size_t)e) = pn;      // packed first-order record: (mu_w, s_w | 1/occ, 0)
-      if (!ad.scaled || touched || ad.store_true) {
-        *reinterpret_cast<float2*>(ad.m_bias + 2 * (size_t)e) = mb;
-        *reinterpret_cast<float2*>(ad.v_bias + 2 * (size_t)e) = vb;
-      }
+      if (touched) first_order_grad<LINK>(own.th, gs, nb_eps, c, gout, g0, g1);
+      const float2 pn = adam_pair_step<false>(own.th, own.mb, own.vb, g0, g1, 0, 0, nullptr, touched, ad);
+      store_first_order(a, ad, e, touched, pn, own.mb, own.vb);
     }
   }
-  if (nclamp != 0 && b.status) atomicAdd(b.status, nclamp);
+  ig.report(b.status);
 }

@@ -86,18 +86,3 @@ __device__ __forceinline__ void eps_of_chunk(const RngKey& k, uint32_t e, int j,
     ep[0] = v;
   }
 }
-
-// eps of the chunk pair (2p, 2p+1) for the lane that owns both (8 adjacent coordinates), plus the bias eps: ONE Philox
-// call, of which eps_of_chunk<4> on chunk 2p uses fields 0, 1 and on chunk 2p+1 fields 2, 3 -- the fields are picked
-// before Box-Muller exactly as there, so ep0 / ep1 / nb are bit for bit what the two calls return
-__device__ __forceinline__ void eps_of_chunk_pair(const RngKey& k, uint32_t e, int p, float (&ep0)[4], float (&ep1)[4], float& nb) {
-  const uint32_t pg = (uint32_t)p + (k.chunk_off >> 1);      // global pair (chunk_off is even)
-  uint32_t o[4];
-  philox4x32_10(pg, e, k.step_lo, k.step_hi, k.seed_lo, k.seed_hi, o);
-  box_muller_bits<16, 10>(o[0], ep0[0], ep0[1]);
-  box_muller_bits<16, 10>(__builtin_amdgcn_alignbit(o[1], o[0], 26), ep0[2], ep0[3]);
-  box_muller_bits<16, 10>(__builtin_amdgcn_alignbit(o[2], o[1], 20), ep1[0], ep1[1]);
-  box_muller_bits<16, 10>(__builtin_amdgcn_alignbit(o[3], o[2], 14), ep1[2], ep1[3]);
-  float unused;
-  box_muller_bits<16, 8>(o[3] >> 8, nb, unused);
-}
