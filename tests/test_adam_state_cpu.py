@@ -92,7 +92,8 @@ def test_planted_states_of_the_gpu_cases_leave_at_most_two_percent_out():
     and the fp64 step -- what falls out of the update assertion are the fresh rows alone, within the cap; and every
     problem has at least 30 % of its rows in the batch and 30 % outside."""
     from test_gpu_adam_state import build_problem, problems_of_gpu_cases
-    for name, kw in problems_of_gpu_cases():
+    from test_gpu_lazy_forms import problems_of_lazy_forms
+    for name, kw in problems_of_gpu_cases() + [(name, kw) for name, kw, _ in problems_of_lazy_forms()]:
         pb = build_problem(**kw)
         touched, T, d = pb["touched"], pb["spec"].T, pb["spec"].d
         assert T >= 200 and 0.3 <= touched.mean() <= 0.7, (name, T, touched.mean())
@@ -105,6 +106,28 @@ def test_planted_states_of_the_gpu_cases_leave_at_most_two_percent_out():
             ok = R.asserted(float(np.abs(g).max()), g, v_ref, fresh)
             assert 1.0 - ok.mean() <= R.MAX_EXCLUDED, (name, 1.0 - ok.mean())
             assert np.array_equal(~ok.all(axis=1), fresh), name          # (only the fresh rows)
+
+
+def test_lookahead_problems_of_the_gpu_cases_meet_their_preconditions():
+    """Pure numpy: every look-ahead problem of tests/test_gpu_lazy_forms.py, with the next batch _case will draw for it, has
+    >= 30 % of its rows in this batch and >= 30 % outside, >= 20 rows only the next batch holds and >= 20 rows in neither
+    (asserted by _lookahead_lag itself), and the fresh rows -- all a record check can lose -- within the 2 % cap."""
+    from test_gpu_adam_state import build_problem
+    from test_gpu_lazy_forms import lookahead_split, problems_of_lazy_forms
+    n = 0
+    for name, kw, steps in problems_of_lazy_forms():
+        if not steps:
+            continue
+        pb = build_problem(**kw)
+        touched, T = pb["touched"], pb["spec"].T
+        assert 0.3 <= touched.mean() <= 0.7, (name, touched.mean())
+        assert 4.0 / T <= R.MAX_EXCLUDED, (name, T)
+        for t in steps:
+            nxt = lookahead_split(pb, t)
+            assert nxt["x"].shape == pb["x"].shape and (nxt["mask"] & ~touched).sum() >= 20, name
+            assert (~nxt["mask"] & ~touched).sum() >= 20, name
+            n += 1
+    assert n >= 28
 
 
 def _consts(lr, t, scaled):

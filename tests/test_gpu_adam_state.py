@@ -223,8 +223,15 @@ def _case(entry, pb, t, form, eps="table", ids=I64, lag=None, run=None, tag=None
         c.st = ops.elbo_forward(c.plan, c.ent, c.bia, c.scal, c.inv_occ, **kw)
         return c.st
     c.forward = forward
+    c.params_at_gradient = None
     run(c)
     torch.cuda.synchronize()
+    if c.params_at_gradient is not None:
+        # A run that caught its rows up itself hands over the (entity, bias) tables its gradient was taken at.  The fp32
+        # replay may differ from the fp64 one by replay_bound (granted to the update below); where the replay has carried
+        # a scale parameter close to zero, the 1 / sigma term of the KL gradient turns that difference into more than the
+        # gradient's own grant, so the reference gradient is taken where the kernel's was.
+        r = oracle([a.astype(np.float64) for a in c.params_at_gradient] + [before[2]])
 
     # reference: the gradient at the fp64 caught-up parameters, one Adam step, a zero-gradient one where the row is not
     # in the batch
@@ -239,6 +246,7 @@ def _case(entry, pb, t, form, eps="table", ids=I64, lag=None, run=None, tag=None
     got_m = [a.cpu().numpy() for a in c.mv]
     got_v = [a.cpu().numpy() for a in c.vv]
     k_step = ((t - 1) % R.PERIOD + 1) if scaled else 0
+    c.keep, c.p_ref, c.du, c.ok = keep, [], [], []     # for callers that go on from the fp64 step (its p', the bound on p')
     for i, kind in enumerate(("entity", "bias", "scalars")):
         rows = (~keep) if i < 2 else sc_ok
         kept = keep if i < 2 else (slice(0, 1) if output == "class" else slice(0, 0))
@@ -251,6 +259,7 @@ def _case(entry, pb, t, form, eps="table", ids=I64, lag=None, run=None, tag=None
         du = du + (R.replay_bound(before[i], moved[i], nrep[i]) if i < 2 else 0.0)
         em, ev = np.abs(m_got - m_ref) / dm, np.abs(v_got - v_ref) / dv
         ok = R.asserted(G[i], g64[i], v_ref, fresh if i < 2 else None)
+        c.p_ref.append(p_ref); c.du.append(du); c.ok.append(ok)
         sel = np.zeros(ok.shape, bool)
         sel[rows] = True
         left_out = 1.0 - (ok | ~sel).mean()
@@ -374,9 +383,12 @@ def test_lazy_step_from_a_lagging_state(d, t):
 
 # ------------------------------------------------------------------------------------------------ f. look-ahead entry
 def _lookahead_lag(rng, c, pb, t, nxt):
-    """A next batch over the same tables (kept in nxt), lags for every row outside this batch, and the rows in neither."""
-    T, sizes = c.spec.T, table_sizes(2, pb["B"])
-    x2 = np.stack([rng.integers(0, sizes[0], pb["B"]), sizes[0] + rng.integers(0, sizes[1], pb["B"])], 1).astype(np.int64)
+    """A next batch over the same tables (kept in nxt), lags for every row outside this batch, and the rows in neither.
+    One column per field, drawn field by field (F = 2: the draws of the two-column form this grew from)."""
+    T = c.spec.T
+    hi = np.asarray(pb["group_hi"], np.int64)
+    lo = np.concatenate([[0], hi[:-1]])
+    x2 = np.stack([int(lo[f]) + rng.integers(0, int(hi[f] - lo[f]), pb["B"]) for f in range(len(hi))], 1).astype(np.int64)
     in_next = np.zeros(T, bool)
     in_next[x2.reshape(-1)] = True
     nxt["x"], nxt["mask"] = x2, in_next
