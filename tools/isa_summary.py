@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Instruction-class counts of named kernel instances from the gfx950 ISA hipcc emits (`--offload-device-only -S`):
 the evidence behind "hand-written CDNA4, no scratch, counted waits" without asking the reader to recompile.
-usage: tools/isa_summary.py > profiles/rNN_isa_summary.txt       (cross-compiles; no GPU needed; ~3 minutes)"""
+usage: tools/isa_summary.py [--only SUBSTRING] > profiles/rNN_isa_summary.txt       (cross-compiles; no GPU needed;
+~3 minutes; --only keeps the entries whose translation unit or instance name holds SUBSTRING)"""
 import collections
 import os
 import re
@@ -27,6 +28,13 @@ WANT = [
     ("vfm_index.hip", [], "k_radix_scatter<true>", "index build: last radix pass (writes occ_rows / occ_other)"),
     ("vfm_index.hip", [], "k_index_count<true>", "index build: occ_ptr by LDS-staged lower bounds + per-chunk counts (256-thread workgroups)"),
     ("vfm_index.hip", [], "k_index_write<false>", "index build: heavy lists, work items, touched list, totals, W"),
+    # field-form elicitation sessions (a path relative to csrc/; --only elicit_field prints these alone)
+    ("../csrc_rank/vfm_elicit_field.hip", ["-ffp-contract=on"], "k_elicit_field<8, 1, 0, false>", "field-form session, d <= 8, closed form, |.|"),
+    ("../csrc_rank/vfm_elicit_field.hip", ["-ffp-contract=on"], "k_elicit_field<64, 2, 0, false>", "field-form session, d = 128 (the benchmark shape), closed form, |.|"),
+    ("../csrc_rank/vfm_elicit_field.hip", ["-ffp-contract=on"], "k_elicit_field<64, 2, 1, true>", "field-form session, d = 128, sampled, softplus"),
+    ("../csrc_rank/vfm_elicit_field.hip", ["-ffp-contract=on"], "k_elicit_field<64, 8, 0, false>", "field-form session, d = 512, closed form, |.|"),
+    ("../csrc_rank/vfm_elicit_field.hip", ["-ffp-contract=on"], "k_elicit_field<64, 8, 1, true>", "field-form session, d = 512, sampled, softplus"),
+    ("../csrc_rank/vfm_elicit_field.hip", ["-ffp-contract=on"], "k_elicit_ctx_prep", "field-form session: the score's operand pass (a wave per context)"),
 ]
 CLASSES = ["global_load_dwordx4", "global_load_dwordx2", "global_load_dword", "global_store_dwordx4", "global_store_dwordx2",
            "global_store_dword", "ds_read_b128", "ds_write_b128", "ds_read", "ds_write", "s_barrier", "v_pk_fma_f32", "v_pk_mul_f32",
@@ -37,7 +45,10 @@ CLASSES = ["global_load_dwordx4", "global_load_dwordx2", "global_load_dword", "g
 def main():
     hipcc = os.environ.get("HIPCC", "hipcc")
     cache = {}
+    only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else ""
     for tu, extra, inst, what in WANT:
+        if only not in tu and only not in inst:
+            continue
         if (tu, tuple(extra)) not in cache:
             out = tempfile.NamedTemporaryFile(suffix=".s", delete=False).name
             subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,

@@ -65,7 +65,10 @@ _UNITS = [("vfm_abi.hip", "", _EXACT), ("vfm_index.hip", "", []), ("vfm_variants
           # elicitation sessions (include/vfm_elicit.h): the fold-in's body (csrc_rank/vfm_foldin_body.hpp) and the pair
           # scores of vfm_rank_tile.hpp in one kernel.  The fold-in's flag: its body is defined under contraction `on`;
           # the pair functions pin `off` with a pragma of their own, so the scores stay those of vfm_rank.hip bit for bit
-          ("csrc_rank/vfm_elicit.hip", "", _EXACT)]
+          ("csrc_rank/vfm_elicit.hip", "", _EXACT),
+          # the field form of the sessions (any number of fields): the same body with the field-form scores of
+          # csrc_rank/vfm_field_ctx.hpp, which pin `off` themselves; a unit of its own so that the two compile side by side
+          ("csrc_rank/vfm_elicit_field.hip", "", _EXACT)]
 RANK_DIR = os.path.join(HERE, "csrc_rank")
 RANK_HDR = os.path.join(ROOT, "include", "vfm_rank.h")
 RANK_OPS = os.path.join(RANK_DIR, "vfm_rank_ops.cpp")

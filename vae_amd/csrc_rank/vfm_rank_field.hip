@@ -18,13 +18,15 @@
 // (vfm_rank_eval.hpp: vfm::launch_rank_eval, k_rank_eval of vfm_rank_eval.hip).
 //
 // Compiled with -ffp-contract=off: field_pair_moments' explicit fmaf chains are the MFMA chains of the tile, and the fp64
-// operand arithmetic (ctx_coord) rounds the same in k_field_ctx_prep and k_field_moments, bit for bit.
+// operand arithmetic (ctx_coord) rounds the same in k_field_ctx_prep and k_field_moments, bit for bit.  That arithmetic
+// lives in vfm_field_ctx.hpp, which the field-form elicitation session (vfm_elicit_field.hip) includes as well.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "vfm_rank.h"
 #include "vfm_rank_tile.hpp"
+#include "vfm_field_ctx.hpp"         // ctx_coord, ctx_op_var, ctx_consts, ctx_valid, cand_op_var, field_pair_moments
 #include "vfm_rank_scan.hpp"
 #include "vfm_rank_eval.hpp"
 
@@ -33,93 +35,13 @@ namespace {
 constexpr int WAVE = 64;
 constexpr int PREP_BLOCK = 256;       // k_field_ctx_prep: four queries per workgroup
 
-// Coordinate k of a context (the columns f != field of xr), in fp64, sums in column order.  With S the sum of the
-// context embeddings and P their pair term:  M = E S,  A = Var S,  C = 2 Cov(S, P) = 2 sum_q sigma_q^2 (M - mu_q),
-// ep = E P = ((sum mu)^2 - sum mu^2) / 2,  vp = Var P = sum_{q<r} sigma_q^2 sigma_r^2 + sum_q sigma_q^2 (M - mu_q)^2
-// (the context-only part of the variance of vfm_rank.h), the sums over q expanded so that one pass over the rows serves.
-struct CtxCoord {
-  double M, A, C, ep, vp;
-};
-
-template <typename ID>
-__device__ __forceinline__ CtxCoord ctx_coord(const ID* xr, int F, int field, int k, int d, bool sp,
-                                              const float* __restrict__ ent) {
-  double s1 = 0., smm = 0., ss = 0., sss = 0., ssm = 0., ssmm = 0.;
-  for (int f = 0; f < F; ++f) {
-    if (f == field) continue;
-    const float* row = ent + (int64_t)xr[f] * 2 * d;
-    const double m = row[k], s = link_of(row[d + k], sp), s2 = s * s;
-    s1 += m; smm += m * m; ss += s2; sss += s2 * s2; ssm += s2 * m; ssmm += s2 * (m * m);
-  }
-  CtxCoord c;
-  c.M = s1;
-  c.A = ss;
-  c.C = 2. * (s1 * ss - ssm);
-  c.ep = 0.5 * (s1 * s1 - smm);
-  c.vp = 0.5 * (ss * ss - sss) + ((s1 * s1) * ss - 2. * s1 * ssm + ssmm);
-  return c;
-}
-
-// The stored (fp32, rounded once) query operands of a coordinate: mean part [M], variance part [A | A + M^2 | C]
-__device__ __forceinline__ float ctx_op_var(const CtxCoord& c, int part) {
-  return part == 0 ? (float)c.A : part == 1 ? (float)(c.A + c.M * c.M) : (float)c.C;
-}
-
-// The context's constants before the coordinates are added: (m0 + sum_q mu_w,q, sigma0^2 + sum_q sigma_w,q^2)
-template <typename ID>
-__device__ __forceinline__ void ctx_consts(const ID* xr, int F, int field, bool sp, const float* __restrict__ bias,
-                                           const float* __restrict__ scal, double& cm, double& cv) {
-  const double sg0 = (double)link_of(scal[2], sp);
-  cm = (double)scal[1];
-  cv = sg0 * sg0;
-  for (int f = 0; f < F; ++f) {
-    if (f == field) continue;
-    const int64_t e = (int64_t)xr[f];
-    const double sw = (double)link_of(bias[e * 2 + 1], sp);
-    cm += (double)bias[e * 2];
-    cv += sw * sw;
-  }
-}
-
-template <typename ID>
-__device__ __forceinline__ bool ctx_valid(const ID* xr, int F, int field, int64_t T) {
-  bool ok = true;
-  for (int f = 0; f < F; ++f) ok = ok && (f == field || ((int64_t)xr[f] >= 0 && (int64_t)xr[f] < T));
-  return ok;
-}
-
-// The candidate's operands: mean part [mu], variance part [mu^2 | sigma^2 | mu]
-__device__ __forceinline__ float cand_op_var(const float* row, int kb, int d, bool sp) {
-  if (kb < d) return row[kb] * row[kb];
-  if (kb < 2 * d) {
-    const float s = link_of(row[kb], sp);        // (row[d + (kb - d)])
-    return s * s;
-  }
-  return row[kb - 2 * d];
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// field_pair_moments: the moments of (context, candidate) from the query's operands q (q.mean_op(k), q.var_op(kb)) and
-// the candidate's table rows: the same fp32 chains, in the same k order, as the MFMA accumulation of the tile, and the
-// tile's epilogue (accumulator + query constant) + candidate constant.
-// ---------------------------------------------------------------------------------------------------------------------
-template <typename QOP>
-__device__ void field_pair_moments(const QOP& q, const float* ec, const float* bc, float c_mean, float c_var, int d,
-                                   bool sp, float& mean, float& var) {
-  float am = 0.f, av = 0.f;
-  for (int k = 0; k < d; ++k) am = fmaf(op_mean(ec, k), q.mean_op(k), am);
-  for (int kb = 0; kb < 3 * d; ++kb) av = fmaf(cand_op_var(ec, kb, d, sp), q.var_op(kb), av);
-  const float sw = link_of(bc[1], sp);
-  mean = (am + c_mean) + bc[0];
-  var = (av + c_var) + sw * sw;
-}
-
 // A query's operands read from its packed row (the ranking's workspace)
 struct StoredOp {
   const float* row;
   int KA;
   __device__ float mean_op(int k) const { return row[k]; }
-  __device__ float var_op(int kb) const { return row[KA + kb]; }
+  int d;
+  __device__ float var_op(int part, int k) const { return row[KA + part * d + k]; }
 };
 
 // A query's operands formed on the fly from the tables (k_field_moments: no workspace)
@@ -130,10 +52,7 @@ struct TableOp {
   bool sp;
   const float* ent;
   __device__ float mean_op(int k) const { return (float)ctx_coord(xr, F, field, k, d, sp, ent).M; }
-  __device__ float var_op(int kb) const {
-    const int part = kb / d;
-    return ctx_op_var(ctx_coord(xr, F, field, kb - part * d, d, sp, ent), part);
-  }
+  __device__ float var_op(int part, int k) const { return ctx_op_var(ctx_coord(xr, F, field, k, d, sp, ent), part); }
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -264,7 +183,7 @@ struct FieldMoments {
   const float *ent, *bias;
   __device__ void operator()(int64_t u, int64_t iid, float& m, float& v) const {
     if (iid >= 0 && iid < T)
-      field_pair_moments(StoredOp{uop + u * Kp, KA}, ent + iid * 2 * d, bias + iid * 2, ucon[u * 2], ucon[u * 2 + 1], d,
+      field_pair_moments(StoredOp{uop + u * Kp, KA, d}, ent + iid * 2 * d, bias + iid * 2, ucon[u * 2], ucon[u * 2 + 1], d,
                          sp, m, v);
   }
 };
@@ -296,7 +215,7 @@ __global__ __launch_bounds__(POS_BLOCK) void k_field_pos_score(int64_t Q, int64_
       sc = philox_uniform(seed, keys[q], iid);
     } else {
       float m, v;
-      field_pair_moments(StoredOp{uop + q * Kp, KA}, ent + iid * 2 * d, bias + iid * 2, ucon[q * 2], ucon[q * 2 + 1], d,
+      field_pair_moments(StoredOp{uop + q * Kp, KA, d}, ent + iid * 2 * d, bias + iid * 2, ucon[q * 2], ucon[q * 2 + 1], d,
                          sp, m, v);
       sc = score_of(strat, m, v);
     }

@@ -6,7 +6,8 @@ refitted.  `VFM.select_next_questions` and `VFM.fold_in` are the two halves; thi
 users inside one kernel ("Elicitation sessions").  It checks the arguments, builds the per-user lists of
 the pool and of the history once (stable sorts: the caller's order is kept within a user) and maps the results back to
 the caller's pool order; the sessions themselves are one HIP launch (plus one operand pass for the closed form)
-through torch.ops.vfm_hip.elicit.
+through torch.ops.vfm_hip.elicit.  `run_field` is the same for the entities of any one column of a model with any
+number of fields (vfm_elicit_field_f32): full rows, one operand per distinct context.
 """
 from __future__ import annotations
 
@@ -47,20 +48,20 @@ def check_args(model, pool, y_pool, n_questions, strategy, history, n_steps, lr,
     return x, y, hx, hy, objective, code
 
 
-def pool_lists(pool):
-    """Stable sort of the pool rows by user: (order [P] -- position in the sorted pool -> caller's row index --,
-    users [U] ascending, ptr [U + 1])."""
-    order = torch.sort(pool[:, 0], stable=True).indices
-    users, counts = torch.unique_consecutive(pool[order, 0], return_counts=True)
+def pool_lists(pool, col=0):
+    """Stable sort of the pool rows by user (column `col`): (order [P] -- position in the sorted pool -> caller's row
+    index --, users [U] ascending, ptr [U + 1])."""
+    order = torch.sort(pool[:, col], stable=True).indices
+    users, counts = torch.unique_consecutive(pool[order, col], return_counts=True)
     ptr = torch.zeros(users.numel() + 1, dtype=torch.int64, device=pool.device)
     torch.cumsum(counts, 0, out=ptr[1:])
     return order, users.contiguous(), ptr
 
 
-def history_lists(users, hx):
+def history_lists(users, hx, col=0):
     """The history rows grouped by the session users (stable: given order kept per user): (order [H], ptr [U + 1])."""
-    order = torch.sort(hx[:, 0], stable=True).indices
-    pos = torch.searchsorted(users, hx[order, 0].contiguous())
+    order = torch.sort(hx[:, col], stable=True).indices
+    pos = torch.searchsorted(users, hx[order, col].contiguous())
     counts = torch.bincount(pos, minlength=users.numel())
     ptr = torch.zeros(users.numel() + 1, dtype=torch.int64, device=hx.device)
     torch.cumsum(counts, 0, out=ptr[1:])
@@ -135,6 +136,88 @@ def run(model, pool, y_pool, n_questions, strategy="variance", history=None, n_s
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the field form: respondents are the entities of one column of a model with any number of fields
+# ---------------------------------------------------------------------------------------------------------------------
+def check_args_field(model, pool, y_pool, n_questions, field, strategy, history, n_steps, lr, objective, n_samples,
+                     kl_weight, key_field):
+    """Validate a field-form session call (no GPU needed).  Returns (pool [P, F] int64, y_pool [P] fp32, hist_x [H, F] or
+    None, hist_y [H] or None, objective name, strategy code, field, key column) on the model's device."""
+    from .rank import _context_rows, _field_arg, _key_field
+    field = _field_arg(model, field)
+    kf = _key_field(model, field, key_field)
+    code = strategy_code(strategy)
+    if strategy == "mean" and model.output != "class":
+        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
+    if isinstance(n_questions, bool) or not isinstance(n_questions, int) or not 0 <= n_questions <= MAX_ROUNDS:
+        raise ValueError(f"n_questions must be an int in [0, {MAX_ROUNDS}]")
+    x = _context_rows(model, pool, "pool", field, check_field_column=True)
+    x, y, objective = foldin.check_args(model, x, y_pool, field, objective, n_samples, n_steps, lr, kl_weight)
+    hx = hy = None
+    if history is not None:
+        if not isinstance(history, (tuple, list)) or len(history) != 2:
+            raise ValueError(f"history must be a pair (X [H, {model.F}], y [H])")
+        hx = _context_rows(model, history[0], "history X", field, check_field_column=True)
+        hx, hy, _ = foldin.check_args(model, hx, history[1], field, objective, n_samples, n_steps, lr, kl_weight)
+        if hx.shape[0] and not bool(torch.isin(hx[:, field], x[:, field]).all()):
+            raise ValueError("history holds respondents without a pool row")
+    return x, y, hx, hy, objective, code, field, kf
+
+
+def run_field(model, pool, y_pool, n_questions, field=0, strategy="variance", history=None, n_steps=200, lr=0.05,
+              objective=None, n_samples=1, seed=0, kl_weight=1.0, reset=False, write=False, return_moments=False,
+              return_theta=False, key_field=None, t0=0, lds_rows=-1):
+    """The sessions of every entity of column `field` of the pool (VFM.elicit_field documents the arguments and the
+    result): the lists of `run` over column `field`, one operand per distinct context of pool and history together, and
+    one call of torch.ops.vfm_hip.elicit_field."""
+    x, y, hx, hy, objective, code, field, kf = check_args_field(model, pool, y_pool, n_questions, field, strategy,
+                                                                history, n_steps, lr, objective, n_samples, kl_weight,
+                                                                key_field)
+    ops._need_cuda(model._flat, "the model's parameters")
+    dev, d, Q = model.device, model.d, int(n_questions)
+    order, ents, ptr = pool_lists(x, field)
+    px, ys = x[order].contiguous(), y[order].contiguous()
+    U, P = ents.numel(), px.shape[0]
+    hptr = hxs = hys = hist_op = None
+    if hx is not None and hx.shape[0]:
+        horder, hptr = history_lists(ents, hx, field)
+        hxs, hys = hx[horder].contiguous(), hy[horder].contiguous()
+    f32 = dict(dtype=torch.float32, device=dev)
+    out_row = torch.full((U, Q), -1, dtype=torch.int64, device=dev)
+    score, loss = torch.full((U, Q), float("nan"), **f32), torch.full((U, Q), float("nan"), **f32)
+    theta = torch.empty(U, Q, 2 * d + 2, **f32) if return_theta else None
+    mean = torch.empty(Q + 1, P, **f32) if return_moments else None
+    var = torch.empty(Q + 1, P, **f32) if return_moments else None
+    res = {"entities": ents}
+    if U:
+        o = _lib.ops()
+        obj = foldin.OBJECTIVES[objective]
+        ctx = (px if hxs is None else torch.cat([px, hxs])).clone()     # one operand per DISTINCT context: it is frozen
+        ctx[:, field] = 0
+        op_x, inv = torch.unique(ctx, dim=0, return_inverse=True)
+        inv = inv.reshape(-1)
+        op_x, pool_op = op_x.contiguous(), inv[:P].contiguous()
+        if hxs is not None:
+            hist_op = inv[P:].contiguous()
+        ws = torch.empty(max(o.elicit_field_workspace_bytes(P, op_x.shape[0], d, obj), 1), dtype=torch.uint8, device=dev)
+        model._fresh_params()
+        ent, bia, scal = model._views(model._flat)
+        lik = _lib.LIK_NORMAL if model.output == "reg" else _lib.LIK_BERNOULLI
+        o.elicit_field(ents, ptr, px, ys, hptr, hxs, hys, op_x, pool_op, hist_op, ent, bia, scal, ws, out_row, score,
+                       loss, theta, mean, var, field, kf, Q, code, obj, lik,
+                       ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, int(n_steps), int(n_samples),
+                       int(bool(reset)), int(bool(write)), int(lds_rows), float(lr), float(kl_weight), _seed64(seed),
+                       int(t0))
+        if write:
+            model.params_changed()      # (rows written outside the step kernels: derived caches are stale)
+    res.update(rows=rows_to_caller(out_row, order), score=score, loss=loss)
+    if return_theta:
+        res["theta"] = theta
+    if return_moments:
+        res["logit_mean"], res["logit_var"] = to_caller_order(mean, order), to_caller_order(var, order)
+    return res
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # the curve of quality against questions asked (torch; any device)
 # ---------------------------------------------------------------------------------------------------------------------
 def asked_round(rows, P):
@@ -172,9 +255,11 @@ def metric(output, mean, var, y):
     return auc(torch.sigmoid(mean / torch.sqrt(1.0 + math.pi / 8.0 * var)), y)
 
 
-def curve(model, pool, y_pool, n_questions, strategies=("mean", "random", "variance"), **kw):
+def curve(model, pool, y_pool, n_questions, strategies=("mean", "random", "variance"), session=None, **kw):
     """VFM.elicitation_curve: {strategy: [metric before round 0, .., metric after round Q - 1]} on the rows still
-    unasked, plus "n_unasked": {strategy: [Q + 1] ints}.  The model is left untouched."""
+    unasked, plus "n_unasked": {strategy: [Q + 1] ints}.  The model is left untouched.  session: the runner (`run`, or
+    `run_field` for the field form)."""
+    session = run if session is None else session
     for key in ("write", "return_moments", "return_theta"):
         if key in kw:
             raise ValueError(f"elicitation_curve sets {key} itself")
@@ -183,7 +268,7 @@ def curve(model, pool, y_pool, n_questions, strategies=("mean", "random", "varia
         strategy_code(s)
     out, left = {}, {}
     for s in strategies:
-        r = run(model, pool, y_pool, n_questions, strategy=s, write=False, return_moments=True, **kw)
+        r = session(model, pool, y_pool, n_questions, strategy=s, write=False, return_moments=True, **kw)
         y = torch.as_tensor(y_pool).to(model.device, torch.float32).reshape(-1)
         when = asked_round(r["rows"], y.numel())
         out[s], left[s] = [], []

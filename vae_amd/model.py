@@ -1239,6 +1239,47 @@ class VFM(nn.Module):
         return elicit.curve(self, pool, y_pool, n_questions, strategies, **kw)
 
     @torch.no_grad()
+    def select_next_questions_field(self, pool, field: int, n: int = 1, strategy: str = "variance", seed: int = 0,
+                                    key_field: Optional[int] = None):
+        """select_next_questions for models with any number of fields (>= 2): pool [P, F] full rows, grouped by the
+        entities of column `field`; per entity the indices of its n best rows under `strategy`, scored by field_moments
+        (field, strategy, seed, key_field as there).  Ties go to the lower row.  Returns (entities [U'] ascending,
+        rows [U', n] int64, -1 padded)."""
+        return rank.select_next_questions_field(self, pool, field, n, strategy, seed, key_field)
+
+    @torch.no_grad()
+    def elicit_field(self, pool, y_pool, n_questions: int, field: int = 0, strategy: str = "variance", history=None,
+                     n_steps: int = 200, lr: float = 0.05, objective: Optional[str] = None, n_samples: int = 1,
+                     seed: int = 0, kl_weight: float = 1.0, reset: bool = False, write: bool = False,
+                     return_moments: bool = False, return_theta: bool = False, key_field: Optional[int] = None):
+        """elicit in the field form, any number of fields (>= 2): an adaptive questionnaire for every entity of column
+        `field` of the pool (the respondents) in one launch (include/vfm_elicit.h: vfm_elicit_field_f32):
+        n_questions rounds of select_next_questions_field(n=1) followed by fold_in(field=field) of the answering
+        respondent, bitwise what that loop computes.
+
+        pool: [P, F] full rows in any order -- column `field` the respondent, the other columns the question's context,
+        frozen (a context column holding ids of the respondents' range raises) --, y_pool [P] the answer each question
+        would receive; history: (X [H, F], y [H]) answers already given (respondents of the pool only).  Per respondent
+        and round q: every row not asked yet is scored from the respondent's CURRENT posterior (field_moments' score
+        with seed + q; "random" keyed on the id in column key_field, default the lowest context column, so rows that
+        share that id tie), the best is asked (ties: the lower pool row) and the posterior is refitted on the history followed by the rows asked so
+        far.  strategy, n_steps, lr, objective, n_samples, kl_weight, reset, write, return_moments, return_theta: as
+        elicit.  Returns elicit's dict with "entities" [U] ascending in place of "users"; rows index the caller's pool;
+        logit_mean / logit_var are bitwise field_moments of the pool under that round's posteriors."""
+        from . import elicit
+        return elicit.run_field(self, pool, y_pool, n_questions, field, strategy, history, n_steps, lr, objective,
+                                n_samples, seed, kl_weight, reset, write, return_moments, return_theta, key_field)
+
+    @torch.no_grad()
+    def elicitation_curve_field(self, pool, y_pool, n_questions: int, field: int = 0,
+                                strategies=("mean", "random", "variance"), **kw):
+        """elicitation_curve on the field form: for each strategy one elicit_field(write=False) session and the metric
+        on the pool rows still unasked before each round.  kw: elicit_field's other options.  Returns {strategy:
+        [Q + 1 floats], "n_unasked": {strategy: [Q + 1 ints]}}.  The model is left untouched."""
+        from . import elicit
+        return elicit.curve(self, pool, y_pool, n_questions, strategies, session=elicit.run_field, field=field, **kw)
+
+    @torch.no_grad()
     def evaluate(self, X_test, y_test):
         """Test metrics of vfm-torch.py:410-422."""
         out = self.predict(X_test)

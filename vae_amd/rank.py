@@ -242,6 +242,36 @@ def field_moments(model, X, field, strategy: Optional[str] = None, seed: int = 0
     return m, v, sc
 
 
+def select_next_questions_field(model, pool, field, n: int = 1, strategy: str = "variance", seed: int = 0, key_field=None):
+    """select_next_questions in the field form: per entity of column `field` of the pool [P, F] of full rows, the indices
+    of its n best rows under `strategy` (the score of field_moments for this field, seed and key_field).  Ties go to the
+    lower row index.  Returns (entities [U'] ascending, rows [U', n] int64, -1 where an entity has fewer than n rows)."""
+    field = _field_arg(model, field)
+    _key_field(model, field, key_field)
+    strategy_code(strategy)
+    if strategy == "mean" and model.output != "class":
+        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
+    if isinstance(n, bool) or int(n) < 1:
+        raise ValueError("n must be >= 1")
+    n = int(n)
+    pool = _context_rows(model, pool, "pool", field, check_field_column=True).contiguous()
+    dev = model.device
+    _, _, score = field_moments(model, pool, field, strategy, seed, key_field)
+    score = torch.nan_to_num(score, nan=-float("inf"))
+    o1 = torch.sort(score, descending=True, stable=True).indices            # best first; ties: lower row first
+    o2 = torch.sort(pool[o1, field], stable=True).indices                    # grouped by entity, order kept
+    order = o1[o2]
+    pe = pool[order, field]
+    ents, counts = torch.unique_consecutive(pe, return_counts=True)
+    start = torch.cumsum(counts, 0) - counts
+    grp = torch.repeat_interleave(torch.arange(ents.numel(), device=dev), counts)
+    rank = torch.arange(pe.numel(), device=dev) - start[grp]
+    keep = rank < n
+    rows = torch.full((ents.numel(), n), -1, dtype=torch.int64, device=dev)
+    rows[grp[keep], rank[keep]] = order[keep]
+    return ents, rows
+
+
 def rank_field(model, contexts, field, k: int = 10, strategy: str = "top", candidates=None, exclude=None,
                match_fields=None, key_field=None, seed: int = 0, n_splits: int = 0):
     """The k best entities of `field` for each context row (model.rank_field documents the arguments)."""
