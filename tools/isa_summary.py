@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Instruction-class counts of named kernel instances from the gfx950 ISA hipcc emits (`--offload-device-only -S`):
 the evidence behind "hand-written CDNA4, no scratch, counted waits" without asking the reader to recompile.
-usage: tools/isa_summary.py [--only SUBSTRING] > profiles/rNN_isa_summary.txt       (cross-compiles; no GPU needed;
-~3 minutes; --only keeps the entries whose translation unit or instance name holds SUBSTRING)"""
+usage: tools/isa_summary.py [--only SUBSTRING] [--every SUBSTRING] > profiles/rNN_isa_summary.txt   (cross-compiles; no GPU
+needed; ~3 minutes; --only keeps the entries whose translation unit or instance name holds SUBSTRING; --every adds one line
+(registers, scratch, LDS, waves per SIMD) for EVERY kernel instance of the listed units whose path holds SUBSTRING)"""
 import collections
 import os
 import re
@@ -35,6 +36,14 @@ WANT = [
     ("../csrc_rank/vfm_elicit_field.hip", ["-ffp-contract=on"], "k_elicit_field<64, 8, 0, false>", "field-form session, d = 512, closed form, |.|"),
     ("../csrc_rank/vfm_elicit_field.hip", ["-ffp-contract=on"], "k_elicit_field<64, 8, 1, true>", "field-form session, d = 512, sampled, softplus"),
     ("../csrc_rank/vfm_elicit_field.hip", ["-ffp-contract=on"], "k_elicit_ctx_prep", "field-form session: the score's operand pass (a wave per context)"),
+    # fused Adam step of the ELBO variants (--only variant_step prints these alone; --every variant_step adds one line per instance)
+    ("../csrc_var/vfm_variant_step.hip", ["-ffp-contract=on"], "k_vstep<8, 16, 1, true, false, true>", "variant step, d = 128 (the benchmark shape), closed form, learnable priors"),
+    ("../csrc_var/vfm_variant_step.hip", ["-ffp-contract=on"], "k_vstep<8, 16, 1, false, true, false>", "variant step, d = 128, sampled objective, feature values, N(0,1) priors"),
+    ("../csrc_var/vfm_variant_step.hip", ["-ffp-contract=on"], "k_vstep<8, 64, 2, true, true, true>", "variant step, d = 1024 (two blocks of 8 per lane), closed form, values, priors"),
+    ("../csrc_var/vfm_variant_step.hip", ["-ffp-contract=on"], "k_vstep<1, 4, 1, true, false, true>", "variant step, d = 2 (VFMClosedForm's default: one coordinate per lane), closed form, priors"),
+    ("../csrc_var/vfm_variant_step.hip", ["-ffp-contract=on"], "k_vstep<1, 64, 16, true, true, true>", "variant step, d % 8 != 0 up to 1024 (sixteen coordinates per lane), closed form, values, priors"),
+    ("../csrc_var/vfm_variant_step.hip", ["-ffp-contract=on"], "k_vstep_small", "variant step: partial rows of the prior gradients summed in order + Adam on priors and scalars"),
+    ("../csrc_var/vfm_variant_step.hip", ["-ffp-contract=on"], "k_vstep_positions", "variant step: positions of the occurrences (with feature values)"),
 ]
 CLASSES = ["global_load_dwordx4", "global_load_dwordx2", "global_load_dword", "global_store_dwordx4", "global_store_dwordx2",
            "global_store_dword", "ds_read_b128", "ds_write_b128", "ds_read", "ds_write", "s_barrier", "v_pk_fma_f32", "v_pk_mul_f32",
@@ -85,6 +94,22 @@ def main():
         print("  s_waitcnt vmcnt:", ", ".join(f"{k.split('vmcnt')[1].split()[0]}x{v}" for k, v in sorted(vm.items())),
               "  (vmcnt(0) = wait for every load in flight)")
         print()
+    every = sys.argv[sys.argv.index("--every") + 1] if "--every" in sys.argv else None
+    if every:
+        for (tu, extra), (txt, names) in cache.items():
+            if every not in tu:
+                continue
+            print(f"## every kernel instance of {tu}: vgprs / scratch bytes per lane / LDS bytes / waves per SIMD")
+            worst = 0
+            for d, label in sorted(names.items()):
+                body = txt[txt.index("\n" + label + ":"):]
+                meta = body[body.index(".Lfunc_end"):][:6000]
+                g = lambda k: (re.search(r"; " + k + r": (\d+)", meta) or [None, "?"])[1]
+                if g("NumVgprs") == "?":
+                    continue                          # (a device function, not a kernel)
+                worst = max(worst, int(g("ScratchSize")))
+                print(f"  {d.split('(')[0]:<62} {g('NumVgprs'):>4} {g('ScratchSize'):>4} {g('LDSByteSize'):>6} {g('Occupancy'):>3}")
+            print(f"largest scratch of any instance: {worst} bytes\n")
 
 
 if __name__ == "__main__":

@@ -71,6 +71,10 @@ ELICIT_EXPORTS = ("vfm_elicit_f32", "vfm_elicit_workspace_bytes", "vfm_elicit_fi
                   "vfm_elicit_field_workspace_bytes")
 
 
+# ---- fused Adam step of the ELBO variants (include/vfm_variant_step.h)
+VARIANT_STEP_EXPORTS = ("vfm_variant_step_f32", "vfm_variant_step_workspace_bytes")
+
+
 class Elicit(_Strict, C.Structure):
     """`vfm_elicit_t` (tests/test_elicit_cpu.py checks the layout against gcc's)."""
     _fields_ = [
@@ -198,6 +202,13 @@ def load():
     lib.vfm_elicit_field_f32.restype = C.c_int
     lib.vfm_elicit_field_workspace_bytes.argtypes = [i64, i64, i32, i32]
     lib.vfm_elicit_field_workspace_bytes.restype = i64
+    # problem, objective, index, workspace, x, values | entity, bias, inv_occ, scalars, W, priors | eps x3 | state, grow,
+    # partials, grad_out | m / v of entity, bias, scalars, priors | lr, beta1, beta2, eps, adam_step, stream
+    lib.vfm_variant_step_f32.argtypes = ([PP, i32, C.POINTER(Index)] + [vp] * 24 +
+                                         [C.c_float, C.c_float, C.c_float, C.c_float, i64, vp])
+    lib.vfm_variant_step_f32.restype = C.c_int
+    lib.vfm_variant_step_workspace_bytes.argtypes = [i64, i32, i32]
+    lib.vfm_variant_step_workspace_bytes.restype = i64
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name != "vfm_last_error":

@@ -68,7 +68,10 @@ _UNITS = [("vfm_abi.hip", "", _EXACT), ("vfm_index.hip", "", []), ("vfm_variants
           ("csrc_rank/vfm_elicit.hip", "", _EXACT),
           # the field form of the sessions (any number of fields): the same body with the field-form scores of
           # csrc_rank/vfm_field_ctx.hpp, which pin `off` themselves; a unit of its own so that the two compile side by side
-          ("csrc_rank/vfm_elicit_field.hip", "", _EXACT)]
+          ("csrc_rank/vfm_elicit_field.hip", "", _EXACT),
+          # fused Adam step of the ELBO variants (include/vfm_variant_step.h): outside csrc/ for the same reason.  It
+          # restates the backward of vfm_variants.hip and holds update arithmetic, hence the flag of the Adam units
+          ("csrc_var/vfm_variant_step.hip", "", _EXACT)]
 RANK_DIR = os.path.join(HERE, "csrc_rank")
 RANK_HDR = os.path.join(ROOT, "include", "vfm_rank.h")
 RANK_OPS = os.path.join(RANK_DIR, "vfm_rank_ops.cpp")
@@ -76,6 +79,8 @@ FOLDIN_HDR = os.path.join(ROOT, "include", "vfm_foldin.h")
 FOLDIN_OPS = os.path.join(RANK_DIR, "vfm_foldin_ops.cpp")
 ELICIT_HDR = os.path.join(ROOT, "include", "vfm_elicit.h")
 ELICIT_OPS = os.path.join(RANK_DIR, "vfm_elicit_ops.cpp")
+VAR_DIR = os.path.join(HERE, "csrc_var")
+VAR_STEP_HDR = os.path.join(ROOT, "include", "vfm_variant_step.h")
 
 
 def _unit_path(src):
@@ -88,7 +93,9 @@ def _unit_obj(objdir, src, suffix):
 
 
 def _rank_sources():
-    return [RANK_HDR, FOLDIN_HDR, ELICIT_HDR] + sorted(os.path.join(RANK_DIR, f) for f in os.listdir(RANK_DIR) if f.endswith((".hip", ".hpp")))
+    return ([RANK_HDR, FOLDIN_HDR, ELICIT_HDR, VAR_STEP_HDR] +
+            sorted(os.path.join(RANK_DIR, f) for f in os.listdir(RANK_DIR) if f.endswith((".hip", ".hpp"))) +
+            sorted(os.path.join(VAR_DIR, f) for f in os.listdir(VAR_DIR) if f.endswith((".hip", ".hpp"))))
 
 
 def build_hip_library(force=False, verbose=False):
@@ -105,7 +112,7 @@ def build_hip_library(force=False, verbose=False):
     common = [HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-fvisibility-inlines-hidden",
               "-I" + os.path.join(ROOT, "include"), "-I" + csrc]
     jobs, objs = [], []
-    shared = [hdr, RANK_HDR, FOLDIN_HDR, ELICIT_HDR, os.path.abspath(__file__)] + [f for f in parts if f.endswith(".hpp")]      # what every unit depends on
+    shared = [hdr, RANK_HDR, FOLDIN_HDR, ELICIT_HDR, VAR_STEP_HDR, os.path.abspath(__file__)] + [f for f in parts if f.endswith(".hpp")]      # what every unit depends on
     for src, suffix, extra in _UNITS:
         obj = _unit_obj(objdir, src, suffix)
         objs.append(obj)
