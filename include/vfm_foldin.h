@@ -84,6 +84,62 @@ int64_t vfm_foldin_workspace_bytes(int64_t n_ops, int32_t d, int32_t objective);
  * id outside [0, T) makes its rows' entities NaN. */
 int vfm_foldin_f32(const vfm_foldin_t* p, void* stream);
 
+/*
+ * Exact fold-in (closed form only): the optimum of L_e itself, in one launch, no iterations.
+ *
+ * With everything else frozen the closed-form L_e is quadratic in the means theta = (mu_w, mu) and separable and convex
+ * in each scale, so its one global optimum has a closed form.  With u_r = (1, M_r), t_r = y_r - c_mean,r,
+ * prec = link(alpha), kl = kl_weight > 0 and n the rows of e (duplicates counted):
+ *   H theta = b,  H = prec (sum_r u_r u_r^T + diag(0, sum_r A_r)) + kl I,  b = prec (sum_r t_r u_r - (0, 1/2 sum_r C_r))
+ *   sigma_w^2 = kl / (kl + prec n),   sigma_k^2 = kl / (kl + prec sum_r (A_rk + M_rk^2))
+ * stored as s = sigma under |.| and s = log(expm1(sigma)) under softplus.  H = D + prec U^T U (D diagonal, U [n, d + 1]):
+ * an entity with n <= d rows is solved in the dual n x n form (Woodbury),
+ *   theta = D^-1 b - D^-1 U^T (I / prec + U D^-1 U^T)^-1 U D^-1 b,
+ * one with more rows in the primal (d + 1) x (d + 1) form.  One workgroup per entity: fp64 row operands (the prep's sums
+ * before their rounding to fp32, links in fp64), sums in fp64 in row-list order, a
+ * packed Cholesky factor in LDS while the system fits, else in the workgroup's slab of the workspace.  No atomics, no
+ * host synchronisation, and the result does not depend on the entity's current row or on the other entities of the call.
+ * out_loss = L_e at the written fp32 parameters, with the arithmetic of vfm_foldin_f32's final pass.
+ */
+#define VFM_FOLDIN_SOLVE_LDS_DIM 135 /* the largest system kept in LDS (packed fp64 triangle: 73,440 bytes)          */
+#define VFM_FOLDIN_SOLVE_SLABS 256   /* workgroups of a launch that may need a workspace slab                        */
+
+typedef struct vfm_foldin_solve_t {
+  int64_t E;          /* folded entities                                                                         */
+  int64_t R;          /* rows, sorted (stably) by the folded id                                                  */
+  int64_t T;          /* table rows                                                                              */
+  int64_t n_ops;      /* distinct frozen-partner tuples (row operands)                                           */
+  int32_t F, d;       /* fields (1 .. VFM_MAX_FIELDS), embedding size (1 .. VFM_FOLDIN_MAX_D)                     */
+  int32_t col;        /* the folded column of op_x                                                               */
+  int32_t objective;  /* VFM_OBJ_CLOSED_FORM                                                                     */
+  int32_t likelihood; /* VFM_LIK_NORMAL                                                                          */
+  int32_t flags;      /* 0 or VFM_FLAG_LINK_SOFTPLUS                                                             */
+  int32_t lds_dim;    /* -1: systems stay in LDS while they fit; >= 0: larger ones go to the workspace (tests)  */
+  float kl_weight;    /* > 0                                                                                     */
+  const int64_t* entities; /* [E] folded ids, ascending                                                           */
+  const int64_t* row_ptr;  /* [E + 1] offsets of each entity's rows                                                */
+  const float* y;          /* [R]                                                                                 */
+  const int64_t* op_x;     /* [n_ops, F] one row of each partner tuple (the folded column is ignored)              */
+  const int64_t* row_op;   /* [R] operand of each row                                                             */
+  float* entity_params;    /* [T, 2d]: read; the rows of `entities` are written                                   */
+  float* bias_params;      /* [T, 2]                                                                              */
+  const float* scalars;    /* [3]                                                                                 */
+  float* out_loss;         /* [E] L_e                                                                             */
+  void* workspace;
+  int64_t workspace_bytes;
+} vfm_foldin_solve_t;
+
+/* Workspace of vfm_foldin_solve_f32 in bytes: the row operands (fp32 for the loss, as vfm_foldin_f32 keeps them, and
+ * unrounded fp64 for the solve), and min(E, VFM_FOLDIN_SOLVE_SLABS) slabs of a packed
+ * (d + 1) x (d + 1) fp64 triangle when such a system would not stay in LDS.  Negative on bad arguments. */
+int64_t vfm_foldin_solve_workspace_bytes(int64_t E, int64_t n_ops, int32_t d, int32_t lds_dim);
+
+/* Write the exact optimum of every entity of p.  An entity id outside [0, T) gets a NaN loss and is not written; a
+ * partner id outside [0, T) makes its rows' entities NaN.  VFM_E_INVALID (nothing launched) for an objective other than
+ * VFM_OBJ_CLOSED_FORM, a likelihood other than VFM_LIK_NORMAL, kl_weight <= 0, d > VFM_FOLDIN_MAX_D, a short or
+ * misaligned (256 bytes) workspace and the other range checks of vfm_foldin_f32. */
+int vfm_foldin_solve_f32(const vfm_foldin_solve_t* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

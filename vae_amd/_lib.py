@@ -75,6 +75,24 @@ ELICIT_EXPORTS = ("vfm_elicit_f32", "vfm_elicit_workspace_bytes", "vfm_elicit_fi
 VARIANT_STEP_EXPORTS = ("vfm_variant_step_f32", "vfm_variant_step_workspace_bytes")
 
 
+# ---- exact fold-in (include/vfm_foldin.h: vfm_foldin_solve_f32)
+FOLDIN_SOLVE_EXPORTS = ("vfm_foldin_solve_f32", "vfm_foldin_solve_workspace_bytes")
+FOLDIN_SOLVE_LDS_DIM = 135
+FOLDIN_SOLVE_SLABS = 256
+
+
+class FoldinSolve(_Strict, C.Structure):
+    """`vfm_foldin_solve_t` (tests/test_foldin_exact_cpu.py checks the layout against gcc's)."""
+    _fields_ = [
+        ("E", C.c_int64), ("R", C.c_int64), ("T", C.c_int64), ("n_ops", C.c_int64),
+        ("F", C.c_int32), ("d", C.c_int32), ("col", C.c_int32), ("objective", C.c_int32),
+        ("likelihood", C.c_int32), ("flags", C.c_int32), ("lds_dim", C.c_int32), ("kl_weight", C.c_float),
+        ("entities", C.c_void_p), ("row_ptr", C.c_void_p), ("y", C.c_void_p), ("op_x", C.c_void_p),
+        ("row_op", C.c_void_p), ("entity_params", C.c_void_p), ("bias_params", C.c_void_p), ("scalars", C.c_void_p),
+        ("out_loss", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+
 class Elicit(_Strict, C.Structure):
     """`vfm_elicit_t` (tests/test_elicit_cpu.py checks the layout against gcc's)."""
     _fields_ = [
@@ -124,7 +142,7 @@ class ElicitField(_Strict, C.Structure):
         self.struct_size, self.abi_version = C.sizeof(type(self)), ABI_VERSION      # (VFM_STRUCT_INIT)
 
 
-for _c in (Problem, Index, Pipe, Elicit, ElicitField):
+for _c in (Problem, Index, Pipe, Elicit, ElicitField, FoldinSolve):
     _c._names = frozenset(n for n, _ in _c._fields_)
 
 
@@ -202,6 +220,10 @@ def load():
     lib.vfm_elicit_field_f32.restype = C.c_int
     lib.vfm_elicit_field_workspace_bytes.argtypes = [i64, i64, i32, i32]
     lib.vfm_elicit_field_workspace_bytes.restype = i64
+    lib.vfm_foldin_solve_f32.argtypes = [C.POINTER(FoldinSolve), vp]
+    lib.vfm_foldin_solve_f32.restype = C.c_int
+    lib.vfm_foldin_solve_workspace_bytes.argtypes = [i64, i64, i32, i32]
+    lib.vfm_foldin_solve_workspace_bytes.restype = i64
     # problem, objective, index, workspace, x, values | entity, bias, inv_occ, scalars, W, priors | eps x3 | state, grow,
     # partials, grad_out | m / v of entity, bias, scalars, priors | lr, beta1, beta2, eps, adam_step, stream
     lib.vfm_variant_step_f32.argtypes = ([PP, i32, C.POINTER(Index)] + [vp] * 24 +

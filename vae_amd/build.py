@@ -62,6 +62,9 @@ _UNITS = [("vfm_abi.hip", "", _EXACT), ("vfm_index.hip", "", []), ("vfm_variants
           # fold-in (include/vfm_foldin.h): outside csrc/ for the same reason; it includes csrc/'s Philox stream and link
           # helpers, so its draws and links are those of the training kernels
           ("csrc_rank/vfm_foldin.hip", "", _EXACT),
+          # exact fold-in (vfm_foldin_solve_f32): the same prep and, for the loss, the same final pass (vfm_foldin_body.hpp),
+          # hence the same flag
+          ("csrc_rank/vfm_foldin_solve.hip", "", _EXACT),
           # elicitation sessions (include/vfm_elicit.h): the fold-in's body (csrc_rank/vfm_foldin_body.hpp) and the pair
           # scores of vfm_rank_tile.hpp in one kernel.  The fold-in's flag: its body is defined under contraction `on`;
           # the pair functions pin `off` with a pragma of their own, so the scores stay those of vfm_rank.hip bit for bit

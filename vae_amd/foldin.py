@@ -126,3 +126,40 @@ def run(model, X, y, field=0, objective=None, n_samples=1, seed=0, kl_weight=1.0
     if mode == MODE_FIT:
         model.params_changed()          # (rows written outside the step kernels: derived caches are stale)
     return ents, loss, counts, grad
+
+
+def check_args_exact(model, X, y, field, kl_weight=1.0):
+    """Validate an exact fold-in call (no GPU needed): check_args, a 'reg' model and kl_weight > 0."""
+    if model.output != "reg":
+        raise ValueError("the exact fold-in needs a 'reg' model (Gaussian likelihood): the closed form it solves has "
+                         "none for 'class'; use fold_in")
+    if not float(kl_weight) > 0.0 or not math.isfinite(float(kl_weight)):
+        raise ValueError("kl_weight must be > 0 and finite: the prior term is what makes each system positive definite")
+    x, y, _ = check_args(model, X, y, field, "closed_form", 1, 0, 0.0, kl_weight)
+    return x, y
+
+
+def run_exact(model, X, y, field=0, kl_weight=1.0, lds_dim=-1):
+    """One exact fold-in launch (vfm_foldin_solve_f32): the closed-form optimum of every folded entity.  Returns
+    (entities [E], loss [E], rows [E])."""
+    x, y = check_args_exact(model, X, y, field, kl_weight)
+    if int(lds_dim) < -1:
+        raise ValueError("lds_dim must be -1 or >= 0")
+    ops._need_cuda(model._flat, "the model's parameters")
+    dev, d = model.device, model.d
+    xs, ys, ents, ptr, counts = row_lists(x, y, field)
+    E = ents.numel()
+    loss = torch.empty(E, dtype=torch.float32, device=dev)
+    if E == 0:
+        return ents, loss, counts
+    o = _lib.ops()
+    op_x, row_op = partner_tuples(xs, field)
+    ws = torch.empty(max(o.foldin_solve_workspace_bytes(E, op_x.shape[0], d, int(lds_dim)), 1), dtype=torch.uint8,
+                     device=dev)
+    model._fresh_params()
+    ent, bia, scal = model._views(model._flat)
+    o.foldin_solve(ents, ptr, ys, op_x, row_op, ent, bia, scal, ws, loss, int(field), OBJECTIVES["closed_form"],
+                   _lib.LIK_NORMAL, ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, int(lds_dim),
+                   float(kl_weight))
+    model.params_changed()              # (rows written outside the step kernels: derived caches are stale)
+    return ents, loss, counts

@@ -1189,6 +1189,23 @@ class VFM(nn.Module):
         return {"entities": ents, "loss": loss, "rows": rows}
 
     @torch.no_grad()
+    def fold_in_exact(self, X, y, field: int = 0, kl_weight: float = 1.0):
+        """fold_in's closed-form objective solved exactly: the entities of X[:, field] get the global optimum of L_e
+        itself, in one launch (include/vfm_foldin.h: vfm_foldin_solve_f32; DESIGN.md §4 "Exact fold-in").  No lr, no
+        n_steps, no reset: with everything else frozen L_e is quadratic in the means (one symmetric positive definite
+        solve per entity, n x n for an entity with n <= d rows, (d + 1) x (d + 1) otherwise) and has a closed form in
+        each scale, so the result does not depend on the rows' current values.
+
+        'reg' models only, kl_weight > 0 (else ValueError, as for everything fold_in rejects).  X, y, field, the row
+        order, what is written and what stays frozen are fold_in's: only the folded rows of entity_params /
+        bias_params change; the training Adam state and the save_weights snapshots are not touched.
+        Returns dict(entities [E] int64, loss [E] fp32 = L_e at the returned parameters, evaluated as fold_in evaluates
+        it, rows [E] int64)."""
+        from . import foldin
+        ents, loss, rows = foldin.run_exact(self, X, y, field, kl_weight)
+        return {"entities": ents, "loss": loss, "rows": rows}
+
+    @torch.no_grad()
     def fold_in_objective(self, X, y, field: int = 0, objective: Optional[str] = None, n_samples: int = 1,
                           seed: int = 0, step: int = 0, kl_weight: float = 1.0):
         """fold_in's objective L_e and its gradient at the current parameters, nothing updated (tests, diagnostics).
