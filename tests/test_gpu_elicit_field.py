@@ -112,6 +112,12 @@ CASES = [  # field sizes, field, output, objective, link, strategy, d, history, 
     (A3, 0, "class", "sampled", "softplus", "random", 300, True, True, 2, None),
     (C2, 0, "reg", "closed_form", "abs", "variance", 16, True, False, 1, None),
     (C2, 0, "class", "sampled", "softplus", "mean", 128, False, False, 1, None),
+    # d = 9 and 129: the smallest d of shapes (16, 1) and (64, 4), neither a multiple of W (lanes past d), at F = 3
+    # (appended, so that the ids of the cases above keep their index)
+    (A3, 0, "reg", "closed_form", "abs", "variance", 9, True, False, 1, None),
+    (A3, 0, "class", "sampled", "softplus", "mean", 9, True, True, 2, None),
+    (A3, 0, "reg", "closed_form", "abs", "top", 129, True, False, 1, None),
+    (A3, 0, "class", "sampled", "softplus", "variance", 129, True, False, 2, None),
 ]
 
 

@@ -4,7 +4,7 @@ both links, both objectives; ties through the butterfly; the documented guards t
 per-round fp64 check (no feedback between rounds) that covers the sampled objective, softplus, 'class' and history."""
 # k_elicit <W, CPL, LINK, SAMPLED>: 7 shapes x 2 links x {closed form, sampled} = 28 instances (vfm_elicit.hip).
 #   shape_of (vfm_foldin_body.hpp): W = 8 / 16 / 32 / 64 lanes for d <= 8 / 16 / 32 / above; CPL = ceil(d / W) rounded up
-#     to 1, 2, 4, 8.  launch_shape switches on W * 16 + CPL; its default case is <64, 8>.
+#     to 1, 2, 4, 8.  for_shape switches on W * 16 + CPL; its default case is <64, 8>.
 #   lds_cap (closed form; the sampled form stages nothing): FB = 256 threads, LDS_BYTES = 48 KiB = 12288 floats per
 #     block, GPB = 256 / W groups per block, DP = W * CPL; per group 12288 / GPB floats hold theta_u's copy (2 DP + 2)
 #     and cap rows of DP + 1:  cap = (12288 / GPB - (2 DP + 2)) / (DP + 1), rounded down.

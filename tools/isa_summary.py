@@ -36,6 +36,17 @@ WANT = [
     ("../csrc_rank/vfm_elicit_field.hip", ["-ffp-contract=on"], "k_elicit_field<64, 8, 0, false>", "field-form session, d = 512, closed form, |.|"),
     ("../csrc_rank/vfm_elicit_field.hip", ["-ffp-contract=on"], "k_elicit_field<64, 8, 1, true>", "field-form session, d = 512, sampled, softplus"),
     ("../csrc_rank/vfm_elicit_field.hip", ["-ffp-contract=on"], "k_elicit_ctx_prep", "field-form session: the score's operand pass (a wave per context)"),
+    # the two-field session and the fold-in at the same shapes: the three kernels restate one another and are compared instance by instance
+    ("../csrc_rank/vfm_elicit.hip", ["-ffp-contract=on"], "k_elicit<8, 1, 0, false>", "two-field session, d <= 8, closed form, |.|"),
+    ("../csrc_rank/vfm_elicit.hip", ["-ffp-contract=on"], "k_elicit<64, 2, 0, false>", "two-field session, d = 128, closed form, |.|"),
+    ("../csrc_rank/vfm_elicit.hip", ["-ffp-contract=on"], "k_elicit<64, 2, 1, true>", "two-field session, d = 128, sampled, softplus"),
+    ("../csrc_rank/vfm_elicit.hip", ["-ffp-contract=on"], "k_elicit<64, 8, 0, false>", "two-field session, d = 512, closed form, |.|"),
+    ("../csrc_rank/vfm_elicit.hip", ["-ffp-contract=on"], "k_elicit<64, 8, 1, true>", "two-field session, d = 512, sampled, softplus"),
+    ("../csrc_rank/vfm_foldin.hip", ["-ffp-contract=on"], "k_foldin<8, 1, 0, false>", "fold-in, d <= 8, closed form, |.|"),
+    ("../csrc_rank/vfm_foldin.hip", ["-ffp-contract=on"], "k_foldin<64, 2, 0, false>", "fold-in, d = 128, closed form, |.|"),
+    ("../csrc_rank/vfm_foldin.hip", ["-ffp-contract=on"], "k_foldin<64, 2, 1, true>", "fold-in, d = 128, sampled, softplus"),
+    ("../csrc_rank/vfm_foldin.hip", ["-ffp-contract=on"], "k_foldin<64, 8, 0, false>", "fold-in, d = 512, closed form, |.|"),
+    ("../csrc_rank/vfm_foldin.hip", ["-ffp-contract=on"], "k_foldin<64, 8, 1, true>", "fold-in, d = 512, sampled, softplus"),
     # fused Adam step of the ELBO variants (--only variant_step prints these alone; --every variant_step adds one line per instance)
     ("../csrc_var/vfm_variant_step.hip", ["-ffp-contract=on"], "k_vstep<8, 16, 1, true, false, true>", "variant step, d = 128 (the benchmark shape), closed form, learnable priors"),
     ("../csrc_var/vfm_variant_step.hip", ["-ffp-contract=on"], "k_vstep<8, 16, 1, false, true, false>", "variant step, d = 128, sampled objective, feature values, N(0,1) priors"),
@@ -108,7 +119,7 @@ def main():
                 if g("NumVgprs") == "?":
                     continue                          # (a device function, not a kernel)
                 worst = max(worst, int(g("ScratchSize")))
-                print(f"  {d.split('(')[0]:<62} {g('NumVgprs'):>4} {g('ScratchSize'):>4} {g('LDSByteSize'):>6} {g('Occupancy'):>3}")
+                print(f"  {d.replace('(anonymous namespace)::', '').split('(')[0]:<62} {g('NumVgprs'):>4} {g('ScratchSize'):>4} {g('LDSByteSize'):>6} {g('Occupancy'):>3}")
             print(f"largest scratch of any instance: {worst} bytes\n")
 
 

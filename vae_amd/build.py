@@ -60,14 +60,16 @@ _UNITS = [("vfm_abi.hip", "", _EXACT), ("vfm_index.hip", "", []), ("vfm_variants
           # field-form ranking (any number of fields): operands of its own for the same tiles and scan, the same flag
           ("csrc_rank/vfm_rank_field.hip", "", ["-ffp-contract=off"]),
           # fold-in (include/vfm_foldin.h): outside csrc/ for the same reason; it includes csrc/'s Philox stream and link
-          # helpers, so its draws and links are those of the training kernels
+          # helpers, so its draws and links are those of the training kernels.  csrc_rank/vfm_foldin_body.hpp holds the
+          # per-entity body and the host helpers (shape dispatch, FoldArgs fill, prep launch) of this unit and the next three
           ("csrc_rank/vfm_foldin.hip", "", _EXACT),
           # exact fold-in (vfm_foldin_solve_f32): the same prep and, for the loss, the same final pass (vfm_foldin_body.hpp),
           # hence the same flag
           ("csrc_rank/vfm_foldin_solve.hip", "", _EXACT),
           # elicitation sessions (include/vfm_elicit.h): the fold-in's body (csrc_rank/vfm_foldin_body.hpp) and the pair
-          # scores of vfm_rank_tile.hpp in one kernel.  The fold-in's flag: its body is defined under contraction `on`;
-          # the pair functions pin `off` with a pragma of their own, so the scores stay those of vfm_rank.hip bit for bit
+          # scores of vfm_rank_tile.hpp in one kernel; the host side it shares with the field form is
+          # csrc_rank/vfm_elicit_host.hpp.  The fold-in's flag: its body is defined under contraction `on`; the pair
+          # functions pin `off` with a pragma of their own, so the scores stay those of vfm_rank.hip bit for bit
           ("csrc_rank/vfm_elicit.hip", "", _EXACT),
           # the field form of the sessions (any number of fields): the same body with the field-form scores of
           # csrc_rank/vfm_field_ctx.hpp, which pin `off` themselves; a unit of its own so that the two compile side by side

@@ -20,6 +20,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "vfm_args.hpp"
 #include "vfm_elicit.h"
 #include "vfm_rank_tile.hpp"         // pair_moments, score_of, philox_uniform: the scores of k_moments, bit for bit
@@ -29,6 +31,7 @@ namespace {
 #include "vfm_rng.hpp"
 #include "vfm_common.hpp"
 #include "vfm_foldin_body.hpp"       // FoldArgs, k_foldin_prep, fold_stage_rows, fold_run: k_foldin's body
+#include "vfm_elicit_host.hpp"       // what the two session entry points share on the host
 
 struct ElicitArgs {
   FoldArgs f;                            // the fold-in's options, tables and operands (its row list is unused)
@@ -190,38 +193,6 @@ __global__ __launch_bounds__(FB) void k_elicit(const ElicitArgs a) {
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// host side
-// ---------------------------------------------------------------------------------------------------------------------
-// fold rows per user staged in LDS: what the block's stage leaves after every group's copy of theta_u
-int lds_cap(const FShape& s) {
-  const int DP = s.W * s.CPL, per_group = LDS_BYTES / 4 / (FB / s.W);
-  const int c = (per_group - (2 * DP + 2)) / (DP + 1);
-  return c < 0 ? 0 : c;
-}
-
-template <int W, int CPL, int LINK, bool SAMPLED>
-void launch(const ElicitArgs& a, hipStream_t st) {
-  constexpr int GPB = FB / W, DP = W * CPL;
-  const size_t shm = (size_t)GPB * ((size_t)a.f.cap * (DP + 1) + 2 * DP + 2) * 4;
-  hipLaunchKernelGGL((k_elicit<W, CPL, LINK, SAMPLED>), dim3((unsigned)((a.U + GPB - 1) / GPB)), dim3(FB), shm, st, a);
-}
-
-template <int LINK, bool SAMPLED>
-void launch_shape(const FShape& s, const ElicitArgs& a, hipStream_t st) {
-  switch (s.W * 16 + s.CPL) {
-    case 8 * 16 + 1: launch<8, 1, LINK, SAMPLED>(a, st); break;
-    case 16 * 16 + 1: launch<16, 1, LINK, SAMPLED>(a, st); break;
-    case 32 * 16 + 1: launch<32, 1, LINK, SAMPLED>(a, st); break;
-    case 64 * 16 + 1: launch<64, 1, LINK, SAMPLED>(a, st); break;
-    case 64 * 16 + 2: launch<64, 2, LINK, SAMPLED>(a, st); break;
-    case 64 * 16 + 4: launch<64, 4, LINK, SAMPLED>(a, st); break;
-    default: launch<64, 8, LINK, SAMPLED>(a, st); break;
-  }
-}
-
-int64_t flags_bytes(int64_t P) { return round_up(P > 0 ? P : 1, 256); }
-
 }  // namespace
 }  // namespace vfm
 
@@ -237,96 +208,41 @@ int64_t vfm_elicit_workspace_bytes(int64_t P, int64_t n_ops, int32_t d, int32_t 
 }
 
 int vfm_elicit_f32(const vfm_elicit_t* p, void* stream) {
-  using vfm::fail;
-  if (!p) return fail(VFM_E_INVALID, "vfm_elicit_f32: NULL argument struct");
-  if (p->struct_size != (uint32_t)sizeof(vfm_elicit_t) || p->abi_version != (uint32_t)VFM_ABI_VERSION)
-    return fail(VFM_E_INVALID, "vfm_elicit_t: struct_size / abi_version differ from this library's (VFM_STRUCT_INIT)");
-  if (p->T < 1) return fail(VFM_E_INVALID, "T < 1");
+  using namespace vfm;
+  if (int rc = check_session_struct(p, "vfm_elicit_f32: NULL argument struct",
+                                    "vfm_elicit_t: struct_size / abi_version differ from this library's (VFM_STRUCT_INIT)"))
+    return rc;
   if (p->F != 2) return fail(VFM_E_INVALID, "elicitation sessions: two-field models only (F must be 2)");
-  if (p->d < 1 || p->d > VFM_FOLDIN_MAX_D) return fail(VFM_E_INVALID, "d out of range [1,512]");
-  if (p->U < 0 || p->P < 0 || p->H < 0) return fail(VFM_E_INVALID, "U < 0, P < 0 or H < 0");
-  if (p->n_rounds < 0 || p->n_rounds > VFM_ELICIT_MAX_ROUNDS) return fail(VFM_E_INVALID, "n_rounds out of range [0,4096]");
-  if (p->strategy < VFM_RANK_TOP || p->strategy > VFM_RANK_RANDOM) return fail(VFM_E_INVALID, "unknown strategy");
-  if (p->likelihood != VFM_LIK_NORMAL && p->likelihood != VFM_LIK_BERNOULLI)
-    return fail(VFM_E_INVALID, "unknown likelihood");
-  if (p->objective == VFM_OBJ_CLOSED_FORM) {
-    if (p->likelihood != VFM_LIK_NORMAL) return fail(VFM_E_INVALID, "the closed form needs the Normal likelihood");
-    if (p->n_ops < 0 || (p->P + p->H > 0 && p->n_ops < 1)) return fail(VFM_E_INVALID, "n_ops out of range");
-  } else if (p->objective == VFM_OBJ_SAMPLED) {
-    if (p->n_samples < 1 || p->n_samples > VFM_FOLDIN_MAX_SAMPLES)
-      return fail(VFM_E_INVALID, "n_samples out of range [1,4]");
-  } else {
-    return fail(VFM_E_INVALID, "unknown objective");
-  }
-  if (p->flags & ~VFM_FLAG_LINK_SOFTPLUS) return fail(VFM_E_INVALID, "flags: only VFM_FLAG_LINK_SOFTPLUS is accepted");
-  if (p->n_steps < 0) return fail(VFM_E_INVALID, "n_steps must be >= 0");
-  if (p->t0 < 0 || p->t0 + (int64_t)(p->n_rounds + 1) * ((int64_t)p->n_steps + 1) >=
-                       ((int64_t)1 << 60) / VFM_FOLDIN_MAX_SAMPLES)
-    return fail(VFM_E_INVALID, "t0 out of range");
-  if (!(p->lr >= 0.f) || !(p->kl_weight >= 0.f)) return fail(VFM_E_INVALID, "lr and kl_weight must be >= 0");
-  if ((p->out_mean == nullptr) != (p->out_var == nullptr))
-    return fail(VFM_E_INVALID, "out_mean and out_var: both or neither");
+  if (int rc = check_session_options(p, false)) return rc;
   if (p->U == 0) return 0;
-  if (!p->users || !p->pool_ptr || !p->entity_params || !p->bias_params || !p->scalars ||
-      (p->P > 0 && (!p->pool_items || !p->pool_y)) || (p->H > 0 && (!p->hist_ptr || !p->hist_items || !p->hist_y)) ||
-      (p->n_rounds > 0 && (!p->out_row || !p->out_score || !p->out_loss)))
+  if (!p->users || (p->P > 0 && !p->pool_items) || (p->H > 0 && !p->hist_items) || session_pointers_missing(p))
     return fail(VFM_E_INVALID, "null pointer");
   const bool cf = p->objective == VFM_OBJ_CLOSED_FORM;
   const int64_t n_ops = cf ? p->n_ops : 0;
   if (cf && ((p->P + p->H > 0 && !p->op_x) || (p->P > 0 && !p->pool_op) || (p->H > 0 && !p->hist_op)))
     return fail(VFM_E_INVALID, "closed form: op_x, pool_op and hist_op needed");
-  const int64_t ws = vfm_elicit_workspace_bytes(p->P, n_ops, p->d, p->objective);
-  if (ws < 0 || p->workspace_bytes < ws || !p->workspace)
-    return fail(VFM_E_INVALID, "workspace too small (vfm_elicit_workspace_bytes)");
-  if (((uintptr_t)p->workspace) & 255) return fail(VFM_E_INVALID, "workspace must be 256-byte aligned");
+  if (int rc = check_session_workspace(p, vfm_elicit_workspace_bytes(p->P, n_ops, p->d, p->objective),
+                                       "workspace too small (vfm_elicit_workspace_bytes)"))
+    return rc;
 
   const hipStream_t st = (hipStream_t)stream;
   const bool sp = (p->flags & VFM_FLAG_LINK_SOFTPLUS) != 0;
-  const vfm::FShape s = vfm::shape_of(p->d);
-  const int DP = s.W * s.CPL;
-  vfm::ElicitArgs a;
-  vfm::FoldArgs& f = a.f;
-  f.E = p->U; f.R = 0; f.T = p->T;
-  f.F = 2; f.d = p->d; f.col = 0; f.lik = p->likelihood; f.S = cf ? 1 : p->n_samples;
-  f.n_steps = p->n_steps; f.reset = p->reset ? 1 : 0; f.mode = VFM_FOLDIN_FIT; f.cap = 0;
-  f.lr = p->lr; f.klw = p->kl_weight; f.t0 = p->t0;
-  f.key.seed_lo = (uint32_t)p->seed; f.key.seed_hi = (uint32_t)(p->seed >> 32);
-  f.key.step_lo = f.key.step_hi = 0; f.key.chunk_off = 0;
-  f.ent = nullptr; f.ptr = nullptr; f.x = nullptr; f.row_op = nullptr; f.y = nullptr;
-  f.ops = nullptr; f.opc = nullptr;
-  f.entity = p->entity_params; f.bias = p->bias_params; f.scal = p->scalars;
-  f.loss = nullptr; f.grad = nullptr;
-  a.U = p->U; a.P = p->P; a.H = p->H; a.Q = p->n_rounds; a.strat = p->strategy; a.write = p->write ? 1 : 0;
-  a.seed = p->seed;
-  a.users = p->users; a.pool_ptr = p->pool_ptr; a.pool_items = p->pool_items; a.pool_y = p->pool_y;
-  a.hist_ptr = p->H > 0 ? p->hist_ptr : nullptr; a.hist_items = p->hist_items; a.hist_y = p->hist_y;
-  a.pool_op = p->pool_op; a.hist_op = p->hist_op;
-  a.out_row = p->out_row; a.out_score = p->out_score; a.out_loss = p->out_loss; a.out_theta = p->out_theta;
-  a.out_mean = p->out_mean; a.out_var = p->out_var;
-  char* w = (char*)p->workspace;
-  a.asked = (uint8_t*)w;
+  const FShape sh = shape_of(p->d);
+  const auto theta_floats = [](int DP) { return 2 * DP + 2; };      // (the group's copy of theta_u: the table's layout)
+  ElicitArgs a = session_args<ElicitArgs>(p, 2, 0);
+  a.users = p->users; a.pool_items = p->pool_items; a.hist_items = p->hist_items;
+  FoldArgs& f = a.f;
   if (cf) {
-    float* ops = (float*)(w + vfm::flags_bytes(p->P));
-    float* opc = (float*)(w + vfm::flags_bytes(p->P) + vfm::ops_off_opc(n_ops, p->d));
+    char* w = (char*)p->workspace + flags_bytes(p->P);
+    float* ops = (float*)w;
+    float* opc = (float*)(w + ops_off_opc(n_ops, p->d));
     f.ops = ops; f.opc = opc;
-    const int cap = vfm::lds_cap(s);
-    f.cap = p->lds_rows < 0 ? cap : (p->lds_rows < cap ? p->lds_rows : cap);
-    if (n_ops > 0) {
-      const unsigned nb = (unsigned)((n_ops + vfm::FB - 1) / vfm::FB);
-      if (sp)
-        hipLaunchKernelGGL(vfm::k_foldin_prep<vfm::LINK_SOFTPLUS>, dim3(nb), dim3(vfm::FB), 0, st, n_ops, 2, p->d, DP, 0,
-                           p->T, p->op_x, p->entity_params, p->bias_params, p->scalars, ops, opc);
-      else
-        hipLaunchKernelGGL(vfm::k_foldin_prep<vfm::LINK_ABS>, dim3(nb), dim3(vfm::FB), 0, st, n_ops, 2, p->d, DP, 0,
-                           p->T, p->op_x, p->entity_params, p->bias_params, p->scalars, ops, opc);
-      if (int rc = launch_status("k_foldin_prep")) return rc;
-    }
-    if (sp) vfm::launch_shape<vfm::LINK_SOFTPLUS, false>(s, a, st);
-    else vfm::launch_shape<vfm::LINK_ABS, false>(s, a, st);
-  } else {
-    if (sp) vfm::launch_shape<vfm::LINK_SOFTPLUS, true>(s, a, st);
-    else vfm::launch_shape<vfm::LINK_ABS, true>(s, a, st);
+    f.cap = lds_cap(sh, theta_floats(sh.W * sh.CPL), p->lds_rows);
+    if (int rc = launch_foldin_prep(sp, f, n_ops, p->op_x, ops, opc, st)) return rc;
   }
+  launch_session(sh, sp, !cf, a, st, theta_floats, [](auto w, auto c, auto link, auto sampled) {
+    return k_elicit<decltype(w)::value, decltype(c)::value, decltype(link)::value, decltype(sampled)::value>;
+  });
   return launch_status("k_elicit");
 }
 

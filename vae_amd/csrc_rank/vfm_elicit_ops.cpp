@@ -8,6 +8,8 @@
 
 #include <string.h>
 
+#include <initializer_list>
+
 #include "vfm_elicit.h"
 
 namespace {
@@ -24,6 +26,66 @@ const Tensor& dev_tensor(const Tensor& t, at::ScalarType dt, const char* name) {
 
 bool given(const optional<Tensor>& t) { return t.has_value() && t->defined(); }
 
+// The checks both ops make first, in their old order: every required tensor (the op names its own: rows, operands),
+// the table shapes, n_rounds.
+struct Named {
+  const Tensor& t;
+  at::ScalarType dt;
+  const char* name;
+};
+
+void check_session_tensors(std::initializer_list<Named> own, const Tensor& entity, const Tensor& bias,
+                           const Tensor& scalars, const Tensor& workspace, const Tensor& out_row, const Tensor& out_score,
+                           const Tensor& out_loss, int64_t n_rounds) {
+  for (const Named& n : own) dev_tensor(n.t, n.dt, n.name);
+  dev_tensor(entity, at::kFloat, "entity_params"); dev_tensor(bias, at::kFloat, "bias_params");
+  dev_tensor(scalars, at::kFloat, "scalars"); dev_tensor(workspace, at::kByte, "workspace");
+  dev_tensor(out_row, at::kLong, "out_row"); dev_tensor(out_score, at::kFloat, "out_score");
+  dev_tensor(out_loss, at::kFloat, "out_loss");
+  TORCH_CHECK(entity.dim() == 2 && bias.dim() == 2 && bias.size(1) == 2 && bias.size(0) == entity.size(0) &&
+              entity.size(1) % 2 == 0 && scalars.numel() >= 3, "table shapes");
+  TORCH_CHECK(n_rounds >= 0 && n_rounds <= VFM_ELICIT_MAX_ROUNDS, "n_rounds out of range");
+}
+
+// The sizes, options, tables, outputs and workspace of p, which both structs name alike, with their size checks.
+// P: vfm_elicit_t or vfm_elicit_field_t; U ids, n_pool pool rows.  The op adds its ids, rows, history and operands.
+template <class P>
+void fill_session(P& p, int64_t U, int64_t n_pool, int64_t F, const Tensor& pool_ptr, const Tensor& pool_y, Tensor& entity,
+                  Tensor& bias, const Tensor& scalars, Tensor& workspace, Tensor& out_row, Tensor& out_score,
+                  Tensor& out_loss, const optional<Tensor>& out_theta, const optional<Tensor>& out_mean,
+                  const optional<Tensor>& out_var, int64_t Q, int64_t strategy, int64_t objective, int64_t likelihood,
+                  int64_t flags, int64_t n_steps, int64_t n_samples, int64_t reset, int64_t write, int64_t lds_rows,
+                  double lr, double kl_weight, int64_t seed, int64_t t0) {
+  TORCH_CHECK(out_row.numel() >= U * Q && out_score.numel() >= U * Q && out_loss.numel() >= U * Q,
+              "out_row, out_score, out_loss must be [U, Q]");
+  VFM_STRUCT_INIT(p);
+  p.U = U; p.P = n_pool; p.T = entity.size(0); p.F = (int32_t)F; p.d = (int32_t)(entity.size(1) / 2);
+  p.n_rounds = (int32_t)Q; p.strategy = (int32_t)strategy; p.objective = (int32_t)objective;
+  p.likelihood = (int32_t)likelihood; p.flags = (int32_t)flags; p.n_steps = (int32_t)n_steps;
+  p.n_samples = (int32_t)n_samples; p.reset = (int32_t)reset; p.write = (int32_t)write; p.lds_rows = (int32_t)lds_rows;
+  p.lr = (float)lr; p.kl_weight = (float)kl_weight; p.seed = (uint64_t)seed; p.t0 = t0;
+  p.pool_ptr = pool_ptr.data_ptr<int64_t>(); p.pool_y = pool_y.data_ptr<float>();
+  p.entity_params = entity.data_ptr<float>(); p.bias_params = bias.data_ptr<float>();
+  p.scalars = scalars.data_ptr<float>();
+  p.out_row = out_row.data_ptr<int64_t>(); p.out_score = out_score.data_ptr<float>();
+  p.out_loss = out_loss.data_ptr<float>();
+  if (given(out_theta)) {
+    TORCH_CHECK(dev_tensor(*out_theta, at::kFloat, "out_theta").numel() >= U * Q * (2 * (int64_t)p.d + 2),
+                "out_theta must be [U, Q, 2d + 2]");
+    p.out_theta = out_theta->data_ptr<float>();
+  }
+  if (given(out_mean) || given(out_var)) {
+    TORCH_CHECK(given(out_mean) && given(out_var), "out_mean and out_var: both or neither");
+    TORCH_CHECK(dev_tensor(*out_mean, at::kFloat, "out_mean").numel() >= (Q + 1) * n_pool &&
+                dev_tensor(*out_var, at::kFloat, "out_var").numel() >= (Q + 1) * n_pool,
+                "out_mean, out_var must be [Q + 1, P]");
+    p.out_mean = out_mean->data_ptr<float>();
+    p.out_var = out_var->data_ptr<float>();
+  }
+  p.workspace = workspace.data_ptr();
+  p.workspace_bytes = workspace.numel();
+}
+
 int64_t elicit_workspace_bytes(int64_t P, int64_t n_ops, int64_t d, int64_t objective) {
   const int64_t b = vfm_elicit_workspace_bytes(P, n_ops, (int32_t)d, (int32_t)objective);
   TORCH_CHECK(b >= 0, "vfm_elicit_workspace_bytes: bad arguments");
@@ -38,40 +100,28 @@ void elicit(const Tensor& users, const Tensor& pool_ptr, const Tensor& pool_item
             const optional<Tensor>& out_var, int64_t n_rounds, int64_t strategy, int64_t objective, int64_t likelihood,
             int64_t flags, int64_t n_steps, int64_t n_samples, int64_t reset, int64_t write, int64_t lds_rows, double lr,
             double kl_weight, int64_t seed, int64_t t0) {
-  dev_tensor(users, at::kLong, "users"); dev_tensor(pool_ptr, at::kLong, "pool_ptr");
-  dev_tensor(pool_items, at::kLong, "pool_items"); dev_tensor(pool_y, at::kFloat, "pool_y");
-  dev_tensor(entity, at::kFloat, "entity_params"); dev_tensor(bias, at::kFloat, "bias_params");
-  dev_tensor(scalars, at::kFloat, "scalars"); dev_tensor(workspace, at::kByte, "workspace");
-  dev_tensor(out_row, at::kLong, "out_row"); dev_tensor(out_score, at::kFloat, "out_score");
-  dev_tensor(out_loss, at::kFloat, "out_loss");
-  TORCH_CHECK(entity.dim() == 2 && bias.dim() == 2 && bias.size(1) == 2 && bias.size(0) == entity.size(0) &&
-              entity.size(1) % 2 == 0 && scalars.numel() >= 3, "table shapes");
-  TORCH_CHECK(n_rounds >= 0 && n_rounds <= VFM_ELICIT_MAX_ROUNDS, "n_rounds out of range");
-  const int64_t U = users.numel(), P = pool_items.numel(), Q = n_rounds;
+  check_session_tensors({{users, at::kLong, "users"}, {pool_ptr, at::kLong, "pool_ptr"},
+                         {pool_items, at::kLong, "pool_items"}, {pool_y, at::kFloat, "pool_y"}},
+                        entity, bias, scalars, workspace, out_row, out_score, out_loss, n_rounds);
+  const int64_t U = users.numel(), P = pool_items.numel();
   TORCH_CHECK(pool_ptr.numel() == U + 1 && pool_y.numel() == P, "pool_ptr [U + 1], pool_y [P]");
-  TORCH_CHECK(out_row.numel() >= U * Q && out_score.numel() >= U * Q && out_loss.numel() >= U * Q,
-              "out_row, out_score, out_loss must be [U, Q]");
   vfm_elicit_t p;
-  VFM_STRUCT_INIT(p);
-  p.U = U; p.P = P; p.T = entity.size(0); p.F = 2; p.d = (int32_t)(entity.size(1) / 2);
-  p.n_rounds = (int32_t)Q; p.strategy = (int32_t)strategy; p.objective = (int32_t)objective;
-  p.likelihood = (int32_t)likelihood; p.flags = (int32_t)flags; p.n_steps = (int32_t)n_steps;
-  p.n_samples = (int32_t)n_samples; p.reset = (int32_t)reset; p.write = (int32_t)write; p.lds_rows = (int32_t)lds_rows;
-  p.lr = (float)lr; p.kl_weight = (float)kl_weight; p.seed = (uint64_t)seed; p.t0 = t0;
-  p.users = users.data_ptr<int64_t>(); p.pool_ptr = pool_ptr.data_ptr<int64_t>();
-  p.pool_items = pool_items.data_ptr<int64_t>(); p.pool_y = pool_y.data_ptr<float>();
+  fill_session(p, U, P, 2, pool_ptr, pool_y, entity, bias, scalars, workspace, out_row, out_score, out_loss, out_theta,
+               out_mean, out_var, n_rounds, strategy, objective, likelihood, flags, n_steps, n_samples, reset, write,
+               lds_rows, lr, kl_weight, seed, t0);
+  p.users = users.data_ptr<int64_t>(); p.pool_items = pool_items.data_ptr<int64_t>();
   if (given(hist_ptr)) {
     TORCH_CHECK(given(hist_items) && given(hist_y), "hist_ptr needs hist_items and hist_y");
     dev_tensor(*hist_ptr, at::kLong, "hist_ptr"); dev_tensor(*hist_items, at::kLong, "hist_items");
     dev_tensor(*hist_y, at::kFloat, "hist_y");
     p.H = hist_items->numel();
-    TORCH_CHECK(hist_ptr->numel() == U + 1 && hist_y->numel() == p.H, "hist_ptr [U + 1], hist_y [H]");
+    TORCH_CHECK(hist_ptr->numel() == p.U + 1 && hist_y->numel() == p.H, "hist_ptr [U + 1], hist_y [H]");
     p.hist_ptr = hist_ptr->data_ptr<int64_t>(); p.hist_items = hist_items->data_ptr<int64_t>();
     p.hist_y = hist_y->data_ptr<float>();
   }
   if (given(op_x)) {
     TORCH_CHECK(dev_tensor(*op_x, at::kLong, "op_x").dim() == 2 && op_x->size(1) == 2, "op_x must be [n_ops, 2]");
-    TORCH_CHECK(given(pool_op) && dev_tensor(*pool_op, at::kLong, "pool_op").numel() == P,
+    TORCH_CHECK(given(pool_op) && dev_tensor(*pool_op, at::kLong, "pool_op").numel() == p.P,
                 "pool_op must hold one operand per pool row");
     p.n_ops = op_x->size(0);
     p.op_x = op_x->data_ptr<int64_t>();
@@ -82,24 +132,6 @@ void elicit(const Tensor& users, const Tensor& pool_ptr, const Tensor& pool_item
       p.hist_op = hist_op->data_ptr<int64_t>();
     }
   }
-  p.entity_params = entity.data_ptr<float>(); p.bias_params = bias.data_ptr<float>();
-  p.scalars = scalars.data_ptr<float>();
-  p.out_row = out_row.data_ptr<int64_t>(); p.out_score = out_score.data_ptr<float>();
-  p.out_loss = out_loss.data_ptr<float>();
-  if (given(out_theta)) {
-    TORCH_CHECK(dev_tensor(*out_theta, at::kFloat, "out_theta").numel() >= U * Q * (2 * (int64_t)p.d + 2),
-                "out_theta must be [U, Q, 2d + 2]");
-    p.out_theta = out_theta->data_ptr<float>();
-  }
-  if (given(out_mean) || given(out_var)) {
-    TORCH_CHECK(given(out_mean) && given(out_var), "out_mean and out_var: both or neither");
-    TORCH_CHECK(dev_tensor(*out_mean, at::kFloat, "out_mean").numel() >= (Q + 1) * P &&
-                dev_tensor(*out_var, at::kFloat, "out_var").numel() >= (Q + 1) * P, "out_mean, out_var must be [Q + 1, P]");
-    p.out_mean = out_mean->data_ptr<float>();
-    p.out_var = out_var->data_ptr<float>();
-  }
-  p.workspace = workspace.data_ptr();
-  p.workspace_bytes = workspace.numel();
   c10::hip::HIPGuard guard(users.get_device());
   const int rc = vfm_elicit_f32(&p, (void*)c10::hip::getCurrentHIPStream(users.get_device()).stream());
   TORCH_CHECK(rc == 0, "vfm_elicit_f32 failed (code ", rc, "): ", vfm_last_error());
@@ -120,33 +152,20 @@ void elicit_field(const Tensor& entities, const Tensor& pool_ptr, const Tensor& 
                   int64_t field, int64_t key_col, int64_t n_rounds, int64_t strategy, int64_t objective,
                   int64_t likelihood, int64_t flags, int64_t n_steps, int64_t n_samples, int64_t reset, int64_t write,
                   int64_t lds_rows, double lr, double kl_weight, int64_t seed, int64_t t0) {
-  dev_tensor(entities, at::kLong, "entities"); dev_tensor(pool_ptr, at::kLong, "pool_ptr");
-  dev_tensor(pool_x, at::kLong, "pool_x"); dev_tensor(pool_y, at::kFloat, "pool_y");
-  dev_tensor(op_x, at::kLong, "op_x"); dev_tensor(pool_op, at::kLong, "pool_op");
-  dev_tensor(entity, at::kFloat, "entity_params"); dev_tensor(bias, at::kFloat, "bias_params");
-  dev_tensor(scalars, at::kFloat, "scalars"); dev_tensor(workspace, at::kByte, "workspace");
-  dev_tensor(out_row, at::kLong, "out_row"); dev_tensor(out_score, at::kFloat, "out_score");
-  dev_tensor(out_loss, at::kFloat, "out_loss");
-  TORCH_CHECK(entity.dim() == 2 && bias.dim() == 2 && bias.size(1) == 2 && bias.size(0) == entity.size(0) &&
-              entity.size(1) % 2 == 0 && scalars.numel() >= 3, "table shapes");
-  TORCH_CHECK(n_rounds >= 0 && n_rounds <= VFM_ELICIT_MAX_ROUNDS, "n_rounds out of range");
+  check_session_tensors({{entities, at::kLong, "entities"}, {pool_ptr, at::kLong, "pool_ptr"}, {pool_x, at::kLong, "pool_x"},
+                         {pool_y, at::kFloat, "pool_y"}, {op_x, at::kLong, "op_x"}, {pool_op, at::kLong, "pool_op"}},
+                        entity, bias, scalars, workspace, out_row, out_score, out_loss, n_rounds);
   TORCH_CHECK(pool_x.dim() == 2 && pool_x.size(1) >= 2 && pool_x.size(1) <= VFM_MAX_FIELDS, "pool_x must be [P, F]");
-  const int64_t U = entities.numel(), P = pool_x.size(0), F = pool_x.size(1), Q = n_rounds;
+  const int64_t U = entities.numel(), P = pool_x.size(0), F = pool_x.size(1);
   TORCH_CHECK(pool_ptr.numel() == U + 1 && pool_y.numel() == P, "pool_ptr [U + 1], pool_y [P]");
   TORCH_CHECK(op_x.dim() == 2 && op_x.size(1) == F && pool_op.numel() == P,
               "op_x must be [n_ops, F], pool_op must hold one operand per pool row");
-  TORCH_CHECK(out_row.numel() >= U * Q && out_score.numel() >= U * Q && out_loss.numel() >= U * Q,
-              "out_row, out_score, out_loss must be [U, Q]");
   vfm_elicit_field_t p;
-  VFM_STRUCT_INIT(p);
-  p.U = U; p.P = P; p.T = entity.size(0); p.F = (int32_t)F; p.d = (int32_t)(entity.size(1) / 2);
+  fill_session(p, U, P, F, pool_ptr, pool_y, entity, bias, scalars, workspace, out_row, out_score, out_loss, out_theta,
+               out_mean, out_var, n_rounds, strategy, objective, likelihood, flags, n_steps, n_samples, reset, write,
+               lds_rows, lr, kl_weight, seed, t0);
   p.field = (int32_t)field; p.key_col = (int32_t)key_col;
-  p.n_rounds = (int32_t)Q; p.strategy = (int32_t)strategy; p.objective = (int32_t)objective;
-  p.likelihood = (int32_t)likelihood; p.flags = (int32_t)flags; p.n_steps = (int32_t)n_steps;
-  p.n_samples = (int32_t)n_samples; p.reset = (int32_t)reset; p.write = (int32_t)write; p.lds_rows = (int32_t)lds_rows;
-  p.lr = (float)lr; p.kl_weight = (float)kl_weight; p.seed = (uint64_t)seed; p.t0 = t0;
-  p.entities = entities.data_ptr<int64_t>(); p.pool_ptr = pool_ptr.data_ptr<int64_t>();
-  p.pool_x = pool_x.data_ptr<int64_t>(); p.pool_y = pool_y.data_ptr<float>();
+  p.entities = entities.data_ptr<int64_t>(); p.pool_x = pool_x.data_ptr<int64_t>();
   p.n_ops = op_x.size(0);
   p.op_x = op_x.data_ptr<int64_t>(); p.pool_op = pool_op.data_ptr<int64_t>();
   if (given(hist_ptr)) {
@@ -155,29 +174,11 @@ void elicit_field(const Tensor& entities, const Tensor& pool_ptr, const Tensor& 
     dev_tensor(*hist_y, at::kFloat, "hist_y"); dev_tensor(*hist_op, at::kLong, "hist_op");
     TORCH_CHECK(hist_x->dim() == 2 && hist_x->size(1) == F, "hist_x must be [H, F]");
     p.H = hist_x->size(0);
-    TORCH_CHECK(hist_ptr->numel() == U + 1 && hist_y->numel() == p.H && hist_op->numel() == p.H,
+    TORCH_CHECK(hist_ptr->numel() == p.U + 1 && hist_y->numel() == p.H && hist_op->numel() == p.H,
                 "hist_ptr [U + 1], hist_y [H], hist_op [H]");
     p.hist_ptr = hist_ptr->data_ptr<int64_t>(); p.hist_x = hist_x->data_ptr<int64_t>();
     p.hist_y = hist_y->data_ptr<float>(); p.hist_op = hist_op->data_ptr<int64_t>();
   }
-  p.entity_params = entity.data_ptr<float>(); p.bias_params = bias.data_ptr<float>();
-  p.scalars = scalars.data_ptr<float>();
-  p.out_row = out_row.data_ptr<int64_t>(); p.out_score = out_score.data_ptr<float>();
-  p.out_loss = out_loss.data_ptr<float>();
-  if (given(out_theta)) {
-    TORCH_CHECK(dev_tensor(*out_theta, at::kFloat, "out_theta").numel() >= U * Q * (2 * (int64_t)p.d + 2),
-                "out_theta must be [U, Q, 2d + 2]");
-    p.out_theta = out_theta->data_ptr<float>();
-  }
-  if (given(out_mean) || given(out_var)) {
-    TORCH_CHECK(given(out_mean) && given(out_var), "out_mean and out_var: both or neither");
-    TORCH_CHECK(dev_tensor(*out_mean, at::kFloat, "out_mean").numel() >= (Q + 1) * P &&
-                dev_tensor(*out_var, at::kFloat, "out_var").numel() >= (Q + 1) * P, "out_mean, out_var must be [Q + 1, P]");
-    p.out_mean = out_mean->data_ptr<float>();
-    p.out_var = out_var->data_ptr<float>();
-  }
-  p.workspace = workspace.data_ptr();
-  p.workspace_bytes = workspace.numel();
   c10::hip::HIPGuard guard(entities.get_device());
   const int rc = vfm_elicit_field_f32(&p, (void*)c10::hip::getCurrentHIPStream(entities.get_device()).stream());
   TORCH_CHECK(rc == 0, "vfm_elicit_field_f32 failed (code ", rc, "): ", vfm_last_error());

@@ -13,15 +13,18 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "vfm_args.hpp"
 #include "vfm_foldin.h"
+#include "vfm_launch.hpp"            // launch_status
 
 namespace vfm {
 namespace {
 #include "vfm_rng.hpp"
 #include "vfm_common.hpp"
 
-#include "vfm_foldin_body.hpp"       // FoldArgs, k_foldin_prep, the per-entity body (shared with vfm_elicit.hip)
+#include "vfm_foldin_body.hpp"       // FoldArgs, k_foldin_prep, the per-entity body (shared with the sessions), the host side
 
 // ---------------------------------------------------------------------------------------------------------------------
 // k_foldin
@@ -98,29 +101,16 @@ __global__ __launch_bounds__(FB) void k_foldin(const FoldArgs a) {
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-template <int W, int CPL, int LINK, bool SAMPLED>
-void launch(const FoldArgs& a, hipStream_t st) {
-  constexpr int GPB = FB / W;
-  const size_t shm = SAMPLED ? 0 : (size_t)GPB * a.cap * (W * CPL + 1) * 4;
-  hipLaunchKernelGGL((k_foldin<W, CPL, LINK, SAMPLED>), dim3((unsigned)((a.E + GPB - 1) / GPB)), dim3(FB), shm, st, a);
-}
-
-template <int LINK, bool SAMPLED>
-void launch_shape(const FShape& s, const FoldArgs& a, hipStream_t st) {
-  switch (s.W * 16 + s.CPL) {
-    case 8 * 16 + 1: launch<8, 1, LINK, SAMPLED>(a, st); break;
-    case 16 * 16 + 1: launch<16, 1, LINK, SAMPLED>(a, st); break;
-    case 32 * 16 + 1: launch<32, 1, LINK, SAMPLED>(a, st); break;
-    case 64 * 16 + 1: launch<64, 1, LINK, SAMPLED>(a, st); break;
-    case 64 * 16 + 2: launch<64, 2, LINK, SAMPLED>(a, st); break;
-    case 64 * 16 + 4: launch<64, 4, LINK, SAMPLED>(a, st); break;
-    default: launch<64, 8, LINK, SAMPLED>(a, st); break;
-  }
-}
-
-int launch_status(const char* where) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail_hip(e, where);
+void launch(const FShape& s, bool sp, bool sampled, const FoldArgs& a, hipStream_t st) {
+  for_link(sp, [&](auto link) {
+    for_shape(s, [&](auto w, auto c) {
+      constexpr int W = decltype(w)::value, CPL = decltype(c)::value, LINK = decltype(link)::value, GPB = FB / W;
+      const dim3 grid((unsigned)((a.E + GPB - 1) / GPB));
+      const size_t shm = (size_t)GPB * a.cap * (W * CPL + 1) * 4;      // (sampled: cap = 0)
+      if (sampled) hipLaunchKernelGGL((k_foldin<W, CPL, LINK, true>), grid, dim3(FB), shm, st, a);
+      else hipLaunchKernelGGL((k_foldin<W, CPL, LINK, false>), grid, dim3(FB), shm, st, a);
+    });
+  });
 }
 
 }  // namespace
@@ -176,42 +166,21 @@ int vfm_foldin_f32(const vfm_foldin_t* p, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   const bool sp = (p->flags & VFM_FLAG_LINK_SOFTPLUS) != 0;
   const vfm::FShape s = vfm::shape_of(p->d);
-  const int DP = s.W * s.CPL;
-  vfm::FoldArgs a;
-  a.E = p->E; a.R = p->R; a.T = p->T;
-  a.F = p->F; a.d = p->d; a.col = p->col; a.lik = p->likelihood; a.S = cf ? 1 : p->n_samples;
-  a.n_steps = p->n_steps; a.reset = p->reset ? 1 : 0; a.mode = p->mode;
-  a.lr = p->lr; a.klw = p->kl_weight; a.t0 = p->t0;
-  a.key.seed_lo = (uint32_t)p->seed; a.key.seed_hi = (uint32_t)(p->seed >> 32);
-  a.key.step_lo = a.key.step_hi = 0; a.key.chunk_off = 0;
-  a.ent = p->entities; a.ptr = p->row_ptr; a.x = p->x; a.row_op = p->row_op; a.y = p->y;
-  a.entity = p->entity_params; a.bias = p->bias_params; a.scal = p->scalars;
+  vfm::FoldArgs a = vfm::fill_fold_args(p->E, p->T, p->F, p->d, p->col, p->likelihood, cf ? 1 : p->n_samples, p->n_steps,
+                                        p->reset ? 1 : 0, p->mode, p->lr, p->kl_weight, p->t0, p->seed,
+                                        p->entity_params, p->bias_params, p->scalars);
+  a.R = p->R; a.ent = p->entities; a.ptr = p->row_ptr; a.x = p->x; a.row_op = p->row_op; a.y = p->y;
   a.loss = p->out_loss; a.grad = p->out_grad;
-  a.ops = nullptr; a.opc = nullptr; a.cap = 0;
   if (cf) {
     char* w = (char*)p->workspace;
     float* ops = (float*)w;
     float* opc = (float*)(w + vfm::ops_off_opc(n_ops, p->d));
     a.ops = ops; a.opc = opc;
-    const int cap = vfm::LDS_BYTES / 4 / (vfm::FB / s.W) / (DP + 1);
-    a.cap = p->lds_rows < 0 ? cap : (p->lds_rows < cap ? p->lds_rows : cap);
-    if (n_ops > 0) {
-      const unsigned nb = (unsigned)((n_ops + vfm::FB - 1) / vfm::FB);
-      if (sp)
-        hipLaunchKernelGGL(vfm::k_foldin_prep<vfm::LINK_SOFTPLUS>, dim3(nb), dim3(vfm::FB), 0, st, n_ops, p->F, p->d, DP,
-                           p->col, p->T, p->op_x, p->entity_params, p->bias_params, p->scalars, ops, opc);
-      else
-        hipLaunchKernelGGL(vfm::k_foldin_prep<vfm::LINK_ABS>, dim3(nb), dim3(vfm::FB), 0, st, n_ops, p->F, p->d, DP,
-                           p->col, p->T, p->op_x, p->entity_params, p->bias_params, p->scalars, ops, opc);
-      if (int rc = vfm::launch_status("k_foldin_prep")) return rc;
-    }
-    if (sp) vfm::launch_shape<vfm::LINK_SOFTPLUS, false>(s, a, st);
-    else vfm::launch_shape<vfm::LINK_ABS, false>(s, a, st);
-  } else {
-    if (sp) vfm::launch_shape<vfm::LINK_SOFTPLUS, true>(s, a, st);
-    else vfm::launch_shape<vfm::LINK_ABS, true>(s, a, st);
+    a.cap = vfm::lds_cap(s, 0, p->lds_rows);
+    if (int rc = vfm::launch_foldin_prep(sp, a, n_ops, p->op_x, ops, opc, st)) return rc;
   }
-  return vfm::launch_status("k_foldin");
+  vfm::launch(s, sp, !cf, a, st);
+  return launch_status("k_foldin");
 }
 
 }  // extern "C"

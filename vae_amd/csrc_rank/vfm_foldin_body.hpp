@@ -1,6 +1,10 @@
-// vfm_foldin_body.hpp -- the per-entity body of the fold-in, shared by k_foldin (vfm_foldin.hip) and the elicitation
-// session k_elicit (vfm_elicit.hip): the operand prep, the row sums and LDS stage of the closed form, and the Adam loop.
-// Included inside `namespace vfm { namespace {` of a unit, after vfm_rng.hpp and vfm_common.hpp.
+// vfm_foldin_body.hpp -- the per-entity body of the fold-in, shared by k_foldin (vfm_foldin.hip), the exact fold-in
+// (vfm_foldin_solve.hip) and the elicitation sessions (vfm_elicit.hip, vfm_elicit_field.hip): the operand prep, the row
+// sums and LDS stage of the closed form, the Adam loop, and the host side every such unit needs (the lane-group shape
+// and its dispatch, the FoldArgs fill, the prep launch, the LDS budget).
+// Included inside `namespace vfm { namespace {` of a unit, after vfm_rng.hpp and vfm_common.hpp.  The host side uses
+// std::integral_constant and launch_status: the unit includes <type_traits> and vfm_launch.hpp at file scope first
+// (an #include here would land inside the namespace).
 //
 // The body is parameterised over where the entity's rows come from (a Rows object: op(i), y(i), partner(i, f) of row i
 // in fold order).  The row sums are sequential in row order, so fold_stage_rows over [0, n) and over [0, m) then [m, n)
@@ -351,7 +355,8 @@ __device__ __forceinline__ void fold_run(const FoldArgs& a, const Rows& rows, in
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// host side: the lane-group shape for an embedding size, the operand block of a workspace
+// host side: the lane-group shape for an embedding size and its dispatch, the operand block of a workspace, the
+// FoldArgs fill, the prep launch, the LDS budget
 // ---------------------------------------------------------------------------------------------------------------------
 struct FShape {
   int W, CPL;
@@ -363,9 +368,68 @@ inline FShape shape_of(int d) {
   return {W, c <= 1 ? 1 : c <= 2 ? 2 : c <= 4 ? 4 : 8};
 }
 
+template <int N>
+using IntC = std::integral_constant<int, N>;
+
+// fn(IntC<W>, IntC<CPL>) for the shape s: the one place that lists the shapes kernels are instantiated for
+template <class Fn>
+void for_shape(const FShape& s, Fn&& fn) {
+  switch (s.W * 16 + s.CPL) {
+    case 8 * 16 + 1: fn(IntC<8>{}, IntC<1>{}); break;
+    case 16 * 16 + 1: fn(IntC<16>{}, IntC<1>{}); break;
+    case 32 * 16 + 1: fn(IntC<32>{}, IntC<1>{}); break;
+    case 64 * 16 + 1: fn(IntC<64>{}, IntC<1>{}); break;
+    case 64 * 16 + 2: fn(IntC<64>{}, IntC<2>{}); break;
+    case 64 * 16 + 4: fn(IntC<64>{}, IntC<4>{}); break;
+    default: fn(IntC<64>{}, IntC<8>{}); break;
+  }
+}
+
+// fn(IntC<LINK>) for the link function of the flags
+template <class Fn>
+void for_link(bool softplus, Fn&& fn) {
+  if (softplus) fn(IntC<LINK_SOFTPLUS>{});
+  else fn(IntC<LINK_ABS>{});
+}
+
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 inline int64_t ops_off_opc(int64_t n_ops, int d) {
   const FShape s = shape_of(d);
   return round_up(n_ops * 3 * (int64_t)(s.W * s.CPL) * 4, 256);
+}
+
+// The options and tables every entry point passes; the rest is zero / NULL (R and the row list, the operands, cap, the
+// outputs) for the caller to set.
+inline FoldArgs fill_fold_args(int64_t E, int64_t T, int F, int d, int col, int lik, int S, int n_steps, int reset,
+                               int mode, float lr, float klw, int64_t t0, uint64_t seed, float* entity, float* bias,
+                               const float* scal) {
+  FoldArgs a = {};
+  a.E = E; a.T = T;
+  a.F = F; a.d = d; a.col = col; a.lik = lik; a.S = S;
+  a.n_steps = n_steps; a.reset = reset; a.mode = mode;
+  a.lr = lr; a.klw = klw; a.t0 = t0;
+  a.key.seed_lo = (uint32_t)seed; a.key.seed_hi = (uint32_t)(seed >> 32);
+  a.entity = entity; a.bias = bias; a.scal = scal;
+  return a;
+}
+
+// k_foldin_prep over the n_ops rows of op_x into a's operand tables (nothing to launch for n_ops = 0)
+inline int launch_foldin_prep(bool sp, const FoldArgs& a, int64_t n_ops, const int64_t* op_x, float* ops, float* opc,
+                              hipStream_t st) {
+  if (n_ops <= 0) return 0;
+  const FShape s = shape_of(a.d);
+  for_link(sp, [&](auto link) {
+    hipLaunchKernelGGL(k_foldin_prep<decltype(link)::value>, dim3((unsigned)((n_ops + FB - 1) / FB)), dim3(FB), 0, st,
+                       n_ops, a.F, a.d, s.W * s.CPL, a.col, a.T, op_x, a.entity, a.bias, a.scal, ops, opc);
+  });
+  return launch_status("k_foldin_prep");
+}
+
+// rows per entity staged in LDS: what a block's LDS_BYTES leave each group after theta_floats of its own, capped by the
+// caller's lds_rows (-1: no cap)
+inline int lds_cap(const FShape& s, int theta_floats, int lds_rows) {
+  const int c = (LDS_BYTES / 4 / (FB / s.W) - theta_floats) / (s.W * s.CPL + 1);
+  const int cap = c < 0 ? 0 : c;
+  return lds_rows < 0 || lds_rows > cap ? cap : lds_rows;
 }

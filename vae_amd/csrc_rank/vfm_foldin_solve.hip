@@ -20,15 +20,18 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "vfm_args.hpp"
 #include "vfm_foldin.h"
+#include "vfm_launch.hpp"            // launch_status
 
 namespace vfm {
 namespace {
 #include "vfm_rng.hpp"
 #include "vfm_common.hpp"
 
-#include "vfm_foldin_body.hpp"       // FoldArgs, k_foldin_prep, fold_stage_rows
+#include "vfm_foldin_body.hpp"       // FoldArgs, k_foldin_prep, fold_stage_rows, the host side
 
 struct SolveArgs {
   FoldArgs f;                            // (cap = 0: fold_stage_rows stages nothing; f.ops / f.opc: the fp32 operands of the loss)
@@ -306,30 +309,16 @@ __global__ __launch_bounds__(FB) void k_foldin_solve(const SolveArgs s) {
   }
 }
 
-template <int W, int CPL, int LINK>
-void launch(const SolveArgs& s, unsigned grid, size_t shm, hipStream_t st) {
-  // (more than 64 KiB of dynamic LDS: state the size; a runtime that needs no opt-in ignores it)
-  (void)hipFuncSetAttribute((const void*)k_foldin_solve<W, CPL, LINK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-  (void)hipGetLastError();
-  hipLaunchKernelGGL((k_foldin_solve<W, CPL, LINK>), dim3(grid), dim3(FB), shm, st, s);
-}
-
-template <int LINK>
-void launch_shape(const FShape& f, const SolveArgs& s, unsigned grid, size_t shm, hipStream_t st) {
-  switch (f.W * 16 + f.CPL) {
-    case 8 * 16 + 1: launch<8, 1, LINK>(s, grid, shm, st); break;
-    case 16 * 16 + 1: launch<16, 1, LINK>(s, grid, shm, st); break;
-    case 32 * 16 + 1: launch<32, 1, LINK>(s, grid, shm, st); break;
-    case 64 * 16 + 1: launch<64, 1, LINK>(s, grid, shm, st); break;
-    case 64 * 16 + 2: launch<64, 2, LINK>(s, grid, shm, st); break;
-    case 64 * 16 + 4: launch<64, 4, LINK>(s, grid, shm, st); break;
-    default: launch<64, 8, LINK>(s, grid, shm, st); break;
-  }
-}
-
-int launch_status(const char* where) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail_hip(e, where);
+void launch(const FShape& f, bool sp, const SolveArgs& s, unsigned grid, size_t shm, hipStream_t st) {
+  for_link(sp, [&](auto link) {
+    for_shape(f, [&](auto w, auto c) {
+      const auto k = k_foldin_solve<decltype(w)::value, decltype(c)::value, decltype(link)::value>;
+      // (more than 64 KiB of dynamic LDS: state the size; a runtime that needs no opt-in ignores it)
+      (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+      (void)hipGetLastError();
+      hipLaunchKernelGGL(k, dim3(grid), dim3(FB), shm, st, s);
+    });
+  });
 }
 
 inline int cap_dim_of(int d, int lds_dim) {
@@ -385,17 +374,12 @@ int vfm_foldin_solve_f32(const vfm_foldin_solve_t* p, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   const bool sp = (p->flags & VFM_FLAG_LINK_SOFTPLUS) != 0;
   const vfm::FShape f = vfm::shape_of(p->d);
-  const int DP = f.W * f.CPL;
   vfm::SolveArgs s;
   vfm::FoldArgs& a = s.f;
-  a.E = p->E; a.R = p->R; a.T = p->T;
-  a.F = p->F; a.d = p->d; a.col = p->col; a.lik = VFM_LIK_NORMAL; a.S = 1;
-  a.n_steps = 0; a.reset = 0; a.mode = VFM_FOLDIN_FIT; a.cap = 0;
-  a.lr = 0.f; a.klw = p->kl_weight; a.t0 = 0;
-  a.key.seed_lo = a.key.seed_hi = a.key.step_lo = a.key.step_hi = 0; a.key.chunk_off = 0;
-  a.ent = p->entities; a.ptr = p->row_ptr; a.x = nullptr; a.row_op = p->row_op; a.y = p->y;
-  a.entity = p->entity_params; a.bias = p->bias_params; a.scal = p->scalars;
-  a.loss = p->out_loss; a.grad = nullptr;
+  a = vfm::fill_fold_args(p->E, p->T, p->F, p->d, p->col, VFM_LIK_NORMAL, 1, 0, 0, VFM_FOLDIN_FIT, 0.f, p->kl_weight, 0, 0,
+                          p->entity_params, p->bias_params, p->scalars);
+  a.R = p->R; a.ent = p->entities; a.ptr = p->row_ptr; a.row_op = p->row_op; a.y = p->y;
+  a.loss = p->out_loss;
   char* w = (char*)p->workspace;
   const int64_t off_opc = vfm::ops_off_opc(p->n_ops, p->d);
   float* ops = (float*)w;
@@ -413,25 +397,16 @@ int vfm_foldin_solve_f32(const vfm_foldin_solve_t* p, void* stream) {
   const size_t shm = (size_t)vfm::lds_doubles(p->d, s.cap_dim) * 8;
 
   if (p->n_ops > 0) {
+    if (int rc = vfm::launch_foldin_prep(sp, a, p->n_ops, p->op_x, ops, opc, st)) return rc;
     const unsigned nb = (unsigned)((p->n_ops + vfm::FB - 1) / vfm::FB);
-    if (sp)
-      hipLaunchKernelGGL(vfm::k_foldin_prep<vfm::LINK_SOFTPLUS>, dim3(nb), dim3(vfm::FB), 0, st, p->n_ops, p->F, p->d, DP,
-                         p->col, p->T, p->op_x, p->entity_params, p->bias_params, p->scalars, ops, opc);
-    else
-      hipLaunchKernelGGL(vfm::k_foldin_prep<vfm::LINK_ABS>, dim3(nb), dim3(vfm::FB), 0, st, p->n_ops, p->F, p->d, DP,
-                         p->col, p->T, p->op_x, p->entity_params, p->bias_params, p->scalars, ops, opc);
-    if (int rc = vfm::launch_status("k_foldin_prep")) return rc;
-    if (sp)
-      hipLaunchKernelGGL(vfm::k_foldin_solve_prep<vfm::LINK_SOFTPLUS>, dim3(nb), dim3(vfm::FB), 0, st, p->n_ops, p->F, p->d,
-                         p->col, p->T, p->op_x, p->entity_params, p->bias_params, p->scalars, ops64, cm64);
-    else
-      hipLaunchKernelGGL(vfm::k_foldin_solve_prep<vfm::LINK_ABS>, dim3(nb), dim3(vfm::FB), 0, st, p->n_ops, p->F, p->d,
-                         p->col, p->T, p->op_x, p->entity_params, p->bias_params, p->scalars, ops64, cm64);
-    if (int rc = vfm::launch_status("k_foldin_solve_prep")) return rc;
+    vfm::for_link(sp, [&](auto link) {
+      hipLaunchKernelGGL(vfm::k_foldin_solve_prep<decltype(link)::value>, dim3(nb), dim3(vfm::FB), 0, st, p->n_ops, p->F,
+                         p->d, p->col, p->T, p->op_x, p->entity_params, p->bias_params, p->scalars, ops64, cm64);
+    });
+    if (int rc = launch_status("k_foldin_solve_prep")) return rc;
   }
-  if (sp) vfm::launch_shape<vfm::LINK_SOFTPLUS>(f, s, grid, shm, st);
-  else vfm::launch_shape<vfm::LINK_ABS>(f, s, grid, shm, st);
-  return vfm::launch_status("k_foldin_solve");
+  vfm::launch(f, sp, s, grid, shm, st);
+  return launch_status("k_foldin_solve");
 }
 
 }  // extern "C"

@@ -10,11 +10,11 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "vfm_launch.hpp"             // launch_status
 #include "vfm_rank.h"
 
 namespace vfm {
 int fail(int code, const char* msg);          // (vfm_abi.hip: the thread's vfm_last_error() text)
-int fail_hip(hipError_t e, const char* where);
 }  // namespace vfm
 
 namespace {
@@ -264,11 +264,6 @@ inline int check_common(int64_t T, int32_t d, int32_t flags, int32_t strategy) {
   if (flags & ~VFM_FLAG_LINK_SOFTPLUS) return vfm::fail(VFM_E_INVALID, "flags: only VFM_FLAG_LINK_SOFTPLUS is accepted");
   if (strategy < VFM_RANK_TOP || strategy > VFM_RANK_RANDOM) return vfm::fail(VFM_E_INVALID, "unknown strategy");
   return 0;
-}
-
-inline int launch_status(const char* where) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : vfm::fail_hip(e, where);
 }
 
 // k_rank_prep over the query users and the candidates into the operand blocks of L (not for VFM_RANK_RANDOM)

@@ -21,25 +21,34 @@ from .rank import _seed64, strategy_code
 MAX_ROUNDS = _lib.ELICIT_MAX_ROUNDS
 
 
+def _check_questions(model, strategy, n_questions):
+    """The strategy / n_questions checks of both forms (after strategy_code)."""
+    if strategy == "mean" and model.output != "class":
+        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
+    if isinstance(n_questions, bool) or not isinstance(n_questions, int) or not 0 <= n_questions <= MAX_ROUNDS:
+        raise ValueError(f"n_questions must be an int in [0, {MAX_ROUNDS}]")
+
+
+def _history_pair(history, width):
+    if not isinstance(history, (tuple, list)) or len(history) != 2:
+        raise ValueError(f"history must be a pair (X [H, {width}], y [H])")
+    return history
+
+
 def check_args(model, pool, y_pool, n_questions, strategy, history, n_steps, lr, objective, n_samples, kl_weight):
     """Validate a session call (no GPU needed).  Returns (pool [P, 2] int64, y_pool [P] fp32, hist_x [H, 2] or None,
     hist_y [H] or None, objective name, strategy code) on the model's device."""
     code = strategy_code(strategy)
     if model.F != 2:
         raise ValueError("elicit: two-field models only")
-    if strategy == "mean" and model.output != "class":
-        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
-    if isinstance(n_questions, bool) or not isinstance(n_questions, int) or not 0 <= n_questions <= MAX_ROUNDS:
-        raise ValueError(f"n_questions must be an int in [0, {MAX_ROUNDS}]")
+    _check_questions(model, strategy, n_questions)
     pool = torch.as_tensor(pool)
     if pool.dim() != 2 or pool.shape[1] != 2:
         raise ValueError("pool must be an [P, 2] tensor of (user, item) rows")
     x, y, objective = foldin.check_args(model, pool, y_pool, 0, objective, n_samples, n_steps, lr, kl_weight)
     hx = hy = None
     if history is not None:
-        if not isinstance(history, (tuple, list)) or len(history) != 2:
-            raise ValueError("history must be a pair (X [H, 2], y [H])")
-        hx = torch.as_tensor(history[0])
+        hx = torch.as_tensor(_history_pair(history, 2)[0])
         if hx.dim() != 2 or hx.shape[1] != 2:
             raise ValueError("history X must be an [H, 2] tensor of (user, item) rows")
         hx, hy, _ = foldin.check_args(model, hx, history[1], 0, objective, n_samples, n_steps, lr, kl_weight)
@@ -82,6 +91,28 @@ def to_caller_order(v, order):
     return out
 
 
+def _outputs(dev, U, Q, P, d, return_theta, return_moments):
+    """The outputs of a session launch: out_row, score, loss [U, Q] (padded: -1, NaN), theta [U, Q, 2d + 2] or None,
+    mean and var [Q + 1, P] or None."""
+    f32 = dict(dtype=torch.float32, device=dev)
+    out_row = torch.full((U, Q), -1, dtype=torch.int64, device=dev)
+    score, loss = torch.full((U, Q), float("nan"), **f32), torch.full((U, Q), float("nan"), **f32)
+    theta = torch.empty(U, Q, 2 * d + 2, **f32) if return_theta else None
+    mean = torch.empty(Q + 1, P, **f32) if return_moments else None
+    var = torch.empty(Q + 1, P, **f32) if return_moments else None
+    return out_row, score, loss, theta, mean, var
+
+
+def _result(res, order, out_row, score, loss, theta, mean, var):
+    """The session's outputs added to res, rows and moments mapped back to the caller's pool order."""
+    res.update(rows=rows_to_caller(out_row, order), score=score, loss=loss)
+    if theta is not None:
+        res["theta"] = theta
+    if mean is not None:
+        res["logit_mean"], res["logit_var"] = to_caller_order(mean, order), to_caller_order(var, order)
+    return res
+
+
 def run(model, pool, y_pool, n_questions, strategy="variance", history=None, n_steps=200, lr=0.05, objective=None,
         n_samples=1, seed=0, kl_weight=1.0, reset=False, write=False, return_moments=False, return_theta=False, t0=0,
         lds_rows=-1):
@@ -97,12 +128,7 @@ def run(model, pool, y_pool, n_questions, strategy="variance", history=None, n_s
     if hx is not None and hx.shape[0]:
         horder, hptr = history_lists(users, hx)
         hitems, hys = hx[horder, 1].contiguous(), hy[horder].contiguous()
-    f32 = dict(dtype=torch.float32, device=dev)
-    out_row = torch.full((U, Q), -1, dtype=torch.int64, device=dev)
-    score, loss = torch.full((U, Q), float("nan"), **f32), torch.full((U, Q), float("nan"), **f32)
-    theta = torch.empty(U, Q, 2 * d + 2, **f32) if return_theta else None
-    mean = torch.empty(Q + 1, P, **f32) if return_moments else None
-    var = torch.empty(Q + 1, P, **f32) if return_moments else None
+    out_row, score, loss, theta, mean, var = _outputs(dev, U, Q, P, d, return_theta, return_moments)
     res = {"users": users}
     if U:
         o = _lib.ops()
@@ -127,12 +153,7 @@ def run(model, pool, y_pool, n_questions, strategy="variance", history=None, n_s
                  float(kl_weight), _seed64(seed), int(t0))
         if write:
             model.params_changed()      # (rows written outside the step kernels: derived caches are stale)
-    res.update(rows=rows_to_caller(out_row, order), score=score, loss=loss)
-    if return_theta:
-        res["theta"] = theta
-    if return_moments:
-        res["logit_mean"], res["logit_var"] = to_caller_order(mean, order), to_caller_order(var, order)
-    return res
+    return _result(res, order, out_row, score, loss, theta, mean, var)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -146,17 +167,12 @@ def check_args_field(model, pool, y_pool, n_questions, field, strategy, history,
     field = _field_arg(model, field)
     kf = _key_field(model, field, key_field)
     code = strategy_code(strategy)
-    if strategy == "mean" and model.output != "class":
-        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
-    if isinstance(n_questions, bool) or not isinstance(n_questions, int) or not 0 <= n_questions <= MAX_ROUNDS:
-        raise ValueError(f"n_questions must be an int in [0, {MAX_ROUNDS}]")
+    _check_questions(model, strategy, n_questions)
     x = _context_rows(model, pool, "pool", field, check_field_column=True)
     x, y, objective = foldin.check_args(model, x, y_pool, field, objective, n_samples, n_steps, lr, kl_weight)
     hx = hy = None
     if history is not None:
-        if not isinstance(history, (tuple, list)) or len(history) != 2:
-            raise ValueError(f"history must be a pair (X [H, {model.F}], y [H])")
-        hx = _context_rows(model, history[0], "history X", field, check_field_column=True)
+        hx = _context_rows(model, _history_pair(history, model.F)[0], "history X", field, check_field_column=True)
         hx, hy, _ = foldin.check_args(model, hx, history[1], field, objective, n_samples, n_steps, lr, kl_weight)
         if hx.shape[0] and not bool(torch.isin(hx[:, field], x[:, field]).all()):
             raise ValueError("history holds respondents without a pool row")
@@ -181,12 +197,7 @@ def run_field(model, pool, y_pool, n_questions, field=0, strategy="variance", hi
     if hx is not None and hx.shape[0]:
         horder, hptr = history_lists(ents, hx, field)
         hxs, hys = hx[horder].contiguous(), hy[horder].contiguous()
-    f32 = dict(dtype=torch.float32, device=dev)
-    out_row = torch.full((U, Q), -1, dtype=torch.int64, device=dev)
-    score, loss = torch.full((U, Q), float("nan"), **f32), torch.full((U, Q), float("nan"), **f32)
-    theta = torch.empty(U, Q, 2 * d + 2, **f32) if return_theta else None
-    mean = torch.empty(Q + 1, P, **f32) if return_moments else None
-    var = torch.empty(Q + 1, P, **f32) if return_moments else None
+    out_row, score, loss, theta, mean, var = _outputs(dev, U, Q, P, d, return_theta, return_moments)
     res = {"entities": ents}
     if U:
         o = _lib.ops()
@@ -209,12 +220,7 @@ def run_field(model, pool, y_pool, n_questions, field=0, strategy="variance", hi
                        int(t0))
         if write:
             model.params_changed()      # (rows written outside the step kernels: derived caches are stale)
-    res.update(rows=rows_to_caller(out_row, order), score=score, loss=loss)
-    if return_theta:
-        res["theta"] = theta
-    if return_moments:
-        res["logit_mean"], res["logit_var"] = to_caller_order(mean, order), to_caller_order(var, order)
-    return res
+    return _result(res, order, out_row, score, loss, theta, mean, var)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
