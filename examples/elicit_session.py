@@ -6,6 +6,12 @@ student's posterior alone is refitted -- all rounds of all students in one launc
 the test AUC on the questions still unasked after every round, once per strategy:
 
     python examples/elicit_session.py [questions] [epochs]     (needs an MI355X; vae_amd has no CPU fallback)
+
+With --exact the same questionnaire runs on a 'reg' model of the 0/1 answers (the closed form needs the Gaussian
+likelihood) and every answer is followed by the exact posterior instead of 200 Adam steps
+(`VFM.elicit_field_exact`): the RMSE on the questions still unasked, beside the Adam session's on the same model.
+
+    python examples/elicit_session.py --exact [questions] [epochs]
 """
 import os
 import sys
@@ -17,7 +23,28 @@ from vae_amd.model import VFM
 from vae_amd.data import load_fraction
 
 
+def main_exact(argv):
+    questions = int(argv[0]) if len(argv) > 0 else 15
+    epochs = int(argv[1]) if len(argv) > 1 else 60
+    N, M, X_train, X_test, y_train, y_test = load_fraction(os.path.join(ROOT, "tests", "golden", "fraction"))
+    X_train, X_test = torch.as_tensor(X_train), torch.as_tensor(X_test)
+    y_train, y_test = torch.as_tensor(y_train).float(), torch.as_tensor(y_test).float()
+    torch.manual_seed(42)
+    model = VFM(N, M, embedding_size=5, output="reg", device="cuda")
+    model.fit(X_train, y_train, n_epochs=epochs, batch_size=100000, verbose=False)
+    strategies = ("random", "variance")
+    exact = model.elicitation_curve_field_exact(X_test, y_test, questions, 0, strategies, reset=True, seed=1)
+    adam = model.elicitation_curve_field(X_test, y_test, questions, 0, strategies, n_steps=200, lr=0.05, reset=True, seed=1)
+    print(f"{len(torch.unique(X_test[:, 0]))} students, {len(X_test)} questions in the pool; RMSE exact / Adam(200)")
+    print("asked  " + "  ".join(f"{s:>26}" for s in strategies))
+    for q in range(questions + 1):
+        print(f"{q:5d}  " + "  ".join(f"{exact[s][q]:8.4f} / {adam[s][q]:8.4f} ({exact['n_unasked'][s][q]:5d})"
+                                      for s in strategies))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--exact":
+        return main_exact(sys.argv[2:])
     questions = int(sys.argv[1]) if len(sys.argv) > 1 else 15
     epochs = int(sys.argv[2]) if len(sys.argv) > 2 else 60
     N, M, X_train, X_test, y_train, y_test = load_fraction(os.path.join(ROOT, "tests", "golden", "fraction"))

@@ -67,8 +67,10 @@ StepConsts, DevStep = _gen.StepConsts, _gen.DevStep
 
 # ---- elicitation sessions (include/vfm_elicit.h): constants and the mirror of vfm_elicit_t, field for field
 ELICIT_MAX_ROUNDS = 4096
+# the exact field-form session (vfm_elicit_solve_f32) is declared in the same header
+ELICIT_SOLVE_EXPORTS = ("vfm_elicit_solve_f32", "vfm_elicit_solve_workspace_bytes")
 ELICIT_EXPORTS = ("vfm_elicit_f32", "vfm_elicit_workspace_bytes", "vfm_elicit_field_f32",
-                  "vfm_elicit_field_workspace_bytes")
+                  "vfm_elicit_field_workspace_bytes") + ELICIT_SOLVE_EXPORTS
 
 
 # ---- fused Adam step of the ELBO variants (include/vfm_variant_step.h)
@@ -142,7 +144,30 @@ class ElicitField(_Strict, C.Structure):
         self.struct_size, self.abi_version = C.sizeof(type(self)), ABI_VERSION      # (VFM_STRUCT_INIT)
 
 
-for _c in (Problem, Index, Pipe, Elicit, ElicitField, FoldinSolve):
+class ElicitSolve(_Strict, C.Structure):
+    """`vfm_elicit_solve_t` (tests/test_elicit_exact_cpu.py checks the layout against gcc's)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("abi_version", C.c_uint32),
+        ("U", C.c_int64), ("P", C.c_int64), ("H", C.c_int64), ("T", C.c_int64), ("n_ops", C.c_int64),
+        ("F", C.c_int32), ("d", C.c_int32), ("field", C.c_int32), ("key_col", C.c_int32), ("n_rounds", C.c_int32),
+        ("strategy", C.c_int32), ("flags", C.c_int32), ("reset", C.c_int32), ("write", C.c_int32),
+        ("lds_dim", C.c_int32), ("kl_weight", C.c_float),
+        ("seed", C.c_uint64),
+        ("entities", C.c_void_p), ("pool_ptr", C.c_void_p), ("pool_x", C.c_void_p), ("pool_y", C.c_void_p),
+        ("hist_ptr", C.c_void_p), ("hist_x", C.c_void_p), ("hist_y", C.c_void_p),
+        ("op_x", C.c_void_p), ("pool_op", C.c_void_p), ("hist_op", C.c_void_p),
+        ("entity_params", C.c_void_p), ("bias_params", C.c_void_p), ("scalars", C.c_void_p),
+        ("out_row", C.c_void_p), ("out_score", C.c_void_p), ("out_loss", C.c_void_p), ("out_theta", C.c_void_p),
+        ("out_mean", C.c_void_p), ("out_var", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size, self.abi_version = C.sizeof(type(self)), ABI_VERSION      # (VFM_STRUCT_INIT)
+
+
+for _c in (Problem, Index, Pipe, Elicit, ElicitField, ElicitSolve, FoldinSolve):
     _c._names = frozenset(n for n, _ in _c._fields_)
 
 
@@ -220,6 +245,10 @@ def load():
     lib.vfm_elicit_field_f32.restype = C.c_int
     lib.vfm_elicit_field_workspace_bytes.argtypes = [i64, i64, i32, i32]
     lib.vfm_elicit_field_workspace_bytes.restype = i64
+    lib.vfm_elicit_solve_f32.argtypes = [C.POINTER(ElicitSolve), vp]
+    lib.vfm_elicit_solve_f32.restype = C.c_int
+    lib.vfm_elicit_solve_workspace_bytes.argtypes = [i64, i64, i64, i32, i32]
+    lib.vfm_elicit_solve_workspace_bytes.restype = i64
     lib.vfm_foldin_solve_f32.argtypes = [C.POINTER(FoldinSolve), vp]
     lib.vfm_foldin_solve_f32.restype = C.c_int
     lib.vfm_foldin_solve_workspace_bytes.argtypes = [i64, i64, i32, i32]

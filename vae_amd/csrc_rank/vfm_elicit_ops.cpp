@@ -1,4 +1,5 @@
-// vfm_elicit_ops.cpp -- torch.ops.vfm_hip.{elicit, elicit_workspace_bytes, elicit_field, elicit_field_workspace_bytes}: the TORCH_LIBRARY fragment over
+// vfm_elicit_ops.cpp -- torch.ops.vfm_hip.{elicit, elicit_workspace_bytes, elicit_field, elicit_field_workspace_bytes,
+// elicit_solve, elicit_solve_workspace_bytes}: the TORCH_LIBRARY fragment over
 // include/vfm_elicit.h.  Like vfm_foldin_ops.cpp it only validates tensors, takes the current HIP stream of the tensors'
 // device and forwards raw pointers; all arithmetic is in the HIP kernels.
 #include <ATen/ATen.h>
@@ -184,6 +185,75 @@ void elicit_field(const Tensor& entities, const Tensor& pool_ptr, const Tensor& 
   TORCH_CHECK(rc == 0, "vfm_elicit_field_f32 failed (code ", rc, "): ", vfm_last_error());
 }
 
+int64_t elicit_solve_workspace_bytes(int64_t U, int64_t P, int64_t n_ops, int64_t d, int64_t lds_dim) {
+  const int64_t b = vfm_elicit_solve_workspace_bytes(U, P, n_ops, (int32_t)d, (int32_t)lds_dim);
+  TORCH_CHECK(b >= 0, "vfm_elicit_solve_workspace_bytes: bad arguments");
+  return b;
+}
+
+// the exact field-form session: elicit_field's tensors, the exact fold-in's options in place of Adam's
+void elicit_solve(const Tensor& entities, const Tensor& pool_ptr, const Tensor& pool_x, const Tensor& pool_y,
+                  const optional<Tensor>& hist_ptr, const optional<Tensor>& hist_x, const optional<Tensor>& hist_y,
+                  const Tensor& op_x, const Tensor& pool_op, const optional<Tensor>& hist_op, Tensor entity, Tensor bias,
+                  const Tensor& scalars, Tensor workspace, Tensor out_row, Tensor out_score, Tensor out_loss,
+                  const optional<Tensor>& out_theta, const optional<Tensor>& out_mean, const optional<Tensor>& out_var,
+                  int64_t field, int64_t key_col, int64_t n_rounds, int64_t strategy, int64_t flags, int64_t reset,
+                  int64_t write, int64_t lds_dim, double kl_weight, int64_t seed) {
+  check_session_tensors({{entities, at::kLong, "entities"}, {pool_ptr, at::kLong, "pool_ptr"}, {pool_x, at::kLong, "pool_x"},
+                         {pool_y, at::kFloat, "pool_y"}, {op_x, at::kLong, "op_x"}, {pool_op, at::kLong, "pool_op"}},
+                        entity, bias, scalars, workspace, out_row, out_score, out_loss, n_rounds);
+  TORCH_CHECK(pool_x.dim() == 2 && pool_x.size(1) >= 2 && pool_x.size(1) <= VFM_MAX_FIELDS, "pool_x must be [P, F]");
+  const int64_t U = entities.numel(), P = pool_x.size(0), F = pool_x.size(1), Q = n_rounds;
+  TORCH_CHECK(pool_ptr.numel() == U + 1 && pool_y.numel() == P, "pool_ptr [U + 1], pool_y [P]");
+  TORCH_CHECK(op_x.dim() == 2 && op_x.size(1) == F && pool_op.numel() == P,
+              "op_x must be [n_ops, F], pool_op must hold one operand per pool row");
+  TORCH_CHECK(out_row.numel() >= U * Q && out_score.numel() >= U * Q && out_loss.numel() >= U * Q,
+              "out_row, out_score, out_loss must be [U, Q]");
+  vfm_elicit_solve_t p;
+  VFM_STRUCT_INIT(p);
+  p.U = U; p.P = P; p.T = entity.size(0); p.F = (int32_t)F; p.d = (int32_t)(entity.size(1) / 2);
+  p.field = (int32_t)field; p.key_col = (int32_t)key_col; p.n_rounds = (int32_t)Q; p.strategy = (int32_t)strategy;
+  p.flags = (int32_t)flags; p.reset = (int32_t)reset; p.write = (int32_t)write; p.lds_dim = (int32_t)lds_dim;
+  p.kl_weight = (float)kl_weight; p.seed = (uint64_t)seed;
+  p.entities = entities.data_ptr<int64_t>(); p.pool_ptr = pool_ptr.data_ptr<int64_t>();
+  p.pool_x = pool_x.data_ptr<int64_t>(); p.pool_y = pool_y.data_ptr<float>();
+  p.n_ops = op_x.size(0);
+  p.op_x = op_x.data_ptr<int64_t>(); p.pool_op = pool_op.data_ptr<int64_t>();
+  p.entity_params = entity.data_ptr<float>(); p.bias_params = bias.data_ptr<float>();
+  p.scalars = scalars.data_ptr<float>();
+  p.out_row = out_row.data_ptr<int64_t>(); p.out_score = out_score.data_ptr<float>();
+  p.out_loss = out_loss.data_ptr<float>();
+  if (given(out_theta)) {
+    TORCH_CHECK(dev_tensor(*out_theta, at::kFloat, "out_theta").numel() >= U * Q * (2 * (int64_t)p.d + 2),
+                "out_theta must be [U, Q, 2d + 2]");
+    p.out_theta = out_theta->data_ptr<float>();
+  }
+  if (given(out_mean) || given(out_var)) {
+    TORCH_CHECK(given(out_mean) && given(out_var), "out_mean and out_var: both or neither");
+    TORCH_CHECK(dev_tensor(*out_mean, at::kFloat, "out_mean").numel() >= (Q + 1) * P &&
+                dev_tensor(*out_var, at::kFloat, "out_var").numel() >= (Q + 1) * P,
+                "out_mean, out_var must be [Q + 1, P]");
+    p.out_mean = out_mean->data_ptr<float>();
+    p.out_var = out_var->data_ptr<float>();
+  }
+  if (given(hist_ptr)) {
+    TORCH_CHECK(given(hist_x) && given(hist_y) && given(hist_op), "hist_ptr needs hist_x, hist_y and hist_op");
+    dev_tensor(*hist_ptr, at::kLong, "hist_ptr"); dev_tensor(*hist_x, at::kLong, "hist_x");
+    dev_tensor(*hist_y, at::kFloat, "hist_y"); dev_tensor(*hist_op, at::kLong, "hist_op");
+    TORCH_CHECK(hist_x->dim() == 2 && hist_x->size(1) == F, "hist_x must be [H, F]");
+    p.H = hist_x->size(0);
+    TORCH_CHECK(hist_ptr->numel() == p.U + 1 && hist_y->numel() == p.H && hist_op->numel() == p.H,
+                "hist_ptr [U + 1], hist_y [H], hist_op [H]");
+    p.hist_ptr = hist_ptr->data_ptr<int64_t>(); p.hist_x = hist_x->data_ptr<int64_t>();
+    p.hist_y = hist_y->data_ptr<float>(); p.hist_op = hist_op->data_ptr<int64_t>();
+  }
+  p.workspace = workspace.data_ptr();
+  p.workspace_bytes = workspace.numel();
+  c10::hip::HIPGuard guard(entities.get_device());
+  const int rc = vfm_elicit_solve_f32(&p, (void*)c10::hip::getCurrentHIPStream(entities.get_device()).stream());
+  TORCH_CHECK(rc == 0, "vfm_elicit_solve_f32 failed (code ", rc, "): ", vfm_last_error());
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(vfm_hip, m) {
@@ -203,4 +273,11 @@ TORCH_LIBRARY_FRAGMENT(vfm_hip, m) {
         "int n_rounds, int strategy, int objective, int likelihood, int flags, int n_steps, int n_samples, int reset, "
         "int write, int lds_rows, float lr, float kl_weight, int seed, int t0) -> ()",
         &elicit_field);
+  m.def("elicit_solve_workspace_bytes(int U, int P, int n_ops, int d, int lds_dim) -> int", &elicit_solve_workspace_bytes);
+  m.def("elicit_solve(Tensor entities, Tensor pool_ptr, Tensor pool_x, Tensor pool_y, Tensor? hist_ptr, Tensor? hist_x, "
+        "Tensor? hist_y, Tensor op_x, Tensor pool_op, Tensor? hist_op, Tensor(a!) entity_params, "
+        "Tensor(b!) bias_params, Tensor scalars, Tensor(c!) workspace, Tensor(d!) out_row, Tensor(e!) out_score, "
+        "Tensor(f!) out_loss, Tensor(g!)? out_theta, Tensor(h!)? out_mean, Tensor(i!)? out_var, int field, int key_col, "
+        "int n_rounds, int strategy, int flags, int reset, int write, int lds_dim, float kl_weight, int seed) -> ()",
+        &elicit_solve);
 }

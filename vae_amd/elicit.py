@@ -7,7 +7,8 @@ users inside one kernel ("Elicitation sessions").  It checks the 
 the pool and of the history once (stable sorts: the caller's order is kept within a user) and maps the results back to
 the caller's pool order; the sessions themselves are one HIP launch (plus one operand pass for the closed form)
 through torch.ops.vfm_hip.elicit.  `run_field` is the same for the entities of any one column of a model with any
-number of fields (vfm_elicit_field_f32): full rows, one operand per distinct context.
+number of fields (vfm_elicit_field_f32): full rows, one operand per distinct context.  `run_field_exact` is the field
+form with each round's Adam fit replaced by the exact fold-in's closed-form optimum (vfm_elicit_solve_f32).
 """
 from __future__ import annotations
 
@@ -224,6 +225,66 @@ def run_field(model, pool, y_pool, n_questions, field=0, strategy="variance", hi
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the exact field form: each round's Adam fit replaced by the closed-form optimum (vfm_elicit_solve_f32)
+# ---------------------------------------------------------------------------------------------------------------------
+def check_args_field_exact(model, pool, y_pool, n_questions, field, strategy, history, kl_weight, key_field):
+    """Validate an exact field-form session call (no GPU needed): the exact fold-in's conditions ('reg', kl_weight > 0
+    and finite), then check_args_field's pool and history checks with the closed-form objective."""
+    if model.output != "reg":
+        raise ValueError("the exact session needs a 'reg' model (Gaussian likelihood): the closed form it solves has "
+                         "none for 'class'; use elicit_field")
+    if not float(kl_weight) > 0.0 or not math.isfinite(float(kl_weight)):
+        raise ValueError("kl_weight must be > 0 and finite: the prior term is what makes each system positive definite")
+    if model.F < 2:
+        raise ValueError("elicit_field_exact needs a model with at least two fields")
+    x, y, hx, hy, _, code, field, kf = check_args_field(model, pool, y_pool, n_questions, field, strategy, history, 0,
+                                                        0.0, "closed_form", 1, kl_weight, key_field)
+    return x, y, hx, hy, code, field, kf
+
+
+def run_field_exact(model, pool, y_pool, n_questions, field=0, strategy="variance", history=None, seed=0,
+                    kl_weight=1.0, reset=False, write=False, return_moments=False, return_theta=False, key_field=None,
+                    lds_dim=-1):
+    """The exact sessions of every entity of column `field` of the pool (VFM.elicit_field_exact documents the arguments
+    and the result): run_field's lists and operands, and one call of torch.ops.vfm_hip.elicit_solve."""
+    x, y, hx, hy, code, field, kf = check_args_field_exact(model, pool, y_pool, n_questions, field, strategy, history,
+                                                           kl_weight, key_field)
+    if int(lds_dim) < -1:
+        raise ValueError("lds_dim must be -1 or >= 0")
+    ops._need_cuda(model._flat, "the model's parameters")
+    dev, d, Q = model.device, model.d, int(n_questions)
+    order, ents, ptr = pool_lists(x, field)
+    px, ys = x[order].contiguous(), y[order].contiguous()
+    U, P = ents.numel(), px.shape[0]
+    hptr = hxs = hys = hist_op = None
+    if hx is not None and hx.shape[0]:
+        horder, hptr = history_lists(ents, hx, field)
+        hxs, hys = hx[horder].contiguous(), hy[horder].contiguous()
+    out_row, score, loss, theta, mean, var = _outputs(dev, U, Q, P, d, return_theta, return_moments)
+    res = {"entities": ents}
+    if U:
+        o = _lib.ops()
+        ctx = (px if hxs is None else torch.cat([px, hxs])).clone()     # one operand per DISTINCT context: it is frozen
+        ctx[:, field] = 0
+        op_x, inv = torch.unique(ctx, dim=0, return_inverse=True)
+        inv = inv.reshape(-1)
+        op_x, pool_op = op_x.contiguous(), inv[:P].contiguous()
+        if hxs is not None:
+            hist_op = inv[P:].contiguous()
+        ws = torch.empty(max(o.elicit_solve_workspace_bytes(U, P, op_x.shape[0], d, int(lds_dim)), 1), dtype=torch.uint8,
+                         device=dev)
+        model._fresh_params()
+        ent, bia, scal = model._views(model._flat)
+        o.elicit_solve(ents, ptr, px, ys, hptr, hxs, hys, op_x, pool_op, hist_op, ent, bia, scal, ws, out_row, score,
+                       loss, theta, mean, var, field, kf, Q, code,
+                       ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, int(bool(reset)), int(bool(write)),
+                       int(lds_dim), float(kl_weight), _seed64(seed))
+        if write:
+            model.params_changed()      # (rows written outside the step kernels: derived caches are stale)
+    return _result(res, order, out_row, score, loss, theta, mean, var)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # the curve of quality against questions asked (torch; any device)
 # ---------------------------------------------------------------------------------------------------------------------
 def asked_round(rows, P):
@@ -264,7 +325,7 @@ def metric(output, mean, var, y):
 def curve(model, pool, y_pool, n_questions, strategies=("mean", "random", "variance"), session=None, **kw):
     """VFM.elicitation_curve: {strategy: [metric before round 0, .., metric after round Q - 1]} on the rows still
     unasked, plus "n_unasked": {strategy: [Q + 1] ints}.  The model is left untouched.  session: the runner (`run`, or
-    `run_field` for the field form)."""
+    `run_field` for the field form, `run_field_exact` for the exact one)."""
     session = run if session is None else session
     for key in ("write", "return_moments", "return_theta"):
         if key in kw:

@@ -1297,6 +1297,34 @@ class VFM(nn.Module):
         return elicit.curve(self, pool, y_pool, n_questions, strategies, session=elicit.run_field, field=field, **kw)
 
     @torch.no_grad()
+    def elicit_field_exact(self, pool, y_pool, n_questions: int, field: int = 0, strategy: str = "variance",
+                           history=None, seed: int = 0, kl_weight: float = 1.0, reset: bool = False, write: bool = False,
+                           return_moments: bool = False, return_theta: bool = False, key_field: Optional[int] = None):
+        """elicit_field with each round's Adam fit replaced by the exact posterior: n_questions rounds of
+        select_next_questions_field(n=1) followed by fold_in_exact(field=field) of the answering respondent, bitwise
+        what that loop computes, for every respondent in one launch (include/vfm_elicit.h: vfm_elicit_solve_f32;
+        DESIGN.md §4 "Exact sessions").  No n_steps, lr or objective: after every answer the respondent's posterior is
+        the global optimum of L_e on the history followed by the rows asked so far, so each next question is chosen
+        from the optimum of the session's own objective.
+
+        'reg' models only, kl_weight > 0, F >= 2 (else ValueError, before anything needs a GPU).  pool, y_pool, history,
+        field, strategy, seed, key_field, write, return_moments, return_theta: as elicit_field.  reset=True scores round
+        0 from the prior instead of the respondents' rows; the optimum itself does not depend on the current rows.
+        Returns elicit_field's dict; loss [U, Q] is fold_in_exact's loss after each round."""
+        from . import elicit
+        return elicit.run_field_exact(self, pool, y_pool, n_questions, field, strategy, history, seed, kl_weight, reset,
+                                      write, return_moments, return_theta, key_field)
+
+    @torch.no_grad()
+    def elicitation_curve_field_exact(self, pool, y_pool, n_questions: int, field: int = 0,
+                                      strategies=("random", "variance"), **kw):
+        """elicitation_curve_field over elicit_field_exact sessions ('reg' models: the RMSE of the mean on the rows
+        still unasked before each round).  kw: elicit_field_exact's other options.  Returns {strategy: [Q + 1 floats],
+        "n_unasked": {strategy: [Q + 1 ints]}}.  The model is left untouched."""
+        from . import elicit
+        return elicit.curve(self, pool, y_pool, n_questions, strategies, session=elicit.run_field_exact, field=field, **kw)
+
+    @torch.no_grad()
     def evaluate(self, X_test, y_test):
         """Test metrics of vfm-torch.py:410-422."""
         out = self.predict(X_test)
