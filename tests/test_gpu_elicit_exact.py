@@ -8,7 +8,9 @@ the curve.
 
 Bounds of the restatement test: those of test_gpu_foldin_exact.py for fold_in_exact against solve_fp64 (rel_err <= 1e-4
 for the parameters, <= 1e-5 for the loss against objective_fp64 at the returned parameters, cond(H) <= 1e3 asserted
-first): the arithmetic is the same."""
+first): the arithmetic is the same.  The cond(H) assertion separates the kernel from the conditioning for the primal
+form only: the dual form (n <= d rows) factors K = I / prec + U D^-1 U^T, whose conditioning is cond(K);
+test_gpu_solve_edges.py asserts that one and runs sessions across the solver's storage and width edges."""
 import contextlib
 
 import numpy as np

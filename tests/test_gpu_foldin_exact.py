@@ -6,7 +6,9 @@ independence of the other entities; the lazy / look-ahead step forms; a 5,000-ro
 
 Bounds: rel_err <= 1e-4 for the rows and <= 1e-5 for the loss, the two bounds test_gpu_foldin.py uses for trajectories
 and for the objective; every comparison asserts cond(H) <= 1e3 of the oracle first, so that the bound tests the kernel
-(fp64 operands, sums and factorisation, fp32 results: about 6e-8) and not the conditioning."""
+(fp64 operands, sums and factorisation, fp32 results: about 6e-8) and not the conditioning.  That holds for the primal
+form: an entity with n <= d rows is solved in the dual form, whose conditioning is that of K = I / prec + U D^-1 U^T, not
+of H; test_gpu_solve_edges.py asserts cond(K) for those and tests the dual path where cond(K) is large."""
 import ctypes as C
 import functools
 
