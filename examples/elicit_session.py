@@ -12,6 +12,13 @@ likelihood) and every answer is followed by the exact posterior instead of 200 A
 (`VFM.elicit_field_exact`): the RMSE on the questions still unasked, beside the Adam session's on the same model.
 
     python examples/elicit_session.py --exact [questions] [epochs]
+
+With --ranking the 'reg' model's exact sessions are also judged as a recommender: beside the RMSE curve, the NDCG@10 of
+each student's correctly answered held-out questions in the ranking of all questions under the student's posterior of
+every round (`VFM.elicitation_ranking_curve_field`: the posteriors stay outside the model, one launch per strategy).
+Every student's test rows are split in two: the first half is the pool of questions, the second half is held out.
+
+    python examples/elicit_session.py --ranking [questions] [epochs]
 """
 import os
 import sys
@@ -42,9 +49,37 @@ def main_exact(argv):
                                       for s in strategies))
 
 
+def main_ranking(argv):
+    questions = int(argv[0]) if len(argv) > 0 else 10
+    epochs = int(argv[1]) if len(argv) > 1 else 60
+    N, M, X_train, X_test, y_train, y_test = load_fraction(os.path.join(ROOT, "tests", "golden", "fraction"))
+    X_train, X_test = torch.as_tensor(X_train), torch.as_tensor(X_test)
+    y_train, y_test = torch.as_tensor(y_train).float(), torch.as_tensor(y_test).float()
+    torch.manual_seed(42)
+    model = VFM(N, M, embedding_size=5, output="reg", device="cuda")
+    model.fit(X_train, y_train, n_epochs=epochs, batch_size=100000, verbose=False)
+    # per student: the even test rows are asked about, the odd ones are held out for the ranking
+    order = torch.sort(X_test[:, 0], stable=True).indices
+    nth = torch.arange(len(order)) - torch.searchsorted(X_test[order, 0].contiguous(), X_test[order, 0].contiguous())
+    ask, held = order[nth % 2 == 0], order[nth % 2 == 1]
+    strategies = ("random", "variance")
+    kw = dict(reset=True, seed=1)
+    rmse = model.elicitation_curve_field_exact(X_test[ask], y_test[ask], questions, 0, strategies, **kw)
+    ndcg = model.elicitation_ranking_curve_field(X_test[ask], y_test[ask], questions, 0, X_test[held], y_test[held], 1,
+                                                 ks=(10,), strategies=strategies, exact=True, threshold=0.5,
+                                                 ineligible="drop", **kw)
+    print(f"{len(torch.unique(X_test[ask, 0]))} students, {len(ask)} questions in the pool, {len(held)} held out, "
+          f"{ndcg['n_queries']} ranking queries per strategy; RMSE on the unasked / NDCG@10 of the held-out")
+    print("asked  " + "  ".join(f"{s:>19}" for s in strategies))
+    for q in range(questions + 1):
+        print(f"{q:5d}  " + "  ".join(f"{rmse[s][q]:8.4f} / {ndcg[s]['ndcg@10'][q]:8.4f}" for s in strategies))
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--exact":
         return main_exact(sys.argv[2:])
+    if len(sys.argv) > 1 and sys.argv[1] == "--ranking":
+        return main_ranking(sys.argv[2:])
     questions = int(sys.argv[1]) if len(sys.argv) > 1 else 15
     epochs = int(sys.argv[2]) if len(sys.argv) > 2 else 60
     N, M, X_train, X_test, y_train, y_test = load_fraction(os.path.join(ROOT, "tests", "golden", "fraction"))

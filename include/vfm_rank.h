@@ -169,6 +169,46 @@ int vfm_rank_heldout_field_f32(int64_t Q, const int64_t* ctx, int32_t field, con
                                int64_t* out_rank, int64_t* out_rank_neg, int64_t* out_n_eligible, int64_t* out_n_neg,
                                void* stream);
 
+/* ---- The field form under supplied posteriors --------------------------------------------------------------------------
+ * The three entry points above with the parameters of ONE context column taken from the caller instead of the tables: a
+ * posterior held outside the model (a session's theta, a what-if, a cold-start respondent) is ranked without writing it
+ * into the tables.  Each takes its table form's arguments plus
+ *   post_field  the context column whose parameters are supplied: 0 <= post_field < F, post_field != field;
+ *   post        [Q, 2d + 2] fp32 ([B, 2d + 2] for the moments), one row per query: [mu (d) | s (d) | mu_w | s_w], s and
+ *               s_w the raw stored values (the link of `flags` is applied as for a table row) -- a row of the theta a
+ *               session of vfm_elicit.h returns.
+ * Query q is the context ctx[q] with the parameters of column post_field taken from post[q].  Every output is bit for
+ * bit what the table form returns for query q from tables in which the entity and bias rows of id ctx[q, post_field] hold
+ * post[q]: for every strategy, both links, any n_splits, grid and stream, and whatever the other queries of the call are
+ * (two queries may carry the same id with different rows: each is its own query).  The id in column post_field keeps
+ * its other roles -- it must lie in [0, T) (else a NaN query), it is what exclusion lists and qkey refer to -- but its
+ * table rows are never read.  The operand arithmetic and its rounding are those defined above; only the source of one
+ * column's row differs.
+ * Workspaces: the layouts do not change; vfm_rank_field_workspace_bytes and vfm_rank_eval_field_workspace_bytes serve
+ * these calls.  Errors: everything the table forms reject; post_field out of range or equal to field; post == NULL
+ * with Q > 0 (B > 0).  Q == 0 (B == 0): returns 0, nothing is launched. */
+int vfm_field_moments_post_f32(int64_t B, int32_t F, int32_t d, int64_t T, int32_t id_bits, int32_t flags, const void* x,
+                               int32_t field, int32_t post_field, const float* post, const float* entity_params,
+                               const float* bias_params, const float* scalars, int32_t strategy, uint64_t seed,
+                               const int64_t* qkey, float* logit_mean, float* logit_var, float* score, void* stream);
+
+int vfm_rank_field_post_f32(int64_t Q, const int64_t* ctx, int32_t field, int32_t post_field, const float* post,
+                            const int64_t* qkey, int64_t n_cand, const int64_t* cand, int64_t cand_lo, int64_t T,
+                            int32_t F, int32_t d, int32_t k, int32_t strategy, int32_t flags, uint64_t seed,
+                            int32_t n_splits, const int64_t* excl_ptr, const int64_t* excl_items, int64_t n_excl,
+                            const float* entity_params, const float* bias_params, const float* scalars, void* workspace,
+                            int64_t workspace_bytes, int64_t* out_items, float* out_score, float* out_mean,
+                            float* out_var, void* stream);
+
+int vfm_rank_heldout_field_post_f32(int64_t Q, const int64_t* ctx, int32_t field, int32_t post_field, const float* post,
+                                    const int64_t* qkey, int64_t n_cand, const int64_t* cand, int64_t cand_lo, int64_t T,
+                                    int32_t F, int32_t d, int32_t strategy, int32_t flags, uint64_t seed,
+                                    int32_t n_splits, const int64_t* excl_ptr, const int64_t* excl_items, int64_t n_excl,
+                                    const int64_t* pos_ptr, const int64_t* pos_items, int64_t n_pos,
+                                    const float* entity_params, const float* bias_params, const float* scalars,
+                                    void* workspace, int64_t workspace_bytes, int64_t* out_rank, int64_t* out_rank_neg,
+                                    int64_t* out_n_eligible, int64_t* out_n_neg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,10 @@ ELICIT_EXPORTS = ("vfm_elicit_f32", "vfm_elicit_workspace_bytes", "vfm_elicit_fi
                   "vfm_elicit_field_workspace_bytes") + ELICIT_SOLVE_EXPORTS
 
 
+# ---- the field-form ranking under supplied posteriors (include/vfm_rank.h: the *_post_f32 entry points)
+RANK_POST_EXPORTS = ("vfm_field_moments_post_f32", "vfm_rank_field_post_f32", "vfm_rank_heldout_field_post_f32")
+
+
 # ---- fused Adam step of the ELBO variants (include/vfm_variant_step.h)
 VARIANT_STEP_EXPORTS = ("vfm_variant_step_f32", "vfm_variant_step_workspace_bytes")
 
@@ -253,6 +257,15 @@ def load():
     lib.vfm_foldin_solve_f32.restype = C.c_int
     lib.vfm_foldin_solve_workspace_bytes.argtypes = [i64, i64, i32, i32]
     lib.vfm_foldin_solve_workspace_bytes.restype = i64
+    u64 = C.c_uint64
+    lib.vfm_field_moments_post_f32.argtypes = [i64, i32, i32, i64, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, u64,
+                                               vp, vp, vp, vp, vp]
+    lib.vfm_rank_field_post_f32.argtypes = ([i64, vp, i32, i32, vp, vp, i64, vp, i64, i64, i32, i32, i32, i32, i32, u64,
+                                             i32, vp, vp, i64, vp, vp, vp, vp, i64] + [vp] * 5)
+    lib.vfm_rank_heldout_field_post_f32.argtypes = ([i64, vp, i32, i32, vp, vp, i64, vp, i64, i64, i32, i32, i32, i32, u64,
+                                                     i32, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i64] + [vp] * 5)
+    for name in RANK_POST_EXPORTS:
+        getattr(lib, name).restype = C.c_int
     # problem, objective, index, workspace, x, values | entity, bias, inv_occ, scalars, W, priors | eps x3 | state, grow,
     # partials, grad_out | m / v of entity, bias, scalars, priors | lr, beta1, beta2, eps, adam_step, stream
     lib.vfm_variant_step_f32.argtypes = ([PP, i32, C.POINTER(Index)] + [vp] * 24 +

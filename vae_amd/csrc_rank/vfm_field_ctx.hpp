@@ -4,6 +4,10 @@
 // fp32 chains of a (context, candidate) pair.  One definition, so a field-form score is the same bits wherever it is
 // formed.  Every function pins fp contraction off itself (#pragma clang fp contract(off)): the ranking units are
 // compiled with -ffp-contract=off anyway, the session unit with `on` for the fold-in's body.
+//
+// A context column's parameters come from a row-source: TableRows (the table rows of the column's id) or PostRows (the
+// same for every column but one, whose parameters are a supplied posterior row [mu | s | mu_w | s_w]: the *_post_f32
+// entry points of vfm_rank.h).  The arithmetic does not know which: the same sums, in the same column order.
 #pragma once
 
 #include "vfm_rank_tile.hpp"         // link_of, op_mean
@@ -18,14 +22,41 @@ struct CtxCoord {
   double M, A, C, ep, vp;
 };
 
-template <typename ID>
-__device__ __forceinline__ CtxCoord ctx_coord(const ID* xr, int F, int field, int k, int d, bool sp,
-                                              const float* __restrict__ ent) {
+// Row-sources: where column f of a context (entity id `id`) keeps its [mu | s] and [mu_w, s_w].  at(r): the source of
+// query r of a call.
+struct TableRows {
+  const float* __restrict__ ent;
+  const float* __restrict__ bias;
+  __device__ __forceinline__ TableRows at(int64_t) const { return *this; }
+  __device__ __forceinline__ const float* ent_row(int, int64_t id, int d) const { return ent + id * 2 * d; }
+  __device__ __forceinline__ const float* bias_row(int, int64_t id, int) const { return bias + id * 2; }
+};
+
+// Column post_field from the query's row of post [., 2d + 2] = [mu | s | mu_w | s_w] (raw stored values: the link is
+// applied as for a table row); the table rows of that column's id are never read
+struct PostRows {
+  const float* __restrict__ ent;
+  const float* __restrict__ bias;
+  const float* __restrict__ post;
+  int post_field, d;
+  __device__ __forceinline__ PostRows at(int64_t r) const {
+    return PostRows{ent, bias, post + r * (2 * (int64_t)d + 2), post_field, d};
+  }
+  __device__ __forceinline__ const float* ent_row(int f, int64_t id, int dd) const {
+    return f == post_field ? post : ent + id * 2 * dd;
+  }
+  __device__ __forceinline__ const float* bias_row(int f, int64_t id, int dd) const {
+    return f == post_field ? post + 2 * dd : bias + id * 2;
+  }
+};
+
+template <typename ID, typename SRC>
+__device__ __forceinline__ CtxCoord ctx_coord_of(const ID* xr, int F, int field, int k, int d, bool sp, const SRC& src) {
 #pragma clang fp contract(off)
   double s1 = 0., smm = 0., ss = 0., sss = 0., ssm = 0., ssmm = 0.;
   for (int f = 0; f < F; ++f) {
     if (f == field) continue;
-    const float* row = ent + (int64_t)xr[f] * 2 * d;
+    const float* row = src.ent_row(f, (int64_t)xr[f], d);
     const double m = row[k], s = link_of(row[d + k], sp), s2 = s * s;
     s1 += m; smm += m * m; ss += s2; sss += s2 * s2; ssm += s2 * m; ssmm += s2 * (m * m);
   }
@@ -38,6 +69,12 @@ __device__ __forceinline__ CtxCoord ctx_coord(const ID* xr, int F, int field, in
   return c;
 }
 
+template <typename ID>
+__device__ __forceinline__ CtxCoord ctx_coord(const ID* xr, int F, int field, int k, int d, bool sp,
+                                              const float* __restrict__ ent) {
+  return ctx_coord_of(xr, F, field, k, d, sp, TableRows{ent, nullptr});
+}
+
 // The stored (fp32, rounded once) query operands of a coordinate: mean part [M], variance part [A | A + M^2 | C]
 __device__ __forceinline__ float ctx_op_var(const CtxCoord& c, int part) {
 #pragma clang fp contract(off)
@@ -45,20 +82,26 @@ __device__ __forceinline__ float ctx_op_var(const CtxCoord& c, int part) {
 }
 
 // The context's constants before the coordinates are added: (m0 + sum_q mu_w,q, sigma0^2 + sum_q sigma_w,q^2)
-template <typename ID>
-__device__ __forceinline__ void ctx_consts(const ID* xr, int F, int field, bool sp, const float* __restrict__ bias,
-                                           const float* __restrict__ scal, double& cm, double& cv) {
+template <typename ID, typename SRC>
+__device__ __forceinline__ void ctx_consts_of(const ID* xr, int F, int field, int d, bool sp, const SRC& src,
+                                              const float* __restrict__ scal, double& cm, double& cv) {
 #pragma clang fp contract(off)
   const double sg0 = (double)link_of(scal[2], sp);
   cm = (double)scal[1];
   cv = sg0 * sg0;
   for (int f = 0; f < F; ++f) {
     if (f == field) continue;
-    const int64_t e = (int64_t)xr[f];
-    const double sw = (double)link_of(bias[e * 2 + 1], sp);
-    cm += (double)bias[e * 2];
+    const float* b = src.bias_row(f, (int64_t)xr[f], d);
+    const double sw = (double)link_of(b[1], sp);
+    cm += (double)b[0];
     cv += sw * sw;
   }
+}
+
+template <typename ID>
+__device__ __forceinline__ void ctx_consts(const ID* xr, int F, int field, bool sp, const float* __restrict__ bias,
+                                           const float* __restrict__ scal, double& cm, double& cv) {
+  ctx_consts_of(xr, F, field, 0, sp, TableRows{nullptr, bias}, scal, cm, cv);
 }
 
 template <typename ID>

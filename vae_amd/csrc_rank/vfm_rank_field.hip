@@ -1,5 +1,6 @@
 // vfm_rank_field.hip -- ranking one field's catalog for models with any number of fields (include/vfm_rank.h:
-// vfm_field_moments_f32, vfm_rank_field_f32) and its held-out evaluation (vfm_rank_heldout_field_f32).
+// vfm_field_moments_f32, vfm_rank_field_f32), its held-out evaluation (vfm_rank_heldout_field_f32), and the three under
+// supplied posteriors (vfm_*_post_f32: one context column's parameters from a caller's row instead of the tables).
 //
 // With every field of a row but one fixed (the query's context), the row's closed-form moments are linear resp.
 // quadratic in the free entity c (include/vfm_foldin.h):
@@ -20,6 +21,9 @@
 // Compiled with -ffp-contract=off: field_pair_moments' explicit fmaf chains are the MFMA chains of the tile, and the fp64
 // operand arithmetic (ctx_coord) rounds the same in k_field_ctx_prep and k_field_moments, bit for bit.  That arithmetic
 // lives in vfm_field_ctx.hpp, which the field-form elicitation session (vfm_elicit_field.hip) includes as well.
+//
+// The posterior forms differ in the operand formation alone: k_field_ctx_prep and k_field_moments are instantiated for
+// both row-sources of vfm_field_ctx.hpp (TableRows, PostRows).  Everything downstream works from the packed row.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -44,24 +48,24 @@ struct StoredOp {
   __device__ float var_op(int part, int k) const { return row[KA + part * d + k]; }
 };
 
-// A query's operands formed on the fly from the tables (k_field_moments: no workspace)
-template <typename ID>
+// A query's operands formed on the fly from its row-source (k_field_moments: no workspace)
+template <typename ID, typename SRC>
 struct TableOp {
   const ID* xr;
   int F, field, d;
   bool sp;
-  const float* ent;
-  __device__ float mean_op(int k) const { return (float)ctx_coord(xr, F, field, k, d, sp, ent).M; }
-  __device__ float var_op(int part, int k) const { return ctx_op_var(ctx_coord(xr, F, field, k, d, sp, ent), part); }
+  SRC src;
+  __device__ float mean_op(int k) const { return (float)ctx_coord_of(xr, F, field, k, d, sp, src).M; }
+  __device__ float var_op(int part, int k) const { return ctx_op_var(ctx_coord_of(xr, F, field, k, d, sp, src), part); }
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
-// k_field_moments: one thread per row x [B, F]; column `field` is the free entity, the others its context.
+// k_field_moments: one thread per row x [B, F]; column `field` is the free entity, the others its context, their
+// parameters from rows.at(r); the candidate's always from the tables.
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename ID>
+template <typename ID, typename SRC>
 __global__ __launch_bounds__(256) void k_field_moments(int64_t B, int F, int field, int d, int64_t T, bool sp,
-                                                       const ID* __restrict__ x, const float* __restrict__ ent,
-                                                       const float* __restrict__ bias, const float* __restrict__ scal,
+                                                       const ID* __restrict__ x, SRC rows, const float* __restrict__ scal,
                                                        int strat, uint64_t seed, const int64_t* __restrict__ qkey,
                                                        float* __restrict__ out_m, float* __restrict__ out_v,
                                                        float* __restrict__ out_s) {
@@ -71,15 +75,16 @@ __global__ __launch_bounds__(256) void k_field_moments(int64_t B, int F, int fie
   const int64_t c = (int64_t)xr[field];
   float mean = __builtin_nanf(""), var = __builtin_nanf(""), sc = __builtin_nanf("");
   if (ctx_valid(xr, F, field, T) && c >= 0 && c < T) {
+    const SRC src = rows.at(r);
     double cm, cv;
-    ctx_consts(xr, F, field, sp, bias, scal, cm, cv);
+    ctx_consts_of(xr, F, field, d, sp, src, scal, cm, cv);
     for (int k = 0; k < d; ++k) {                 // (in k order, as the prep's ordered lane sum)
-      const CtxCoord cc = ctx_coord(xr, F, field, k, d, sp, ent);
+      const CtxCoord cc = ctx_coord_of(xr, F, field, k, d, sp, src);
       cm += cc.ep;
       cv += cc.vp;
     }
-    field_pair_moments(TableOp<ID>{xr, F, field, d, sp, ent}, ent + c * 2 * d, bias + c * 2, (float)cm, (float)cv, d, sp,
-                       mean, var);
+    field_pair_moments(TableOp<ID, SRC>{xr, F, field, d, sp, src}, rows.ent + c * 2 * d, rows.bias + c * 2, (float)cm,
+                       (float)cv, d, sp, mean, var);
     sc = strat == VFM_RANK_RANDOM ? philox_uniform(seed, qkey ? qkey[r] : r, c) : score_of(strat, mean, var);
   }
   out_m[r] = mean;
@@ -91,12 +96,14 @@ __global__ __launch_bounds__(256) void k_field_moments(int64_t B, int F, int fie
 // k_field_ctx_prep: a wave per query row (rows past Q: zero padding), lanes over coordinates, so every gather of a
 // context entity's 8d bytes is coalesced.  Writes the packed row [M .. 0 | A | A + M^2 | C .. 0], the constants
 // (c_mean, c_var) -- the coordinates' E P and Var P added in k order: an ordered sum over the lanes of each chunk of 64 --
-// and, without caller keys, the query's position as its Philox key.  A context id outside [0, T): a NaN row.
+// and, without caller keys, the query's position as its Philox key.  A context id outside [0, T): a NaN row.  The
+// columns' parameters come from rows.at(r): with PostRows the lanes read the query's posterior row as they read a table
+// row, 4 bytes per lane and coordinate, contiguous.
 // ---------------------------------------------------------------------------------------------------------------------
+template <typename SRC>
 __global__ __launch_bounds__(PREP_BLOCK) void k_field_ctx_prep(int64_t Q_pad, int64_t Q, const int64_t* __restrict__ ctx,
                                                                int F, int field, int64_t T, int Kp, int KA, int KB,
-                                                               int d, bool sp, const float* __restrict__ ent,
-                                                               const float* __restrict__ bias,
+                                                               int d, bool sp, SRC rows,
                                                                const float* __restrict__ scal, float* __restrict__ op,
                                                                float* __restrict__ con, int64_t* __restrict__ key_out) {
   const int lane = threadIdx.x & (WAVE - 1);
@@ -111,13 +118,14 @@ __global__ __launch_bounds__(PREP_BLOCK) void k_field_ctx_prep(int64_t Q_pad, in
     for (int k = lane; k < Kp; k += WAVE) row[k] = fill;
     if (lane < 2) con[r * 2 + lane] = fill;
   } else {
+    const SRC src = rows.at(r);
     double cm, cv;
-    ctx_consts(xr, F, field, sp, bias, scal, cm, cv);
+    ctx_consts_of(xr, F, field, d, sp, src, scal, cm, cv);
     for (int k0 = 0; k0 < d; k0 += WAVE) {
       const int k = k0 + lane;
       CtxCoord cc = {0., 0., 0., 0., 0.};
       if (k < d) {
-        cc = ctx_coord(xr, F, field, k, d, sp, ent);
+        cc = ctx_coord_of(xr, F, field, k, d, sp, src);
         row[k] = (float)cc.M;
         row[KA + k] = ctx_op_var(cc, 0);
         row[KA + d + k] = ctx_op_var(cc, 1);
@@ -272,15 +280,22 @@ FieldEvalLayout field_eval_layout_of(int64_t Q, int64_t n_cand, int64_t n_pos, i
 
 // k_field_ctx_prep and k_field_cand_prep into the operand blocks of L.  VFM_RANK_RANDOM: no tile runs, so the candidates
 // are never packed; the contexts only where their position keys are needed (ctx_rows false: the caller reads neither the
-// packed rows nor, with keys of its own, the position keys)
+// packed rows nor, with keys of its own, the position keys).  post: NULL for the table form, else the queries'
+// posterior rows of column post_field.
 int launch_field_prep(const FieldOps& L, char* ws, int64_t Q, const int64_t* ctx, int F, int field, const int64_t* qkey,
                       int64_t n_cand, const int64_t* cand, int64_t cand_lo, int64_t T, int d, bool sp, int strategy,
-                      bool ctx_rows, const float* ent, const float* bias, const float* scal, hipStream_t st) {
+                      bool ctx_rows, const float* ent, const float* bias, const float* scal, int post_field,
+                      const float* post, hipStream_t st) {
   if (ctx_rows || !qkey) {
-    hipLaunchKernelGGL(k_field_ctx_prep, dim3((unsigned)((L.U_pad + PREP_BLOCK / WAVE - 1) / (PREP_BLOCK / WAVE))),
-                       dim3(PREP_BLOCK), 0, st, L.U_pad, Q, ctx, F, field, T, L.Kp, L.KA, L.KB, d, sp, ent, bias, scal,
-                       (float*)(ws + L.off_uop), (float*)(ws + L.off_ucon),
-                       qkey ? (int64_t*)nullptr : (int64_t*)(ws + L.off_key));
+    const dim3 grid((unsigned)((L.U_pad + PREP_BLOCK / WAVE - 1) / (PREP_BLOCK / WAVE)));
+    float *uop = (float*)(ws + L.off_uop), *ucon = (float*)(ws + L.off_ucon);
+    int64_t* key_out = qkey ? (int64_t*)nullptr : (int64_t*)(ws + L.off_key);
+    if (post)
+      hipLaunchKernelGGL(k_field_ctx_prep<PostRows>, grid, dim3(PREP_BLOCK), 0, st, L.U_pad, Q, ctx, F, field, T, L.Kp,
+                         L.KA, L.KB, d, sp, PostRows{ent, bias, post, post_field, d}, scal, uop, ucon, key_out);
+    else
+      hipLaunchKernelGGL(k_field_ctx_prep<TableRows>, grid, dim3(PREP_BLOCK), 0, st, L.U_pad, Q, ctx, F, field, T, L.Kp,
+                         L.KA, L.KB, d, sp, TableRows{ent, bias}, scal, uop, ucon, key_out);
     if (int rc = launch_status("k_field_ctx_prep")) return rc;
   }
   const int64_t ni = L.C_pad * (L.Kp + 2);
@@ -298,50 +313,70 @@ int check_fields(int32_t F, int32_t field) {
   return 0;
 }
 
-}  // namespace
+// The posterior forms' own arguments: the supplied column is a context column
+int check_post_field(int32_t F, int32_t field, int32_t post_field) {
+  if (post_field < 0 || post_field >= F) return vfm::fail(VFM_E_INVALID, "post_field out of range [0,F)");
+  if (post_field == field)
+    return vfm::fail(VFM_E_INVALID, "post_field must differ from field: the posterior is a context column's");
+  return 0;
+}
 
-extern "C" {
+template <typename ID, typename SRC>
+void launch_field_moments(int64_t B, int F, int field, int d, int64_t T, bool sp, const void* x, SRC rows,
+                          const float* scal, int strategy, uint64_t seed, const int64_t* qkey, float* m, float* v,
+                          float* s, hipStream_t st) {
+  hipLaunchKernelGGL((k_field_moments<ID, SRC>), dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, B, F, field, d, T,
+                     sp, (const ID*)x, rows, scal, strategy, seed, qkey, m, v, s);
+}
 
-int vfm_field_moments_f32(int64_t B, int32_t F, int32_t d, int64_t T, int32_t id_bits, int32_t flags, const void* x,
-                          int32_t field, const float* entity_params, const float* bias_params, const float* scalars,
-                          int32_t strategy, uint64_t seed, const int64_t* qkey, float* logit_mean, float* logit_var,
-                          float* score, void* stream) {
+// vfm_field_moments_f32 (has_post false) and vfm_field_moments_post_f32
+int field_moments_impl(int64_t B, int32_t F, int32_t d, int64_t T, int32_t id_bits, int32_t flags, const void* x,
+                       int32_t field, bool has_post, int32_t post_field, const float* post, const float* entity_params,
+                       const float* bias_params, const float* scalars, int32_t strategy, uint64_t seed,
+                       const int64_t* qkey, float* logit_mean, float* logit_var, float* score, void* stream) {
   if (int rc = check_common(T, d, flags, strategy)) return rc;
   if (int rc = check_fields(F, field)) return rc;
+  if (has_post)
+    if (int rc = check_post_field(F, field, post_field)) return rc;
   if (B < 0) return vfm::fail(VFM_E_INVALID, "B < 0");
   if (id_bits != 32 && id_bits != 64) return vfm::fail(VFM_E_INVALID, "id_bits must be 32 or 64");
   if (B == 0) return 0;
   if (!x || !entity_params || !bias_params || !scalars || !logit_mean || !logit_var)
     return vfm::fail(VFM_E_INVALID, "null pointer");
+  if (has_post && !post) return vfm::fail(VFM_E_INVALID, "null pointer: post");
   const hipStream_t st = (hipStream_t)stream;
   const bool sp = (flags & VFM_FLAG_LINK_SOFTPLUS) != 0;
-  const unsigned nb = (unsigned)((B + 255) / 256);
-  if (id_bits == 64)
-    hipLaunchKernelGGL(k_field_moments<int64_t>, dim3(nb), dim3(256), 0, st, B, F, field, d, T, sp, (const int64_t*)x,
-                       entity_params, bias_params, scalars, strategy, seed, qkey, logit_mean, logit_var, score);
-  else
-    hipLaunchKernelGGL(k_field_moments<int32_t>, dim3(nb), dim3(256), 0, st, B, F, field, d, T, sp, (const int32_t*)x,
-                       entity_params, bias_params, scalars, strategy, seed, qkey, logit_mean, logit_var, score);
+  const TableRows tab{entity_params, bias_params};
+  const PostRows pst{entity_params, bias_params, post, post_field, d};
+  if (id_bits == 64) {
+    if (has_post)
+      launch_field_moments<int64_t>(B, F, field, d, T, sp, x, pst, scalars, strategy, seed, qkey, logit_mean, logit_var,
+                                    score, st);
+    else
+      launch_field_moments<int64_t>(B, F, field, d, T, sp, x, tab, scalars, strategy, seed, qkey, logit_mean, logit_var,
+                                    score, st);
+  } else {
+    if (has_post)
+      launch_field_moments<int32_t>(B, F, field, d, T, sp, x, pst, scalars, strategy, seed, qkey, logit_mean, logit_var,
+                                    score, st);
+    else
+      launch_field_moments<int32_t>(B, F, field, d, T, sp, x, tab, scalars, strategy, seed, qkey, logit_mean, logit_var,
+                                    score, st);
+  }
   return launch_status("k_field_moments");
 }
 
-int64_t vfm_rank_field_workspace_bytes(int64_t Q, int64_t n_cand, int32_t F, int32_t d, int32_t k, int32_t strategy,
-                                       int32_t n_splits) {
-  if (Q < 0 || n_cand < 0 || n_cand >= ((int64_t)1 << 31) || F < 2 || F > VFM_MAX_FIELDS || d < 1 || d > 4096 || k < 1 ||
-      k > VFM_RANK_MAX_K || strategy < VFM_RANK_TOP || strategy > VFM_RANK_RANDOM || n_splits < 0 ||
-      n_splits > VFM_RANK_MAX_SPLITS)
-    return VFM_E_INVALID;
-  return field_layout_of(Q, n_cand, d, k, strategy, n_splits).bytes;
-}
-
-int vfm_rank_field_f32(int64_t Q, const int64_t* ctx, int32_t field, const int64_t* qkey, int64_t n_cand,
-                       const int64_t* cand, int64_t cand_lo, int64_t T, int32_t F, int32_t d, int32_t k,
-                       int32_t strategy, int32_t flags, uint64_t seed, int32_t n_splits, const int64_t* excl_ptr,
-                       const int64_t* excl_items, int64_t n_excl, const float* entity_params, const float* bias_params,
-                       const float* scalars, void* workspace, int64_t workspace_bytes, int64_t* out_items,
-                       float* out_score, float* out_mean, float* out_var, void* stream) {
+// vfm_rank_field_f32 (has_post false) and vfm_rank_field_post_f32
+int rank_field_impl(int64_t Q, const int64_t* ctx, int32_t field, bool has_post, int32_t post_field, const float* post,
+                    const int64_t* qkey, int64_t n_cand, const int64_t* cand, int64_t cand_lo, int64_t T, int32_t F,
+                    int32_t d, int32_t k, int32_t strategy, int32_t flags, uint64_t seed, int32_t n_splits,
+                    const int64_t* excl_ptr, const int64_t* excl_items, int64_t n_excl, const float* entity_params,
+                    const float* bias_params, const float* scalars, void* workspace, int64_t workspace_bytes,
+                    int64_t* out_items, float* out_score, float* out_mean, float* out_var, void* stream) {
   if (int rc = check_common(T, d, flags, strategy)) return rc;
   if (int rc = check_fields(F, field)) return rc;
+  if (has_post)
+    if (int rc = check_post_field(F, field, post_field)) return rc;
   if (k < 1 || k > VFM_RANK_MAX_K) return vfm::fail(VFM_E_INVALID, "k out of range [1,128]");
   if (Q < 0) return vfm::fail(VFM_E_INVALID, "Q < 0");
   if (n_cand < 0 || n_cand >= ((int64_t)1 << 31)) return vfm::fail(VFM_E_INVALID, "n_cand out of range [0,2^31)");
@@ -353,6 +388,7 @@ int vfm_rank_field_f32(int64_t Q, const int64_t* ctx, int32_t field, const int64
   if (!ctx || !entity_params || !bias_params || !scalars || !workspace || !out_items || !out_score || !out_mean ||
       !out_var)
     return vfm::fail(VFM_E_INVALID, "null pointer");
+  if (has_post && !post) return vfm::fail(VFM_E_INVALID, "null pointer: post");
   const FieldLayout L = field_layout_of(Q, n_cand, d, k, strategy, n_splits);
   if (workspace_bytes < L.bytes)
     return vfm::fail(VFM_E_INVALID, "workspace too small (vfm_rank_field_workspace_bytes)");
@@ -365,7 +401,7 @@ int vfm_rank_field_f32(int64_t Q, const int64_t* ctx, int32_t field, const int64
         *icon = (float*)(ws + L.off_icon);
   int64_t* keys = (int64_t*)(ws + L.off_key);
   if (int rc = launch_field_prep(L, ws, Q, ctx, F, field, qkey, n_cand, cand, cand_lo, T, d, sp, strategy, true,
-                                 entity_params, bias_params, scalars, st))
+                                 entity_params, bias_params, scalars, post_field, has_post ? post : nullptr, st))
     return rc;
   vfm::RankScan a;
   a.U = Q; a.n_cand = n_cand; a.item_lo = cand_lo; a.n_excl = excl_ptr ? n_excl : 0;
@@ -381,24 +417,19 @@ int vfm_rank_field_f32(int64_t Q, const int64_t* ctx, int32_t field, const int64
   return launch_status("k_rank_merge");
 }
 
-int64_t vfm_rank_eval_field_workspace_bytes(int64_t Q, int64_t n_cand, int64_t n_pos, int32_t F, int32_t d,
-                                            int32_t strategy, int32_t n_splits) {
-  if (!eval_sizes_ok(Q, n_cand, n_pos) || F < 2 || F > VFM_MAX_FIELDS || d < 1 || d > 4096 ||
-      strategy < VFM_RANK_TOP || strategy > VFM_RANK_RANDOM || n_splits < 0 || n_splits > VFM_RANK_MAX_SPLITS)
-    return VFM_E_INVALID;
-  return field_eval_layout_of(Q, n_cand, n_pos, d, strategy, n_splits).bytes;
-}
-
-int vfm_rank_heldout_field_f32(int64_t Q, const int64_t* ctx, int32_t field, const int64_t* qkey, int64_t n_cand,
-                               const int64_t* cand, int64_t cand_lo, int64_t T, int32_t F, int32_t d, int32_t strategy,
-                               int32_t flags, uint64_t seed, int32_t n_splits, const int64_t* excl_ptr,
-                               const int64_t* excl_items, int64_t n_excl, const int64_t* pos_ptr,
-                               const int64_t* pos_items, int64_t n_pos, const float* entity_params,
-                               const float* bias_params, const float* scalars, void* workspace, int64_t workspace_bytes,
-                               int64_t* out_rank, int64_t* out_rank_neg, int64_t* out_n_eligible, int64_t* out_n_neg,
-                               void* stream) {
+// vfm_rank_heldout_field_f32 (has_post false) and vfm_rank_heldout_field_post_f32
+int rank_heldout_field_impl(int64_t Q, const int64_t* ctx, int32_t field, bool has_post, int32_t post_field,
+                            const float* post, const int64_t* qkey, int64_t n_cand, const int64_t* cand, int64_t cand_lo,
+                            int64_t T, int32_t F, int32_t d, int32_t strategy, int32_t flags, uint64_t seed,
+                            int32_t n_splits, const int64_t* excl_ptr, const int64_t* excl_items, int64_t n_excl,
+                            const int64_t* pos_ptr, const int64_t* pos_items, int64_t n_pos, const float* entity_params,
+                            const float* bias_params, const float* scalars, void* workspace, int64_t workspace_bytes,
+                            int64_t* out_rank, int64_t* out_rank_neg, int64_t* out_n_eligible, int64_t* out_n_neg,
+                            void* stream) {
   if (int rc = check_common(T, d, flags, strategy)) return rc;
   if (int rc = check_fields(F, field)) return rc;
+  if (has_post)
+    if (int rc = check_post_field(F, field, post_field)) return rc;
   if (Q < 0) return vfm::fail(VFM_E_INVALID, "Q < 0");
   if (n_cand < 0 || n_cand >= ((int64_t)1 << 31)) return vfm::fail(VFM_E_INVALID, "n_cand out of range [0,2^31)");
   if (n_pos < 0 || n_pos >= ((int64_t)1 << 40)) return vfm::fail(VFM_E_INVALID, "n_pos out of range [0,2^40)");
@@ -411,6 +442,7 @@ int vfm_rank_heldout_field_f32(int64_t Q, const int64_t* ctx, int32_t field, con
   if (!ctx || !pos_ptr || !entity_params || !bias_params || !scalars || !workspace || !out_n_eligible || !out_n_neg ||
       (n_pos > 0 && (!out_rank || !out_rank_neg)))
     return vfm::fail(VFM_E_INVALID, "null pointer");
+  if (has_post && !post) return vfm::fail(VFM_E_INVALID, "null pointer: post");
   const FieldEvalLayout L = field_eval_layout_of(Q, n_cand, n_pos, d, strategy, n_splits);
   if (workspace_bytes < L.bytes)
     return vfm::fail(VFM_E_INVALID, "workspace too small (vfm_rank_eval_field_workspace_bytes)");
@@ -420,7 +452,8 @@ int vfm_rank_heldout_field_f32(int64_t Q, const int64_t* ctx, int32_t field, con
   const bool sp = (flags & VFM_FLAG_LINK_SOFTPLUS) != 0;
   char* ws = (char*)workspace;
   if (int rc = launch_field_prep(L, ws, Q, ctx, F, field, qkey, n_cand, cand, cand_lo, T, d, sp, strategy,
-                                 strategy != VFM_RANK_RANDOM, entity_params, bias_params, scalars, st))
+                                 strategy != VFM_RANK_RANDOM, entity_params, bias_params, scalars, post_field,
+                                 has_post ? post : nullptr, st))
     return rc;
   vfm::RankEval a;
   a.U = Q; a.n_cand = n_cand; a.item_lo = cand_lo; a.n_excl = excl_ptr ? n_excl : 0; a.n_pos = n_pos;
@@ -440,6 +473,94 @@ int vfm_rank_heldout_field_f32(int64_t Q, const int64_t* ctx, int32_t field, con
     if (int rc = launch_status("k_field_pos_score")) return rc;
   }
   return vfm::launch_rank_eval(a, strategy, (unsigned)(L.U_pad / UT), st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int vfm_field_moments_f32(int64_t B, int32_t F, int32_t d, int64_t T, int32_t id_bits, int32_t flags, const void* x,
+                          int32_t field, const float* entity_params, const float* bias_params, const float* scalars,
+                          int32_t strategy, uint64_t seed, const int64_t* qkey, float* logit_mean, float* logit_var,
+                          float* score, void* stream) {
+  return field_moments_impl(B, F, d, T, id_bits, flags, x, field, false, -1, nullptr, entity_params, bias_params,
+                            scalars, strategy, seed, qkey, logit_mean, logit_var, score, stream);
+}
+
+int vfm_field_moments_post_f32(int64_t B, int32_t F, int32_t d, int64_t T, int32_t id_bits, int32_t flags, const void* x,
+                               int32_t field, int32_t post_field, const float* post, const float* entity_params,
+                               const float* bias_params, const float* scalars, int32_t strategy, uint64_t seed,
+                               const int64_t* qkey, float* logit_mean, float* logit_var, float* score, void* stream) {
+  return field_moments_impl(B, F, d, T, id_bits, flags, x, field, true, post_field, post, entity_params, bias_params,
+                            scalars, strategy, seed, qkey, logit_mean, logit_var, score, stream);
+}
+
+int64_t vfm_rank_field_workspace_bytes(int64_t Q, int64_t n_cand, int32_t F, int32_t d, int32_t k, int32_t strategy,
+                                       int32_t n_splits) {
+  if (Q < 0 || n_cand < 0 || n_cand >= ((int64_t)1 << 31) || F < 2 || F > VFM_MAX_FIELDS || d < 1 || d > 4096 || k < 1 ||
+      k > VFM_RANK_MAX_K || strategy < VFM_RANK_TOP || strategy > VFM_RANK_RANDOM || n_splits < 0 ||
+      n_splits > VFM_RANK_MAX_SPLITS)
+    return VFM_E_INVALID;
+  return field_layout_of(Q, n_cand, d, k, strategy, n_splits).bytes;
+}
+
+int vfm_rank_field_f32(int64_t Q, const int64_t* ctx, int32_t field, const int64_t* qkey, int64_t n_cand,
+                       const int64_t* cand, int64_t cand_lo, int64_t T, int32_t F, int32_t d, int32_t k,
+                       int32_t strategy, int32_t flags, uint64_t seed, int32_t n_splits, const int64_t* excl_ptr,
+                       const int64_t* excl_items, int64_t n_excl, const float* entity_params, const float* bias_params,
+                       const float* scalars, void* workspace, int64_t workspace_bytes, int64_t* out_items,
+                       float* out_score, float* out_mean, float* out_var, void* stream) {
+  return rank_field_impl(Q, ctx, field, false, -1, nullptr, qkey, n_cand, cand, cand_lo, T, F, d, k, strategy, flags,
+                         seed, n_splits, excl_ptr, excl_items, n_excl, entity_params, bias_params, scalars, workspace,
+                         workspace_bytes, out_items, out_score, out_mean, out_var, stream);
+}
+
+int vfm_rank_field_post_f32(int64_t Q, const int64_t* ctx, int32_t field, int32_t post_field, const float* post,
+                            const int64_t* qkey, int64_t n_cand, const int64_t* cand, int64_t cand_lo, int64_t T,
+                            int32_t F, int32_t d, int32_t k, int32_t strategy, int32_t flags, uint64_t seed,
+                            int32_t n_splits, const int64_t* excl_ptr, const int64_t* excl_items, int64_t n_excl,
+                            const float* entity_params, const float* bias_params, const float* scalars, void* workspace,
+                            int64_t workspace_bytes, int64_t* out_items, float* out_score, float* out_mean,
+                            float* out_var, void* stream) {
+  return rank_field_impl(Q, ctx, field, true, post_field, post, qkey, n_cand, cand, cand_lo, T, F, d, k, strategy, flags,
+                         seed, n_splits, excl_ptr, excl_items, n_excl, entity_params, bias_params, scalars, workspace,
+                         workspace_bytes, out_items, out_score, out_mean, out_var, stream);
+}
+
+int64_t vfm_rank_eval_field_workspace_bytes(int64_t Q, int64_t n_cand, int64_t n_pos, int32_t F, int32_t d,
+                                            int32_t strategy, int32_t n_splits) {
+  if (!eval_sizes_ok(Q, n_cand, n_pos) || F < 2 || F > VFM_MAX_FIELDS || d < 1 || d > 4096 ||
+      strategy < VFM_RANK_TOP || strategy > VFM_RANK_RANDOM || n_splits < 0 || n_splits > VFM_RANK_MAX_SPLITS)
+    return VFM_E_INVALID;
+  return field_eval_layout_of(Q, n_cand, n_pos, d, strategy, n_splits).bytes;
+}
+
+int vfm_rank_heldout_field_f32(int64_t Q, const int64_t* ctx, int32_t field, const int64_t* qkey, int64_t n_cand,
+                               const int64_t* cand, int64_t cand_lo, int64_t T, int32_t F, int32_t d, int32_t strategy,
+                               int32_t flags, uint64_t seed, int32_t n_splits, const int64_t* excl_ptr,
+                               const int64_t* excl_items, int64_t n_excl, const int64_t* pos_ptr,
+                               const int64_t* pos_items, int64_t n_pos, const float* entity_params,
+                               const float* bias_params, const float* scalars, void* workspace, int64_t workspace_bytes,
+                               int64_t* out_rank, int64_t* out_rank_neg, int64_t* out_n_eligible, int64_t* out_n_neg,
+                               void* stream) {
+  return rank_heldout_field_impl(Q, ctx, field, false, -1, nullptr, qkey, n_cand, cand, cand_lo, T, F, d, strategy,
+                                 flags, seed, n_splits, excl_ptr, excl_items, n_excl, pos_ptr, pos_items, n_pos,
+                                 entity_params, bias_params, scalars, workspace, workspace_bytes, out_rank, out_rank_neg,
+                                 out_n_eligible, out_n_neg, stream);
+}
+
+int vfm_rank_heldout_field_post_f32(int64_t Q, const int64_t* ctx, int32_t field, int32_t post_field, const float* post,
+                                    const int64_t* qkey, int64_t n_cand, const int64_t* cand, int64_t cand_lo, int64_t T,
+                                    int32_t F, int32_t d, int32_t strategy, int32_t flags, uint64_t seed,
+                                    int32_t n_splits, const int64_t* excl_ptr, const int64_t* excl_items, int64_t n_excl,
+                                    const int64_t* pos_ptr, const int64_t* pos_items, int64_t n_pos,
+                                    const float* entity_params, const float* bias_params, const float* scalars,
+                                    void* workspace, int64_t workspace_bytes, int64_t* out_rank, int64_t* out_rank_neg,
+                                    int64_t* out_n_eligible, int64_t* out_n_neg, void* stream) {
+  return rank_heldout_field_impl(Q, ctx, field, true, post_field, post, qkey, n_cand, cand, cand_lo, T, F, d, strategy,
+                                 flags, seed, n_splits, excl_ptr, excl_items, n_excl, pos_ptr, pos_items, n_pos,
+                                 entity_params, bias_params, scalars, workspace, workspace_bytes, out_rank, out_rank_neg,
+                                 out_n_eligible, out_n_neg, stream);
 }
 
 }  // extern "C"

@@ -345,3 +345,120 @@ def curve(model, pool, y_pool, n_questions, strategies=("mean", "random", "varia
             left[s].append(int(keep.sum()))
     out["n_unasked"] = left
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the ranking curve of a session: held-out ranking metrics under the posteriors of every round, one launch per strategy
+# ---------------------------------------------------------------------------------------------------------------------
+def ranking_curve_plan(ents, rows, pool, hist_x, exclude, X_rel, field, rank_field, match, T):
+    """The host-side bookkeeping of the ranking curve (torch, any device; every tensor int64): which queries, which
+    posterior of which round, which positives and which exclusions.
+
+    ents [U] ascending: the session's respondents (column `field`); rows [U, Q]: the pool rows asked per round (-1 once
+    a respondent has nothing left); pool [P, F]; hist_x [H, F] or None; exclude [R, F] or None; X_rel [B, F]: the
+    relevant test rows (rows of other respondents are left out).  Nc distinct contexts of X_rel (column `rank_field`
+    zeroed, in torch.unique's row order) times the rounds 0 .. Q, round-major: query q Nc + c is context c under its
+    respondent's posterior BEFORE round q.  The exclusions of round q are the rows of `exclude`, of the history and of
+    the pool rows asked (by anyone) before round q, matched to the contexts on the columns `match` as rank_field
+    matches them.
+    Returns dict(contexts [Nc, F], queries [(Q + 1) Nc, F], resp [(Q + 1) Nc] (index into ents), round [(Q + 1) Nc],
+    pos = (query_index, ids), excl = (query_index, ids), n_contexts = Nc)."""
+    from .rank import field_exclusion_csr, field_positive_csr
+    dev = ents.device
+    Q = rows.shape[1]
+    mine = torch.isin(X_rel[:, field], ents)
+    C, pptr, pitems = field_positive_csr(X_rel[mine], rank_field, T)
+    Nc = C.shape[0]
+    resp = torch.searchsorted(ents, C[:, field].contiguous()) if Nc else torch.zeros(0, dtype=torch.int64, device=dev)
+    pc = torch.repeat_interleave(torch.arange(Nc, device=dev), pptr[1:] - pptr[:-1])
+    fixed = [t for t in (exclude, hist_x) if t is not None and t.shape[0]]
+    pos_q, pos_i, ex_q, ex_i = [], [], [], []
+    for q in range(Q + 1):
+        asked = rows[:, :q].reshape(-1)
+        asked = asked[asked >= 0]
+        parts = fixed + ([pool[asked]] if asked.numel() else [])
+        pos_q.append(q * Nc + pc)
+        pos_i.append(pitems)
+        if parts and Nc:
+            eptr, eitems = field_exclusion_csr(C, torch.cat(parts), rank_field, match, T)
+            ex_q.append(q * Nc + torch.repeat_interleave(torch.arange(Nc, device=dev), eptr[1:] - eptr[:-1]))
+            ex_i.append(eitems)
+    empty = torch.zeros(0, dtype=torch.int64, device=dev)
+    cat = lambda v: torch.cat(v) if v else empty
+    return {"contexts": C, "queries": C.repeat(Q + 1, 1), "resp": resp.repeat(Q + 1),
+            "round": torch.repeat_interleave(torch.arange(Q + 1, device=dev), Nc), "pos": (cat(pos_q), cat(pos_i)),
+            "excl": (cat(ex_q), cat(ex_i)), "n_contexts": Nc}
+
+
+def round_posteriors(theta0, theta, resp, rnd):
+    """[n, 2d + 2]: per query the posterior of respondent resp[i] before round rnd[i] -- theta0 [U, 2d + 2] for round 0,
+    theta[:, q - 1] (theta [U, Q, 2d + 2], the session's return_theta) for round q > 0."""
+    if theta.shape[1] == 0:
+        return theta0[resp].contiguous()
+    later = theta[resp, (rnd - 1).clamp(min=0)]
+    return torch.where((rnd == 0)[:, None], theta0[resp], later).contiguous()
+
+
+def ranking_curve(model, pool, y_pool, n_questions, field, X_test, y_test, rank_field, ks=(10,),
+                  strategies=("random", "variance"), exact=False, exclude=None, match_fields=None, threshold=None,
+                  ineligible="raise", **session_kw):
+    """VFM.elicitation_ranking_curve_field (which documents the arguments and the result)."""
+    from . import rank
+    for key in ("write", "return_moments", "return_theta", "strategy"):
+        if key in session_kw:
+            raise ValueError(f"elicitation_ranking_curve_field sets {key} itself")
+    strategies = list(strategies)
+    for s in strategies:
+        strategy_code(s)
+    field = rank._field_arg(model, field)
+    rank_field = rank._field_arg(model, rank_field)
+    if rank_field == field:
+        raise ValueError("rank_field must differ from field: the respondents' column is a context column of the ranking")
+    ks = [int(k) for k in ks]
+    if not ks or any(k <= 0 for k in ks):
+        raise ValueError("ks must be a non-empty list of positive ints")
+    if ineligible not in ("raise", "drop"):
+        raise ValueError(f"ineligible must be 'raise' or 'drop', not {ineligible!r}")
+    match = rank._match_arg(model, rank_field, match_fields)
+    X = torch.as_tensor(X_test)
+    y = torch.as_tensor(y_test).reshape(-1)
+    if X.dim() != 2 or X.shape[1] != model.F or X.shape[0] != y.numel():
+        raise ValueError(f"X_test must be [B, {model.F}] with one y_test value per row")
+    relevant = (y >= (4.0 if threshold is None else float(threshold))) if model.output == "reg" else (y == 1)
+    X_rel = rank._context_rows(model, X[relevant.to(X.device)], "X_test", rank_field, check_field_column=True)
+    ex = rank._context_rows(model, exclude, "exclude", rank_field, check_field_column=True) if exclude is not None else None
+    session = run_field_exact if exact else run_field
+    dev, d = model.device, model.d
+    out = {}
+    n_queries = 0
+    for s in strategies:
+        r = session(model, pool, y_pool, n_questions, field, strategy=s, write=False, return_theta=True, **session_kw)
+        ents, Q = r["entities"], int(n_questions)
+        U = ents.numel()
+        if session_kw.get("reset", False):
+            theta0 = torch.zeros(U, 2 * d + 2, dtype=torch.float32, device=dev)
+            theta0[:, d:2 * d] = foldin.prior_s(model.link)
+            theta0[:, 2 * d + 1] = foldin.prior_s(model.link)
+        else:
+            model._fresh_params()
+            ent, bia, _ = model._views(model._flat)
+            theta0 = torch.cat([ent[ents], bia[ents]], 1)
+        hist = session_kw.get("history")
+        hx = torch.as_tensor(hist[0]).to(dev, torch.int64) if hist is not None else None
+        px = torch.as_tensor(pool).to(dev, torch.int64)
+        plan = ranking_curve_plan(ents, r["rows"], px, hx, ex, X_rel, field, rank_field, match, model.T)
+        Nc = plan["n_contexts"]
+        n_queries = (Q + 1) * Nc
+        post = round_posteriors(theta0, r["theta"], plan["resp"], plan["round"])
+        h = rank.rank_heldout_field_posterior(model, plan["queries"], plan["pos"], post, field, rank_field,
+                                              ineligible=ineligible, query_exclude=plan["excl"])
+        curve_s = {}
+        for q in range(Q + 1):
+            a, b = int(h["ptr"][q * Nc]), int(h["ptr"][(q + 1) * Nc])
+            means, _ = rank.ranking_metrics(h["rank"][a:b], h["rank_neg"][a:b], h["ptr"][q * Nc:(q + 1) * Nc + 1] - a,
+                                            h["n_neg"][q * Nc:(q + 1) * Nc], ks)
+            for key, v in means.items():
+                curve_s.setdefault(key, []).append(v)
+        out[s] = curve_s
+    out["n_queries"] = n_queries
+    return out

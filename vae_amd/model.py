@@ -1160,6 +1160,107 @@ class VFM(nn.Module):
             means["per_query"] = dict(contexts=r["contexts"], **per)
         return means
 
+    # ------------------------------------------------------------------ ranking under supplied posteriors (vae_amd/rank.py)
+    @torch.no_grad()
+    def field_moments_posterior(self, X, theta, post_field: int, field: int, strategy: Optional[str] = None,
+                                seed: int = 0, key_field: Optional[int] = None):
+        """field_moments with the parameters of ONE context column supplied by the caller (include/vfm_rank.h:
+        vfm_field_moments_post_f32): row r of X is scored with the entity of column post_field at theta[r] =
+        [mu (d) | s (d) | mu_w | s_w] (raw stored values, a row of a session's return_theta) instead of its table rows,
+        which are never read.  theta: [B, 2d + 2] float32, one row per row of X; post_field != field.  Bitwise
+        field_moments on a model whose rows of X[r, post_field] hold theta[r]; the model is not modified.  Returns
+        (mean, var, score)."""
+        return rank.field_moments_posterior(self, X, theta, post_field, field, strategy, seed, key_field)
+
+    @torch.no_grad()
+    def rank_field_posterior(self, contexts, theta, post_field: int, field: int, k: int = 10, strategy: str = "top",
+                             candidates=None, exclude=None, match_fields=None, key_field: Optional[int] = None,
+                             seed: int = 0, n_splits: int = 0, query_exclude=None):
+        """rank_field under posteriors held outside the model: "ask five questions, then recommend" without writing
+        the answers into the tables (include/vfm_rank.h: vfm_rank_field_post_f32).  contexts [Q, F],
+        theta [Q, 2d + 2] float32 = [mu | s | mu_w | s_w], one row per context: the parameters of the entity in column
+        post_field (a context column, != field) for that query -- e.g. elicit_field(..., write=False,
+        return_theta=True)["theta"][:, -1].  EVERY ROW IS A QUERY: equal contexts are not merged, since equal ids may
+        carry different posteriors; the outputs are in the caller's row order.  The id in column post_field is still
+        checked, matched by the exclusions and used as the "random" key; its table rows are never read.
+        candidates, exclude, match_fields, key_field, k, strategy, seed, n_splits: as rank_field.  query_exclude:
+        (query_index [R], ids [R]), candidates excluded for single queries (by row index of `contexts`), united with the
+        id-matched ones.  Every output is bitwise rank_field's on a model whose rows of that id hold theta[q]; the model
+        is not modified.  Returns rank_field's dict."""
+        return rank.rank_field_posterior(self, contexts, theta, post_field, field, k, strategy, candidates, exclude,
+                                         match_fields, key_field, seed, n_splits, query_exclude)
+
+    @torch.no_grad()
+    def rank_heldout_field_posterior(self, queries, pos, theta, post_field: int, field: int, exclude=None,
+                                     candidates=None, match_fields=None, key_field: Optional[int] = None,
+                                     strategy: str = "top", seed: int = 0, n_splits: int = 0, ineligible: str = "raise",
+                                     query_exclude=None):
+        """rank_heldout_field under supplied posteriors (vfm_rank_heldout_field_post_f32).  queries [Q, F] contexts
+        (column `field` ignored) and theta [Q, 2d + 2], as rank_field_posterior: every row is a query.  pos =
+        (query_index [P], ids [P]): the held-out positives, each naming its query by row index -- the ids of a row no
+        longer identify a query; duplicates are dropped.  exclude, match_fields, candidates, key_field, strategy, seed,
+        n_splits, ineligible: as rank_heldout_field; query_exclude: as rank_field_posterior.  Returns
+        rank_heldout_field's dict with contexts = the queries as given (column `field` zeroed) and ptr / items /
+        query_index / rank / rank_neg over them; the ranks are bitwise rank_heldout_field's on a model whose rows hold
+        theta[q].  The model is not modified."""
+        return rank.rank_heldout_field_posterior(self, queries, pos, theta, post_field, field, exclude, candidates,
+                                                 match_fields, key_field, strategy, seed, n_splits, ineligible,
+                                                 query_exclude)
+
+    @torch.no_grad()
+    def evaluate_ranking_field_posterior(self, queries, test, y_test, theta, post_field: int, field: int, ks=(10,),
+                                         exclude=None, candidates=None, match_fields=None,
+                                         threshold: Optional[float] = None, per_query: bool = False,
+                                         ineligible: str = "raise", query_exclude=None):
+        """evaluate_ranking_field under supplied posteriors.  queries [Q, F], theta [Q, 2d + 2]: as
+        rank_heldout_field_posterior; test = (query_index [B], ids [B]) the test entities of `field` per query, y_test
+        [B] their labels (relevant: y >= threshold for 'reg', default 4.0; y == 1 for 'class').  Returns
+        evaluate_ranking_field's metrics over the queries with a relevant test entity; with per_query=True also
+        "per_query": {"contexts": [Q, F], metric: [Q] float64}."""
+        ks = [int(k) for k in ks]
+        if not ks or any(k <= 0 for k in ks):
+            raise ValueError("ks must be a non-empty list of positive ints")
+        if not isinstance(test, (tuple, list)) or len(test) != 2:
+            raise ValueError("test must be a pair (query_index [B], ids [B])")
+        qi, ids = torch.as_tensor(test[0]).reshape(-1), torch.as_tensor(test[1]).reshape(-1)
+        y = torch.as_tensor(y_test).reshape(-1)
+        if qi.numel() != ids.numel() or qi.numel() != y.numel():
+            raise ValueError("test must hold one (query index, id) pair per y_test value")
+        if self.output == "reg":
+            relevant = y >= (4.0 if threshold is None else float(threshold))
+        else:
+            relevant = y == 1
+        r = rank.rank_heldout_field_posterior(self, queries, (qi[relevant.to(qi.device)], ids[relevant.to(ids.device)]),
+                                              theta, post_field, field, exclude, candidates, match_fields, None, "top",
+                                              0, 0, ineligible, query_exclude)
+        means, per = rank.ranking_metrics(r["rank"], r["rank_neg"], r["ptr"], r["n_neg"], ks)
+        if per_query:
+            means["per_query"] = dict(contexts=r["contexts"], **per)
+        return means
+
+    @torch.no_grad()
+    def elicitation_ranking_curve_field(self, pool, y_pool, n_questions: int, field: int, X_test, y_test,
+                                        rank_field: int, ks=(10,), strategies=("random", "variance"),
+                                        exact: bool = False, exclude=None, match_fields=None,
+                                        threshold: Optional[float] = None, ineligible: str = "raise", **session_kw):
+        """How good are the recommendations after q questions?  For each strategy one session over the pool --
+        elicit_field, or elicit_field_exact with exact=True, run with write=False, return_theta=True -- and, per round
+        q = 0 .. n_questions, the held-out ranking metrics of the `rank_field` catalog (evaluate_ranking_field's:
+        hit / precision / recall / ndcg @ ks, mrr, auc) under each respondent's posterior BEFORE round q: round 0 the
+        posterior the session scored round 0 from (the table rows, or the prior with reset=True), round q > 0
+        theta[:, q - 1].  field: the respondents' column; rank_field: the ranked column (a two-field model: field the
+        user column, rank_field the item column).  X_test [B, F], y_test [B]: held-out rows; those of the session's
+        respondents are used, a query is a distinct context of a relevant row.  The exclusions of round q are the rows of
+        `exclude`, of the history and of the pool rows asked before round q (a recommender does not recommend what it
+        has just asked about), matched on match_fields as rank_field matches them.  All (Q + 1) x contexts queries of a
+        strategy go through ONE rank_heldout_field_posterior call.  session_kw: the session's other options (history,
+        n_steps, lr, objective, n_samples, seed, kl_weight, reset, key_field).
+        Returns {strategy: {metric: [Q + 1 floats]}, "n_queries": queries ranked per strategy}.  The model is left
+        untouched, bit for bit."""
+        from . import elicit
+        return elicit.ranking_curve(self, pool, y_pool, n_questions, field, X_test, y_test, rank_field, ks, strategies,
+                                    exact, exclude, match_fields, threshold, ineligible, **session_kw)
+
     # ------------------------------------------------------------------ fold-in (vae_amd/foldin.py)
     @torch.no_grad()
     def fold_in(self, X, y, field: int = 0, n_steps: int = 200, lr: float = 0.05, objective: Optional[str] = None,

@@ -556,3 +556,232 @@ def ranking_metrics(rank, rank_neg, ptr, n_neg, ks=(10,)):
         means[key] = float(v[ok].mean()) if bool(ok.any()) else float("nan")
     means["n_users"] = int(has.sum())
     return means, per
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the field form under supplied posteriors (include/vfm_rank.h: the *_post_f32 entry points): one context column's
+# parameters come from the caller's theta rows, not from the model's tables, which are never written
+# ---------------------------------------------------------------------------------------------------------------------
+def _posterior_args(model, theta, post_field, field, n_rows, what="contexts"):
+    """The checks of (theta, post_field) shared by the posterior forms (no GPU needed).  Returns theta [n_rows, 2d + 2]
+    fp32, contiguous, on the model's device."""
+    if isinstance(post_field, bool) or not isinstance(post_field, int) or not 0 <= post_field < model.F:
+        raise ValueError(f"post_field must be an int in [0, {model.F})")
+    if post_field == field:
+        raise ValueError("post_field must differ from field: the posterior is a context column's, the ranked field's "
+                         "parameters are the candidates'")
+    if not isinstance(theta, torch.Tensor):
+        raise ValueError("theta must be a torch tensor [Q, 2d + 2] of dtype float32")
+    if theta.dtype != torch.float32:
+        raise ValueError(f"theta must be float32, not {theta.dtype}")
+    W = 2 * model.d + 2
+    if theta.dim() != 2 or theta.shape[0] != n_rows or theta.shape[1] != W:
+        raise ValueError(f"theta must be [{n_rows}, {W}] = [mu | s | mu_w | s_w], one row per row of {what}, not "
+                         f"{list(theta.shape)}")
+    return theta.to(model.device).contiguous()
+
+
+def _match_arg(model, field, match_fields):
+    ctx_cols = [f for f in range(model.F) if f != field]
+    if match_fields is None:
+        return ctx_cols
+    match = sorted({int(f) for f in match_fields})
+    if any(f not in ctx_cols for f in match):
+        raise ValueError(f"match_fields must be context columns, a subset of {ctx_cols}")
+    return match
+
+
+def _candidates_field(model, candidates, lo, hi):
+    """(cand sorted int64 or None, n_cand) of the field forms' `candidates` argument."""
+    if candidates is None:
+        return None, hi - lo
+    cand = torch.as_tensor(candidates).to(model.device, torch.int64).reshape(-1)
+    if cand.numel() and (int(cand.min()) < lo or int(cand.max()) >= hi):
+        raise ValueError(f"candidate ids must lie in the field's range [{lo}, {hi})")
+    cand = torch.sort(cand).values
+    if cand.numel() > 1 and bool((cand[1:] == cand[:-1]).any()):
+        raise ValueError("duplicate candidates")
+    return cand, cand.numel()
+
+
+def _query_pairs(model, pairs, name, Q, lo, hi):
+    """(query_index [R], ids [R]) int64 on the model's device: query indices in [0, Q), ids in the ranked field's range."""
+    if not isinstance(pairs, (tuple, list)) or len(pairs) != 2:
+        raise ValueError(f"{name} must be a pair (query_index [R], ids [R])")
+    qi, ids = torch.as_tensor(pairs[0]), torch.as_tensor(pairs[1])
+    for t in (qi, ids):
+        if t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise ValueError(f"{name} must hold integers")
+    qi, ids = qi.to(model.device, torch.int64).reshape(-1), ids.to(model.device, torch.int64).reshape(-1)
+    if qi.numel() != ids.numel():
+        raise ValueError(f"{name}: one id per query index")
+    if qi.numel():
+        if int(qi.min()) < 0 or int(qi.max()) >= Q:
+            raise ValueError(f"{name}: query indices must lie in [0, {Q})")
+        if int(ids.min()) < lo or int(ids.max()) >= hi:
+            raise ValueError(f"{name}: ids must lie in the field's range [{lo}, {hi})")
+    return qi, ids
+
+
+def query_csr(qi: torch.Tensor, ids: torch.Tensor, Q: int, T: int):
+    """CSR over the queries 0 .. Q - 1 of the (query index, id) pairs: (ptr [Q+1] int64, items [n] int64 ascending per
+    query, duplicates dropped)."""
+    return exclusion_csr(torch.arange(Q, device=qi.device), torch.stack([qi, ids], 1), T)
+
+
+def posterior_exclusions(model, ctx, field, match, exclude, query_exclude, lo, hi):
+    """The exclusion CSR of the posterior forms over the queries ctx [Q, F] (every row a query): the rows of `exclude`
+    matched on ids as rank_field matches them, united with the per-query pairs `query_exclude`.  (None, None) without
+    either."""
+    Q, T = ctx.shape[0], model.T
+    qi = ids = None
+    if exclude is not None:
+        ptr, items = field_exclusion_csr(ctx, exclude, field, match, T)
+        if query_exclude is None:
+            return ptr, items
+        qi = torch.repeat_interleave(torch.arange(Q, device=ctx.device), ptr[1:] - ptr[:-1])
+        ids = items
+    if query_exclude is not None:
+        qi = query_exclude[0] if qi is None else torch.cat([qi, query_exclude[0]])
+        ids = query_exclude[1] if ids is None else torch.cat([ids, query_exclude[1]])
+    if qi is None:
+        return None, None
+    return query_csr(qi, ids, Q, T)
+
+
+def field_moments_posterior(model, X, theta, post_field, field, strategy: Optional[str] = None, seed: int = 0,
+                            key_field=None):
+    """field_moments with column post_field's parameters taken from theta (model.field_moments_posterior documents the
+    arguments)."""
+    field = _field_arg(model, field)
+    kf = _key_field(model, field, key_field)
+    code = strategy_code(strategy) if strategy is not None else 0
+    if strategy == "mean" and model.output != "class":
+        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
+    x = torch.as_tensor(X)
+    if x.dim() != 2 or x.shape[1] != model.F:
+        raise ValueError(f"X must be [B, {model.F}]")
+    post = _posterior_args(model, theta, post_field, field, x.shape[0], "X")
+    ops._need_cuda(model._flat, "the model's parameters")
+    x = x.to(model.device)
+    x = (x if x.dtype in (torch.int32, torch.int64) else x.to(torch.int64)).contiguous()
+    model._fresh_params()
+    ent, bia, scal = model._views(model._flat)
+    B = x.shape[0]
+    m = torch.empty(B, dtype=torch.float32, device=x.device)
+    v = torch.empty_like(m)
+    sc = torch.empty_like(m) if strategy is not None else None
+    qkey = x[:, kf].to(torch.int64).contiguous()
+    _lib.ops().field_moments_post(x, field, post, post_field, qkey, ent, bia, scal, m, v, sc,
+                                  ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, code, _seed64(seed))
+    return m, v, sc
+
+
+def rank_field_posterior(model, contexts, theta, post_field, field, k: int = 10, strategy: str = "top", candidates=None,
+                         exclude=None, match_fields=None, key_field=None, seed: int = 0, n_splits: int = 0,
+                         query_exclude=None):
+    """rank_field with column post_field's parameters taken from theta, every row its own query
+    (model.rank_field_posterior documents the arguments)."""
+    from .foldin import field_range
+    field = _field_arg(model, field)
+    code = strategy_code(strategy)
+    if strategy == "mean" and model.output != "class":
+        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
+    if not 1 <= int(k) <= MAX_K:
+        raise ValueError(f"k must lie in [1, {MAX_K}]")
+    if not 0 <= int(n_splits) <= MAX_SPLITS:
+        raise ValueError(f"n_splits must lie in [0, {MAX_SPLITS}]")
+    k = int(k)
+    kf = _key_field(model, field, key_field)
+    match = _match_arg(model, field, match_fields)
+    dev = model.device
+    lo, hi = field_range(model, field)
+    ctx = _context_rows(model, contexts, "contexts", field).clone()
+    ctx[:, field] = 0                                          # (ignored by the kernels)
+    Q = ctx.shape[0]
+    post = _posterior_args(model, theta, post_field, field, Q)
+    cand, n_cand = _candidates_field(model, candidates, lo, hi)
+    ex = _context_rows(model, exclude, "exclude", field, check_field_column=True) if exclude is not None else None
+    qex = _query_pairs(model, query_exclude, "query_exclude", Q, lo, hi) if query_exclude is not None else None
+    ops._need_cuda(model._flat, "the model's parameters")
+    ptr, ex_items = posterior_exclusions(model, ctx, field, match, ex, qex, lo, hi)
+    model._fresh_params()
+    ent, bia, scal = model._views(model._flat)
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = {"items": torch.empty(Q, k, dtype=torch.int64, device=dev), "score": torch.empty(Q, k, **f32),
+           "logit_mean": torch.empty(Q, k, **f32), "logit_var": torch.empty(Q, k, **f32)}
+    o = _lib.ops()
+    ws = torch.empty(max(o.rank_field_workspace_bytes(Q, n_cand, model.F, model.d, k, code, int(n_splits)), 1),
+                     dtype=torch.uint8, device=dev)
+    o.rank_field_post(ctx.contiguous(), field, post, post_field, ctx[:, kf].contiguous(), cand, n_cand, lo, ptr,
+                      ex_items, ent, bia, scal, ws, out["items"], out["score"], out["logit_mean"], out["logit_var"], k,
+                      code, ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, _seed64(seed), int(n_splits))
+    return out
+
+
+def rank_heldout_field_posterior(model, queries, pos, theta, post_field, field, exclude=None, candidates=None,
+                                 match_fields=None, key_field=None, strategy: str = "top", seed: int = 0,
+                                 n_splits: int = 0, ineligible: str = "raise", query_exclude=None):
+    """rank_heldout_field with column post_field's parameters taken from theta: the queries are given, the positives
+    name their query by index (model.rank_heldout_field_posterior documents the arguments and outputs)."""
+    from .foldin import field_range
+    field = _field_arg(model, field)
+    code = strategy_code(strategy)
+    if strategy == "mean" and model.output != "class":
+        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
+    if not 0 <= int(n_splits) <= MAX_SPLITS:
+        raise ValueError(f"n_splits must lie in [0, {MAX_SPLITS}]")
+    if ineligible not in ("raise", "drop"):
+        raise ValueError(f"ineligible must be 'raise' or 'drop', not {ineligible!r}")
+    kf = _key_field(model, field, key_field)
+    match = _match_arg(model, field, match_fields)
+    dev, T = model.device, model.T
+    lo, hi = field_range(model, field)
+    ctx = _context_rows(model, queries, "queries", field).clone()
+    ctx[:, field] = 0
+    Q = ctx.shape[0]
+    post = _posterior_args(model, theta, post_field, field, Q, "queries")
+    pqi, pids = _query_pairs(model, pos, "pos", Q, lo, hi)
+    cand, n_cand = _candidates_field(model, candidates, lo, hi)
+    ex = _context_rows(model, exclude, "exclude", field, check_field_column=True) if exclude is not None else None
+    qex = _query_pairs(model, query_exclude, "query_exclude", Q, lo, hi) if query_exclude is not None else None
+    ops._need_cuda(model._flat, "the model's parameters")
+    pptr, pitems = query_csr(pqi, pids, Q, T)                  # (ascending per query, duplicates dropped)
+    pq = torch.repeat_interleave(torch.arange(Q, device=dev), pptr[1:] - pptr[:-1])
+    # eligibility (torch, on the device): every positive is a candidate and not excluded
+    bad = torch.zeros(pitems.numel(), dtype=torch.bool, device=dev)
+    if cand is not None:
+        j = torch.searchsorted(cand, pitems).clamp_(max=max(n_cand - 1, 0))
+        bad |= (cand[j] != pitems) if n_cand > 0 else torch.ones_like(bad)
+    eptr, ex_items = posterior_exclusions(model, ctx, field, match, ex, qex, lo, hi)
+    if eptr is not None:
+        ekey = torch.repeat_interleave(torch.arange(Q, device=dev), eptr[1:] - eptr[:-1]) * T + ex_items   # sorted
+        if ekey.numel():
+            pkey = pq * T + pitems
+            j = torch.searchsorted(ekey, pkey).clamp_(max=ekey.numel() - 1)
+            bad |= ekey[j] == pkey
+    n_dropped = int(bad.sum())
+    if n_dropped:
+        if ineligible == "raise":
+            j = int(torch.nonzero(bad)[0, 0])
+            raise ValueError(f"positive {int(pitems[j])} of query {int(pq[j])} is not an eligible candidate of its query "
+                             "(excluded, or outside `candidates`); ineligible='drop' removes such positives")
+        keep = ~bad
+        pitems, pq = pitems[keep].contiguous(), pq[keep]
+        pptr = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(torch.bincount(pq, minlength=Q), 0, out=pptr[1:])
+    model._fresh_params()
+    ent, bia, scal = model._views(model._flat)
+    n_pos = pitems.numel()
+    i64 = dict(dtype=torch.int64, device=dev)
+    out = {"contexts": ctx, "ptr": pptr, "items": pitems, "query_index": pq, "rank": torch.empty(n_pos, **i64),
+           "rank_neg": torch.empty(n_pos, **i64), "n_eligible": torch.empty(Q, **i64), "n_neg": torch.empty(Q, **i64),
+           "n_dropped": n_dropped}
+    o = _lib.ops()
+    ws = torch.empty(max(o.rank_eval_field_workspace_bytes(Q, n_cand, n_pos, model.F, model.d, code, int(n_splits)), 1),
+                     dtype=torch.uint8, device=dev)
+    o.rank_heldout_field_post(ctx.contiguous(), field, post, post_field, ctx[:, kf].contiguous(), cand, n_cand, lo, eptr,
+                              ex_items, pptr, pitems, ent, bia, scal, ws, out["rank"], out["rank_neg"],
+                              out["n_eligible"], out["n_neg"], code,
+                              ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, _seed64(seed), int(n_splits))
+    return out
