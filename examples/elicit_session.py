@@ -19,6 +19,12 @@ every round (`VFM.elicitation_ranking_curve_field`: the posteriors stay outside 
 Every student's test rows are split in two: the first half is the pool of questions, the second half is held out.
 
     python examples/elicit_session.py --ranking [questions] [epochs]
+
+With --design the same split compares which question is asked: the NDCG@10 curves of random / variance / design side
+by side, where "design" (`VFM.elicit_field_design`) asks the question that most reduces the predictive variance over
+the student's held-out questions.
+
+    python examples/elicit_session.py --design [questions] [epochs]
 """
 import os
 import sys
@@ -49,7 +55,7 @@ def main_exact(argv):
                                       for s in strategies))
 
 
-def main_ranking(argv):
+def main_ranking(argv, design=False):
     questions = int(argv[0]) if len(argv) > 0 else 10
     epochs = int(argv[1]) if len(argv) > 1 else 60
     N, M, X_train, X_test, y_train, y_test = load_fraction(os.path.join(ROOT, "tests", "golden", "fraction"))
@@ -62,8 +68,8 @@ def main_ranking(argv):
     order = torch.sort(X_test[:, 0], stable=True).indices
     nth = torch.arange(len(order)) - torch.searchsorted(X_test[order, 0].contiguous(), X_test[order, 0].contiguous())
     ask, held = order[nth % 2 == 0], order[nth % 2 == 1]
-    strategies = ("random", "variance")
-    kw = dict(reset=True, seed=1)
+    strategies = ("random", "variance", "design") if design else ("random", "variance")
+    kw = dict(reset=True, seed=1, targets=X_test[held]) if design else dict(reset=True, seed=1)
     rmse = model.elicitation_curve_field_exact(X_test[ask], y_test[ask], questions, 0, strategies, **kw)
     ndcg = model.elicitation_ranking_curve_field(X_test[ask], y_test[ask], questions, 0, X_test[held], y_test[held], 1,
                                                  ks=(10,), strategies=strategies, exact=True, threshold=0.5,
@@ -78,8 +84,8 @@ def main_ranking(argv):
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--exact":
         return main_exact(sys.argv[2:])
-    if len(sys.argv) > 1 and sys.argv[1] == "--ranking":
-        return main_ranking(sys.argv[2:])
+    if len(sys.argv) > 1 and sys.argv[1] in ("--ranking", "--design"):
+        return main_ranking(sys.argv[2:], design=sys.argv[1] == "--design")
     questions = int(sys.argv[1]) if len(sys.argv) > 1 else 15
     epochs = int(sys.argv[2]) if len(sys.argv) > 2 else 60
     N, M, X_train, X_test, y_train, y_test = load_fraction(os.path.join(ROOT, "tests", "golden", "fraction"))

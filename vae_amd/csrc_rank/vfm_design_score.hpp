@@ -1,0 +1,83 @@
+// vfm_design_score.hpp -- the target-aware question score (include/vfm_design.h) on the device: the two walks that form
+// a respondent's scale sums S and target weights W, and the score of one candidate row.  Used by k_design_score (every
+// pool row's score, one round) and k_elicit_design (the sessions), both in vfm_elicit_design.hip, so a score exists
+// once.  Included inside `namespace vfm { namespace {` of a unit, after vfm_foldin_solve_body.hpp.
+//
+// With the partners frozen the scales of a respondent's optimum do not depend on the answers:
+//   sigma_k^2 = v_k(S_k) = kl / (kl + prec S_k),  S_k = sum_{r in R} (A_rk + M_rk^2);  sigma_w^2 = v_w(n) = kl / (kl + prec n)
+// so the posterior a question q would leave behind is known before it is asked, and with it the drop of the mean over
+// the target contexts J of the part of Var pred_j that the respondent's scales carry:
+//   score(q) = (v_w(n) - v_w(n + 1)) + sum_k W_k (v_k(S_k) - v_k(S_k + a_qk)),  W_k = (1 / |J|) sum_{j in J} a_jk,
+//   a_rk = A_rk + M_rk^2.
+// Everything is fp64 over the unrounded operands of k_foldin_solve_prep (ops64 [n_ops, 3, d] = M | A | C) and rounded
+// to fp32 once.  Orders: S in row order, W in the target list's order, the score from the bias term on in k order.
+// Contraction: S is phase A of solve_body -- the same statement under the same pragma (`on`), so the same bits; W, v
+// and the score are under `off`.
+#pragma once
+
+// v(S) = kl / (kl + prec S): the squared scale of the optimum of a coordinate whose rows sum to S
+__device__ __forceinline__ double design_v(double kl, double prec, double S) {
+#pragma clang fp contract(off)
+  return kl / (kl + prec * S);
+}
+
+// S [d]: thread t forms the coordinates t, t + FB, .. over the n rows of `rows` (op(i): the operand of row i) in row
+// order.  An operand outside [0, n_ops) makes the respondent's sums NaN.  No barrier: the caller publishes S.
+template <class Rows>
+__device__ __forceinline__ void design_walk_S(const double* ops64, int64_t n_ops, int d, const Rows& rows, int64_t n,
+                                              double* S) {
+#pragma clang fp contract(on)
+  const int64_t os = 3 * (int64_t)d;
+  for (int k = threadIdx.x; k < d; k += FB) {
+    double SB = 0.;
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t o = rows.op(i);
+      if (o < 0 || o >= n_ops) { SB += __builtin_nan(""); continue; }
+      const double* op = ops64 + o * os + k;
+      const double M = op[0], A = op[d];
+      SB += A + M * M;                   // (phase A of solve_body, to the letter)
+    }
+    S[k] = SB;
+  }
+}
+
+// W [d]: the mean of a_jk over the nt target operands, in the list's order; an empty list gives 0, a target operand
+// outside [0, n_ops) or of an invalid context (a NaN row of ops64) gives NaN.  No barrier.
+__device__ __forceinline__ void design_walk_W(const double* ops64, int64_t n_ops, int d, const int64_t* tgt_op, int64_t nt,
+                                              double* W) {
+#pragma clang fp contract(off)
+  const int64_t os = 3 * (int64_t)d;
+  const double inv = nt > 0 ? 1.0 / (double)nt : 0.0;
+  for (int k = threadIdx.x; k < d; k += FB) {
+    double s = 0.;
+    for (int64_t j = 0; j < nt; ++j) {
+      const int64_t o = tgt_op[j];
+      if (o < 0 || o >= n_ops) { s += __builtin_nan(""); continue; }
+      const double* op = ops64 + o * os + k;
+      const double M = op[0], A = op[d];
+      const double a = A + M * M;
+      s += a;
+    }
+    W[k] = nt > 0 ? inv * s : 0.0;
+  }
+}
+
+// the score of the candidate whose operand row is opq = ops64 + o * 3 d, for a respondent with n fold rows, sums S,
+// weights W and vS[k] = design_v(kl, prec, S[k])
+__device__ __forceinline__ float design_score(const double* S, const double* W, const double* vS, double n,
+                                              const double* opq, int d, double kl, double prec) {
+#pragma clang fp contract(off)
+  double acc = design_v(kl, prec, n) - design_v(kl, prec, n + 1.0);
+  for (int k = 0; k < d; ++k) {
+    const double M = opq[k], A = opq[d + k];
+    const double a = A + M * M;
+    const double drop = vS[k] - design_v(kl, prec, S[k] + a);
+    acc += W[k] * drop;
+  }
+  return (float)acc;
+}
+
+// the order of the choice: score descending, position ascending (k_elicit_solve's); op < 0: no candidate
+__device__ __forceinline__ bool design_better(float os, long long op, float bs, long long bp) {
+  return op >= 0 && (bp < 0 || os > bs || (os == bs && op < bp));
+}

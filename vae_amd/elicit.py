@@ -322,6 +322,21 @@ def metric(output, mean, var, y):
     return auc(torch.sigmoid(mean / torch.sqrt(1.0 + math.pi / 8.0 * var)), y)
 
 
+def _curve_strategy(s, exact):
+    """A curve's strategy name: rank.STRATEGIES', or "design" (vae_amd/design.py) over the exact sessions."""
+    if not (exact and s == "design"):
+        strategy_code(s)
+
+
+def _session_of(s, session, kw):
+    """(runner, options) of strategy s of a curve: the exact curves route "design" to design.run_field_design, where
+    alone `targets` is an option; everything else is `session` with the caller's options."""
+    if session is run_field_exact:
+        from . import design
+        return design.session_for(s, session, kw)
+    return session, kw
+
+
 def curve(model, pool, y_pool, n_questions, strategies=("mean", "random", "variance"), session=None, **kw):
     """VFM.elicitation_curve: {strategy: [metric before round 0, .., metric after round Q - 1]} on the rows still
     unasked, plus "n_unasked": {strategy: [Q + 1] ints}.  The model is left untouched.  session: the runner (`run`, or
@@ -332,10 +347,11 @@ def curve(model, pool, y_pool, n_questions, strategies=("mean", "random", "varia
             raise ValueError(f"elicitation_curve sets {key} itself")
     strategies = list(strategies)
     for s in strategies:
-        strategy_code(s)
+        _curve_strategy(s, session is run_field_exact)
     out, left = {}, {}
     for s in strategies:
-        r = session(model, pool, y_pool, n_questions, strategy=s, write=False, return_moments=True, **kw)
+        run_s, kw_s = _session_of(s, session, kw)
+        r = run_s(model, pool, y_pool, n_questions, strategy=s, write=False, return_moments=True, **kw_s)
         y = torch.as_tensor(y_pool).to(model.device, torch.float32).reshape(-1)
         when = asked_round(r["rows"], y.numel())
         out[s], left[s] = [], []
@@ -409,7 +425,7 @@ def ranking_curve(model, pool, y_pool, n_questions, field, X_test, y_test, rank_
             raise ValueError(f"elicitation_ranking_curve_field sets {key} itself")
     strategies = list(strategies)
     for s in strategies:
-        strategy_code(s)
+        _curve_strategy(s, bool(exact))
     field = rank._field_arg(model, field)
     rank_field = rank._field_arg(model, rank_field)
     if rank_field == field:
@@ -432,7 +448,8 @@ def ranking_curve(model, pool, y_pool, n_questions, field, X_test, y_test, rank_
     out = {}
     n_queries = 0
     for s in strategies:
-        r = session(model, pool, y_pool, n_questions, field, strategy=s, write=False, return_theta=True, **session_kw)
+        run_s, kw_s = _session_of(s, session, session_kw)
+        r = run_s(model, pool, y_pool, n_questions, field, strategy=s, write=False, return_theta=True, **kw_s)
         ents, Q = r["entities"], int(n_questions)
         U = ents.numel()
         if session_kw.get("reset", False):

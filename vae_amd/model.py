@@ -1254,7 +1254,8 @@ class VFM(nn.Module):
         `exclude`, of the history and of the pool rows asked before round q (a recommender does not recommend what it
         has just asked about), matched on match_fields as rank_field matches them.  All (Q + 1) x contexts queries of a
         strategy go through ONE rank_heldout_field_posterior call.  session_kw: the session's other options (history,
-        n_steps, lr, objective, n_samples, seed, kl_weight, reset, key_field).
+        n_steps, lr, objective, n_samples, seed, kl_weight, reset, key_field).  With exact=True the name "design" is a
+        strategy too: elicit_field_design, with `targets` taken from session_kw.
         Returns {strategy: {metric: [Q + 1 floats]}, "n_queries": queries ranked per strategy}.  The model is left
         untouched, bit for bit."""
         from . import elicit
@@ -1420,10 +1421,55 @@ class VFM(nn.Module):
     def elicitation_curve_field_exact(self, pool, y_pool, n_questions: int, field: int = 0,
                                       strategies=("random", "variance"), **kw):
         """elicitation_curve_field over elicit_field_exact sessions ('reg' models: the RMSE of the mean on the rows
-        still unasked before each round).  kw: elicit_field_exact's other options.  Returns {strategy: [Q + 1 floats],
-        "n_unasked": {strategy: [Q + 1 ints]}}.  The model is left untouched."""
+        still unasked before each round).  kw: elicit_field_exact's other options.  One more strategy name is known
+        here: "design" runs elicit_field_design (its `targets` option passes through kw and reaches no other strategy;
+        seed and key_field do not reach it).  Returns {strategy: [Q + 1 floats], "n_unasked": {strategy: [Q + 1
+        ints]}}.  The model is left untouched."""
         from . import elicit
         return elicit.curve(self, pool, y_pool, n_questions, strategies, session=elicit.run_field_exact, field=field, **kw)
+
+    # ------------------------------------------------------------------ target-aware elicitation (vae_amd/design.py)
+    @torch.no_grad()
+    def design_scores_field(self, pool, field: int, targets=None, history=None, kl_weight: float = 1.0):
+        """How much would each question reduce the uncertainty of the predictions that matter?  [P] fp32 in the caller's
+        pool order: per pool row q of respondent e (column `field`) the drop of the mean, over e's target contexts, of
+        the part of Var pred carried by e's scales if q were asked next (include/vfm_design.h; DESIGN.md §4
+        "Target-aware elicitation"):  (v_w(n) - v_w(n + 1)) + sum_k W_k (v_k(S_k) - v_k(S_k + a_qk)),  with
+        v(S) = kl_weight / (kl_weight + prec S) the squared scale of fold_in_exact's optimum, S_k the sum of
+        a_rk = A_rk + M_rk^2 over e's history rows and W_k the mean of a_jk over the targets.  fp64, rounded once.  It
+        does not depend on any answer nor on e's current row.
+
+        'reg' models only, kl_weight > 0 and finite, F >= 2 (else ValueError, before anything needs a GPU).  pool [P, F]
+        full rows; history: (X [H, F], y [H]) as in the sessions (y is not read), rows of the pool's respondents; targets: None -- each
+        respondent's own pool rows, in pool order -- or [R, F] rows whose column `field` names the respondent (grouped
+        per respondent in the given order; a respondent without any gets an empty list: W = 0, and only the bias term
+        is left; rows of entities not in the pool raise)."""
+        from . import design
+        return design.scores(self, pool, field, targets, history, kl_weight)
+
+    @torch.no_grad()
+    def select_next_questions_design_field(self, pool, field: int, n: int = 1, targets=None, history=None,
+                                           kl_weight: float = 1.0):
+        """select_next_questions_field by the design score: per entity of column `field` the indices of its n best
+        rows by design_scores_field (same arguments).  Ties go to the lower row; a NaN score is never chosen.  Returns
+        (entities [U'] ascending, rows [U', n] int64, -1 padded)."""
+        from . import design
+        return design.select_next_questions(self, pool, field, n, targets, history, kl_weight)
+
+    @torch.no_grad()
+    def elicit_field_design(self, pool, y_pool, n_questions: int, field: int = 0, targets=None, history=None,
+                            kl_weight: float = 1.0, reset: bool = False, write: bool = False,
+                            return_moments: bool = False, return_theta: bool = False, lds_dim: int = -1):
+        """elicit_field_exact with the question chosen for what the answers are used for: n_questions rounds of
+        select_next_questions_design_field(n=1, history = history + the rows asked so far) followed by
+        fold_in_exact(field=field) of the answering respondent, bitwise what that loop computes, for every respondent
+        in one launch (include/vfm_design.h: vfm_design_elicit_f32).  targets: as design_scores_field, fixed over the
+        session (None: the respondent's whole pool, asked or not).  pool, y_pool, history, kl_weight, reset (round 0's
+        moments only: the score does not read the current row), write, return_moments, return_theta: as
+        elicit_field_exact, and so is the result; score [U, Q] is the asked row's design score."""
+        from . import design
+        return design.run_field_design(self, pool, y_pool, n_questions, field, targets, history, kl_weight, reset, write,
+                                       return_moments, return_theta, lds_dim)
 
     @torch.no_grad()
     def evaluate(self, X_test, y_test):

@@ -255,8 +255,16 @@ def select_next_questions_field(model, pool, field, n: int = 1, strategy: str = 
         raise ValueError("n must be >= 1")
     n = int(n)
     pool = _context_rows(model, pool, "pool", field, check_field_column=True).contiguous()
-    dev = model.device
     _, _, score = field_moments(model, pool, field, strategy, seed, key_field)
+    return best_rows_per_entity(pool, score, field, n)
+
+
+def best_rows_per_entity(pool, score, field, n, drop_nan=False):
+    """(entities [U'] ascending, rows [U', n] int64, -1 padded): per entity of column `field` of pool [P, F] the indices
+    of its n best rows by score [P]; ties go to the lower row index.  A NaN score ranks last; with drop_nan it is never
+    chosen."""
+    dev = pool.device
+    nan = torch.isnan(score)
     score = torch.nan_to_num(score, nan=-float("inf"))
     o1 = torch.sort(score, descending=True, stable=True).indices            # best first; ties: lower row first
     o2 = torch.sort(pool[o1, field], stable=True).indices                    # grouped by entity, order kept
@@ -267,6 +275,8 @@ def select_next_questions_field(model, pool, field, n: int = 1, strategy: str = 
     grp = torch.repeat_interleave(torch.arange(ents.numel(), device=dev), counts)
     rank = torch.arange(pe.numel(), device=dev) - start[grp]
     keep = rank < n
+    if drop_nan:
+        keep = keep & ~nan[order]
     rows = torch.full((ents.numel(), n), -1, dtype=torch.int64, device=dev)
     rows[grp[keep], rank[keep]] = order[keep]
     return ents, rows
