@@ -82,7 +82,10 @@ _UNITS = [("vfm_abi.hip", "", _EXACT), ("vfm_index.hip", "", []), ("vfm_variants
           ("csrc_rank/vfm_elicit_design.hip", "", _EXACT),
           # fused Adam step of the ELBO variants (include/vfm_variant_step.h): outside csrc/ for the same reason.  It
           # restates the backward of vfm_variants.hip and holds update arithmetic, hence the flag of the Adam units
-          ("csrc_var/vfm_variant_step.hip", "", _EXACT)]
+          ("csrc_var/vfm_variant_step.hip", "", _EXACT),
+          # split exact solve (include/vfm_sweep.h): the exact fold-in's prep, factorisation and rounding
+          # (csrc_rank/vfm_foldin_solve_body.hpp) with a chunk-parallel assembly in front, hence its flag
+          ("csrc_rank/vfm_foldin_split.hip", "", _EXACT)]
 RANK_DIR = os.path.join(HERE, "csrc_rank")
 RANK_HDR = os.path.join(ROOT, "include", "vfm_rank.h")
 RANK_OPS = os.path.join(RANK_DIR, "vfm_rank_ops.cpp")
@@ -92,6 +95,8 @@ ELICIT_HDR = os.path.join(ROOT, "include", "vfm_elicit.h")
 ELICIT_OPS = os.path.join(RANK_DIR, "vfm_elicit_ops.cpp")
 DESIGN_HDR = os.path.join(ROOT, "include", "vfm_design.h")
 DESIGN_OPS = os.path.join(RANK_DIR, "vfm_design_ops.cpp")
+SWEEP_HDR = os.path.join(ROOT, "include", "vfm_sweep.h")
+SWEEP_OPS = os.path.join(RANK_DIR, "vfm_sweep_ops.cpp")
 VAR_DIR = os.path.join(HERE, "csrc_var")
 VAR_STEP_HDR = os.path.join(ROOT, "include", "vfm_variant_step.h")
 
@@ -106,7 +111,7 @@ def _unit_obj(objdir, src, suffix):
 
 
 def _rank_sources():
-    return ([RANK_HDR, FOLDIN_HDR, ELICIT_HDR, DESIGN_HDR, VAR_STEP_HDR] +
+    return ([RANK_HDR, FOLDIN_HDR, ELICIT_HDR, DESIGN_HDR, VAR_STEP_HDR, SWEEP_HDR] +
             sorted(os.path.join(RANK_DIR, f) for f in os.listdir(RANK_DIR) if f.endswith((".hip", ".hpp"))) +
             sorted(os.path.join(VAR_DIR, f) for f in os.listdir(VAR_DIR) if f.endswith((".hip", ".hpp"))))
 
@@ -125,7 +130,7 @@ def build_hip_library(force=False, verbose=False):
     common = [HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-fvisibility-inlines-hidden",
               "-I" + os.path.join(ROOT, "include"), "-I" + csrc]
     jobs, objs = [], []
-    shared = [hdr, RANK_HDR, FOLDIN_HDR, ELICIT_HDR, DESIGN_HDR, VAR_STEP_HDR, os.path.abspath(__file__)] + [f for f in parts if f.endswith(".hpp")]      # what every unit depends on
+    shared = [hdr, RANK_HDR, FOLDIN_HDR, ELICIT_HDR, DESIGN_HDR, VAR_STEP_HDR, SWEEP_HDR, os.path.abspath(__file__)] + [f for f in parts if f.endswith(".hpp")]      # what every unit depends on
     for src, suffix, extra in _UNITS:
         obj = _unit_obj(objdir, src, suffix)
         objs.append(obj)
@@ -154,14 +159,14 @@ def build_hip_library(force=False, verbose=False):
 
 def build_torch_ops(force=False, verbose=False):
     """libvfm_torch_ops.so: TORCH_LIBRARY shim `torch.ops.vfm_hip.*` over the C ABI (host C++ only); the ranking and
-    fold-in, session and design ops are TORCH_LIBRARY_FRAGMENTs of their own sources (csrc_rank/vfm_{rank,foldin,elicit,design}_ops.cpp) linked
+    fold-in, session and design ops are TORCH_LIBRARY_FRAGMENTs of their own sources (csrc_rank/vfm_{rank,foldin,elicit,design,sweep}_ops.cpp) linked
     into the same shim."""
     import torch
     src = os.path.join(HERE, "csrc", "vfm_torch_ops.cpp")
     hdr = os.path.join(ROOT, "include", "vfm_hip.h")
     out = os.path.join(HERE, "libvfm_torch_ops.so")
     lib = os.path.join(HERE, "libvfm_hip.so")
-    if not force and not _stale(out, [src, hdr, lib, RANK_OPS, RANK_HDR, FOLDIN_OPS, FOLDIN_HDR, ELICIT_OPS, ELICIT_HDR, DESIGN_OPS, DESIGN_HDR]):
+    if not force and not _stale(out, [src, hdr, lib, RANK_OPS, RANK_HDR, FOLDIN_OPS, FOLDIN_HDR, ELICIT_OPS, ELICIT_HDR, DESIGN_OPS, DESIGN_HDR, SWEEP_OPS, SWEEP_HDR]):
         return out
     ti = os.path.dirname(torch.__file__)
     rocm = os.environ.get("ROCM_HOME", "/opt/rocm")
@@ -169,7 +174,7 @@ def build_torch_ops(force=False, verbose=False):
            "-D_GLIBCXX_USE_CXX11_ABI=%d" % int(torch._C._GLIBCXX_USE_CXX11_ABI),
            "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ti, "include"),
            "-I" + os.path.join(ti, "include", "torch", "csrc", "api", "include"),
-           "-I" + os.path.join(rocm, "include"), "-o", out, src, RANK_OPS, FOLDIN_OPS, ELICIT_OPS, DESIGN_OPS,
+           "-I" + os.path.join(rocm, "include"), "-o", out, src, RANK_OPS, FOLDIN_OPS, ELICIT_OPS, DESIGN_OPS, SWEEP_OPS,
            "-L" + os.path.join(ti, "lib"), "-ltorch", "-ltorch_cpu", "-lc10", "-lc10_hip", "-ltorch_hip",
            "-L" + HERE, "-lvfm_hip", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(ti, "lib")]
     if verbose:
@@ -196,7 +201,7 @@ def build_sanitized(force=False, verbose=False):
     os.makedirs(outdir, exist_ok=True)
     stamp = os.path.join(outdir, "digest.txt")
     import hashlib
-    digest = sources_digest() + hashlib.sha1(b"".join(open(f, "rb").read() for f in _rank_sources() + [RANK_OPS, FOLDIN_OPS, ELICIT_OPS, DESIGN_OPS])).hexdigest()
+    digest = sources_digest() + hashlib.sha1(b"".join(open(f, "rb").read() for f in _rank_sources() + [RANK_OPS, FOLDIN_OPS, ELICIT_OPS, DESIGN_OPS, SWEEP_OPS])).hexdigest()
     out = os.path.join(outdir, "libvfm_hip.so")
     out_ops = os.path.join(outdir, "libvfm_torch_ops.so")
     if (not force and os.path.exists(out) and os.path.exists(out_ops) and os.path.exists(stamp)
@@ -229,7 +234,7 @@ def build_sanitized(force=False, verbose=False):
            "-D_GLIBCXX_USE_CXX11_ABI=%d" % int(torch._C._GLIBCXX_USE_CXX11_ABI),
            "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ti, "include"),
            "-I" + os.path.join(ti, "include", "torch", "csrc", "api", "include"),
-           "-I" + os.path.join(rocm, "include"), "-o", out_ops, os.path.join(csrc, "vfm_torch_ops.cpp"), RANK_OPS, FOLDIN_OPS, ELICIT_OPS, DESIGN_OPS,
+           "-I" + os.path.join(rocm, "include"), "-o", out_ops, os.path.join(csrc, "vfm_torch_ops.cpp"), RANK_OPS, FOLDIN_OPS, ELICIT_OPS, DESIGN_OPS, SWEEP_OPS,
            "-L" + os.path.join(ti, "lib"), "-ltorch", "-ltorch_cpu", "-lc10", "-lc10_hip", "-ltorch_hip",
            "-L" + outdir, "-lvfm_hip", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(ti, "lib")]
     if verbose:

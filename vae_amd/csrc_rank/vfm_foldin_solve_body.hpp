@@ -81,6 +81,48 @@ __global__ __launch_bounds__(FB) void k_foldin_solve_prep(int64_t n_ops, int F, 
 // the size of the system of an entity with n rows: the dual n x n while n <= d, else the primal (d + 1) x (d + 1)
 __device__ __forceinline__ int solve_dim(int64_t n, int d) { return n <= d ? (int)n : d + 1; }
 
+// phase C of solve_body, by the whole workgroup (it holds barriers): L L^T = the packed system Hm [m] (row i of L:
+// thread i mod FB; row m: the right-hand side yv), one barrier per column, so the forward substitution is part of the
+// factorisation; then L^T x = yv from the last column back.  dv: 1 / L_jj; xv: the solution.
+__device__ __forceinline__ void chol_solve(double* Hm, double* yv, double* dv, double* xv, int m) {
+#pragma clang fp contract(on)
+  const int tid = threadIdx.x;
+  for (int j = 0; j < m; ++j) {
+    const double* Lj = Hm + tri(j);
+    int i = j + 1 + (tid - (j + 1) % FB + FB) % FB;        // the first row below j that this thread owns
+    if (i <= m) {
+      double sjj = Lj[j];
+      for (int k = 0; k < j; ++k) sjj -= Lj[k] * Lj[k];
+      const double rinv = 1.0 / sqrt(sjj);
+      if (i == j + 1) dv[j] = rinv;
+      for (; i <= m; i += FB) {
+        double* Li = i < m ? Hm + tri(i) : yv;
+        double sij = Li[j];
+        for (int k = 0; k < j; ++k) sij -= Li[k] * Lj[k];
+        Li[j] = sij * rinv;
+      }
+    }
+    __syncthreads();
+  }
+  // L^T x = yv, from the last column back
+  for (int j = m - 1; j >= 0; --j) {
+    const double xj = yv[j] * dv[j];
+    const double* Lj = Hm + tri(j);
+    for (int i = tid; i < j; i += FB) yv[i] -= Lj[i] * xj;
+    if (tid == 0) xv[j] = xj;
+    __syncthreads();
+  }
+}
+
+// phase D's rounding: coordinate c's mean th and its scale from the closed form sigma^2 = kl / (kl + prec SB), to fp32
+template <int LINK>
+__device__ __forceinline__ void put_params(float* pf, int d1, int c, double th, double kl, double prec, double SB) {
+#pragma clang fp contract(on)
+  const double sg = sqrt(kl / (kl + prec * SB));
+  pf[c] = (float)th;
+  pf[d1 + c] = (float)(LINK == LINK_ABS ? sg : log(expm1(sg)));
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // solve_body: the closed-form optimum of one entity over its n rows, by the whole workgroup (FB threads, every thread
 // calls it: it holds barriers).  a: the options and the fp32 operands of the loss pass (a.cap = 0: nothing staged);
@@ -179,32 +221,8 @@ __device__ __forceinline__ void solve_body(const FoldArgs& a, const double* ops6
   }
   __syncthreads();
 
-  // ---- C: L L^T = system (row i of L: thread i mod FB; row m: the right-hand side), one barrier per column
-  for (int j = 0; j < m; ++j) {
-    const double* Lj = Hm + tri(j);
-    int i = j + 1 + (tid - (j + 1) % FB + FB) % FB;        // the first row below j that this thread owns
-    if (i <= m) {
-      double sjj = Lj[j];
-      for (int k = 0; k < j; ++k) sjj -= Lj[k] * Lj[k];
-      const double rinv = 1.0 / sqrt(sjj);
-      if (i == j + 1) dv[j] = rinv;
-      for (; i <= m; i += FB) {
-        double* Li = i < m ? Hm + tri(i) : yv;
-        double sij = Li[j];
-        for (int k = 0; k < j; ++k) sij -= Li[k] * Lj[k];
-        Li[j] = sij * rinv;
-      }
-    }
-    __syncthreads();
-  }
-  // L^T x = yv, from the last column back
-  for (int j = m - 1; j >= 0; --j) {
-    const double xj = yv[j] * dv[j];
-    const double* Lj = Hm + tri(j);
-    for (int i = tid; i < j; i += FB) yv[i] -= Lj[i] * xj;
-    if (tid == 0) xv[j] = xj;
-    __syncthreads();
-  }
+  // ---- C: the factorisation and the two substitutions
+  chol_solve(Hm, yv, dv, xv, m);
 
   // ---- D: the means and the scales, rounded to fp32
   for (int c = tid; c < d1; c += FB) {
@@ -220,9 +238,7 @@ __device__ __forceinline__ void solve_body(const FoldArgs& a, const double* ops6
     } else {
       th = xv[c];
     }
-    const double sg = sqrt(kl / (kl + prec * SBd[c]));
-    pf[c] = (float)th;
-    pf[d1 + c] = (float)(LINK == LINK_ABS ? sg : log(expm1(sg)));
+    put_params<LINK>(pf, d1, c, th, kl, prec, SBd[c]);
   }
   __syncthreads();
   store(pf);

@@ -1291,7 +1291,8 @@ class VFM(nn.Module):
         return {"entities": ents, "loss": loss, "rows": rows}
 
     @torch.no_grad()
-    def fold_in_exact(self, X, y, field: int = 0, kl_weight: float = 1.0):
+    def fold_in_exact(self, X, y, field: int = 0, kl_weight: float = 1.0, split_rows=None, chunk_rows: int = 2048,
+                      max_workspace_bytes: int = 1 << 30):
         """fold_in's closed-form objective solved exactly: the entities of X[:, field] get the global optimum of L_e
         itself, in one launch (include/vfm_foldin.h: vfm_foldin_solve_f32; DESIGN.md §4 "Exact fold-in").  No lr, no
         n_steps, no reset: with everything else frozen L_e is quadratic in the means (one symmetric positive definite
@@ -1302,10 +1303,52 @@ class VFM(nn.Module):
         order, what is written and what stays frozen are fold_in's: only the folded rows of entity_params /
         bias_params change; the training Adam state and the save_weights snapshots are not touched.
         Returns dict(entities [E] int64, loss [E] fp32 = L_e at the returned parameters, evaluated as fold_in evaluates
-        it, rows [E] int64)."""
-        from . import foldin
-        ents, loss, rows = foldin.run_exact(self, X, y, field, kl_weight)
+        it, rows [E] int64).
+
+        split_rows: None (the default) solves every entity in one workgroup.  An integer, or "auto" = 4 (d + 1), sends the
+        entities with more than max(split_rows, d + 1) rows through the split solve (include/vfm_sweep.h): their rows
+        are cut in chunks of chunk_rows, a workgroup per chunk assembles its share of the system and a workgroup per
+        entity adds the shares in chunk order and solves.  The other entities get the bits they get with None; a split
+        entity's bits depend on its rows, chunk_rows and d alone.  The chunks' shares of one call take at most
+        max_workspace_bytes: the split entities are processed in as many groups as that needs, with the same result."""
+        from . import foldin, sweep
+        if split_rows is None:
+            sweep.check_chunk_rows(chunk_rows)
+            ents, loss, rows = foldin.run_exact(self, X, y, field, kl_weight)
+        else:
+            ents, loss, rows = sweep.run_exact_split(self, X, y, field, kl_weight, split_rows, chunk_rows,
+                                                     max_workspace_bytes)
         return {"entities": ents, "loss": loss, "rows": rows}
+
+    @torch.no_grad()
+    def exact_objective(self, X, y, kl_weight: float = 1.0) -> float:
+        """The objective J of fit_exact at the current parameters ("Exact sweeps"): over the rows of X the
+        expected negative log likelihood 1/2 prec ((y - E pred)^2 + Var pred) - 1/2 log prec + 1/2 log 2 pi, plus
+        kl_weight times the KL to N(0, 1) of the factors of every entity that occurs in X (embedding and first-order
+        weight) and of the global bias.  The per-row moments are the predictive_moments kernel's; the sums and the KL
+        terms are taken in fp64 on the device.  'reg' models only."""
+        from . import sweep
+        return sweep.exact_objective(self, X, y, kl_weight)
+
+    @torch.no_grad()
+    def fit_exact(self, X, y, n_sweeps: int = 10, kl_weight: float = 1.0, fields=None, update_scalars: bool = True,
+                  split_rows="auto", chunk_rows: int = 2048, on_step=None, tol: Optional[float] = None):
+        """Train by exact coordinate ascent on exact_objective: no learning rate, no sampling.  One sweep solves, for each
+        field of `fields` in turn (default: all, in order), the closed-form optimum of every entity of that field over
+        all rows of X with the rest of the model frozen (fold_in_exact's solve: the exact minimiser of J over that
+        field's factors), then sets the global bias (mean and scale) and after it the precision alpha to their exact
+        minimisers (update_scalars=False leaves the three scalars alone).  J never increases, up to the fp32 rounding of
+        the rows written.  Entities that do not occur in X are neither written nor counted.
+
+        split_rows, chunk_rows: as in fold_in_exact; "auto" = 4 (d + 1).  The row lists, partner tuples and chunk tables
+        of each field are built once, before the first sweep.  on_step(sweep, what) is called after every block, `what`
+        the field index or "scalars".  tol: stop after a sweep whose relative decrease of J is at most tol.
+        'reg' models only, kl_weight > 0, ids as fold_in checks them for every field (else ValueError).  The training
+        Adam state and the save_weights snapshots are not touched.
+        Returns dict(objective = J before the first block and after every sweep, sweeps = the number run, ms = each
+        sweep's device time from HIP events)."""
+        from . import sweep
+        return sweep.fit(self, X, y, n_sweeps, kl_weight, fields, update_scalars, split_rows, chunk_rows, on_step, tol)
 
     @torch.no_grad()
     def fold_in_objective(self, X, y, field: int = 0, objective: Optional[str] = None, n_samples: int = 1,

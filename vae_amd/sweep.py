@@ -1,0 +1,281 @@
+"""Exact coordinate-ascent training (VFM.fit_exact) and the split exact solve behind it (include/vfm_sweep.h).
+
+`fold_in_exact` over every row of a training set, field after field, is exact coordinate-ascent variational inference
+on one objective J ("Exact sweeps"): each call is the exact minimiser of J over one field's factors.  This
+module holds what such a sweep needs beyond foldin.run_exact:
+
+  SweepPlan        the sorted rows, row lists, partner tuples and chunk table of one (X, y, field), built once
+  exact_objective  J itself, from the predictive_moments kernel's per-row moments and the tables, summed in fp64
+  update_scalars   the exact block minimisers of the global bias and of the precision
+  fit              the sweeps
+
+Entities with more rows than the plan's threshold go through vfm_foldin_solve_split_f32 (their system assembled by a
+workgroup per chunk of rows), the others through vfm_foldin_solve_f32, unchanged.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+from . import _lib, foldin, ops, rank
+
+LOG_2PI_HALF = 0.5 * math.log(2.0 * math.pi)
+MAX_WORKSPACE_BYTES = 1 << 30
+
+
+def resolve_split_rows(split_rows, d):
+    """The row count above which an entity is split: None (never), "auto" = 4 (d + 1), or an integer; at least d + 1, so
+    that a split entity is always solved in the primal form."""
+    if split_rows is None:
+        return None
+    if isinstance(split_rows, str):
+        if split_rows != "auto":
+            raise ValueError('split_rows must be None, "auto" or an integer >= 0')
+        return 4 * (d + 1)
+    if isinstance(split_rows, bool) or not isinstance(split_rows, int) or split_rows < 0:
+        raise ValueError('split_rows must be None, "auto" or an integer >= 0')
+    return max(split_rows, d + 1)
+
+
+def check_chunk_rows(chunk_rows):
+    if isinstance(chunk_rows, bool) or not isinstance(chunk_rows, int) or chunk_rows < 1:
+        raise ValueError("chunk_rows must be an integer >= 1")
+    return chunk_rows
+
+
+def chunk_table(first, counts, chunk_rows):
+    """The chunk table of entities whose rows start at first [E] and number counts [E] (numpy int64): (chunk_ptr [E + 1],
+    chunks [n_chunks, 3] = (entity number, first row, rows)), an entity's chunks consecutive and in row order."""
+    first, counts = np.asarray(first, np.int64), np.asarray(counts, np.int64)
+    nch = (counts + chunk_rows - 1) // chunk_rows
+    ptr = np.zeros(counts.size + 1, np.int64)
+    np.cumsum(nch, out=ptr[1:])
+    ent = np.repeat(np.arange(counts.size, dtype=np.int64), nch)
+    k = np.arange(int(ptr[-1]), dtype=np.int64) - ptr[ent]
+    rows = np.minimum(chunk_rows, counts[ent] - k * chunk_rows)
+    return ptr, np.stack([ent, first[ent] + k * chunk_rows, rows], 1).reshape(-1, 3)
+
+
+class SweepPlan:
+    """Everything about one (X, y, field) that an exact solve needs and that does not depend on the parameters: the rows
+    sorted (stably) by (split or not, folded id), so that the light entities come first with a contiguous row_ptr and the
+    heavy ones after; the partner tuples and each row's tuple; the heavy entities' chunk table, cut in groups whose
+    workspace stays under max_workspace_bytes.  Building it reads the row counts back once; running it reads nothing
+    back.  x, y: as foldin.check_args_exact returns them."""
+
+    def __init__(self, model, x, y, field, split_rows=None, chunk_rows=2048, max_workspace_bytes=MAX_WORKSPACE_BYTES,
+                 lds_dim=-1):
+        self.field, self.d, self.lds_dim = int(field), model.d, int(lds_dim)
+        self.threshold = resolve_split_rows(split_rows, model.d)
+        self.chunk_rows = check_chunk_rows(chunk_rows)
+        dev = x.device
+        lo, hi = foldin.field_range(model, field)
+        col = x[:, field]
+        if self.threshold is None or x.shape[0] == 0:
+            key = col
+        else:
+            per_id = torch.bincount(col - lo, minlength=hi - lo)
+            key = col + (per_id[col - lo] > self.threshold).to(torch.int64) * model.T      # (heavy ids sort last)
+        order = torch.sort(key, stable=True).indices
+        xs, self.ys = x[order].contiguous(), y[order].contiguous()
+        self.ents, counts = torch.unique_consecutive(xs[:, field], return_counts=True)
+        self.ents = self.ents.contiguous()
+        self.E = self.ents.numel()
+        self.ptr = torch.zeros(self.E + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(counts, 0, out=self.ptr[1:])
+        self.counts = counts
+        self.op_x, self.row_op = foldin.partner_tuples(xs, field) if self.E else (None, None)
+        self.asc = torch.sort(self.ents).indices              # the entities in ascending order, as fold_in returns them
+        self.n_light, self.groups = self.E, []
+        if self.threshold is None or self.E == 0:
+            return
+        cnt = counts.cpu().numpy()                            # (the one readback)
+        heavy = cnt > self.threshold
+        self.n_light = int(self.E - heavy.sum())
+        assert not heavy[:self.n_light].any()
+        if self.n_light == self.E:
+            return
+        first = np.concatenate([[0], np.cumsum(cnt)])[:-1]
+        wsb = _lib.load().vfm_foldin_split_workspace_bytes
+        n_ops, nch = self.op_x.shape[0], (cnt + self.chunk_rows - 1) // self.chunk_rows
+        g0, chunks = self.n_light, 0
+        bounds = []
+        for g in range(self.n_light, self.E):                 # greedy: a group takes entities while its workspace fits
+            if g > g0 and wsb(chunks + int(nch[g]), g + 1 - g0, n_ops, self.d, self.lds_dim) > max_workspace_bytes:
+                bounds.append((g0, g))
+                g0, chunks = g, 0
+            chunks += int(nch[g])
+        bounds.append((g0, self.E))
+        for a, b in bounds:
+            cptr, tab = chunk_table(first[a:b], cnt[a:b], self.chunk_rows)
+            self.groups.append((a, b, torch.from_numpy(cptr).to(dev), torch.from_numpy(np.ascontiguousarray(tab)).to(dev)))
+
+    def run(self, model, kl_weight):
+        """Write the exact optimum of every entity of the plan into the model's tables.  Returns (entities [E] ascending,
+        loss [E], rows [E])."""
+        dev, d = model.device, self.d
+        loss = torch.empty(self.E, dtype=torch.float32, device=dev)
+        if self.E == 0:
+            return self.ents, loss, self.counts
+        o = _lib.ops()
+        model._fresh_params()
+        ent, bia, scal = model._views(model._flat)
+        flags = ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0
+        n_ops = self.op_x.shape[0]
+        if self.n_light:
+            nl = self.n_light
+            ws = torch.empty(max(o.foldin_solve_workspace_bytes(nl, n_ops, d, self.lds_dim), 1), dtype=torch.uint8,
+                             device=dev)
+            o.foldin_solve(self.ents[:nl], self.ptr[:nl + 1], self.ys, self.op_x, self.row_op, ent, bia, scal, ws,
+                           loss[:nl], self.field, foldin.OBJECTIVES["closed_form"], _lib.LIK_NORMAL, flags,
+                           self.lds_dim, float(kl_weight))
+        for a, b, cptr, tab in self.groups:
+            ws = torch.empty(max(o.foldin_split_workspace_bytes(tab.shape[0], b - a, n_ops, d, self.lds_dim), 1),
+                             dtype=torch.uint8, device=dev)
+            o.foldin_solve_split(self.ents[a:b], cptr, tab, self.ys, self.op_x, self.row_op, ent, bia, scal, ws,
+                                 loss[a:b], self.field, flags, self.lds_dim, float(kl_weight))
+        model.params_changed()              # (rows written outside the step kernels: derived caches are stale)
+        return self.ents[self.asc], loss[self.asc], self.counts[self.asc]
+
+
+def run_exact_split(model, X, y, field=0, kl_weight=1.0, split_rows="auto", chunk_rows=2048,
+                    max_workspace_bytes=MAX_WORKSPACE_BYTES, lds_dim=-1):
+    """foldin.run_exact with the entities of more than max(split_rows, d + 1) rows solved by the split path."""
+    x, y = foldin.check_args_exact(model, X, y, field, kl_weight)
+    resolve_split_rows(split_rows, model.d)
+    check_chunk_rows(chunk_rows)
+    if int(lds_dim) < -1:
+        raise ValueError("lds_dim must be -1 or >= 0")
+    if int(max_workspace_bytes) < 0:
+        raise ValueError("max_workspace_bytes must be >= 0")
+    ops._need_cuda(model._flat, "the model's parameters")
+    return SweepPlan(model, x, y, field, split_rows, chunk_rows, int(max_workspace_bytes), lds_dim).run(model, kl_weight)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the objective and the scalars
+# ---------------------------------------------------------------------------------------------------------------------
+def _link64(s, link):
+    s = s.double()
+    return s.abs() if link == "abs" else torch.nn.functional.softplus(s)
+
+
+def _inv_link64(v, link):
+    return v if link == "abs" else torch.log(torch.expm1(v))
+
+
+def _kl64(mu, sg):
+    return 0.5 * (sg * sg + mu * mu - 1.0) - torch.log(sg)
+
+
+def _moments64(model, x):
+    ent, bia, scal = model._views(model._flat)
+    m, v, _ = rank.predictive_moments(x, ent, bia, scal, model.link)
+    return m.double(), v.double()
+
+
+def objective_terms(model, x, y, seen, kl_weight):
+    """J as a 0-dim fp64 tensor on the device: the rows' expected negative log likelihood from the predictive_moments
+    kernel's fp32 moments, the KL of the entities `seen` (distinct ids) and of the global bias from the tables."""
+    d = model.d
+    ent, bia, scal = model._views(model._flat)
+    prec = _link64(scal[0], model.link)
+    n = x.shape[0]
+    J = torch.zeros((), dtype=torch.float64, device=x.device)
+    if n:
+        m, v = _moments64(model, x)
+        J = J + 0.5 * prec * ((y.double() - m) ** 2 + v).sum() + n * (LOG_2PI_HALF - 0.5 * torch.log(prec))
+    kl = _kl64(scal[1].double(), _link64(scal[2], model.link))
+    if seen.numel():
+        e, b = ent[seen], bia[seen]
+        kl = kl + _kl64(e[:, :d].double(), _link64(e[:, d:], model.link)).sum()
+        kl = kl + _kl64(b[:, 0].double(), _link64(b[:, 1], model.link)).sum()
+    return J + float(kl_weight) * kl
+
+
+def update_scalars(model, x, y, kl_weight):
+    """The exact block minimisers of J over the scalars, written in place: first the global bias (mean and scale
+    jointly), then the precision from the moments recomputed after it.  No readback."""
+    n = x.shape[0]
+    if n == 0:
+        return
+    scal = model._views(model._flat)[2]
+    kl = float(kl_weight)
+    yd = y.double()
+    prec = _link64(scal[0], model.link)
+    m, _ = _moments64(model, x)
+    m0 = scal[1].double()
+    den = kl + prec * n
+    new_m0 = prec * (yd - (m - m0)).sum() / den
+    new_s0 = _inv_link64(torch.sqrt(kl / den), model.link)
+    scal[1:3] = torch.stack([new_m0, new_s0]).float()
+    m, v = _moments64(model, x)
+    new_prec = n / ((yd - m) ** 2 + v).sum()
+    scal[0:1] = _inv_link64(new_prec, model.link).float().reshape(1)
+
+
+def check_fit_args(model, X, y, n_sweeps, kl_weight, fields, split_rows, chunk_rows, tol):
+    """Validate a fit_exact call (no GPU needed).  Returns (x, y, fields)."""
+    if model.output != "reg":
+        raise ValueError("fit_exact needs a 'reg' model (Gaussian likelihood): the closed form its blocks solve has none "
+                         "for 'class'; use fit")
+    if not float(kl_weight) > 0.0 or not math.isfinite(float(kl_weight)):
+        raise ValueError("kl_weight must be > 0 and finite: the prior term is what makes each system positive definite")
+    if isinstance(n_sweeps, bool) or not isinstance(n_sweeps, int) or n_sweeps < 0:
+        raise ValueError("n_sweeps must be an integer >= 0")
+    if fields is None:
+        fields = tuple(range(model.F))
+    else:
+        fields = tuple(fields)
+        for f in fields:
+            if isinstance(f, bool) or not isinstance(f, int) or not 0 <= f < model.F:
+                raise ValueError(f"fields must hold ints in [0, {model.F})")
+    resolve_split_rows(split_rows, model.d)
+    check_chunk_rows(chunk_rows)
+    if tol is not None and not float(tol) >= 0.0:
+        raise ValueError("tol must be None or >= 0")
+    x = yy = None
+    for f in range(model.F):                                  # (every column is some block's or a partner of one)
+        x, yy = foldin.check_args_exact(model, X, y, f, kl_weight)
+    return x, yy, fields
+
+
+def exact_objective(model, X, y, kl_weight=1.0):
+    x, y, _ = check_fit_args(model, X, y, 0, kl_weight, None, None, 1, None)
+    ops._need_cuda(model._flat, "the model's parameters")
+    model._fresh_params()
+    return float(objective_terms(model, x, y, torch.unique(x), kl_weight))
+
+
+def fit(model, X, y, n_sweeps=10, kl_weight=1.0, fields=None, update_scalars_=True, split_rows="auto", chunk_rows=2048,
+        on_step=None, tol=None, max_workspace_bytes=MAX_WORKSPACE_BYTES):
+    x, y, fields = check_fit_args(model, X, y, n_sweeps, kl_weight, fields, split_rows, chunk_rows, tol)
+    ops._need_cuda(model._flat, "the model's parameters")
+    model._fresh_params()
+    seen = torch.unique(x)
+    plans = {f: SweepPlan(model, x, y, f, split_rows, chunk_rows, max_workspace_bytes) for f in dict.fromkeys(fields)}
+    objective = [float(objective_terms(model, x, y, seen, kl_weight))]
+    events = []
+    done = 0
+    for sweep in range(n_sweeps):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for f in fields:
+            plans[f].run(model, kl_weight)
+            if on_step is not None:
+                on_step(sweep, f)
+        if update_scalars_:
+            update_scalars(model, x, y, kl_weight)
+            if on_step is not None:
+                on_step(sweep, "scalars")
+        t1.record()
+        events.append((t0, t1))
+        objective.append(float(objective_terms(model, x, y, seen, kl_weight)))
+        done += 1
+        if tol is not None and objective[-2] - objective[-1] <= float(tol) * abs(objective[-2]):
+            break
+    model.params_changed()
+    torch.cuda.synchronize(model.device)
+    return {"objective": objective, "sweeps": done, "ms": [a.elapsed_time(b) for a, b in events]}
