@@ -47,6 +47,16 @@ WANT = [
     ("../csrc_rank/vfm_foldin.hip", ["-ffp-contract=on"], "k_foldin<64, 2, 1, true>", "fold-in, d = 128, sampled, softplus"),
     ("../csrc_rank/vfm_foldin.hip", ["-ffp-contract=on"], "k_foldin<64, 8, 0, false>", "fold-in, d = 512, closed form, |.|"),
     ("../csrc_rank/vfm_foldin.hip", ["-ffp-contract=on"], "k_foldin<64, 8, 1, true>", "fold-in, d = 512, sampled, softplus"),
+    # the exact sessions: two kernels, one session loop (csrc_rank/vfm_elicit_exact_body.hpp), compared instance by instance
+    # (--only elicit_solve --every elicit_solve, and the same for elicit_design: profiles/exact_session_isa*.txt)
+    ("../csrc_rank/vfm_elicit_solve.hip", ["-ffp-contract=on"], "k_elicit_solve<8, 1, 0>", "exact session, moment scores, d <= 8, |.|"),
+    ("../csrc_rank/vfm_elicit_solve.hip", ["-ffp-contract=on"], "k_elicit_solve<64, 2, 0>", "exact session, moment scores, d = 128 (the benchmark shape), |.|"),
+    ("../csrc_rank/vfm_elicit_solve.hip", ["-ffp-contract=on"], "k_elicit_solve<64, 2, 1>", "exact session, moment scores, d = 128, softplus"),
+    ("../csrc_rank/vfm_elicit_solve.hip", ["-ffp-contract=on"], "k_elicit_solve<64, 8, 0>", "exact session, moment scores, d = 512, |.|"),
+    ("../csrc_rank/vfm_elicit_design.hip", ["-ffp-contract=on"], "k_elicit_design<8, 1, 0>", "exact session, target-aware score, d <= 8, |.|"),
+    ("../csrc_rank/vfm_elicit_design.hip", ["-ffp-contract=on"], "k_elicit_design<64, 2, 0>", "exact session, target-aware score, d = 128 (the benchmark shape), |.|"),
+    ("../csrc_rank/vfm_elicit_design.hip", ["-ffp-contract=on"], "k_elicit_design<64, 2, 1>", "exact session, target-aware score, d = 128, softplus"),
+    ("../csrc_rank/vfm_elicit_design.hip", ["-ffp-contract=on"], "k_elicit_design<64, 8, 0>", "exact session, target-aware score, d = 512, |.|"),
     # fused Adam step of the ELBO variants (--only variant_step prints these alone; --every variant_step adds one line per instance)
     ("../csrc_var/vfm_variant_step.hip", ["-ffp-contract=on"], "k_vstep<8, 16, 1, true, false, true>", "variant step, d = 128 (the benchmark shape), closed form, learnable priors"),
     ("../csrc_var/vfm_variant_step.hip", ["-ffp-contract=on"], "k_vstep<8, 16, 1, false, true, false>", "variant step, d = 128, sampled objective, feature values, N(0,1) priors"),

@@ -74,11 +74,13 @@ _UNITS = [("vfm_abi.hip", "", _EXACT), ("vfm_index.hip", "", []), ("vfm_variants
           # the field form of the sessions (any number of fields): the same body with the field-form scores of
           # csrc_rank/vfm_field_ctx.hpp, which pin `off` themselves; a unit of its own so that the two compile side by side
           ("csrc_rank/vfm_elicit_field.hip", "", _EXACT),
-          # the exact field-form session (vfm_elicit_solve_f32): the field form's scores (csrc_rank/vfm_elicit_field_score.hpp)
-          # and the exact fold-in's body (csrc_rank/vfm_foldin_solve_body.hpp) in one kernel, hence their flag
+          # the exact field-form session (vfm_elicit_solve_f32): the session loop and host path of
+          # csrc_rank/vfm_elicit_exact_body.hpp with the field form's scores (csrc_rank/vfm_elicit_field_score.hpp); the
+          # loop runs the exact fold-in's body (csrc_rank/vfm_foldin_solve_body.hpp), hence its flag
           ("csrc_rank/vfm_elicit_solve.hip", "", _EXACT),
-          # target-aware elicitation (include/vfm_design.h): the exact session's layout and body with the score of
-          # csrc_rank/vfm_design_score.hpp, which pins its own contraction expression by expression; the same flag
+          # target-aware elicitation (include/vfm_design.h): the same session loop and host path with the score of
+          # csrc_rank/vfm_design_score.hpp, which pins its own contraction expression by expression; the same flag, and a
+          # unit of its own so that the two compile side by side
           ("csrc_rank/vfm_elicit_design.hip", "", _EXACT),
           # fused Adam step of the ELBO variants (include/vfm_variant_step.h): outside csrc/ for the same reason.  It
           # restates the backward of vfm_variants.hip and holds update arithmetic, hence the flag of the Adam units

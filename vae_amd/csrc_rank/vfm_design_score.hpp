@@ -1,7 +1,8 @@
 // vfm_design_score.hpp -- the target-aware question score (include/vfm_design.h) on the device: the two walks that form
 // a respondent's scale sums S and target weights W, and the score of one candidate row.  Used by k_design_score (every
-// pool row's score, one round) and k_elicit_design (the sessions), both in vfm_elicit_design.hip, so a score exists
-// once.  Included inside `namespace vfm { namespace {` of a unit, after vfm_foldin_solve_body.hpp.
+// pool row's score, one round) and DesignScore (the score k_elicit_design gives the session loop of
+// vfm_elicit_exact_body.hpp, whose order of the choice it shares with k_elicit_solve), both in vfm_elicit_design.hip,
+// so a score exists once.  Included inside `namespace vfm { namespace {` of a unit, after vfm_foldin_solve_body.hpp.
 //
 // With the partners frozen the scales of a respondent's optimum do not depend on the answers:
 //   sigma_k^2 = v_k(S_k) = kl / (kl + prec S_k),  S_k = sum_{r in R} (A_rk + M_rk^2);  sigma_w^2 = v_w(n) = kl / (kl + prec n)
@@ -75,9 +76,4 @@ __device__ __forceinline__ float design_score(const double* S, const double* W, 
     acc += W[k] * drop;
   }
   return (float)acc;
-}
-
-// the order of the choice: score descending, position ascending (k_elicit_solve's); op < 0: no candidate
-__device__ __forceinline__ bool design_better(float os, long long op, float bs, long long bp) {
-  return op >= 0 && (bp < 0 || os > bs || (os == bs && op < bp));
 }

@@ -1,8 +1,8 @@
 // vfm_elicit_field_score.hpp -- what the field-form sessions share on the device: the score's operand pass over the
 // distinct contexts (k_elicit_ctx_prep), the kernel arguments, the fold rows of a respondent and the two operand views
 // of a score (a context's row of the score table, the respondent's candidate operands in LDS).  Used by
-// vfm_elicit_field.hip (the Adam session) and vfm_elicit_solve.hip (the exact session), so a score is the same bits in
-// both.  Included inside `namespace vfm { namespace {` of a unit, after vfm_foldin_body.hpp; the unit includes
+// vfm_elicit_field.hip (the Adam session) and vfm_elicit_exact_body.hpp (the exact sessions: vfm_elicit_solve.hip and,
+// for out_mean / out_var, vfm_elicit_design.hip), so a score is the same bits in all.  Included inside `namespace vfm { namespace {` of a unit, after vfm_foldin_body.hpp; the unit includes
 // vfm_rank_tile.hpp and vfm_field_ctx.hpp at file scope first.
 #pragma once
 

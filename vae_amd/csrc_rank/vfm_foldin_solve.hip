@@ -2,7 +2,7 @@
 // folded entity in one launch.
 //
 // k_foldin_solve: one workgroup of FB threads per entity (a grid-stride loop over the entities).  Phases A-E are
-//   solve_body of vfm_foldin_solve_body.hpp, which the exact elicitation session (vfm_elicit_solve.hip) runs on a
+//   solve_body of vfm_foldin_solve_body.hpp, which the exact elicitation sessions (vfm_elicit_exact_body.hpp) run on a
 //   respondent's rows round after round.  Per entity, with the
 //   row operands M_r, A_r, C_r, c_mean,r in fp64 (k_foldin_solve_prep: k_foldin_prep's sums, kept unrounded, with the
 //   links in fp64 -- rounded to fp32 they would move the optimum by about 1e-7, more than the last fp32 bit of the rows
@@ -40,9 +40,7 @@ struct SolveArgs {
   FoldArgs f;                            // (cap = 0: fold_stage_rows stages nothing; f.ops / f.opc: the fp32 operands of the loss)
   const double* ops64;                   // [n_ops, 3, d]  M | A | C, unrounded
   const double* cm64;                    // [n_ops]        c_mean
-  double* slab;                          // [gridDim.x, slab_elems] or NULL when every system stays in LDS
-  int64_t slab_elems;
-  int32_t cap_dim;                       // systems up to this size live in LDS
+  SolveSlabs sl;                         // the slabs and the LDS rule of the triangle
 };
 
 template <int W, int CPL, int LINK>
@@ -53,7 +51,7 @@ __global__ __launch_bounds__(FB) void k_foldin_solve(const SolveArgs s) {
   const int tid = threadIdx.x;
   const int d = a.d, d1 = d + 1;
   double* Hl = sm + 8 * d1;              // (past solve_body's vectors and fp32 parameters)
-  double* Hg = s.slab ? s.slab + (int64_t)blockIdx.x * s.slab_elems : nullptr;
+  double* Hg = s.sl.slab ? s.sl.slab + (int64_t)blockIdx.x * s.sl.slab_elems : nullptr;
   const float precf = link_f<LINK>(a.scal[0]);
   const double prec = link_d<LINK>(a.scal[0]);
 
@@ -62,7 +60,7 @@ __global__ __launch_bounds__(FB) void k_foldin_solve(const SolveArgs s) {
     const int64_t n = min(max(a.ptr[g + 1], r0), a.R) - r0;
     const int64_t e = a.ent[g];
     const int m = solve_dim(n, d);
-    double* Hm = m <= s.cap_dim ? Hl : Hg;
+    double* Hm = m <= s.sl.cap_dim ? Hl : Hg;
     if (e < 0 || e >= a.T || !Hm) {      // (block-uniform)
       if (tid == 0) a.loss[g] = __builtin_nanf("");
       continue;
@@ -102,10 +100,7 @@ extern "C" {
 
 int64_t vfm_foldin_solve_workspace_bytes(int64_t E, int64_t n_ops, int32_t d, int32_t lds_dim) {
   if (E < 0 || n_ops < 0 || d < 1 || d > VFM_FOLDIN_MAX_D || lds_dim < -1) return VFM_E_INVALID;
-  int64_t b = vfm::off_slabs(n_ops, d);
-  if (d + 1 > vfm::cap_dim_of(d, lds_dim))
-    b += (E < VFM_FOLDIN_SOLVE_SLABS ? E : VFM_FOLDIN_SOLVE_SLABS) * vfm::slab_bytes(d);
-  return b;
+  return vfm::off_slabs(n_ops, d) + vfm::slabs_bytes(E, d, lds_dim);
 }
 
 int vfm_foldin_solve_f32(const vfm_foldin_solve_t* p, void* stream) {
@@ -147,16 +142,11 @@ int vfm_foldin_solve_f32(const vfm_foldin_solve_t* p, void* stream) {
   float* ops = (float*)w;
   float* opc = (float*)(w + off_opc);
   a.ops = ops; a.opc = opc;
-  s.cap_dim = vfm::cap_dim_of(p->d, p->lds_dim);
-  const bool slabs = p->d + 1 > s.cap_dim;
-  double* ops64 = (double*)(w + vfm::off_ops64(p->n_ops, p->d));
-  double* cm64 = (double*)(w + vfm::off_cm64(p->n_ops, p->d));
-  s.ops64 = ops64; s.cm64 = cm64;
-  s.slab = slabs ? (double*)(w + vfm::off_slabs(p->n_ops, p->d)) : nullptr;
-  s.slab_elems = vfm::slab_bytes(p->d) / 8;
-  const int64_t gmax = slabs ? VFM_FOLDIN_SOLVE_SLABS : ((int64_t)1 << 20);
-  const unsigned grid = (unsigned)(p->E < gmax ? p->E : gmax);
-  const size_t shm = (size_t)vfm::lds_doubles(p->d, s.cap_dim) * 8;
+  s.ops64 = (double*)(w + vfm::off_ops64(p->n_ops, p->d));
+  s.cm64 = (double*)(w + vfm::off_cm64(p->n_ops, p->d));
+  const unsigned grid =
+      vfm::place_slabs(p->d, p->lds_dim, p->E, w + vfm::off_slabs(p->n_ops, p->d), (int64_t)1 << 20, s.sl);
+  const size_t shm = (size_t)vfm::lds_doubles(p->d, s.sl.cap_dim) * 8;
 
   if (p->n_ops > 0) {
     if (int rc = vfm::launch_solve_preps(sp, a, p->n_ops, p->op_x, w, st)) return rc;

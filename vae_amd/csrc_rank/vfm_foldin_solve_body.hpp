@@ -1,8 +1,9 @@
 // vfm_foldin_solve_body.hpp -- the per-entity body of the exact fold-in, shared by k_foldin_solve
-// (vfm_foldin_solve.hip) and the exact elicitation session (vfm_elicit_solve.hip): the fp64 operand pass, the solve of
-// one entity's closed-form optimum by a workgroup (phases A-E of vfm_foldin_solve.hip's head comment) and the host
-// helpers of the workspace both units lay out alike.  Included inside `namespace vfm { namespace {` of a unit, after
-// vfm_foldin_body.hpp.
+// (vfm_foldin_solve.hip), the exact elicitation sessions (exact_session of vfm_elicit_exact_body.hpp: k_elicit_solve and
+// k_elicit_design) and, for its phases C and D, the split solve (vfm_foldin_split.hip): the fp64 operand pass, the solve
+// of one entity's closed-form optimum by a workgroup (phases A-E of vfm_foldin_solve.hip's head comment) and the host
+// helpers of the workspace the units lay out alike -- the operand block and the placement of the slabs (SolveSlabs,
+// place_slabs, slabs_bytes).  Included inside `namespace vfm { namespace {` of a unit, after vfm_foldin_body.hpp.
 //
 // The body is parameterised over where the entity's rows come from (a Rows object: op(i), y(i) of row i in fold
 // order), as fold_run is.  Every sum is fp64 in a fixed order that depends on the entity's rows alone, under fp
@@ -292,6 +293,30 @@ inline int cap_dim_of(int d, int lds_dim) {
 }
 
 inline int64_t slab_bytes(int d) { return round_up(tri(d + 1) * 8, 256); }
+
+// where the systems too large for LDS go: a slab per workgroup of the solving kernel
+struct SolveSlabs {
+  double* slab;                          // [gridDim.x, slab_elems] or NULL when every system stays in LDS
+  int64_t slab_elems;
+  int32_t cap_dim;                       // systems up to this size live in LDS
+};
+
+// the slabs' bytes in a workspace that solves n entities
+inline int64_t slabs_bytes(int64_t n, int d, int lds_dim) {
+  if (d + 1 <= cap_dim_of(d, lds_dim)) return 0;
+  return (n < VFM_FOLDIN_SOLVE_SLABS ? n : VFM_FOLDIN_SOLVE_SLABS) * slab_bytes(d);
+}
+
+// sl for n entities with the slabs at `base`; returns the grid of the solving kernel: n, capped at the slabs when they
+// are needed, else at gcap
+inline unsigned place_slabs(int d, int lds_dim, int64_t n, char* base, int64_t gcap, SolveSlabs& sl) {
+  sl.cap_dim = cap_dim_of(d, lds_dim);
+  const bool slabs = d + 1 > sl.cap_dim;
+  sl.slab = slabs ? (double*)base : nullptr;
+  sl.slab_elems = slab_bytes(d) / 8;
+  const int64_t gmax = slabs ? VFM_FOLDIN_SOLVE_SLABS : gcap;
+  return (unsigned)(n < gmax ? n : gmax);
+}
 
 inline int64_t off_ops64(int64_t n_ops, int d) { return ops_off_opc(n_ops, d) + round_up(n_ops * 2 * 4, 256); }
 inline int64_t off_cm64(int64_t n_ops, int d) { return off_ops64(n_ops, d) + round_up(n_ops * 3 * d * 8, 256); }

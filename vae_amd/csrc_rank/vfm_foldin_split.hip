@@ -43,9 +43,8 @@ struct SplitArgs {
   const int64_t* chunks;                 // [n_chunks, 3]  entity number, first row, rows
   double* part;                          // [n_chunks, part_elems]
   double* lpart;                         // [n_chunks]     the chunks' shares of the loss
-  double* slab;                          // [gridDim.x of k_split_solve, slab_elems] or NULL when the system stays in LDS
-  int64_t n_ops, n_chunks, part_elems, slab_elems;
-  int32_t cap_dim;
+  SolveSlabs sl;                         // the slabs of k_split_solve's workgroups and the LDS rule of the triangle
+  int64_t n_ops, n_chunks, part_elems;
 };
 
 __host__ __device__ inline int64_t part_doubles(int d) { return tri(d + 1) + 4 * (int64_t)d + 3; }
@@ -165,8 +164,8 @@ __global__ __launch_bounds__(FB) void k_split_solve(const SplitArgs s) {
   double* SBd = xv + d1;
   float* pf = (float*)(SBd + d1);
   double* Hl = sm + 8 * d1;
-  double* Hg = s.slab ? s.slab + (int64_t)blockIdx.x * s.slab_elems : nullptr;
-  double* Hm = d1 <= s.cap_dim ? Hl : Hg;
+  double* Hg = s.sl.slab ? s.sl.slab + (int64_t)blockIdx.x * s.sl.slab_elems : nullptr;
+  double* Hm = d1 <= s.sl.cap_dim ? Hl : Hg;
   const double prec = link_d<LINK>(a.scal[0]);
   const double kl = a.klw;
   const int64_t nt = tri(d1);
@@ -311,10 +310,8 @@ int64_t vfm_foldin_split_workspace_bytes(int64_t n_chunks, int64_t n_heavy, int6
   if (n_chunks < 0 || n_heavy < 0 || n_ops < 0 || n_chunks > lim || n_heavy > lim || n_ops > lim || d < 1 ||
       d > VFM_FOLDIN_MAX_D || lds_dim < -1)
     return VFM_E_INVALID;
-  int64_t b = vfm::off_slabs(n_ops, d) + vfm::part_bytes(n_chunks, d) + vfm::lpart_bytes(n_chunks);
-  if (d + 1 > vfm::cap_dim_of(d, lds_dim))
-    b += (n_heavy < VFM_FOLDIN_SOLVE_SLABS ? n_heavy : VFM_FOLDIN_SOLVE_SLABS) * vfm::slab_bytes(d);
-  return b;
+  return vfm::off_slabs(n_ops, d) + vfm::part_bytes(n_chunks, d) + vfm::lpart_bytes(n_chunks) +
+         vfm::slabs_bytes(n_heavy, d, lds_dim);
 }
 
 int vfm_foldin_solve_split_f32(const vfm_foldin_split_t* p, void* stream) {
@@ -362,15 +359,11 @@ int vfm_foldin_solve_split_f32(const vfm_foldin_split_t* p, void* stream) {
   const int64_t off_lpart = off_part + vfm::part_bytes(p->n_chunks, p->d);
   s.part = (double*)(w + off_part);
   s.lpart = (double*)(w + off_lpart);
-  s.cap_dim = vfm::cap_dim_of(p->d, p->lds_dim);
-  const bool slabs = p->d + 1 > s.cap_dim;
-  s.slab = slabs ? (double*)(w + off_lpart + vfm::lpart_bytes(p->n_chunks)) : nullptr;
-  s.slab_elems = vfm::slab_bytes(p->d) / 8;
   const int64_t gcap = (int64_t)1 << 20;
-  const int64_t gmax = slabs ? VFM_FOLDIN_SOLVE_SLABS : gcap;
-  const unsigned grid_e = (unsigned)(p->E < gmax ? p->E : gmax);
+  const unsigned grid_e =
+      vfm::place_slabs(p->d, p->lds_dim, p->E, w + off_lpart + vfm::lpart_bytes(p->n_chunks), gcap, s.sl);
   const unsigned grid_c = (unsigned)(p->n_chunks < gcap ? p->n_chunks : gcap);
-  const size_t shm = (size_t)vfm::lds_doubles(p->d, s.cap_dim) * 8;
+  const size_t shm = (size_t)vfm::lds_doubles(p->d, s.sl.cap_dim) * 8;
 
   if (p->n_ops > 0) {
     if (int rc = vfm::launch_solve_preps(sp, a, p->n_ops, p->op_x, w, st)) return rc;
