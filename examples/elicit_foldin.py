@@ -3,14 +3,17 @@
 the answering students are folded in (`VFM.fold_in`, every other parameter frozen) instead of refitting the whole model.
 Prints the test AUC per round for both, side by side:
 
-    python examples/elicit_foldin.py [rounds] [epochs] [strategy] [--exact]   (needs an MI355X; vae_amd has no CPU fallback)
+    python examples/elicit_foldin.py [rounds] [epochs] [strategy] [--exact | --bound]   (needs an MI355X; vae_amd has no CPU fallback)
 
 The refit moves every student's and question's posterior on every Adam step (dense Adam); the fold-in moves only the
 rows of the students who answered, warm-started from their current posteriors.
 
 --exact: the same loop with 'reg' models (the 0/1 answers as a regression target, test RMSE in place of the AUC), whose
 fold-in objective has a closed-form optimum: the students are folded in with `VFM.fold_in_exact`, one solve per student
-in one launch, no n_steps and no lr to choose."""
+in one launch, no n_steps and no lr to choose.
+
+--bound: the 'class' models and the AUC of the default loop, the students folded in with `VFM.fold_in_bound`: a few rounds
+of exact solves of the Jaakkola-Jordan bound of the Bernoulli likelihood, no lr, no sampling and no seed to choose."""
 import os
 import sys
 
@@ -22,8 +25,10 @@ from vae_amd.data import load_fraction
 
 
 def main():
-    argv = [a for a in sys.argv[1:] if a != "--exact"]
-    exact = "--exact" in sys.argv[1:]
+    argv = [a for a in sys.argv[1:] if a not in ("--exact", "--bound")]
+    exact, bound = "--exact" in sys.argv[1:], "--bound" in sys.argv[1:]
+    if exact and bound:
+        raise SystemExit("--exact ('reg' models) and --bound ('class' models) exclude each other")
     rounds = int(argv[0]) if len(argv) > 0 else 5
     epochs = int(argv[1]) if len(argv) > 1 else 60
     strategy = argv[2] if len(argv) > 2 else "variance"
@@ -54,6 +59,8 @@ def main():
                 who = torch.isin(Xt[:, 0], pool[asked][:, 0])
                 if exact:
                     model.fold_in_exact(Xt[who], yt[who])
+                elif bound:
+                    model.fold_in_bound(Xt[who], yt[who])
                 else:
                     model.fold_in(Xt[who], yt[who], n_steps=200, lr=0.05)
             pool, y_pool = pool[keep], y_pool[keep]

@@ -115,6 +115,23 @@ class FoldinSplit(_Strict, C.Structure):
     ]
 
 
+# ---- bound fold-in for 'class' models (include/vfm_bound.h)
+BOUND_EXPORTS = ("vfm_foldin_bound_f32", "vfm_foldin_bound_workspace_bytes")
+
+
+class FoldinBound(_Strict, C.Structure):
+    """`vfm_foldin_bound_t` (tests/test_foldin_bound_cpu.py checks the layout against gcc's)."""
+    _fields_ = [
+        ("E", C.c_int64), ("R", C.c_int64), ("T", C.c_int64), ("n_ops", C.c_int64),
+        ("F", C.c_int32), ("d", C.c_int32), ("col", C.c_int32), ("objective", C.c_int32),
+        ("likelihood", C.c_int32), ("flags", C.c_int32), ("lds_dim", C.c_int32), ("kl_weight", C.c_float),
+        ("n_iters", C.c_int32), ("reset", C.c_int32), ("mode", C.c_int32), ("pad0", C.c_int32),
+        ("entities", C.c_void_p), ("row_ptr", C.c_void_p), ("y", C.c_void_p), ("op_x", C.c_void_p),
+        ("row_op", C.c_void_p), ("entity_params", C.c_void_p), ("bias_params", C.c_void_p), ("scalars", C.c_void_p),
+        ("out_loss", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+
 class Elicit(_Strict, C.Structure):
     """`vfm_elicit_t` (tests/test_elicit_cpu.py checks the layout against gcc's)."""
     _fields_ = [
@@ -214,7 +231,7 @@ class ElicitDesign(_Strict, C.Structure):
         self.struct_size, self.abi_version = C.sizeof(type(self)), ABI_VERSION      # (VFM_STRUCT_INIT)
 
 
-for _c in (Problem, Index, Pipe, Elicit, ElicitField, ElicitSolve, ElicitDesign, FoldinSolve, FoldinSplit):
+for _c in (Problem, Index, Pipe, Elicit, ElicitField, ElicitSolve, ElicitDesign, FoldinSolve, FoldinSplit, FoldinBound):
     _c._names = frozenset(n for n, _ in _c._fields_)
 
 
@@ -309,6 +326,10 @@ def load():
     lib.vfm_foldin_solve_split_f32.restype = C.c_int
     lib.vfm_foldin_split_workspace_bytes.argtypes = [i64, i64, i64, i32, i32]
     lib.vfm_foldin_split_workspace_bytes.restype = i64
+    lib.vfm_foldin_bound_f32.argtypes = [C.POINTER(FoldinBound), vp]
+    lib.vfm_foldin_bound_f32.restype = C.c_int
+    lib.vfm_foldin_bound_workspace_bytes.argtypes = [i64, i64, i64, i32, i32]
+    lib.vfm_foldin_bound_workspace_bytes.restype = i64
     u64 = C.c_uint64
     lib.vfm_field_moments_post_f32.argtypes = [i64, i32, i32, i64, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, u64,
                                                vp, vp, vp, vp, vp]

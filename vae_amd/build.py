@@ -87,7 +87,11 @@ _UNITS = [("vfm_abi.hip", "", _EXACT), ("vfm_index.hip", "", []), ("vfm_variants
           ("csrc_var/vfm_variant_step.hip", "", _EXACT),
           # split exact solve (include/vfm_sweep.h): the exact fold-in's prep, factorisation and rounding
           # (csrc_rank/vfm_foldin_solve_body.hpp) with a chunk-parallel assembly in front, hence its flag
-          ("csrc_rank/vfm_foldin_split.hip", "", _EXACT)]
+          ("csrc_rank/vfm_foldin_split.hip", "", _EXACT),
+          # bound fold-in (include/vfm_bound.h): the exact fold-in's preps, factorisation and rounding
+          # (csrc_rank/vfm_foldin_solve_body.hpp) under weights of the Jaakkola-Jordan bound, and the fold-in's fp32 row
+          # moments (csrc_rank/vfm_foldin_body.hpp) for the loss, hence their flag
+          ("csrc_rank/vfm_foldin_bound.hip", "", _EXACT)]
 RANK_DIR = os.path.join(HERE, "csrc_rank")
 RANK_HDR = os.path.join(ROOT, "include", "vfm_rank.h")
 RANK_OPS = os.path.join(RANK_DIR, "vfm_rank_ops.cpp")
@@ -99,6 +103,7 @@ DESIGN_HDR = os.path.join(ROOT, "include", "vfm_design.h")
 DESIGN_OPS = os.path.join(RANK_DIR, "vfm_design_ops.cpp")
 SWEEP_HDR = os.path.join(ROOT, "include", "vfm_sweep.h")
 SWEEP_OPS = os.path.join(RANK_DIR, "vfm_sweep_ops.cpp")
+BOUND_HDR = os.path.join(ROOT, "include", "vfm_bound.h")      # (its op lives in vfm_foldin_ops.cpp)
 VAR_DIR = os.path.join(HERE, "csrc_var")
 VAR_STEP_HDR = os.path.join(ROOT, "include", "vfm_variant_step.h")
 
@@ -113,7 +118,7 @@ def _unit_obj(objdir, src, suffix):
 
 
 def _rank_sources():
-    return ([RANK_HDR, FOLDIN_HDR, ELICIT_HDR, DESIGN_HDR, VAR_STEP_HDR, SWEEP_HDR] +
+    return ([RANK_HDR, FOLDIN_HDR, ELICIT_HDR, DESIGN_HDR, VAR_STEP_HDR, SWEEP_HDR, BOUND_HDR] +
             sorted(os.path.join(RANK_DIR, f) for f in os.listdir(RANK_DIR) if f.endswith((".hip", ".hpp"))) +
             sorted(os.path.join(VAR_DIR, f) for f in os.listdir(VAR_DIR) if f.endswith((".hip", ".hpp"))))
 
@@ -132,7 +137,7 @@ def build_hip_library(force=False, verbose=False):
     common = [HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-fvisibility-inlines-hidden",
               "-I" + os.path.join(ROOT, "include"), "-I" + csrc]
     jobs, objs = [], []
-    shared = [hdr, RANK_HDR, FOLDIN_HDR, ELICIT_HDR, DESIGN_HDR, VAR_STEP_HDR, SWEEP_HDR, os.path.abspath(__file__)] + [f for f in parts if f.endswith(".hpp")]      # what every unit depends on
+    shared = [hdr, RANK_HDR, FOLDIN_HDR, ELICIT_HDR, DESIGN_HDR, VAR_STEP_HDR, SWEEP_HDR, BOUND_HDR, os.path.abspath(__file__)] + [f for f in parts if f.endswith(".hpp")]      # what every unit depends on
     for src, suffix, extra in _UNITS:
         obj = _unit_obj(objdir, src, suffix)
         objs.append(obj)
@@ -168,7 +173,7 @@ def build_torch_ops(force=False, verbose=False):
     hdr = os.path.join(ROOT, "include", "vfm_hip.h")
     out = os.path.join(HERE, "libvfm_torch_ops.so")
     lib = os.path.join(HERE, "libvfm_hip.so")
-    if not force and not _stale(out, [src, hdr, lib, RANK_OPS, RANK_HDR, FOLDIN_OPS, FOLDIN_HDR, ELICIT_OPS, ELICIT_HDR, DESIGN_OPS, DESIGN_HDR, SWEEP_OPS, SWEEP_HDR]):
+    if not force and not _stale(out, [src, hdr, lib, RANK_OPS, RANK_HDR, FOLDIN_OPS, FOLDIN_HDR, ELICIT_OPS, ELICIT_HDR, DESIGN_OPS, DESIGN_HDR, SWEEP_OPS, SWEEP_HDR, BOUND_HDR]):
         return out
     ti = os.path.dirname(torch.__file__)
     rocm = os.environ.get("ROCM_HOME", "/opt/rocm")

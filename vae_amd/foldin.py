@@ -132,7 +132,7 @@ def check_args_exact(model, X, y, field, kl_weight=1.0):
     """Validate an exact fold-in call (no GPU needed): check_args, a 'reg' model and kl_weight > 0."""
     if model.output != "reg":
         raise ValueError("the exact fold-in needs a 'reg' model (Gaussian likelihood): the closed form it solves has "
-                         "none for 'class'; use fold_in")
+                         "none for 'class'; use fold_in or fold_in_bound")
     if not float(kl_weight) > 0.0 or not math.isfinite(float(kl_weight)):
         raise ValueError("kl_weight must be > 0 and finite: the prior term is what makes each system positive definite")
     x, y, _ = check_args(model, X, y, field, "closed_form", 1, 0, 0.0, kl_weight)
@@ -162,4 +162,48 @@ def run_exact(model, X, y, field=0, kl_weight=1.0, lds_dim=-1):
                    _lib.LIK_NORMAL, ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, int(lds_dim),
                    float(kl_weight))
     model.params_changed()              # (rows written outside the step kernels: derived caches are stale)
+    return ents, loss, counts
+
+
+def check_args_bound(model, X, y, field, kl_weight=1.0, n_iters=8):
+    """Validate a bound fold-in call (no GPU needed): check_args, a 'class' model, kl_weight > 0 and finite,
+    n_iters >= 1 and y in {0, 1}."""
+    if model.output != "class":
+        raise ValueError("the bound fold-in needs a 'class' model (Bernoulli likelihood): a 'reg' model has the exact "
+                         "optimum itself; use fold_in_exact")
+    if not float(kl_weight) > 0.0 or not math.isfinite(float(kl_weight)):
+        raise ValueError("kl_weight must be > 0 and finite: the prior term is what makes each system positive definite")
+    if isinstance(n_iters, bool) or int(n_iters) != n_iters or int(n_iters) < 1:
+        raise ValueError("n_iters must be an integer >= 1")
+    x, y, _ = check_args(model, X, y, field, "sampled", 1, 0, 0.0, kl_weight)
+    if y.numel() and not bool(((y == 0) | (y == 1)).all()):
+        raise ValueError("y must hold the labels 0 and 1 of a 'class' model")
+    return x, y
+
+
+def run_bound(model, X, y, field=0, kl_weight=1.0, n_iters=8, reset=False, lds_dim=-1, mode=MODE_FIT):
+    """One bound fold-in launch (include/vfm_bound.h: vfm_foldin_bound_f32): n_iters rounds of the Jaakkola-Jordan
+    bound's two exact block minimisers for every folded entity (mode=MODE_OBJECTIVE: B_e at the current rows, nothing
+    written; n_iters is not used).  Returns (entities [E], loss [E] = B_e, rows [E])."""
+    x, y = check_args_bound(model, X, y, field, kl_weight, n_iters)
+    if int(lds_dim) < -1:
+        raise ValueError("lds_dim must be -1 or >= 0")
+    ops._need_cuda(model._flat, "the model's parameters")
+    dev, d = model.device, model.d
+    xs, ys, ents, ptr, counts = row_lists(x, y, field)
+    E = ents.numel()
+    loss = torch.empty(E, dtype=torch.float32, device=dev)
+    if E == 0:
+        return ents, loss, counts
+    o = _lib.ops()
+    op_x, row_op = partner_tuples(xs, field)
+    ws = torch.empty(max(o.foldin_bound_workspace_bytes(E, ys.numel(), op_x.shape[0], d, int(lds_dim)), 1),
+                     dtype=torch.uint8, device=dev)
+    model._fresh_params()
+    ent, bia, scal = model._views(model._flat)
+    o.foldin_bound(ents, ptr, ys, op_x, row_op, ent, bia, scal, ws, loss, int(field), OBJECTIVES["closed_form"],
+                   _lib.LIK_BERNOULLI, ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, int(lds_dim),
+                   float(kl_weight), int(n_iters) if mode == MODE_FIT else 0, int(bool(reset)), int(mode))
+    if mode == MODE_FIT:
+        model.params_changed()          # (rows written outside the step kernels: derived caches are stale)
     return ents, loss, counts

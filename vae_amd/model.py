@@ -1321,6 +1321,38 @@ class VFM(nn.Module):
         return {"entities": ents, "loss": loss, "rows": rows}
 
     @torch.no_grad()
+    def fold_in_bound(self, X_new, y_new, field: int = 0, kl_weight: float = 1.0, n_iters: int = 8,
+                      reset: bool = False):
+        """fold_in for a 'class' model without Adam: the entities of X_new[:, field] are fitted by n_iters rounds of
+        exact solves of the Jaakkola-Jordan quadratic bound of the Bernoulli likelihood, in one launch
+        (include/vfm_bound.h: vfm_foldin_bound_f32; DESIGN.md §4 "Bound fold-in").  No lr, no n_samples, no seed: each
+        round sets every row's variational parameter xi_r to its optimum at the current posterior and then solves the
+        resulting Gaussian problem exactly (fold_in_exact's system with a weight per row), so one deterministic
+        objective B_e, an upper bound on fold_in's L_e, never increases.  The iterate stays in fp64 on the device and
+        is rounded to fp32 once, at the end.
+
+        n_iters = 8 is a starting value: it comes from a numpy fp64 run (d = 6, n = 9) in which the decrease per round
+        fell from 1.5 to below 1e-13 in seven rounds; it has not been tuned on a GPU.  reset=True takes the first xi
+        at the prior (mu = 0, sigma = 1) instead of the current rows; the starting row enters through that first xi
+        only.  'class' models only, kl_weight > 0, y in {0, 1} (else ValueError, as for everything fold_in rejects).
+        X_new, y_new, field, the row order, what is written and what stays frozen are fold_in's: only the folded rows
+        of entity_params / bias_params change; the training Adam state and the save_weights snapshots are not touched.
+        Returns dict(entities [E] int64, loss [E] fp32 = B_e at the returned parameters, rows [E] int64)."""
+        from . import foldin
+        ents, loss, rows = foldin.run_bound(self, X_new, y_new, field, kl_weight, n_iters, reset)
+        return {"entities": ents, "loss": loss, "rows": rows}
+
+    @torch.no_grad()
+    def fold_in_bound_objective(self, X, y, field: int = 0, kl_weight: float = 1.0):
+        """fold_in_bound's objective B_e at the current rows of the entities of X[:, field], nothing written: with
+        xi_r = sqrt((E f_r)^2 + Var f_r), B_e = sum_r [-(y_r - 1/2) E f_r + xi_r / 2 + log1p(e^-xi_r)] + kl_weight KL.
+        Right after fold_in_bound on the same rows it returns that call's loss, bit for bit.  Returns dict(entities
+        [E], loss [E] fp32, rows [E])."""
+        from . import foldin
+        ents, loss, rows = foldin.run_bound(self, X, y, field, kl_weight, 1, False, mode=foldin.MODE_OBJECTIVE)
+        return {"entities": ents, "loss": loss, "rows": rows}
+
+    @torch.no_grad()
     def exact_objective(self, X, y, kl_weight: float = 1.0) -> float:
         """The objective J of fit_exact at the current parameters ("Exact sweeps"): over the rows of X the
         expected negative log likelihood 1/2 prec ((y - E pred)^2 + Var pred) - 1/2 log prec + 1/2 log 2 pi, plus
