@@ -25,6 +25,12 @@ by side, where "design" (`VFM.elicit_field_design`) asks the question that most 
 the student's held-out questions.
 
     python examples/elicit_session.py --design [questions] [epochs]
+
+With --bound the 'class' model's questionnaire runs without Adam: every answer is followed by n_iters = 8 rounds of the
+Jaakkola-Jordan bound's exact solves (`VFM.elicit_field_bound`; 8 is an untuned starting value): the AUC on the questions
+still unasked, beside the Adam session's (200 steps on the sampled objective) on the same model.
+
+    python examples/elicit_session.py --bound [questions] [epochs]
 """
 import os
 import sys
@@ -81,9 +87,30 @@ def main_ranking(argv, design=False):
         print(f"{q:5d}  " + "  ".join(f"{rmse[s][q]:8.4f} / {ndcg[s]['ndcg@10'][q]:8.4f}" for s in strategies))
 
 
+def main_bound(argv):
+    questions = int(argv[0]) if len(argv) > 0 else 15
+    epochs = int(argv[1]) if len(argv) > 1 else 60
+    N, M, X_train, X_test, y_train, y_test = load_fraction(os.path.join(ROOT, "tests", "golden", "fraction"))
+    X_train, X_test = torch.as_tensor(X_train), torch.as_tensor(X_test)
+    y_train, y_test = torch.as_tensor(y_train).float(), torch.as_tensor(y_test).float()
+    torch.manual_seed(42)
+    model = VFM(N, M, embedding_size=5, output="class", device="cuda")
+    model.fit(X_train, y_train, n_epochs=epochs, batch_size=100000, verbose=False)
+    strategies = ("mean", "random", "variance")
+    bound = model.elicitation_curve_field_bound(X_test, y_test, questions, 0, strategies, n_iters=8, reset=True, seed=1)
+    adam = model.elicitation_curve_field(X_test, y_test, questions, 0, strategies, n_steps=200, lr=0.05, reset=True, seed=1)
+    print(f"{len(torch.unique(X_test[:, 0]))} students, {len(X_test)} questions in the pool; AUC bound(8) / Adam(200)")
+    print("asked  " + "  ".join(f"{s:>26}" for s in strategies))
+    for q in range(questions + 1):
+        print(f"{q:5d}  " + "  ".join(f"{bound[s][q]:8.4f} / {adam[s][q]:8.4f} ({bound['n_unasked'][s][q]:5d})"
+                                      for s in strategies))
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--exact":
         return main_exact(sys.argv[2:])
+    if len(sys.argv) > 1 and sys.argv[1] == "--bound":
+        return main_bound(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] in ("--ranking", "--design"):
         return main_ranking(sys.argv[2:], design=sys.argv[1] == "--design")
     questions = int(sys.argv[1]) if len(sys.argv) > 1 else 15

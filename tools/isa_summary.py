@@ -57,6 +57,12 @@ WANT = [
     ("../csrc_rank/vfm_elicit_design.hip", ["-ffp-contract=on"], "k_elicit_design<64, 2, 0>", "exact session, target-aware score, d = 128 (the benchmark shape), |.|"),
     ("../csrc_rank/vfm_elicit_design.hip", ["-ffp-contract=on"], "k_elicit_design<64, 2, 1>", "exact session, target-aware score, d = 128, softplus"),
     ("../csrc_rank/vfm_elicit_design.hip", ["-ffp-contract=on"], "k_elicit_design<64, 8, 0>", "exact session, target-aware score, d = 512, |.|"),
+    # the bound session: the same session loop with the bound fold-in's body as the fold of a round
+    # (--only elicit_bound --every elicit_bound: profiles/bound_session_isa.txt)
+    ("../csrc_rank/vfm_elicit_bound.hip", ["-ffp-contract=on"], "k_elicit_bound<8, 1, 0>", "bound session ('class'), moment scores, d <= 8 (the questionnaire's shape), |.|"),
+    ("../csrc_rank/vfm_elicit_bound.hip", ["-ffp-contract=on"], "k_elicit_bound<64, 2, 0>", "bound session, moment scores, d = 128 (the benchmark shape), |.|"),
+    ("../csrc_rank/vfm_elicit_bound.hip", ["-ffp-contract=on"], "k_elicit_bound<64, 2, 1>", "bound session, moment scores, d = 128, softplus"),
+    ("../csrc_rank/vfm_elicit_bound.hip", ["-ffp-contract=on"], "k_elicit_bound<64, 8, 0>", "bound session, moment scores, d = 512, |.|"),
     # fused Adam step of the ELBO variants (--only variant_step prints these alone; --every variant_step adds one line per instance)
     ("../csrc_var/vfm_variant_step.hip", ["-ffp-contract=on"], "k_vstep<8, 16, 1, true, false, true>", "variant step, d = 128 (the benchmark shape), closed form, learnable priors"),
     ("../csrc_var/vfm_variant_step.hip", ["-ffp-contract=on"], "k_vstep<8, 16, 1, false, true, false>", "variant step, d = 128, sampled objective, feature values, N(0,1) priors"),

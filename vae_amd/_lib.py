@@ -132,6 +132,10 @@ class FoldinBound(_Strict, C.Structure):
     ]
 
 
+# the bound field-form session (vfm_elicit_bound_f32) is declared in the same header
+ELICIT_BOUND_EXPORTS = ("vfm_elicit_bound_f32", "vfm_elicit_bound_workspace_bytes")
+
+
 class Elicit(_Strict, C.Structure):
     """`vfm_elicit_t` (tests/test_elicit_cpu.py checks the layout against gcc's)."""
     _fields_ = [
@@ -204,6 +208,30 @@ class ElicitSolve(_Strict, C.Structure):
         self.struct_size, self.abi_version = C.sizeof(type(self)), ABI_VERSION      # (VFM_STRUCT_INIT)
 
 
+class ElicitBound(_Strict, C.Structure):
+    """`vfm_elicit_bound_t`: vfm_elicit_solve_t's fields and n_iters (tests/test_elicit_bound_cpu.py checks the layout
+    against gcc's)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("abi_version", C.c_uint32),
+        ("U", C.c_int64), ("P", C.c_int64), ("H", C.c_int64), ("T", C.c_int64), ("n_ops", C.c_int64),
+        ("F", C.c_int32), ("d", C.c_int32), ("field", C.c_int32), ("key_col", C.c_int32), ("n_rounds", C.c_int32),
+        ("strategy", C.c_int32), ("flags", C.c_int32), ("reset", C.c_int32), ("write", C.c_int32),
+        ("lds_dim", C.c_int32), ("kl_weight", C.c_float), ("n_iters", C.c_int32),
+        ("seed", C.c_uint64),
+        ("entities", C.c_void_p), ("pool_ptr", C.c_void_p), ("pool_x", C.c_void_p), ("pool_y", C.c_void_p),
+        ("hist_ptr", C.c_void_p), ("hist_x", C.c_void_p), ("hist_y", C.c_void_p),
+        ("op_x", C.c_void_p), ("pool_op", C.c_void_p), ("hist_op", C.c_void_p),
+        ("entity_params", C.c_void_p), ("bias_params", C.c_void_p), ("scalars", C.c_void_p),
+        ("out_row", C.c_void_p), ("out_score", C.c_void_p), ("out_loss", C.c_void_p), ("out_theta", C.c_void_p),
+        ("out_mean", C.c_void_p), ("out_var", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size, self.abi_version = C.sizeof(type(self)), ABI_VERSION      # (VFM_STRUCT_INIT)
+
+
 # ---- target-aware elicitation (include/vfm_design.h)
 DESIGN_EXPORTS = ("vfm_design_workspace_bytes", "vfm_design_scores_f32", "vfm_design_elicit_f32")
 
@@ -231,7 +259,8 @@ class ElicitDesign(_Strict, C.Structure):
         self.struct_size, self.abi_version = C.sizeof(type(self)), ABI_VERSION      # (VFM_STRUCT_INIT)
 
 
-for _c in (Problem, Index, Pipe, Elicit, ElicitField, ElicitSolve, ElicitDesign, FoldinSolve, FoldinSplit, FoldinBound):
+for _c in (Problem, Index, Pipe, Elicit, ElicitField, ElicitSolve, ElicitBound, ElicitDesign, FoldinSolve, FoldinSplit,
+           FoldinBound):
     _c._names = frozenset(n for n, _ in _c._fields_)
 
 
@@ -330,6 +359,10 @@ def load():
     lib.vfm_foldin_bound_f32.restype = C.c_int
     lib.vfm_foldin_bound_workspace_bytes.argtypes = [i64, i64, i64, i32, i32]
     lib.vfm_foldin_bound_workspace_bytes.restype = i64
+    lib.vfm_elicit_bound_f32.argtypes = [C.POINTER(ElicitBound), vp]
+    lib.vfm_elicit_bound_f32.restype = C.c_int
+    lib.vfm_elicit_bound_workspace_bytes.argtypes = [i64, i64, i64, i64, i32, i32, i32]
+    lib.vfm_elicit_bound_workspace_bytes.restype = i64
     u64 = C.c_uint64
     lib.vfm_field_moments_post_f32.argtypes = [i64, i32, i32, i64, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, u64,
                                                vp, vp, vp, vp, vp]

@@ -91,7 +91,11 @@ _UNITS = [("vfm_abi.hip", "", _EXACT), ("vfm_index.hip", "", []), ("vfm_variants
           # bound fold-in (include/vfm_bound.h): the exact fold-in's preps, factorisation and rounding
           # (csrc_rank/vfm_foldin_solve_body.hpp) under weights of the Jaakkola-Jordan bound, and the fold-in's fp32 row
           # moments (csrc_rank/vfm_foldin_body.hpp) for the loss, hence their flag
-          ("csrc_rank/vfm_foldin_bound.hip", "", _EXACT)]
+          ("csrc_rank/vfm_foldin_bound.hip", "", _EXACT),
+          # bound elicitation session (include/vfm_bound.h: vfm_elicit_bound_f32): the exact sessions' loop and host path
+          # (csrc_rank/vfm_elicit_exact_body.hpp) with the bound fold-in's body (csrc_rank/vfm_foldin_bound_body.hpp) as
+          # the fold of a round, hence their flag
+          ("csrc_rank/vfm_elicit_bound.hip", "", _EXACT)]
 RANK_DIR = os.path.join(HERE, "csrc_rank")
 RANK_HDR = os.path.join(ROOT, "include", "vfm_rank.h")
 RANK_OPS = os.path.join(RANK_DIR, "vfm_rank_ops.cpp")
@@ -103,7 +107,7 @@ DESIGN_HDR = os.path.join(ROOT, "include", "vfm_design.h")
 DESIGN_OPS = os.path.join(RANK_DIR, "vfm_design_ops.cpp")
 SWEEP_HDR = os.path.join(ROOT, "include", "vfm_sweep.h")
 SWEEP_OPS = os.path.join(RANK_DIR, "vfm_sweep_ops.cpp")
-BOUND_HDR = os.path.join(ROOT, "include", "vfm_bound.h")      # (its op lives in vfm_foldin_ops.cpp)
+BOUND_HDR = os.path.join(ROOT, "include", "vfm_bound.h")      # (its ops live in vfm_foldin_ops.cpp and vfm_elicit_ops.cpp)
 VAR_DIR = os.path.join(HERE, "csrc_var")
 VAR_STEP_HDR = os.path.join(ROOT, "include", "vfm_variant_step.h")
 

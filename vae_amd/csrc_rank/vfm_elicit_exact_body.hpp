@@ -1,7 +1,8 @@
 // vfm_elicit_exact_body.hpp -- the exact elicitation session, once: ask, solve the respondent's closed-form optimum,
 // ask again -- every round of every respondent in one launch.  Used by k_elicit_solve (vfm_elicit_solve.hip: the
-// questions scored by the predictive moments) and k_elicit_design (vfm_elicit_design.hip: the target-aware score); each
-// of the two kernels is exact_session instantiated with its score.  Also the host path both entry points share: the
+// questions scored by the predictive moments), k_elicit_design (vfm_elicit_design.hip: the target-aware score) and
+// k_elicit_bound (vfm_elicit_bound.hip: a 'class' model, the fold of a round exchanged for the bound's rounds); each
+// of the kernels is exact_session instantiated with its score and its fold.  Also the host path both entry points share: the
 // workspace, the kernel arguments, the operand passes, the launch and the checks the two word alike.  Included inside
 // `namespace vfm { namespace {` of a unit, after vfm_foldin_solve_body.hpp, vfm_elicit_host.hpp and
 // vfm_elicit_field_score.hpp.
@@ -103,8 +104,25 @@ __device__ __forceinline__ void put_moments(const ElicitFieldArgs& a, int q, int
   a.out_var[(int64_t)q * a.P + p0 + p] = var;
 }
 
-template <class Score, int W, int CPL, int LINK>
-__device__ __forceinline__ void exact_session(const typename Score::Args& s) {
+// The fold of a round, the second compile-time policy of the session: the closed-form optimum of a 'reg' model
+// (solve_body), the present one; BoundFold of vfm_elicit_bound.hip runs the Jaakkola-Jordan rounds of a 'class' model
+// (bound_body of vfm_foldin_bound_body.hpp) in its place.
+//   lds_doubles(d)             doubles of LDS of its own, between the triangle and the score's
+//   run<W, CPL, LINK>(s, f, rows, n, g, sm, Hm, own, precf, prec, loss, store)   the fold of respondent g over its n rows
+//                              from theta_e in pf; solve_body's contract: pf rewritten, store(pf) by every thread after
+//                              the barrier that publishes it, the loss by wave 0, no barrier at the end
+struct SolveFold {
+  __host__ __device__ static int64_t lds_doubles(int) { return 0; }
+  template <int W, int CPL, int LINK, class Args, class Rows, class Store>
+  __device__ __forceinline__ static void run(const Args& s, const FoldArgs& f, const Rows& rows, int64_t n, int64_t,
+                                             double* sm, double* Hm, double*, float precf, double prec, float* loss,
+                                             Store&& store) {
+    solve_body<W, CPL, LINK>(f, s.ops64, s.cm64, rows, n, sm, Hm, precf, prec, loss, store);
+  }
+};
+
+template <class Score, int W, int CPL, int LINK, class Fold = SolveFold, class Args>
+__device__ __forceinline__ void exact_session(const Args& s) {
   extern __shared__ double sm[];
   constexpr int DP = W * CPL;
   constexpr bool SP = LINK == LINK_SOFTPLUS;
@@ -114,7 +132,8 @@ __device__ __forceinline__ void exact_session(const typename Score::Args& s) {
   const int d = f.d, d1 = d + 1, Q = a.Q;
   float* pf = (float*)(sm + 7 * d1);     // theta_e: mu_w, mu [d] | s_w, s [d]  (solve_body's)
   double* Hl = sm + 8 * d1;
-  double* own = Hl + tri(s.sl.cap_dim);                     // the score's own doubles
+  double* fown = Hl + tri(s.sl.cap_dim);                    // the fold's own doubles
+  double* own = fown + Fold::lds_doubles(d);                // the score's own doubles
   long long* rpos = (long long*)(own + Score::lds_doubles(d));  // [NW] the waves' winners
   float* rsc = (float*)(rpos + NW);                         // [NW]
   float* uth = rsc + NW;                                    // [3 DP + 2] the candidate operands of theta_e
@@ -206,8 +225,8 @@ __device__ __forceinline__ void exact_session(const typename Score::Args& s) {
       if (act) {
         ++n;
         const int m = solve_dim(n, d);
-        solve_body<W, CPL, LINK>(f, s.ops64, s.cm64, rows, n, sm, m <= s.sl.cap_dim ? Hl : Hg, precf, prec,
-                                 a.out_loss + g * Q + q, [&](const float*) { put_theta(q); });
+        Fold::template run<W, CPL, LINK>(s, f, rows, n, g, sm, m <= s.sl.cap_dim ? Hl : Hg, fown, precf, prec,
+                                         a.out_loss + g * Q + q, [&](const float*) { put_theta(q); });
       } else {
         put_theta(q);
       }
@@ -322,13 +341,14 @@ int launch_exact_session_preps(const P* p, bool sp, const ElicitSolveArgs& s, hi
 }
 
 // One launch of the session kernel.  kernel_of(IntC<W>, IntC<CPL>, IntC<LINK>): the unit's instance.
-template <class Score, class KernelOf>
-void launch_exact_session(bool sp, const typename Score::Args& s, unsigned grid, hipStream_t st, KernelOf&& kernel_of) {
+template <class Score, class Fold = SolveFold, class Args, class KernelOf>
+void launch_exact_session(bool sp, const Args& s, unsigned grid, hipStream_t st, KernelOf&& kernel_of) {
   const int d = s.e.f.d;
   for_link(sp, [&](auto link) {
     for_shape(shape_of(d), [&](auto w, auto c) {
       constexpr int DP = decltype(w)::value * decltype(c)::value;
-      const size_t shm = (size_t)(lds_doubles(d, s.sl.cap_dim) + Score::lds_doubles(d)) * 8 + (size_t)session_tail_bytes(DP);
+      const size_t shm = (size_t)(lds_doubles(d, s.sl.cap_dim) + Fold::lds_doubles(d) + Score::lds_doubles(d)) * 8 +
+                         (size_t)session_tail_bytes(DP);
       const auto k = kernel_of(w, c, link);
       // (more than 64 KiB of dynamic LDS: state the size; a runtime that needs no opt-in ignores it)
       (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);

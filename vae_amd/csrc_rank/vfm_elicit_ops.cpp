@@ -1,6 +1,6 @@
 // vfm_elicit_ops.cpp -- torch.ops.vfm_hip.{elicit, elicit_workspace_bytes, elicit_field, elicit_field_workspace_bytes,
-// elicit_solve, elicit_solve_workspace_bytes}: the TORCH_LIBRARY fragment over
-// include/vfm_elicit.h.  Like vfm_foldin_ops.cpp it only validates tensors, takes the current HIP stream of the tensors'
+// elicit_solve, elicit_solve_workspace_bytes, elicit_bound, elicit_bound_workspace_bytes}: the TORCH_LIBRARY fragment over
+// include/vfm_elicit.h and the session of include/vfm_bound.h.  Like vfm_foldin_ops.cpp it only validates tensors, takes the current HIP stream of the tensors'
 // device and forwards raw pointers; all arithmetic is in the HIP kernels.
 #include <ATen/ATen.h>
 #include <c10/hip/HIPGuard.h>
@@ -11,6 +11,7 @@
 
 #include <initializer_list>
 
+#include "vfm_bound.h"
 #include "vfm_elicit.h"
 
 namespace {
@@ -191,14 +192,16 @@ int64_t elicit_solve_workspace_bytes(int64_t U, int64_t P, int64_t n_ops, int64_
   return b;
 }
 
-// the exact field-form session: elicit_field's tensors, the exact fold-in's options in place of Adam's
-void elicit_solve(const Tensor& entities, const Tensor& pool_ptr, const Tensor& pool_x, const Tensor& pool_y,
-                  const optional<Tensor>& hist_ptr, const optional<Tensor>& hist_x, const optional<Tensor>& hist_y,
-                  const Tensor& op_x, const Tensor& pool_op, const optional<Tensor>& hist_op, Tensor entity, Tensor bias,
-                  const Tensor& scalars, Tensor workspace, Tensor out_row, Tensor out_score, Tensor out_loss,
-                  const optional<Tensor>& out_theta, const optional<Tensor>& out_mean, const optional<Tensor>& out_var,
-                  int64_t field, int64_t key_col, int64_t n_rounds, int64_t strategy, int64_t flags, int64_t reset,
-                  int64_t write, int64_t lds_dim, double kl_weight, int64_t seed) {
+// The tensors, sizes and options that the exact and the bound field-form sessions name alike, checked and put into p.
+// S: vfm_elicit_solve_t or vfm_elicit_bound_t; the op adds its own options and the workspace check is the library's.
+template <class S>
+void fill_exact_session(S& p, const Tensor& entities, const Tensor& pool_ptr, const Tensor& pool_x, const Tensor& pool_y,
+                        const optional<Tensor>& hist_ptr, const optional<Tensor>& hist_x, const optional<Tensor>& hist_y,
+                        const Tensor& op_x, const Tensor& pool_op, const optional<Tensor>& hist_op, Tensor& entity,
+                        Tensor& bias, const Tensor& scalars, Tensor& workspace, Tensor& out_row, Tensor& out_score,
+                        Tensor& out_loss, const optional<Tensor>& out_theta, const optional<Tensor>& out_mean,
+                        const optional<Tensor>& out_var, int64_t field, int64_t key_col, int64_t n_rounds, int64_t strategy,
+                        int64_t flags, int64_t reset, int64_t write, int64_t lds_dim, double kl_weight, int64_t seed) {
   check_session_tensors({{entities, at::kLong, "entities"}, {pool_ptr, at::kLong, "pool_ptr"}, {pool_x, at::kLong, "pool_x"},
                          {pool_y, at::kFloat, "pool_y"}, {op_x, at::kLong, "op_x"}, {pool_op, at::kLong, "pool_op"}},
                         entity, bias, scalars, workspace, out_row, out_score, out_loss, n_rounds);
@@ -209,7 +212,6 @@ void elicit_solve(const Tensor& entities, const Tensor& pool_ptr, const Tensor& 
               "op_x must be [n_ops, F], pool_op must hold one operand per pool row");
   TORCH_CHECK(out_row.numel() >= U * Q && out_score.numel() >= U * Q && out_loss.numel() >= U * Q,
               "out_row, out_score, out_loss must be [U, Q]");
-  vfm_elicit_solve_t p;
   VFM_STRUCT_INIT(p);
   p.U = U; p.P = P; p.T = entity.size(0); p.F = (int32_t)F; p.d = (int32_t)(entity.size(1) / 2);
   p.field = (int32_t)field; p.key_col = (int32_t)key_col; p.n_rounds = (int32_t)Q; p.strategy = (int32_t)strategy;
@@ -249,9 +251,49 @@ void elicit_solve(const Tensor& entities, const Tensor& pool_ptr, const Tensor& 
   }
   p.workspace = workspace.data_ptr();
   p.workspace_bytes = workspace.numel();
+}
+
+// the exact field-form session: elicit_field's tensors, the exact fold-in's options in place of Adam's
+void elicit_solve(const Tensor& entities, const Tensor& pool_ptr, const Tensor& pool_x, const Tensor& pool_y,
+                  const optional<Tensor>& hist_ptr, const optional<Tensor>& hist_x, const optional<Tensor>& hist_y,
+                  const Tensor& op_x, const Tensor& pool_op, const optional<Tensor>& hist_op, Tensor entity, Tensor bias,
+                  const Tensor& scalars, Tensor workspace, Tensor out_row, Tensor out_score, Tensor out_loss,
+                  const optional<Tensor>& out_theta, const optional<Tensor>& out_mean, const optional<Tensor>& out_var,
+                  int64_t field, int64_t key_col, int64_t n_rounds, int64_t strategy, int64_t flags, int64_t reset,
+                  int64_t write, int64_t lds_dim, double kl_weight, int64_t seed) {
+  vfm_elicit_solve_t p;
+  fill_exact_session(p, entities, pool_ptr, pool_x, pool_y, hist_ptr, hist_x, hist_y, op_x, pool_op, hist_op, entity, bias,
+                     scalars, workspace, out_row, out_score, out_loss, out_theta, out_mean, out_var, field, key_col,
+                     n_rounds, strategy, flags, reset, write, lds_dim, kl_weight, seed);
   c10::hip::HIPGuard guard(entities.get_device());
   const int rc = vfm_elicit_solve_f32(&p, (void*)c10::hip::getCurrentHIPStream(entities.get_device()).stream());
   TORCH_CHECK(rc == 0, "vfm_elicit_solve_f32 failed (code ", rc, "): ", vfm_last_error());
+}
+
+int64_t elicit_bound_workspace_bytes(int64_t U, int64_t P, int64_t H, int64_t n_ops, int64_t d, int64_t n_rounds,
+                                     int64_t lds_dim) {
+  const int64_t b = vfm_elicit_bound_workspace_bytes(U, P, H, n_ops, (int32_t)d, (int32_t)n_rounds, (int32_t)lds_dim);
+  TORCH_CHECK(b >= 0, "vfm_elicit_bound_workspace_bytes: bad arguments");
+  return b;
+}
+
+// the bound field-form session ('class' models): elicit_solve's tensors and options, and the rounds of the bound per fold
+void elicit_bound(const Tensor& entities, const Tensor& pool_ptr, const Tensor& pool_x, const Tensor& pool_y,
+                  const optional<Tensor>& hist_ptr, const optional<Tensor>& hist_x, const optional<Tensor>& hist_y,
+                  const Tensor& op_x, const Tensor& pool_op, const optional<Tensor>& hist_op, Tensor entity, Tensor bias,
+                  const Tensor& scalars, Tensor workspace, Tensor out_row, Tensor out_score, Tensor out_loss,
+                  const optional<Tensor>& out_theta, const optional<Tensor>& out_mean, const optional<Tensor>& out_var,
+                  int64_t field, int64_t key_col, int64_t n_rounds, int64_t strategy, int64_t flags, int64_t reset,
+                  int64_t write, int64_t lds_dim, double kl_weight, int64_t seed, int64_t n_iters) {
+  vfm_elicit_bound_t p;
+  fill_exact_session(p, entities, pool_ptr, pool_x, pool_y, hist_ptr, hist_x, hist_y, op_x, pool_op, hist_op, entity, bias,
+                     scalars, workspace, out_row, out_score, out_loss, out_theta, out_mean, out_var, field, key_col,
+                     n_rounds, strategy, flags, reset, write, lds_dim, kl_weight, seed);
+  TORCH_CHECK(n_iters >= 1 && n_iters <= INT32_MAX, "n_iters must be >= 1");
+  p.n_iters = (int32_t)n_iters;
+  c10::hip::HIPGuard guard(entities.get_device());
+  const int rc = vfm_elicit_bound_f32(&p, (void*)c10::hip::getCurrentHIPStream(entities.get_device()).stream());
+  TORCH_CHECK(rc == 0, "vfm_elicit_bound_f32 failed (code ", rc, "): ", vfm_last_error());
 }
 
 }  // namespace
@@ -280,4 +322,13 @@ TORCH_LIBRARY_FRAGMENT(vfm_hip, m) {
         "Tensor(f!) out_loss, Tensor(g!)? out_theta, Tensor(h!)? out_mean, Tensor(i!)? out_var, int field, int key_col, "
         "int n_rounds, int strategy, int flags, int reset, int write, int lds_dim, float kl_weight, int seed) -> ()",
         &elicit_solve);
+  m.def("elicit_bound_workspace_bytes(int U, int P, int H, int n_ops, int d, int n_rounds, int lds_dim) -> int",
+        &elicit_bound_workspace_bytes);
+  m.def("elicit_bound(Tensor entities, Tensor pool_ptr, Tensor pool_x, Tensor pool_y, Tensor? hist_ptr, Tensor? hist_x, "
+        "Tensor? hist_y, Tensor op_x, Tensor pool_op, Tensor? hist_op, Tensor(a!) entity_params, "
+        "Tensor(b!) bias_params, Tensor scalars, Tensor(c!) workspace, Tensor(d!) out_row, Tensor(e!) out_score, "
+        "Tensor(f!) out_loss, Tensor(g!)? out_theta, Tensor(h!)? out_mean, Tensor(i!)? out_var, int field, int key_col, "
+        "int n_rounds, int strategy, int flags, int reset, int write, int lds_dim, float kl_weight, int seed, "
+        "int n_iters) -> ()",
+        &elicit_bound);
 }

@@ -19,6 +19,9 @@
 //   E  wave 0 evaluates B_e at the written fp32 parameters: per row the fp32 moments of the closed-form final pass
 //      (fold_stage_rows over that row alone, the same lane groups), xi = sqrtf(.), the rows added in row order in fp64.
 //   VFM_FOLDIN_OBJECTIVE runs E alone, at the table row.
+// The per-entity work (the start from the fp32 parameters in LDS, the rounds, D's rounding and E) is bound_body of
+// vfm_foldin_bound_body.hpp, shared with the bound elicitation session (vfm_elicit_bound.hip); this kernel loads the
+// entity's table row into LDS for it and writes the table row from its store step.
 // Every sum has a fixed order that depends on the entity's rows and d alone: no atomics, no host sync, the same bits
 // whichever other entities share the launch and wherever the triangle lives.
 #include <hip/hip_runtime.h>
@@ -38,6 +41,7 @@ namespace {
 
 #include "vfm_foldin_body.hpp"       // FoldArgs, k_foldin_prep, fold_stage_rows, the host side
 #include "vfm_foldin_solve_body.hpp" // k_foldin_solve_prep, chol_solve, put_params, the operand block and the slabs
+#include "vfm_foldin_bound_body.hpp" // k_foldin_bound_prep, bound_body, bound_loss
 
 struct BoundArgs {
   FoldArgs f;                            // (cap = 0; n_steps: the rounds; f.ops / f.opc: the fp32 operands of the loss)
@@ -48,101 +52,9 @@ struct BoundArgs {
   SolveSlabs sl;                         // the slabs and the LDS rule of the triangle
 };
 
-// LDS of a block in doubles: the exact fold-in's and sigma_w^2, sigma_k^2 [d] behind the triangle
-__host__ __device__ inline int64_t bound_lds_doubles(int d, int cap_dim) { return lds_doubles(d, cap_dim) + d + 1; }
-
 inline int64_t off_cv64(int64_t n_ops, int d) { return off_slabs(n_ops, d); }
 inline int64_t off_wrow(int64_t n_ops, int d) { return off_cv64(n_ops, d) + round_up(n_ops * 8, 256); }
 inline int64_t off_bound_slabs(int64_t R, int64_t n_ops, int d) { return off_wrow(n_ops, d) + round_up(R * 8, 256); }
-
-template <int LINK>
-__global__ __launch_bounds__(FB) void k_foldin_bound_prep(int64_t n_ops, int F, int d, int col, int64_t T,
-                                                          const int64_t* __restrict__ opx, const float* __restrict__ ent,
-                                                          const float* __restrict__ bias, const float* __restrict__ scal,
-                                                          double* __restrict__ cvo) {
-#pragma clang fp contract(on)
-  const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (o >= n_ops) return;
-  const int64_t* xr = opx + o * F;
-  bool ok = true;
-  for (int f = 0; f < F; ++f) ok = ok && (f == col || (xr[f] >= 0 && xr[f] < T));
-  if (!ok) {
-    cvo[o] = __builtin_nan("");
-    return;
-  }
-  const double sg0 = link_d<LINK>(scal[2]);
-  double cv = sg0 * sg0;
-  for (int f = 0; f < F; ++f) {
-    if (f == col) continue;
-    const double sw = link_d<LINK>(bias[xr[f] * 2 + 1]);
-    cv += sw * sw;
-  }
-  for (int k = 0; k < d; ++k) {
-    double sm = 0., ss = 0., sss = 0.;
-    for (int f = 0; f < F; ++f) {
-      if (f == col) continue;
-      const float* row = ent + xr[f] * 2 * (int64_t)d;
-      const double m = row[k], sg = link_d<LINK>(row[d + k]), s2 = sg * sg;
-      sm += m; ss += s2; sss += s2 * s2;
-    }
-    double lin = 0.;
-    for (int f = 0; f < F; ++f) {
-      if (f == col) continue;
-      const float* row = ent + xr[f] * 2 * (int64_t)d;
-      const double m = row[k], sg = link_d<LINK>(row[d + k]), oth = sm - m;
-      lin += sg * sg * oth * oth;
-    }
-    cv += 0.5 * (ss * ss - sss) + lin;
-  }
-  cvo[o] = cv;
-}
-
-// phase E: B_e at the fp32 parameters pf = [mu_w, mu [d] | s_w, s [d]] (LDS), by wave 0; its 64 / W lane groups all
-// hold this entity, lane l of a group owns coordinates j W + l
-template <int W, int CPL, int LINK, class Rows>
-__device__ __forceinline__ void bound_loss(const FoldArgs& a, const Rows& rows, int64_t n, const float* pf, int lane,
-                                           float* loss) {
-#pragma clang fp contract(on)
-  constexpr int DP = W * CPL;
-  const int d = a.d, d1 = d + 1, l = lane % W;
-  float mu[CPL], sg[CPL];
-  bool vk[CPL];
-#pragma unroll
-  for (int j = 0; j < CPL; ++j) {
-    const int kc = j * W + l;
-    vk[j] = kc < d;
-    mu[j] = vk[j] ? pf[1 + kc] : 0.f;
-    sg[j] = link_f<LINK>(vk[j] ? pf[d1 + 1 + kc] : prior_s<LINK>());
-  }
-  const float muw = pf[0], sgw = link_f<LINK>(pf[d1]);
-  double lsum = 0.0;
-  for (int64_t i = 0; i < n; ++i) {
-    float SA[CPL], SB[CPL], SC[CPL], Scv = 0.f;
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) SA[j] = SB[j] = SC[j] = 0.f;
-    fold_stage_rows<W, CPL>(a, rows, i, i + 1, l, nullptr, nullptr, SA, SB, SC, Scv);   // (a.cap = 0: nothing staged)
-    const int64_t o = rows.op(i);
-    float p = 0.f;
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) p = fmaf(mu[j], a.ops[o * 3 * DP + j * W + l], p);
-    const float Ef = (a.opc[o * 2] + muw) + group_sum<W>(p);
-    float vq = 0.f;
-#pragma unroll
-    for (int j = 0; j < CPL; ++j) vq += fmaf(mu[j] * mu[j], SA[j], fmaf(sg[j] * sg[j], SB[j], mu[j] * SC[j]));
-    const float Vf = (Scv + sgw * sgw) + group_sum<W>(vq);
-    float x2 = fmaf(Ef, Ef, Vf);
-    x2 = x2 < 0.f ? 0.f : x2;            // (a NaN stays a NaN)
-    const float xi = sqrtf(x2);
-    const float t = -(rows.y(i) - 0.5f) * Ef + 0.5f * xi + log1pf(expf(-xi));
-    lsum += (double)t;
-  }
-  float klq = 0.f;
-#pragma unroll
-  for (int j = 0; j < CPL; ++j)
-    if (vk[j]) klq += kl_std_normal(mu[j], sg[j]);
-  klq = group_sum<W>(klq) + kl_std_normal(muw, sgw);
-  if (lane == 0) *loss = (float)(lsum + (double)a.klw * (double)klq);
-}
 
 template <int W, int CPL, int LINK>
 __global__ __launch_bounds__(FB) void k_foldin_bound(const BoundArgs s) {
@@ -151,26 +63,15 @@ __global__ __launch_bounds__(FB) void k_foldin_bound(const BoundArgs s) {
   const FoldArgs& a = s.f;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int d = a.d, d1 = d + 1;
-  double* Dd = sm;                       // D                                  [d + 1]  (0: the first-order weight)
-  double* Di = Dd + d1;                  // 1 / D
-  double* bv = Di + d1;                  // primal: b; dual: D^-1 b
-  double* yv = bv + d1;                  // the right-hand side, then L^-1 of it; between two rounds: theta
-  double* dv = yv + d1;                  // 1 / L_jj
-  double* xv = dv + d1;                  // the solution of the system
-  double* SBd = xv + d1;                 // sum_r w_r, sum_r w_r (A_rk + M_rk^2)
-  float* pf = (float*)(SBd + d1);        // the fp32 parameters: mu_w, mu [d] | s_w, s [d]
+  float* pf = (float*)(sm + 7 * d1);     // the fp32 parameters: mu_w, mu [d] | s_w, s [d]  (bound_body's)
   double* Hl = sm + 8 * d1;              // the triangle while it fits
   double* sg2 = Hl + tri(s.sl.cap_dim);  // sigma_w^2, sigma_k^2 [d]
-  double* th = yv;
   double* Hg = s.sl.slab ? s.sl.slab + (int64_t)blockIdx.x * s.sl.slab_elems : nullptr;
-  const double kl = a.klw;
-  const int64_t os = 3 * (int64_t)d;     // stride of an fp64 operand
 
   for (int64_t g = blockIdx.x; g < a.E; g += gridDim.x) {
     const int64_t r0 = min(max(a.ptr[g], (int64_t)0), a.R);
     const int64_t n = min(max(a.ptr[g + 1], r0), a.R) - r0;
     const int64_t e = a.ent[g];
-    const bool dual = n <= d;
     const int m = solve_dim(n, d);
     double* Hm = m <= s.sl.cap_dim ? Hl : Hg;
     if (e < 0 || e >= a.T || !Hm) {      // (block-uniform)
@@ -180,158 +81,30 @@ __global__ __launch_bounds__(FB) void k_foldin_bound(const BoundArgs s) {
     const ListRows rows{a, r0};
     float* erow = a.entity + e * 2 * (int64_t)d;
 
-    if (a.mode == VFM_FOLDIN_OBJECTIVE) {
+    // ---- the fp32 parameters at the entity's row: where B_e is evaluated, or where xi^(0) is taken
+    if (a.mode == VFM_FOLDIN_OBJECTIVE || !a.reset) {
       for (int c = tid; c < d1; c += FB) {
         pf[c] = c ? erow[c - 1] : a.bias[e * 2];
         pf[d1 + c] = c ? erow[d + c - 1] : a.bias[e * 2 + 1];
       }
-    } else {
-      // ---- the start: xi^(0) is taken at the entity's row, or at the prior
-      for (int c = tid; c < d1; c += FB) {
-        double t0 = 0., v0 = 1.;
-        if (!a.reset) {
-          const double sg = link_d<LINK>(c ? erow[d + c - 1] : a.bias[e * 2 + 1]);
-          t0 = c ? erow[c - 1] : a.bias[e * 2];
-          v0 = sg * sg;
-        }
-        th[c] = t0;
-        sg2[c] = v0;
-      }
-      __syncthreads();
-
-      for (int it = 0; it < a.n_steps; ++it) {
-        // ---- X: the rows' weights at the current iterate
-        for (int64_t i = wv; i < n; i += FB / 64) {
-          const int64_t o = rows.op(i);
-          const double* op = s.ops64 + o * os;
-          double pe = 0., pv = 0.;
-          for (int k = lane; k < d; k += 64) {
-            const double M = op[k], A = op[d + k], C = op[2 * d + k], mu = th[k + 1];
-            pe += mu * M;
-            pv += mu * mu * A + sg2[k + 1] * (A + M * M) + mu * C;
-          }
-          pe = wave_sum_d(pe);
-          pv = wave_sum_d(pv);
-          const double Ef = s.cm64[o] + th[0] + pe;
-          const double Vf = s.cv64[o] + sg2[0] + pv;
-          double x2 = Ef * Ef + Vf;
-          x2 = x2 < 0. ? 0. : x2;        // (a NaN stays a NaN)
-          const double xi = sqrt(x2);
-          const double w = xi < 1e-3 ? 0.25 - x2 / 48.0 : tanh(0.5 * xi) / (2.0 * xi);
-          if (lane == 0) s.wrow[r0 + i] = w;
-        }
-        __syncthreads();
-
-        // ---- A: the weighted row sums of each coordinate
-        for (int c = tid; c < d1; c += FB) {
-          double SA = 0., SB = 0., SC = 0., bM = 0.;
-          if (c == 0) {
-            for (int64_t i = 0; i < n; ++i) {
-              const double w = s.wrow[r0 + i];
-              SB += w;
-              bM += ((double)rows.y(i) - 0.5) - w * s.cm64[rows.op(i)];
-            }
-          } else {
-            for (int64_t i = 0; i < n; ++i) {
-              const int64_t o = rows.op(i);
-              const double* op = s.ops64 + o * os + (c - 1);
-              const double M = op[0], A = op[d], C = op[2 * d], w = s.wrow[r0 + i];
-              const double t = ((double)rows.y(i) - 0.5) - w * s.cm64[o];
-              SA += w * A;
-              SB += w * (A + M * M);
-              SC += w * C;
-              bM += t * M;
-            }
-          }
-          const double D = kl + SA, b = bM - 0.5 * SC;
-          Dd[c] = D;
-          Di[c] = 1.0 / D;
-          bv[c] = dual ? b / D : b;
-          SBd[c] = SB;
-        }
-        __syncthreads();
-
-        // ---- B: the system and its right-hand side
-        if (dual) {
-          const int64_t np = tri(m);
-          for (int64_t p = wv; p < np; p += FB / 64) {
-            int i, j;
-            tri_decode(p, i, j);
-            const double* Mi = s.ops64 + rows.op(i) * os;
-            const double* Mj = s.ops64 + rows.op(j) * os;
-            double acc = 0.;
-            for (int k = lane; k < d; k += 64) acc += Mi[k] * Mj[k] * Di[k + 1];
-            acc = wave_sum_d(acc);
-            if (lane == 0) Hm[p] = acc + Di[0] + (i == j ? 1.0 / s.wrow[r0 + i] : 0.0);
-          }
-          for (int i = wv; i < m; i += FB / 64) {
-            const double* Mi = s.ops64 + rows.op(i) * os;
-            double acc = 0.;
-            for (int k = lane; k < d; k += 64) acc += Mi[k] * bv[k + 1];
-            acc = wave_sum_d(acc);
-            if (lane == 0) yv[i] = acc + bv[0];
-          }
-        } else {
-          const int64_t np = tri(d1);
-          for (int64_t p = tid; p < np; p += FB) {
-            int i, j;
-            tri_decode(p, i, j);
-            double acc = 0.;
-            if (i == 0) {
-              for (int64_t r = 0; r < n; ++r) acc += s.wrow[r0 + r];
-            } else if (j == 0) {
-              for (int64_t r = 0; r < n; ++r) acc += s.wrow[r0 + r] * s.ops64[rows.op(r) * os + (i - 1)];
-            } else {
-              for (int64_t r = 0; r < n; ++r) {
-                const double* op = s.ops64 + rows.op(r) * os;
-                acc += s.wrow[r0 + r] * op[i - 1] * op[j - 1];
-              }
-            }
-            Hm[p] = acc + (i == j ? Dd[i] : 0.0);
-          }
-          for (int c = tid; c < d1; c += FB) yv[c] = bv[c];
-        }
-        __syncthreads();
-
-        // ---- C: the factorisation and the two substitutions
-        chol_solve(Hm, yv, dv, xv, m);
-
-        // ---- the iterate, in fp64: the means and the scales' closed forms
-        for (int c = tid; c < d1; c += FB) {
-          double t;
-          if (dual) {
-            double acc = 0.;
-            if (c == 0) {
-              for (int i = 0; i < m; ++i) acc += xv[i];
-            } else {
-              for (int i = 0; i < m; ++i) acc += s.ops64[rows.op(i) * os + (c - 1)] * xv[i];
-            }
-            t = bv[c] - Di[c] * acc;
-          } else {
-            t = xv[c];
-          }
-          th[c] = t;
-          sg2[c] = kl / (kl + SBd[c]);
-        }
-        __syncthreads();
-      }
-
-      // ---- D: rounded to fp32 once and written
-      for (int c = tid; c < d1; c += FB) put_params<LINK>(pf, d1, c, th[c], kl, 1.0, SBd[c]);
-      __syncthreads();
-      for (int k = tid; k < d; k += FB) {
-        erow[k] = pf[1 + k];
-        erow[d + k] = pf[d1 + 1 + k];
-      }
-      if (tid == 0) {
-        a.bias[e * 2] = pf[0];
-        a.bias[e * 2 + 1] = pf[d1];
-      }
     }
     __syncthreads();
 
-    // ---- E: B_e at the fp32 parameters
-    if (wv == 0) bound_loss<W, CPL, LINK>(a, rows, n, pf, lane, a.loss + g);
+    if (a.mode == VFM_FOLDIN_OBJECTIVE) {
+      if (wv == 0) bound_loss<W, CPL, LINK>(a, rows, n, pf, lane, a.loss + g);
+    } else {
+      bound_body<W, CPL, LINK>(a, s.ops64, s.cm64, s.cv64, s.wrow + r0, rows, n, a.reset != 0, sm, Hm, sg2, a.loss + g,
+                               [&](const float*) {           // the table row, rounded once
+                                 for (int k = tid; k < d; k += FB) {
+                                   erow[k] = pf[1 + k];
+                                   erow[d + k] = pf[d1 + 1 + k];
+                                 }
+                                 if (tid == 0) {
+                                   a.bias[e * 2] = pf[0];
+                                   a.bias[e * 2 + 1] = pf[d1];
+                                 }
+                               });
+    }
     __syncthreads();                     // (pf and the iterate are rewritten by the next entity)
   }
 }
@@ -412,12 +185,7 @@ int vfm_foldin_bound_f32(const vfm_foldin_bound_t* p, void* stream) {
 
   if (p->n_ops > 0) {
     if (int rc = vfm::launch_solve_preps(sp, a, p->n_ops, p->op_x, w, st)) return rc;
-    const unsigned nb = (unsigned)((p->n_ops + vfm::FB - 1) / vfm::FB);
-    vfm::for_link(sp, [&](auto link) {
-      hipLaunchKernelGGL(vfm::k_foldin_bound_prep<decltype(link)::value>, dim3(nb), dim3(vfm::FB), 0, st, p->n_ops, a.F,
-                         a.d, a.col, a.T, p->op_x, a.entity, a.bias, a.scal, cv64);
-    });
-    if (int rc = launch_status("k_foldin_bound_prep")) return rc;
+    if (int rc = vfm::launch_bound_prep(sp, a, p->n_ops, p->op_x, cv64, st)) return rc;
   }
   vfm::launch(f, sp, s, grid, shm, st);
   return launch_status("k_foldin_bound");

@@ -8,7 +8,8 @@ the pool and of the history once (stable sorts: the caller's order is kept withi
 the caller's pool order; the sessions themselves are one HIP launch (plus one operand pass for the closed form)
 through torch.ops.vfm_hip.elicit.  `run_field` is the same for the entities of any one column of a model with any
 number of fields (vfm_elicit_field_f32): full rows, one operand per distinct context.  `run_field_exact` is the field
-form with each round's Adam fit replaced by the exact fold-in's closed-form optimum (vfm_elicit_solve_f32).
+form with each round's Adam fit replaced by the exact fold-in's closed-form optimum (vfm_elicit_solve_f32), and
+`run_field_bound` the same for 'class' models with the bound fold-in's rounds (include/vfm_bound.h: vfm_elicit_bound_f32).
 """
 from __future__ import annotations
 
@@ -285,6 +286,79 @@ def run_field_exact(model, pool, y_pool, n_questions, field=0, strategy="varianc
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the bound field form ('class' models): each round's Adam fit replaced by the bound fold-in (vfm_elicit_bound_f32)
+# ---------------------------------------------------------------------------------------------------------------------
+DESIGN_NEEDS_REG = ("strategy 'design' is not available for the bound sessions: its score is the drop of the optimum's "
+                    "scales, which for a 'reg' model depend on the rows alone; under the bound the scales of the optimum "
+                    "depend on the answers through xi, so there is no answer-free score to rank the questions by")
+
+
+def check_args_field_bound(model, pool, y_pool, n_questions, field, strategy, history, kl_weight, n_iters, key_field):
+    """Validate a bound field-form session call (no GPU needed): the bound fold-in's conditions ('class', kl_weight > 0
+    and finite, n_iters >= 1, labels in {0, 1}), F >= 2, then check_args_field's pool and history checks."""
+    if model.output != "class":
+        raise ValueError("the bound session needs a 'class' model (Bernoulli likelihood): a 'reg' model has the exact "
+                         "optimum itself; use elicit_field_exact")
+    if strategy == "design":
+        raise ValueError(DESIGN_NEEDS_REG)
+    if not float(kl_weight) > 0.0 or not math.isfinite(float(kl_weight)):
+        raise ValueError("kl_weight must be > 0 and finite: the prior term is what makes each system positive definite")
+    if isinstance(n_iters, bool) or int(n_iters) != n_iters or int(n_iters) < 1:
+        raise ValueError("n_iters must be an integer >= 1")
+    if model.F < 2:
+        raise ValueError("elicit_field_bound needs a model with at least two fields")
+    x, y, hx, hy, _, code, field, kf = check_args_field(model, pool, y_pool, n_questions, field, strategy, history, 0,
+                                                        0.0, "sampled", 1, kl_weight, key_field)
+    for v, what in ((y, "y_pool"), (hy, "the history's y")):
+        if v is not None and v.numel() and not bool(((v == 0) | (v == 1)).all()):
+            raise ValueError(f"{what} must hold the labels 0 and 1 of a 'class' model")
+    return x, y, hx, hy, code, field, kf
+
+
+def run_field_bound(model, pool, y_pool, n_questions, field=0, strategy="variance", history=None, seed=0, kl_weight=1.0,
+                    n_iters=8, reset=False, write=False, return_moments=False, return_theta=False, key_field=None,
+                    lds_dim=-1):
+    """The bound sessions of every entity of column `field` of the pool (VFM.elicit_field_bound documents the arguments
+    and the result): run_field's lists and operands, and one call of torch.ops.vfm_hip.elicit_bound."""
+    x, y, hx, hy, code, field, kf = check_args_field_bound(model, pool, y_pool, n_questions, field, strategy, history,
+                                                           kl_weight, n_iters, key_field)
+    if int(lds_dim) < -1:
+        raise ValueError("lds_dim must be -1 or >= 0")
+    ops._need_cuda(model._flat, "the model's parameters")
+    dev, d, Q = model.device, model.d, int(n_questions)
+    order, ents, ptr = pool_lists(x, field)
+    px, ys = x[order].contiguous(), y[order].contiguous()
+    U, P = ents.numel(), px.shape[0]
+    hptr = hxs = hys = hist_op = None
+    if hx is not None and hx.shape[0]:
+        horder, hptr = history_lists(ents, hx, field)
+        hxs, hys = hx[horder].contiguous(), hy[horder].contiguous()
+    out_row, score, loss, theta, mean, var = _outputs(dev, U, Q, P, d, return_theta, return_moments)
+    res = {"entities": ents}
+    if U:
+        o = _lib.ops()
+        ctx = (px if hxs is None else torch.cat([px, hxs])).clone()     # one operand per DISTINCT context: it is frozen
+        ctx[:, field] = 0
+        op_x, inv = torch.unique(ctx, dim=0, return_inverse=True)
+        inv = inv.reshape(-1)
+        op_x, pool_op = op_x.contiguous(), inv[:P].contiguous()
+        H = 0
+        if hxs is not None:
+            hist_op, H = inv[P:].contiguous(), hxs.shape[0]
+        ws = torch.empty(max(o.elicit_bound_workspace_bytes(U, P, H, op_x.shape[0], d, Q, int(lds_dim)), 1),
+                         dtype=torch.uint8, device=dev)
+        model._fresh_params()
+        ent, bia, scal = model._views(model._flat)
+        o.elicit_bound(ents, ptr, px, ys, hptr, hxs, hys, op_x, pool_op, hist_op, ent, bia, scal, ws, out_row, score,
+                       loss, theta, mean, var, field, kf, Q, code,
+                       ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, int(bool(reset)), int(bool(write)),
+                       int(lds_dim), float(kl_weight), _seed64(seed), int(n_iters))
+        if write:
+            model.params_changed()      # (rows written outside the step kernels: derived caches are stale)
+    return _result(res, order, out_row, score, loss, theta, mean, var)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # the curve of quality against questions asked (torch; any device)
 # ---------------------------------------------------------------------------------------------------------------------
 def asked_round(rows, P):
@@ -323,7 +397,10 @@ def metric(output, mean, var, y):
 
 
 def _curve_strategy(s, exact):
-    """A curve's strategy name: rank.STRATEGIES', or "design" (vae_amd/design.py) over the exact sessions."""
+    """A curve's strategy name: rank.STRATEGIES', or "design" (vae_amd/design.py) over the exact sessions (exact: True;
+    "bound": the bound sessions, which refuse it)."""
+    if s == "design" and exact == "bound":
+        raise ValueError(DESIGN_NEEDS_REG)
     if not (exact and s == "design"):
         strategy_code(s)
 
@@ -340,14 +417,14 @@ def _session_of(s, session, kw):
 def curve(model, pool, y_pool, n_questions, strategies=("mean", "random", "variance"), session=None, **kw):
     """VFM.elicitation_curve: {strategy: [metric before round 0, .., metric after round Q - 1]} on the rows still
     unasked, plus "n_unasked": {strategy: [Q + 1] ints}.  The model is left untouched.  session: the runner (`run`, or
-    `run_field` for the field form, `run_field_exact` for the exact one)."""
+    `run_field` for the field form, `run_field_exact` for the exact one, `run_field_bound` for the bound one)."""
     session = run if session is None else session
     for key in ("write", "return_moments", "return_theta"):
         if key in kw:
             raise ValueError(f"elicitation_curve sets {key} itself")
     strategies = list(strategies)
     for s in strategies:
-        _curve_strategy(s, session is run_field_exact)
+        _curve_strategy(s, "bound" if session is run_field_bound else session is run_field_exact)
     out, left = {}, {}
     for s in strategies:
         run_s, kw_s = _session_of(s, session, kw)
@@ -417,15 +494,17 @@ def round_posteriors(theta0, theta, resp, rnd):
 
 def ranking_curve(model, pool, y_pool, n_questions, field, X_test, y_test, rank_field, ks=(10,),
                   strategies=("random", "variance"), exact=False, exclude=None, match_fields=None, threshold=None,
-                  ineligible="raise", **session_kw):
+                  ineligible="raise", bound=False, **session_kw):
     """VFM.elicitation_ranking_curve_field (which documents the arguments and the result)."""
     from . import rank
     for key in ("write", "return_moments", "return_theta", "strategy"):
         if key in session_kw:
             raise ValueError(f"elicitation_ranking_curve_field sets {key} itself")
+    if bound and exact:
+        raise ValueError("bound=True and exact=True: the exact sessions are for 'reg' models, the bound ones for 'class'")
     strategies = list(strategies)
     for s in strategies:
-        _curve_strategy(s, bool(exact))
+        _curve_strategy(s, "bound" if bound else bool(exact))
     field = rank._field_arg(model, field)
     rank_field = rank._field_arg(model, rank_field)
     if rank_field == field:
@@ -443,7 +522,7 @@ def ranking_curve(model, pool, y_pool, n_questions, field, X_test, y_test, rank_
     relevant = (y >= (4.0 if threshold is None else float(threshold))) if model.output == "reg" else (y == 1)
     X_rel = rank._context_rows(model, X[relevant.to(X.device)], "X_test", rank_field, check_field_column=True)
     ex = rank._context_rows(model, exclude, "exclude", rank_field, check_field_column=True) if exclude is not None else None
-    session = run_field_exact if exact else run_field
+    session = run_field_bound if bound else run_field_exact if exact else run_field
     dev, d = model.device, model.d
     out = {}
     n_queries = 0

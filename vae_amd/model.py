@@ -1242,7 +1242,8 @@ class VFM(nn.Module):
     def elicitation_ranking_curve_field(self, pool, y_pool, n_questions: int, field: int, X_test, y_test,
                                         rank_field: int, ks=(10,), strategies=("random", "variance"),
                                         exact: bool = False, exclude=None, match_fields=None,
-                                        threshold: Optional[float] = None, ineligible: str = "raise", **session_kw):
+                                        threshold: Optional[float] = None, ineligible: str = "raise",
+                                        bound: bool = False, **session_kw):
         """How good are the recommendations after q questions?  For each strategy one session over the pool --
         elicit_field, or elicit_field_exact with exact=True, run with write=False, return_theta=True -- and, per round
         q = 0 .. n_questions, the held-out ranking metrics of the `rank_field` catalog (evaluate_ranking_field's:
@@ -1255,12 +1256,14 @@ class VFM(nn.Module):
         has just asked about), matched on match_fields as rank_field matches them.  All (Q + 1) x contexts queries of a
         strategy go through ONE rank_heldout_field_posterior call.  session_kw: the session's other options (history,
         n_steps, lr, objective, n_samples, seed, kl_weight, reset, key_field).  With exact=True the name "design" is a
-        strategy too: elicit_field_design, with `targets` taken from session_kw.
+        strategy too: elicit_field_design, with `targets` taken from session_kw.  bound=True runs elicit_field_bound
+        sessions ('class' models; session_kw then also takes n_iters, 8 being its untuned starting value; "design" is
+        refused); together with exact=True it is a ValueError.
         Returns {strategy: {metric: [Q + 1 floats]}, "n_queries": queries ranked per strategy}.  The model is left
         untouched, bit for bit."""
         from . import elicit
         return elicit.ranking_curve(self, pool, y_pool, n_questions, field, X_test, y_test, rank_field, ks, strategies,
-                                    exact, exclude, match_fields, threshold, ineligible, **session_kw)
+                                    exact, exclude, match_fields, threshold, ineligible, bound, **session_kw)
 
     # ------------------------------------------------------------------ fold-in (vae_amd/foldin.py)
     @torch.no_grad()
@@ -1502,6 +1505,39 @@ class VFM(nn.Module):
         ints]}}.  The model is left untouched."""
         from . import elicit
         return elicit.curve(self, pool, y_pool, n_questions, strategies, session=elicit.run_field_exact, field=field, **kw)
+
+    @torch.no_grad()
+    def elicit_field_bound(self, pool, y_pool, n_questions: int, field: int = 0, strategy: str = "variance",
+                           history=None, seed: int = 0, kl_weight: float = 1.0, n_iters: int = 8, reset: bool = False,
+                           write: bool = False, return_moments: bool = False, return_theta: bool = False,
+                           key_field: Optional[int] = None):
+        """elicit_field for a 'class' model without Adam: n_questions rounds of select_next_questions_field(n=1)
+        followed by fold_in_bound(field=field, n_iters=n_iters, reset=False) of the answering respondent, bitwise what
+        that loop computes, for every respondent in one launch (include/vfm_bound.h: vfm_elicit_bound_f32; DESIGN.md §4
+        "Bound sessions").  No n_steps, lr, objective or n_samples: after every answer the respondent's posterior is
+        n_iters rounds of the Jaakkola-Jordan bound's exact block minimisers on the history followed by the rows asked
+        so far, started at the posterior the round was scored from (fp32, as a table row would hold it); the iterate
+        stays in fp64 inside a fold and is rounded to fp32 once per round.
+
+        'class' models only, kl_weight > 0, n_iters >= 1, answers and history labels in {0, 1}, F >= 2 (else ValueError,
+        before anything needs a GPU).  n_iters = 8 is fold_in_bound's untuned starting value.  All four strategies
+        apply; "mean" (closest to p = 0.5) is the natural one here; "design" is refused: the scales of the optimum
+        depend on the answers through xi.  reset=True starts round 0 (its scores and its fold) from the prior row
+        (mu = 0, s = link^-1(1)).  pool, y_pool, history, field, seed, key_field, write, return_moments, return_theta: as
+        elicit_field.  Returns elicit_field's dict; loss [U, Q] is B_e, fold_in_bound's loss, after each round."""
+        from . import elicit
+        return elicit.run_field_bound(self, pool, y_pool, n_questions, field, strategy, history, seed, kl_weight, n_iters,
+                                      reset, write, return_moments, return_theta, key_field)
+
+    @torch.no_grad()
+    def elicitation_curve_field_bound(self, pool, y_pool, n_questions: int, field: int = 0,
+                                      strategies=("mean", "random", "variance"), **kw):
+        """elicitation_curve_field over elicit_field_bound sessions ('class' models: the AUC on the rows still unasked
+        before each round, the curve the reference's interactive experiment prints).  kw: elicit_field_bound's other
+        options (n_iters = 8 is its untuned starting value).  Returns {strategy: [Q + 1 floats], "n_unasked":
+        {strategy: [Q + 1 ints]}}.  The model is left untouched."""
+        from . import elicit
+        return elicit.curve(self, pool, y_pool, n_questions, strategies, session=elicit.run_field_bound, field=field, **kw)
 
     # ------------------------------------------------------------------ target-aware elicitation (vae_amd/design.py)
     @torch.no_grad()
