@@ -194,6 +194,95 @@ def test_list_helpers_keep_pool_order_and_map_rows_back():
     assert torch.equal(u2, us) and torch.equal(p2, ptr)
 
 
+def _lists_restated(E, x, y, hx, hy, field, targets):
+    """field_lists from its primitives, as the four sessions spelt it out before they shared it: run_field's text for
+    targets "absent", design's for targets None (own pool rows) or given."""
+    order, ents, ptr = E.pool_lists(x, field)
+    px, ys = x[order].contiguous(), y[order].contiguous()
+    P = px.shape[0]
+    hptr = hxs = hys = hist_op = None
+    if hx is not None and hx.shape[0]:
+        horder, hptr = E.history_lists(ents, hx, field)
+        hxs, hys = hx[horder].contiguous(), hy[horder].contiguous()
+    if isinstance(targets, str):
+        ctx = (px if hxs is None else torch.cat([px, hxs])).clone()
+        ctx[:, field] = 0
+        op_x, inv = torch.unique(ctx, dim=0, return_inverse=True)
+        inv = inv.reshape(-1)
+        op_x, pool_op = op_x.contiguous(), inv[:P].contiguous()
+        if hxs is not None:
+            hist_op = inv[P:].contiguous()
+        return dict(order=order, ents=ents, ptr=ptr, px=px, ys=ys, hptr=hptr, hxs=hxs, hys=hys, tptr=None, op_x=op_x,
+                    pool_op=pool_op, hist_op=hist_op, tgt_op=None)
+    H = 0 if hxs is None else hxs.shape[0]
+    if targets is None:
+        txs, tptr = None, ptr
+    else:
+        torder, tptr = E.history_lists(ents, targets, field)
+        txs = targets[torder]
+    parts = [px] + ([hxs] if hxs is not None else []) + ([txs] if txs is not None else [])
+    ctx = torch.cat(parts).clone()
+    ctx[:, field] = 0
+    op_x, inv = torch.unique(ctx, dim=0, return_inverse=True)
+    inv = inv.reshape(-1)
+    pool_op = inv[:P].contiguous()
+    if hxs is not None:
+        hist_op = inv[P:P + H].contiguous()
+    tgt_op = pool_op if txs is None else inv[P + H:].contiguous()
+    return dict(order=order, ents=ents, ptr=ptr, px=px, ys=ys, hptr=hptr, hxs=hxs, hys=hys, tptr=tptr,
+                op_x=op_x.contiguous(), pool_op=pool_op, hist_op=hist_op, tgt_op=tgt_op)
+
+
+@pytest.mark.parametrize("targets", ["absent", "own", "given"])
+@pytest.mark.parametrize("history", ["none", "empty", "some"])
+@pytest.mark.parametrize("F,field", [(2, 0), (2, 1), (3, 0), (3, 2)])
+def test_field_lists_are_the_restated_lists(F, field, history, targets):
+    from vae_amd import elicit as E
+    shared = [20, 30][:F - 1]                               # the context that pool, history and targets all hold
+
+    def rows(resp, ctxs):                                   # [n, F]: respondent ids in column `field`, contexts beside
+        out = torch.tensor([c[:F - 1] for c in ctxs])
+        return torch.cat([out[:, :field], torch.tensor(resp)[:, None], out[:, field:]], 1)
+
+    # respondents 4, 1, 7 in shuffled order; contexts repeat within and across respondents
+    x = rows([4, 1, 7, 1, 4, 4, 7, 1, 4, 1],
+             [shared, [21, 30], [22, 31], [21, 30], [21, 31], shared, [23, 30], [20, 31], [22, 31], [24, 32]])
+    y = torch.arange(10.0)
+    hx, hy = {"none": (None, None), "empty": (x[:0], y[:0]),
+              "some": (rows([4, 1, 4], [[21, 30], shared, [25, 33]]), torch.tensor([7.0, 8.0, 9.0]))}[history]
+    tx = {"absent": "absent", "own": None,                  # given: respondent 1 has none, one context is the targets' own
+          "given": rows([7, 4, 7, 4], [[26, 34], [21, 30], shared, [24, 32]])}[targets]
+    want = _lists_restated(E, x, y, hx, hy, field, tx)
+    got = E.field_lists(x, y, hx, hy, field) if targets == "absent" else E.field_lists(x, y, hx, hy, field, tx)
+    assert sorted(got) == sorted(want)
+    for key, w in want.items():
+        if w is None:
+            assert got[key] is None, key
+        else:
+            assert got[key].dtype == w.dtype and torch.equal(got[key], w), key
+    assert got["ents"].tolist() == [1, 4, 7] and got["px"].shape == (10, F)
+    n_hist = 3 if history == "some" else 0
+    assert (got["hist_op"] is None) == (n_hist == 0) and (n_hist == 0 or got["hist_op"].shape == (n_hist,))
+    zeroed = lambda t: torch.cat([t[:, :field], torch.zeros_like(t[:, :1]), t[:, field + 1:]], 1)
+    if targets == "absent":                                 # nothing of the targets: the operands of pool and history alone
+        assert got["tptr"] is None and got["tgt_op"] is None
+        both = x if n_hist == 0 else torch.cat([x, hx])
+        assert torch.equal(got["op_x"], torch.unique(zeroed(both), dim=0))
+    elif targets == "own":
+        assert got["tgt_op"] is got["pool_op"] and got["tptr"] is got["ptr"]
+    else:
+        assert got["tptr"].tolist() == [0, 0, 2, 4] and got["tgt_op"].shape == (4,)
+    # the shared context is one operand wherever it occurs, and every index points at its own row's context
+    c0 = zeroed(rows([0], [shared]))[0]
+    hit = (got["op_x"] == c0).all(1).nonzero().reshape(-1)
+    assert hit.numel() == 1
+    assert torch.equal(got["op_x"][got["pool_op"]], zeroed(got["px"])) and int(hit) in got["pool_op"].tolist()
+    if n_hist:
+        assert torch.equal(got["op_x"][got["hist_op"]], zeroed(got["hxs"])) and int(hit) in got["hist_op"].tolist()
+    if targets == "given":
+        assert int(hit) in got["tgt_op"].tolist() and got["op_x"][got["tgt_op"]][:, field].eq(0).all()
+
+
 def test_metric_helpers():
     from vae_amd import elicit as E
     y = torch.tensor([1.0, 0.0, 1.0, 0.0, 1.0])

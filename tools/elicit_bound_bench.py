@@ -80,6 +80,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--shapes", default="fraction,ml20m")
     ap.add_argument("--record", action="store_true", help="append the lines to profiles/elicit_bound_bench.jsonl")
+    ap.add_argument("--note", default=None, help="kept in the line: what was measured, e.g. the commit")
     args = ap.parse_args()
     dev = torch.device("cuda")
     for shape in args.shapes.split(","):
@@ -137,6 +138,8 @@ def main():
                "sum_final_bound_session": round(B_bound, 3), "sum_bound_at_adam_rows": round(B_adam, 3),
                "bound_below_adam_by": round(1.0 - B_bound / B_adam, 4), "same_rows_asked": same_rows,
                "device": torch.cuda.get_device_name(0), "when": time.strftime("%Y-%m-%dT%H:%M:%S")}
+        if args.note:
+            rec["note"] = args.note
         print(json.dumps(rec), flush=True)
         if args.record:
             with open(os.path.join(ROOT, "profiles", "elicit_bound_bench.jsonl"), "a") as f:

@@ -41,6 +41,7 @@ def main():
     ap.add_argument("--test-rows", type=int, default=20)
     ap.add_argument("--curve-respondents", type=int, default=300)
     ap.add_argument("--record", action="store_true", help="append the line to profiles/elicit_design_bench.jsonl")
+    ap.add_argument("--note", default=None, help="kept in the line: what was measured, e.g. the commit")
     args = ap.parse_args()
     from vae_amd.model import VFM
     dev = torch.device("cuda")
@@ -100,6 +101,8 @@ def main():
            "n_queries": curves["n_queries"],
            **{f"ndcg10_{s}": [round(v, 5) for v in curves[s]["ndcg@10"]] for s in ("random", "variance", "design")},
            "device": torch.cuda.get_device_name(0), "when": time.strftime("%Y-%m-%dT%H:%M:%S")}
+    if args.note:
+        rec["note"] = args.note
     print(json.dumps(rec), flush=True)
     if args.record:
         with open(os.path.join(ROOT, "profiles", "elicit_design_bench.jsonl"), "a") as f:

@@ -83,6 +83,7 @@ def main():
     ap.add_argument("--pool", type=int, default=100)
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--record", action="store_true", help="append the line to profiles/elicit_field_exact_bench.jsonl")
+    ap.add_argument("--note", default=None, help="kept in the line: what was measured, e.g. the commit")
     args = ap.parse_args()
     from vae_amd.model import VFM
     dev = torch.device("cuda")
@@ -138,6 +139,8 @@ def main():
            **split,
            "rmse_exact": [round(v, 5) for v in c_exact[strategy]], "rmse_adam": [round(v, 5) for v in c_adam[strategy]],
            "device": torch.cuda.get_device_name(0), "when": time.strftime("%Y-%m-%dT%H:%M:%S")}
+    if args.note:
+        rec["note"] = args.note
     print(json.dumps(rec), flush=True)
     if args.record:
         with open(os.path.join(ROOT, "profiles", "elicit_field_exact_bench.jsonl"), "a") as f:

@@ -136,127 +136,68 @@ class FoldinBound(_Strict, C.Structure):
 ELICIT_BOUND_EXPORTS = ("vfm_elicit_bound_f32", "vfm_elicit_bound_workspace_bytes")
 
 
-class Elicit(_Strict, C.Structure):
+# ---- the session structs: the runs of fields that every form names alike, and the stamp every one starts with
+def _fields(ctype, *names):
+    return tuple((n, ctype) for n in names)
+
+
+_STAMP = _fields(C.c_uint32, "struct_size", "abi_version")
+_COUNTS = _fields(C.c_int64, "U", "P", "H", "T", "n_ops")
+_FIELD_ROWS = _fields(C.c_void_p, "entities", "pool_ptr", "pool_x", "pool_y", "hist_ptr", "hist_x", "hist_y")
+_OPERANDS = _fields(C.c_void_p, "op_x", "pool_op", "hist_op")
+_TABLES_OUTPUTS = _fields(C.c_void_p, "entity_params", "bias_params", "scalars", "out_row", "out_score", "out_loss",
+                          "out_theta", "out_mean", "out_var")
+_WORKSPACE = (("workspace", C.c_void_p), ("workspace_bytes", C.c_int64))
+_ADAM_TAIL = (_fields(C.c_int32, "objective", "likelihood", "flags", "n_steps", "n_samples", "reset", "write", "lds_rows")
+              + _fields(C.c_float, "lr", "kl_weight") + (("seed", C.c_uint64), ("t0", C.c_int64)))
+_SOLVE_HEAD = (_fields(C.c_int32, "F", "d", "field", "key_col", "n_rounds", "strategy", "flags", "reset", "write", "lds_dim")
+               + (("kl_weight", C.c_float),))
+_SEED = (("seed", C.c_uint64),)
+
+
+class _Session(_Strict, C.Structure):
+    """A session struct: struct_size and abi_version stamped as VFM_STRUCT_INIT does."""
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size, self.abi_version = C.sizeof(type(self)), ABI_VERSION
+
+
+class Elicit(_Session):
     """`vfm_elicit_t` (tests/test_elicit_cpu.py checks the layout against gcc's)."""
-    _fields_ = [
-        ("struct_size", C.c_uint32), ("abi_version", C.c_uint32),
-        ("U", C.c_int64), ("P", C.c_int64), ("H", C.c_int64), ("T", C.c_int64), ("n_ops", C.c_int64),
-        ("F", C.c_int32), ("d", C.c_int32), ("n_rounds", C.c_int32), ("strategy", C.c_int32),
-        ("objective", C.c_int32), ("likelihood", C.c_int32), ("flags", C.c_int32), ("n_steps", C.c_int32),
-        ("n_samples", C.c_int32), ("reset", C.c_int32), ("write", C.c_int32), ("lds_rows", C.c_int32),
-        ("lr", C.c_float), ("kl_weight", C.c_float),
-        ("seed", C.c_uint64), ("t0", C.c_int64),
-        ("users", C.c_void_p), ("pool_ptr", C.c_void_p), ("pool_items", C.c_void_p), ("pool_y", C.c_void_p),
-        ("hist_ptr", C.c_void_p), ("hist_items", C.c_void_p), ("hist_y", C.c_void_p),
-        ("op_x", C.c_void_p), ("pool_op", C.c_void_p), ("hist_op", C.c_void_p),
-        ("entity_params", C.c_void_p), ("bias_params", C.c_void_p), ("scalars", C.c_void_p),
-        ("out_row", C.c_void_p), ("out_score", C.c_void_p), ("out_loss", C.c_void_p), ("out_theta", C.c_void_p),
-        ("out_mean", C.c_void_p), ("out_var", C.c_void_p),
-        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
-    ]
-
-    def __init__(self, *a, **k):
-        super().__init__(*a, **k)
-        self.struct_size, self.abi_version = C.sizeof(type(self)), ABI_VERSION      # (VFM_STRUCT_INIT)
+    _fields_ = list(_STAMP + _COUNTS + _fields(C.c_int32, "F", "d", "n_rounds", "strategy") + _ADAM_TAIL
+                    + _fields(C.c_void_p, "users", "pool_ptr", "pool_items", "pool_y", "hist_ptr", "hist_items", "hist_y")
+                    + _OPERANDS + _TABLES_OUTPUTS + _WORKSPACE)
 
 
-class ElicitField(_Strict, C.Structure):
+class ElicitField(_Session):
     """`vfm_elicit_field_t` (tests/test_elicit_field_cpu.py checks the layout against gcc's)."""
-    _fields_ = [
-        ("struct_size", C.c_uint32), ("abi_version", C.c_uint32),
-        ("U", C.c_int64), ("P", C.c_int64), ("H", C.c_int64), ("T", C.c_int64), ("n_ops", C.c_int64),
-        ("F", C.c_int32), ("d", C.c_int32), ("field", C.c_int32), ("key_col", C.c_int32), ("n_rounds", C.c_int32),
-        ("strategy", C.c_int32), ("objective", C.c_int32), ("likelihood", C.c_int32), ("flags", C.c_int32),
-        ("n_steps", C.c_int32), ("n_samples", C.c_int32), ("reset", C.c_int32), ("write", C.c_int32),
-        ("lds_rows", C.c_int32),
-        ("lr", C.c_float), ("kl_weight", C.c_float),
-        ("seed", C.c_uint64), ("t0", C.c_int64),
-        ("entities", C.c_void_p), ("pool_ptr", C.c_void_p), ("pool_x", C.c_void_p), ("pool_y", C.c_void_p),
-        ("hist_ptr", C.c_void_p), ("hist_x", C.c_void_p), ("hist_y", C.c_void_p),
-        ("op_x", C.c_void_p), ("pool_op", C.c_void_p), ("hist_op", C.c_void_p),
-        ("entity_params", C.c_void_p), ("bias_params", C.c_void_p), ("scalars", C.c_void_p),
-        ("out_row", C.c_void_p), ("out_score", C.c_void_p), ("out_loss", C.c_void_p), ("out_theta", C.c_void_p),
-        ("out_mean", C.c_void_p), ("out_var", C.c_void_p),
-        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
-    ]
-
-    def __init__(self, *a, **k):
-        super().__init__(*a, **k)
-        self.struct_size, self.abi_version = C.sizeof(type(self)), ABI_VERSION      # (VFM_STRUCT_INIT)
+    _fields_ = list(_STAMP + _COUNTS + _fields(C.c_int32, "F", "d", "field", "key_col", "n_rounds", "strategy")
+                    + _ADAM_TAIL + _FIELD_ROWS + _OPERANDS + _TABLES_OUTPUTS + _WORKSPACE)
 
 
-class ElicitSolve(_Strict, C.Structure):
+class ElicitSolve(_Session):
     """`vfm_elicit_solve_t` (tests/test_elicit_exact_cpu.py checks the layout against gcc's)."""
-    _fields_ = [
-        ("struct_size", C.c_uint32), ("abi_version", C.c_uint32),
-        ("U", C.c_int64), ("P", C.c_int64), ("H", C.c_int64), ("T", C.c_int64), ("n_ops", C.c_int64),
-        ("F", C.c_int32), ("d", C.c_int32), ("field", C.c_int32), ("key_col", C.c_int32), ("n_rounds", C.c_int32),
-        ("strategy", C.c_int32), ("flags", C.c_int32), ("reset", C.c_int32), ("write", C.c_int32),
-        ("lds_dim", C.c_int32), ("kl_weight", C.c_float),
-        ("seed", C.c_uint64),
-        ("entities", C.c_void_p), ("pool_ptr", C.c_void_p), ("pool_x", C.c_void_p), ("pool_y", C.c_void_p),
-        ("hist_ptr", C.c_void_p), ("hist_x", C.c_void_p), ("hist_y", C.c_void_p),
-        ("op_x", C.c_void_p), ("pool_op", C.c_void_p), ("hist_op", C.c_void_p),
-        ("entity_params", C.c_void_p), ("bias_params", C.c_void_p), ("scalars", C.c_void_p),
-        ("out_row", C.c_void_p), ("out_score", C.c_void_p), ("out_loss", C.c_void_p), ("out_theta", C.c_void_p),
-        ("out_mean", C.c_void_p), ("out_var", C.c_void_p),
-        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
-    ]
-
-    def __init__(self, *a, **k):
-        super().__init__(*a, **k)
-        self.struct_size, self.abi_version = C.sizeof(type(self)), ABI_VERSION      # (VFM_STRUCT_INIT)
+    _fields_ = list(_STAMP + _COUNTS + _SOLVE_HEAD + _SEED + _FIELD_ROWS + _OPERANDS + _TABLES_OUTPUTS + _WORKSPACE)
 
 
-class ElicitBound(_Strict, C.Structure):
+class ElicitBound(_Session):
     """`vfm_elicit_bound_t`: vfm_elicit_solve_t's fields and n_iters (tests/test_elicit_bound_cpu.py checks the layout
     against gcc's)."""
-    _fields_ = [
-        ("struct_size", C.c_uint32), ("abi_version", C.c_uint32),
-        ("U", C.c_int64), ("P", C.c_int64), ("H", C.c_int64), ("T", C.c_int64), ("n_ops", C.c_int64),
-        ("F", C.c_int32), ("d", C.c_int32), ("field", C.c_int32), ("key_col", C.c_int32), ("n_rounds", C.c_int32),
-        ("strategy", C.c_int32), ("flags", C.c_int32), ("reset", C.c_int32), ("write", C.c_int32),
-        ("lds_dim", C.c_int32), ("kl_weight", C.c_float), ("n_iters", C.c_int32),
-        ("seed", C.c_uint64),
-        ("entities", C.c_void_p), ("pool_ptr", C.c_void_p), ("pool_x", C.c_void_p), ("pool_y", C.c_void_p),
-        ("hist_ptr", C.c_void_p), ("hist_x", C.c_void_p), ("hist_y", C.c_void_p),
-        ("op_x", C.c_void_p), ("pool_op", C.c_void_p), ("hist_op", C.c_void_p),
-        ("entity_params", C.c_void_p), ("bias_params", C.c_void_p), ("scalars", C.c_void_p),
-        ("out_row", C.c_void_p), ("out_score", C.c_void_p), ("out_loss", C.c_void_p), ("out_theta", C.c_void_p),
-        ("out_mean", C.c_void_p), ("out_var", C.c_void_p),
-        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
-    ]
-
-    def __init__(self, *a, **k):
-        super().__init__(*a, **k)
-        self.struct_size, self.abi_version = C.sizeof(type(self)), ABI_VERSION      # (VFM_STRUCT_INIT)
+    _fields_ = list(_STAMP + _COUNTS + _SOLVE_HEAD + (("n_iters", C.c_int32),) + _SEED + _FIELD_ROWS + _OPERANDS
+                    + _TABLES_OUTPUTS + _WORKSPACE)
 
 
 # ---- target-aware elicitation (include/vfm_design.h)
 DESIGN_EXPORTS = ("vfm_design_workspace_bytes", "vfm_design_scores_f32", "vfm_design_elicit_f32")
 
 
-class ElicitDesign(_Strict, C.Structure):
+class ElicitDesign(_Session):
     """`vfm_design_t` (tests/test_design_cpu.py checks the layout against gcc's)."""
-    _fields_ = [
-        ("struct_size", C.c_uint32), ("abi_version", C.c_uint32),
-        ("U", C.c_int64), ("P", C.c_int64), ("H", C.c_int64), ("T", C.c_int64), ("n_ops", C.c_int64),
-        ("n_targets", C.c_int64),
-        ("F", C.c_int32), ("d", C.c_int32), ("field", C.c_int32), ("n_rounds", C.c_int32), ("flags", C.c_int32),
-        ("reset", C.c_int32), ("write", C.c_int32), ("lds_dim", C.c_int32), ("kl_weight", C.c_float),
-        ("entities", C.c_void_p), ("pool_ptr", C.c_void_p), ("pool_x", C.c_void_p), ("pool_y", C.c_void_p),
-        ("hist_ptr", C.c_void_p), ("hist_x", C.c_void_p), ("hist_y", C.c_void_p),
-        ("tgt_ptr", C.c_void_p), ("tgt_op", C.c_void_p),
-        ("op_x", C.c_void_p), ("pool_op", C.c_void_p), ("hist_op", C.c_void_p),
-        ("entity_params", C.c_void_p), ("bias_params", C.c_void_p), ("scalars", C.c_void_p),
-        ("out_row", C.c_void_p), ("out_score", C.c_void_p), ("out_loss", C.c_void_p), ("out_theta", C.c_void_p),
-        ("out_mean", C.c_void_p), ("out_var", C.c_void_p), ("out_pool_score", C.c_void_p),
-        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
-    ]
-
-    def __init__(self, *a, **k):
-        super().__init__(*a, **k)
-        self.struct_size, self.abi_version = C.sizeof(type(self)), ABI_VERSION      # (VFM_STRUCT_INIT)
+    _fields_ = list(_STAMP + _COUNTS + (("n_targets", C.c_int64),)
+                    + _fields(C.c_int32, "F", "d", "field", "n_rounds", "flags", "reset", "write", "lds_dim")
+                    + (("kl_weight", C.c_float),) + _FIELD_ROWS + _fields(C.c_void_p, "tgt_ptr", "tgt_op") + _OPERANDS
+                    + _TABLES_OUTPUTS + (("out_pool_score", C.c_void_p),) + _WORKSPACE)
 
 
 for _c in (Problem, Index, Pipe, Elicit, ElicitField, ElicitSolve, ElicitBound, ElicitDesign, FoldinSolve, FoldinSplit,

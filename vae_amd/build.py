@@ -97,19 +97,14 @@ _UNITS = [("vfm_abi.hip", "", _EXACT), ("vfm_index.hip", "", []), ("vfm_variants
           # the fold of a round, hence their flag
           ("csrc_rank/vfm_elicit_bound.hip", "", _EXACT)]
 RANK_DIR = os.path.join(HERE, "csrc_rank")
-RANK_HDR = os.path.join(ROOT, "include", "vfm_rank.h")
-RANK_OPS = os.path.join(RANK_DIR, "vfm_rank_ops.cpp")
-FOLDIN_HDR = os.path.join(ROOT, "include", "vfm_foldin.h")
-FOLDIN_OPS = os.path.join(RANK_DIR, "vfm_foldin_ops.cpp")
-ELICIT_HDR = os.path.join(ROOT, "include", "vfm_elicit.h")
-ELICIT_OPS = os.path.join(RANK_DIR, "vfm_elicit_ops.cpp")
-DESIGN_HDR = os.path.join(ROOT, "include", "vfm_design.h")
-DESIGN_OPS = os.path.join(RANK_DIR, "vfm_design_ops.cpp")
-SWEEP_HDR = os.path.join(ROOT, "include", "vfm_sweep.h")
-SWEEP_OPS = os.path.join(RANK_DIR, "vfm_sweep_ops.cpp")
-BOUND_HDR = os.path.join(ROOT, "include", "vfm_bound.h")      # (its ops live in vfm_foldin_ops.cpp and vfm_elicit_ops.cpp)
 VAR_DIR = os.path.join(HERE, "csrc_var")
-VAR_STEP_HDR = os.path.join(ROOT, "include", "vfm_variant_step.h")
+# the public headers beside include/vfm_hip.h (vfm_bound.h's ops live in vfm_foldin_ops.cpp and vfm_elicit_ops.cpp)
+PUBLIC_HDRS = tuple(os.path.join(ROOT, "include", f"vfm_{n}.h")
+                    for n in ("rank", "foldin", "elicit", "design", "variant_step", "sweep", "bound"))
+# the TORCH_LIBRARY fragments linked into the shim beside csrc/vfm_torch_ops.cpp, and the header they share: host C++
+# only, so it is no source of libvfm_hip.so
+OPS_SOURCES = tuple(os.path.join(RANK_DIR, f"vfm_{n}_ops.cpp") for n in ("rank", "foldin", "elicit", "design", "sweep"))
+OPS_HDR = os.path.join(RANK_DIR, "vfm_ops_common.hpp")
 
 
 def _unit_path(src):
@@ -122,9 +117,11 @@ def _unit_obj(objdir, src, suffix):
 
 
 def _rank_sources():
-    return ([RANK_HDR, FOLDIN_HDR, ELICIT_HDR, DESIGN_HDR, VAR_STEP_HDR, SWEEP_HDR, BOUND_HDR] +
-            sorted(os.path.join(RANK_DIR, f) for f in os.listdir(RANK_DIR) if f.endswith((".hip", ".hpp"))) +
-            sorted(os.path.join(VAR_DIR, f) for f in os.listdir(VAR_DIR) if f.endswith((".hip", ".hpp"))))
+    """What libvfm_hip.so is built from outside csrc/: the public headers and every .hip / .hpp of csrc_rank/ and
+    csrc_var/ but the shim's own header."""
+    return ([*PUBLIC_HDRS] +
+            [f for d in (RANK_DIR, VAR_DIR) for f in sorted(os.path.join(d, n) for n in os.listdir(d))
+             if f.endswith((".hip", ".hpp")) and f != OPS_HDR])
 
 
 def build_hip_library(force=False, verbose=False):
@@ -141,7 +138,7 @@ def build_hip_library(force=False, verbose=False):
     common = [HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-fvisibility-inlines-hidden",
               "-I" + os.path.join(ROOT, "include"), "-I" + csrc]
     jobs, objs = [], []
-    shared = [hdr, RANK_HDR, FOLDIN_HDR, ELICIT_HDR, DESIGN_HDR, VAR_STEP_HDR, SWEEP_HDR, BOUND_HDR, os.path.abspath(__file__)] + [f for f in parts if f.endswith(".hpp")]      # what every unit depends on
+    shared = [hdr, *PUBLIC_HDRS, os.path.abspath(__file__)] + [f for f in parts if f.endswith(".hpp")]      # what every unit depends on
     for src, suffix, extra in _UNITS:
         obj = _unit_obj(objdir, src, suffix)
         objs.append(obj)
@@ -170,14 +167,14 @@ def build_hip_library(force=False, verbose=False):
 
 def build_torch_ops(force=False, verbose=False):
     """libvfm_torch_ops.so: TORCH_LIBRARY shim `torch.ops.vfm_hip.*` over the C ABI (host C++ only); the ranking and
-    fold-in, session and design ops are TORCH_LIBRARY_FRAGMENTs of their own sources (csrc_rank/vfm_{rank,foldin,elicit,design,sweep}_ops.cpp) linked
+    fold-in, session and design ops are TORCH_LIBRARY_FRAGMENTs of their own sources (OPS_SOURCES, over OPS_HDR) linked
     into the same shim."""
     import torch
     src = os.path.join(HERE, "csrc", "vfm_torch_ops.cpp")
     hdr = os.path.join(ROOT, "include", "vfm_hip.h")
     out = os.path.join(HERE, "libvfm_torch_ops.so")
     lib = os.path.join(HERE, "libvfm_hip.so")
-    if not force and not _stale(out, [src, hdr, lib, RANK_OPS, RANK_HDR, FOLDIN_OPS, FOLDIN_HDR, ELICIT_OPS, ELICIT_HDR, DESIGN_OPS, DESIGN_HDR, SWEEP_OPS, SWEEP_HDR, BOUND_HDR]):
+    if not force and not _stale(out, [src, hdr, lib, OPS_HDR, *OPS_SOURCES, *PUBLIC_HDRS]):
         return out
     ti = os.path.dirname(torch.__file__)
     rocm = os.environ.get("ROCM_HOME", "/opt/rocm")
@@ -185,7 +182,7 @@ def build_torch_ops(force=False, verbose=False):
            "-D_GLIBCXX_USE_CXX11_ABI=%d" % int(torch._C._GLIBCXX_USE_CXX11_ABI),
            "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ti, "include"),
            "-I" + os.path.join(ti, "include", "torch", "csrc", "api", "include"),
-           "-I" + os.path.join(rocm, "include"), "-o", out, src, RANK_OPS, FOLDIN_OPS, ELICIT_OPS, DESIGN_OPS, SWEEP_OPS,
+           "-I" + os.path.join(rocm, "include"), "-o", out, src, *OPS_SOURCES,
            "-L" + os.path.join(ti, "lib"), "-ltorch", "-ltorch_cpu", "-lc10", "-lc10_hip", "-ltorch_hip",
            "-L" + HERE, "-lvfm_hip", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(ti, "lib")]
     if verbose:
@@ -212,7 +209,7 @@ def build_sanitized(force=False, verbose=False):
     os.makedirs(outdir, exist_ok=True)
     stamp = os.path.join(outdir, "digest.txt")
     import hashlib
-    digest = sources_digest() + hashlib.sha1(b"".join(open(f, "rb").read() for f in _rank_sources() + [RANK_OPS, FOLDIN_OPS, ELICIT_OPS, DESIGN_OPS, SWEEP_OPS])).hexdigest()
+    digest = sources_digest() + hashlib.sha1(b"".join(open(f, "rb").read() for f in _rank_sources() + [OPS_HDR, *OPS_SOURCES])).hexdigest()
     out = os.path.join(outdir, "libvfm_hip.so")
     out_ops = os.path.join(outdir, "libvfm_torch_ops.so")
     if (not force and os.path.exists(out) and os.path.exists(out_ops) and os.path.exists(stamp)
@@ -245,7 +242,7 @@ def build_sanitized(force=False, verbose=False):
            "-D_GLIBCXX_USE_CXX11_ABI=%d" % int(torch._C._GLIBCXX_USE_CXX11_ABI),
            "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ti, "include"),
            "-I" + os.path.join(ti, "include", "torch", "csrc", "api", "include"),
-           "-I" + os.path.join(rocm, "include"), "-o", out_ops, os.path.join(csrc, "vfm_torch_ops.cpp"), RANK_OPS, FOLDIN_OPS, ELICIT_OPS, DESIGN_OPS, SWEEP_OPS,
+           "-I" + os.path.join(rocm, "include"), "-o", out_ops, os.path.join(csrc, "vfm_torch_ops.cpp"), *OPS_SOURCES,
            "-L" + os.path.join(ti, "lib"), "-ltorch", "-ltorch_cpu", "-lc10", "-lc10_hip", "-ltorch_hip",
            "-L" + outdir, "-lvfm_hip", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(ti, "lib")]
     if verbose:

@@ -1,27 +1,14 @@
 // vfm_foldin_ops.cpp -- torch.ops.vfm_hip.{foldin, foldin_workspace_bytes, foldin_solve, foldin_solve_workspace_bytes,
 // foldin_bound, foldin_bound_workspace_bytes}: the TORCH_LIBRARY fragment over include/vfm_foldin.h and include/vfm_bound.h.  Like vfm_rank_ops.cpp it only validates tensors, takes the current HIP stream of the tensors'
 // device and forwards raw pointers; all arithmetic is in the HIP kernels.
-#include <ATen/ATen.h>
-#include <c10/hip/HIPGuard.h>
-#include <c10/hip/HIPStream.h>
-#include <torch/library.h>
-
-#include <string.h>
+#include "vfm_ops_common.hpp"
 
 #include "vfm_bound.h"
 #include "vfm_foldin.h"
 
 namespace {
 
-using at::Tensor;
-using c10::optional;
-
-const Tensor& dev_tensor(const Tensor& t, at::ScalarType dt, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on the GPU (vae_amd has no CPU fallback)");
-  TORCH_CHECK(t.scalar_type() == dt, name, " has the wrong dtype");
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-  return t;
-}
+using namespace vfm_ops;
 
 int64_t foldin_workspace_bytes(int64_t n_ops, int64_t d, int64_t objective) {
   const int64_t b = vfm_foldin_workspace_bytes(n_ops, (int32_t)d, (int32_t)objective);
@@ -51,28 +38,27 @@ void foldin(const Tensor& entities, const Tensor& row_ptr, const Tensor& x, cons
   p.lds_rows = (int32_t)lds_rows; p.lr = (float)lr; p.kl_weight = (float)kl_weight; p.seed = (uint64_t)seed; p.t0 = t0;
   p.entities = entities.data_ptr<int64_t>(); p.row_ptr = row_ptr.data_ptr<int64_t>();
   p.x = x.data_ptr<int64_t>(); p.y = y.data_ptr<float>();
-  if (op_x.has_value() && op_x->defined()) {
+  if (given(op_x)) {
     TORCH_CHECK(dev_tensor(*op_x, at::kLong, "op_x").dim() == 2 && op_x->size(1) == x.size(1), "op_x must be [n_ops, F]");
-    TORCH_CHECK(row_op.has_value() && row_op->defined() && dev_tensor(*row_op, at::kLong, "row_op").numel() == p.R,
+    TORCH_CHECK(given(row_op) && dev_tensor(*row_op, at::kLong, "row_op").numel() == p.R,
                 "row_op must hold one operand per row");
     p.n_ops = op_x->size(0);
     p.op_x = op_x->data_ptr<int64_t>();
     p.row_op = row_op->data_ptr<int64_t>();
   }
-  if (workspace.has_value() && workspace->defined()) {
+  if (given(workspace)) {
     dev_tensor(*workspace, at::kByte, "workspace");
     p.workspace = workspace->data_ptr();
     p.workspace_bytes = workspace->numel();
   }
   p.entity_params = entity.data_ptr<float>(); p.bias_params = bias.data_ptr<float>();
   p.scalars = scalars.data_ptr<float>(); p.out_loss = loss.data_ptr<float>();
-  if (grad.has_value() && grad->defined()) {
+  if (given(grad)) {
     TORCH_CHECK(dev_tensor(*grad, at::kFloat, "grad").numel() >= E * (2 * (int64_t)p.d + 2), "grad must be [E, 2d + 2]");
     p.out_grad = grad->data_ptr<float>();
   }
   c10::hip::HIPGuard guard(x.get_device());
-  const int rc = vfm_foldin_f32(&p, (void*)c10::hip::getCurrentHIPStream(x.get_device()).stream());
-  TORCH_CHECK(rc == 0, "vfm_foldin_f32 failed (code ", rc, "): ", vfm_last_error());
+  check(vfm_foldin_f32(&p, stream_of(x)), "vfm_foldin_f32");
 }
 
 int64_t foldin_solve_workspace_bytes(int64_t E, int64_t n_ops, int64_t d, int64_t lds_dim) {
@@ -106,8 +92,7 @@ void foldin_solve(const Tensor& entities, const Tensor& row_ptr, const Tensor& y
   p.scalars = scalars.data_ptr<float>(); p.out_loss = loss.data_ptr<float>();
   p.workspace = workspace.data_ptr(); p.workspace_bytes = workspace.numel();
   c10::hip::HIPGuard guard(y.get_device());
-  const int rc = vfm_foldin_solve_f32(&p, (void*)c10::hip::getCurrentHIPStream(y.get_device()).stream());
-  TORCH_CHECK(rc == 0, "vfm_foldin_solve_f32 failed (code ", rc, "): ", vfm_last_error());
+  check(vfm_foldin_solve_f32(&p, stream_of(y)), "vfm_foldin_solve_f32");
 }
 
 int64_t foldin_bound_workspace_bytes(int64_t E, int64_t R, int64_t n_ops, int64_t d, int64_t lds_dim) {
@@ -143,8 +128,7 @@ void foldin_bound(const Tensor& entities, const Tensor& row_ptr, const Tensor& y
   p.scalars = scalars.data_ptr<float>(); p.out_loss = loss.data_ptr<float>();
   p.workspace = workspace.data_ptr(); p.workspace_bytes = workspace.numel();
   c10::hip::HIPGuard guard(y.get_device());
-  const int rc = vfm_foldin_bound_f32(&p, (void*)c10::hip::getCurrentHIPStream(y.get_device()).stream());
-  TORCH_CHECK(rc == 0, "vfm_foldin_bound_f32 failed (code ", rc, "): ", vfm_last_error());
+  check(vfm_foldin_bound_f32(&p, stream_of(y)), "vfm_foldin_bound_f32");
 }
 
 }  // namespace

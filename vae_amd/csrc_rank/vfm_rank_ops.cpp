@@ -2,32 +2,13 @@
 // rank_eval_workspace_bytes, field_moments, rank_field, rank_field_workspace_bytes, rank_heldout_field,
 // rank_eval_field_workspace_bytes, field_moments_post, rank_field_post, rank_heldout_field_post}: the TORCH_LIBRARY fragment over include/vfm_rank.h.  Like vfm_torch_ops.cpp it only validates tensors, takes the current HIP stream
 // of the tensors' device and forwards raw pointers; all arithmetic is in the HIP kernels.
-#include <ATen/ATen.h>
-#include <c10/hip/HIPGuard.h>
-#include <c10/hip/HIPStream.h>
-#include <torch/library.h>
-
-#include <string.h>
+#include "vfm_ops_common.hpp"
 
 #include "vfm_rank.h"
 
 namespace {
 
-using at::Tensor;
-using c10::optional;
-
-void check(int rc, const char* what) {
-  TORCH_CHECK(rc == 0, what, " failed (code ", rc, "): ", vfm_last_error());
-}
-
-const Tensor& dev_tensor(const Tensor& t, at::ScalarType dt, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on the GPU (vae_amd has no CPU fallback)");
-  TORCH_CHECK(t.scalar_type() == dt, name, " has the wrong dtype");
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-  return t;
-}
-
-void* stream_of(const Tensor& t) { return (void*)c10::hip::getCurrentHIPStream(t.get_device()).stream(); }
+using namespace vfm_ops;
 
 void tables(const Tensor& entity, const Tensor& bias, const Tensor& scalars) {
   dev_tensor(entity, at::kFloat, "entity_params"); dev_tensor(bias, at::kFloat, "bias_params");

@@ -1,25 +1,13 @@
 // vfm_sweep_ops.cpp -- torch.ops.vfm_hip.{foldin_solve_split, foldin_split_workspace_bytes}: the TORCH_LIBRARY fragment
 // over include/vfm_sweep.h.  Like vfm_foldin_ops.cpp it only validates tensors, takes the current HIP stream of the
 // tensors' device and forwards raw pointers; all arithmetic is in the HIP kernels.
-#include <ATen/ATen.h>
-#include <c10/hip/HIPGuard.h>
-#include <c10/hip/HIPStream.h>
-#include <torch/library.h>
-
-#include <string.h>
+#include "vfm_ops_common.hpp"
 
 #include "vfm_sweep.h"
 
 namespace {
 
-using at::Tensor;
-
-const Tensor& dev_tensor(const Tensor& t, at::ScalarType dt, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be on the GPU (vae_amd has no CPU fallback)");
-  TORCH_CHECK(t.scalar_type() == dt, name, " has the wrong dtype");
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-  return t;
-}
+using namespace vfm_ops;
 
 int64_t foldin_split_workspace_bytes(int64_t n_chunks, int64_t n_heavy, int64_t n_ops, int64_t d, int64_t lds_dim) {
   const int64_t b = vfm_foldin_split_workspace_bytes(n_chunks, n_heavy, n_ops, (int32_t)d, (int32_t)lds_dim);
@@ -54,8 +42,7 @@ void foldin_solve_split(const Tensor& entities, const Tensor& chunk_ptr, const T
   p.scalars = scalars.data_ptr<float>(); p.out_loss = loss.data_ptr<float>();
   p.workspace = workspace.data_ptr(); p.workspace_bytes = workspace.numel();
   c10::hip::HIPGuard guard(y.get_device());
-  const int rc = vfm_foldin_solve_split_f32(&p, (void*)c10::hip::getCurrentHIPStream(y.get_device()).stream());
-  TORCH_CHECK(rc == 0, "vfm_foldin_solve_split_f32 failed (code ", rc, "): ", vfm_last_error());
+  check(vfm_foldin_solve_split_f32(&p, stream_of(y)), "vfm_foldin_solve_split_f32");
 }
 
 }  // namespace

@@ -4,16 +4,17 @@
 For a 'reg' model the scales of the exact fold-in's optimum do not depend on the answers, so the posterior variance a
 question would leave behind is known before it is asked.  The score of a candidate is the expected drop of the mean
 predictive variance over the respondent's target contexts (Cohn's ALC, A-optimal design under the mean-field
-posterior), a closed form of O(d) per candidate.  This module checks the arguments, builds the per-respondent lists of
-the pool, the history and the targets (stable sorts: the caller's order is kept within a respondent) and one operand
-per distinct context of all three; the scores are one HIP launch (torch.ops.vfm_hip.design_scores) and the sessions
-one more (design_elicit), beside the operand passes.
+posterior), a closed form of O(d) per candidate.  This module checks the arguments; elicit.field_lists builds the
+per-respondent lists of the pool, the history and the targets (stable sorts: the caller's order is kept within a
+respondent) and one operand per distinct context of all three; the scores are one HIP launch
+(torch.ops.vfm_hip.design_scores) and the sessions one more (design_elicit, through elicit.run_field_session), beside
+the operand passes.
 """
 from __future__ import annotations
 
 import torch
 
-from . import _lib, elicit, ops
+from . import _lib, elicit, foldin, ops
 
 STRATEGY = "design"                      # the name the exact curves route here (rank.STRATEGIES does not hold it)
 
@@ -42,45 +43,12 @@ def check_args(model, pool, y_pool, n_questions, field, targets, history, kl_wei
     return x, y, hx, hy, tx, field
 
 
-def _lists(x, y, hx, hy, tx, field):
-    """The per-respondent lists and the operand table of pool, history and targets together: dict(order, ents, ptr, px,
-    ys, hptr, hxs, hys, tptr, op_x, pool_op, hist_op, tgt_op).  targets None: each respondent's own pool rows."""
-    order, ents, ptr = elicit.pool_lists(x, field)
-    px, ys = x[order].contiguous(), y[order].contiguous()
-    P = px.shape[0]
-    hptr = hxs = hys = hist_op = None
-    if hx is not None and hx.shape[0]:
-        horder, hptr = elicit.history_lists(ents, hx, field)
-        hxs, hys = hx[horder].contiguous(), hy[horder].contiguous()
-    H = 0 if hxs is None else hxs.shape[0]
-    if tx is None:
-        txs, tptr = None, ptr
-    else:
-        torder, tptr = elicit.history_lists(ents, tx, field)
-        txs = tx[torder]
-    parts = [px] + ([hxs] if hxs is not None else []) + ([txs] if txs is not None else [])
-    ctx = torch.cat(parts).clone()                                    # one operand per DISTINCT context: it is frozen
-    ctx[:, field] = 0
-    op_x, inv = torch.unique(ctx, dim=0, return_inverse=True)
-    inv = inv.reshape(-1)
-    pool_op = inv[:P].contiguous()
-    if hxs is not None:
-        hist_op = inv[P:P + H].contiguous()
-    tgt_op = pool_op if txs is None else inv[P + H:].contiguous()
-    return dict(order=order, ents=ents, ptr=ptr, px=px, ys=ys, hptr=hptr, hxs=hxs, hys=hys, tptr=tptr,
-                op_x=op_x.contiguous(), pool_op=pool_op, hist_op=hist_op, tgt_op=tgt_op)
-
-
-def _flags(model):
-    return ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0
-
-
 def scores(model, pool, field, targets=None, history=None, kl_weight=1.0):
     """VFM.design_scores_field: [P] fp32, the score of every pool row in the caller's order."""
     x, y, hx, hy, tx, field = check_args(model, pool, None, 0, field, targets, history, kl_weight)
     ops._need_cuda(model._flat, "the model's parameters")
     dev, d = model.device, model.d
-    L = _lists(x, y, hx, hy, tx, field)
+    L = elicit.field_lists(x, y, hx, hy, field, tx)
     U, P = L["ents"].numel(), L["px"].shape[0]
     out = torch.full((P,), float("nan"), dtype=torch.float32, device=dev)
     if U:
@@ -89,7 +57,7 @@ def scores(model, pool, field, targets=None, history=None, kl_weight=1.0):
         model._fresh_params()
         ent, bia, scal = model._views(model._flat)
         o.design_scores(L["ents"], L["ptr"], L["px"], L["hptr"], L["hist_op"], L["tptr"], L["tgt_op"], L["op_x"],
-                        L["pool_op"], ent, bia, scal, ws, out, field, _flags(model), float(kl_weight))
+                        L["pool_op"], ent, bia, scal, ws, out, field, elicit.link_flags(model), float(kl_weight))
     return elicit.to_caller_order(out, L["order"])
 
 
@@ -107,29 +75,14 @@ def select_next_questions(model, pool, field, n=1, targets=None, history=None, k
 def run_field_design(model, pool, y_pool, n_questions, field=0, targets=None, history=None, kl_weight=1.0, reset=False,
                      write=False, return_moments=False, return_theta=False, lds_dim=-1):
     """The design sessions of every entity of column `field` of the pool (VFM.elicit_field_design documents the
-    arguments and the result): the lists above and one call of torch.ops.vfm_hip.design_elicit."""
+    arguments and the result): elicit.run_field_session with the targets' lists and torch.ops.vfm_hip.design_elicit."""
     x, y, hx, hy, tx, field = check_args(model, pool, y_pool, n_questions, field, targets, history, kl_weight)
-    if int(lds_dim) < -1:
-        raise ValueError("lds_dim must be -1 or >= 0")
-    ops._need_cuda(model._flat, "the model's parameters")
-    dev, d, Q = model.device, model.d, int(n_questions)
-    L = _lists(x, y, hx, hy, tx, field)
-    ents = L["ents"]
-    U, P = ents.numel(), L["px"].shape[0]
-    out_row, score, loss, theta, mean, var = elicit._outputs(dev, U, Q, P, d, return_theta, return_moments)
-    res = {"entities": ents}
-    if U:
-        o = _lib.ops()
-        ws = torch.empty(max(o.design_workspace_bytes(U, P, L["op_x"].shape[0], d, int(lds_dim)), 1), dtype=torch.uint8,
-                         device=dev)
-        model._fresh_params()
-        ent, bia, scal = model._views(model._flat)
-        o.design_elicit(ents, L["ptr"], L["px"], L["ys"], L["hptr"], L["hxs"], L["hys"], L["hist_op"], L["tptr"],
-                        L["tgt_op"], L["op_x"], L["pool_op"], ent, bia, scal, ws, out_row, score, loss, theta, mean, var,
-                        field, Q, _flags(model), int(bool(reset)), int(bool(write)), int(lds_dim), float(kl_weight))
-        if write:
-            model.params_changed()      # (rows written outside the step kernels: derived caches are stale)
-    return elicit._result(res, L["order"], out_row, score, loss, theta, mean, var)
+    foldin._check_lds_dim(lds_dim)
+    return elicit.run_field_session(
+        model, x, y, hx, hy, field, n_questions,
+        lambda o, U, P, H, n_ops, d: o.design_workspace_bytes(U, P, n_ops, d, int(lds_dim)), "design_elicit",
+        (field, int(n_questions), elicit.link_flags(model), int(bool(reset)), int(bool(write)), int(lds_dim),
+         float(kl_weight)), write, return_moments, return_theta, targets=tx)
 
 
 def session_for(strategy, session, kw):

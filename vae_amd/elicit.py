@@ -10,6 +10,8 @@ through torch.ops.vfm_hip.elicit.  `run_field` is the same for the entities of a
 number of fields (vfm_elicit_field_f32): full rows, one operand per distinct context.  `run_field_exact` is the field
 form with each round's Adam fit replaced by the exact fold-in's closed-form optimum (vfm_elicit_solve_f32), and
 `run_field_bound` the same for 'class' models with the bound fold-in's rounds (include/vfm_bound.h: vfm_elicit_bound_f32).
+The field forms, design.run_field_design among them, are their argument checks and one call of `run_field_session`
+over the lists of `field_lists`; SESSION_KINDS says which of them the curves run under which strategy names.
 """
 from __future__ import annotations
 
@@ -150,9 +152,8 @@ def run(model, pool, y_pool, n_questions, strategy="variance", history=None, n_s
         ent, bia, scal = model._views(model._flat)
         lik = _lib.LIK_NORMAL if model.output == "reg" else _lib.LIK_BERNOULLI
         o.elicit(users, ptr, items, ys, hptr, hitems, hys, op_x, pool_op, hist_op, ent, bia, scal, ws, out_row, score,
-                 loss, theta, mean, var, Q, code, obj, lik, ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0,
-                 int(n_steps), int(n_samples), int(bool(reset)), int(bool(write)), int(lds_rows), float(lr),
-                 float(kl_weight), _seed64(seed), int(t0))
+                 loss, theta, mean, var, Q, code, obj, lik, link_flags(model), int(n_steps), int(n_samples),
+                 int(bool(reset)), int(bool(write)), int(lds_rows), float(lr), float(kl_weight), _seed64(seed), int(t0))
         if write:
             model.params_changed()      # (rows written outside the step kernels: derived caches are stale)
     return _result(res, order, out_row, score, loss, theta, mean, var)
@@ -161,6 +162,75 @@ def run(model, pool, y_pool, n_questions, strategy="variance", history=None, n_s
 # ---------------------------------------------------------------------------------------------------------------------
 # the field form: respondents are the entities of one column of a model with any number of fields
 # ---------------------------------------------------------------------------------------------------------------------
+NO_TARGETS = object()                    # field_lists' `targets` when the caller has no use for target lists
+
+
+def field_lists(x, y, hx, hy, field, targets=NO_TARGETS):
+    """The per-respondent lists of a field-form session (torch, any device; stable sorts: the caller's order is kept
+    within a respondent) and one operand per distinct context of all the rows listed: dict(order, ents, ptr, px, ys,
+    hptr, hxs, hys, tptr, op_x, pool_op, hist_op, tgt_op).  hx None or without rows: no history (None for its four).
+    targets: [R, F] rows grouped as the history's; None: each respondent's own pool rows (tptr is ptr, tgt_op is
+    pool_op); NO_TARGETS: none are built (tptr, tgt_op None) and op_x is the distinct contexts of pool and history."""
+    order, ents, ptr = pool_lists(x, field)
+    px, ys = x[order].contiguous(), y[order].contiguous()
+    hptr = hxs = hys = hist_op = txs = tptr = tgt_op = None
+    if hx is not None and hx.shape[0]:
+        horder, hptr = history_lists(ents, hx, field)
+        hxs, hys = hx[horder].contiguous(), hy[horder].contiguous()
+    if targets is None:
+        tptr = ptr
+    elif targets is not NO_TARGETS:
+        torder, tptr = history_lists(ents, targets, field)
+        txs = targets[torder]
+    parts = [t for t in (px, hxs, txs) if t is not None]
+    ctx = (px if len(parts) == 1 else torch.cat(parts)).clone()       # one operand per DISTINCT context: it is frozen
+    ctx[:, field] = 0
+    op_x, inv = torch.unique(ctx, dim=0, return_inverse=True)
+    inv = inv.reshape(-1)
+    P, H = px.shape[0], 0 if hxs is None else hxs.shape[0]
+    pool_op = inv[:P].contiguous()
+    if hxs is not None:
+        hist_op = inv[P:P + H].contiguous()
+    if targets is None:
+        tgt_op = pool_op
+    elif txs is not None:
+        tgt_op = inv[P + H:P + H + txs.shape[0]].contiguous()
+    return dict(order=order, ents=ents, ptr=ptr, px=px, ys=ys, hptr=hptr, hxs=hxs, hys=hys, tptr=tptr,
+                op_x=op_x.contiguous(), pool_op=pool_op, hist_op=hist_op, tgt_op=tgt_op)
+
+
+def link_flags(model):
+    return ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0
+
+
+def run_field_session(model, x, y, hx, hy, field, n_questions, workspace, op, options, write, return_moments,
+                      return_theta, targets=NO_TARGETS):
+    """One launch of a field-form session over checked arguments, whichever form: the lists, the outputs, the workspace,
+    the call and the result in the caller's pool order.  workspace(o, U, P, H, n_ops, d): the form's size call on
+    o = torch.ops.vfm_hip; op: the session op's name there; options: what follows out_var in its schema.  targets (as
+    field_lists'): given or None for the one form that has tgt_ptr and tgt_op, which sit where its schema has them."""
+    ops._need_cuda(model._flat, "the model's parameters")
+    dev, d, Q = model.device, model.d, int(n_questions)
+    L = field_lists(x, y, hx, hy, field, targets)
+    ents, px = L["ents"], L["px"]
+    U, P = ents.numel(), px.shape[0]
+    out_row, score, loss, theta, mean, var = _outputs(dev, U, Q, P, d, return_theta, return_moments)
+    res = {"entities": ents}
+    if U:
+        o = _lib.ops()
+        H = 0 if L["hxs"] is None else L["hxs"].shape[0]
+        ws = torch.empty(max(workspace(o, U, P, H, L["op_x"].shape[0], d), 1), dtype=torch.uint8, device=dev)
+        model._fresh_params()
+        ent, bia, scal = model._views(model._flat)
+        operands = ((L["op_x"], L["pool_op"], L["hist_op"]) if targets is NO_TARGETS else
+                    (L["hist_op"], L["tptr"], L["tgt_op"], L["op_x"], L["pool_op"]))
+        getattr(o, op)(ents, L["ptr"], px, L["ys"], L["hptr"], L["hxs"], L["hys"], *operands, ent, bia, scal, ws, out_row,
+                       score, loss, theta, mean, var, *options)
+        if write:
+            model.params_changed()      # (rows written outside the step kernels: derived caches are stale)
+    return _result(res, L["order"], out_row, score, loss, theta, mean, var)
+
+
 def check_args_field(model, pool, y_pool, n_questions, field, strategy, history, n_steps, lr, objective, n_samples,
                      kl_weight, key_field):
     """Validate a field-form session call (no GPU needed).  Returns (pool [P, F] int64, y_pool [P] fp32, hist_x [H, F] or
@@ -190,39 +260,14 @@ def run_field(model, pool, y_pool, n_questions, field=0, strategy="variance", hi
     x, y, hx, hy, objective, code, field, kf = check_args_field(model, pool, y_pool, n_questions, field, strategy,
                                                                 history, n_steps, lr, objective, n_samples, kl_weight,
                                                                 key_field)
-    ops._need_cuda(model._flat, "the model's parameters")
-    dev, d, Q = model.device, model.d, int(n_questions)
-    order, ents, ptr = pool_lists(x, field)
-    px, ys = x[order].contiguous(), y[order].contiguous()
-    U, P = ents.numel(), px.shape[0]
-    hptr = hxs = hys = hist_op = None
-    if hx is not None and hx.shape[0]:
-        horder, hptr = history_lists(ents, hx, field)
-        hxs, hys = hx[horder].contiguous(), hy[horder].contiguous()
-    out_row, score, loss, theta, mean, var = _outputs(dev, U, Q, P, d, return_theta, return_moments)
-    res = {"entities": ents}
-    if U:
-        o = _lib.ops()
-        obj = foldin.OBJECTIVES[objective]
-        ctx = (px if hxs is None else torch.cat([px, hxs])).clone()     # one operand per DISTINCT context: it is frozen
-        ctx[:, field] = 0
-        op_x, inv = torch.unique(ctx, dim=0, return_inverse=True)
-        inv = inv.reshape(-1)
-        op_x, pool_op = op_x.contiguous(), inv[:P].contiguous()
-        if hxs is not None:
-            hist_op = inv[P:].contiguous()
-        ws = torch.empty(max(o.elicit_field_workspace_bytes(P, op_x.shape[0], d, obj), 1), dtype=torch.uint8, device=dev)
-        model._fresh_params()
-        ent, bia, scal = model._views(model._flat)
-        lik = _lib.LIK_NORMAL if model.output == "reg" else _lib.LIK_BERNOULLI
-        o.elicit_field(ents, ptr, px, ys, hptr, hxs, hys, op_x, pool_op, hist_op, ent, bia, scal, ws, out_row, score,
-                       loss, theta, mean, var, field, kf, Q, code, obj, lik,
-                       ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, int(n_steps), int(n_samples),
-                       int(bool(reset)), int(bool(write)), int(lds_rows), float(lr), float(kl_weight), _seed64(seed),
-                       int(t0))
-        if write:
-            model.params_changed()      # (rows written outside the step kernels: derived caches are stale)
-    return _result(res, order, out_row, score, loss, theta, mean, var)
+    obj = foldin.OBJECTIVES[objective]
+    lik = _lib.LIK_NORMAL if model.output == "reg" else _lib.LIK_BERNOULLI
+    return run_field_session(
+        model, x, y, hx, hy, field, n_questions,
+        lambda o, U, P, H, n_ops, d: o.elicit_field_workspace_bytes(P, n_ops, d, obj), "elicit_field",
+        (field, kf, int(n_questions), code, obj, lik, link_flags(model), int(n_steps), int(n_samples), int(bool(reset)),
+         int(bool(write)), int(lds_rows), float(lr), float(kl_weight), _seed64(seed), int(t0)),
+        write, return_moments, return_theta)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -234,8 +279,7 @@ def check_args_field_exact(model, pool, y_pool, n_questions, field, strategy, hi
     if model.output != "reg":
         raise ValueError("the exact session needs a 'reg' model (Gaussian likelihood): the closed form it solves has "
                          "none for 'class'; use elicit_field")
-    if not float(kl_weight) > 0.0 or not math.isfinite(float(kl_weight)):
-        raise ValueError("kl_weight must be > 0 and finite: the prior term is what makes each system positive definite")
+    foldin._check_kl_positive(kl_weight)
     if model.F < 2:
         raise ValueError("elicit_field_exact needs a model with at least two fields")
     x, y, hx, hy, _, code, field, kf = check_args_field(model, pool, y_pool, n_questions, field, strategy, history, 0,
@@ -250,39 +294,12 @@ def run_field_exact(model, pool, y_pool, n_questions, field=0, strategy="varianc
     and the result): run_field's lists and operands, and one call of torch.ops.vfm_hip.elicit_solve."""
     x, y, hx, hy, code, field, kf = check_args_field_exact(model, pool, y_pool, n_questions, field, strategy, history,
                                                            kl_weight, key_field)
-    if int(lds_dim) < -1:
-        raise ValueError("lds_dim must be -1 or >= 0")
-    ops._need_cuda(model._flat, "the model's parameters")
-    dev, d, Q = model.device, model.d, int(n_questions)
-    order, ents, ptr = pool_lists(x, field)
-    px, ys = x[order].contiguous(), y[order].contiguous()
-    U, P = ents.numel(), px.shape[0]
-    hptr = hxs = hys = hist_op = None
-    if hx is not None and hx.shape[0]:
-        horder, hptr = history_lists(ents, hx, field)
-        hxs, hys = hx[horder].contiguous(), hy[horder].contiguous()
-    out_row, score, loss, theta, mean, var = _outputs(dev, U, Q, P, d, return_theta, return_moments)
-    res = {"entities": ents}
-    if U:
-        o = _lib.ops()
-        ctx = (px if hxs is None else torch.cat([px, hxs])).clone()     # one operand per DISTINCT context: it is frozen
-        ctx[:, field] = 0
-        op_x, inv = torch.unique(ctx, dim=0, return_inverse=True)
-        inv = inv.reshape(-1)
-        op_x, pool_op = op_x.contiguous(), inv[:P].contiguous()
-        if hxs is not None:
-            hist_op = inv[P:].contiguous()
-        ws = torch.empty(max(o.elicit_solve_workspace_bytes(U, P, op_x.shape[0], d, int(lds_dim)), 1), dtype=torch.uint8,
-                         device=dev)
-        model._fresh_params()
-        ent, bia, scal = model._views(model._flat)
-        o.elicit_solve(ents, ptr, px, ys, hptr, hxs, hys, op_x, pool_op, hist_op, ent, bia, scal, ws, out_row, score,
-                       loss, theta, mean, var, field, kf, Q, code,
-                       ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, int(bool(reset)), int(bool(write)),
-                       int(lds_dim), float(kl_weight), _seed64(seed))
-        if write:
-            model.params_changed()      # (rows written outside the step kernels: derived caches are stale)
-    return _result(res, order, out_row, score, loss, theta, mean, var)
+    foldin._check_lds_dim(lds_dim)
+    return run_field_session(
+        model, x, y, hx, hy, field, n_questions,
+        lambda o, U, P, H, n_ops, d: o.elicit_solve_workspace_bytes(U, P, n_ops, d, int(lds_dim)), "elicit_solve",
+        (field, kf, int(n_questions), code, link_flags(model), int(bool(reset)), int(bool(write)), int(lds_dim),
+         float(kl_weight), _seed64(seed)), write, return_moments, return_theta)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -301,10 +318,8 @@ def check_args_field_bound(model, pool, y_pool, n_questions, field, strategy, hi
                          "optimum itself; use elicit_field_exact")
     if strategy == "design":
         raise ValueError(DESIGN_NEEDS_REG)
-    if not float(kl_weight) > 0.0 or not math.isfinite(float(kl_weight)):
-        raise ValueError("kl_weight must be > 0 and finite: the prior term is what makes each system positive definite")
-    if isinstance(n_iters, bool) or int(n_iters) != n_iters or int(n_iters) < 1:
-        raise ValueError("n_iters must be an integer >= 1")
+    foldin._check_kl_positive(kl_weight)
+    foldin._check_n_iters(n_iters)
     if model.F < 2:
         raise ValueError("elicit_field_bound needs a model with at least two fields")
     x, y, hx, hy, _, code, field, kf = check_args_field(model, pool, y_pool, n_questions, field, strategy, history, 0,
@@ -322,40 +337,13 @@ def run_field_bound(model, pool, y_pool, n_questions, field=0, strategy="varianc
     and the result): run_field's lists and operands, and one call of torch.ops.vfm_hip.elicit_bound."""
     x, y, hx, hy, code, field, kf = check_args_field_bound(model, pool, y_pool, n_questions, field, strategy, history,
                                                            kl_weight, n_iters, key_field)
-    if int(lds_dim) < -1:
-        raise ValueError("lds_dim must be -1 or >= 0")
-    ops._need_cuda(model._flat, "the model's parameters")
-    dev, d, Q = model.device, model.d, int(n_questions)
-    order, ents, ptr = pool_lists(x, field)
-    px, ys = x[order].contiguous(), y[order].contiguous()
-    U, P = ents.numel(), px.shape[0]
-    hptr = hxs = hys = hist_op = None
-    if hx is not None and hx.shape[0]:
-        horder, hptr = history_lists(ents, hx, field)
-        hxs, hys = hx[horder].contiguous(), hy[horder].contiguous()
-    out_row, score, loss, theta, mean, var = _outputs(dev, U, Q, P, d, return_theta, return_moments)
-    res = {"entities": ents}
-    if U:
-        o = _lib.ops()
-        ctx = (px if hxs is None else torch.cat([px, hxs])).clone()     # one operand per DISTINCT context: it is frozen
-        ctx[:, field] = 0
-        op_x, inv = torch.unique(ctx, dim=0, return_inverse=True)
-        inv = inv.reshape(-1)
-        op_x, pool_op = op_x.contiguous(), inv[:P].contiguous()
-        H = 0
-        if hxs is not None:
-            hist_op, H = inv[P:].contiguous(), hxs.shape[0]
-        ws = torch.empty(max(o.elicit_bound_workspace_bytes(U, P, H, op_x.shape[0], d, Q, int(lds_dim)), 1),
-                         dtype=torch.uint8, device=dev)
-        model._fresh_params()
-        ent, bia, scal = model._views(model._flat)
-        o.elicit_bound(ents, ptr, px, ys, hptr, hxs, hys, op_x, pool_op, hist_op, ent, bia, scal, ws, out_row, score,
-                       loss, theta, mean, var, field, kf, Q, code,
-                       ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, int(bool(reset)), int(bool(write)),
-                       int(lds_dim), float(kl_weight), _seed64(seed), int(n_iters))
-        if write:
-            model.params_changed()      # (rows written outside the step kernels: derived caches are stale)
-    return _result(res, order, out_row, score, loss, theta, mean, var)
+    foldin._check_lds_dim(lds_dim)
+    Q = int(n_questions)
+    return run_field_session(
+        model, x, y, hx, hy, field, Q,
+        lambda o, U, P, H, n_ops, d: o.elicit_bound_workspace_bytes(U, P, H, n_ops, d, Q, int(lds_dim)), "elicit_bound",
+        (field, kf, Q, code, link_flags(model), int(bool(reset)), int(bool(write)), int(lds_dim), float(kl_weight),
+         _seed64(seed), int(n_iters)), write, return_moments, return_theta)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -396,19 +384,33 @@ def metric(output, mean, var, y):
     return auc(torch.sigmoid(mean / torch.sqrt(1.0 + math.pi / 8.0 * var)), y)
 
 
-def _curve_strategy(s, exact):
-    """A curve's strategy name: rank.STRATEGIES', or "design" (vae_amd/design.py) over the exact sessions (exact: True;
-    "bound": the bound sessions, which refuse it)."""
-    if s == "design" and exact == "bound":
-        raise ValueError(DESIGN_NEEDS_REG)
-    if not (exact and s == "design"):
+# The session kinds of the curves: the runner (by its name in this module, looked up when used), the strategy names
+# beyond rank.STRATEGIES that the kind accepts -- they run under design.session_for -- and the ones it refuses, with why.
+# The two-field `run` and any other runner count as "adam": rank.STRATEGIES' names and nothing else.
+SESSION_KINDS = {
+    "adam": dict(runner="run_field", accepts=(), refuses={}),
+    "exact": dict(runner="run_field_exact", accepts=("design",), refuses={}),
+    "bound": dict(runner="run_field_bound", accepts=(), refuses={"design": DESIGN_NEEDS_REG}),
+}
+
+
+def _kind_of(session):
+    return next((k for k, e in SESSION_KINDS.items() if session is globals()[e["runner"]]), "adam")
+
+
+def _curve_strategy(s, kind):
+    """Check a curve's strategy name: rank.STRATEGIES', or one the session kind accepts."""
+    if s in SESSION_KINDS[kind]["refuses"]:
+        raise ValueError(SESSION_KINDS[kind]["refuses"][s])
+    if s not in SESSION_KINDS[kind]["accepts"]:
         strategy_code(s)
 
 
-def _session_of(s, session, kw):
-    """(runner, options) of strategy s of a curve: the exact curves route "design" to design.run_field_design, where
-    alone `targets` is an option; everything else is `session` with the caller's options."""
-    if session is run_field_exact:
+def _session_of(s, kind, session, kw):
+    """(runner, options) of strategy s of a curve: a kind with names of its own routes through design.session_for (the
+    exact curves: "design" to design.run_field_design, where alone `targets` is an option); everything else is
+    `session` with the caller's options."""
+    if SESSION_KINDS[kind]["accepts"]:
         from . import design
         return design.session_for(s, session, kw)
     return session, kw
@@ -422,12 +424,12 @@ def curve(model, pool, y_pool, n_questions, strategies=("mean", "random", "varia
     for key in ("write", "return_moments", "return_theta"):
         if key in kw:
             raise ValueError(f"elicitation_curve sets {key} itself")
-    strategies = list(strategies)
+    kind, strategies = _kind_of(session), list(strategies)
     for s in strategies:
-        _curve_strategy(s, "bound" if session is run_field_bound else session is run_field_exact)
+        _curve_strategy(s, kind)
     out, left = {}, {}
     for s in strategies:
-        run_s, kw_s = _session_of(s, session, kw)
+        run_s, kw_s = _session_of(s, kind, session, kw)
         r = run_s(model, pool, y_pool, n_questions, strategy=s, write=False, return_moments=True, **kw_s)
         y = torch.as_tensor(y_pool).to(model.device, torch.float32).reshape(-1)
         when = asked_round(r["rows"], y.numel())
@@ -502,9 +504,9 @@ def ranking_curve(model, pool, y_pool, n_questions, field, X_test, y_test, rank_
             raise ValueError(f"elicitation_ranking_curve_field sets {key} itself")
     if bound and exact:
         raise ValueError("bound=True and exact=True: the exact sessions are for 'reg' models, the bound ones for 'class'")
-    strategies = list(strategies)
+    kind, strategies = "bound" if bound else "exact" if exact else "adam", list(strategies)
     for s in strategies:
-        _curve_strategy(s, "bound" if bound else bool(exact))
+        _curve_strategy(s, kind)
     field = rank._field_arg(model, field)
     rank_field = rank._field_arg(model, rank_field)
     if rank_field == field:
@@ -522,12 +524,12 @@ def ranking_curve(model, pool, y_pool, n_questions, field, X_test, y_test, rank_
     relevant = (y >= (4.0 if threshold is None else float(threshold))) if model.output == "reg" else (y == 1)
     X_rel = rank._context_rows(model, X[relevant.to(X.device)], "X_test", rank_field, check_field_column=True)
     ex = rank._context_rows(model, exclude, "exclude", rank_field, check_field_column=True) if exclude is not None else None
-    session = run_field_bound if bound else run_field_exact if exact else run_field
+    session = globals()[SESSION_KINDS[kind]["runner"]]
     dev, d = model.device, model.d
     out = {}
     n_queries = 0
     for s in strategies:
-        run_s, kw_s = _session_of(s, session, session_kw)
+        run_s, kw_s = _session_of(s, kind, session, session_kw)
         r = run_s(model, pool, y_pool, n_questions, field, strategy=s, write=False, return_theta=True, **kw_s)
         ents, Q = r["entities"], int(n_questions)
         U = ents.numel()

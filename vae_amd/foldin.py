@@ -30,6 +30,22 @@ def field_range(model, field: int):
     return lo, lo + model.field_sizes[field]
 
 
+def _check_kl_positive(kl_weight):
+    """The exact and the bound solves' condition on kl_weight (the sessions over them and the design score share it)."""
+    if not float(kl_weight) > 0.0 or not math.isfinite(float(kl_weight)):
+        raise ValueError("kl_weight must be > 0 and finite: the prior term is what makes each system positive definite")
+
+
+def _check_n_iters(n_iters):
+    if isinstance(n_iters, bool) or int(n_iters) != n_iters or int(n_iters) < 1:
+        raise ValueError("n_iters must be an integer >= 1")
+
+
+def _check_lds_dim(lds_dim):
+    if int(lds_dim) < -1:
+        raise ValueError("lds_dim must be -1 or >= 0")
+
+
 def check_args(model, X, y, field, objective, n_samples, n_steps=0, lr=0.0, kl_weight=1.0):
     """Validate a fold-in call (no GPU needed).  Returns (x [R, F] int64, y [R] fp32, objective name) on the model's
     device."""
@@ -133,8 +149,7 @@ def check_args_exact(model, X, y, field, kl_weight=1.0):
     if model.output != "reg":
         raise ValueError("the exact fold-in needs a 'reg' model (Gaussian likelihood): the closed form it solves has "
                          "none for 'class'; use fold_in or fold_in_bound")
-    if not float(kl_weight) > 0.0 or not math.isfinite(float(kl_weight)):
-        raise ValueError("kl_weight must be > 0 and finite: the prior term is what makes each system positive definite")
+    _check_kl_positive(kl_weight)
     x, y, _ = check_args(model, X, y, field, "closed_form", 1, 0, 0.0, kl_weight)
     return x, y
 
@@ -143,8 +158,7 @@ def run_exact(model, X, y, field=0, kl_weight=1.0, lds_dim=-1):
     """One exact fold-in launch (vfm_foldin_solve_f32): the closed-form optimum of every folded entity.  Returns
     (entities [E], loss [E], rows [E])."""
     x, y = check_args_exact(model, X, y, field, kl_weight)
-    if int(lds_dim) < -1:
-        raise ValueError("lds_dim must be -1 or >= 0")
+    _check_lds_dim(lds_dim)
     ops._need_cuda(model._flat, "the model's parameters")
     dev, d = model.device, model.d
     xs, ys, ents, ptr, counts = row_lists(x, y, field)
@@ -171,10 +185,8 @@ def check_args_bound(model, X, y, field, kl_weight=1.0, n_iters=8):
     if model.output != "class":
         raise ValueError("the bound fold-in needs a 'class' model (Bernoulli likelihood): a 'reg' model has the exact "
                          "optimum itself; use fold_in_exact")
-    if not float(kl_weight) > 0.0 or not math.isfinite(float(kl_weight)):
-        raise ValueError("kl_weight must be > 0 and finite: the prior term is what makes each system positive definite")
-    if isinstance(n_iters, bool) or int(n_iters) != n_iters or int(n_iters) < 1:
-        raise ValueError("n_iters must be an integer >= 1")
+    _check_kl_positive(kl_weight)
+    _check_n_iters(n_iters)
     x, y, _ = check_args(model, X, y, field, "sampled", 1, 0, 0.0, kl_weight)
     if y.numel() and not bool(((y == 0) | (y == 1)).all()):
         raise ValueError("y must hold the labels 0 and 1 of a 'class' model")
@@ -186,8 +198,7 @@ def run_bound(model, X, y, field=0, kl_weight=1.0, n_iters=8, reset=False, lds_d
     bound's two exact block minimisers for every folded entity (mode=MODE_OBJECTIVE: B_e at the current rows, nothing
     written; n_iters is not used).  Returns (entities [E], loss [E] = B_e, rows [E])."""
     x, y = check_args_bound(model, X, y, field, kl_weight, n_iters)
-    if int(lds_dim) < -1:
-        raise ValueError("lds_dim must be -1 or >= 0")
+    _check_lds_dim(lds_dim)
     ops._need_cuda(model._flat, "the model's parameters")
     dev, d = model.device, model.d
     xs, ys, ents, ptr, counts = row_lists(x, y, field)
