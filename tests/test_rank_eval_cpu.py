@@ -1,5 +1,6 @@
 """CPU: the ranking metrics of the held-out evaluation (vae_amd.rank.ranking_metrics) from exact ranks against brute
-force and sklearn, their edge cases, and the argument checks of the two C entry points (include/vfm_rank.h)."""
+force and sklearn, their edge cases, the eligibility and candidates helpers every ranking form shares against Python
+sets, and the argument checks of the two C entry points (include/vfm_rank.h)."""
 import ctypes as C
 import math
 import os
@@ -86,6 +87,74 @@ def test_metric_edge_cases():
     for ks in ([], [0], [3, -1]):
         with pytest.raises(ValueError):
             ranking_metrics(torch.tensor([0]), torch.tensor([0]), torch.tensor([0, 1]), torch.tensor([1]), ks)
+
+
+def test_eligibility_helpers_match_python_sets():
+    """rank._ineligible and rank._apply_ineligible against sets, through the CSRs of the pair form (the queries are the
+    users) and of the field form (the queries are contexts), and rank._candidates with both wordings of its errors."""
+    from vae_amd import rank
+    Q, lo, n_items = 7, 20, 9                               # ids lo .. lo + 8; T past them
+    T = lo + n_items + 3
+    g = torch.Generator().manual_seed(5)
+    all_ids = list(range(lo, lo + n_items))
+
+    def pairs(n, skip=()):
+        q = torch.randint(0, Q, (n,), generator=g)
+        ids = lo + torch.randint(0, n_items, (n,), generator=g)
+        keep = torch.tensor([int(v) not in skip for v in q])
+        return q[keep], ids[keep]
+
+    pos_q, pos_id = pairs(30, skip=(3,))                    # query 3 has no positive
+    ex_q, ex_id = pairs(25, skip=(5,))                      # query 5 has an empty exclusion list
+    # the pair form: users 100 .. 106 in a scrambled order are the queries; the field form: contexts [u, 0, c]
+    users = torch.tensor([104, 100, 106, 101, 105, 103, 102])
+    ctx = torch.stack([users, torch.zeros_like(users), 200 + torch.arange(Q)], 1)
+    forms = {
+        "pair": (rank.exclusion_csr(users, torch.stack([users[pos_q], pos_id], 1), T),
+                 rank.exclusion_csr(users, torch.stack([users[ex_q], ex_id], 1), T)),
+        "field": (rank.query_csr(pos_q, pos_id, Q, T),
+                  rank.field_exclusion_csr(ctx, torch.stack([users[ex_q], ex_id, 200 + ex_q], 1), 1, [0, 2], T)),
+    }
+    excluded = {(int(q), int(i)) for q, i in zip(ex_q, ex_id)}
+    assert not any(q == 5 for q, _ in excluded) and 3 not in set(pos_q.tolist())
+    cands = {"explicit": [lo + 1, lo + 2, lo + 4, lo + 7, lo + 8], "range": None, "empty": []}
+    for form, ((pptr, pitems), (eptr, ex_items)) in forms.items():
+        pq = torch.repeat_interleave(torch.arange(Q), pptr[1:] - pptr[:-1])
+        assert {(int(q), int(i)) for q, i in zip(pq, pitems)} == {(int(q), int(i)) for q, i in zip(pos_q, pos_id)}
+        assert int(eptr[6] - eptr[5]) == 0 and int(pptr[4] - pptr[3]) == 0
+        for name, values in cands.items():
+            for with_excl in (True, False):
+                cand, n_cand = rank._candidates(values, lo, lo + n_items, "cpu")
+                assert n_cand == (n_items if values is None else len(values))
+                allowed = set(all_ids if values is None else values)
+                want = [int(i) not in allowed or (with_excl and (int(q), int(i)) in excluded) for q, i in zip(pq, pitems)]
+                e = (eptr, ex_items) if with_excl else (None, None)
+                bad = rank._ineligible(pitems, pq, cand, *e, Q, T)
+                assert bad.tolist() == want, (form, name, with_excl)
+                # the drop step: the survivors, their CSR, the count
+                ptr2, items2, pq2, n_dropped = rank._apply_ineligible(bad, pptr, pitems, pq, Q, "drop", None)
+                kept = [(int(q), int(i)) for (q, i), b in zip(zip(pq, pitems), want) if not b]
+                assert list(zip(pq2.tolist(), items2.tolist())) == kept and n_dropped == sum(want)
+                assert ptr2.tolist() == [sum(q < u for q, _ in kept) for u in range(Q + 1)]
+                if any(want):
+                    first = want.index(True)
+                    with pytest.raises(ValueError, match=f"positive {first} of its form"):
+                        rank._apply_ineligible(bad, pptr, pitems, pq, Q, "raise", lambda j: f"positive {j} of its form")
+                else:
+                    assert ptr2 is pptr and items2 is pitems
+        no_lists = (torch.zeros(Q + 1, dtype=torch.int64), torch.zeros(0, dtype=torch.int64))      # every list empty
+        assert not rank._ineligible(pitems, pq, None, *no_lists, Q, T).any()
+    # the candidates parser: sorted, and its two errors in the wording of either form
+    cand, n_cand = rank._candidates([lo + 5, lo, lo + 3], lo, lo + n_items, "cpu")
+    assert cand.tolist() == [lo, lo + 3, lo + 5] and n_cand == 3 and cand.dtype == torch.int64
+    with pytest.raises(ValueError, match=r"candidate ids must lie in the field's range \[20, 29\)"):
+        rank._candidates([lo + n_items], lo, lo + n_items, "cpu")
+    with pytest.raises(ValueError, match="duplicate candidates"):
+        rank._candidates([lo, lo + 1, lo], lo, lo + n_items, "cpu")
+    with pytest.raises(ValueError, match=r"item ids must lie in \[20, 29\)"):
+        rank._candidates([lo - 1], lo, lo + n_items, "cpu", rank._ITEM_WORDS)
+    with pytest.raises(ValueError, match="duplicate candidate items"):
+        rank._candidates([lo + 2, lo + 2], lo, lo + n_items, "cpu", rank._ITEM_WORDS)
 
 
 def _lib():

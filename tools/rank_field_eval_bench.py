@@ -103,10 +103,7 @@ def main():
     cols = [0, 2]
     ptr, ex_items = rank.field_exclusion_csr(ctx, ex, field, cols, T)
     qi = torch.repeat_interleave(torch.arange(Q, device=dev), npos)
-    ek = torch.repeat_interleave(torch.arange(Q, device=dev), ptr[1:] - ptr[:-1]) * T + ex_items       # sorted
-    pk = qi * T + pos[:, field]
-    j = torch.searchsorted(ek, pk).clamp_(max=ek.numel() - 1)
-    keep = ek[j] != pk                                                                    # none of them excluded
+    keep = ~rank._ineligible(pos[:, field], qi, None, ptr, ex_items, Q, T)                # none of them excluded
     pos = pos[keep]
     # the positives CSR over the FIXED queries (a context whose every draw was excluded keeps an empty segment)
     pptr, pitems = rank.exclusion_csr(torch.arange(Q, device=dev), torch.stack([qi[keep], pos[:, field]], 1), T)

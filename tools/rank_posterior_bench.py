@@ -78,10 +78,7 @@ def main():
     npos = (torch.rand(Q, device=dev, generator=g).log() * (-13.5)).long() + 1            # mean ~14
     qi = torch.repeat_interleave(torch.arange(Q, device=dev), npos)
     pid = lo + torch.randint(0, M, (qi.numel(),), device=dev, generator=g)
-    ek = torch.repeat_interleave(torch.arange(Q, device=dev), ptr[1:] - ptr[:-1]) * T + ex_items       # sorted
-    pk = qi * T + pid
-    j = torch.searchsorted(ek, pk).clamp_(max=ek.numel() - 1)
-    keep = ek[j] != pk                                                                    # none of them excluded
+    keep = ~rank._ineligible(pid, qi, None, ptr, ex_items, Q, T)                          # none of them excluded
     pptr, pitems = rank.query_csr(qi[keep], pid[keep], Q, T)
     n_pos = pitems.numel()
     ent, bia, scal = m._views(m._flat)

@@ -36,7 +36,8 @@ inline void* stream_of(const Tensor& t) { return (void*)c10::hip::getCurrentHIPS
 // vfm_design_t), after VFM_STRUCT_INIT.  An op is a sequence of them plus its own scalars; the rows come first: the
 // outputs and the history are sized by the U, P and F they set.
 
-// the model's tables: T, d and the three pointers
+// the model's tables: T, d and the three pointers.  S: a session struct, or any struct with these five members (the
+// ranking ops, whose C entry points take plain arguments, keep one of their own: vfm_rank_ops.cpp)
 template <class S>
 void fill_tables(S& p, const Tensor& entity, const Tensor& bias, const Tensor& scalars) {
   dev_tensor(entity, at::kFloat, "entity_params"); dev_tensor(bias, at::kFloat, "bias_params");

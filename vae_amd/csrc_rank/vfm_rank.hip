@@ -262,42 +262,25 @@ int vfm_rank_items_f32(int64_t U, const int64_t* users, int64_t n_cand, const in
                        const float* entity_params, const float* bias_params, const float* scalars, void* workspace,
                        int64_t workspace_bytes, int64_t* out_items, float* out_score, float* out_mean,
                        float* out_var, void* stream) {
+  RankCall r;
+  r.Q = U; r.queries = users;
+  r.n_cand = n_cand; r.cand = cand; r.cand_lo = item_lo;
+  r.excl_ptr = excl_ptr; r.excl_items = excl_items; r.n_excl = n_excl;
+  r.T = T; r.F = F; r.d = d; r.ent = entity_params; r.bias = bias_params; r.scal = scalars;
+  r.workspace = workspace; r.workspace_bytes = workspace_bytes;
+  r.k = k; r.strategy = strategy; r.flags = flags; r.n_splits = n_splits; r.seed = seed;
+  r.out_items = out_items; r.out_score = out_score; r.out_mean = out_mean; r.out_var = out_var;
+  r.stream = (hipStream_t)stream;
   if (int rc = check_common(T, d, flags, strategy)) return rc;
   if (F != 2) return vfm::fail(VFM_E_INVALID, "rank_items: two-field models only (F == 2)");
-  if (k < 1 || k > VFM_RANK_MAX_K) return vfm::fail(VFM_E_INVALID, "k out of range [1,128]");
-  if (U < 0) return vfm::fail(VFM_E_INVALID, "U < 0");
-  if (n_cand < 0 || n_cand >= ((int64_t)1 << 31)) return vfm::fail(VFM_E_INVALID, "n_cand out of range [0,2^31)");
-  if (n_splits < 0 || n_splits > VFM_RANK_MAX_SPLITS) return vfm::fail(VFM_E_INVALID, "n_splits out of range [0,64]");
-  if (!cand && (item_lo < 0 || item_lo + n_cand > T)) return vfm::fail(VFM_E_INVALID, "item range outside [0,T)");
-  if (n_excl < 0 || (n_excl > 0 && (!excl_ptr || !excl_items)))
-    return vfm::fail(VFM_E_INVALID, "exclusion lists: excl_ptr and excl_items together, n_excl >= 0");
+  if (int rc = check_rank_call(r, RANK_ASK_TOPK)) return rc;
   if (U == 0) return 0;
-  if (!users || !entity_params || !bias_params || !scalars || !workspace || !out_items || !out_score || !out_mean ||
-      !out_var)
-    return vfm::fail(VFM_E_INVALID, "null pointer");
   const Layout L = layout_of(U, n_cand, d, k, strategy, n_splits);
-  if (workspace_bytes < L.bytes) return vfm::fail(VFM_E_INVALID, "workspace too small (vfm_rank_workspace_bytes)");
-  if (((uintptr_t)workspace) & 255) return vfm::fail(VFM_E_INVALID, "workspace must be 256-byte aligned");
+  if (int rc = check_rank_workspace(r, L.bytes, "workspace too small (vfm_rank_workspace_bytes)")) return rc;
 
-  const hipStream_t st = (hipStream_t)stream;
-  const bool sp = (flags & VFM_FLAG_LINK_SOFTPLUS) != 0;
-  char* ws = (char*)workspace;
-  RankArgs a;
-  a.U = U; a.n_cand = n_cand; a.item_lo = item_lo; a.n_excl = excl_ptr ? n_excl : 0;
-  a.users = users; a.cand = cand; a.excl_ptr = excl_ptr; a.excl_items = excl_items;
-  a.ops = TileOps{(const float*)(ws + L.off_uop), (const float*)(ws + L.off_iop), (const float*)(ws + L.off_ucon),
-                  (const float*)(ws + L.off_icon), L.Kp, L.KA, L.KB};
-  a.ls = (float*)(ws + L.off_ls); a.lc = (int*)(ws + L.off_lc);
-  a.k = k; a.n_tiles = L.n_tiles; a.S = L.S; a.seed = seed;
   if (strategy != VFM_RANK_RANDOM)
-    if (int rc = launch_rank_prep(L, ws, U, users, n_cand, cand, item_lo, T, d, sp, entity_params, bias_params, scalars,
-                                  st))
-      return rc;
-  if (int rc = launch_scan(a, strategy, dim3((unsigned)(L.U_pad / UT), (unsigned)L.S), st)) return rc;
-  hipLaunchKernelGGL(k_rank_merge<PairMoments>, dim3((unsigned)U), dim3(MERGE_BLOCK), 0, st, U, k, L.S, a.ls, a.lc, cand,
-                     item_lo, PairMoments{users, T, d, sp, entity_params, bias_params, scalars}, out_items, out_score,
-                     out_mean, out_var);
-  return launch_status("k_rank_merge");
+    if (int rc = launch_rank_prep(L, r)) return rc;
+  return scan_and_merge(r, L, users, PairMoments{users, T, d, r.softplus(), entity_params, bias_params, scalars});
 }
 
 }  // extern "C"

@@ -301,49 +301,34 @@ int vfm_rank_heldout_f32(int64_t U, const int64_t* users, int64_t n_cand, const 
                          const float* entity_params, const float* bias_params, const float* scalars, void* workspace,
                          int64_t workspace_bytes, int64_t* out_rank, int64_t* out_rank_neg, int64_t* out_n_eligible,
                          int64_t* out_n_neg, void* stream) {
+  RankCall r;
+  r.Q = U; r.queries = users;
+  r.n_cand = n_cand; r.cand = cand; r.cand_lo = item_lo;
+  r.excl_ptr = excl_ptr; r.excl_items = excl_items; r.n_excl = n_excl;
+  r.pos_ptr = pos_ptr; r.pos_items = pos_items; r.n_pos = n_pos;
+  r.T = T; r.F = F; r.d = d; r.ent = entity_params; r.bias = bias_params; r.scal = scalars;
+  r.workspace = workspace; r.workspace_bytes = workspace_bytes;
+  r.strategy = strategy; r.flags = flags; r.n_splits = n_splits; r.seed = seed;
+  r.out_rank = out_rank; r.out_rank_neg = out_rank_neg; r.out_n_eligible = out_n_eligible; r.out_n_neg = out_n_neg;
+  r.stream = (hipStream_t)stream;
   if (int rc = check_common(T, d, flags, strategy)) return rc;
   if (F != 2) return vfm::fail(VFM_E_INVALID, "rank_heldout: two-field models only (F == 2)");
-  if (U < 0) return vfm::fail(VFM_E_INVALID, "U < 0");
-  if (n_cand < 0 || n_cand >= ((int64_t)1 << 31)) return vfm::fail(VFM_E_INVALID, "n_cand out of range [0,2^31)");
-  if (n_pos < 0 || n_pos >= ((int64_t)1 << 40)) return vfm::fail(VFM_E_INVALID, "n_pos out of range [0,2^40)");
-  if (n_splits < 0 || n_splits > VFM_RANK_MAX_SPLITS) return vfm::fail(VFM_E_INVALID, "n_splits out of range [0,64]");
-  if (!cand && (item_lo < 0 || item_lo + n_cand > T)) return vfm::fail(VFM_E_INVALID, "item range outside [0,T)");
-  if (n_excl < 0 || (n_excl > 0 && (!excl_ptr || !excl_items)))
-    return vfm::fail(VFM_E_INVALID, "exclusion lists: excl_ptr and excl_items together, n_excl >= 0");
-  if (n_pos > 0 && !pos_items) return vfm::fail(VFM_E_INVALID, "null pointer: pos_items");
+  if (int rc = check_rank_call(r, RANK_ASK_HELDOUT)) return rc;
   if (U == 0) return 0;
-  if (!users || !pos_ptr || !entity_params || !bias_params || !scalars || !workspace || !out_n_eligible || !out_n_neg ||
-      (n_pos > 0 && (!out_rank || !out_rank_neg)))
-    return vfm::fail(VFM_E_INVALID, "null pointer");
   const EvalLayout L = eval_layout_of(U, n_cand, n_pos, d, strategy, n_splits);
-  if (workspace_bytes < L.bytes) return vfm::fail(VFM_E_INVALID, "workspace too small (vfm_rank_eval_workspace_bytes)");
-  if (((uintptr_t)workspace) & 255) return vfm::fail(VFM_E_INVALID, "workspace must be 256-byte aligned");
+  if (int rc = check_rank_workspace(r, L.bytes, "workspace too small (vfm_rank_eval_workspace_bytes)")) return rc;
 
-  const hipStream_t st = (hipStream_t)stream;
-  const bool sp = (flags & VFM_FLAG_LINK_SOFTPLUS) != 0;
   char* ws = (char*)workspace;
   if (n_pos > 0) {
     const unsigned nb = (unsigned)((n_pos + POS_BLOCK - 1) / POS_BLOCK);
-    hipLaunchKernelGGL(k_eval_pos_score, dim3(nb), dim3(POS_BLOCK), 0, st, U, n_pos, users, pos_ptr, pos_items, T, d, sp,
-                       strategy, seed, entity_params, bias_params, scalars, (float*)(ws + L.off_raw),
+    hipLaunchKernelGGL(k_eval_pos_score, dim3(nb), dim3(POS_BLOCK), 0, r.stream, U, n_pos, users, pos_ptr, pos_items, T,
+                       d, r.softplus(), strategy, seed, entity_params, bias_params, scalars, (float*)(ws + L.off_raw),
                        (int64_t*)(ws + L.off_pusr));
     if (int rc = launch_status("k_eval_pos_score")) return rc;
   }
   if (strategy != VFM_RANK_RANDOM)
-    if (int rc = launch_rank_prep(L, ws, U, users, n_cand, cand, item_lo, T, d, sp, entity_params, bias_params, scalars,
-                                  st))
-      return rc;
-  vfm::RankEval a;
-  a.U = U; a.n_cand = n_cand; a.item_lo = item_lo; a.n_excl = excl_ptr ? n_excl : 0; a.n_pos = n_pos;
-  a.keys = users; a.cand = cand; a.excl_ptr = excl_ptr; a.excl_items = excl_items;
-  a.pos_ptr = pos_ptr; a.pos_items = pos_items;
-  a.uop = (const float*)(ws + L.off_uop); a.iop = (const float*)(ws + L.off_iop);
-  a.ucon = (const float*)(ws + L.off_ucon); a.icon = (const float*)(ws + L.off_icon);
-  a.Kp = L.Kp; a.KA = L.KA; a.KB = L.KB;
-  eval_tail_into(a, ws, L);
-  a.n_tiles = L.n_tiles; a.S = L.S; a.seed = seed;
-  a.out_rank = out_rank; a.out_rank_neg = out_rank_neg; a.out_n_eligible = out_n_eligible; a.out_n_neg = out_n_neg;
-  return vfm::launch_rank_eval(a, strategy, (unsigned)(L.U_pad / UT), st);
+    if (int rc = launch_rank_prep(L, r)) return rc;
+  return eval_after_scores(r, L, users);
 }
 
 }  // extern "C"

@@ -85,12 +85,21 @@ inline EvalTail eval_tail_of(int64_t ops_end, int S, int64_t U, int64_t n_pos) {
   return L;
 }
 
-// The tail's buffers of a workspace into the launch record
-inline void eval_tail_into(vfm::RankEval& a, char* ws, const EvalTail& L) {
-  a.raw = (const float*)(ws + L.off_raw); a.pusr = (const int64_t*)(ws + L.off_pusr);
-  a.pscore = (float*)(ws + L.off_pscore); a.pid = (int64_t*)(ws + L.off_pid); a.slot = (int64_t*)(ws + L.off_slot);
-  a.hist_all = (int*)(ws + L.off_ha); a.hist_neg = (int*)(ws + L.off_hn);
-  a.cnt_el = (int*)(ws + L.off_cel); a.cnt_pos = (int*)(ws + L.off_cpos);
+// The evaluation of a checked call once the positives' raw scores and query rows stand in the eval tail of its workspace:
+// the launch record from the call and its layout L (operand blocks and EvalTail), then vfm::launch_rank_eval.  keys [Q]:
+// the queries' Philox keys.
+template <class L>
+inline int eval_after_scores(const RankCall& r, const L& lay, const int64_t* keys) {
+  char* ws = (char*)r.workspace;
+  vfm::RankEval a;
+  fill_scan(a, r, lay, keys);
+  a.n_pos = r.n_pos; a.pos_ptr = r.pos_ptr; a.pos_items = r.pos_items;
+  a.raw = (const float*)(ws + lay.off_raw); a.pusr = (const int64_t*)(ws + lay.off_pusr);
+  a.pscore = (float*)(ws + lay.off_pscore); a.pid = (int64_t*)(ws + lay.off_pid); a.slot = (int64_t*)(ws + lay.off_slot);
+  a.hist_all = (int*)(ws + lay.off_ha); a.hist_neg = (int*)(ws + lay.off_hn);
+  a.cnt_el = (int*)(ws + lay.off_cel); a.cnt_pos = (int*)(ws + lay.off_cpos);
+  a.out_rank = r.out_rank; a.out_rank_neg = r.out_rank_neg; a.out_n_eligible = r.out_n_eligible; a.out_n_neg = r.out_n_neg;
+  return vfm::launch_rank_eval(a, r.strategy, (unsigned)(lay.U_pad / UT), r.stream);
 }
 
 inline bool eval_sizes_ok(int64_t U, int64_t n_cand, int64_t n_pos) {

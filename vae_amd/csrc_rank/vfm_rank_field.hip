@@ -280,199 +280,123 @@ FieldEvalLayout field_eval_layout_of(int64_t Q, int64_t n_cand, int64_t n_pos, i
 
 // k_field_ctx_prep and k_field_cand_prep into the operand blocks of L.  VFM_RANK_RANDOM: no tile runs, so the candidates
 // are never packed; the contexts only where their position keys are needed (ctx_rows false: the caller reads neither the
-// packed rows nor, with keys of its own, the position keys).  post: NULL for the table form, else the queries'
-// posterior rows of column post_field.
-int launch_field_prep(const FieldOps& L, char* ws, int64_t Q, const int64_t* ctx, int F, int field, const int64_t* qkey,
-                      int64_t n_cand, const int64_t* cand, int64_t cand_lo, int64_t T, int d, bool sp, int strategy,
-                      bool ctx_rows, const float* ent, const float* bias, const float* scal, int post_field,
-                      const float* post, hipStream_t st) {
-  if (ctx_rows || !qkey) {
+// packed rows nor, with keys of its own, the position keys).  The table form or, with r.has_post, the queries' posterior
+// rows of column r.post_field.
+int launch_field_prep(const FieldOps& L, const RankCall& r, bool ctx_rows) {
+  char* ws = (char*)r.workspace;
+  const bool sp = r.softplus();
+  if (ctx_rows || !r.qkey) {
     const dim3 grid((unsigned)((L.U_pad + PREP_BLOCK / WAVE - 1) / (PREP_BLOCK / WAVE)));
     float *uop = (float*)(ws + L.off_uop), *ucon = (float*)(ws + L.off_ucon);
-    int64_t* key_out = qkey ? (int64_t*)nullptr : (int64_t*)(ws + L.off_key);
-    if (post)
-      hipLaunchKernelGGL(k_field_ctx_prep<PostRows>, grid, dim3(PREP_BLOCK), 0, st, L.U_pad, Q, ctx, F, field, T, L.Kp,
-                         L.KA, L.KB, d, sp, PostRows{ent, bias, post, post_field, d}, scal, uop, ucon, key_out);
+    int64_t* key_out = r.qkey ? (int64_t*)nullptr : (int64_t*)(ws + L.off_key);
+    if (r.has_post)
+      hipLaunchKernelGGL(k_field_ctx_prep<PostRows>, grid, dim3(PREP_BLOCK), 0, r.stream, L.U_pad, r.Q, r.queries,
+                         (int)r.F, (int)r.field, r.T, L.Kp, L.KA, L.KB, (int)r.d, sp,
+                         PostRows{r.ent, r.bias, r.post, r.post_field, r.d}, r.scal, uop, ucon, key_out);
     else
-      hipLaunchKernelGGL(k_field_ctx_prep<TableRows>, grid, dim3(PREP_BLOCK), 0, st, L.U_pad, Q, ctx, F, field, T, L.Kp,
-                         L.KA, L.KB, d, sp, TableRows{ent, bias}, scal, uop, ucon, key_out);
+      hipLaunchKernelGGL(k_field_ctx_prep<TableRows>, grid, dim3(PREP_BLOCK), 0, r.stream, L.U_pad, r.Q, r.queries,
+                         (int)r.F, (int)r.field, r.T, L.Kp, L.KA, L.KB, (int)r.d, sp, TableRows{r.ent, r.bias}, r.scal,
+                         uop, ucon, key_out);
     if (int rc = launch_status("k_field_ctx_prep")) return rc;
   }
   const int64_t ni = L.C_pad * (L.Kp + 2);
-  if (strategy != VFM_RANK_RANDOM && ni > 0) {
-    hipLaunchKernelGGL(k_field_cand_prep, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, st, L.C_pad, n_cand, cand,
-                       cand_lo, T, L.Kp, L.KA, d, sp, ent, bias, (float*)(ws + L.off_iop), (float*)(ws + L.off_icon));
+  if (r.strategy != VFM_RANK_RANDOM && ni > 0) {
+    hipLaunchKernelGGL(k_field_cand_prep, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, r.stream, L.C_pad, r.n_cand,
+                       r.cand, r.cand_lo, r.T, L.Kp, L.KA, (int)r.d, sp, r.ent, r.bias, (float*)(ws + L.off_iop),
+                       (float*)(ws + L.off_icon));
     if (int rc = launch_status("k_field_cand_prep")) return rc;
   }
   return 0;
 }
 
-int check_fields(int32_t F, int32_t field) {
+// The field forms' own conditions: the ranked column and, for the posterior forms, the supplied one (a context column)
+int check_fields(int32_t F, int32_t field, bool has_post, int32_t post_field) {
   if (F < 2 || F > VFM_MAX_FIELDS) return vfm::fail(VFM_E_INVALID, "F out of range [2,64]");
   if (field < 0 || field >= F) return vfm::fail(VFM_E_INVALID, "field out of range [0,F)");
-  return 0;
-}
-
-// The posterior forms' own arguments: the supplied column is a context column
-int check_post_field(int32_t F, int32_t field, int32_t post_field) {
+  if (!has_post) return 0;
   if (post_field < 0 || post_field >= F) return vfm::fail(VFM_E_INVALID, "post_field out of range [0,F)");
   if (post_field == field)
     return vfm::fail(VFM_E_INVALID, "post_field must differ from field: the posterior is a context column's");
   return 0;
 }
 
+// One moments call as vfm_field_moments_f32 / vfm_field_moments_post_f32 received it
+struct MomentsCall {
+  int64_t B, T;
+  int32_t F, d, id_bits, flags, field, post_field, strategy;
+  bool has_post;
+  const void* x;
+  const float *post, *ent, *bias, *scal;
+  uint64_t seed;
+  const int64_t* qkey;
+  float *mean, *var, *score;
+  hipStream_t stream;
+};
+
 template <typename ID, typename SRC>
-void launch_field_moments(int64_t B, int F, int field, int d, int64_t T, bool sp, const void* x, SRC rows,
-                          const float* scal, int strategy, uint64_t seed, const int64_t* qkey, float* m, float* v,
-                          float* s, hipStream_t st) {
-  hipLaunchKernelGGL((k_field_moments<ID, SRC>), dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, B, F, field, d, T,
-                     sp, (const ID*)x, rows, scal, strategy, seed, qkey, m, v, s);
+void launch_field_moments(const MomentsCall& c, SRC rows) {
+  hipLaunchKernelGGL((k_field_moments<ID, SRC>), dim3((unsigned)((c.B + 255) / 256)), dim3(256), 0, c.stream, c.B,
+                     (int)c.F, (int)c.field, (int)c.d, c.T, (c.flags & VFM_FLAG_LINK_SOFTPLUS) != 0, (const ID*)c.x, rows,
+                     c.scal, (int)c.strategy, c.seed, c.qkey, c.mean, c.var, c.score);
 }
 
-// vfm_field_moments_f32 (has_post false) and vfm_field_moments_post_f32
-int field_moments_impl(int64_t B, int32_t F, int32_t d, int64_t T, int32_t id_bits, int32_t flags, const void* x,
-                       int32_t field, bool has_post, int32_t post_field, const float* post, const float* entity_params,
-                       const float* bias_params, const float* scalars, int32_t strategy, uint64_t seed,
-                       const int64_t* qkey, float* logit_mean, float* logit_var, float* score, void* stream) {
-  if (int rc = check_common(T, d, flags, strategy)) return rc;
-  if (int rc = check_fields(F, field)) return rc;
-  if (has_post)
-    if (int rc = check_post_field(F, field, post_field)) return rc;
-  if (B < 0) return vfm::fail(VFM_E_INVALID, "B < 0");
-  if (id_bits != 32 && id_bits != 64) return vfm::fail(VFM_E_INVALID, "id_bits must be 32 or 64");
-  if (B == 0) return 0;
-  if (!x || !entity_params || !bias_params || !scalars || !logit_mean || !logit_var)
-    return vfm::fail(VFM_E_INVALID, "null pointer");
-  if (has_post && !post) return vfm::fail(VFM_E_INVALID, "null pointer: post");
-  const hipStream_t st = (hipStream_t)stream;
-  const bool sp = (flags & VFM_FLAG_LINK_SOFTPLUS) != 0;
-  const TableRows tab{entity_params, bias_params};
-  const PostRows pst{entity_params, bias_params, post, post_field, d};
-  if (id_bits == 64) {
-    if (has_post)
-      launch_field_moments<int64_t>(B, F, field, d, T, sp, x, pst, scalars, strategy, seed, qkey, logit_mean, logit_var,
-                                    score, st);
-    else
-      launch_field_moments<int64_t>(B, F, field, d, T, sp, x, tab, scalars, strategy, seed, qkey, logit_mean, logit_var,
-                                    score, st);
+int field_moments_call(const MomentsCall& c) {
+  if (int rc = check_common(c.T, c.d, c.flags, c.strategy)) return rc;
+  if (int rc = check_fields(c.F, c.field, c.has_post, c.post_field)) return rc;
+  if (c.B < 0) return vfm::fail(VFM_E_INVALID, "B < 0");
+  if (c.id_bits != 32 && c.id_bits != 64) return vfm::fail(VFM_E_INVALID, "id_bits must be 32 or 64");
+  if (c.B == 0) return 0;
+  if (!c.x || !c.ent || !c.bias || !c.scal || !c.mean || !c.var) return vfm::fail(VFM_E_INVALID, "null pointer");
+  if (c.has_post && !c.post) return vfm::fail(VFM_E_INVALID, "null pointer: post");
+  const TableRows tab{c.ent, c.bias};
+  const PostRows pst{c.ent, c.bias, c.post, c.post_field, c.d};
+  if (c.id_bits == 64) {
+    if (c.has_post) launch_field_moments<int64_t>(c, pst);
+    else launch_field_moments<int64_t>(c, tab);
   } else {
-    if (has_post)
-      launch_field_moments<int32_t>(B, F, field, d, T, sp, x, pst, scalars, strategy, seed, qkey, logit_mean, logit_var,
-                                    score, st);
-    else
-      launch_field_moments<int32_t>(B, F, field, d, T, sp, x, tab, scalars, strategy, seed, qkey, logit_mean, logit_var,
-                                    score, st);
+    if (c.has_post) launch_field_moments<int32_t>(c, pst);
+    else launch_field_moments<int32_t>(c, tab);
   }
   return launch_status("k_field_moments");
 }
 
-// vfm_rank_field_f32 (has_post false) and vfm_rank_field_post_f32
-int rank_field_impl(int64_t Q, const int64_t* ctx, int32_t field, bool has_post, int32_t post_field, const float* post,
-                    const int64_t* qkey, int64_t n_cand, const int64_t* cand, int64_t cand_lo, int64_t T, int32_t F,
-                    int32_t d, int32_t k, int32_t strategy, int32_t flags, uint64_t seed, int32_t n_splits,
-                    const int64_t* excl_ptr, const int64_t* excl_items, int64_t n_excl, const float* entity_params,
-                    const float* bias_params, const float* scalars, void* workspace, int64_t workspace_bytes,
-                    int64_t* out_items, float* out_score, float* out_mean, float* out_var, void* stream) {
-  if (int rc = check_common(T, d, flags, strategy)) return rc;
-  if (int rc = check_fields(F, field)) return rc;
-  if (has_post)
-    if (int rc = check_post_field(F, field, post_field)) return rc;
-  if (k < 1 || k > VFM_RANK_MAX_K) return vfm::fail(VFM_E_INVALID, "k out of range [1,128]");
-  if (Q < 0) return vfm::fail(VFM_E_INVALID, "Q < 0");
-  if (n_cand < 0 || n_cand >= ((int64_t)1 << 31)) return vfm::fail(VFM_E_INVALID, "n_cand out of range [0,2^31)");
-  if (n_splits < 0 || n_splits > VFM_RANK_MAX_SPLITS) return vfm::fail(VFM_E_INVALID, "n_splits out of range [0,64]");
-  if (!cand && (cand_lo < 0 || cand_lo + n_cand > T)) return vfm::fail(VFM_E_INVALID, "candidate range outside [0,T)");
-  if (n_excl < 0 || (n_excl > 0 && (!excl_ptr || !excl_items)))
-    return vfm::fail(VFM_E_INVALID, "exclusion lists: excl_ptr and excl_items together, n_excl >= 0");
-  if (Q == 0) return 0;
-  if (!ctx || !entity_params || !bias_params || !scalars || !workspace || !out_items || !out_score || !out_mean ||
-      !out_var)
-    return vfm::fail(VFM_E_INVALID, "null pointer");
-  if (has_post && !post) return vfm::fail(VFM_E_INVALID, "null pointer: post");
-  const FieldLayout L = field_layout_of(Q, n_cand, d, k, strategy, n_splits);
-  if (workspace_bytes < L.bytes)
-    return vfm::fail(VFM_E_INVALID, "workspace too small (vfm_rank_field_workspace_bytes)");
-  if (((uintptr_t)workspace) & 255) return vfm::fail(VFM_E_INVALID, "workspace must be 256-byte aligned");
+// vfm_rank_field_f32 and vfm_rank_field_post_f32 (r.has_post)
+int rank_field_call(const RankCall& r) {
+  if (int rc = check_common(r.T, r.d, r.flags, r.strategy)) return rc;
+  if (int rc = check_fields(r.F, r.field, r.has_post, r.post_field)) return rc;
+  if (int rc = check_rank_call(r, RANK_ASK_TOPK | RANK_ASK_FIELD)) return rc;
+  if (r.Q == 0) return 0;
+  const FieldLayout L = field_layout_of(r.Q, r.n_cand, r.d, r.k, r.strategy, r.n_splits);
+  if (int rc = check_rank_workspace(r, L.bytes, "workspace too small (vfm_rank_field_workspace_bytes)")) return rc;
 
-  const hipStream_t st = (hipStream_t)stream;
-  const bool sp = (flags & VFM_FLAG_LINK_SOFTPLUS) != 0;
-  char* ws = (char*)workspace;
-  float *uop = (float*)(ws + L.off_uop), *iop = (float*)(ws + L.off_iop), *ucon = (float*)(ws + L.off_ucon),
-        *icon = (float*)(ws + L.off_icon);
-  int64_t* keys = (int64_t*)(ws + L.off_key);
-  if (int rc = launch_field_prep(L, ws, Q, ctx, F, field, qkey, n_cand, cand, cand_lo, T, d, sp, strategy, true,
-                                 entity_params, bias_params, scalars, post_field, has_post ? post : nullptr, st))
-    return rc;
-  vfm::RankScan a;
-  a.U = Q; a.n_cand = n_cand; a.item_lo = cand_lo; a.n_excl = excl_ptr ? n_excl : 0;
-  a.keys = qkey ? qkey : keys; a.cand = cand; a.excl_ptr = excl_ptr; a.excl_items = excl_items;
-  a.uop = uop; a.iop = iop; a.ucon = ucon; a.icon = icon;
-  a.Kp = L.Kp; a.KA = L.KA; a.KB = L.KB;
-  a.ls = (float*)(ws + L.off_ls); a.lc = (int*)(ws + L.off_lc);
-  a.k = k; a.n_tiles = L.n_tiles; a.S = L.S; a.seed = seed;
-  if (int rc = vfm::launch_rank_scan(a, strategy, (unsigned)(L.U_pad / UT), st)) return rc;
-  hipLaunchKernelGGL(k_rank_merge<FieldMoments>, dim3((unsigned)Q), dim3(MERGE_BLOCK), 0, st, Q, k, L.S, a.ls, a.lc, cand,
-                     cand_lo, FieldMoments{uop, ucon, L.Kp, L.KA, T, d, sp, entity_params, bias_params}, out_items,
-                     out_score, out_mean, out_var);
-  return launch_status("k_rank_merge");
+  const char* ws = (const char*)r.workspace;
+  if (int rc = launch_field_prep(L, r, true)) return rc;
+  return scan_and_merge(r, L, r.qkey ? r.qkey : (const int64_t*)(ws + L.off_key),
+                        FieldMoments{(const float*)(ws + L.off_uop), (const float*)(ws + L.off_ucon), L.Kp, L.KA, r.T, r.d,
+                                     r.softplus(), r.ent, r.bias});
 }
 
-// vfm_rank_heldout_field_f32 (has_post false) and vfm_rank_heldout_field_post_f32
-int rank_heldout_field_impl(int64_t Q, const int64_t* ctx, int32_t field, bool has_post, int32_t post_field,
-                            const float* post, const int64_t* qkey, int64_t n_cand, const int64_t* cand, int64_t cand_lo,
-                            int64_t T, int32_t F, int32_t d, int32_t strategy, int32_t flags, uint64_t seed,
-                            int32_t n_splits, const int64_t* excl_ptr, const int64_t* excl_items, int64_t n_excl,
-                            const int64_t* pos_ptr, const int64_t* pos_items, int64_t n_pos, const float* entity_params,
-                            const float* bias_params, const float* scalars, void* workspace, int64_t workspace_bytes,
-                            int64_t* out_rank, int64_t* out_rank_neg, int64_t* out_n_eligible, int64_t* out_n_neg,
-                            void* stream) {
-  if (int rc = check_common(T, d, flags, strategy)) return rc;
-  if (int rc = check_fields(F, field)) return rc;
-  if (has_post)
-    if (int rc = check_post_field(F, field, post_field)) return rc;
-  if (Q < 0) return vfm::fail(VFM_E_INVALID, "Q < 0");
-  if (n_cand < 0 || n_cand >= ((int64_t)1 << 31)) return vfm::fail(VFM_E_INVALID, "n_cand out of range [0,2^31)");
-  if (n_pos < 0 || n_pos >= ((int64_t)1 << 40)) return vfm::fail(VFM_E_INVALID, "n_pos out of range [0,2^40)");
-  if (n_splits < 0 || n_splits > VFM_RANK_MAX_SPLITS) return vfm::fail(VFM_E_INVALID, "n_splits out of range [0,64]");
-  if (!cand && (cand_lo < 0 || cand_lo + n_cand > T)) return vfm::fail(VFM_E_INVALID, "candidate range outside [0,T)");
-  if (n_excl < 0 || (n_excl > 0 && (!excl_ptr || !excl_items)))
-    return vfm::fail(VFM_E_INVALID, "exclusion lists: excl_ptr and excl_items together, n_excl >= 0");
-  if (n_pos > 0 && !pos_items) return vfm::fail(VFM_E_INVALID, "null pointer: pos_items");
-  if (Q == 0) return 0;
-  if (!ctx || !pos_ptr || !entity_params || !bias_params || !scalars || !workspace || !out_n_eligible || !out_n_neg ||
-      (n_pos > 0 && (!out_rank || !out_rank_neg)))
-    return vfm::fail(VFM_E_INVALID, "null pointer");
-  if (has_post && !post) return vfm::fail(VFM_E_INVALID, "null pointer: post");
-  const FieldEvalLayout L = field_eval_layout_of(Q, n_cand, n_pos, d, strategy, n_splits);
-  if (workspace_bytes < L.bytes)
-    return vfm::fail(VFM_E_INVALID, "workspace too small (vfm_rank_eval_field_workspace_bytes)");
-  if (((uintptr_t)workspace) & 255) return vfm::fail(VFM_E_INVALID, "workspace must be 256-byte aligned");
+// vfm_rank_heldout_field_f32 and vfm_rank_heldout_field_post_f32 (r.has_post)
+int rank_heldout_field_call(const RankCall& r) {
+  if (int rc = check_common(r.T, r.d, r.flags, r.strategy)) return rc;
+  if (int rc = check_fields(r.F, r.field, r.has_post, r.post_field)) return rc;
+  if (int rc = check_rank_call(r, RANK_ASK_HELDOUT | RANK_ASK_FIELD)) return rc;
+  if (r.Q == 0) return 0;
+  const FieldEvalLayout L = field_eval_layout_of(r.Q, r.n_cand, r.n_pos, r.d, r.strategy, r.n_splits);
+  if (int rc = check_rank_workspace(r, L.bytes, "workspace too small (vfm_rank_eval_field_workspace_bytes)")) return rc;
 
-  const hipStream_t st = (hipStream_t)stream;
-  const bool sp = (flags & VFM_FLAG_LINK_SOFTPLUS) != 0;
-  char* ws = (char*)workspace;
-  if (int rc = launch_field_prep(L, ws, Q, ctx, F, field, qkey, n_cand, cand, cand_lo, T, d, sp, strategy,
-                                 strategy != VFM_RANK_RANDOM, entity_params, bias_params, scalars, post_field,
-                                 has_post ? post : nullptr, st))
-    return rc;
-  vfm::RankEval a;
-  a.U = Q; a.n_cand = n_cand; a.item_lo = cand_lo; a.n_excl = excl_ptr ? n_excl : 0; a.n_pos = n_pos;
-  a.keys = qkey ? qkey : (const int64_t*)(ws + L.off_key); a.cand = cand; a.excl_ptr = excl_ptr;
-  a.excl_items = excl_items; a.pos_ptr = pos_ptr; a.pos_items = pos_items;
-  a.uop = (const float*)(ws + L.off_uop); a.iop = (const float*)(ws + L.off_iop);
-  a.ucon = (const float*)(ws + L.off_ucon); a.icon = (const float*)(ws + L.off_icon);
-  a.Kp = L.Kp; a.KA = L.KA; a.KB = L.KB;
-  eval_tail_into(a, ws, L);
-  a.n_tiles = L.n_tiles; a.S = L.S; a.seed = seed;
-  a.out_rank = out_rank; a.out_rank_neg = out_rank_neg; a.out_n_eligible = out_n_eligible; a.out_n_neg = out_n_neg;
-  if (n_pos > 0) {
-    hipLaunchKernelGGL(k_field_pos_score, dim3((unsigned)((n_pos + POS_BLOCK - 1) / POS_BLOCK)), dim3(POS_BLOCK), 0, st,
-                       Q, n_pos, ctx, (int)F, (int)field, a.keys, pos_ptr, pos_items, T, (int)d, sp, (int)strategy, seed,
-                       a.uop, a.ucon, L.Kp, L.KA, entity_params, bias_params, (float*)(ws + L.off_raw),
+  char* ws = (char*)r.workspace;
+  if (int rc = launch_field_prep(L, r, r.strategy != VFM_RANK_RANDOM)) return rc;
+  const int64_t* keys = r.qkey ? r.qkey : (const int64_t*)(ws + L.off_key);
+  if (r.n_pos > 0) {
+    hipLaunchKernelGGL(k_field_pos_score, dim3((unsigned)((r.n_pos + POS_BLOCK - 1) / POS_BLOCK)), dim3(POS_BLOCK), 0,
+                       r.stream, r.Q, r.n_pos, r.queries, (int)r.F, (int)r.field, keys, r.pos_ptr, r.pos_items, r.T,
+                       (int)r.d, r.softplus(), (int)r.strategy, r.seed, (const float*)(ws + L.off_uop),
+                       (const float*)(ws + L.off_ucon), L.Kp, L.KA, r.ent, r.bias, (float*)(ws + L.off_raw),
                        (int64_t*)(ws + L.off_pusr));
     if (int rc = launch_status("k_field_pos_score")) return rc;
   }
-  return vfm::launch_rank_eval(a, strategy, (unsigned)(L.U_pad / UT), st);
+  return eval_after_scores(r, L, keys);
 }
 
 }  // namespace
@@ -483,16 +407,18 @@ int vfm_field_moments_f32(int64_t B, int32_t F, int32_t d, int64_t T, int32_t id
                           int32_t field, const float* entity_params, const float* bias_params, const float* scalars,
                           int32_t strategy, uint64_t seed, const int64_t* qkey, float* logit_mean, float* logit_var,
                           float* score, void* stream) {
-  return field_moments_impl(B, F, d, T, id_bits, flags, x, field, false, -1, nullptr, entity_params, bias_params,
-                            scalars, strategy, seed, qkey, logit_mean, logit_var, score, stream);
+  return field_moments_call(MomentsCall{B, T, F, d, id_bits, flags, field, -1, strategy, false, x, nullptr,
+                                        entity_params, bias_params, scalars, seed, qkey, logit_mean, logit_var, score,
+                                        (hipStream_t)stream});
 }
 
 int vfm_field_moments_post_f32(int64_t B, int32_t F, int32_t d, int64_t T, int32_t id_bits, int32_t flags, const void* x,
                                int32_t field, int32_t post_field, const float* post, const float* entity_params,
                                const float* bias_params, const float* scalars, int32_t strategy, uint64_t seed,
                                const int64_t* qkey, float* logit_mean, float* logit_var, float* score, void* stream) {
-  return field_moments_impl(B, F, d, T, id_bits, flags, x, field, true, post_field, post, entity_params, bias_params,
-                            scalars, strategy, seed, qkey, logit_mean, logit_var, score, stream);
+  return field_moments_call(MomentsCall{B, T, F, d, id_bits, flags, field, post_field, strategy, true, x, post,
+                                        entity_params, bias_params, scalars, seed, qkey, logit_mean, logit_var, score,
+                                        (hipStream_t)stream});
 }
 
 int64_t vfm_rank_field_workspace_bytes(int64_t Q, int64_t n_cand, int32_t F, int32_t d, int32_t k, int32_t strategy,
@@ -504,17 +430,6 @@ int64_t vfm_rank_field_workspace_bytes(int64_t Q, int64_t n_cand, int32_t F, int
   return field_layout_of(Q, n_cand, d, k, strategy, n_splits).bytes;
 }
 
-int vfm_rank_field_f32(int64_t Q, const int64_t* ctx, int32_t field, const int64_t* qkey, int64_t n_cand,
-                       const int64_t* cand, int64_t cand_lo, int64_t T, int32_t F, int32_t d, int32_t k,
-                       int32_t strategy, int32_t flags, uint64_t seed, int32_t n_splits, const int64_t* excl_ptr,
-                       const int64_t* excl_items, int64_t n_excl, const float* entity_params, const float* bias_params,
-                       const float* scalars, void* workspace, int64_t workspace_bytes, int64_t* out_items,
-                       float* out_score, float* out_mean, float* out_var, void* stream) {
-  return rank_field_impl(Q, ctx, field, false, -1, nullptr, qkey, n_cand, cand, cand_lo, T, F, d, k, strategy, flags,
-                         seed, n_splits, excl_ptr, excl_items, n_excl, entity_params, bias_params, scalars, workspace,
-                         workspace_bytes, out_items, out_score, out_mean, out_var, stream);
-}
-
 int vfm_rank_field_post_f32(int64_t Q, const int64_t* ctx, int32_t field, int32_t post_field, const float* post,
                             const int64_t* qkey, int64_t n_cand, const int64_t* cand, int64_t cand_lo, int64_t T,
                             int32_t F, int32_t d, int32_t k, int32_t strategy, int32_t flags, uint64_t seed,
@@ -522,9 +437,35 @@ int vfm_rank_field_post_f32(int64_t Q, const int64_t* ctx, int32_t field, int32_
                             const float* entity_params, const float* bias_params, const float* scalars, void* workspace,
                             int64_t workspace_bytes, int64_t* out_items, float* out_score, float* out_mean,
                             float* out_var, void* stream) {
-  return rank_field_impl(Q, ctx, field, true, post_field, post, qkey, n_cand, cand, cand_lo, T, F, d, k, strategy, flags,
-                         seed, n_splits, excl_ptr, excl_items, n_excl, entity_params, bias_params, scalars, workspace,
-                         workspace_bytes, out_items, out_score, out_mean, out_var, stream);
+  RankCall r;
+  r.Q = Q; r.queries = ctx; r.qkey = qkey; r.field = field;
+  r.has_post = true; r.post_field = post_field; r.post = post;
+  r.n_cand = n_cand; r.cand = cand; r.cand_lo = cand_lo;
+  r.excl_ptr = excl_ptr; r.excl_items = excl_items; r.n_excl = n_excl;
+  r.T = T; r.F = F; r.d = d; r.ent = entity_params; r.bias = bias_params; r.scal = scalars;
+  r.workspace = workspace; r.workspace_bytes = workspace_bytes;
+  r.k = k; r.strategy = strategy; r.flags = flags; r.n_splits = n_splits; r.seed = seed;
+  r.out_items = out_items; r.out_score = out_score; r.out_mean = out_mean; r.out_var = out_var;
+  r.stream = (hipStream_t)stream;
+  return rank_field_call(r);
+}
+
+int vfm_rank_field_f32(int64_t Q, const int64_t* ctx, int32_t field, const int64_t* qkey, int64_t n_cand,
+                       const int64_t* cand, int64_t cand_lo, int64_t T, int32_t F, int32_t d, int32_t k,
+                       int32_t strategy, int32_t flags, uint64_t seed, int32_t n_splits, const int64_t* excl_ptr,
+                       const int64_t* excl_items, int64_t n_excl, const float* entity_params, const float* bias_params,
+                       const float* scalars, void* workspace, int64_t workspace_bytes, int64_t* out_items,
+                       float* out_score, float* out_mean, float* out_var, void* stream) {
+  RankCall r;
+  r.Q = Q; r.queries = ctx; r.qkey = qkey; r.field = field;
+  r.n_cand = n_cand; r.cand = cand; r.cand_lo = cand_lo;
+  r.excl_ptr = excl_ptr; r.excl_items = excl_items; r.n_excl = n_excl;
+  r.T = T; r.F = F; r.d = d; r.ent = entity_params; r.bias = bias_params; r.scal = scalars;
+  r.workspace = workspace; r.workspace_bytes = workspace_bytes;
+  r.k = k; r.strategy = strategy; r.flags = flags; r.n_splits = n_splits; r.seed = seed;
+  r.out_items = out_items; r.out_score = out_score; r.out_mean = out_mean; r.out_var = out_var;
+  r.stream = (hipStream_t)stream;
+  return rank_field_call(r);
 }
 
 int64_t vfm_rank_eval_field_workspace_bytes(int64_t Q, int64_t n_cand, int64_t n_pos, int32_t F, int32_t d,
@@ -535,20 +476,6 @@ int64_t vfm_rank_eval_field_workspace_bytes(int64_t Q, int64_t n_cand, int64_t n
   return field_eval_layout_of(Q, n_cand, n_pos, d, strategy, n_splits).bytes;
 }
 
-int vfm_rank_heldout_field_f32(int64_t Q, const int64_t* ctx, int32_t field, const int64_t* qkey, int64_t n_cand,
-                               const int64_t* cand, int64_t cand_lo, int64_t T, int32_t F, int32_t d, int32_t strategy,
-                               int32_t flags, uint64_t seed, int32_t n_splits, const int64_t* excl_ptr,
-                               const int64_t* excl_items, int64_t n_excl, const int64_t* pos_ptr,
-                               const int64_t* pos_items, int64_t n_pos, const float* entity_params,
-                               const float* bias_params, const float* scalars, void* workspace, int64_t workspace_bytes,
-                               int64_t* out_rank, int64_t* out_rank_neg, int64_t* out_n_eligible, int64_t* out_n_neg,
-                               void* stream) {
-  return rank_heldout_field_impl(Q, ctx, field, false, -1, nullptr, qkey, n_cand, cand, cand_lo, T, F, d, strategy,
-                                 flags, seed, n_splits, excl_ptr, excl_items, n_excl, pos_ptr, pos_items, n_pos,
-                                 entity_params, bias_params, scalars, workspace, workspace_bytes, out_rank, out_rank_neg,
-                                 out_n_eligible, out_n_neg, stream);
-}
-
 int vfm_rank_heldout_field_post_f32(int64_t Q, const int64_t* ctx, int32_t field, int32_t post_field, const float* post,
                                     const int64_t* qkey, int64_t n_cand, const int64_t* cand, int64_t cand_lo, int64_t T,
                                     int32_t F, int32_t d, int32_t strategy, int32_t flags, uint64_t seed,
@@ -557,10 +484,39 @@ int vfm_rank_heldout_field_post_f32(int64_t Q, const int64_t* ctx, int32_t field
                                     const float* entity_params, const float* bias_params, const float* scalars,
                                     void* workspace, int64_t workspace_bytes, int64_t* out_rank, int64_t* out_rank_neg,
                                     int64_t* out_n_eligible, int64_t* out_n_neg, void* stream) {
-  return rank_heldout_field_impl(Q, ctx, field, true, post_field, post, qkey, n_cand, cand, cand_lo, T, F, d, strategy,
-                                 flags, seed, n_splits, excl_ptr, excl_items, n_excl, pos_ptr, pos_items, n_pos,
-                                 entity_params, bias_params, scalars, workspace, workspace_bytes, out_rank, out_rank_neg,
-                                 out_n_eligible, out_n_neg, stream);
+  RankCall r;
+  r.Q = Q; r.queries = ctx; r.qkey = qkey; r.field = field;
+  r.has_post = true; r.post_field = post_field; r.post = post;
+  r.n_cand = n_cand; r.cand = cand; r.cand_lo = cand_lo;
+  r.excl_ptr = excl_ptr; r.excl_items = excl_items; r.n_excl = n_excl;
+  r.pos_ptr = pos_ptr; r.pos_items = pos_items; r.n_pos = n_pos;
+  r.T = T; r.F = F; r.d = d; r.ent = entity_params; r.bias = bias_params; r.scal = scalars;
+  r.workspace = workspace; r.workspace_bytes = workspace_bytes;
+  r.strategy = strategy; r.flags = flags; r.n_splits = n_splits; r.seed = seed;
+  r.out_rank = out_rank; r.out_rank_neg = out_rank_neg; r.out_n_eligible = out_n_eligible; r.out_n_neg = out_n_neg;
+  r.stream = (hipStream_t)stream;
+  return rank_heldout_field_call(r);
+}
+
+int vfm_rank_heldout_field_f32(int64_t Q, const int64_t* ctx, int32_t field, const int64_t* qkey, int64_t n_cand,
+                               const int64_t* cand, int64_t cand_lo, int64_t T, int32_t F, int32_t d, int32_t strategy,
+                               int32_t flags, uint64_t seed, int32_t n_splits, const int64_t* excl_ptr,
+                               const int64_t* excl_items, int64_t n_excl, const int64_t* pos_ptr,
+                               const int64_t* pos_items, int64_t n_pos, const float* entity_params,
+                               const float* bias_params, const float* scalars, void* workspace, int64_t workspace_bytes,
+                               int64_t* out_rank, int64_t* out_rank_neg, int64_t* out_n_eligible, int64_t* out_n_neg,
+                               void* stream) {
+  RankCall r;
+  r.Q = Q; r.queries = ctx; r.qkey = qkey; r.field = field;
+  r.n_cand = n_cand; r.cand = cand; r.cand_lo = cand_lo;
+  r.excl_ptr = excl_ptr; r.excl_items = excl_items; r.n_excl = n_excl;
+  r.pos_ptr = pos_ptr; r.pos_items = pos_items; r.n_pos = n_pos;
+  r.T = T; r.F = F; r.d = d; r.ent = entity_params; r.bias = bias_params; r.scal = scalars;
+  r.workspace = workspace; r.workspace_bytes = workspace_bytes;
+  r.strategy = strategy; r.flags = flags; r.n_splits = n_splits; r.seed = seed;
+  r.out_rank = out_rank; r.out_rank_neg = out_rank_neg; r.out_n_eligible = out_n_eligible; r.out_n_neg = out_n_neg;
+  r.stream = (hipStream_t)stream;
+  return rank_heldout_field_call(r);
 }
 
 }  // extern "C"

@@ -96,4 +96,20 @@ inline ListLayout list_layout_of(int64_t ops_end, int S, int64_t U, int k) {
   return L;
 }
 
+// The scan of a checked call over the operand blocks of its workspace, then the merge of the split lists into the call's
+// outputs.  L: the workspace's layout (operand blocks and ListLayout); keys [Q]: the queries' Philox keys; pm: the
+// winners' moments (k_rank_merge).
+template <class L, class PM>
+inline int scan_and_merge(const RankCall& r, const L& lay, const int64_t* keys, const PM& pm) {
+  char* ws = (char*)r.workspace;
+  vfm::RankScan a;
+  fill_scan(a, r, lay, keys);
+  a.ls = (float*)(ws + lay.off_ls); a.lc = (int*)(ws + lay.off_lc);
+  a.k = r.k;
+  if (int rc = vfm::launch_rank_scan(a, r.strategy, (unsigned)(lay.U_pad / UT), r.stream)) return rc;
+  hipLaunchKernelGGL(k_rank_merge<PM>, dim3((unsigned)r.Q), dim3(MERGE_BLOCK), 0, r.stream, r.Q, (int)r.k, lay.S, a.ls,
+                     a.lc, r.cand, r.cand_lo, pm, r.out_items, r.out_score, r.out_mean, r.out_var);
+  return launch_status("k_rank_merge");
+}
+
 }  // namespace

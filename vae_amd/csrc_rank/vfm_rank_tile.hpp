@@ -221,7 +221,8 @@ __device__ __forceinline__ void score_tile(const TileOps& o, TileSmem& sm, float
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// host side: the packed-operand part of a workspace, the split count, the argument checks both units share
+// host side: the packed-operand part of a workspace, the split count, and the call record (RankCall) with the argument
+// checks and the launch-record fill that every ranking entry shares
 // ---------------------------------------------------------------------------------------------------------------------
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
@@ -266,16 +267,97 @@ inline int check_common(int64_t T, int32_t d, int32_t flags, int32_t strategy) {
   return 0;
 }
 
+// One ranking call as its extern "C" entry received it (host only; never a kernel argument).  The six ranking entries
+// fill it and hand it on: the checks, the preps and the launch records read it instead of thirty positional arguments.
+struct RankCall {
+  int64_t Q = 0;                                            // the queries:
+  const int64_t* queries = nullptr;                         //   users [Q] (pair forms) or contexts [Q, F] (field forms)
+  const int64_t* qkey = nullptr;                            //   field forms: the caller's Philox keys [Q], or NULL
+  int32_t field = 0, post_field = -1;                       //   field forms: the ranked column; the supplied column
+  bool has_post = false;
+  const float* post = nullptr;                              //   [Q, 2d + 2] when has_post
+  int64_t n_cand = 0, cand_lo = 0;                          // the candidates: cand [n_cand], or the range from cand_lo
+  const int64_t* cand = nullptr;
+  const int64_t *excl_ptr = nullptr, *excl_items = nullptr; // the exclusion CSR over the queries
+  int64_t n_excl = 0;
+  const int64_t *pos_ptr = nullptr, *pos_items = nullptr;   // held-out forms: the positives CSR over the queries
+  int64_t n_pos = 0;
+  int64_t T = 0;                                            // the tables
+  int32_t F = 0, d = 0;
+  const float *ent = nullptr, *bias = nullptr, *scal = nullptr;
+  void* workspace = nullptr;
+  int64_t workspace_bytes = 0;
+  int32_t k = 0, strategy = 0, flags = 0, n_splits = 0;     // k: top-k forms
+  uint64_t seed = 0;
+  int64_t* out_items = nullptr;                             // top-k forms: [Q, k] each
+  float *out_score = nullptr, *out_mean = nullptr, *out_var = nullptr;
+  int64_t *out_rank = nullptr, *out_rank_neg = nullptr;     // held-out forms: [n_pos] each
+  int64_t *out_n_eligible = nullptr, *out_n_neg = nullptr;  //   and [Q] each
+  hipStream_t stream = nullptr;
+
+  bool softplus() const { return (flags & VFM_FLAG_LINK_SOFTPLUS) != 0; }
+  int64_t n_excl_used() const { return excl_ptr ? n_excl : 0; }
+};
+
+// What an entry asks of a call
+enum RankAsk { RANK_ASK_TOPK = 0, RANK_ASK_HELDOUT = 1, RANK_ASK_FIELD = 2 };      // (FIELD: or-ed in by the field forms)
+
+// The checks every ranking entry makes after check_common and its own conditions on F and the fields.  Q == 0 passes
+// before any pointer is looked at: the caller returns 0 then.
+inline int check_rank_call(const RankCall& r, int ask) {
+  const bool heldout = (ask & RANK_ASK_HELDOUT) != 0, fieldf = (ask & RANK_ASK_FIELD) != 0;
+  if (!heldout && (r.k < 1 || r.k > VFM_RANK_MAX_K)) return vfm::fail(VFM_E_INVALID, "k out of range [1,128]");
+  if (r.Q < 0) return vfm::fail(VFM_E_INVALID, fieldf ? "Q < 0" : "U < 0");
+  if (r.n_cand < 0 || r.n_cand >= ((int64_t)1 << 31)) return vfm::fail(VFM_E_INVALID, "n_cand out of range [0,2^31)");
+  if (heldout && (r.n_pos < 0 || r.n_pos >= ((int64_t)1 << 40)))
+    return vfm::fail(VFM_E_INVALID, "n_pos out of range [0,2^40)");
+  if (r.n_splits < 0 || r.n_splits > VFM_RANK_MAX_SPLITS) return vfm::fail(VFM_E_INVALID, "n_splits out of range [0,64]");
+  if (!r.cand && (r.cand_lo < 0 || r.cand_lo + r.n_cand > r.T))
+    return vfm::fail(VFM_E_INVALID, fieldf ? "candidate range outside [0,T)" : "item range outside [0,T)");
+  if (r.n_excl < 0 || (r.n_excl > 0 && (!r.excl_ptr || !r.excl_items)))
+    return vfm::fail(VFM_E_INVALID, "exclusion lists: excl_ptr and excl_items together, n_excl >= 0");
+  if (heldout && r.n_pos > 0 && !r.pos_items) return vfm::fail(VFM_E_INVALID, "null pointer: pos_items");
+  if (r.Q == 0) return 0;
+  if (!r.queries || !r.ent || !r.bias || !r.scal || !r.workspace) return vfm::fail(VFM_E_INVALID, "null pointer");
+  if (heldout ? (!r.pos_ptr || !r.out_n_eligible || !r.out_n_neg || (r.n_pos > 0 && (!r.out_rank || !r.out_rank_neg)))
+              : (!r.out_items || !r.out_score || !r.out_mean || !r.out_var))
+    return vfm::fail(VFM_E_INVALID, "null pointer");
+  if (r.has_post && !r.post) return vfm::fail(VFM_E_INVALID, "null pointer: post");
+  return 0;
+}
+
+// The workspace of a checked call against the bytes its layout needs (too_small: the message, which names the entry
+// point that tells the size)
+inline int check_rank_workspace(const RankCall& r, int64_t bytes, const char* too_small) {
+  if (r.workspace_bytes < bytes) return vfm::fail(VFM_E_INVALID, too_small);
+  if (((uintptr_t)r.workspace) & 255) return vfm::fail(VFM_E_INVALID, "workspace must be 256-byte aligned");
+  return 0;
+}
+
+// What a scan record (vfm::RankScan) and an evaluation record (vfm::RankEval) name alike, from the call and the operand
+// blocks of its workspace (L: OpLayout, or the field form's layout with the same members)
+template <class R, class L>
+inline void fill_scan(R& a, const RankCall& r, const L& lay, const int64_t* keys) {
+  const char* ws = (const char*)r.workspace;
+  a.U = r.Q; a.n_cand = r.n_cand; a.item_lo = r.cand_lo; a.n_excl = r.n_excl_used();
+  a.keys = keys; a.cand = r.cand; a.excl_ptr = r.excl_ptr; a.excl_items = r.excl_items;
+  a.uop = (const float*)(ws + lay.off_uop); a.iop = (const float*)(ws + lay.off_iop);
+  a.ucon = (const float*)(ws + lay.off_ucon); a.icon = (const float*)(ws + lay.off_icon);
+  a.Kp = lay.Kp; a.KA = lay.KA; a.KB = lay.KB;
+  a.n_tiles = lay.n_tiles; a.S = lay.S; a.seed = r.seed;
+}
+
 // k_rank_prep over the query users and the candidates into the operand blocks of L (not for VFM_RANK_RANDOM)
-inline int launch_rank_prep(const OpLayout& L, char* ws, int64_t U, const int64_t* users, int64_t n_cand,
-                            const int64_t* cand, int64_t item_lo, int64_t T, int d, bool sp, const float* ent,
-                            const float* bias, const float* scal, hipStream_t st) {
+inline int launch_rank_prep(const OpLayout& L, const RankCall& r) {
+  char* ws = (char*)r.workspace;
+  const bool sp = r.softplus();
   const int64_t nu = L.U_pad * (L.Kp + 2), ni = L.C_pad * (L.Kp + 2);
-  hipLaunchKernelGGL(k_rank_prep, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, st, L.U_pad, U, users, (int64_t)0,
-                     T, L.Kp, L.KA, d, false, sp, ent, bias, scal, (float*)(ws + L.off_uop), (float*)(ws + L.off_ucon));
+  hipLaunchKernelGGL(k_rank_prep, dim3((unsigned)((nu + 255) / 256)), dim3(256), 0, r.stream, L.U_pad, r.Q, r.queries,
+                     (int64_t)0, r.T, L.Kp, L.KA, (int)r.d, false, sp, r.ent, r.bias, r.scal, (float*)(ws + L.off_uop),
+                     (float*)(ws + L.off_ucon));
   if (ni > 0)
-    hipLaunchKernelGGL(k_rank_prep, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, st, L.C_pad, n_cand, cand,
-                       item_lo, T, L.Kp, L.KA, d, true, sp, ent, bias, scal, (float*)(ws + L.off_iop),
+    hipLaunchKernelGGL(k_rank_prep, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, r.stream, L.C_pad, r.n_cand, r.cand,
+                       r.cand_lo, r.T, L.Kp, L.KA, (int)r.d, true, sp, r.ent, r.bias, r.scal, (float*)(ws + L.off_iop),
                        (float*)(ws + L.off_icon));
   return launch_status("k_rank_prep");
 }

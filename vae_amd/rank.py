@@ -31,16 +31,40 @@ def strategy_code(strategy: str) -> int:
     return STRATEGIES[strategy]
 
 
+def _link_flags(link: str) -> int:
+    return ops.FLAG_LINK_SOFTPLUS if link == "softplus" else 0
+
+
+def flags_of(model) -> int:
+    """The `flags` argument of every ranking op for this model."""
+    return _link_flags(model.link)
+
+
+def _score_args(model, strategy, k=None, n_splits=None, optional=False) -> int:
+    """The one check of (strategy, k, n_splits) against the model; returns the strategy's code.  k, n_splits None: the
+    form has no such argument; optional: strategy None asks for no score (code 0)."""
+    code = 0 if optional and strategy is None else strategy_code(strategy)
+    if strategy == "mean" and model.output != "class":
+        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
+    if k is not None and not 1 <= int(k) <= MAX_K:
+        raise ValueError(f"k must lie in [1, {MAX_K}]")
+    if n_splits is not None and not 0 <= int(n_splits) <= MAX_SPLITS:
+        raise ValueError(f"n_splits must lie in [0, {MAX_SPLITS}]")
+    return code
+
+
+def _moment_outputs(x, scored: bool):
+    m = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    return m, torch.empty_like(m), torch.empty_like(m) if scored else None
+
+
 def predictive_moments(x, ent, bia, scal, link: str = "abs", strategy: Optional[str] = None, seed: int = 0):
     """(logit_mean [B], logit_var [B], score [B] or None) of the rows x [B, F] under the mean-field posterior."""
     ops._need_cuda(x, "x")
     x = x if x.dtype in (torch.int32, torch.int64) else x.to(torch.int64)
-    B = x.shape[0]
-    m = torch.empty(B, dtype=torch.float32, device=x.device)
-    v = torch.empty_like(m)
-    sc = torch.empty_like(m) if strategy is not None else None
-    _lib.ops().predictive_moments(x.contiguous(), ent, bia, scal, m, v, sc, ops.FLAG_LINK_SOFTPLUS if link == "softplus"
-                                  else 0, strategy_code(strategy) if strategy is not None else 0, _seed64(seed))
+    m, v, sc = _moment_outputs(x, strategy is not None)
+    _lib.ops().predictive_moments(x.contiguous(), ent, bia, scal, m, v, sc, _link_flags(link),
+                                  strategy_code(strategy) if strategy is not None else 0, _seed64(seed))
     return m, v, sc
 
 
@@ -60,58 +84,169 @@ def exclusion_csr(users: torch.Tensor, exclude: torch.Tensor, T: int):
     return ptr, (key - qk * T).contiguous()
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# the preparation and launch path every ranking form shares: the candidates, the positives' eligibility, the two
+# launchers.  A form is named by the leading arguments of its ops (`_pair_head`, `_field_head`).
+# ---------------------------------------------------------------------------------------------------------------------
+_ITEM_WORDS = ("item ids must lie in", "duplicate candidate items")
+_FIELD_WORDS = ("candidate ids must lie in the field's range", "duplicate candidates")
+
+
+def _candidates(values, lo: int, hi: int, dev, words=_FIELD_WORDS):
+    """(cand sorted int64 or None, n_cand) of a candidates argument over the id range [lo, hi); None: the whole range.
+    words: the wording of the range error and of the duplicate error."""
+    if values is None:
+        return None, hi - lo
+    cand = torch.as_tensor(values).to(dev, torch.int64).reshape(-1)
+    if cand.numel() and (int(cand.min()) < lo or int(cand.max()) >= hi):
+        raise ValueError(f"{words[0]} [{lo}, {hi})")
+    cand = torch.sort(cand).values
+    if cand.numel() > 1 and bool((cand[1:] == cand[:-1]).any()):
+        raise ValueError(words[1])
+    return cand, cand.numel()
+
+
+def _ineligible(pitems, pq, cand, eptr, ex_items, Q: int, T: int):
+    """bad [n_pos] bool: positive j (id pitems[j] of query pq[j]) is no eligible candidate of its query -- outside `cand`
+    (sorted; None: every id is a candidate) or in the query's list of the exclusion CSR (eptr [Q+1], ex_items; None:
+    nothing excluded).  The queries are the users of the pair form, the contexts of the field form."""
+    dev = pitems.device
+    bad = torch.zeros(pitems.numel(), dtype=torch.bool, device=dev)
+    if cand is not None:
+        j = torch.searchsorted(cand, pitems).clamp_(max=max(cand.numel() - 1, 0))
+        bad |= (cand[j] != pitems) if cand.numel() > 0 else torch.ones_like(bad)
+    if eptr is not None:
+        ekey = torch.repeat_interleave(torch.arange(Q, device=dev), eptr[1:] - eptr[:-1]) * T + ex_items   # sorted
+        if ekey.numel():
+            pkey = pq * T + pitems
+            j = torch.searchsorted(ekey, pkey).clamp_(max=ekey.numel() - 1)
+            bad |= ekey[j] == pkey
+    return bad
+
+
+def _apply_ineligible(bad, pptr, pitems, pq, Q: int, ineligible: str, describe):
+    """(pptr, pitems, pq, n_dropped) without the positives marked in `bad`; ineligible 'raise': a ValueError with
+    describe(j) for the first of them instead."""
+    n_dropped = int(bad.sum())
+    if n_dropped:
+        if ineligible == "raise":
+            raise ValueError(describe(int(torch.nonzero(bad)[0, 0])))
+        keep = ~bad
+        pitems, pq = pitems[keep].contiguous(), pq[keep]
+        pptr = torch.zeros(Q + 1, dtype=torch.int64, device=pitems.device)
+        torch.cumsum(torch.bincount(pq, minlength=Q), 0, out=pptr[1:])
+    return pptr, pitems, pq, n_dropped
+
+
+def _pair_head(users):
+    return "", (users,)
+
+
+def _field_head(ctx, field, kf, post=None, post_field=None):
+    """The field form's leading op arguments: the table form or, with `post`, the form under supplied posteriors."""
+    if post is None:
+        return "_field", (ctx.contiguous(), field, ctx[:, kf].contiguous())
+    return "_field_post", (ctx.contiguous(), field, post, post_field, ctx[:, kf].contiguous())
+
+
+def _workspace(o, name, dev, *sizes):
+    return torch.empty(max(getattr(o, name)(*sizes), 1), dtype=torch.uint8, device=dev)
+
+
+def _launch_topk(model, head, Q, cand, n_cand, lo, ptr, ex_items, k, code, seed, n_splits):
+    """Allocates the top-k outputs [Q, k] and the workspace, runs the form's ranking op, returns the outputs."""
+    form, lead = head
+    dev, k, n_splits = model.device, int(k), int(n_splits)
+    model._fresh_params()
+    ent, bia, scal = model._views(model._flat)
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = {"items": torch.empty(Q, k, dtype=torch.int64, device=dev), "score": torch.empty(Q, k, **f32),
+           "logit_mean": torch.empty(Q, k, **f32), "logit_var": torch.empty(Q, k, **f32)}
+    o = _lib.ops()
+    if form:
+        ws = _workspace(o, "rank_field_workspace_bytes", dev, Q, n_cand, model.F, model.d, k, code, n_splits)
+    else:
+        ws = _workspace(o, "rank_workspace_bytes", dev, Q, n_cand, model.d, k, code, n_splits)
+    getattr(o, "rank" + (form or "_items"))(*lead, cand, n_cand, lo, ptr, ex_items, ent, bia, scal, ws, *out.values(),
+                                            *(() if form else (2,)), k, code, flags_of(model), _seed64(seed), n_splits)
+    return out
+
+
+def _launch_heldout(model, head, Q, cand, n_cand, lo, eptr, ex_items, pptr, pitems, code, seed, n_splits):
+    """Allocates the held-out outputs (rank, rank_neg [n_pos]; n_eligible, n_neg [Q]) and the workspace, runs the form's
+    evaluation op, returns the outputs."""
+    form, lead = head
+    dev, n_pos, n_splits = model.device, pitems.numel(), int(n_splits)
+    model._fresh_params()
+    ent, bia, scal = model._views(model._flat)
+    i64 = dict(dtype=torch.int64, device=dev)
+    out = {"rank": torch.empty(n_pos, **i64), "rank_neg": torch.empty(n_pos, **i64), "n_eligible": torch.empty(Q, **i64),
+           "n_neg": torch.empty(Q, **i64)}
+    o = _lib.ops()
+    if form:
+        ws = _workspace(o, "rank_eval_field_workspace_bytes", dev, Q, n_cand, n_pos, model.F, model.d, code, n_splits)
+    else:
+        ws = _workspace(o, "rank_eval_workspace_bytes", dev, Q, n_cand, n_pos, model.d, code, n_splits)
+    getattr(o, "rank_heldout" + form)(*lead, cand, n_cand, lo, eptr, ex_items, pptr, pitems, ent, bia, scal, ws,
+                                      *out.values(), *(() if form else (2,)), code, flags_of(model), _seed64(seed),
+                                      n_splits)
+    return out
+
+
+def _pair_rows(x, name, N, T, dev):
+    x = torch.as_tensor(x).to(dev, torch.int64)
+    if x.dim() != 2 or x.shape[1] != 2:
+        raise ValueError(f"{name} must be an [R, 2] tensor of (user, item) rows")
+    if x.numel() and (int(x[:, 0].min()) < 0 or int(x[:, 0].max()) >= N or int(x[:, 1].min()) < N
+                      or int(x[:, 1].max()) >= T):
+        raise ValueError(f"{name} holds ids outside the user / item ranges")
+    return x
+
+
 def rank_items(model, users, k: int = 10, strategy: str = "top", items=None, exclude=None, seed: int = 0,
                n_splits: int = 0):
     """The k best candidate items of each query user (model.rank_items documents the arguments)."""
     ops._need_cuda(model._flat, "the model's parameters")
-    code = strategy_code(strategy)
     if model.F != 2:
         raise ValueError("rank_items ranks (user, item) pairs: two-field models only")
-    if strategy == "mean" and model.output != "class":
-        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
-    if not 1 <= int(k) <= MAX_K:
-        raise ValueError(f"k must lie in [1, {MAX_K}]")
-    if not 0 <= int(n_splits) <= MAX_SPLITS:
-        raise ValueError(f"n_splits must lie in [0, {MAX_SPLITS}]")
-    k = int(k)
-    dev = model.device
-    N, M, T = model.N, model.M, model.T
+    code = _score_args(model, strategy, k, n_splits)
+    dev, N, T = model.device, model.N, model.T
     users = torch.as_tensor(users).to(dev, torch.int64).reshape(-1)
     if users.numel() and (int(users.min()) < 0 or int(users.max()) >= N):
         raise ValueError(f"user ids must lie in [0, {N})")
     uq, inv = torch.unique(users, return_inverse=True)       # (each distinct user ranked once)
-    cand, n_cand = None, M
-    if items is not None:
-        cand = torch.as_tensor(items).to(dev, torch.int64).reshape(-1)
-        if cand.numel() and (int(cand.min()) < N or int(cand.max()) >= T):
-            raise ValueError(f"item ids must lie in [{N}, {T})")
-        cand = torch.sort(cand).values
-        if cand.numel() > 1 and bool((cand[1:] == cand[:-1]).any()):
-            raise ValueError("duplicate candidate items")
-        n_cand = cand.numel()
+    cand, n_cand = _candidates(items, N, T, dev, _ITEM_WORDS)
     ptr = ex_items = None
     if exclude is not None:
-        ex = torch.as_tensor(exclude).to(dev, torch.int64)
-        if ex.dim() != 2 or ex.shape[1] != 2:
-            raise ValueError("exclude must be an [R, 2] tensor of (user, item) rows")
-        if ex.numel() and (int(ex[:, 0].min()) < 0 or int(ex[:, 0].max()) >= N or int(ex[:, 1].min()) < N
-                           or int(ex[:, 1].max()) >= T):
-            raise ValueError("exclude holds ids outside the user / item ranges")
-        ptr, ex_items = exclusion_csr(uq, ex, T)
-    model._fresh_params()
-    ent, bia, scal = model._views(model._flat)
-    U = uq.numel()
-    f32 = dict(dtype=torch.float32, device=dev)
-    out = {"items": torch.empty(U, k, dtype=torch.int64, device=dev), "score": torch.empty(U, k, **f32),
-           "logit_mean": torch.empty(U, k, **f32), "logit_var": torch.empty(U, k, **f32)}
-    o = _lib.ops()
-    ws = torch.empty(max(o.rank_workspace_bytes(U, n_cand, model.d, k, code, int(n_splits)), 1), dtype=torch.uint8,
-                     device=dev)
-    o.rank_items(uq, cand, n_cand, N, ptr, ex_items, ent, bia, scal, ws, out["items"], out["score"], out["logit_mean"],
-                 out["logit_var"], 2, k, code, ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, _seed64(seed),
-                 int(n_splits))
-    if U != users.numel() or not bool((uq == users).all()):
+        ptr, ex_items = exclusion_csr(uq, _pair_rows(exclude, "exclude", N, T, dev), T)
+    out = _launch_topk(model, _pair_head(uq), uq.numel(), cand, n_cand, N, ptr, ex_items, k, code, seed, n_splits)
+    if uq.numel() != users.numel() or not bool((uq == users).all()):
         out = {key: val[inv] for key, val in out.items()}
+    return out
+
+
+def rank_heldout(model, pos, exclude=None, items=None, strategy: str = "top", seed: int = 0, n_splits: int = 0):
+    """Exact full-catalog positions of held-out positives (model.rank_heldout documents the arguments and outputs)."""
+    ops._need_cuda(model._flat, "the model's parameters")
+    if model.F != 2:
+        raise ValueError("rank_heldout ranks (user, item) pairs: two-field models only")
+    code = _score_args(model, strategy, None, n_splits)
+    dev, N, T = model.device, model.N, model.T
+    pos = _pair_rows(pos, "pos", N, T, dev)
+    users = torch.unique(pos[:, 0])                          # sorted: every user with a positive
+    pptr, pitems = exclusion_csr(users, pos, T)              # (ascending per user, duplicates dropped)
+    cand, n_cand = _candidates(items, N, T, dev, _ITEM_WORDS)
+    U = users.numel()
+    puser = torch.repeat_interleave(torch.arange(U, device=dev), pptr[1:] - pptr[:-1])
+    eptr = ex_items = None
+    if exclude is not None:
+        eptr, ex_items = exclusion_csr(users, _pair_rows(exclude, "exclude", N, T, dev), T)
+    _apply_ineligible(_ineligible(pitems, puser, cand, eptr, ex_items, U, T), pptr, pitems, puser, U, "raise",
+                      lambda j: f"positive (user {int(users[puser[j]])}, item {int(pitems[j])}) is not an eligible "
+                                "candidate (excluded, or outside `items`)")
+    out = {"users": users, "ptr": pptr, "items": pitems, "user_index": puser}
+    out.update(_launch_heldout(model, _pair_head(users), U, cand, n_cand, N, eptr, ex_items, pptr, pitems, code, seed,
+                               n_splits))
     return out
 
 
@@ -120,16 +255,12 @@ def select_next_questions(model, pool, n: int = 1, strategy: str = "variance", s
     rank_items, from the closed-form moments).  Ties go to the lower row index.  Returns (users [U'] ascending,
     rows [U', n] int64, -1 where a user has fewer than n rows)."""
     ops._need_cuda(model._flat, "the model's parameters")
-    strategy_code(strategy)
     if model.F != 2:
         raise ValueError("select_next_questions: two-field models only")
-    if strategy == "mean" and model.output != "class":
-        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
+    _score_args(model, strategy)
     if int(n) < 1:
         raise ValueError("n must be >= 1")
-    n = int(n)
-    dev = model.device
-    pool = torch.as_tensor(pool).to(dev, torch.int64).contiguous()
+    pool = torch.as_tensor(pool).to(model.device, torch.int64).contiguous()
     if pool.dim() != 2 or pool.shape[1] != 2:
         raise ValueError("pool must be an [P, 2] tensor of (user, item) rows")
     if pool.numel() and (int(pool.min()) < 0 or int(pool.max()) >= model.T):
@@ -137,19 +268,7 @@ def select_next_questions(model, pool, n: int = 1, strategy: str = "variance", s
     model._fresh_params()
     ent, bia, scal = model._views(model._flat)
     _, _, score = predictive_moments(pool, ent, bia, scal, model.link, strategy, seed)
-    score = torch.nan_to_num(score, nan=-float("inf"))
-    o1 = torch.sort(score, descending=True, stable=True).indices            # best first; ties: lower row first
-    o2 = torch.sort(pool[o1, 0], stable=True).indices                        # grouped by user, order kept
-    order = o1[o2]
-    pu = pool[order, 0]
-    users, counts = torch.unique_consecutive(pu, return_counts=True)
-    start = torch.cumsum(counts, 0) - counts
-    grp = torch.repeat_interleave(torch.arange(users.numel(), device=dev), counts)
-    rank = torch.arange(pu.numel(), device=dev) - start[grp]
-    keep = rank < n
-    rows = torch.full((users.numel(), n), -1, dtype=torch.int64, device=dev)
-    rows[grp[keep], rank[keep]] = order[keep]
-    return users, rows
+    return best_rows_per_entity(pool, score, 0, int(n))
 
 
 def field_exclusion_csr(ctx: torch.Tensor, exclude: torch.Tensor, field: int, match_fields, T: int):
@@ -216,30 +335,35 @@ def _context_rows(model, x, name, field, check_field_column=False):
     return x
 
 
-def field_moments(model, X, field, strategy: Optional[str] = None, seed: int = 0, key_field=None):
-    """(logit_mean [B], logit_var [B], score [B] or None) of the rows X [B, F] in the field form: the bitwise definition
-    of what rank_field returns (model.field_moments documents the arguments)."""
+def _field_moments(model, X, field, strategy, seed, key_field, post=None):
+    """field_moments (post None) and field_moments_posterior (post = (theta, post_field))."""
     field = _field_arg(model, field)
     kf = _key_field(model, field, key_field)
-    code = strategy_code(strategy) if strategy is not None else 0
-    if strategy == "mean" and model.output != "class":
-        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
+    code = _score_args(model, strategy, optional=True)
     x = torch.as_tensor(X)
     if x.dim() != 2 or x.shape[1] != model.F:
         raise ValueError(f"X must be [B, {model.F}]")
+    if post is not None:
+        post = (_posterior_args(model, post[0], post[1], field, x.shape[0], "X"), post[1])
     ops._need_cuda(model._flat, "the model's parameters")
     x = x.to(model.device)
     x = (x if x.dtype in (torch.int32, torch.int64) else x.to(torch.int64)).contiguous()
     model._fresh_params()
     ent, bia, scal = model._views(model._flat)
-    B = x.shape[0]
-    m = torch.empty(B, dtype=torch.float32, device=x.device)
-    v = torch.empty_like(m)
-    sc = torch.empty_like(m) if strategy is not None else None
+    m, v, sc = _moment_outputs(x, strategy is not None)
     qkey = x[:, kf].to(torch.int64).contiguous()
-    _lib.ops().field_moments(x, field, qkey, ent, bia, scal, m, v, sc,
-                             ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, code, _seed64(seed))
+    tail = (qkey, ent, bia, scal, m, v, sc, flags_of(model), code, _seed64(seed))
+    if post is None:
+        _lib.ops().field_moments(x, field, *tail)
+    else:
+        _lib.ops().field_moments_post(x, field, *post, *tail)
     return m, v, sc
+
+
+def field_moments(model, X, field, strategy: Optional[str] = None, seed: int = 0, key_field=None):
+    """(logit_mean [B], logit_var [B], score [B] or None) of the rows X [B, F] in the field form: the bitwise definition
+    of what rank_field returns (model.field_moments documents the arguments)."""
+    return _field_moments(model, X, field, strategy, seed, key_field)
 
 
 def select_next_questions_field(model, pool, field, n: int = 1, strategy: str = "variance", seed: int = 0, key_field=None):
@@ -248,9 +372,7 @@ def select_next_questions_field(model, pool, field, n: int = 1, strategy: str = 
     lower row index.  Returns (entities [U'] ascending, rows [U', n] int64, -1 where an entity has fewer than n rows)."""
     field = _field_arg(model, field)
     _key_field(model, field, key_field)
-    strategy_code(strategy)
-    if strategy == "mean" and model.output != "class":
-        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
+    _score_args(model, strategy)
     if isinstance(n, bool) or int(n) < 1:
         raise ValueError("n must be >= 1")
     n = int(n)
@@ -282,62 +404,45 @@ def best_rows_per_entity(pool, score, field, n, drop_nan=False):
     return ents, rows
 
 
+def _query_contexts(model, contexts, name, field):
+    ctx = _context_rows(model, contexts, name, field).clone()
+    ctx[:, field] = 0                                          # (ignored by the kernels; zeroed so that duplicates meet)
+    return ctx
+
+
+def _rank_field(model, contexts, field, k, strategy, candidates, exclude, match_fields, key_field, seed, n_splits,
+                post=None, query_exclude=None, merge=True):
+    """rank_field (post None; merge: each distinct context is ranked once) and rank_field_posterior
+    (post = (theta, post_field); every row its own query, which `query_exclude` names by index)."""
+    from .foldin import field_range
+    field = _field_arg(model, field)
+    code = _score_args(model, strategy, k, n_splits)
+    kf = _key_field(model, field, key_field)
+    match = _match_arg(model, field, match_fields)
+    lo, hi = field_range(model, field)
+    ctx = _query_contexts(model, contexts, "contexts", field)
+    if post is not None:
+        post = (_posterior_args(model, post[0], post[1], field, ctx.shape[0]), post[1])
+    cand, n_cand = _candidates(candidates, lo, hi, model.device)
+    ex = _context_rows(model, exclude, "exclude", field, check_field_column=True) if exclude is not None else None
+    qex = _query_pairs(model, query_exclude, "query_exclude", ctx.shape[0], lo, hi) if query_exclude is not None else None
+    ops._need_cuda(model._flat, "the model's parameters")
+    uq, inv = ctx, None
+    if merge:
+        uq, inv = torch.unique(ctx, dim=0, return_inverse=True)
+        inv = inv.reshape(-1)
+    ptr, ex_items = posterior_exclusions(model, uq, field, match, ex, qex, lo, hi)
+    out = _launch_topk(model, _field_head(uq, field, kf, *(post or ())), uq.shape[0], cand, n_cand, lo, ptr, ex_items, k,
+                       code, seed, n_splits)
+    if merge and (uq.shape[0] != ctx.shape[0] or not bool((uq == ctx).all())):
+        out = {key: val[inv] for key, val in out.items()}
+    return out
+
+
 def rank_field(model, contexts, field, k: int = 10, strategy: str = "top", candidates=None, exclude=None,
                match_fields=None, key_field=None, seed: int = 0, n_splits: int = 0):
     """The k best entities of `field` for each context row (model.rank_field documents the arguments)."""
-    from .foldin import field_range
-    field = _field_arg(model, field)
-    code = strategy_code(strategy)
-    if strategy == "mean" and model.output != "class":
-        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
-    if not 1 <= int(k) <= MAX_K:
-        raise ValueError(f"k must lie in [1, {MAX_K}]")
-    if not 0 <= int(n_splits) <= MAX_SPLITS:
-        raise ValueError(f"n_splits must lie in [0, {MAX_SPLITS}]")
-    k = int(k)
-    kf = _key_field(model, field, key_field)
-    ctx_cols = [f for f in range(model.F) if f != field]
-    if match_fields is None:
-        match = ctx_cols
-    else:
-        match = sorted({int(f) for f in match_fields})
-        if any(f not in ctx_cols for f in match):
-            raise ValueError(f"match_fields must be context columns, a subset of {ctx_cols}")
-    dev, T = model.device, model.T
-    lo, hi = field_range(model, field)
-    ctx = _context_rows(model, contexts, "contexts", field).clone()
-    ctx[:, field] = 0                                          # (ignored by the kernels; zeroed so that duplicates meet)
-    cand, n_cand = None, hi - lo
-    if candidates is not None:
-        cand = torch.as_tensor(candidates).to(dev, torch.int64).reshape(-1)
-        if cand.numel() and (int(cand.min()) < lo or int(cand.max()) >= hi):
-            raise ValueError(f"candidate ids must lie in the field's range [{lo}, {hi})")
-        cand = torch.sort(cand).values
-        if cand.numel() > 1 and bool((cand[1:] == cand[:-1]).any()):
-            raise ValueError("duplicate candidates")
-        n_cand = cand.numel()
-    ex = _context_rows(model, exclude, "exclude", field, check_field_column=True) if exclude is not None else None
-    ops._need_cuda(model._flat, "the model's parameters")
-    uq, inv = torch.unique(ctx, dim=0, return_inverse=True)    # (each distinct context ranked once)
-    inv = inv.reshape(-1)
-    ptr = ex_items = None
-    if ex is not None:
-        ptr, ex_items = field_exclusion_csr(uq, ex, field, match, T)
-    model._fresh_params()
-    ent, bia, scal = model._views(model._flat)
-    Q = uq.shape[0]
-    f32 = dict(dtype=torch.float32, device=dev)
-    out = {"items": torch.empty(Q, k, dtype=torch.int64, device=dev), "score": torch.empty(Q, k, **f32),
-           "logit_mean": torch.empty(Q, k, **f32), "logit_var": torch.empty(Q, k, **f32)}
-    o = _lib.ops()
-    ws = torch.empty(max(o.rank_field_workspace_bytes(Q, n_cand, model.F, model.d, k, code, int(n_splits)), 1),
-                     dtype=torch.uint8, device=dev)
-    o.rank_field(uq.contiguous(), field, uq[:, kf].contiguous(), cand, n_cand, lo, ptr, ex_items, ent, bia, scal, ws,
-                 out["items"], out["score"], out["logit_mean"], out["logit_var"], k, code,
-                 ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, _seed64(seed), int(n_splits))
-    if Q != ctx.shape[0] or not bool((uq == ctx).all()):
-        out = {key: val[inv] for key, val in out.items()}
-    return out
+    return _rank_field(model, contexts, field, k, strategy, candidates, exclude, match_fields, key_field, seed, n_splits)
 
 
 def field_positive_csr(rows: torch.Tensor, field: int, T: int):
@@ -357,159 +462,64 @@ def field_positive_csr(rows: torch.Tensor, field: int, T: int):
     return uq, ptr, items
 
 
+def _rank_heldout_field(model, pos, field, exclude, candidates, match_fields, key_field, strategy, seed, n_splits,
+                        ineligible, post=None, queries=None, query_exclude=None):
+    """rank_heldout_field (post None: `pos` holds full rows, the queries are their distinct contexts) and
+    rank_heldout_field_posterior (post = (theta, post_field): `queries` are given, `pos` and `query_exclude` name them by
+    index)."""
+    from .foldin import field_range
+    field = _field_arg(model, field)
+    code = _score_args(model, strategy, None, n_splits)
+    if ineligible not in ("raise", "drop"):
+        raise ValueError(f"ineligible must be 'raise' or 'drop', not {ineligible!r}")
+    kf = _key_field(model, field, key_field)
+    match = _match_arg(model, field, match_fields)
+    dev, T = model.device, model.T
+    lo, hi = field_range(model, field)
+    if post is None:
+        pos = _context_rows(model, pos, "pos", field, check_field_column=True)
+        n_queries = 0                                          # (no argument names a query by index)
+    else:
+        ctx = _query_contexts(model, queries, "queries", field)
+        n_queries = ctx.shape[0]
+        post = (_posterior_args(model, post[0], post[1], field, n_queries, "queries"), post[1])
+        pqi, pids = _query_pairs(model, pos, "pos", n_queries, lo, hi)
+    cand, n_cand = _candidates(candidates, lo, hi, dev)
+    ex = _context_rows(model, exclude, "exclude", field, check_field_column=True) if exclude is not None else None
+    qex = _query_pairs(model, query_exclude, "query_exclude", n_queries, lo, hi) if query_exclude is not None else None
+    ops._need_cuda(model._flat, "the model's parameters")
+    if post is None:
+        ctx, pptr, pitems = field_positive_csr(pos, field, T)
+    else:
+        pptr, pitems = query_csr(pqi, pids, n_queries, T)      # (ascending per query, duplicates dropped)
+    Q = ctx.shape[0]
+    pq = torch.repeat_interleave(torch.arange(Q, device=dev), pptr[1:] - pptr[:-1])
+    eptr, ex_items = posterior_exclusions(model, ctx, field, match, ex, qex, lo, hi)
+
+    def describe(j):
+        if post is not None:
+            return (f"positive {int(pitems[j])} of query {int(pq[j])} is not an eligible candidate of its query "
+                    "(excluded, or outside `candidates`); ineligible='drop' removes such positives")
+        row = ctx[pq[j]].clone()
+        row[field] = pitems[j]
+        return (f"positive row {row.tolist()} is not an eligible candidate of its context (excluded, or outside "
+                "`candidates`); ineligible='drop' removes such rows")
+
+    pptr, pitems, pq, n_dropped = _apply_ineligible(_ineligible(pitems, pq, cand, eptr, ex_items, Q, T), pptr, pitems, pq,
+                                                    Q, ineligible, describe)
+    out = {"contexts": ctx, "ptr": pptr, "items": pitems, "query_index": pq}
+    out.update(_launch_heldout(model, _field_head(ctx, field, kf, *(post or ())), Q, cand, n_cand, lo, eptr, ex_items,
+                               pptr, pitems, code, seed, n_splits))
+    out["n_dropped"] = n_dropped
+    return out
+
+
 def rank_heldout_field(model, pos, field, exclude=None, candidates=None, match_fields=None, key_field=None,
                        strategy: str = "top", seed: int = 0, n_splits: int = 0, ineligible: str = "raise"):
     """Exact positions of held-out positives in their contexts' full rankings of one field (model.rank_heldout_field
     documents the arguments and outputs)."""
-    from .foldin import field_range
-    field = _field_arg(model, field)
-    code = strategy_code(strategy)
-    if strategy == "mean" and model.output != "class":
-        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
-    if not 0 <= int(n_splits) <= MAX_SPLITS:
-        raise ValueError(f"n_splits must lie in [0, {MAX_SPLITS}]")
-    if ineligible not in ("raise", "drop"):
-        raise ValueError(f"ineligible must be 'raise' or 'drop', not {ineligible!r}")
-    kf = _key_field(model, field, key_field)
-    ctx_cols = [f for f in range(model.F) if f != field]
-    if match_fields is None:
-        match = ctx_cols
-    else:
-        match = sorted({int(f) for f in match_fields})
-        if any(f not in ctx_cols for f in match):
-            raise ValueError(f"match_fields must be context columns, a subset of {ctx_cols}")
-    dev, T = model.device, model.T
-    lo, hi = field_range(model, field)
-    pos = _context_rows(model, pos, "pos", field, check_field_column=True)
-    cand, n_cand = None, hi - lo
-    if candidates is not None:
-        cand = torch.as_tensor(candidates).to(dev, torch.int64).reshape(-1)
-        if cand.numel() and (int(cand.min()) < lo or int(cand.max()) >= hi):
-            raise ValueError(f"candidate ids must lie in the field's range [{lo}, {hi})")
-        cand = torch.sort(cand).values
-        if cand.numel() > 1 and bool((cand[1:] == cand[:-1]).any()):
-            raise ValueError("duplicate candidates")
-        n_cand = cand.numel()
-    ex = _context_rows(model, exclude, "exclude", field, check_field_column=True) if exclude is not None else None
-    ops._need_cuda(model._flat, "the model's parameters")
-    uq, pptr, pitems = field_positive_csr(pos, field, T)
-    Q = uq.shape[0]
-    pq = torch.repeat_interleave(torch.arange(Q, device=dev), pptr[1:] - pptr[:-1])
-    # eligibility (torch, on the device): every positive is a candidate and not excluded
-    bad = torch.zeros(pitems.numel(), dtype=torch.bool, device=dev)
-    if cand is not None:
-        j = torch.searchsorted(cand, pitems).clamp_(max=max(n_cand - 1, 0))
-        bad |= (cand[j] != pitems) if n_cand > 0 else torch.ones_like(bad)
-    eptr = ex_items = None
-    if ex is not None:
-        eptr, ex_items = field_exclusion_csr(uq, ex, field, match, T)
-        ekey = torch.repeat_interleave(torch.arange(Q, device=dev), eptr[1:] - eptr[:-1]) * T + ex_items   # sorted
-        if ekey.numel():
-            pkey = pq * T + pitems
-            j = torch.searchsorted(ekey, pkey).clamp_(max=ekey.numel() - 1)
-            bad |= ekey[j] == pkey
-    n_dropped = int(bad.sum())
-    if n_dropped:
-        if ineligible == "raise":
-            j = int(torch.nonzero(bad)[0, 0])
-            row = uq[pq[j]].clone()
-            row[field] = pitems[j]
-            raise ValueError(f"positive row {row.tolist()} is not an eligible candidate of its context (excluded, or "
-                             "outside `candidates`); ineligible='drop' removes such rows")
-        keep = ~bad
-        pitems, pq = pitems[keep].contiguous(), pq[keep]
-        pptr = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(torch.bincount(pq, minlength=Q), 0, out=pptr[1:])
-    model._fresh_params()
-    ent, bia, scal = model._views(model._flat)
-    n_pos = pitems.numel()
-    i64 = dict(dtype=torch.int64, device=dev)
-    out = {"contexts": uq, "ptr": pptr, "items": pitems, "query_index": pq, "rank": torch.empty(n_pos, **i64),
-           "rank_neg": torch.empty(n_pos, **i64), "n_eligible": torch.empty(Q, **i64), "n_neg": torch.empty(Q, **i64),
-           "n_dropped": n_dropped}
-    o = _lib.ops()
-    ws = torch.empty(max(o.rank_eval_field_workspace_bytes(Q, n_cand, n_pos, model.F, model.d, code, int(n_splits)), 1),
-                     dtype=torch.uint8, device=dev)
-    o.rank_heldout_field(uq.contiguous(), field, uq[:, kf].contiguous(), cand, n_cand, lo, eptr, ex_items, pptr, pitems,
-                         ent, bia, scal, ws, out["rank"], out["rank_neg"], out["n_eligible"], out["n_neg"], code,
-                         ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, _seed64(seed), int(n_splits))
-    return out
-
-
-def _candidates(model, items):
-    """(cand sorted int64 or None, n_cand) of rank_items' `items` argument."""
-    N, M, T = model.N, model.M, model.T
-    if items is None:
-        return None, M
-    cand = torch.as_tensor(items).to(model.device, torch.int64).reshape(-1)
-    if cand.numel() and (int(cand.min()) < N or int(cand.max()) >= T):
-        raise ValueError(f"item ids must lie in [{N}, {T})")
-    cand = torch.sort(cand).values
-    if cand.numel() > 1 and bool((cand[1:] == cand[:-1]).any()):
-        raise ValueError("duplicate candidate items")
-    return cand, cand.numel()
-
-
-def _pair_rows(x, name, N, T, dev):
-    x = torch.as_tensor(x).to(dev, torch.int64)
-    if x.dim() != 2 or x.shape[1] != 2:
-        raise ValueError(f"{name} must be an [R, 2] tensor of (user, item) rows")
-    if x.numel() and (int(x[:, 0].min()) < 0 or int(x[:, 0].max()) >= N or int(x[:, 1].min()) < N
-                      or int(x[:, 1].max()) >= T):
-        raise ValueError(f"{name} holds ids outside the user / item ranges")
-    return x
-
-
-def rank_heldout(model, pos, exclude=None, items=None, strategy: str = "top", seed: int = 0, n_splits: int = 0):
-    """Exact full-catalog positions of held-out positives (model.rank_heldout documents the arguments and outputs)."""
-    ops._need_cuda(model._flat, "the model's parameters")
-    code = strategy_code(strategy)
-    if model.F != 2:
-        raise ValueError("rank_heldout ranks (user, item) pairs: two-field models only")
-    if strategy == "mean" and model.output != "class":
-        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
-    if not 0 <= int(n_splits) <= MAX_SPLITS:
-        raise ValueError(f"n_splits must lie in [0, {MAX_SPLITS}]")
-    dev = model.device
-    N, T = model.N, model.T
-    pos = _pair_rows(pos, "pos", N, T, dev)
-    users = torch.unique(pos[:, 0])                          # sorted: every user with a positive
-    pptr, pitems = exclusion_csr(users, pos, T)              # (ascending per user, duplicates dropped)
-    cand, n_cand = _candidates(model, items)
-    U = users.numel()
-    counts = pptr[1:] - pptr[:-1]
-    puser = torch.repeat_interleave(torch.arange(U, device=dev), counts)
-    # eligibility (torch, on the device): every positive is a candidate and not excluded
-    bad = torch.zeros(pitems.numel(), dtype=torch.bool, device=dev)
-    if cand is not None:
-        j = torch.searchsorted(cand, pitems).clamp_(max=max(n_cand - 1, 0))
-        bad |= (cand[j] != pitems) if n_cand > 0 else torch.ones_like(bad)
-    eptr = ex_items = None
-    if exclude is not None:
-        ex = _pair_rows(exclude, "exclude", N, T, dev)
-        eptr, ex_items = exclusion_csr(users, ex, T)
-        ekey = torch.repeat_interleave(torch.arange(U, device=dev), eptr[1:] - eptr[:-1]) * T + ex_items   # sorted
-        pkey = puser * T + pitems
-        if ekey.numel():
-            j = torch.searchsorted(ekey, pkey).clamp_(max=ekey.numel() - 1)
-            bad |= ekey[j] == pkey
-    if bool(bad.any()):
-        q = int(torch.nonzero(bad)[0, 0])
-        raise ValueError(f"positive (user {int(users[puser[q]])}, item {int(pitems[q])}) is not an eligible candidate "
-                         "(excluded, or outside `items`)")
-    model._fresh_params()
-    ent, bia, scal = model._views(model._flat)
-    n_pos = pitems.numel()
-    i64 = dict(dtype=torch.int64, device=dev)
-    out = {"users": users, "ptr": pptr, "items": pitems, "user_index": puser, "rank": torch.empty(n_pos, **i64),
-           "rank_neg": torch.empty(n_pos, **i64), "n_eligible": torch.empty(U, **i64), "n_neg": torch.empty(U, **i64)}
-    o = _lib.ops()
-    ws = torch.empty(max(o.rank_eval_workspace_bytes(U, n_cand, n_pos, model.d, code, int(n_splits)), 1),
-                     dtype=torch.uint8, device=dev)
-    o.rank_heldout(users, cand, n_cand, N, eptr, ex_items, pptr, pitems, ent, bia, scal, ws, out["rank"],
-                   out["rank_neg"], out["n_eligible"], out["n_neg"], 2, code,
-                   ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, _seed64(seed), int(n_splits))
-    return out
+    return _rank_heldout_field(model, pos, field, exclude, candidates, match_fields, key_field, strategy, seed, n_splits,
+                               ineligible)
 
 
 def ranking_metrics(rank, rank_neg, ptr, n_neg, ks=(10,)):
@@ -601,19 +611,6 @@ def _match_arg(model, field, match_fields):
     return match
 
 
-def _candidates_field(model, candidates, lo, hi):
-    """(cand sorted int64 or None, n_cand) of the field forms' `candidates` argument."""
-    if candidates is None:
-        return None, hi - lo
-    cand = torch.as_tensor(candidates).to(model.device, torch.int64).reshape(-1)
-    if cand.numel() and (int(cand.min()) < lo or int(cand.max()) >= hi):
-        raise ValueError(f"candidate ids must lie in the field's range [{lo}, {hi})")
-    cand = torch.sort(cand).values
-    if cand.numel() > 1 and bool((cand[1:] == cand[:-1]).any()):
-        raise ValueError("duplicate candidates")
-    return cand, cand.numel()
-
-
 def _query_pairs(model, pairs, name, Q, lo, hi):
     """(query_index [R], ids [R]) int64 on the model's device: query indices in [0, Q), ids in the ranked field's range."""
     if not isinstance(pairs, (tuple, list)) or len(pairs) != 2:
@@ -663,28 +660,7 @@ def field_moments_posterior(model, X, theta, post_field, field, strategy: Option
                             key_field=None):
     """field_moments with column post_field's parameters taken from theta (model.field_moments_posterior documents the
     arguments)."""
-    field = _field_arg(model, field)
-    kf = _key_field(model, field, key_field)
-    code = strategy_code(strategy) if strategy is not None else 0
-    if strategy == "mean" and model.output != "class":
-        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
-    x = torch.as_tensor(X)
-    if x.dim() != 2 or x.shape[1] != model.F:
-        raise ValueError(f"X must be [B, {model.F}]")
-    post = _posterior_args(model, theta, post_field, field, x.shape[0], "X")
-    ops._need_cuda(model._flat, "the model's parameters")
-    x = x.to(model.device)
-    x = (x if x.dtype in (torch.int32, torch.int64) else x.to(torch.int64)).contiguous()
-    model._fresh_params()
-    ent, bia, scal = model._views(model._flat)
-    B = x.shape[0]
-    m = torch.empty(B, dtype=torch.float32, device=x.device)
-    v = torch.empty_like(m)
-    sc = torch.empty_like(m) if strategy is not None else None
-    qkey = x[:, kf].to(torch.int64).contiguous()
-    _lib.ops().field_moments_post(x, field, post, post_field, qkey, ent, bia, scal, m, v, sc,
-                                  ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, code, _seed64(seed))
-    return m, v, sc
+    return _field_moments(model, X, field, strategy, seed, key_field, post=(theta, post_field))
 
 
 def rank_field_posterior(model, contexts, theta, post_field, field, k: int = 10, strategy: str = "top", candidates=None,
@@ -692,41 +668,8 @@ def rank_field_posterior(model, contexts, theta, post_field, field, k: int = 10,
                          query_exclude=None):
     """rank_field with column post_field's parameters taken from theta, every row its own query
     (model.rank_field_posterior documents the arguments)."""
-    from .foldin import field_range
-    field = _field_arg(model, field)
-    code = strategy_code(strategy)
-    if strategy == "mean" and model.output != "class":
-        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
-    if not 1 <= int(k) <= MAX_K:
-        raise ValueError(f"k must lie in [1, {MAX_K}]")
-    if not 0 <= int(n_splits) <= MAX_SPLITS:
-        raise ValueError(f"n_splits must lie in [0, {MAX_SPLITS}]")
-    k = int(k)
-    kf = _key_field(model, field, key_field)
-    match = _match_arg(model, field, match_fields)
-    dev = model.device
-    lo, hi = field_range(model, field)
-    ctx = _context_rows(model, contexts, "contexts", field).clone()
-    ctx[:, field] = 0                                          # (ignored by the kernels)
-    Q = ctx.shape[0]
-    post = _posterior_args(model, theta, post_field, field, Q)
-    cand, n_cand = _candidates_field(model, candidates, lo, hi)
-    ex = _context_rows(model, exclude, "exclude", field, check_field_column=True) if exclude is not None else None
-    qex = _query_pairs(model, query_exclude, "query_exclude", Q, lo, hi) if query_exclude is not None else None
-    ops._need_cuda(model._flat, "the model's parameters")
-    ptr, ex_items = posterior_exclusions(model, ctx, field, match, ex, qex, lo, hi)
-    model._fresh_params()
-    ent, bia, scal = model._views(model._flat)
-    f32 = dict(dtype=torch.float32, device=dev)
-    out = {"items": torch.empty(Q, k, dtype=torch.int64, device=dev), "score": torch.empty(Q, k, **f32),
-           "logit_mean": torch.empty(Q, k, **f32), "logit_var": torch.empty(Q, k, **f32)}
-    o = _lib.ops()
-    ws = torch.empty(max(o.rank_field_workspace_bytes(Q, n_cand, model.F, model.d, k, code, int(n_splits)), 1),
-                     dtype=torch.uint8, device=dev)
-    o.rank_field_post(ctx.contiguous(), field, post, post_field, ctx[:, kf].contiguous(), cand, n_cand, lo, ptr,
-                      ex_items, ent, bia, scal, ws, out["items"], out["score"], out["logit_mean"], out["logit_var"], k,
-                      code, ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, _seed64(seed), int(n_splits))
-    return out
+    return _rank_field(model, contexts, field, k, strategy, candidates, exclude, match_fields, key_field, seed, n_splits,
+                       post=(theta, post_field), query_exclude=query_exclude, merge=False)
 
 
 def rank_heldout_field_posterior(model, queries, pos, theta, post_field, field, exclude=None, candidates=None,
@@ -734,64 +677,5 @@ def rank_heldout_field_posterior(model, queries, pos, theta, post_field, field, 
                                  n_splits: int = 0, ineligible: str = "raise", query_exclude=None):
     """rank_heldout_field with column post_field's parameters taken from theta: the queries are given, the positives
     name their query by index (model.rank_heldout_field_posterior documents the arguments and outputs)."""
-    from .foldin import field_range
-    field = _field_arg(model, field)
-    code = strategy_code(strategy)
-    if strategy == "mean" and model.output != "class":
-        raise ValueError("strategy 'mean' (closest to p = 0.5) needs a 'class' model")
-    if not 0 <= int(n_splits) <= MAX_SPLITS:
-        raise ValueError(f"n_splits must lie in [0, {MAX_SPLITS}]")
-    if ineligible not in ("raise", "drop"):
-        raise ValueError(f"ineligible must be 'raise' or 'drop', not {ineligible!r}")
-    kf = _key_field(model, field, key_field)
-    match = _match_arg(model, field, match_fields)
-    dev, T = model.device, model.T
-    lo, hi = field_range(model, field)
-    ctx = _context_rows(model, queries, "queries", field).clone()
-    ctx[:, field] = 0
-    Q = ctx.shape[0]
-    post = _posterior_args(model, theta, post_field, field, Q, "queries")
-    pqi, pids = _query_pairs(model, pos, "pos", Q, lo, hi)
-    cand, n_cand = _candidates_field(model, candidates, lo, hi)
-    ex = _context_rows(model, exclude, "exclude", field, check_field_column=True) if exclude is not None else None
-    qex = _query_pairs(model, query_exclude, "query_exclude", Q, lo, hi) if query_exclude is not None else None
-    ops._need_cuda(model._flat, "the model's parameters")
-    pptr, pitems = query_csr(pqi, pids, Q, T)                  # (ascending per query, duplicates dropped)
-    pq = torch.repeat_interleave(torch.arange(Q, device=dev), pptr[1:] - pptr[:-1])
-    # eligibility (torch, on the device): every positive is a candidate and not excluded
-    bad = torch.zeros(pitems.numel(), dtype=torch.bool, device=dev)
-    if cand is not None:
-        j = torch.searchsorted(cand, pitems).clamp_(max=max(n_cand - 1, 0))
-        bad |= (cand[j] != pitems) if n_cand > 0 else torch.ones_like(bad)
-    eptr, ex_items = posterior_exclusions(model, ctx, field, match, ex, qex, lo, hi)
-    if eptr is not None:
-        ekey = torch.repeat_interleave(torch.arange(Q, device=dev), eptr[1:] - eptr[:-1]) * T + ex_items   # sorted
-        if ekey.numel():
-            pkey = pq * T + pitems
-            j = torch.searchsorted(ekey, pkey).clamp_(max=ekey.numel() - 1)
-            bad |= ekey[j] == pkey
-    n_dropped = int(bad.sum())
-    if n_dropped:
-        if ineligible == "raise":
-            j = int(torch.nonzero(bad)[0, 0])
-            raise ValueError(f"positive {int(pitems[j])} of query {int(pq[j])} is not an eligible candidate of its query "
-                             "(excluded, or outside `candidates`); ineligible='drop' removes such positives")
-        keep = ~bad
-        pitems, pq = pitems[keep].contiguous(), pq[keep]
-        pptr = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(torch.bincount(pq, minlength=Q), 0, out=pptr[1:])
-    model._fresh_params()
-    ent, bia, scal = model._views(model._flat)
-    n_pos = pitems.numel()
-    i64 = dict(dtype=torch.int64, device=dev)
-    out = {"contexts": ctx, "ptr": pptr, "items": pitems, "query_index": pq, "rank": torch.empty(n_pos, **i64),
-           "rank_neg": torch.empty(n_pos, **i64), "n_eligible": torch.empty(Q, **i64), "n_neg": torch.empty(Q, **i64),
-           "n_dropped": n_dropped}
-    o = _lib.ops()
-    ws = torch.empty(max(o.rank_eval_field_workspace_bytes(Q, n_cand, n_pos, model.F, model.d, code, int(n_splits)), 1),
-                     dtype=torch.uint8, device=dev)
-    o.rank_heldout_field_post(ctx.contiguous(), field, post, post_field, ctx[:, kf].contiguous(), cand, n_cand, lo, eptr,
-                              ex_items, pptr, pitems, ent, bia, scal, ws, out["rank"], out["rank_neg"],
-                              out["n_eligible"], out["n_neg"], code,
-                              ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, _seed64(seed), int(n_splits))
-    return out
+    return _rank_heldout_field(model, pos, field, exclude, candidates, match_fields, key_field, strategy, seed, n_splits,
+                               ineligible, post=(theta, post_field), queries=queries, query_exclude=query_exclude)
