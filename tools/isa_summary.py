@@ -63,6 +63,12 @@ WANT = [
     ("../csrc_rank/vfm_elicit_bound.hip", ["-ffp-contract=on"], "k_elicit_bound<64, 2, 0>", "bound session, moment scores, d = 128 (the benchmark shape), |.|"),
     ("../csrc_rank/vfm_elicit_bound.hip", ["-ffp-contract=on"], "k_elicit_bound<64, 2, 1>", "bound session, moment scores, d = 128, softplus"),
     ("../csrc_rank/vfm_elicit_bound.hip", ["-ffp-contract=on"], "k_elicit_bound<64, 8, 0>", "bound session, moment scores, d = 512, |.|"),
+    # the split bound rounds beside the split exact solve's assembly they are modelled on
+    # (--only _split --every _split: profiles/bound_split_isa.txt)
+    ("../csrc_rank/vfm_foldin_split.hip", ["-ffp-contract=on"], "k_split_assemble", "split exact solve: a chunk's share of the system (4 x 4 fp64 register tiles)"),
+    ("../csrc_rank/vfm_foldin_bound_split.hip", ["-ffp-contract=on"], "k_bsplit_assemble", "split bound rounds: a chunk's weights and its weighted share of the system"),
+    ("../csrc_rank/vfm_foldin_bound_split.hip", ["-ffp-contract=on"], "k_bsplit_solve<0>", "split bound rounds: a round's solve of one entity, |.|"),
+    ("../csrc_rank/vfm_foldin_bound_split.hip", ["-ffp-contract=on"], "k_bsplit_loss<64, 2, 0>", "split bound rounds: a chunk's share of B_e, d = 128, |.|"),
     # fused Adam step of the ELBO variants (--only variant_step prints these alone; --every variant_step adds one line per instance)
     ("../csrc_var/vfm_variant_step.hip", ["-ffp-contract=on"], "k_vstep<8, 16, 1, true, false, true>", "variant step, d = 128 (the benchmark shape), closed form, learnable priors"),
     ("../csrc_var/vfm_variant_step.hip", ["-ffp-contract=on"], "k_vstep<8, 16, 1, false, true, false>", "variant step, d = 128, sampled objective, feature values, N(0,1) priors"),

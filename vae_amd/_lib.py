@@ -132,7 +132,24 @@ class FoldinBound(_Strict, C.Structure):
     ]
 
 
-# the bound field-form session (vfm_elicit_bound_f32) is declared in the same header
+# ---- split bound rounds (include/vfm_bound_sweep.h), the hot path of VFM.fit_bound
+BOUND_SWEEP_EXPORTS = ("vfm_foldin_bound_split_f32", "vfm_foldin_bound_split_workspace_bytes")
+
+
+class FoldinBoundSplit(_Strict, C.Structure):
+    """`vfm_foldin_bound_split_t`: vfm_foldin_split_t's fields, n_iters and reset (tests/test_fit_bound_cpu.py checks the
+    layout against gcc's)."""
+    _fields_ = [
+        ("E", C.c_int64), ("R", C.c_int64), ("T", C.c_int64), ("n_ops", C.c_int64), ("n_chunks", C.c_int64),
+        ("F", C.c_int32), ("d", C.c_int32), ("col", C.c_int32), ("flags", C.c_int32), ("lds_dim", C.c_int32),
+        ("kl_weight", C.c_float), ("n_iters", C.c_int32), ("reset", C.c_int32),
+        ("entities", C.c_void_p), ("chunk_ptr", C.c_void_p), ("chunks", C.c_void_p), ("y", C.c_void_p),
+        ("op_x", C.c_void_p), ("row_op", C.c_void_p), ("entity_params", C.c_void_p), ("bias_params", C.c_void_p),
+        ("scalars", C.c_void_p), ("out_loss", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+
+# the bound field-form session (vfm_elicit_bound_f32) is declared in vfm_bound.h too
 ELICIT_BOUND_EXPORTS = ("vfm_elicit_bound_f32", "vfm_elicit_bound_workspace_bytes")
 
 
@@ -201,7 +218,7 @@ class ElicitDesign(_Session):
 
 
 for _c in (Problem, Index, Pipe, Elicit, ElicitField, ElicitSolve, ElicitBound, ElicitDesign, FoldinSolve, FoldinSplit,
-           FoldinBound):
+           FoldinBound, FoldinBoundSplit):
     _c._names = frozenset(n for n, _ in _c._fields_)
 
 
@@ -300,6 +317,10 @@ def load():
     lib.vfm_foldin_bound_f32.restype = C.c_int
     lib.vfm_foldin_bound_workspace_bytes.argtypes = [i64, i64, i64, i32, i32]
     lib.vfm_foldin_bound_workspace_bytes.restype = i64
+    lib.vfm_foldin_bound_split_f32.argtypes = [C.POINTER(FoldinBoundSplit), vp]
+    lib.vfm_foldin_bound_split_f32.restype = C.c_int
+    lib.vfm_foldin_bound_split_workspace_bytes.argtypes = [i64, i64, i64, i64, i32, i32]
+    lib.vfm_foldin_bound_split_workspace_bytes.restype = i64
     lib.vfm_elicit_bound_f32.argtypes = [C.POINTER(ElicitBound), vp]
     lib.vfm_elicit_bound_f32.restype = C.c_int
     lib.vfm_elicit_bound_workspace_bytes.argtypes = [i64, i64, i64, i64, i32, i32, i32]

@@ -95,15 +95,18 @@ _UNITS = [("vfm_abi.hip", "", _EXACT), ("vfm_index.hip", "", []), ("vfm_variants
           # bound elicitation session (include/vfm_bound.h: vfm_elicit_bound_f32): the exact sessions' loop and host path
           # (csrc_rank/vfm_elicit_exact_body.hpp) with the bound fold-in's body (csrc_rank/vfm_foldin_bound_body.hpp) as
           # the fold of a round, hence their flag
-          ("csrc_rank/vfm_elicit_bound.hip", "", _EXACT)]
+          ("csrc_rank/vfm_elicit_bound.hip", "", _EXACT),
+          # split bound rounds (include/vfm_bound_sweep.h): the bound fold-in's preps and weights with the split solve's
+          # chunk-parallel assembly in front of the same factorisation and rounding, hence their flag
+          ("csrc_rank/vfm_foldin_bound_split.hip", "", _EXACT)]
 RANK_DIR = os.path.join(HERE, "csrc_rank")
 VAR_DIR = os.path.join(HERE, "csrc_var")
 # the public headers beside include/vfm_hip.h (vfm_bound.h's ops live in vfm_foldin_ops.cpp and vfm_elicit_ops.cpp)
 PUBLIC_HDRS = tuple(os.path.join(ROOT, "include", f"vfm_{n}.h")
-                    for n in ("rank", "foldin", "elicit", "design", "variant_step", "sweep", "bound"))
+                    for n in ("rank", "foldin", "elicit", "design", "variant_step", "sweep", "bound", "bound_sweep"))
 # the TORCH_LIBRARY fragments linked into the shim beside csrc/vfm_torch_ops.cpp, and the header they share: host C++
 # only, so it is no source of libvfm_hip.so
-OPS_SOURCES = tuple(os.path.join(RANK_DIR, f"vfm_{n}_ops.cpp") for n in ("rank", "foldin", "elicit", "design", "sweep"))
+OPS_SOURCES = tuple(os.path.join(RANK_DIR, f"vfm_{n}_ops.cpp") for n in ("rank", "foldin", "elicit", "design", "sweep", "bound_sweep"))
 OPS_HDR = os.path.join(RANK_DIR, "vfm_ops_common.hpp")
 
 

@@ -1325,7 +1325,7 @@ class VFM(nn.Module):
 
     @torch.no_grad()
     def fold_in_bound(self, X_new, y_new, field: int = 0, kl_weight: float = 1.0, n_iters: int = 8,
-                      reset: bool = False):
+                      reset: bool = False, split_rows=None, chunk_rows: int = 2048, max_workspace_bytes: int = 1 << 30):
         """fold_in for a 'class' model without Adam: the entities of X_new[:, field] are fitted by n_iters rounds of
         exact solves of the Jaakkola-Jordan quadratic bound of the Bernoulli likelihood, in one launch
         (include/vfm_bound.h: vfm_foldin_bound_f32; DESIGN.md §4 "Bound fold-in").  No lr, no n_samples, no seed: each
@@ -1340,9 +1340,23 @@ class VFM(nn.Module):
         only.  'class' models only, kl_weight > 0, y in {0, 1} (else ValueError, as for everything fold_in rejects).
         X_new, y_new, field, the row order, what is written and what stays frozen are fold_in's: only the folded rows
         of entity_params / bias_params change; the training Adam state and the save_weights snapshots are not touched.
-        Returns dict(entities [E] int64, loss [E] fp32 = B_e at the returned parameters, rows [E] int64)."""
-        from . import foldin
-        ents, loss, rows = foldin.run_bound(self, X_new, y_new, field, kl_weight, n_iters, reset)
+        Returns dict(entities [E] int64, loss [E] fp32 = B_e at the returned parameters, rows [E] int64).
+
+        split_rows: None (the default) gives every entity to one workgroup.  An integer, or "auto" = 4 (d + 1), sends the
+        entities with more than max(split_rows, d + 1) rows through the split rounds (include/vfm_bound_sweep.h): their
+        rows are cut in chunks of chunk_rows, every round a workgroup per chunk computes its rows' weights and
+        assembles its share of the system, and a workgroup per entity adds the shares in chunk order and solves.  The
+        other entities get the bits they get with None; a split entity's bits depend on its rows, chunk_rows and d
+        alone, and are not those of None (the chunked sums associate differently).  The chunks' shares of one call
+        take at most max_workspace_bytes: the split entities are processed in as many groups as that needs, with the
+        same result."""
+        from . import foldin, sweep
+        if split_rows is None:
+            sweep.check_chunk_rows(chunk_rows)
+            ents, loss, rows = foldin.run_bound(self, X_new, y_new, field, kl_weight, n_iters, reset)
+        else:
+            ents, loss, rows = sweep.run_bound_split(self, X_new, y_new, field, kl_weight, n_iters, reset, split_rows,
+                                                     chunk_rows, max_workspace_bytes)
         return {"entities": ents, "loss": loss, "rows": rows}
 
     @torch.no_grad()
@@ -1384,6 +1398,45 @@ class VFM(nn.Module):
         sweep's device time from HIP events)."""
         from . import sweep
         return sweep.fit(self, X, y, n_sweeps, kl_weight, fields, update_scalars, split_rows, chunk_rows, on_step, tol)
+
+    @torch.no_grad()
+    def bound_objective(self, X, y, kl_weight: float = 1.0) -> float:
+        """The objective J of fit_bound at the current parameters ("Bound sweeps"): over the rows of X
+        the Jaakkola-Jordan bound with xi at its optimum, -(y_r - 1/2) E f_r + xi_r / 2 + log1p(e^-xi_r) with
+        xi_r = sqrt((E f_r)^2 + Var f_r), plus kl_weight times the KL to N(0, 1) of the factors of every entity that
+        occurs in X (embedding and first-order weight) and of the global bias: an upper bound on the expected
+        Bernoulli negative log likelihood plus kl_weight KL.  The per-row moments are the predictive_moments kernel's;
+        the sums and the KL terms are taken in fp64 on the device.  'class' models only, y in {0, 1}."""
+        from . import sweep
+        return sweep.bound_objective(self, X, y, kl_weight)
+
+    @torch.no_grad()
+    def fit_bound(self, X, y, n_sweeps: int = 10, kl_weight: float = 1.0, n_iters: int = 8, fields=None,
+                  update_bias: bool = True, split_rows="auto", chunk_rows: int = 2048, on_step=None,
+                  tol: Optional[float] = None):
+        """fit_exact's counterpart for a 'class' model: coordinate ascent on bound_objective in which each block is the
+        bound's exact minimiser, no learning rate, no sampling, no seed.  One sweep runs, for each field of `fields` in
+        turn (default: all, in order), fold_in_bound's n_iters rounds for every entity of that field over all rows of X
+        from its current row (reset=False: the first xi is taken at the current posterior, where the bound equals J, and
+        no round increases it, so no block increases J), then sets the global bias (mean and scale jointly) to its exact
+        minimiser under the bound at the current xi (update_bias=False leaves it alone).  scalars[0] is never touched:
+        the Bernoulli likelihood has no precision.  J never increases, up to the fp32 rounding of the rows written and
+        of the moments J is evaluated from.  Entities that do not occur in X are neither written nor counted.
+
+        n_iters = 8 is fold_in_bound's untuned starting value, not a choice made from sweeps: one round per block is
+        already a valid (monotone) sweep, and tools/fit_bound_bench.py records J per sweep for 1, 2 and 8.
+        split_rows, chunk_rows: as in fold_in_bound; "auto" = 4 (d + 1).  The row lists, partner tuples and chunk tables
+        of each field are built once, before the first sweep.  on_step(sweep, what) is called after every block, `what`
+        the field index or "bias".  tol: stop after a sweep whose relative decrease of J is at most tol.
+        'class' models only ('reg': use fit_exact), kl_weight > 0, n_iters >= 1, y in {0, 1}, ids as fold_in checks
+        them for every field (else ValueError).  The training Adam state and the save_weights snapshots are not touched.
+        Measured on an MI355X against the fp64 restatement (tests/test_gpu_fit_bound.py): every written element within
+        0.498 of its bound 2^-23 |ref| + n_iters solve_abs_term (+ scale_abs_term), J within 1.3e-8 relative.
+        Returns dict(objective = J before the first block and after every sweep, sweeps = the number run, ms = each
+        sweep's device time from HIP events)."""
+        from . import sweep
+        return sweep.fit_bound(self, X, y, n_sweeps, kl_weight, n_iters, fields, update_bias, split_rows, chunk_rows,
+                               on_step, tol)
 
     @torch.no_grad()
     def fold_in_objective(self, X, y, field: int = 0, objective: Optional[str] = None, n_samples: int = 1,

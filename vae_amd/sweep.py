@@ -1,4 +1,5 @@
-"""Exact coordinate-ascent training (VFM.fit_exact) and the split exact solve behind it (include/vfm_sweep.h).
+"""Coordinate-ascent training by per-entity solves: VFM.fit_exact ('reg', include/vfm_sweep.h) and VFM.fit_bound ('class',
+include/vfm_bound_sweep.h), and the split solves behind them.
 
 `fold_in_exact` over every row of a training set, field after field, is exact coordinate-ascent variational inference
 on one objective J ("Exact sweeps"): each call is the exact minimiser of J over one field's factors.  This
@@ -11,6 +12,13 @@ module holds what such a sweep needs beyond foldin.run_exact:
 
 Entities with more rows than the plan's threshold go through vfm_foldin_solve_split_f32 (their system assembled by a
 workgroup per chunk of rows), the others through vfm_foldin_solve_f32, unchanged.
+
+For a 'class' model the same plan runs the Jaakkola-Jordan bound's rounds ("Bound sweeps"): light
+entities through vfm_foldin_bound_f32, unchanged, heavy ones through vfm_foldin_bound_split_f32;
+
+  bound_objective  J of fit_bound, from the same moments
+  update_bias_bound  the global bias' exact block minimiser under the bound at the current xi
+  fit_bound        the sweeps
 """
 from __future__ import annotations
 
@@ -63,10 +71,12 @@ class SweepPlan:
     sorted (stably) by (split or not, folded id), so that the light entities come first with a contiguous row_ptr and the
     heavy ones after; the partner tuples and each row's tuple; the heavy entities' chunk table, cut in groups whose
     workspace stays under max_workspace_bytes.  Building it reads the row counts back once; running it reads nothing
-    back.  x, y: as foldin.check_args_exact returns them."""
+    back.  x, y: as foldin.check_args_exact returns them.  The plan does not depend on the likelihood but for the size
+    of a group: bound=True sizes the groups by the workspace of the split bound rounds (run_bound) instead of the split
+    exact solve's (run)."""
 
     def __init__(self, model, x, y, field, split_rows=None, chunk_rows=2048, max_workspace_bytes=MAX_WORKSPACE_BYTES,
-                 lds_dim=-1):
+                 lds_dim=-1, bound=False):
         self.field, self.d, self.lds_dim = int(field), model.d, int(lds_dim)
         self.threshold = resolve_split_rows(split_rows, model.d)
         self.chunk_rows = check_chunk_rows(chunk_rows)
@@ -98,8 +108,12 @@ class SweepPlan:
         if self.n_light == self.E:
             return
         first = np.concatenate([[0], np.cumsum(cnt)])[:-1]
-        wsb = _lib.load().vfm_foldin_split_workspace_bytes
         n_ops, nch = self.op_x.shape[0], (cnt + self.chunk_rows - 1) // self.chunk_rows
+        if bound:
+            n_rows, bsb = int(x.shape[0]), _lib.load().vfm_foldin_bound_split_workspace_bytes
+            wsb = lambda n_chunks, n_heavy, n_ops, d, lds_dim: bsb(n_chunks, n_heavy, n_rows, n_ops, d, lds_dim)
+        else:
+            wsb = _lib.load().vfm_foldin_split_workspace_bytes
         g0, chunks = self.n_light, 0
         bounds = []
         for g in range(self.n_light, self.E):                 # greedy: a group takes entities while its workspace fits
@@ -138,6 +152,51 @@ class SweepPlan:
                                  loss[a:b], self.field, flags, self.lds_dim, float(kl_weight))
         model.params_changed()              # (rows written outside the step kernels: derived caches are stale)
         return self.ents[self.asc], loss[self.asc], self.counts[self.asc]
+
+    def run_bound(self, model, kl_weight, n_iters, reset=False):
+        """n_iters rounds of the bound's two block minimisers for every entity of the plan, written into the model's
+        tables: the light entities by vfm_foldin_bound_f32, the heavy ones by vfm_foldin_bound_split_f32.  Returns
+        (entities [E] ascending, loss [E] = B_e, rows [E])."""
+        dev, d = model.device, self.d
+        loss = torch.empty(self.E, dtype=torch.float32, device=dev)
+        if self.E == 0:
+            return self.ents, loss, self.counts
+        o = _lib.ops()
+        model._fresh_params()
+        ent, bia, scal = model._views(model._flat)
+        flags = ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0
+        n_ops, n_rows = self.op_x.shape[0], self.ys.numel()
+        if self.n_light:
+            nl = self.n_light
+            ws = torch.empty(max(o.foldin_bound_workspace_bytes(nl, n_rows, n_ops, d, self.lds_dim), 1),
+                             dtype=torch.uint8, device=dev)
+            o.foldin_bound(self.ents[:nl], self.ptr[:nl + 1], self.ys, self.op_x, self.row_op, ent, bia, scal, ws,
+                           loss[:nl], self.field, foldin.OBJECTIVES["closed_form"], _lib.LIK_BERNOULLI, flags,
+                           self.lds_dim, float(kl_weight), int(n_iters), int(bool(reset)), foldin.MODE_FIT)
+        for a, b, cptr, tab in self.groups:
+            ws = torch.empty(max(o.foldin_bound_split_workspace_bytes(tab.shape[0], b - a, n_rows, n_ops, d,
+                                                                      self.lds_dim), 1), dtype=torch.uint8, device=dev)
+            o.foldin_bound_split(self.ents[a:b], cptr, tab, self.ys, self.op_x, self.row_op, ent, bia, scal, ws,
+                                 loss[a:b], self.field, flags, self.lds_dim, float(kl_weight), int(n_iters),
+                                 int(bool(reset)))
+        model.params_changed()              # (rows written outside the step kernels: derived caches are stale)
+        return self.ents[self.asc], loss[self.asc], self.counts[self.asc]
+
+
+def run_bound_split(model, X, y, field=0, kl_weight=1.0, n_iters=8, reset=False, split_rows="auto", chunk_rows=2048,
+                    max_workspace_bytes=MAX_WORKSPACE_BYTES, lds_dim=-1):
+    """foldin.run_bound with the entities of more than max(split_rows, d + 1) rows run by the split path; the same
+    output contract: (entities [E] ascending, loss [E] = B_e, rows [E])."""
+    x, y = foldin.check_args_bound(model, X, y, field, kl_weight, n_iters)
+    resolve_split_rows(split_rows, model.d)
+    check_chunk_rows(chunk_rows)
+    if int(lds_dim) < -1:
+        raise ValueError("lds_dim must be -1 or >= 0")
+    if int(max_workspace_bytes) < 0:
+        raise ValueError("max_workspace_bytes must be >= 0")
+    ops._need_cuda(model._flat, "the model's parameters")
+    plan = SweepPlan(model, x, y, field, split_rows, chunk_rows, int(max_workspace_bytes), lds_dim, bound=True)
+    return plan.run_bound(model, kl_weight, n_iters, reset)
 
 
 def run_exact_split(model, X, y, field=0, kl_weight=1.0, split_rows="auto", chunk_rows=2048,
@@ -273,6 +332,119 @@ def fit(model, X, y, n_sweeps=10, kl_weight=1.0, fields=None, update_scalars_=Tr
         t1.record()
         events.append((t0, t1))
         objective.append(float(objective_terms(model, x, y, seen, kl_weight)))
+        done += 1
+        if tol is not None and objective[-2] - objective[-1] <= float(tol) * abs(objective[-2]):
+            break
+    model.params_changed()
+    torch.cuda.synchronize(model.device)
+    return {"objective": objective, "sweeps": done, "ms": [a.elapsed_time(b) for a, b in events]}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 'class' models: the bound's objective, the global bias' block and the sweeps ("Bound sweeps")
+# ---------------------------------------------------------------------------------------------------------------------
+def _xi64(m, v):
+    return torch.sqrt(torch.clamp(m * m + v, min=0.0))
+
+
+def _jj_weight64(xi):
+    """w = tanh(xi / 2) / (2 xi), 1/4 - xi^2 / 48 below 1e-3: the kernels' rule."""
+    small = xi < 1e-3
+    safe = torch.where(small, torch.ones_like(xi), xi)
+    return torch.where(small, 0.25 - xi * xi / 48.0, torch.tanh(0.5 * safe) / (2.0 * safe))
+
+
+def bound_objective_terms(model, x, y, seen, kl_weight):
+    """J of fit_bound as a 0-dim fp64 tensor on the device: the rows' collapsed bound terms
+    -(y - 1/2) E f + xi / 2 + log1p(e^-xi), xi = sqrt((E f)^2 + Var f), from the predictive_moments kernel's fp32
+    moments, the KL of the entities `seen` (distinct ids) and of the global bias from the tables."""
+    d = model.d
+    ent, bia, scal = model._views(model._flat)
+    J = torch.zeros((), dtype=torch.float64, device=x.device)
+    if x.shape[0]:
+        m, v = _moments64(model, x)
+        xi = _xi64(m, v)
+        J = J + (-(y.double() - 0.5) * m + 0.5 * xi + torch.log1p(torch.exp(-xi))).sum()
+    kl = _kl64(scal[1].double(), _link64(scal[2], model.link))
+    if seen.numel():
+        e, b = ent[seen], bia[seen]
+        kl = kl + _kl64(e[:, :d].double(), _link64(e[:, d:], model.link)).sum()
+        kl = kl + _kl64(b[:, 0].double(), _link64(b[:, 1], model.link)).sum()
+    return J + float(kl_weight) * kl
+
+
+def update_bias_bound(model, x, y, kl_weight):
+    """The exact block minimiser of the bound over the global bias (mean and scale jointly) at xi of the current
+    posterior, written in place: m0 = sum_r ((y_r - 1/2) - w_r (E f_r - m0_old)) / (kl + sum_r w_r),
+    s0^2 = kl / (kl + sum_r w_r).  scalars[0] is left alone.  No readback."""
+    if x.shape[0] == 0:
+        return
+    scal = model._views(model._flat)[2]
+    kl = float(kl_weight)
+    m, v = _moments64(model, x)
+    w = _jj_weight64(_xi64(m, v))
+    den = kl + w.sum()
+    new_m0 = ((y.double() - 0.5) - w * (m - scal[1].double())).sum() / den
+    new_s0 = _inv_link64(torch.sqrt(kl / den), model.link)
+    scal[1:3] = torch.stack([new_m0, new_s0]).float()
+
+
+def check_fit_bound_args(model, X, y, n_sweeps, kl_weight, n_iters, fields, split_rows, chunk_rows, tol):
+    """Validate a fit_bound call (no GPU needed).  Returns (x, y, fields)."""
+    if model.output != "class":
+        raise ValueError("fit_bound needs a 'class' model (Bernoulli likelihood): a 'reg' model's blocks have their exact "
+                         "optimum; use fit_exact")
+    if isinstance(n_sweeps, bool) or not isinstance(n_sweeps, int) or n_sweeps < 0:
+        raise ValueError("n_sweeps must be an integer >= 0")
+    if fields is None:
+        fields = tuple(range(model.F))
+    else:
+        fields = tuple(fields)
+        for f in fields:
+            if isinstance(f, bool) or not isinstance(f, int) or not 0 <= f < model.F:
+                raise ValueError(f"fields must hold ints in [0, {model.F})")
+    resolve_split_rows(split_rows, model.d)
+    check_chunk_rows(chunk_rows)
+    if tol is not None and not float(tol) >= 0.0:
+        raise ValueError("tol must be None or >= 0")
+    x = yy = None
+    for f in range(model.F):                                  # (every column is some block's or a partner of one)
+        x, yy = foldin.check_args_bound(model, X, y, f, kl_weight, n_iters)
+    return x, yy, fields
+
+
+def bound_objective(model, X, y, kl_weight=1.0):
+    x, y, _ = check_fit_bound_args(model, X, y, 0, kl_weight, 1, None, None, 1, None)
+    ops._need_cuda(model._flat, "the model's parameters")
+    model._fresh_params()
+    return float(bound_objective_terms(model, x, y, torch.unique(x), kl_weight))
+
+
+def fit_bound(model, X, y, n_sweeps=10, kl_weight=1.0, n_iters=8, fields=None, update_bias=True, split_rows="auto",
+              chunk_rows=2048, on_step=None, tol=None, max_workspace_bytes=MAX_WORKSPACE_BYTES):
+    x, y, fields = check_fit_bound_args(model, X, y, n_sweeps, kl_weight, n_iters, fields, split_rows, chunk_rows, tol)
+    ops._need_cuda(model._flat, "the model's parameters")
+    model._fresh_params()
+    seen = torch.unique(x)
+    plans = {f: SweepPlan(model, x, y, f, split_rows, chunk_rows, max_workspace_bytes, bound=True)
+             for f in dict.fromkeys(fields)}
+    objective = [float(bound_objective_terms(model, x, y, seen, kl_weight))]
+    events = []
+    done = 0
+    for sweep in range(n_sweeps):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for f in fields:
+            plans[f].run_bound(model, kl_weight, n_iters, False)        # (from the current rows: B = J at the start)
+            if on_step is not None:
+                on_step(sweep, f)
+        if update_bias:
+            update_bias_bound(model, x, y, kl_weight)
+            if on_step is not None:
+                on_step(sweep, "bias")
+        t1.record()
+        events.append((t0, t1))
+        objective.append(float(bound_objective_terms(model, x, y, seen, kl_weight)))
         done += 1
         if tol is not None and objective[-2] - objective[-1] <= float(tol) * abs(objective[-2]):
             break
