@@ -115,6 +115,11 @@ class FoldinSplit(_Strict, C.Structure):
     ]
 
 
+# ---- the exact solves under a learnt field prior (include/vfm_prior.h): the parent calls' structs plus the prior pointer
+PRIOR_EXPORTS = ("vfm_foldin_solve_prior_f32", "vfm_foldin_solve_prior_workspace_bytes",
+                 "vfm_foldin_solve_split_prior_f32", "vfm_foldin_split_prior_workspace_bytes")
+
+
 # ---- bound fold-in for 'class' models (include/vfm_bound.h)
 BOUND_EXPORTS = ("vfm_foldin_bound_f32", "vfm_foldin_bound_workspace_bytes")
 
@@ -313,6 +318,14 @@ def load():
     lib.vfm_foldin_solve_split_f32.restype = C.c_int
     lib.vfm_foldin_split_workspace_bytes.argtypes = [i64, i64, i64, i32, i32]
     lib.vfm_foldin_split_workspace_bytes.restype = i64
+    lib.vfm_foldin_solve_prior_f32.argtypes = [C.POINTER(FoldinSolve), vp, vp]
+    lib.vfm_foldin_solve_prior_f32.restype = C.c_int
+    lib.vfm_foldin_solve_prior_workspace_bytes.argtypes = [i64, i64, i32, i32]
+    lib.vfm_foldin_solve_prior_workspace_bytes.restype = i64
+    lib.vfm_foldin_solve_split_prior_f32.argtypes = [C.POINTER(FoldinSplit), vp, vp]
+    lib.vfm_foldin_solve_split_prior_f32.restype = C.c_int
+    lib.vfm_foldin_split_prior_workspace_bytes.argtypes = [i64, i64, i64, i32, i32]
+    lib.vfm_foldin_split_prior_workspace_bytes.restype = i64
     lib.vfm_foldin_bound_f32.argtypes = [C.POINTER(FoldinBound), vp]
     lib.vfm_foldin_bound_f32.restype = C.c_int
     lib.vfm_foldin_bound_workspace_bytes.argtypes = [i64, i64, i64, i32, i32]

@@ -18,6 +18,10 @@
 //      chains in row order, the same lane groups), so the loss is comparable with vfm_foldin_f32's.
 // Every sum has a fixed order that depends on the entity's rows alone: no atomics, no host sync, the same bits
 // whichever other entities share the launch and wherever the triangle lives.
+//
+// vfm_foldin_solve_prior_f32 (include/vfm_prior.h) is the PRIOR = true instantiation of the same kernel: the folded
+// field's prior [2, d + 1] = mean | precision is staged once per workgroup in fp64 in LDS in front of solve_body's
+// vectors; the instantiation without it is the parent's, unchanged.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -26,6 +30,7 @@
 
 #include "vfm_args.hpp"
 #include "vfm_foldin.h"
+#include "vfm_prior.h"
 #include "vfm_launch.hpp"            // launch_status
 
 namespace vfm {
@@ -41,15 +46,22 @@ struct SolveArgs {
   const double* ops64;                   // [n_ops, 3, d]  M | A | C, unrounded
   const double* cm64;                    // [n_ops]        c_mean
   SolveSlabs sl;                         // the slabs and the LDS rule of the triangle
+  const float* prior;                    // [2, d + 1] mean | precision of the folded field (PRIOR instantiations only)
 };
 
-template <int W, int CPL, int LINK>
+template <int W, int CPL, int LINK, bool PRIOR>
 __global__ __launch_bounds__(FB) void k_foldin_solve(const SolveArgs s) {
 #pragma clang fp contract(on)
-  extern __shared__ double sm[];
+  extern __shared__ double sm_all[];
   const FoldArgs& a = s.f;
   const int tid = threadIdx.x;
   const int d = a.d, d1 = d + 1;
+  double* sm = sm_all + (PRIOR ? 2 * d1 : 0);              // (the prior in front: lds_doubles_prior)
+  const double* pr = PRIOR ? sm_all : nullptr;
+  if constexpr (PRIOR) {
+    stage_prior(s.prior, sm_all, d1);
+    __syncthreads();
+  }
   double* Hl = sm + 8 * d1;              // (past solve_body's vectors and fp32 parameters)
   double* Hg = s.sl.slab ? s.sl.slab + (int64_t)blockIdx.x * s.sl.slab_elems : nullptr;
   const float precf = link_f<LINK>(a.scal[0]);
@@ -67,7 +79,7 @@ __global__ __launch_bounds__(FB) void k_foldin_solve(const SolveArgs s) {
     }
     const ListRows rows{a, r0};
     // phases A-E (vfm_foldin_solve_body.hpp); the table row is written where the parameters are published
-    solve_body<W, CPL, LINK>(a, s.ops64, s.cm64, rows, n, sm, Hm, precf, prec, a.loss + g, [&](const float* pf) {
+    solve_body<W, CPL, LINK, PRIOR>(a, s.ops64, s.cm64, rows, n, sm, Hm, precf, prec, a.loss + g, [&](const float* pf) {
       for (int k = tid; k < d; k += FB) {
         a.entity[e * 2 * d + k] = pf[1 + k];
         a.entity[e * 2 * d + d + k] = pf[d1 + 1 + k];
@@ -76,15 +88,16 @@ __global__ __launch_bounds__(FB) void k_foldin_solve(const SolveArgs s) {
         a.bias[e * 2] = pf[0];
         a.bias[e * 2 + 1] = pf[d1];
       }
-    });
+    }, pr);
     __syncthreads();                     // (pf is rewritten by the next entity)
   }
 }
 
+template <bool PRIOR>
 void launch(const FShape& f, bool sp, const SolveArgs& s, unsigned grid, size_t shm, hipStream_t st) {
   for_link(sp, [&](auto link) {
     for_shape(f, [&](auto w, auto c) {
-      const auto k = k_foldin_solve<decltype(w)::value, decltype(c)::value, decltype(link)::value>;
+      const auto k = k_foldin_solve<decltype(w)::value, decltype(c)::value, decltype(link)::value, PRIOR>;
       // (more than 64 KiB of dynamic LDS: state the size; a runtime that needs no opt-in ignores it)
       (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
       (void)hipGetLastError();
@@ -96,6 +109,8 @@ void launch(const FShape& f, bool sp, const SolveArgs& s, unsigned grid, size_t 
 }  // namespace
 }  // namespace vfm
 
+static int solve_call(const vfm_foldin_solve_t* p, const float* prior, void* stream);
+
 extern "C" {
 
 int64_t vfm_foldin_solve_workspace_bytes(int64_t E, int64_t n_ops, int32_t d, int32_t lds_dim) {
@@ -103,7 +118,20 @@ int64_t vfm_foldin_solve_workspace_bytes(int64_t E, int64_t n_ops, int32_t d, in
   return vfm::off_slabs(n_ops, d) + vfm::slabs_bytes(E, d, lds_dim);
 }
 
-int vfm_foldin_solve_f32(const vfm_foldin_solve_t* p, void* stream) {
+int64_t vfm_foldin_solve_prior_workspace_bytes(int64_t E, int64_t n_ops, int32_t d, int32_t lds_dim) {
+  return vfm_foldin_solve_workspace_bytes(E, n_ops, d, lds_dim);       // (the prior lives in LDS, not in the workspace)
+}
+
+int vfm_foldin_solve_f32(const vfm_foldin_solve_t* p, void* stream) { return solve_call(p, nullptr, stream); }
+
+int vfm_foldin_solve_prior_f32(const vfm_foldin_solve_t* p, const float* prior, void* stream) {
+  return solve_call(p, prior, stream);
+}
+
+}  // extern "C"
+
+// both entry points: prior == NULL is vfm_foldin_solve_f32
+static int solve_call(const vfm_foldin_solve_t* p, const float* prior, void* stream) {
   using vfm::fail;
   if (!p) return fail(VFM_E_INVALID, "vfm_foldin_solve_f32: NULL argument struct");
   if (p->T < 1) return fail(VFM_E_INVALID, "T < 1");
@@ -146,13 +174,13 @@ int vfm_foldin_solve_f32(const vfm_foldin_solve_t* p, void* stream) {
   s.cm64 = (double*)(w + vfm::off_cm64(p->n_ops, p->d));
   const unsigned grid =
       vfm::place_slabs(p->d, p->lds_dim, p->E, w + vfm::off_slabs(p->n_ops, p->d), (int64_t)1 << 20, s.sl);
-  const size_t shm = (size_t)vfm::lds_doubles(p->d, s.sl.cap_dim) * 8;
+  s.prior = prior;
+  const size_t shm = (size_t)(prior ? vfm::lds_doubles_prior(p->d, s.sl.cap_dim) : vfm::lds_doubles(p->d, s.sl.cap_dim)) * 8;
 
   if (p->n_ops > 0) {
     if (int rc = vfm::launch_solve_preps(sp, a, p->n_ops, p->op_x, w, st)) return rc;
   }
-  vfm::launch(f, sp, s, grid, shm, st);
+  if (prior) vfm::launch<true>(f, sp, s, grid, shm, st);
+  else vfm::launch<false>(f, sp, s, grid, shm, st);
   return launch_status("k_foldin_solve");
 }
-
-}  // extern "C"

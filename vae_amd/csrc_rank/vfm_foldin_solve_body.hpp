@@ -31,6 +31,8 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 
 // LDS of a block in doubles: seven vectors of d + 1, the fp32 parameters (2 (d + 1) floats), the triangle
 __host__ __device__ inline int64_t lds_doubles(int d, int cap_dim) { return 8 * (int64_t)(d + 1) + tri(cap_dim); }
+// ... of a block that solves under a field prior (include/vfm_prior.h): the prior's mean | precision [2, d + 1] in front
+__host__ __device__ inline int64_t lds_doubles_prior(int d, int cap_dim) { return 2 * (int64_t)(d + 1) + lds_doubles(d, cap_dim); }
 
 template <int LINK>
 __device__ __forceinline__ double link_d(float s) { return LINK == LINK_ABS ? fabs((double)s) : softplus_d((double)s); }
@@ -115,11 +117,27 @@ __device__ __forceinline__ void chol_solve(double* Hm, double* yv, double* dv, d
   }
 }
 
+// the field prior of a workgroup (PRIOR instantiations): prior [2, d + 1] fp32 = mean | precision into pr in fp64, by the
+// whole workgroup; the caller puts the barrier
+__device__ __forceinline__ void stage_prior(const float* __restrict__ prior, double* pr, int d1) {
+  for (int c = threadIdx.x; c < 2 * d1; c += FB) pr[c] = (double)prior[c];
+}
+
+// KL(N(mu, sg^2) || N(m, 1 / lam)) = kl_std_normal(sqrt(lam) (mu - m), sqrt(lam) sg); at m = 0, lam = 1 its bits
+__device__ __forceinline__ float kl_prior_normal(float mu, float sg, float m, float sl) {
+  return kl_std_normal(sl * (mu - m), sl * sg);
+}
+
 // phase D's rounding: coordinate c's mean th and its scale from the closed form sigma^2 = kl / (kl + prec SB), to fp32
-template <int LINK>
-__device__ __forceinline__ void put_params(float* pf, int d1, int c, double th, double kl, double prec, double SB) {
+// (PRIOR: kl / (kll + prec SB), kll = kl lam_c)
+template <int LINK, bool PRIOR = false>
+__device__ __forceinline__ void put_params(float* pf, int d1, int c, double th, double kl, double prec, double SB,
+                                           double kll = 0.) {
 #pragma clang fp contract(on)
-  const double sg = sqrt(kl / (kl + prec * SB));
+  double den;
+  if constexpr (PRIOR) den = kll + prec * SB;
+  else den = kl + prec * SB;
+  const double sg = sqrt(kl / den);
   pf[c] = (float)th;
   pf[d1 + c] = (float)(LINK == LINK_ABS ? sg : log(expm1(sg)));
 }
@@ -132,11 +150,14 @@ __device__ __forceinline__ void put_params(float* pf, int d1, int c, double th, 
 // (float*)(sm + 7 (d + 1)): [mu_w, mu [d] | s_w, s [d]]; after the barrier that publishes them every thread calls
 // store() (the fold-in writes the table row there, a session its out_theta); then wave 0 evaluates L_e at them into
 // *loss.  The caller puts a barrier before pf or any other LDS of the block is written again.
+// PRIOR (include/vfm_prior.h): the entity's prior is N(m_c, 1 / lam_c) per coordinate, pr = m [d + 1] | lam [d + 1] in
+// LDS (stage_prior): D_c = kl lam_c + prec SA_c, b_c += kl lam_c m_c, sigma_c^2 = kl / (kl lam_c + prec SB_c), and the
+// KL of the loss is to that prior.  At m = 0, lam = 1 every expression rounds as with PRIOR off.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int W, int CPL, int LINK, class Rows, class Store>
+template <int W, int CPL, int LINK, bool PRIOR = false, class Rows, class Store>
 __device__ __forceinline__ void solve_body(const FoldArgs& a, const double* ops64, const double* cm64, const Rows& rows,
                                            int64_t n, double* sm, double* Hm, float precf, double prec, float* loss,
-                                           Store&& store) {
+                                           Store&& store, const double* pr = nullptr) {
 #pragma clang fp contract(on)
   constexpr int DP = W * CPL;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -172,7 +193,15 @@ __device__ __forceinline__ void solve_body(const FoldArgs& a, const double* ops6
         bM += t * M;
       }
     }
-    const double D = kl + prec * SA, b = prec * (bM - 0.5 * SC);
+    double D, b;
+    if constexpr (PRIOR) {
+      const double kll = kl * pr[d1 + c], b0 = prec * (bM - 0.5 * SC);
+      D = kll + prec * SA;
+      b = b0 + kll * pr[c];
+    } else {
+      D = kl + prec * SA;
+      b = prec * (bM - 0.5 * SC);
+    }
     Dd[c] = D;
     Di[c] = 1.0 / D;
     bv[c] = dual ? b / D : b;
@@ -239,7 +268,8 @@ __device__ __forceinline__ void solve_body(const FoldArgs& a, const double* ops6
     } else {
       th = xv[c];
     }
-    put_params<LINK>(pf, d1, c, th, kl, prec, SBd[c]);
+    if constexpr (PRIOR) put_params<LINK, true>(pf, d1, c, th, kl, prec, SBd[c], kl * pr[d1 + c]);
+    else put_params<LINK>(pf, d1, c, th, kl, prec, SBd[c]);
   }
   __syncthreads();
   store(pf);
@@ -273,10 +303,15 @@ __device__ __forceinline__ void solve_body(const FoldArgs& a, const double* ops6
 #pragma unroll
     for (int j = 0; j < CPL; ++j) {
       vq += fmaf(mu[j] * mu[j], SA[j], fmaf(sg[j] * sg[j], SB[j], mu[j] * SC[j]));
-      if (vk[j]) klq += kl_std_normal(mu[j], sg[j]);
+      if constexpr (PRIOR) {
+        if (vk[j]) klq += kl_prior_normal(mu[j], sg[j], (float)pr[1 + j * W + l], sqrtf((float)pr[d1 + 1 + j * W + l]));
+      } else {
+        if (vk[j]) klq += kl_std_normal(mu[j], sg[j]);
+      }
     }
     vq = group_sum<W>(vq);
-    klq = group_sum<W>(klq) + kl_std_normal(muw, sgw);
+    if constexpr (PRIOR) klq = group_sum<W>(klq) + kl_prior_normal(muw, sgw, (float)pr[0], sqrtf((float)pr[d1]));
+    else klq = group_sum<W>(klq) + kl_std_normal(muw, sgw);
     const double sumv = (double)Scv + (double)n * sgw * sgw + vq;
     const double lsum = 0.5 * precf * ((double)rsq + sumv) + (double)n * ((double)LOG_2PI_HALF - 0.5 * log((double)precf));
     if (lane == 0) *loss = (float)(lsum + (double)a.klw * (double)klq);

@@ -15,6 +15,11 @@
 //                      + mu SC) at the written fp32 row, fold_stage_rows and the residual chain of solve_body's phase E
 //   k_split_loss_sum   a thread per entity: the shares in chunk order in fp64, the sigma_w, precision and KL terms
 // Every sum has a fixed order that depends on the entity's rows, the chunk length and d alone: no atomics, no host sync.
+//
+// vfm_foldin_solve_split_prior_f32 (include/vfm_prior.h) runs the PRIOR = true instantiations of k_split_solve and
+// k_split_loss_sum: the folded field's prior [2, d + 1] = mean | precision staged once per workgroup in LDS
+// (D = kl lam + prec SA, b += kl lam m, the scales and the KL to that prior).  The preps, k_split_assemble and
+// k_split_loss do not depend on the prior; the instantiations without it are the parent's, unchanged.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -23,6 +28,7 @@
 
 #include "vfm_args.hpp"
 #include "vfm_sweep.h"
+#include "vfm_prior.h"
 #include "vfm_launch.hpp"            // launch_status
 
 namespace vfm {
@@ -45,6 +51,7 @@ struct SplitArgs {
   double* lpart;                         // [n_chunks]     the chunks' shares of the loss
   SolveSlabs sl;                         // the slabs of k_split_solve's workgroups and the LDS rule of the triangle
   int64_t n_ops, n_chunks, part_elems;
+  const float* prior;                    // [2, d + 1] mean | precision of the folded field (PRIOR instantiations only)
 };
 
 __host__ __device__ inline int64_t part_doubles(int d) { return tri(d + 1) + 4 * (int64_t)d + 3; }
@@ -150,13 +157,19 @@ __global__ __launch_bounds__(FB) void k_split_assemble(const SplitArgs s) {
   }
 }
 
-template <int LINK>
+template <int LINK, bool PRIOR>
 __global__ __launch_bounds__(FB) void k_split_solve(const SplitArgs s) {
 #pragma clang fp contract(on)
-  extern __shared__ double sm[];
+  extern __shared__ double sm_all[];
   const FoldArgs& a = s.f;
   const int tid = threadIdx.x;
   const int d = a.d, d1 = d + 1;
+  double* sm = sm_all + (PRIOR ? 2 * d1 : 0);              // (the prior in front: lds_doubles_prior)
+  const double* pr = sm_all;                               // (PRIOR only) m [d + 1] | lam [d + 1]
+  if constexpr (PRIOR) {
+    stage_prior(s.prior, sm_all, d1);
+    __syncthreads();
+  }
   double* Dd = sm;                       // solve_body's layout: D | . | . | right-hand side | 1 / L_jj | solution | SB | fp32
   double* yv = Dd + 3 * d1;
   double* dv = yv + d1;
@@ -184,8 +197,14 @@ __global__ __launch_bounds__(FB) void k_split_solve(const SplitArgs s) {
         bM += V[2 * d1 + c];
         if (c > 0) SC += V[3 * d1 + c - 1];
       }
-      Dd[c] = kl + prec * SA;
-      yv[c] = prec * (bM - 0.5 * SC);
+      if constexpr (PRIOR) {
+        const double kll = kl * pr[d1 + c], b0 = prec * (bM - 0.5 * SC);
+        Dd[c] = kll + prec * SA;
+        yv[c] = b0 + kll * pr[c];
+      } else {
+        Dd[c] = kl + prec * SA;
+        yv[c] = prec * (bM - 0.5 * SC);
+      }
       SBd[c] = SB;
     }
     __syncthreads();
@@ -198,7 +217,10 @@ __global__ __launch_bounds__(FB) void k_split_solve(const SplitArgs s) {
     }
     __syncthreads();
     chol_solve(Hm, yv, dv, xv, d1);
-    for (int c = tid; c < d1; c += FB) put_params<LINK>(pf, d1, c, xv[c], kl, prec, SBd[c]);
+    for (int c = tid; c < d1; c += FB) {
+      if constexpr (PRIOR) put_params<LINK, true>(pf, d1, c, xv[c], kl, prec, SBd[c], kl * pr[d1 + c]);
+      else put_params<LINK>(pf, d1, c, xv[c], kl, prec, SBd[c]);
+    }
     __syncthreads();
     for (int k = tid; k < d; k += FB) {
       a.entity[e * 2 * d + k] = pf[1 + k];
@@ -266,11 +288,19 @@ __global__ __launch_bounds__(64) void k_split_loss(const SplitArgs s) {
   }
 }
 
-template <int LINK>
+template <int LINK, bool PRIOR>
 __global__ __launch_bounds__(FB) void k_split_loss_sum(const SplitArgs s) {
 #pragma clang fp contract(on)
   const FoldArgs& a = s.f;
   const int d = a.d;
+  __shared__ float prs[PRIOR ? 2 * (VFM_FOLDIN_MAX_D + 1) : 1];          // (PRIOR) m [d + 1] | sqrt(lam) [d + 1]
+  if constexpr (PRIOR) {
+    for (int c = threadIdx.x; c <= d; c += FB) {
+      prs[c] = s.prior[c];
+      prs[d + 1 + c] = sqrtf(s.prior[d + 1 + c]);
+    }
+    __syncthreads();
+  }
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= a.E) return;
   const int64_t e = a.ent[g];
@@ -290,8 +320,15 @@ __global__ __launch_bounds__(FB) void k_split_loss_sum(const SplitArgs s) {
   }
   const float precf = link_f<LINK>(a.scal[0]);
   const float muw = a.bias[e * 2], sgw = link_f<LINK>(a.bias[e * 2 + 1]);
-  double klq = kl_std_normal(muw, sgw);
-  for (int k = 0; k < d; ++k) klq += kl_std_normal(a.entity[e * 2 * d + k], link_f<LINK>(a.entity[e * 2 * d + d + k]));
+  double klq;
+  if constexpr (PRIOR) {
+    klq = kl_prior_normal(muw, sgw, prs[0], prs[d + 1]);
+    for (int k = 0; k < d; ++k)
+      klq += kl_prior_normal(a.entity[e * 2 * d + k], link_f<LINK>(a.entity[e * 2 * d + d + k]), prs[1 + k], prs[d + 2 + k]);
+  } else {
+    klq = kl_std_normal(muw, sgw);
+    for (int k = 0; k < d; ++k) klq += kl_std_normal(a.entity[e * 2 * d + k], link_f<LINK>(a.entity[e * 2 * d + d + k]));
+  }
   const double sumv = sum + (double)n * sgw * sgw;
   const double lsum = 0.5 * precf * sumv + (double)n * ((double)LOG_2PI_HALF - 0.5 * log((double)precf));
   a.loss[g] = (float)(lsum + (double)a.klw * klq);
@@ -302,6 +339,8 @@ inline int64_t lpart_bytes(int64_t n_chunks) { return round_up(n_chunks * 8, 256
 
 }  // namespace
 }  // namespace vfm
+
+static int split_call(const vfm_foldin_split_t* p, const float* prior, void* stream);
 
 extern "C" {
 
@@ -314,7 +353,22 @@ int64_t vfm_foldin_split_workspace_bytes(int64_t n_chunks, int64_t n_heavy, int6
          vfm::slabs_bytes(n_heavy, d, lds_dim);
 }
 
-int vfm_foldin_solve_split_f32(const vfm_foldin_split_t* p, void* stream) {
+int64_t vfm_foldin_split_prior_workspace_bytes(int64_t n_chunks, int64_t n_heavy, int64_t n_ops, int32_t d,
+                                               int32_t lds_dim) {
+  // (the prior lives in LDS, not in the workspace)
+  return vfm_foldin_split_workspace_bytes(n_chunks, n_heavy, n_ops, d, lds_dim);
+}
+
+int vfm_foldin_solve_split_f32(const vfm_foldin_split_t* p, void* stream) { return split_call(p, nullptr, stream); }
+
+int vfm_foldin_solve_split_prior_f32(const vfm_foldin_split_t* p, const float* prior, void* stream) {
+  return split_call(p, prior, stream);
+}
+
+}  // extern "C"
+
+// both entry points: prior == NULL is vfm_foldin_solve_split_f32
+static int split_call(const vfm_foldin_split_t* p, const float* prior, void* stream) {
   using vfm::fail;
   if (!p) return fail(VFM_E_INVALID, "vfm_foldin_solve_split_f32: NULL argument struct");
   if (p->T < 1) return fail(VFM_E_INVALID, "T < 1");
@@ -363,7 +417,8 @@ int vfm_foldin_solve_split_f32(const vfm_foldin_split_t* p, void* stream) {
   const unsigned grid_e =
       vfm::place_slabs(p->d, p->lds_dim, p->E, w + off_lpart + vfm::lpart_bytes(p->n_chunks), gcap, s.sl);
   const unsigned grid_c = (unsigned)(p->n_chunks < gcap ? p->n_chunks : gcap);
-  const size_t shm = (size_t)vfm::lds_doubles(p->d, s.sl.cap_dim) * 8;
+  s.prior = prior;
+  const size_t shm = (size_t)(prior ? vfm::lds_doubles_prior(p->d, s.sl.cap_dim) : vfm::lds_doubles(p->d, s.sl.cap_dim)) * 8;
 
   if (p->n_ops > 0) {
     if (int rc = vfm::launch_solve_preps(sp, a, p->n_ops, p->op_x, w, st)) return rc;
@@ -373,7 +428,7 @@ int vfm_foldin_solve_split_f32(const vfm_foldin_split_t* p, void* stream) {
     if (int rc = launch_status("k_split_assemble")) return rc;
   }
   vfm::for_link(sp, [&](auto link) {
-    const auto k = vfm::k_split_solve<decltype(link)::value>;
+    const auto k = prior ? vfm::k_split_solve<decltype(link)::value, true> : vfm::k_split_solve<decltype(link)::value, false>;
     // (more than 64 KiB of dynamic LDS: state the size; a runtime that needs no opt-in ignores it)
     (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
     (void)hipGetLastError();
@@ -390,10 +445,8 @@ int vfm_foldin_solve_split_f32(const vfm_foldin_split_t* p, void* stream) {
     if (int rc = launch_status("k_split_loss")) return rc;
   }
   vfm::for_link(sp, [&](auto link) {
-    hipLaunchKernelGGL(vfm::k_split_loss_sum<decltype(link)::value>, dim3((unsigned)((p->E + vfm::FB - 1) / vfm::FB)),
-                       dim3(vfm::FB), 0, st, s);
+    const auto k = prior ? vfm::k_split_loss_sum<decltype(link)::value, true> : vfm::k_split_loss_sum<decltype(link)::value, false>;
+    hipLaunchKernelGGL(k, dim3((unsigned)((p->E + vfm::FB - 1) / vfm::FB)), dim3(vfm::FB), 0, st, s);
   });
   return launch_status("k_split_loss_sum");
 }
-
-}  // extern "C"

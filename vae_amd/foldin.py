@@ -154,10 +154,14 @@ def check_args_exact(model, X, y, field, kl_weight=1.0):
     return x, y
 
 
-def run_exact(model, X, y, field=0, kl_weight=1.0, lds_dim=-1):
-    """One exact fold-in launch (vfm_foldin_solve_f32): the closed-form optimum of every folded entity.  Returns
+def run_exact(model, X, y, field=0, kl_weight=1.0, lds_dim=-1, priors=None):
+    """One exact fold-in launch (vfm_foldin_solve_f32): the closed-form optimum of every folded entity.  priors (a
+    sweep.GroupPriors): under the folded field's prior, by vfm_foldin_solve_prior_f32 (include/vfm_prior.h).  Returns
     (entities [E], loss [E], rows [E])."""
     x, y = check_args_exact(model, X, y, field, kl_weight)
+    if priors is not None:
+        from . import sweep
+        sweep.check_priors(model, priors)
     _check_lds_dim(lds_dim)
     ops._need_cuda(model._flat, "the model's parameters")
     dev, d = model.device, model.d
@@ -172,11 +176,39 @@ def run_exact(model, X, y, field=0, kl_weight=1.0, lds_dim=-1):
                      device=dev)
     model._fresh_params()
     ent, bia, scal = model._views(model._flat)
-    o.foldin_solve(ents, ptr, ys, op_x, row_op, ent, bia, scal, ws, loss, int(field), OBJECTIVES["closed_form"],
-                   _lib.LIK_NORMAL, ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, int(lds_dim),
-                   float(kl_weight))
+    flags = ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0
+    if priors is None:
+        o.foldin_solve(ents, ptr, ys, op_x, row_op, ent, bia, scal, ws, loss, int(field), OBJECTIVES["closed_form"],
+                       _lib.LIK_NORMAL, flags, int(lds_dim), float(kl_weight))
+    else:
+        o.foldin_solve_prior(ents, ptr, ys, op_x, row_op, ent, bia, scal, ws, loss, priors.row(int(field)).to(dev),
+                             int(field), OBJECTIVES["closed_form"], _lib.LIK_NORMAL, flags, int(lds_dim),
+                             float(kl_weight))
     model.params_changed()              # (rows written outside the step kernels: derived caches are stale)
     return ents, loss, counts
+
+
+def objective_under_prior(model, ents, loss, grad, prior, kl_weight):
+    """fold_in_objective's closed-form L_e and gradient moved from the N(0, 1) prior to `prior` [2, d + 1]: the rows'
+    term is the kernel's; the KL terms differ by kl_weight (KL(q || N(m, 1 / lam)) - KL(q || N(0, 1))) per coordinate,
+    O(E d) elementwise work taken in torch fp64 on the device from the table rows.  Returns (loss [E] fp32,
+    grad [E, 2d + 2] fp32 = dL/d[mu | s | mu_w | s_w])."""
+    d, kl = model.d, float(kl_weight)
+    ent, bia, _ = model._views(model._flat)
+    m, lam = prior[0].double(), prior[1].double()
+    m = torch.cat([m[1:], m[:1]])                              # (the gradient's order: factors, then the weight)
+    lam = torch.cat([lam[1:], lam[:1]])
+    mu = torch.cat([ent[ents, :d], bia[ents, :1]], 1).double()
+    s = torch.cat([ent[ents, d:], bia[ents, 1:]], 1).double()
+    sg = s.abs() if model.link == "abs" else torch.nn.functional.softplus(s)
+    dsg = torch.sign(s) if model.link == "abs" else torch.sigmoid(s)
+    dkl = 0.5 * ((lam - 1.0) * sg * sg + lam * (mu - m) ** 2 - mu * mu - torch.log(lam))
+    g_mu = kl * (lam * (mu - m) - mu)
+    g_s = kl * (lam - 1.0) * sg * dsg
+    loss = (loss.double() + kl * dkl.sum(1)).float()
+    g = grad.double()
+    g = g + torch.cat([g_mu[:, :d], g_s[:, :d], g_mu[:, d:], g_s[:, d:]], 1)
+    return loss, g.float()
 
 
 def check_args_bound(model, X, y, field, kl_weight=1.0, n_iters=8):

@@ -1295,7 +1295,7 @@ class VFM(nn.Module):
 
     @torch.no_grad()
     def fold_in_exact(self, X, y, field: int = 0, kl_weight: float = 1.0, split_rows=None, chunk_rows: int = 2048,
-                      max_workspace_bytes: int = 1 << 30):
+                      max_workspace_bytes: int = 1 << 30, priors=None):
         """fold_in's closed-form objective solved exactly: the entities of X[:, field] get the global optimum of L_e
         itself, in one launch (include/vfm_foldin.h: vfm_foldin_solve_f32; DESIGN.md §4 "Exact fold-in").  No lr, no
         n_steps, no reset: with everything else frozen L_e is quadratic in the means (one symmetric positive definite
@@ -1313,14 +1313,19 @@ class VFM(nn.Module):
         are cut in chunks of chunk_rows, a workgroup per chunk assembles its share of the system and a workgroup per
         entity adds the shares in chunk order and solves.  The other entities get the bits they get with None; a split
         entity's bits depend on its rows, chunk_rows and d alone.  The chunks' shares of one call take at most
-        max_workspace_bytes: the split entities are processed in as many groups as that needs, with the same result."""
+        max_workspace_bytes: the split entities are processed in as many groups as that needs, with the same result.
+
+        priors: None, or a sweep.GroupPriors: the entities are solved under their field's prior N(mean, 1 / prec) per
+        coordinate in place of N(0, 1) (include/vfm_prior.h; DESIGN.md §4 "Hierarchical sweeps"), and the loss carries
+        the KL to it; an entity's bits then depend on the prior too.  With the standard prior (0, 1) the rows and the
+        losses are those of priors=None, bit for bit.  Non-finite values or prec <= 0: ValueError."""
         from . import foldin, sweep
         if split_rows is None:
             sweep.check_chunk_rows(chunk_rows)
-            ents, loss, rows = foldin.run_exact(self, X, y, field, kl_weight)
+            ents, loss, rows = foldin.run_exact(self, X, y, field, kl_weight, priors=priors)
         else:
             ents, loss, rows = sweep.run_exact_split(self, X, y, field, kl_weight, split_rows, chunk_rows,
-                                                     max_workspace_bytes)
+                                                     max_workspace_bytes, priors=priors)
         return {"entities": ents, "loss": loss, "rows": rows}
 
     @torch.no_grad()
@@ -1370,18 +1375,21 @@ class VFM(nn.Module):
         return {"entities": ents, "loss": loss, "rows": rows}
 
     @torch.no_grad()
-    def exact_objective(self, X, y, kl_weight: float = 1.0) -> float:
+    def exact_objective(self, X, y, kl_weight: float = 1.0, priors=None) -> float:
         """The objective J of fit_exact at the current parameters ("Exact sweeps"): over the rows of X the
         expected negative log likelihood 1/2 prec ((y - E pred)^2 + Var pred) - 1/2 log prec + 1/2 log 2 pi, plus
         kl_weight times the KL to N(0, 1) of the factors of every entity that occurs in X (embedding and first-order
         weight) and of the global bias.  The per-row moments are the predictive_moments kernel's; the sums and the KL
-        terms are taken in fp64 on the device.  'reg' models only."""
+        terms are taken in fp64 on the device.  'reg' models only.  priors (a sweep.GroupPriors): every entity's KL is
+        to its field's N(mean, 1 / prec), 1/2 (lam s^2 + lam (mu - m)^2 - 1 - log(lam s^2)) per coordinate; the global
+        bias keeps N(0, 1)."""
         from . import sweep
-        return sweep.exact_objective(self, X, y, kl_weight)
+        return sweep.exact_objective(self, X, y, kl_weight, priors)
 
     @torch.no_grad()
     def fit_exact(self, X, y, n_sweeps: int = 10, kl_weight: float = 1.0, fields=None, update_scalars: bool = True,
-                  split_rows="auto", chunk_rows: int = 2048, on_step=None, tol: Optional[float] = None):
+                  split_rows="auto", chunk_rows: int = 2048, on_step=None, tol: Optional[float] = None, priors=None,
+                  learn_priors: bool = False, learn_mean: bool = True, prec_min: float = 1e-4, prec_max: float = 1e4):
         """Train by exact coordinate ascent on exact_objective: no learning rate, no sampling.  One sweep solves, for each
         field of `fields` in turn (default: all, in order), the closed-form optimum of every entity of that field over
         all rows of X with the rest of the model frozen (fold_in_exact's solve: the exact minimiser of J over that
@@ -1395,9 +1403,26 @@ class VFM(nn.Module):
         'reg' models only, kl_weight > 0, ids as fold_in checks them for every field (else ValueError).  The training
         Adam state and the save_weights snapshots are not touched.
         Returns dict(objective = J before the first block and after every sweep, sweeps = the number run, ms = each
-        sweep's device time from HIP events)."""
+        sweep's device time from HIP events).
+
+        Hierarchical sweeps.  priors: a sweep.GroupPriors; every field block then solves under its
+        field's prior N(mean, 1 / prec) per coordinate and J is exact_objective(priors=priors).  learn_priors=True:
+        after each field's entity block its prior block sets that field's prior to the exact minimiser of J over the
+        entities of the field that occur in X: mean* = the mean of their mu, 1 / prec* = the mean of sigma^2 +
+        (mu - mean*)^2 (learn_mean=False keeps the means and takes 1 / prec* around them); in torch fp64 on the device
+        from the table rows, no readback, rounded to fp32 when stored; on_step(sweep, ("prior", field)) follows it.
+        `priors` is updated in place; with priors=None one is created at (0, 1), and the result holds it under
+        "priors" either way.  prec_min, prec_max: prec* is clamped to [prec_min, prec_max].  They are conditions, not
+        tuned values: they only keep a precision representable in the fp32 prior tables (a field whose entities all
+        collapse onto one point would ask for an infinite one); KL is unimodal in 1 / prec, so the clamped value is
+        the constrained minimiser and J still does not rise.  "clamped" in the result counts, per field, the
+        (sweep, coordinate) pairs at which a clamp bound.  The global bias keeps N(0, 1).  learn_priors=False with
+        priors given leaves them untouched.  Sessions, ranking, the bound paths and the Adam trainers do not read
+        priors."""
         from . import sweep
-        return sweep.fit(self, X, y, n_sweeps, kl_weight, fields, update_scalars, split_rows, chunk_rows, on_step, tol)
+        return sweep.fit(self, X, y, n_sweeps, kl_weight, fields, update_scalars, split_rows, chunk_rows, on_step, tol,
+                         priors=priors, learn_priors=learn_priors, learn_mean=learn_mean, prec_min=prec_min,
+                         prec_max=prec_max)
 
     @torch.no_grad()
     def bound_objective(self, X, y, kl_weight: float = 1.0) -> float:
@@ -1440,13 +1465,23 @@ class VFM(nn.Module):
 
     @torch.no_grad()
     def fold_in_objective(self, X, y, field: int = 0, objective: Optional[str] = None, n_samples: int = 1,
-                          seed: int = 0, step: int = 0, kl_weight: float = 1.0):
+                          seed: int = 0, step: int = 0, kl_weight: float = 1.0, priors=None):
         """fold_in's objective L_e and its gradient at the current parameters, nothing updated (tests, diagnostics).
         step: the draw key t of the sampled objective.  Returns (loss [E], grads) with grads = dict(entities [E],
-        entity [E, 2d] = dL/d[mu | s], bias [E, 2] = dL/d[mu_w, s_w])."""
+        entity [E, 2d] = dL/d[mu | s], bias [E, 2] = dL/d[mu_w, s_w]).
+        priors (a sweep.GroupPriors; the closed-form objective of a 'reg' model only, else ValueError): L_e with the KL
+        to the folded field's prior, the objective fold_in_exact(priors=) minimises.  The rows' term is the kernel's;
+        the difference of the two KL terms, O(E d) elementwise, is added in fp64 on the device."""
         from . import foldin
+        if priors is not None:
+            from . import sweep
+            if self.output != "reg" or objective not in (None, "closed_form"):
+                raise ValueError("priors need the closed-form objective of a 'reg' model")
+            sweep.check_priors(self, priors)
         ents, loss, _, g = foldin.run(self, X, y, field, objective, n_samples, seed, kl_weight,
                                       mode=foldin.MODE_OBJECTIVE, t0=int(step))
+        if priors is not None and ents.numel():
+            loss, g = foldin.objective_under_prior(self, ents, loss, g, priors.row(int(field)).to(self.device), kl_weight)
         d = self.d
         return loss, {"entities": ents, "entity": g[:, :2 * d], "bias": g[:, 2 * d:]}
 

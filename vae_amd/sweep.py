@@ -13,6 +13,10 @@ module holds what such a sweep needs beyond foldin.run_exact:
 Entities with more rows than the plan's threshold go through vfm_foldin_solve_split_f32 (their system assembled by a
 workgroup per chunk of rows), the others through vfm_foldin_solve_f32, unchanged.
 
+With a GroupPriors (include/vfm_prior.h; DESIGN.md §4, "Hierarchical sweeps") every field has a Gaussian prior
+N(m, 1 / lam) per coordinate in place of N(0, 1): the same plan solves under it (vfm_foldin_solve_prior_f32,
+vfm_foldin_solve_split_prior_f32), update_prior is the prior's own exact block minimiser, and J carries the KL to it.
+
 For a 'class' model the same plan runs the Jaakkola-Jordan bound's rounds ("Bound sweeps"): light
 entities through vfm_foldin_bound_f32, unchanged, heavy ones through vfm_foldin_bound_split_f32;
 
@@ -31,6 +35,80 @@ from . import _lib, foldin, ops, rank
 
 LOG_2PI_HALF = 0.5 * math.log(2.0 * math.pi)
 MAX_WORKSPACE_BYTES = 1 << 30
+
+
+class GroupPriors:
+    """The Gaussian prior of every field of a 'reg' model: mean [F, d + 1] and prec [F, d + 1] fp32 (column 0: the
+    first-order weight, 1 .. d: the factors), N(mean, 1 / prec) per coordinate.  It starts at (0, 1), the N(0, 1) every
+    other path of the package assumes.  Held outside the model, like a session's theta: a model file stays a model file;
+    state_dict / load_state_dict keep it beside one."""
+
+    def __init__(self, F, d, device="cpu"):
+        if isinstance(F, bool) or isinstance(d, bool) or int(F) != F or int(d) != d or F < 1 or d < 1:
+            raise ValueError("GroupPriors(F, d): F and d must be integers >= 1")
+        self.F, self.d = int(F), int(d)
+        self.mean = torch.zeros(self.F, self.d + 1, dtype=torch.float32, device=device)
+        self.prec = torch.ones(self.F, self.d + 1, dtype=torch.float32, device=device)
+
+    def state_dict(self):
+        return {"mean": self.mean.detach().clone(), "prec": self.prec.detach().clone()}
+
+    def load_state_dict(self, state):
+        if set(state) != {"mean", "prec"}:
+            raise ValueError('a GroupPriors state holds "mean" and "prec"')
+        for k in ("mean", "prec"):
+            t = torch.as_tensor(state[k])
+            if tuple(t.shape) != (self.F, self.d + 1):
+                raise ValueError(f"{k} must be [{self.F}, {self.d + 1}], not {list(t.shape)}")
+        mean = torch.as_tensor(state["mean"]).to(self.mean.device, torch.float32)
+        prec = torch.as_tensor(state["prec"]).to(self.prec.device, torch.float32)
+        _check_prior_values(mean, prec)
+        self.mean.copy_(mean)
+        self.prec.copy_(prec)
+
+    def row(self, field):
+        """Field `field`'s prior as the kernels read it: [2, d + 1] fp32, mean | precision."""
+        if isinstance(field, bool) or not isinstance(field, int) or not 0 <= field < self.F:
+            raise ValueError(f"field must be an int in [0, {self.F})")
+        return torch.stack([self.mean[field], self.prec[field]]).contiguous()
+
+    def validate(self):
+        """ValueError unless every value is finite and every precision > 0 (before any kernel reads them)."""
+        _check_prior_values(self.mean, self.prec)
+        return self
+
+
+def _check_prior_values(mean, prec):
+    if not bool(torch.isfinite(mean).all()) or not bool(torch.isfinite(prec).all()):
+        raise ValueError("priors: mean and prec must be finite")
+    if not bool((prec > 0).all()):
+        raise ValueError("priors: prec must be > 0 (a prior precision is what makes each system positive definite)")
+
+
+def check_priors(model, priors):
+    """Validate a priors= argument (no kernel runs): None, or a GroupPriors of the model's F and d with finite values
+    and prec > 0.  Returns it."""
+    if priors is None:
+        return None
+    if not isinstance(priors, GroupPriors):
+        raise ValueError("priors must be a sweep.GroupPriors or None")
+    if priors.F != model.F or priors.d != model.d:
+        raise ValueError(f"priors are for F = {priors.F}, d = {priors.d}; the model has F = {model.F}, d = {model.d}")
+    return priors.validate()
+
+
+def _prior_row(model, priors, field):
+    return None if priors is None else priors.row(int(field)).to(model.device)
+
+
+def check_prec_bounds(prec_min, prec_max):
+    lo, hi = float(prec_min), float(prec_max)
+    if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi):
+        raise ValueError("prec_min and prec_max must be finite with 0 < prec_min <= prec_max")
+    f32 = torch.tensor([lo, hi], dtype=torch.float64).float()
+    if float(f32[0]) <= 0.0 or not math.isfinite(float(f32[1])):
+        raise ValueError("prec_min and prec_max must be representable in fp32 (the prior tables are fp32)")
+    return lo, hi
 
 
 def resolve_split_rows(split_rows, d):
@@ -126,9 +204,10 @@ class SweepPlan:
             cptr, tab = chunk_table(first[a:b], cnt[a:b], self.chunk_rows)
             self.groups.append((a, b, torch.from_numpy(cptr).to(dev), torch.from_numpy(np.ascontiguousarray(tab)).to(dev)))
 
-    def run(self, model, kl_weight):
-        """Write the exact optimum of every entity of the plan into the model's tables.  Returns (entities [E] ascending,
-        loss [E], rows [E])."""
+    def run(self, model, kl_weight, prior=None):
+        """Write the exact optimum of every entity of the plan into the model's tables.  prior: None (N(0, 1), the parent
+        entry points) or the folded field's [2, d + 1] fp32 mean | precision on the device (include/vfm_prior.h).
+        Returns (entities [E] ascending, loss [E], rows [E])."""
         dev, d = model.device, self.d
         loss = torch.empty(self.E, dtype=torch.float32, device=dev)
         if self.E == 0:
@@ -142,14 +221,23 @@ class SweepPlan:
             nl = self.n_light
             ws = torch.empty(max(o.foldin_solve_workspace_bytes(nl, n_ops, d, self.lds_dim), 1), dtype=torch.uint8,
                              device=dev)
-            o.foldin_solve(self.ents[:nl], self.ptr[:nl + 1], self.ys, self.op_x, self.row_op, ent, bia, scal, ws,
-                           loss[:nl], self.field, foldin.OBJECTIVES["closed_form"], _lib.LIK_NORMAL, flags,
-                           self.lds_dim, float(kl_weight))
+            if prior is None:
+                o.foldin_solve(self.ents[:nl], self.ptr[:nl + 1], self.ys, self.op_x, self.row_op, ent, bia, scal, ws,
+                               loss[:nl], self.field, foldin.OBJECTIVES["closed_form"], _lib.LIK_NORMAL, flags,
+                               self.lds_dim, float(kl_weight))
+            else:
+                o.foldin_solve_prior(self.ents[:nl], self.ptr[:nl + 1], self.ys, self.op_x, self.row_op, ent, bia, scal,
+                                     ws, loss[:nl], prior, self.field, foldin.OBJECTIVES["closed_form"], _lib.LIK_NORMAL,
+                                     flags, self.lds_dim, float(kl_weight))
         for a, b, cptr, tab in self.groups:
             ws = torch.empty(max(o.foldin_split_workspace_bytes(tab.shape[0], b - a, n_ops, d, self.lds_dim), 1),
                              dtype=torch.uint8, device=dev)
-            o.foldin_solve_split(self.ents[a:b], cptr, tab, self.ys, self.op_x, self.row_op, ent, bia, scal, ws,
-                                 loss[a:b], self.field, flags, self.lds_dim, float(kl_weight))
+            if prior is None:
+                o.foldin_solve_split(self.ents[a:b], cptr, tab, self.ys, self.op_x, self.row_op, ent, bia, scal, ws,
+                                     loss[a:b], self.field, flags, self.lds_dim, float(kl_weight))
+            else:
+                o.foldin_solve_split_prior(self.ents[a:b], cptr, tab, self.ys, self.op_x, self.row_op, ent, bia, scal,
+                                           ws, loss[a:b], prior, self.field, flags, self.lds_dim, float(kl_weight))
         model.params_changed()              # (rows written outside the step kernels: derived caches are stale)
         return self.ents[self.asc], loss[self.asc], self.counts[self.asc]
 
@@ -200,9 +288,10 @@ def run_bound_split(model, X, y, field=0, kl_weight=1.0, n_iters=8, reset=False,
 
 
 def run_exact_split(model, X, y, field=0, kl_weight=1.0, split_rows="auto", chunk_rows=2048,
-                    max_workspace_bytes=MAX_WORKSPACE_BYTES, lds_dim=-1):
+                    max_workspace_bytes=MAX_WORKSPACE_BYTES, lds_dim=-1, priors=None):
     """foldin.run_exact with the entities of more than max(split_rows, d + 1) rows solved by the split path."""
     x, y = foldin.check_args_exact(model, X, y, field, kl_weight)
+    check_priors(model, priors)
     resolve_split_rows(split_rows, model.d)
     check_chunk_rows(chunk_rows)
     if int(lds_dim) < -1:
@@ -210,7 +299,8 @@ def run_exact_split(model, X, y, field=0, kl_weight=1.0, split_rows="auto", chun
     if int(max_workspace_bytes) < 0:
         raise ValueError("max_workspace_bytes must be >= 0")
     ops._need_cuda(model._flat, "the model's parameters")
-    return SweepPlan(model, x, y, field, split_rows, chunk_rows, int(max_workspace_bytes), lds_dim).run(model, kl_weight)
+    return SweepPlan(model, x, y, field, split_rows, chunk_rows, int(max_workspace_bytes), lds_dim).run(
+        model, kl_weight, _prior_row(model, priors, field))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -229,15 +319,38 @@ def _kl64(mu, sg):
     return 0.5 * (sg * sg + mu * mu - 1.0) - torch.log(sg)
 
 
+def _kl64_prior(mu, sg, m, lam):
+    """KL(N(mu, sg^2) || N(m, 1 / lam)) = 1/2 (lam sg^2 + lam (mu - m)^2 - 1 - log(lam sg^2))."""
+    v = lam * sg * sg
+    return 0.5 * (v + lam * (mu - m) ** 2 - 1.0 - torch.log(v))
+
+
+def _field_of(model, ids):
+    """The field of each id (ids within [0, T))."""
+    edges = torch.tensor(np.cumsum(model.field_sizes)[:-1].tolist(), dtype=torch.int64, device=ids.device)
+    return torch.bucketize(ids, edges, right=True)
+
+
+def _theta64(model, ids):
+    """(mu [n, d + 1], sigma [n, d + 1]) in fp64 of the table rows `ids`, column 0 the first-order weight."""
+    d = model.d
+    ent, bia, _ = model._views(model._flat)
+    e, b = ent[ids], bia[ids]
+    mu = torch.cat([b[:, :1], e[:, :d]], 1).double()
+    sg = _link64(torch.cat([b[:, 1:], e[:, d:]], 1), model.link)
+    return mu, sg
+
+
 def _moments64(model, x):
     ent, bia, scal = model._views(model._flat)
     m, v, _ = rank.predictive_moments(x, ent, bia, scal, model.link)
     return m.double(), v.double()
 
 
-def objective_terms(model, x, y, seen, kl_weight):
+def objective_terms(model, x, y, seen, kl_weight, priors=None):
     """J as a 0-dim fp64 tensor on the device: the rows' expected negative log likelihood from the predictive_moments
-    kernel's fp32 moments, the KL of the entities `seen` (distinct ids) and of the global bias from the tables."""
+    kernel's fp32 moments, the KL of the entities `seen` (distinct ids) and of the global bias from the tables.  priors:
+    the entities' KL is to their field's N(mean, 1 / prec); the global bias keeps N(0, 1)."""
     d = model.d
     ent, bia, scal = model._views(model._flat)
     prec = _link64(scal[0], model.link)
@@ -247,11 +360,38 @@ def objective_terms(model, x, y, seen, kl_weight):
         m, v = _moments64(model, x)
         J = J + 0.5 * prec * ((y.double() - m) ** 2 + v).sum() + n * (LOG_2PI_HALF - 0.5 * torch.log(prec))
     kl = _kl64(scal[1].double(), _link64(scal[2], model.link))
-    if seen.numel():
+    if seen.numel() and priors is not None:
+        f = _field_of(model, seen)
+        mu, sg = _theta64(model, seen)
+        kl = kl + _kl64_prior(mu, sg, priors.mean.to(x.device).double()[f], priors.prec.to(x.device).double()[f]).sum()
+    elif seen.numel():
         e, b = ent[seen], bia[seen]
         kl = kl + _kl64(e[:, :d].double(), _link64(e[:, d:], model.link)).sum()
         kl = kl + _kl64(b[:, 0].double(), _link64(b[:, 1], model.link)).sum()
     return J + float(kl_weight) * kl
+
+
+def prior_block64(mu, sg, m_old, learn_mean, prec_min, prec_max):
+    """The exact minimiser of J over one field's prior, from its seen entities' mu, sigma [n, d + 1] (fp64):
+    m* = mean_e mu (learn_mean; else m_old), 1 / lam* = mean_e (sigma^2 + (mu - m*)^2), lam* clamped to
+    [prec_min, prec_max] (KL is unimodal in 1 / lam: the clamped value is the constrained minimiser).  Returns
+    (m* [d + 1], lam* [d + 1], the number of coordinates at which a clamp binds)."""
+    m = mu.mean(0) if learn_mean else m_old
+    lam = 1.0 / (sg * sg + (mu - m) ** 2).mean(0)
+    return m, lam.clamp(prec_min, prec_max), ((lam < prec_min) | (lam > prec_max)).sum()
+
+
+def update_prior(model, priors, field, seen_f, learn_mean=True, prec_min=1e-4, prec_max=1e4):
+    """Field `field`'s prior block, written into `priors` in place: prior_block64 in torch fp64 on the device from the
+    table rows of seen_f (the field's ids that occur in X), rounded to fp32 when stored.  No readback.  Returns the
+    0-dim int64 count of coordinates clamped (None when the field has no seen entity: nothing is written)."""
+    if seen_f.numel() == 0:
+        return None
+    mu, sg = _theta64(model, seen_f)
+    m, lam, n_clamped = prior_block64(mu, sg, priors.mean[field].to(mu.device).double(), learn_mean, prec_min, prec_max)
+    priors.mean[field] = m.float().to(priors.mean.device)
+    priors.prec[field] = lam.float().to(priors.prec.device)
+    return n_clamped
 
 
 def update_scalars(model, x, y, kl_weight):
@@ -301,43 +441,62 @@ def check_fit_args(model, X, y, n_sweeps, kl_weight, fields, split_rows, chunk_r
     return x, yy, fields
 
 
-def exact_objective(model, X, y, kl_weight=1.0):
+def exact_objective(model, X, y, kl_weight=1.0, priors=None):
     x, y, _ = check_fit_args(model, X, y, 0, kl_weight, None, None, 1, None)
+    check_priors(model, priors)
     ops._need_cuda(model._flat, "the model's parameters")
     model._fresh_params()
-    return float(objective_terms(model, x, y, torch.unique(x), kl_weight))
+    return float(objective_terms(model, x, y, torch.unique(x), kl_weight, priors))
 
 
 def fit(model, X, y, n_sweeps=10, kl_weight=1.0, fields=None, update_scalars_=True, split_rows="auto", chunk_rows=2048,
-        on_step=None, tol=None, max_workspace_bytes=MAX_WORKSPACE_BYTES):
+        on_step=None, tol=None, max_workspace_bytes=MAX_WORKSPACE_BYTES, priors=None, learn_priors=False,
+        learn_mean=True, prec_min=1e-4, prec_max=1e4):
     x, y, fields = check_fit_args(model, X, y, n_sweeps, kl_weight, fields, split_rows, chunk_rows, tol)
+    check_priors(model, priors)
+    prec_min, prec_max = check_prec_bounds(prec_min, prec_max)
     ops._need_cuda(model._flat, "the model's parameters")
+    if learn_priors and priors is None:
+        priors = GroupPriors(model.F, model.d, model.device)          # (created at N(0, 1), returned under "priors")
     model._fresh_params()
     seen = torch.unique(x)
     plans = {f: SweepPlan(model, x, y, f, split_rows, chunk_rows, max_workspace_bytes) for f in dict.fromkeys(fields)}
-    objective = [float(objective_terms(model, x, y, seen, kl_weight))]
+    seen_f = {f: plans[f].ents[plans[f].asc] for f in plans} if learn_priors else {}
+    clamped = {f: torch.zeros((), dtype=torch.int64, device=x.device) for f in plans} if learn_priors else {}
+    objective = [float(objective_terms(model, x, y, seen, kl_weight, priors))]
     events = []
     done = 0
     for sweep in range(n_sweeps):
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0.record()
         for f in fields:
-            plans[f].run(model, kl_weight)
+            plans[f].run(model, kl_weight, _prior_row(model, priors, f))
             if on_step is not None:
                 on_step(sweep, f)
+            if learn_priors:
+                n_clamped = update_prior(model, priors, f, seen_f[f], learn_mean, prec_min, prec_max)
+                if n_clamped is not None:
+                    clamped[f] += n_clamped
+                if on_step is not None:
+                    on_step(sweep, ("prior", f))
         if update_scalars_:
             update_scalars(model, x, y, kl_weight)
             if on_step is not None:
                 on_step(sweep, "scalars")
         t1.record()
         events.append((t0, t1))
-        objective.append(float(objective_terms(model, x, y, seen, kl_weight)))
+        objective.append(float(objective_terms(model, x, y, seen, kl_weight, priors)))
         done += 1
         if tol is not None and objective[-2] - objective[-1] <= float(tol) * abs(objective[-2]):
             break
     model.params_changed()
     torch.cuda.synchronize(model.device)
-    return {"objective": objective, "sweeps": done, "ms": [a.elapsed_time(b) for a, b in events]}
+    out = {"objective": objective, "sweeps": done, "ms": [a.elapsed_time(b) for a, b in events]}
+    if priors is not None:
+        out["priors"] = priors
+    if learn_priors:
+        out["clamped"] = {f: int(n) for f, n in clamped.items()}
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------
