@@ -246,3 +246,47 @@ def test_cpu_model_ops_fail_loudly():
     m = VFM(5, 5, 4, device="cpu")
     with pytest.raises(VfmLibraryError):
         m.set_training_data(torch.tensor([[0, 5]]), nb_train=1)
+
+
+def test_fold_structs_are_the_literal_field_lists():
+    """The four fold-in solve structs are built from shared runs of fields (vae_amd/_lib.py); each must equal, name for
+    name and type for type, the literal list it replaced."""
+    from vae_amd import _lib
+    i64, i32, f32, vp = C.c_int64, C.c_int32, C.c_float, C.c_void_p
+    solve = [
+        ("E", i64), ("R", i64), ("T", i64), ("n_ops", i64),
+        ("F", i32), ("d", i32), ("col", i32), ("objective", i32),
+        ("likelihood", i32), ("flags", i32), ("lds_dim", i32), ("kl_weight", f32),
+        ("entities", vp), ("row_ptr", vp), ("y", vp), ("op_x", vp),
+        ("row_op", vp), ("entity_params", vp), ("bias_params", vp), ("scalars", vp),
+        ("out_loss", vp), ("workspace", vp), ("workspace_bytes", i64),
+    ]
+    split = [
+        ("E", i64), ("R", i64), ("T", i64), ("n_ops", i64), ("n_chunks", i64),
+        ("F", i32), ("d", i32), ("col", i32), ("flags", i32), ("lds_dim", i32),
+        ("kl_weight", f32),
+        ("entities", vp), ("chunk_ptr", vp), ("chunks", vp), ("y", vp),
+        ("op_x", vp), ("row_op", vp), ("entity_params", vp), ("bias_params", vp),
+        ("scalars", vp), ("out_loss", vp), ("workspace", vp), ("workspace_bytes", i64),
+    ]
+    bound = [
+        ("E", i64), ("R", i64), ("T", i64), ("n_ops", i64),
+        ("F", i32), ("d", i32), ("col", i32), ("objective", i32),
+        ("likelihood", i32), ("flags", i32), ("lds_dim", i32), ("kl_weight", f32),
+        ("n_iters", i32), ("reset", i32), ("mode", i32), ("pad0", i32),
+        ("entities", vp), ("row_ptr", vp), ("y", vp), ("op_x", vp),
+        ("row_op", vp), ("entity_params", vp), ("bias_params", vp), ("scalars", vp),
+        ("out_loss", vp), ("workspace", vp), ("workspace_bytes", i64),
+    ]
+    bound_split = [
+        ("E", i64), ("R", i64), ("T", i64), ("n_ops", i64), ("n_chunks", i64),
+        ("F", i32), ("d", i32), ("col", i32), ("flags", i32), ("lds_dim", i32),
+        ("kl_weight", f32), ("n_iters", i32), ("reset", i32),
+        ("entities", vp), ("chunk_ptr", vp), ("chunks", vp), ("y", vp),
+        ("op_x", vp), ("row_op", vp), ("entity_params", vp), ("bias_params", vp),
+        ("scalars", vp), ("out_loss", vp), ("workspace", vp), ("workspace_bytes", i64),
+    ]
+    for cls, fields in ((_lib.FoldinSolve, solve), (_lib.FoldinSplit, split), (_lib.FoldinBound, bound),
+                        (_lib.FoldinBoundSplit, bound_split)):
+        assert list(cls._fields_) == fields, cls.__name__
+        assert cls._names == frozenset(n for n, _ in fields)

@@ -303,3 +303,96 @@ def test_the_plan_sizes_its_groups_by_the_solve_it_is_for():
         bound = lib.vfm_foldin_bound_split_workspace_bytes(args[0], args[1], 500, *args[2:])
         ru = lambda v: (v + 255) // 256 * 256
         assert bound == exact + ru(args[2] * 8) + ru(500 * 8) + ru(args[1] * 2 * (args[3] + 1) * 8)
+
+
+def _former_check_fit_args(model, X, y, n_sweeps, kl_weight, fields, split_rows, chunk_rows, tol):
+    """sweep.check_fit_args as it stood before the two fits shared one checker."""
+    import math
+    from vae_amd import foldin, sweep
+    if model.output != "reg":
+        raise ValueError("fit_exact needs a 'reg' model (Gaussian likelihood): the closed form its blocks solve has none "
+                         "for 'class'; use fit")
+    if not float(kl_weight) > 0.0 or not math.isfinite(float(kl_weight)):
+        raise ValueError("kl_weight must be > 0 and finite: the prior term is what makes each system positive definite")
+    if isinstance(n_sweeps, bool) or not isinstance(n_sweeps, int) or n_sweeps < 0:
+        raise ValueError("n_sweeps must be an integer >= 0")
+    if fields is None:
+        fields = tuple(range(model.F))
+    else:
+        fields = tuple(fields)
+        for f in fields:
+            if isinstance(f, bool) or not isinstance(f, int) or not 0 <= f < model.F:
+                raise ValueError(f"fields must hold ints in [0, {model.F})")
+    sweep.resolve_split_rows(split_rows, model.d)
+    sweep.check_chunk_rows(chunk_rows)
+    if tol is not None and not float(tol) >= 0.0:
+        raise ValueError("tol must be None or >= 0")
+    x = yy = None
+    for f in range(model.F):
+        x, yy = foldin.check_args_exact(model, X, y, f, kl_weight)
+    return x, yy, fields
+
+
+def _former_check_fit_bound_args(model, X, y, n_sweeps, kl_weight, n_iters, fields, split_rows, chunk_rows, tol):
+    """sweep.check_fit_bound_args as it stood before the two fits shared one checker."""
+    from vae_amd import foldin, sweep
+    if model.output != "class":
+        raise ValueError("fit_bound needs a 'class' model (Bernoulli likelihood): a 'reg' model's blocks have their exact "
+                         "optimum; use fit_exact")
+    if isinstance(n_sweeps, bool) or not isinstance(n_sweeps, int) or n_sweeps < 0:
+        raise ValueError("n_sweeps must be an integer >= 0")
+    if fields is None:
+        fields = tuple(range(model.F))
+    else:
+        fields = tuple(fields)
+        for f in fields:
+            if isinstance(f, bool) or not isinstance(f, int) or not 0 <= f < model.F:
+                raise ValueError(f"fields must hold ints in [0, {model.F})")
+    sweep.resolve_split_rows(split_rows, model.d)
+    sweep.check_chunk_rows(chunk_rows)
+    if tol is not None and not float(tol) >= 0.0:
+        raise ValueError("tol must be None or >= 0")
+    x = yy = None
+    for f in range(model.F):
+        x, yy = foldin.check_args_bound(model, X, y, f, kl_weight, n_iters)
+    return x, yy, fields
+
+
+# one case per message of the two former checkers: what differs from a valid call
+_FIT_ARG_CASES = [dict(other_model=True), dict(kl_weight=0.0), dict(n_sweeps=-1), dict(fields=(2,)), dict(split_rows="big"),
+                  dict(chunk_rows=0), dict(tol=-1.0), dict(X=torch.tensor([[6, 7]]), y=torch.tensor([1.0])),
+                  dict(X=torch.tensor([[0, 10]]), y=torch.tensor([1.0])), dict(y=torch.tensor([1.0, 0.0])),
+                  dict(X=torch.tensor([[0.5, 6.0]]), y=torch.tensor([1.0]))]
+
+
+@pytest.mark.parametrize("kind", ["reg", "class"])
+def test_merged_fit_checker_raises_the_former_texts(kind):
+    """sweep.check_fit_args serves fit_exact and fit_bound; for each message of the two checkers it replaced, a 'reg'
+    and a 'class' model raise the former text, and a valid call returns what the former one returned."""
+    from vae_amd import sweep
+    base = dict(X=torch.tensor([[0, 6], [1, 7], [0, 9]]), y=torch.tensor([1.0, 0.0, 1.0]), n_sweeps=3, kl_weight=0.7,
+                fields=None, split_rows="auto", chunk_rows=16, tol=None)
+    cases = list(_FIT_ARG_CASES)
+    if kind == "class":
+        cases += [dict(n_iters=0), dict(y=torch.tensor([1.0, 0.5, 0.0]))]          # the bound's own: n_iters, the labels
+
+    def both(other_model=False, n_iters=8, **kw):
+        a = dict(base, **kw)
+        m = _cpu_model(("class" if kind == "reg" else "reg") if other_model else kind)
+        rest = (a["fields"], a["split_rows"], a["chunk_rows"], a["tol"])
+        if kind == "reg":
+            return (lambda: _former_check_fit_args(m, a["X"], a["y"], a["n_sweeps"], a["kl_weight"], *rest),
+                    lambda: sweep._check_fit_exact(m, a["X"], a["y"], a["n_sweeps"], a["kl_weight"], *rest))
+        return (lambda: _former_check_fit_bound_args(m, a["X"], a["y"], a["n_sweeps"], a["kl_weight"], n_iters, *rest),
+                lambda: sweep._check_fit_bound(m, a["X"], a["y"], a["n_sweeps"], a["kl_weight"], n_iters, *rest))
+
+    for case in cases:
+        former, merged = both(**case)
+        with pytest.raises(ValueError) as want:
+            former()
+        with pytest.raises(ValueError) as got:
+            merged()
+        assert str(got.value) == str(want.value), case
+    former, merged = both()
+    (x0, y0, f0), (x1, y1, f1) = former(), merged()
+    assert torch.equal(x0, x1) and torch.equal(y0, y1) and f0 == f1 == (0, 1)

@@ -259,3 +259,32 @@ def test_split_rows_rule():
     from vae_amd.sweep import resolve_split_rows
     assert resolve_split_rows(None, 8) is None and resolve_split_rows("auto", 8) == 36
     assert resolve_split_rows(0, 8) == 9 and resolve_split_rows(9, 8) == 9 and resolve_split_rows(50, 8) == 50
+
+
+@pytest.mark.parametrize("link", ["abs", "softplus"])
+@pytest.mark.parametrize("n, d", [(1, 1), (7, 5), (300, 20)])
+def test_shared_kl_of_the_seen_rows_is_the_two_former_expressions(n, d, link):
+    """sweep._add_kl64_rows, which objective_terms and bound_objective_terms now share, against the expression each of
+    them held: the same two fp64 sums added in the same order, so torch.equal."""
+    from vae_amd import sweep
+    g = torch.Generator().manual_seed(17 * n + d)
+    e = torch.randn(n, 2 * d, generator=g) * 0.7                           # fp32 table rows, as the model holds them
+    b = torch.randn(n, 2, generator=g) * 0.7
+    if link == "abs":
+        e[:, d:] = e[:, d:].abs() + 0.05                                   # (sigma = |s| > 0)
+        b[:, 1] = b[:, 1].abs() + 0.05
+    kl0 = sweep._kl64(torch.randn((), generator=g).double(), torch.rand((), generator=g).double() + 0.1)
+
+    def former_exact(kl):                                                  # objective_terms, the branch without priors
+        kl = kl + sweep._kl64(e[:, :d].double(), sweep._link64(e[:, d:], link)).sum()
+        kl = kl + sweep._kl64(b[:, 0].double(), sweep._link64(b[:, 1], link)).sum()
+        return kl
+
+    def former_bound(kl):                                                  # bound_objective_terms
+        kl = kl + sweep._kl64(e[:, :d].double(), sweep._link64(e[:, d:], link)).sum()
+        kl = kl + sweep._kl64(b[:, 0].double(), sweep._link64(b[:, 1], link)).sum()
+        return kl
+
+    got = sweep._add_kl64_rows(kl0, e, b, d, link)
+    assert got.dtype == torch.float64 and bool(torch.isfinite(got))
+    assert torch.equal(got, former_exact(kl0)) and torch.equal(got, former_bound(kl0))

@@ -216,7 +216,7 @@ def test_header_exports_and_workspace_formulas():
     for bad in [(-1, 1, 1, 8, -1), (1, -1, 1, 8, -1), (1, 1, -1, 8, -1), (1, 1, 1, 0, -1), (1, 1, 1, 513, -1),
                 (1, 1, 1, 8, -2), (1 << 41, 1, 1, 8, -1)]:
         assert lib.vfm_foldin_split_prior_workspace_bytes(*bad) == E_INVALID
-    ops = open(os.path.join(ROOT, "vae_amd", "csrc_rank", "vfm_prior_ops.cpp")).read()
+    ops = open(os.path.join(ROOT, "vae_amd", "csrc_rank", "vfm_foldin_ops.cpp")).read()
     assert "foldin_solve_prior(" in ops and "foldin_solve_split_prior(" in ops
 
 

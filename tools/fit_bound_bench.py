@@ -184,11 +184,14 @@ def main():
     ap.add_argument("--sweeps", type=int, default=8)
     ap.add_argument("--sweeps-curve", type=int, default=3)
     ap.add_argument("--write", action="store_true", help="append the lines to profiles/fit_bound_bench.jsonl")
+    ap.add_argument("--note", default=None, help="kept in the line: what was measured, e.g. the commit")
     args = ap.parse_args()
     dev = torch.device("cuda")
     for what in args.what.split(","):
         rec = {"heavy": heavy, "sweep": sweep, "curve": curve, "auc": auc}[what](args, dev)
         rec.update({"device": torch.cuda.get_device_name(0), "when": time.strftime("%Y-%m-%dT%H:%M:%S")})
+        if args.note:
+            rec["note"] = args.note
         print(json.dumps(rec), flush=True)
         if args.write:
             with open(os.path.join(ROOT, "profiles", "fit_bound_bench.jsonl"), "a") as f:

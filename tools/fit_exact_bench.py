@@ -134,6 +134,7 @@ def main():
     ap.add_argument("--zipf", type=float, default=1.0)
     ap.add_argument("--sweeps", type=int, default=8)
     ap.add_argument("--write", action="store_true", help="append the lines to profiles/fit_exact_bench.jsonl")
+    ap.add_argument("--note", default=None, help="kept in the line: what was measured, e.g. the commit")
     args = ap.parse_args()
     dev = torch.device("cuda")
     for what in args.what.split(","):
@@ -142,6 +143,8 @@ def main():
             rec.update({"warmup": args.warmup if what == "heavy" else args.warmup_sweep,
                         "reps": args.reps if what == "heavy" else args.reps_sweep})
         rec.update({"device": torch.cuda.get_device_name(0), "when": time.strftime("%Y-%m-%dT%H:%M:%S")})
+        if args.note:
+            rec["note"] = args.note
         print(json.dumps(rec), flush=True)
         if args.write:
             with open(os.path.join(ROOT, "profiles", "fit_exact_bench.jsonl"), "a") as f:

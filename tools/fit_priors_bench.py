@@ -133,11 +133,14 @@ def main():
     ap.add_argument("--sweeps", type=int, default=8)
     ap.add_argument("--kl-grid", type=float, nargs="+", default=[0.25, 0.5, 1.0, 2.0, 4.0])
     ap.add_argument("--write", action="store_true", help="append the lines to profiles/fit_priors_bench.jsonl")
+    ap.add_argument("--note", default=None, help="kept in the line: what was measured, e.g. the commit")
     args = ap.parse_args()
     dev = torch.device("cuda")
     for what in args.what.split(","):
         rec = {"cost_heavy": cost_heavy, "cost_sweep": cost_sweep, "benefit": benefit}[what](args, dev)
         rec.update({"device": torch.cuda.get_device_name(0), "when": time.strftime("%Y-%m-%dT%H:%M:%S")})
+        if args.note:
+            rec["note"] = args.note
         print(json.dumps(rec), flush=True)
         if args.write:
             with open(os.path.join(ROOT, "profiles", "fit_priors_bench.jsonl"), "a") as f:

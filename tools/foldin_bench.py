@@ -78,6 +78,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--shapes", default="fraction,ml20m")
     ap.add_argument("--write", action="store_true", help="append the lines to profiles/foldin_bench.jsonl")
+    ap.add_argument("--note", default=None, help="kept in the line: what was measured, e.g. the commit")
     args = ap.parse_args()
     from vae_amd.model import VFM
     from vae_amd.data import load_fraction
@@ -123,6 +124,8 @@ def main():
             rec["refit_ms"] = round(timed(refit, 0, 1), 3)
         rec["device"] = torch.cuda.get_device_name(0)
         rec["when"] = time.strftime("%Y-%m-%dT%H:%M:%S")
+        if args.note:
+            rec["note"] = args.note
         print(json.dumps(rec), flush=True)
         lines.append(rec)
     if args.write:

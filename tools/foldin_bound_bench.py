@@ -35,6 +35,7 @@ def main():
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--shapes", default="fraction,ml20m")
     ap.add_argument("--write", action="store_true", help="append the lines to profiles/foldin_bound_bench.jsonl")
+    ap.add_argument("--note", default=None, help="kept in the line: what was measured, e.g. the commit")
     args = ap.parse_args()
     from vae_amd.model import VFM
     dev = torch.device("cuda")
@@ -72,6 +73,8 @@ def main():
                "bound_over_adam": round(t["bound"][len(t["bound"]) // 2] / t["adam"][len(t["adam"]) // 2], 4),
                "bound_at_start": at_start, "bound_after": after, "bound_at_adam": at_adam,
                "device": torch.cuda.get_device_name(0), "when": time.strftime("%Y-%m-%dT%H:%M:%S")}
+        if args.note:
+            rec["note"] = args.note
         print(json.dumps(rec), flush=True)
         lines.append(rec)
     if args.write:

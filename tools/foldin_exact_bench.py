@@ -55,6 +55,7 @@ def main():
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--shapes", default="ml20m,ml20m_heavy")
     ap.add_argument("--write", action="store_true", help="append the lines to profiles/foldin_exact_bench.jsonl")
+    ap.add_argument("--note", default=None, help="kept in the line: what was measured, e.g. the commit")
     args = ap.parse_args()
     from vae_amd import _lib, foldin, ops
     from vae_amd.model import VFM
@@ -117,6 +118,8 @@ def main():
                "gap_adam_minus_exact": {"min": float(gap.min()), "median": float(gap.median()), "max": float(gap.max())},
                "rel_gap_max": float((gap / l_exact.cpu()).max()),
                "device": torch.cuda.get_device_name(0), "when": time.strftime("%Y-%m-%dT%H:%M:%S")}
+        if args.note:
+            rec["note"] = args.note
         print(json.dumps(rec), flush=True)
         lines.append(rec)
     if args.write:

@@ -81,77 +81,68 @@ RANK_POST_EXPORTS = ("vfm_field_moments_post_f32", "vfm_rank_field_post_f32", "v
 VARIANT_STEP_EXPORTS = ("vfm_variant_step_f32", "vfm_variant_step_workspace_bytes")
 
 
-# ---- exact fold-in (include/vfm_foldin.h: vfm_foldin_solve_f32)
+def _fields(ctype, *names):
+    return tuple((n, ctype) for n in names)
+
+
+# ---- the fold-in solves: exact (include/vfm_foldin.h: vfm_foldin_solve_f32), split exact (include/vfm_sweep.h, the hot
+# path of VFM.fit_exact), under a learnt field prior (include/vfm_prior.h: the same structs plus the prior pointer), bound
+# for 'class' models (include/vfm_bound.h) and split bound (include/vfm_bound_sweep.h, the hot path of VFM.fit_bound)
 FOLDIN_SOLVE_EXPORTS = ("vfm_foldin_solve_f32", "vfm_foldin_solve_workspace_bytes")
 FOLDIN_SOLVE_LDS_DIM = 135
 FOLDIN_SOLVE_SLABS = 256
+SWEEP_EXPORTS = ("vfm_foldin_solve_split_f32", "vfm_foldin_split_workspace_bytes")
+PRIOR_EXPORTS = ("vfm_foldin_solve_prior_f32", "vfm_foldin_solve_prior_workspace_bytes",
+                 "vfm_foldin_solve_split_prior_f32", "vfm_foldin_split_prior_workspace_bytes")
+BOUND_EXPORTS = ("vfm_foldin_bound_f32", "vfm_foldin_bound_workspace_bytes")
+BOUND_SWEEP_EXPORTS = ("vfm_foldin_bound_split_f32", "vfm_foldin_bound_split_workspace_bytes")
+
+# the runs of fields that the four structs name alike; between them the row-list forms have objective and likelihood and
+# a row_ptr, the chunk forms n_chunks and the chunk table, the bound forms n_iters and reset
+_FOLD_COUNTS = _fields(C.c_int64, "E", "R", "T", "n_ops")
+_FOLD_DIMS = _fields(C.c_int32, "F", "d", "col")
+_FOLD_OPTIONS = _fields(C.c_int32, "flags", "lds_dim") + (("kl_weight", C.c_float),)
+_FOLD_IDS = (("entities", C.c_void_p),)
+_FOLD_TAIL = (_fields(C.c_void_p, "y", "op_x", "row_op", "entity_params", "bias_params", "scalars", "out_loss", "workspace")
+              + (("workspace_bytes", C.c_int64),))
+_FOLD_LIST_HEAD = _FOLD_COUNTS + _FOLD_DIMS + _fields(C.c_int32, "objective", "likelihood") + _FOLD_OPTIONS
+_FOLD_CHUNK_HEAD = _FOLD_COUNTS + (("n_chunks", C.c_int64),) + _FOLD_DIMS + _FOLD_OPTIONS
+_FOLD_LIST_ROWS = _FOLD_IDS + (("row_ptr", C.c_void_p),) + _FOLD_TAIL
+_FOLD_CHUNK_ROWS = _FOLD_IDS + _fields(C.c_void_p, "chunk_ptr", "chunks") + _FOLD_TAIL
 
 
 class FoldinSolve(_Strict, C.Structure):
     """`vfm_foldin_solve_t` (tests/test_foldin_exact_cpu.py checks the layout against gcc's)."""
-    _fields_ = [
-        ("E", C.c_int64), ("R", C.c_int64), ("T", C.c_int64), ("n_ops", C.c_int64),
-        ("F", C.c_int32), ("d", C.c_int32), ("col", C.c_int32), ("objective", C.c_int32),
-        ("likelihood", C.c_int32), ("flags", C.c_int32), ("lds_dim", C.c_int32), ("kl_weight", C.c_float),
-        ("entities", C.c_void_p), ("row_ptr", C.c_void_p), ("y", C.c_void_p), ("op_x", C.c_void_p),
-        ("row_op", C.c_void_p), ("entity_params", C.c_void_p), ("bias_params", C.c_void_p), ("scalars", C.c_void_p),
-        ("out_loss", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
-    ]
-
-
-# ---- split exact solve (include/vfm_sweep.h), the hot path of VFM.fit_exact
-SWEEP_EXPORTS = ("vfm_foldin_solve_split_f32", "vfm_foldin_split_workspace_bytes")
+    _fields_ = list(_FOLD_LIST_HEAD + _FOLD_LIST_ROWS)
 
 
 class FoldinSplit(_Strict, C.Structure):
     """`vfm_foldin_split_t` (tests/test_fit_exact_cpu.py checks the layout against gcc's)."""
-    _fields_ = [
-        ("E", C.c_int64), ("R", C.c_int64), ("T", C.c_int64), ("n_ops", C.c_int64), ("n_chunks", C.c_int64),
-        ("F", C.c_int32), ("d", C.c_int32), ("col", C.c_int32), ("flags", C.c_int32), ("lds_dim", C.c_int32),
-        ("kl_weight", C.c_float),
-        ("entities", C.c_void_p), ("chunk_ptr", C.c_void_p), ("chunks", C.c_void_p), ("y", C.c_void_p),
-        ("op_x", C.c_void_p), ("row_op", C.c_void_p), ("entity_params", C.c_void_p), ("bias_params", C.c_void_p),
-        ("scalars", C.c_void_p), ("out_loss", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
-    ]
-
-
-# ---- the exact solves under a learnt field prior (include/vfm_prior.h): the parent calls' structs plus the prior pointer
-PRIOR_EXPORTS = ("vfm_foldin_solve_prior_f32", "vfm_foldin_solve_prior_workspace_bytes",
-                 "vfm_foldin_solve_split_prior_f32", "vfm_foldin_split_prior_workspace_bytes")
-
-
-# ---- bound fold-in for 'class' models (include/vfm_bound.h)
-BOUND_EXPORTS = ("vfm_foldin_bound_f32", "vfm_foldin_bound_workspace_bytes")
+    _fields_ = list(_FOLD_CHUNK_HEAD + _FOLD_CHUNK_ROWS)
 
 
 class FoldinBound(_Strict, C.Structure):
     """`vfm_foldin_bound_t` (tests/test_foldin_bound_cpu.py checks the layout against gcc's)."""
-    _fields_ = [
-        ("E", C.c_int64), ("R", C.c_int64), ("T", C.c_int64), ("n_ops", C.c_int64),
-        ("F", C.c_int32), ("d", C.c_int32), ("col", C.c_int32), ("objective", C.c_int32),
-        ("likelihood", C.c_int32), ("flags", C.c_int32), ("lds_dim", C.c_int32), ("kl_weight", C.c_float),
-        ("n_iters", C.c_int32), ("reset", C.c_int32), ("mode", C.c_int32), ("pad0", C.c_int32),
-        ("entities", C.c_void_p), ("row_ptr", C.c_void_p), ("y", C.c_void_p), ("op_x", C.c_void_p),
-        ("row_op", C.c_void_p), ("entity_params", C.c_void_p), ("bias_params", C.c_void_p), ("scalars", C.c_void_p),
-        ("out_loss", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
-    ]
-
-
-# ---- split bound rounds (include/vfm_bound_sweep.h), the hot path of VFM.fit_bound
-BOUND_SWEEP_EXPORTS = ("vfm_foldin_bound_split_f32", "vfm_foldin_bound_split_workspace_bytes")
+    _fields_ = list(_FOLD_LIST_HEAD + _fields(C.c_int32, "n_iters", "reset", "mode", "pad0") + _FOLD_LIST_ROWS)
 
 
 class FoldinBoundSplit(_Strict, C.Structure):
     """`vfm_foldin_bound_split_t`: vfm_foldin_split_t's fields, n_iters and reset (tests/test_fit_bound_cpu.py checks the
     layout against gcc's)."""
-    _fields_ = [
-        ("E", C.c_int64), ("R", C.c_int64), ("T", C.c_int64), ("n_ops", C.c_int64), ("n_chunks", C.c_int64),
-        ("F", C.c_int32), ("d", C.c_int32), ("col", C.c_int32), ("flags", C.c_int32), ("lds_dim", C.c_int32),
-        ("kl_weight", C.c_float), ("n_iters", C.c_int32), ("reset", C.c_int32),
-        ("entities", C.c_void_p), ("chunk_ptr", C.c_void_p), ("chunks", C.c_void_p), ("y", C.c_void_p),
-        ("op_x", C.c_void_p), ("row_op", C.c_void_p), ("entity_params", C.c_void_p), ("bias_params", C.c_void_p),
-        ("scalars", C.c_void_p), ("out_loss", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
-    ]
+    _fields_ = list(_FOLD_CHUNK_HEAD + _fields(C.c_int32, "n_iters", "reset") + _FOLD_CHUNK_ROWS)
+
+
+# the family's prototypes: (entry point, struct, extra arguments, size function, its argument types)
+_I64, _I32 = C.c_int64, C.c_int32
+_SOLVE_SIZES, _SPLIT_SIZES = [_I64, _I64, _I32, _I32], [_I64, _I64, _I64, _I32, _I32]
+_FOLD_PROTOTYPES = (
+    ("vfm_foldin_solve_f32", FoldinSolve, [], "vfm_foldin_solve_workspace_bytes", _SOLVE_SIZES),
+    ("vfm_foldin_solve_split_f32", FoldinSplit, [], "vfm_foldin_split_workspace_bytes", _SPLIT_SIZES),
+    ("vfm_foldin_solve_prior_f32", FoldinSolve, [C.c_void_p], "vfm_foldin_solve_prior_workspace_bytes", _SOLVE_SIZES),
+    ("vfm_foldin_solve_split_prior_f32", FoldinSplit, [C.c_void_p], "vfm_foldin_split_prior_workspace_bytes", _SPLIT_SIZES),
+    ("vfm_foldin_bound_f32", FoldinBound, [], "vfm_foldin_bound_workspace_bytes", [_I64] + _SOLVE_SIZES),
+    ("vfm_foldin_bound_split_f32", FoldinBoundSplit, [], "vfm_foldin_bound_split_workspace_bytes", [_I64] + _SPLIT_SIZES),
+)
 
 
 # the bound field-form session (vfm_elicit_bound_f32) is declared in vfm_bound.h too
@@ -159,10 +150,6 @@ ELICIT_BOUND_EXPORTS = ("vfm_elicit_bound_f32", "vfm_elicit_bound_workspace_byte
 
 
 # ---- the session structs: the runs of fields that every form names alike, and the stamp every one starts with
-def _fields(ctype, *names):
-    return tuple((n, ctype) for n in names)
-
-
 _STAMP = _fields(C.c_uint32, "struct_size", "abi_version")
 _COUNTS = _fields(C.c_int64, "U", "P", "H", "T", "n_ops")
 _FIELD_ROWS = _fields(C.c_void_p, "entities", "pool_ptr", "pool_x", "pool_y", "hist_ptr", "hist_x", "hist_y")
@@ -310,30 +297,11 @@ def load():
     for name in ("vfm_design_scores_f32", "vfm_design_elicit_f32"):
         getattr(lib, name).argtypes = [C.POINTER(ElicitDesign), vp]
         getattr(lib, name).restype = C.c_int
-    lib.vfm_foldin_solve_f32.argtypes = [C.POINTER(FoldinSolve), vp]
-    lib.vfm_foldin_solve_f32.restype = C.c_int
-    lib.vfm_foldin_solve_workspace_bytes.argtypes = [i64, i64, i32, i32]
-    lib.vfm_foldin_solve_workspace_bytes.restype = i64
-    lib.vfm_foldin_solve_split_f32.argtypes = [C.POINTER(FoldinSplit), vp]
-    lib.vfm_foldin_solve_split_f32.restype = C.c_int
-    lib.vfm_foldin_split_workspace_bytes.argtypes = [i64, i64, i64, i32, i32]
-    lib.vfm_foldin_split_workspace_bytes.restype = i64
-    lib.vfm_foldin_solve_prior_f32.argtypes = [C.POINTER(FoldinSolve), vp, vp]
-    lib.vfm_foldin_solve_prior_f32.restype = C.c_int
-    lib.vfm_foldin_solve_prior_workspace_bytes.argtypes = [i64, i64, i32, i32]
-    lib.vfm_foldin_solve_prior_workspace_bytes.restype = i64
-    lib.vfm_foldin_solve_split_prior_f32.argtypes = [C.POINTER(FoldinSplit), vp, vp]
-    lib.vfm_foldin_solve_split_prior_f32.restype = C.c_int
-    lib.vfm_foldin_split_prior_workspace_bytes.argtypes = [i64, i64, i64, i32, i32]
-    lib.vfm_foldin_split_prior_workspace_bytes.restype = i64
-    lib.vfm_foldin_bound_f32.argtypes = [C.POINTER(FoldinBound), vp]
-    lib.vfm_foldin_bound_f32.restype = C.c_int
-    lib.vfm_foldin_bound_workspace_bytes.argtypes = [i64, i64, i64, i32, i32]
-    lib.vfm_foldin_bound_workspace_bytes.restype = i64
-    lib.vfm_foldin_bound_split_f32.argtypes = [C.POINTER(FoldinBoundSplit), vp]
-    lib.vfm_foldin_bound_split_f32.restype = C.c_int
-    lib.vfm_foldin_bound_split_workspace_bytes.argtypes = [i64, i64, i64, i64, i32, i32]
-    lib.vfm_foldin_bound_split_workspace_bytes.restype = i64
+    for entry, struct, extra, size, size_args in _FOLD_PROTOTYPES:
+        getattr(lib, entry).argtypes = [C.POINTER(struct)] + extra + [vp]
+        getattr(lib, entry).restype = C.c_int
+        getattr(lib, size).argtypes = size_args
+        getattr(lib, size).restype = i64
     lib.vfm_elicit_bound_f32.argtypes = [C.POINTER(ElicitBound), vp]
     lib.vfm_elicit_bound_f32.restype = C.c_int
     lib.vfm_elicit_bound_workspace_bytes.argtypes = [i64, i64, i64, i64, i32, i32, i32]

@@ -349,11 +349,7 @@ void launch_exact_session(bool sp, const Args& s, unsigned grid, hipStream_t st,
       constexpr int DP = decltype(w)::value * decltype(c)::value;
       const size_t shm = (size_t)(lds_doubles(d, s.sl.cap_dim) + Fold::lds_doubles(d) + Score::lds_doubles(d)) * 8 +
                          (size_t)session_tail_bytes(DP);
-      const auto k = kernel_of(w, c, link);
-      // (more than 64 KiB of dynamic LDS: state the size; a runtime that needs no opt-in ignores it)
-      (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      (void)hipGetLastError();
-      hipLaunchKernelGGL(k, dim3(grid), dim3(FB), shm, st, s);
+      launch_lds(kernel_of(w, c, link), grid, shm, st, s);
     });
   });
 }

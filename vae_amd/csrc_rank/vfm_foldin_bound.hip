@@ -52,10 +52,6 @@ struct BoundArgs {
   SolveSlabs sl;                         // the slabs and the LDS rule of the triangle
 };
 
-inline int64_t off_cv64(int64_t n_ops, int d) { return off_slabs(n_ops, d); }
-inline int64_t off_wrow(int64_t n_ops, int d) { return off_cv64(n_ops, d) + round_up(n_ops * 8, 256); }
-inline int64_t off_bound_slabs(int64_t R, int64_t n_ops, int d) { return off_wrow(n_ops, d) + round_up(R * 8, 256); }
-
 template <int W, int CPL, int LINK>
 __global__ __launch_bounds__(FB) void k_foldin_bound(const BoundArgs s) {
 #pragma clang fp contract(on)
@@ -112,11 +108,7 @@ __global__ __launch_bounds__(FB) void k_foldin_bound(const BoundArgs s) {
 void launch(const FShape& f, bool sp, const BoundArgs& s, unsigned grid, size_t shm, hipStream_t st) {
   for_link(sp, [&](auto link) {
     for_shape(f, [&](auto w, auto c) {
-      const auto k = k_foldin_bound<decltype(w)::value, decltype(c)::value, decltype(link)::value>;
-      // (more than 64 KiB of dynamic LDS: state the size; a runtime that needs no opt-in ignores it)
-      (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      (void)hipGetLastError();
-      hipLaunchKernelGGL(k, dim3(grid), dim3(FB), shm, st, s);
+      launch_lds(k_foldin_bound<decltype(w)::value, decltype(c)::value, decltype(link)::value>, grid, shm, st, s);
     });
   });
 }
@@ -128,64 +120,37 @@ extern "C" {
 
 int64_t vfm_foldin_bound_workspace_bytes(int64_t E, int64_t R, int64_t n_ops, int32_t d, int32_t lds_dim) {
   if (E < 0 || R < 0 || n_ops < 0 || d < 1 || d > VFM_FOLDIN_MAX_D || lds_dim < -1) return VFM_E_INVALID;
-  return vfm::off_bound_slabs(R, n_ops, d) + vfm::slabs_bytes(E, d, lds_dim);
+  return vfm::off_bound_own(R, n_ops, d) + vfm::slabs_bytes(E, d, lds_dim);
 }
 
 int vfm_foldin_bound_f32(const vfm_foldin_bound_t* p, void* stream) {
-  using vfm::fail;
-  if (!p) return fail(VFM_E_INVALID, "vfm_foldin_bound_f32: NULL argument struct");
-  if (p->T < 1) return fail(VFM_E_INVALID, "T < 1");
-  if (p->d < 1 || p->d > VFM_FOLDIN_MAX_D) return fail(VFM_E_INVALID, "d out of range [1,512]");
-  if (p->F < 1 || p->F > VFM_MAX_FIELDS) return fail(VFM_E_INVALID, "F out of range [1,64]");
-  if (p->col < 0 || p->col >= p->F) return fail(VFM_E_INVALID, "col out of range [0,F)");
-  if (p->E < 0 || p->R < 0) return fail(VFM_E_INVALID, "E < 0 or R < 0");
-  if (p->objective != VFM_OBJ_CLOSED_FORM)
-    return fail(VFM_E_INVALID, "the bound fold-in uses the closed-form moments only (VFM_OBJ_CLOSED_FORM)");
-  if (p->likelihood != VFM_LIK_BERNOULLI)
-    return fail(VFM_E_INVALID, "the bound fold-in needs the Bernoulli likelihood (VFM_LIK_BERNOULLI)");
-  if (p->n_ops < 0 || (p->R > 0 && p->n_ops < 1)) return fail(VFM_E_INVALID, "n_ops out of range");
-  if (p->flags & ~VFM_FLAG_LINK_SOFTPLUS) return fail(VFM_E_INVALID, "flags: only VFM_FLAG_LINK_SOFTPLUS is accepted");
-  if (p->lds_dim < -1) return fail(VFM_E_INVALID, "lds_dim: -1 or >= 0");
-  if (!(p->kl_weight > 0.f) || !(p->kl_weight <= 3.0e38f))
-    return fail(VFM_E_INVALID, "kl_weight must be > 0 and finite (the prior is what makes the system positive definite)");
-  if (p->mode != VFM_FOLDIN_FIT && p->mode != VFM_FOLDIN_OBJECTIVE)
-    return fail(VFM_E_INVALID, "mode: VFM_FOLDIN_FIT or VFM_FOLDIN_OBJECTIVE");
-  if (p->mode == VFM_FOLDIN_FIT && p->n_iters < 1) return fail(VFM_E_INVALID, "n_iters must be >= 1 for a fit");
-  if (p->mode == VFM_FOLDIN_OBJECTIVE && p->n_iters != 0)
-    return fail(VFM_E_INVALID, "n_iters must be 0 in VFM_FOLDIN_OBJECTIVE");
-  if (p->E == 0) return 0;
-  if (!p->entities || !p->row_ptr || !p->entity_params || !p->bias_params || !p->scalars || !p->out_loss ||
-      (p->R > 0 && (!p->y || !p->op_x || !p->row_op)))
-    return fail(VFM_E_INVALID, "null pointer");
+  if (!p) return vfm::fail(VFM_E_INVALID, "vfm_foldin_bound_f32: NULL argument struct");
   const int64_t ws = vfm_foldin_bound_workspace_bytes(p->E, p->R, p->n_ops, p->d, p->lds_dim);
-  if (p->workspace_bytes < ws || (ws > 0 && !p->workspace))
-    return fail(VFM_E_INVALID, "workspace too small (vfm_foldin_bound_workspace_bytes)");
-  if (ws > 0 && (((uintptr_t)p->workspace) & 255)) return fail(VFM_E_INVALID, "workspace must be 256-byte aligned");
+  const auto own = [&]() -> const char* {
+    if (p->objective != VFM_OBJ_CLOSED_FORM)
+      return "the bound fold-in uses the closed-form moments only (VFM_OBJ_CLOSED_FORM)";
+    if (p->likelihood != VFM_LIK_BERNOULLI) return "the bound fold-in needs the Bernoulli likelihood (VFM_LIK_BERNOULLI)";
+    if (p->mode != VFM_FOLDIN_FIT && p->mode != VFM_FOLDIN_OBJECTIVE) return "mode: VFM_FOLDIN_FIT or VFM_FOLDIN_OBJECTIVE";
+    if (p->mode == VFM_FOLDIN_FIT && p->n_iters < 1) return "n_iters must be >= 1 for a fit";
+    return p->mode == VFM_FOLDIN_OBJECTIVE && p->n_iters != 0 ? "n_iters must be 0 in VFM_FOLDIN_OBJECTIVE" : nullptr;
+  };
+  if (int rc = vfm::check_solve(p, p->row_ptr, true, ws, "vfm_foldin_bound_workspace_bytes", own)) return rc;
+  if (p->E == 0) return 0;
 
   const hipStream_t st = (hipStream_t)stream;
   const bool sp = (p->flags & VFM_FLAG_LINK_SOFTPLUS) != 0;
   const vfm::FShape f = vfm::shape_of(p->d);
   vfm::BoundArgs s;
-  vfm::FoldArgs& a = s.f;
-  a = vfm::fill_fold_args(p->E, p->T, p->F, p->d, p->col, VFM_LIK_BERNOULLI, 1, p->n_iters, p->reset != 0, p->mode, 0.f,
-                          p->kl_weight, 0, 0, p->entity_params, p->bias_params, p->scalars);
-  a.R = p->R; a.ent = p->entities; a.ptr = p->row_ptr; a.row_op = p->row_op; a.y = p->y;
-  a.loss = p->out_loss;
+  vfm::fill_bound_args(s, p, p->mode);
+  s.f.ptr = p->row_ptr;
   char* w = (char*)p->workspace;
-  a.ops = (float*)w;
-  a.opc = (float*)(w + vfm::ops_off_opc(p->n_ops, p->d));
-  s.ops64 = (double*)(w + vfm::off_ops64(p->n_ops, p->d));
-  s.cm64 = (double*)(w + vfm::off_cm64(p->n_ops, p->d));
-  double* cv64 = (double*)(w + vfm::off_cv64(p->n_ops, p->d));
-  s.cv64 = cv64;
-  s.wrow = (double*)(w + vfm::off_wrow(p->n_ops, p->d));
-  const unsigned grid = vfm::place_slabs(p->d, p->lds_dim, p->E, w + vfm::off_bound_slabs(p->R, p->n_ops, p->d),
+  const unsigned grid = vfm::place_slabs(p->d, p->lds_dim, p->E, w + vfm::off_bound_own(p->R, p->n_ops, p->d),
                                          (int64_t)1 << 20, s.sl);
   const size_t shm = (size_t)vfm::bound_lds_doubles(p->d, s.sl.cap_dim) * 8;
 
   if (p->n_ops > 0) {
-    if (int rc = vfm::launch_solve_preps(sp, a, p->n_ops, p->op_x, w, st)) return rc;
-    if (int rc = vfm::launch_bound_prep(sp, a, p->n_ops, p->op_x, cv64, st)) return rc;
+    if (int rc = vfm::launch_solve_preps(sp, s.f, p->n_ops, p->op_x, w, st)) return rc;
+    if (int rc = vfm::launch_bound_prep(sp, s.f, p->n_ops, p->op_x, const_cast<double*>(s.cv64), st)) return rc;
   }
   vfm::launch(f, sp, s, grid, shm, st);
   return launch_status("k_foldin_bound");

@@ -66,6 +66,21 @@ inline int launch_bound_prep(bool sp, const FoldArgs& a, int64_t n_ops, const in
   return launch_status("k_foldin_bound_prep");
 }
 
+// what the bound fold-in's workspaces (vfm_foldin_bound.hip, vfm_foldin_bound_split.hip) hold behind the operand block:
+// c_var [n_ops], the row weights [R], then the unit's own
+inline int64_t off_cv64(int64_t n_ops, int d) { return off_slabs(n_ops, d); }
+inline int64_t off_wrow(int64_t n_ops, int d) { return off_cv64(n_ops, d) + round_up(n_ops * 8, 256); }
+inline int64_t off_bound_own(int64_t R, int64_t n_ops, int d) { return off_wrow(n_ops, d) + round_up(R * 8, 256); }
+
+// fill_solve_args for the two bound entries, with cv64 and wrow
+template <class S, class P>
+void fill_bound_args(S& s, const P* p, int mode) {
+  fill_solve_args(s, p, VFM_LIK_BERNOULLI, p->n_iters, p->reset != 0, mode);
+  char* w = (char*)p->workspace;
+  s.cv64 = (double*)(w + off_cv64(p->n_ops, p->d));
+  s.wrow = (double*)(w + off_wrow(p->n_ops, p->d));
+}
+
 // phase E: B_e at the fp32 parameters pf = [mu_w, mu [d] | s_w, s [d]] (LDS), by wave 0; its 64 / W lane groups all
 // hold this entity, lane l of a group owns coordinates j W + l
 template <int W, int CPL, int LINK, class Rows>

@@ -59,9 +59,6 @@ struct BSplitArgs {
   int32_t last;                          // k_bsplit_solve: the last round, the table row is written
 };
 
-// the layout of vfm_foldin_split.hip's slab
-__host__ __device__ inline int64_t part_doubles(int d) { return tri(d + 1) + 4 * (int64_t)d + 3; }
-
 // chunk q's rows, clamped to [0, R)
 __device__ __forceinline__ void chunk_rows_of(const BSplitArgs& s, int64_t q, int64_t& r0, int64_t& n) {
   r0 = min(max(s.chunks[q * 3 + 1], (int64_t)0), s.f.R);
@@ -375,14 +372,10 @@ __global__ __launch_bounds__(FB) void k_bsplit_loss_sum(const BSplitArgs s) {
 }
 
 // the workspace: [operand block | c_var | row weights | iterate | chunk slabs | loss partials | solve slabs]
-inline int64_t off_cv64(int64_t n_ops, int d) { return off_slabs(n_ops, d); }
-inline int64_t off_wrow(int64_t n_ops, int d) { return off_cv64(n_ops, d) + round_up(n_ops * 8, 256); }
-inline int64_t off_iter(int64_t R, int64_t n_ops, int d) { return off_wrow(n_ops, d) + round_up(R * 8, 256); }
+// (vfm_foldin_bound_body.hpp: off_cv64, off_wrow, off_bound_own -- the iterate; vfm_foldin_solve_body.hpp: the rest)
 inline int64_t off_part(int64_t n_heavy, int64_t R, int64_t n_ops, int d) {
-  return off_iter(R, n_ops, d) + round_up(n_heavy * 2 * (int64_t)(d + 1) * 8, 256);
+  return off_bound_own(R, n_ops, d) + round_up(n_heavy * 2 * (int64_t)(d + 1) * 8, 256);
 }
-inline int64_t part_bytes(int64_t n_chunks, int d) { return round_up(n_chunks * part_doubles(d) * 8, 256); }
-inline int64_t lpart_bytes(int64_t n_chunks) { return round_up(n_chunks * 8, 256); }
 
 }  // namespace
 }  // namespace vfm
@@ -400,64 +393,31 @@ int64_t vfm_foldin_bound_split_workspace_bytes(int64_t n_chunks, int64_t n_heavy
 }
 
 int vfm_foldin_bound_split_f32(const vfm_foldin_bound_split_t* p, void* stream) {
-  using vfm::fail;
-  if (!p) return fail(VFM_E_INVALID, "vfm_foldin_bound_split_f32: NULL argument struct");
-  if (p->T < 1) return fail(VFM_E_INVALID, "T < 1");
-  if (p->d < 1 || p->d > VFM_FOLDIN_MAX_D) return fail(VFM_E_INVALID, "d out of range [1,512]");
-  if (p->F < 1 || p->F > VFM_MAX_FIELDS) return fail(VFM_E_INVALID, "F out of range [1,64]");
-  if (p->col < 0 || p->col >= p->F) return fail(VFM_E_INVALID, "col out of range [0,F)");
-  if (p->E < 0 || p->R < 0) return fail(VFM_E_INVALID, "E < 0 or R < 0");
-  if (p->n_chunks < 0) return fail(VFM_E_INVALID, "n_chunks < 0");
-  if (p->n_ops < 0 || (p->R > 0 && p->n_ops < 1)) return fail(VFM_E_INVALID, "n_ops out of range");
-  if (p->flags & ~VFM_FLAG_LINK_SOFTPLUS) return fail(VFM_E_INVALID, "flags: only VFM_FLAG_LINK_SOFTPLUS is accepted");
-  if (p->lds_dim < -1) return fail(VFM_E_INVALID, "lds_dim: -1 or >= 0");
-  if (!(p->kl_weight > 0.f) || !(p->kl_weight <= 3.0e38f))
-    return fail(VFM_E_INVALID, "kl_weight must be > 0 and finite (the prior is what makes the system positive definite)");
-  if (p->n_iters < 1) return fail(VFM_E_INVALID, "n_iters must be >= 1");
-  if (p->E == 0) return 0;
-  if (!p->entities || !p->chunk_ptr || !p->entity_params || !p->bias_params || !p->scalars || !p->out_loss ||
-      (p->n_chunks > 0 && !p->chunks) || (p->R > 0 && (!p->y || !p->op_x || !p->row_op)))
-    return fail(VFM_E_INVALID, "null pointer");
+  if (!p) return vfm::fail(VFM_E_INVALID, "vfm_foldin_bound_split_f32: NULL argument struct");
   const int64_t ws = vfm_foldin_bound_split_workspace_bytes(p->n_chunks, p->E, p->R, p->n_ops, p->d, p->lds_dim);
-  if (ws < 0) return fail(VFM_E_INVALID, "sizes out of range (vfm_foldin_bound_split_workspace_bytes)");
-  if (p->workspace_bytes < ws || (ws > 0 && !p->workspace))
-    return fail(VFM_E_INVALID, "workspace too small (vfm_foldin_bound_split_workspace_bytes)");
-  if (ws > 0 && (((uintptr_t)p->workspace) & 255)) return fail(VFM_E_INVALID, "workspace must be 256-byte aligned");
+  const auto own = [&]() -> const char* {
+    if (p->n_chunks < 0) return "n_chunks < 0";
+    return p->n_iters < 1 ? "n_iters must be >= 1" : nullptr;
+  };
+  if (int rc = vfm::check_solve(p, p->chunk_ptr, p->n_chunks <= 0 || p->chunks, ws, "vfm_foldin_bound_split_workspace_bytes",
+                                own))
+    return rc;
+  if (p->E == 0) return 0;
 
   const hipStream_t st = (hipStream_t)stream;
   const bool sp = (p->flags & VFM_FLAG_LINK_SOFTPLUS) != 0;
   const vfm::FShape f = vfm::shape_of(p->d);
   vfm::BSplitArgs s = {};
-  vfm::FoldArgs& a = s.f;
-  a = vfm::fill_fold_args(p->E, p->T, p->F, p->d, p->col, VFM_LIK_BERNOULLI, 1, p->n_iters, p->reset != 0, VFM_FOLDIN_FIT,
-                          0.f, p->kl_weight, 0, 0, p->entity_params, p->bias_params, p->scalars);
-  a.R = p->R; a.ent = p->entities; a.row_op = p->row_op; a.y = p->y;
-  a.loss = p->out_loss;
+  vfm::fill_bound_args(s, p, VFM_FOLDIN_FIT);
+  const vfm::FoldArgs& a = s.f;
   char* w = (char*)p->workspace;
-  a.ops = (float*)w;
-  a.opc = (float*)(w + vfm::ops_off_opc(p->n_ops, p->d));
-  s.ops64 = (double*)(w + vfm::off_ops64(p->n_ops, p->d));
-  s.cm64 = (double*)(w + vfm::off_cm64(p->n_ops, p->d));
-  double* cv64 = (double*)(w + vfm::off_cv64(p->n_ops, p->d));
-  s.cv64 = cv64;
-  s.wrow = (double*)(w + vfm::off_wrow(p->n_ops, p->d));
-  s.iter = (double*)(w + vfm::off_iter(p->R, p->n_ops, p->d));
-  s.chunk_ptr = p->chunk_ptr; s.chunks = p->chunks;
-  s.n_ops = p->n_ops; s.n_chunks = p->n_chunks;
-  s.part_elems = vfm::part_doubles(p->d);
-  const int64_t off_part = vfm::off_part(p->E, p->R, p->n_ops, p->d);
-  const int64_t off_lpart = off_part + vfm::part_bytes(p->n_chunks, p->d);
-  s.part = (double*)(w + off_part);
-  s.lpart = (double*)(w + off_lpart);
-  const int64_t gcap = (int64_t)1 << 20;
-  const unsigned grid_e =
-      vfm::place_slabs(p->d, p->lds_dim, p->E, w + off_lpart + vfm::lpart_bytes(p->n_chunks), gcap, s.sl);
-  const unsigned grid_c = (unsigned)(p->n_chunks < gcap ? p->n_chunks : gcap);
+  s.iter = (double*)(w + vfm::off_bound_own(p->R, p->n_ops, p->d));
+  const vfm::SplitGrids grid = vfm::place_split(s, p, w + vfm::off_part(p->E, p->R, p->n_ops, p->d));
   const size_t shm = (size_t)vfm::lds_doubles(p->d, s.sl.cap_dim) * 8;
 
   if (p->n_ops > 0) {
     if (int rc = vfm::launch_solve_preps(sp, a, p->n_ops, p->op_x, w, st)) return rc;
-    if (int rc = vfm::launch_bound_prep(sp, a, p->n_ops, p->op_x, cv64, st)) return rc;
+    if (int rc = vfm::launch_bound_prep(sp, a, p->n_ops, p->op_x, const_cast<double*>(s.cv64), st)) return rc;
   }
   const int64_t n_it = p->E * (int64_t)(p->d + 1);
   vfm::for_link(sp, [&](auto link) {
@@ -468,15 +428,11 @@ int vfm_foldin_bound_split_f32(const vfm_foldin_bound_split_t* p, void* stream) 
   for (int it = 0; it < p->n_iters; ++it) {
     s.last = it == p->n_iters - 1;
     if (p->n_chunks > 0) {
-      hipLaunchKernelGGL(vfm::k_bsplit_assemble, dim3(grid_c), dim3(vfm::FB), 0, st, s);
+      hipLaunchKernelGGL(vfm::k_bsplit_assemble, dim3(grid.c), dim3(vfm::FB), 0, st, s);
       if (int rc = launch_status("k_bsplit_assemble")) return rc;
     }
     vfm::for_link(sp, [&](auto link) {
-      const auto k = vfm::k_bsplit_solve<decltype(link)::value>;
-      // (more than 64 KiB of dynamic LDS: state the size; a runtime that needs no opt-in ignores it)
-      (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      (void)hipGetLastError();
-      hipLaunchKernelGGL(k, dim3(grid_e), dim3(vfm::FB), shm, st, s);
+      vfm::launch_lds(vfm::k_bsplit_solve<decltype(link)::value>, grid.e, shm, st, s);
     });
     if (int rc = launch_status("k_bsplit_solve")) return rc;
   }
@@ -484,7 +440,7 @@ int vfm_foldin_bound_split_f32(const vfm_foldin_bound_split_t* p, void* stream) 
     vfm::for_link(sp, [&](auto link) {
       vfm::for_shape(f, [&](auto wd, auto c) {
         hipLaunchKernelGGL((vfm::k_bsplit_loss<decltype(wd)::value, decltype(c)::value, decltype(link)::value>),
-                           dim3(grid_c), dim3(64), 0, st, s);
+                           dim3(grid.c), dim3(64), 0, st, s);
       });
     });
     if (int rc = launch_status("k_bsplit_loss")) return rc;

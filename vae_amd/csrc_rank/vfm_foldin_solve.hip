@@ -97,11 +97,7 @@ template <bool PRIOR>
 void launch(const FShape& f, bool sp, const SolveArgs& s, unsigned grid, size_t shm, hipStream_t st) {
   for_link(sp, [&](auto link) {
     for_shape(f, [&](auto w, auto c) {
-      const auto k = k_foldin_solve<decltype(w)::value, decltype(c)::value, decltype(link)::value, PRIOR>;
-      // (more than 64 KiB of dynamic LDS: state the size; a runtime that needs no opt-in ignores it)
-      (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      (void)hipGetLastError();
-      hipLaunchKernelGGL(k, dim3(grid), dim3(FB), shm, st, s);
+      launch_lds(k_foldin_solve<decltype(w)::value, decltype(c)::value, decltype(link)::value, PRIOR>, grid, shm, st, s);
     });
   });
 }
@@ -132,53 +128,30 @@ int vfm_foldin_solve_prior_f32(const vfm_foldin_solve_t* p, const float* prior, 
 
 // both entry points: prior == NULL is vfm_foldin_solve_f32
 static int solve_call(const vfm_foldin_solve_t* p, const float* prior, void* stream) {
-  using vfm::fail;
-  if (!p) return fail(VFM_E_INVALID, "vfm_foldin_solve_f32: NULL argument struct");
-  if (p->T < 1) return fail(VFM_E_INVALID, "T < 1");
-  if (p->d < 1 || p->d > VFM_FOLDIN_MAX_D) return fail(VFM_E_INVALID, "d out of range [1,512]");
-  if (p->F < 1 || p->F > VFM_MAX_FIELDS) return fail(VFM_E_INVALID, "F out of range [1,64]");
-  if (p->col < 0 || p->col >= p->F) return fail(VFM_E_INVALID, "col out of range [0,F)");
-  if (p->E < 0 || p->R < 0) return fail(VFM_E_INVALID, "E < 0 or R < 0");
-  if (p->objective != VFM_OBJ_CLOSED_FORM)
-    return fail(VFM_E_INVALID, "the exact fold-in solves the closed-form objective only (VFM_OBJ_CLOSED_FORM)");
-  if (p->likelihood != VFM_LIK_NORMAL) return fail(VFM_E_INVALID, "the closed form needs the Normal likelihood");
-  if (p->n_ops < 0 || (p->R > 0 && p->n_ops < 1)) return fail(VFM_E_INVALID, "n_ops out of range");
-  if (p->flags & ~VFM_FLAG_LINK_SOFTPLUS) return fail(VFM_E_INVALID, "flags: only VFM_FLAG_LINK_SOFTPLUS is accepted");
-  if (p->lds_dim < -1) return fail(VFM_E_INVALID, "lds_dim: -1 or >= 0");
-  if (!(p->kl_weight > 0.f) || !(p->kl_weight <= 3.0e38f))
-    return fail(VFM_E_INVALID, "kl_weight must be > 0 and finite (the prior is what makes the system positive definite)");
-  if (p->E == 0) return 0;
-  if (!p->entities || !p->row_ptr || !p->entity_params || !p->bias_params || !p->scalars || !p->out_loss ||
-      (p->R > 0 && (!p->y || !p->op_x || !p->row_op)))
-    return fail(VFM_E_INVALID, "null pointer");
+  if (!p) return vfm::fail(VFM_E_INVALID, "vfm_foldin_solve_f32: NULL argument struct");
   const int64_t ws = vfm_foldin_solve_workspace_bytes(p->E, p->n_ops, p->d, p->lds_dim);
-  if (p->workspace_bytes < ws || (ws > 0 && !p->workspace))
-    return fail(VFM_E_INVALID, "workspace too small (vfm_foldin_solve_workspace_bytes)");
-  if (ws > 0 && (((uintptr_t)p->workspace) & 255)) return fail(VFM_E_INVALID, "workspace must be 256-byte aligned");
+  const auto own = [&]() -> const char* {
+    if (p->objective != VFM_OBJ_CLOSED_FORM)
+      return "the exact fold-in solves the closed-form objective only (VFM_OBJ_CLOSED_FORM)";
+    return p->likelihood != VFM_LIK_NORMAL ? "the closed form needs the Normal likelihood" : nullptr;
+  };
+  if (int rc = vfm::check_solve(p, p->row_ptr, true, ws, "vfm_foldin_solve_workspace_bytes", own)) return rc;
+  if (p->E == 0) return 0;
 
   const hipStream_t st = (hipStream_t)stream;
   const bool sp = (p->flags & VFM_FLAG_LINK_SOFTPLUS) != 0;
   const vfm::FShape f = vfm::shape_of(p->d);
   vfm::SolveArgs s;
-  vfm::FoldArgs& a = s.f;
-  a = vfm::fill_fold_args(p->E, p->T, p->F, p->d, p->col, VFM_LIK_NORMAL, 1, 0, 0, VFM_FOLDIN_FIT, 0.f, p->kl_weight, 0, 0,
-                          p->entity_params, p->bias_params, p->scalars);
-  a.R = p->R; a.ent = p->entities; a.ptr = p->row_ptr; a.row_op = p->row_op; a.y = p->y;
-  a.loss = p->out_loss;
+  vfm::fill_solve_args(s, p, VFM_LIK_NORMAL, 0, 0, VFM_FOLDIN_FIT);
+  s.f.ptr = p->row_ptr;
   char* w = (char*)p->workspace;
-  const int64_t off_opc = vfm::ops_off_opc(p->n_ops, p->d);
-  float* ops = (float*)w;
-  float* opc = (float*)(w + off_opc);
-  a.ops = ops; a.opc = opc;
-  s.ops64 = (double*)(w + vfm::off_ops64(p->n_ops, p->d));
-  s.cm64 = (double*)(w + vfm::off_cm64(p->n_ops, p->d));
   const unsigned grid =
       vfm::place_slabs(p->d, p->lds_dim, p->E, w + vfm::off_slabs(p->n_ops, p->d), (int64_t)1 << 20, s.sl);
   s.prior = prior;
   const size_t shm = (size_t)(prior ? vfm::lds_doubles_prior(p->d, s.sl.cap_dim) : vfm::lds_doubles(p->d, s.sl.cap_dim)) * 8;
 
   if (p->n_ops > 0) {
-    if (int rc = vfm::launch_solve_preps(sp, a, p->n_ops, p->op_x, w, st)) return rc;
+    if (int rc = vfm::launch_solve_preps(sp, s.f, p->n_ops, p->op_x, w, st)) return rc;
   }
   if (prior) vfm::launch<true>(f, sp, s, grid, shm, st);
   else vfm::launch<false>(f, sp, s, grid, shm, st);

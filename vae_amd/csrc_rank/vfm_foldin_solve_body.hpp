@@ -320,7 +320,8 @@ __device__ __forceinline__ void solve_body(const FoldArgs& a, const double* ops6
 
 // ---------------------------------------------------------------------------------------------------------------------
 // host side: the LDS rule of the triangle, the slabs, the operand block both units put in their workspace
-// [fp32 operands | their constants | fp64 operands | fp64 c_mean | slabs], and the two operand passes
+// [fp32 operands | their constants | fp64 operands | fp64 c_mean | slabs], the two operand passes, and what the four
+// solve entry points do alike: the checks, the FoldArgs fill, the launch with dynamic LDS, the split units' placement
 // ---------------------------------------------------------------------------------------------------------------------
 inline int cap_dim_of(int d, int lds_dim) {
   const int fit = d + 1 < VFM_FOLDIN_SOLVE_LDS_DIM ? d + 1 : VFM_FOLDIN_SOLVE_LDS_DIM;
@@ -370,4 +371,89 @@ inline int launch_solve_preps(bool sp, const FoldArgs& a, int64_t n_ops, const i
                        op_x, a.entity, a.bias, a.scal, ops64, cm64);
   });
   return launch_status("k_foldin_solve_prep");
+}
+
+// ---- what the four solve entry points (vfm_foldin_solve.hip, vfm_foldin_split.hip, vfm_foldin_bound.hip,
+// vfm_foldin_bound_split.hip) do alike; P: the entry's C struct, S: its kernel-argument struct
+
+// The checks of *p, p not NULL: the scalars, then own() -- the entry's own checks, a message or NULL -- and, for
+// E > 0, the pointers (list: row_ptr or chunk_ptr; chunks: false only when a chunk table with rows is missing) and the
+// workspace against ws, the value of the size function named ws_fn.  0 with E == 0: nothing to do.
+template <class P, class Own>
+int check_solve(const P* p, const void* list, bool chunks, int64_t ws, const char* ws_fn, Own own) {
+  if (p->T < 1) return fail(VFM_E_INVALID, "T < 1");
+  if (p->d < 1 || p->d > VFM_FOLDIN_MAX_D) return fail(VFM_E_INVALID, "d out of range [1,512]");
+  if (p->F < 1 || p->F > VFM_MAX_FIELDS) return fail(VFM_E_INVALID, "F out of range [1,64]");
+  if (p->col < 0 || p->col >= p->F) return fail(VFM_E_INVALID, "col out of range [0,F)");
+  if (p->E < 0 || p->R < 0) return fail(VFM_E_INVALID, "E < 0 or R < 0");
+  if (p->n_ops < 0 || (p->R > 0 && p->n_ops < 1)) return fail(VFM_E_INVALID, "n_ops out of range");
+  if (p->flags & ~VFM_FLAG_LINK_SOFTPLUS) return fail(VFM_E_INVALID, "flags: only VFM_FLAG_LINK_SOFTPLUS is accepted");
+  if (p->lds_dim < -1) return fail(VFM_E_INVALID, "lds_dim: -1 or >= 0");
+  if (!(p->kl_weight > 0.f) || !(p->kl_weight <= 3.0e38f))
+    return fail(VFM_E_INVALID, "kl_weight must be > 0 and finite (the prior is what makes the system positive definite)");
+  if (const char* msg = own()) return fail(VFM_E_INVALID, msg);
+  if (p->E == 0) return 0;
+  if (!p->entities || !list || !p->entity_params || !p->bias_params || !p->scalars || !p->out_loss || !chunks ||
+      (p->R > 0 && (!p->y || !p->op_x || !p->row_op)))
+    return fail(VFM_E_INVALID, "null pointer");
+  char msg[96];
+  if (ws < 0) {
+    snprintf(msg, sizeof(msg), "sizes out of range (%s)", ws_fn);
+    return fail(VFM_E_INVALID, msg);
+  }
+  if (p->workspace_bytes < ws || (ws > 0 && !p->workspace)) {
+    snprintf(msg, sizeof(msg), "workspace too small (%s)", ws_fn);
+    return fail(VFM_E_INVALID, msg);
+  }
+  if (ws > 0 && (((uintptr_t)p->workspace) & 255)) return fail(VFM_E_INVALID, "workspace must be 256-byte aligned");
+  return 0;
+}
+
+// s.f for a solve of p's rows (a.ptr stays NULL: the entries with a row list set it) and the operand block at the head
+// of p's workspace
+template <class S, class P>
+void fill_solve_args(S& s, const P* p, int lik, int n_iters, int reset, int mode) {
+  FoldArgs& a = s.f;
+  a = fill_fold_args(p->E, p->T, p->F, p->d, p->col, lik, 1, n_iters, reset, mode, 0.f, p->kl_weight, 0, 0,
+                     p->entity_params, p->bias_params, p->scalars);
+  a.R = p->R; a.ent = p->entities; a.row_op = p->row_op; a.y = p->y;
+  a.loss = p->out_loss;
+  char* w = (char*)p->workspace;
+  a.ops = (float*)w;
+  a.opc = (float*)(w + ops_off_opc(p->n_ops, p->d));
+  s.ops64 = (double*)(w + off_ops64(p->n_ops, p->d));
+  s.cm64 = (double*)(w + off_cm64(p->n_ops, p->d));
+}
+
+// a kernel of FB threads with shm bytes of dynamic LDS (more than 64 KiB: state the size first; a runtime that needs no
+// opt-in ignores it)
+template <class K, class S>
+void launch_lds(K k, unsigned grid, size_t shm, hipStream_t st, const S& s) {
+  (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k, dim3(grid), dim3(FB), shm, st, s);
+}
+
+// ---- the two split units: a slab of part_doubles(d) per chunk [triangle tri(d + 1) | SA [d + 1] | SB [d + 1] |
+// sum t u [d + 1] | SC [d]], a loss partial per chunk, then the solve slabs
+inline int64_t part_doubles(int d) { return tri(d + 1) + 4 * (int64_t)d + 3; }
+inline int64_t part_bytes(int64_t n_chunks, int d) { return round_up(n_chunks * part_doubles(d) * 8, 256); }
+inline int64_t lpart_bytes(int64_t n_chunks) { return round_up(n_chunks * 8, 256); }
+
+struct SplitGrids {
+  unsigned c, e;                         // a workgroup per chunk, per entity
+};
+
+// p's chunk table and, from `base` on, part, lpart and the solve slabs into s
+template <class S, class P>
+SplitGrids place_split(S& s, const P* p, char* base) {
+  s.chunk_ptr = p->chunk_ptr; s.chunks = p->chunks;
+  s.n_ops = p->n_ops; s.n_chunks = p->n_chunks;
+  s.part_elems = part_doubles(p->d);
+  s.part = (double*)base;
+  base += part_bytes(p->n_chunks, p->d);
+  s.lpart = (double*)base;
+  const int64_t gcap = (int64_t)1 << 20;
+  const unsigned grid_e = place_slabs(p->d, p->lds_dim, p->E, base + lpart_bytes(p->n_chunks), gcap, s.sl);
+  return {(unsigned)(p->n_chunks < gcap ? p->n_chunks : gcap), grid_e};
 }

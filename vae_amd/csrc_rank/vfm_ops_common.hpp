@@ -1,6 +1,6 @@
 // vfm_ops_common.hpp -- what the TORCH_LIBRARY fragments of this directory (vfm_*_ops.cpp) share: the tensor checks,
-// and the parts of a session struct that every session form names alike, each checked and filled in one place.  Host
-// C++ for the shim only: no .hip unit includes it.
+// and the parts of a session struct and of a fold-in struct that every form names alike, each checked and filled in one
+// place.  Host C++ for the shim only: no .hip unit includes it.
 #pragma once
 
 #include <ATen/ATen.h>
@@ -121,6 +121,52 @@ void fill_session_outputs(S& p, int64_t n_rounds, const Tensor& out_row, const T
     p.out_mean = out_mean->data_ptr<float>();
     p.out_var = out_var->data_ptr<float>();
   }
+}
+
+// ---- the parts of a fold-in struct S (vfm_foldin_solve_t, vfm_foldin_split_t, vfm_foldin_bound_t,
+// vfm_foldin_bound_split_t; vfm_foldin_t takes the row list), after a memset.  The rows come first: they set E.
+
+// the folded ids, the rows' targets and operands and the loss: E, R, F, n_ops and the five pointers
+template <class S>
+void fill_fold_rows(S& p, const Tensor& entities, const Tensor& y, const Tensor& op_x, const Tensor& row_op,
+                    const Tensor& loss) {
+  dev_tensor(entities, at::kLong, "entities"); dev_tensor(y, at::kFloat, "y");
+  dev_tensor(op_x, at::kLong, "op_x"); dev_tensor(row_op, at::kLong, "row_op"); dev_tensor(loss, at::kFloat, "loss");
+  TORCH_CHECK(op_x.dim() == 2 && row_op.numel() == y.numel(), "op_x must be [n_ops, F], row_op [R] with y [R]");
+  TORCH_CHECK(loss.numel() >= entities.numel(), "loss [E]");
+  p.E = entities.numel(); p.R = y.numel(); p.F = (int32_t)op_x.size(1); p.n_ops = op_x.size(0);
+  p.entities = entities.data_ptr<int64_t>(); p.y = y.data_ptr<float>();
+  p.op_x = op_x.data_ptr<int64_t>(); p.row_op = row_op.data_ptr<int64_t>(); p.out_loss = loss.data_ptr<float>();
+}
+
+// the row list of the p.E ids
+template <class S>
+void fill_row_list(S& p, const Tensor& row_ptr) {
+  TORCH_CHECK(dev_tensor(row_ptr, at::kLong, "row_ptr").numel() == p.E + 1, "row_ptr [E + 1]");
+  p.row_ptr = row_ptr.data_ptr<int64_t>();
+}
+
+// the chunk table of the p.E ids: n_chunks and the two pointers
+template <class S>
+void fill_chunk_table(S& p, const Tensor& chunk_ptr, const Tensor& chunks) {
+  dev_tensor(chunk_ptr, at::kLong, "chunk_ptr"); dev_tensor(chunks, at::kLong, "chunks");
+  TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 3, "chunks must be [n_chunks, 3]");
+  TORCH_CHECK(chunk_ptr.numel() == p.E + 1, "chunk_ptr [E + 1]");
+  p.n_chunks = chunks.size(0);
+  p.chunk_ptr = chunk_ptr.data_ptr<int64_t>(); p.chunks = chunks.data_ptr<int64_t>();
+}
+
+// the folded field's prior, mean | precision, for tables of width d (fill_tables)
+inline const float* prior_of(const Tensor& prior, int64_t d) {
+  dev_tensor(prior, at::kFloat, "prior");
+  TORCH_CHECK(prior.dim() == 2 && prior.size(0) == 2 && prior.size(1) == d + 1, "prior must be [2, d + 1]");
+  return prior.data_ptr<float>();
+}
+
+// a *_workspace_bytes result: negative is the library's "bad arguments"
+inline int64_t checked_bytes(int64_t b, const char* what) {
+  TORCH_CHECK(b >= 0, what, ": bad arguments");
+  return b;
 }
 
 }  // namespace vfm_ops

@@ -115,33 +115,47 @@ def partner_tuples(xs, field):
     return u.contiguous(), inv.contiguous()
 
 
-def run(model, X, y, field=0, objective=None, n_samples=1, seed=0, kl_weight=1.0, mode=MODE_FIT, n_steps=0, lr=0.0,
-        reset=False, t0=0, lds_rows=-1):
-    """One fold-in launch.  Returns (entities [E], loss [E], rows [E], grad [E, 2d + 2] or None)."""
-    x, y, objective = check_args(model, X, y, field, objective, n_samples, n_steps, lr, kl_weight)
+def _link_flags(model):
+    return ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0
+
+
+def _launch(model, x, y, field, ws_bytes, call, tuples=True, grad=False, writes=True):
+    """The host path of the three fold-in forms over checked rows: the row lists, the outputs, the partner tuples and
+    the workspace of ws_bytes(o, E, R, n_ops) bytes where the form has them (`tuples`), the table views and one op call,
+    call(o, a, xs, grad, flags) with a = (entities, row_ptr, ys, op_x, row_op, entity, bias, scalars, workspace, loss):
+    the leading arguments of every solve op.  Returns (entities [E], loss [E], rows [E], grad [E, 2d + 2] or None)."""
     ops._need_cuda(model._flat, "the model's parameters")
     dev, d = model.device, model.d
     xs, ys, ents, ptr, counts = row_lists(x, y, field)
     E = ents.numel()
     loss = torch.empty(E, dtype=torch.float32, device=dev)
-    grad = torch.empty(E, 2 * d + 2, dtype=torch.float32, device=dev) if mode == MODE_OBJECTIVE else None
+    g = torch.empty(E, 2 * d + 2, dtype=torch.float32, device=dev) if grad else None
     if E == 0:
-        return ents, loss, counts, grad
-    code = OBJECTIVES[objective]
+        return ents, loss, counts, g
     o = _lib.ops()
     op_x = row_op = ws = None
-    if objective == "closed_form":
+    if tuples:
         op_x, row_op = partner_tuples(xs, field)
-        ws = torch.empty(max(o.foldin_workspace_bytes(op_x.shape[0], d, code), 1), dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(ws_bytes(o, E, ys.numel(), op_x.shape[0]), 1), dtype=torch.uint8, device=dev)
     model._fresh_params()
     ent, bia, scal = model._views(model._flat)
-    lik = _lib.LIK_NORMAL if model.output == "reg" else _lib.LIK_BERNOULLI
-    o.foldin(ents, ptr, xs, ys, op_x, row_op, ent, bia, scal, ws, loss, grad, int(field), code, lik,
-             ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, int(mode), int(n_steps), int(n_samples),
-             int(bool(reset)), int(lds_rows), float(lr), float(kl_weight), _seed64(seed), int(t0))
-    if mode == MODE_FIT:
+    call(o, (ents, ptr, ys, op_x, row_op, ent, bia, scal, ws, loss), xs, g, _link_flags(model))
+    if writes:
         model.params_changed()          # (rows written outside the step kernels: derived caches are stale)
-    return ents, loss, counts, grad
+    return ents, loss, counts, g
+
+
+def run(model, X, y, field=0, objective=None, n_samples=1, seed=0, kl_weight=1.0, mode=MODE_FIT, n_steps=0, lr=0.0,
+        reset=False, t0=0, lds_rows=-1):
+    """One fold-in launch.  Returns (entities [E], loss [E], rows [E], grad [E, 2d + 2] or None)."""
+    x, y, objective = check_args(model, X, y, field, objective, n_samples, n_steps, lr, kl_weight)
+    code, d = OBJECTIVES[objective], model.d
+    lik = _lib.LIK_NORMAL if model.output == "reg" else _lib.LIK_BERNOULLI
+    return _launch(model, x, y, field, lambda o, E, R, n_ops: o.foldin_workspace_bytes(n_ops, d, code),
+                   lambda o, a, xs, grad, flags: o.foldin(
+                       *a[:2], xs, *a[2:], grad, int(field), code, lik, flags, int(mode), int(n_steps), int(n_samples),
+                       int(bool(reset)), int(lds_rows), float(lr), float(kl_weight), _seed64(seed), int(t0)),
+                   tuples=objective == "closed_form", grad=mode == MODE_OBJECTIVE, writes=mode == MODE_FIT)
 
 
 def check_args_exact(model, X, y, field, kl_weight=1.0):
@@ -163,29 +177,17 @@ def run_exact(model, X, y, field=0, kl_weight=1.0, lds_dim=-1, priors=None):
         from . import sweep
         sweep.check_priors(model, priors)
     _check_lds_dim(lds_dim)
-    ops._need_cuda(model._flat, "the model's parameters")
-    dev, d = model.device, model.d
-    xs, ys, ents, ptr, counts = row_lists(x, y, field)
-    E = ents.numel()
-    loss = torch.empty(E, dtype=torch.float32, device=dev)
-    if E == 0:
-        return ents, loss, counts
-    o = _lib.ops()
-    op_x, row_op = partner_tuples(xs, field)
-    ws = torch.empty(max(o.foldin_solve_workspace_bytes(E, op_x.shape[0], d, int(lds_dim)), 1), dtype=torch.uint8,
-                     device=dev)
-    model._fresh_params()
-    ent, bia, scal = model._views(model._flat)
-    flags = ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0
-    if priors is None:
-        o.foldin_solve(ents, ptr, ys, op_x, row_op, ent, bia, scal, ws, loss, int(field), OBJECTIVES["closed_form"],
-                       _lib.LIK_NORMAL, flags, int(lds_dim), float(kl_weight))
-    else:
-        o.foldin_solve_prior(ents, ptr, ys, op_x, row_op, ent, bia, scal, ws, loss, priors.row(int(field)).to(dev),
-                             int(field), OBJECTIVES["closed_form"], _lib.LIK_NORMAL, flags, int(lds_dim),
-                             float(kl_weight))
-    model.params_changed()              # (rows written outside the step kernels: derived caches are stale)
-    return ents, loss, counts
+    d, tail = model.d, (int(field), OBJECTIVES["closed_form"], _lib.LIK_NORMAL)
+    prior = None if priors is None else priors.row(int(field)).to(model.device)
+
+    def call(o, a, xs, grad, flags):
+        if prior is None:
+            o.foldin_solve(*a, *tail, flags, int(lds_dim), float(kl_weight))
+        else:
+            o.foldin_solve_prior(*a, prior, *tail, flags, int(lds_dim), float(kl_weight))
+
+    return _launch(model, x, y, field, lambda o, E, R, n_ops: o.foldin_solve_workspace_bytes(E, n_ops, d, int(lds_dim)),
+                   call)[:3]
 
 
 def objective_under_prior(model, ents, loss, grad, prior, kl_weight):
@@ -231,22 +233,10 @@ def run_bound(model, X, y, field=0, kl_weight=1.0, n_iters=8, reset=False, lds_d
     written; n_iters is not used).  Returns (entities [E], loss [E] = B_e, rows [E])."""
     x, y = check_args_bound(model, X, y, field, kl_weight, n_iters)
     _check_lds_dim(lds_dim)
-    ops._need_cuda(model._flat, "the model's parameters")
-    dev, d = model.device, model.d
-    xs, ys, ents, ptr, counts = row_lists(x, y, field)
-    E = ents.numel()
-    loss = torch.empty(E, dtype=torch.float32, device=dev)
-    if E == 0:
-        return ents, loss, counts
-    o = _lib.ops()
-    op_x, row_op = partner_tuples(xs, field)
-    ws = torch.empty(max(o.foldin_bound_workspace_bytes(E, ys.numel(), op_x.shape[0], d, int(lds_dim)), 1),
-                     dtype=torch.uint8, device=dev)
-    model._fresh_params()
-    ent, bia, scal = model._views(model._flat)
-    o.foldin_bound(ents, ptr, ys, op_x, row_op, ent, bia, scal, ws, loss, int(field), OBJECTIVES["closed_form"],
-                   _lib.LIK_BERNOULLI, ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0, int(lds_dim),
-                   float(kl_weight), int(n_iters) if mode == MODE_FIT else 0, int(bool(reset)), int(mode))
-    if mode == MODE_FIT:
-        model.params_changed()          # (rows written outside the step kernels: derived caches are stale)
-    return ents, loss, counts
+    d = model.d
+    return _launch(model, x, y, field,
+                   lambda o, E, R, n_ops: o.foldin_bound_workspace_bytes(E, R, n_ops, d, int(lds_dim)),
+                   lambda o, a, xs, grad, flags: o.foldin_bound(
+                       *a, int(field), OBJECTIVES["closed_form"], _lib.LIK_BERNOULLI, flags, int(lds_dim),
+                       float(kl_weight), int(n_iters) if mode == MODE_FIT else 0, int(bool(reset)), int(mode)),
+                   writes=mode == MODE_FIT)[:3]

@@ -204,71 +204,63 @@ class SweepPlan:
             cptr, tab = chunk_table(first[a:b], cnt[a:b], self.chunk_rows)
             self.groups.append((a, b, torch.from_numpy(cptr).to(dev), torch.from_numpy(np.ascontiguousarray(tab)).to(dev)))
 
+    def _solve(self, model, kl_weight, light, split, lik, rows=(), mid=(), tail=()):
+        """One pass over the plan: the light entities in one call, then a call per group of heavy ones.  light, split:
+        the form's (workspace-size op, solve op) pairs; lik: the light op's likelihood; rows: what the size ops take
+        between the entity counts and n_ops; mid: what the solve ops take behind the loss (the prior); tail: behind
+        kl_weight (the bound's n_iters and reset).  Returns (entities [E] ascending, loss [E], rows [E])."""
+        dev = model.device
+        loss = torch.empty(self.E, dtype=torch.float32, device=dev)
+        if self.E == 0:
+            return self.ents, loss, self.counts
+        model._fresh_params()
+        data = (self.ys, self.op_x, self.row_op, *model._views(model._flat))
+        opts = (foldin._link_flags(model), self.lds_dim, float(kl_weight), *tail)
+
+        def workspace(size, *counts):
+            n = size(*counts, *rows, self.op_x.shape[0], self.d, self.lds_dim)
+            return torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+
+        if self.n_light:
+            nl = self.n_light
+            light[1](self.ents[:nl], self.ptr[:nl + 1], *data, workspace(light[0], nl), loss[:nl], *mid, self.field,
+                     foldin.OBJECTIVES["closed_form"], lik, *opts)
+        for a, b, cptr, tab in self.groups:
+            split[1](self.ents[a:b], cptr, tab, *data, workspace(split[0], tab.shape[0], b - a), loss[a:b], *mid,
+                     self.field, *opts)
+        model.params_changed()              # (rows written outside the step kernels: derived caches are stale)
+        return self.ents[self.asc], loss[self.asc], self.counts[self.asc]
+
     def run(self, model, kl_weight, prior=None):
         """Write the exact optimum of every entity of the plan into the model's tables.  prior: None (N(0, 1), the parent
         entry points) or the folded field's [2, d + 1] fp32 mean | precision on the device (include/vfm_prior.h).
         Returns (entities [E] ascending, loss [E], rows [E])."""
-        dev, d = model.device, self.d
-        loss = torch.empty(self.E, dtype=torch.float32, device=dev)
-        if self.E == 0:
-            return self.ents, loss, self.counts
         o = _lib.ops()
-        model._fresh_params()
-        ent, bia, scal = model._views(model._flat)
-        flags = ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0
-        n_ops = self.op_x.shape[0]
-        if self.n_light:
-            nl = self.n_light
-            ws = torch.empty(max(o.foldin_solve_workspace_bytes(nl, n_ops, d, self.lds_dim), 1), dtype=torch.uint8,
-                             device=dev)
-            if prior is None:
-                o.foldin_solve(self.ents[:nl], self.ptr[:nl + 1], self.ys, self.op_x, self.row_op, ent, bia, scal, ws,
-                               loss[:nl], self.field, foldin.OBJECTIVES["closed_form"], _lib.LIK_NORMAL, flags,
-                               self.lds_dim, float(kl_weight))
-            else:
-                o.foldin_solve_prior(self.ents[:nl], self.ptr[:nl + 1], self.ys, self.op_x, self.row_op, ent, bia, scal,
-                                     ws, loss[:nl], prior, self.field, foldin.OBJECTIVES["closed_form"], _lib.LIK_NORMAL,
-                                     flags, self.lds_dim, float(kl_weight))
-        for a, b, cptr, tab in self.groups:
-            ws = torch.empty(max(o.foldin_split_workspace_bytes(tab.shape[0], b - a, n_ops, d, self.lds_dim), 1),
-                             dtype=torch.uint8, device=dev)
-            if prior is None:
-                o.foldin_solve_split(self.ents[a:b], cptr, tab, self.ys, self.op_x, self.row_op, ent, bia, scal, ws,
-                                     loss[a:b], self.field, flags, self.lds_dim, float(kl_weight))
-            else:
-                o.foldin_solve_split_prior(self.ents[a:b], cptr, tab, self.ys, self.op_x, self.row_op, ent, bia, scal,
-                                           ws, loss[a:b], prior, self.field, flags, self.lds_dim, float(kl_weight))
-        model.params_changed()              # (rows written outside the step kernels: derived caches are stale)
-        return self.ents[self.asc], loss[self.asc], self.counts[self.asc]
+        light, split, mid = ((o.foldin_solve, o.foldin_solve_split, ()) if prior is None else
+                             (o.foldin_solve_prior, o.foldin_solve_split_prior, (prior,)))
+        return self._solve(model, kl_weight, (o.foldin_solve_workspace_bytes, light),
+                           (o.foldin_split_workspace_bytes, split), _lib.LIK_NORMAL, mid=mid)
 
     def run_bound(self, model, kl_weight, n_iters, reset=False):
         """n_iters rounds of the bound's two block minimisers for every entity of the plan, written into the model's
         tables: the light entities by vfm_foldin_bound_f32, the heavy ones by vfm_foldin_bound_split_f32.  Returns
         (entities [E] ascending, loss [E] = B_e, rows [E])."""
-        dev, d = model.device, self.d
-        loss = torch.empty(self.E, dtype=torch.float32, device=dev)
-        if self.E == 0:
-            return self.ents, loss, self.counts
         o = _lib.ops()
-        model._fresh_params()
-        ent, bia, scal = model._views(model._flat)
-        flags = ops.FLAG_LINK_SOFTPLUS if model.link == "softplus" else 0
-        n_ops, n_rows = self.op_x.shape[0], self.ys.numel()
-        if self.n_light:
-            nl = self.n_light
-            ws = torch.empty(max(o.foldin_bound_workspace_bytes(nl, n_rows, n_ops, d, self.lds_dim), 1),
-                             dtype=torch.uint8, device=dev)
-            o.foldin_bound(self.ents[:nl], self.ptr[:nl + 1], self.ys, self.op_x, self.row_op, ent, bia, scal, ws,
-                           loss[:nl], self.field, foldin.OBJECTIVES["closed_form"], _lib.LIK_BERNOULLI, flags,
-                           self.lds_dim, float(kl_weight), int(n_iters), int(bool(reset)), foldin.MODE_FIT)
-        for a, b, cptr, tab in self.groups:
-            ws = torch.empty(max(o.foldin_bound_split_workspace_bytes(tab.shape[0], b - a, n_rows, n_ops, d,
-                                                                      self.lds_dim), 1), dtype=torch.uint8, device=dev)
-            o.foldin_bound_split(self.ents[a:b], cptr, tab, self.ys, self.op_x, self.row_op, ent, bia, scal, ws,
-                                 loss[a:b], self.field, flags, self.lds_dim, float(kl_weight), int(n_iters),
-                                 int(bool(reset)))
-        model.params_changed()              # (rows written outside the step kernels: derived caches are stale)
-        return self.ents[self.asc], loss[self.asc], self.counts[self.asc]
+        return self._solve(model, kl_weight,
+                           (o.foldin_bound_workspace_bytes, lambda *a: o.foldin_bound(*a, foldin.MODE_FIT)),
+                           (o.foldin_bound_split_workspace_bytes, o.foldin_bound_split), _lib.LIK_BERNOULLI,
+                           rows=(self.ys.numel(),), tail=(int(n_iters), int(bool(reset))))
+
+
+def _run_split(model, x, y, field, split_rows, chunk_rows, max_workspace_bytes, lds_dim, bound, run):
+    """The body of the two split entry points over checked rows: the plan's own arguments checked, the plan, run(plan)."""
+    resolve_split_rows(split_rows, model.d)
+    check_chunk_rows(chunk_rows)
+    foldin._check_lds_dim(lds_dim)
+    if int(max_workspace_bytes) < 0:
+        raise ValueError("max_workspace_bytes must be >= 0")
+    ops._need_cuda(model._flat, "the model's parameters")
+    return run(SweepPlan(model, x, y, field, split_rows, chunk_rows, int(max_workspace_bytes), lds_dim, bound=bound))
 
 
 def run_bound_split(model, X, y, field=0, kl_weight=1.0, n_iters=8, reset=False, split_rows="auto", chunk_rows=2048,
@@ -276,15 +268,8 @@ def run_bound_split(model, X, y, field=0, kl_weight=1.0, n_iters=8, reset=False,
     """foldin.run_bound with the entities of more than max(split_rows, d + 1) rows run by the split path; the same
     output contract: (entities [E] ascending, loss [E] = B_e, rows [E])."""
     x, y = foldin.check_args_bound(model, X, y, field, kl_weight, n_iters)
-    resolve_split_rows(split_rows, model.d)
-    check_chunk_rows(chunk_rows)
-    if int(lds_dim) < -1:
-        raise ValueError("lds_dim must be -1 or >= 0")
-    if int(max_workspace_bytes) < 0:
-        raise ValueError("max_workspace_bytes must be >= 0")
-    ops._need_cuda(model._flat, "the model's parameters")
-    plan = SweepPlan(model, x, y, field, split_rows, chunk_rows, int(max_workspace_bytes), lds_dim, bound=True)
-    return plan.run_bound(model, kl_weight, n_iters, reset)
+    return _run_split(model, x, y, field, split_rows, chunk_rows, max_workspace_bytes, lds_dim, True,
+                      lambda plan: plan.run_bound(model, kl_weight, n_iters, reset))
 
 
 def run_exact_split(model, X, y, field=0, kl_weight=1.0, split_rows="auto", chunk_rows=2048,
@@ -292,15 +277,8 @@ def run_exact_split(model, X, y, field=0, kl_weight=1.0, split_rows="auto", chun
     """foldin.run_exact with the entities of more than max(split_rows, d + 1) rows solved by the split path."""
     x, y = foldin.check_args_exact(model, X, y, field, kl_weight)
     check_priors(model, priors)
-    resolve_split_rows(split_rows, model.d)
-    check_chunk_rows(chunk_rows)
-    if int(lds_dim) < -1:
-        raise ValueError("lds_dim must be -1 or >= 0")
-    if int(max_workspace_bytes) < 0:
-        raise ValueError("max_workspace_bytes must be >= 0")
-    ops._need_cuda(model._flat, "the model's parameters")
-    return SweepPlan(model, x, y, field, split_rows, chunk_rows, int(max_workspace_bytes), lds_dim).run(
-        model, kl_weight, _prior_row(model, priors, field))
+    return _run_split(model, x, y, field, split_rows, chunk_rows, max_workspace_bytes, lds_dim, False,
+                      lambda plan: plan.run(model, kl_weight, _prior_row(model, priors, field)))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -323,6 +301,13 @@ def _kl64_prior(mu, sg, m, lam):
     """KL(N(mu, sg^2) || N(m, 1 / lam)) = 1/2 (lam sg^2 + lam (mu - m)^2 - 1 - log(lam sg^2))."""
     v = lam * sg * sg
     return 0.5 * (v + lam * (mu - m) ** 2 - 1.0 - torch.log(v))
+
+
+def _add_kl64_rows(kl, e, b, d, link):
+    """kl plus the N(0, 1) KL of the table rows e [n, 2d], b [n, 2]: the factors' sum, then the weights'.  Two sums
+    added in this order: the objectives' fp64 bits depend on it."""
+    kl = kl + _kl64(e[:, :d].double(), _link64(e[:, d:], link)).sum()
+    return kl + _kl64(b[:, 0].double(), _link64(b[:, 1], link)).sum()
 
 
 def _field_of(model, ids):
@@ -351,7 +336,6 @@ def objective_terms(model, x, y, seen, kl_weight, priors=None):
     """J as a 0-dim fp64 tensor on the device: the rows' expected negative log likelihood from the predictive_moments
     kernel's fp32 moments, the KL of the entities `seen` (distinct ids) and of the global bias from the tables.  priors:
     the entities' KL is to their field's N(mean, 1 / prec); the global bias keeps N(0, 1)."""
-    d = model.d
     ent, bia, scal = model._views(model._flat)
     prec = _link64(scal[0], model.link)
     n = x.shape[0]
@@ -365,9 +349,7 @@ def objective_terms(model, x, y, seen, kl_weight, priors=None):
         mu, sg = _theta64(model, seen)
         kl = kl + _kl64_prior(mu, sg, priors.mean.to(x.device).double()[f], priors.prec.to(x.device).double()[f]).sum()
     elif seen.numel():
-        e, b = ent[seen], bia[seen]
-        kl = kl + _kl64(e[:, :d].double(), _link64(e[:, d:], model.link)).sum()
-        kl = kl + _kl64(b[:, 0].double(), _link64(b[:, 1], model.link)).sum()
+        kl = _add_kl64_rows(kl, ent[seen], bia[seen], model.d, model.link)
     return J + float(kl_weight) * kl
 
 
@@ -415,13 +397,17 @@ def update_scalars(model, x, y, kl_weight):
     scal[0:1] = _inv_link64(new_prec, model.link).float().reshape(1)
 
 
-def check_fit_args(model, X, y, n_sweeps, kl_weight, fields, split_rows, chunk_rows, tol):
-    """Validate a fit_exact call (no GPU needed).  Returns (x, y, fields)."""
-    if model.output != "reg":
-        raise ValueError("fit_exact needs a 'reg' model (Gaussian likelihood): the closed form its blocks solve has none "
-                         "for 'class'; use fit")
-    if not float(kl_weight) > 0.0 or not math.isfinite(float(kl_weight)):
-        raise ValueError("kl_weight must be > 0 and finite: the prior term is what makes each system positive definite")
+_FIT_MODEL = {"reg": "fit_exact needs a 'reg' model (Gaussian likelihood): the closed form its blocks solve has none for "
+                     "'class'; use fit",
+              "class": "fit_bound needs a 'class' model (Bernoulli likelihood): a 'reg' model's blocks have their exact "
+                       "optimum; use fit_exact"}
+
+
+def check_fit_args(model, X, y, kind, check_field, n_sweeps, fields, split_rows, chunk_rows, tol):
+    """Validate a fit_exact (kind 'reg') or fit_bound ('class') call (no GPU needed); check_field(f) -> (x, y): the
+    fold-in's own check of the rows with field f folded, kl_weight (and n_iters) with it.  Returns (x, y, fields)."""
+    if model.output != kind:
+        raise ValueError(_FIT_MODEL[kind])
     if isinstance(n_sweeps, bool) or not isinstance(n_sweeps, int) or n_sweeps < 0:
         raise ValueError("n_sweeps must be an integer >= 0")
     if fields is None:
@@ -437,12 +423,53 @@ def check_fit_args(model, X, y, n_sweeps, kl_weight, fields, split_rows, chunk_r
         raise ValueError("tol must be None or >= 0")
     x = yy = None
     for f in range(model.F):                                  # (every column is some block's or a partner of one)
-        x, yy = foldin.check_args_exact(model, X, y, f, kl_weight)
+        x, yy = check_field(f)
     return x, yy, fields
 
 
+def _check_fit_exact(model, X, y, n_sweeps, kl_weight, fields, split_rows, chunk_rows, tol):
+    return check_fit_args(model, X, y, "reg", lambda f: foldin.check_args_exact(model, X, y, f, kl_weight), n_sweeps,
+                          fields, split_rows, chunk_rows, tol)
+
+
+def _check_fit_bound(model, X, y, n_sweeps, kl_weight, n_iters, fields, split_rows, chunk_rows, tol):
+    return check_fit_args(model, X, y, "class", lambda f: foldin.check_args_bound(model, X, y, f, kl_weight, n_iters),
+                          n_sweeps, fields, split_rows, chunk_rows, tol)
+
+
+def _sweeps(model, fields, n_sweeps, tol, on_step, objective, run_block, after_block=None, after_sweep=None, tag=None):
+    """The sweep loop of fit and fit_bound: per sweep run_block(f) for every field, after_block(f) behind each where
+    given (the prior's update, on_step's ("prior", f)), then after_sweep() where given (the scalars' blocks, on_step's
+    `tag`), then objective(); it stops at the tol rule.  Returns {"objective", "sweeps", "ms"}."""
+    values = [float(objective())]
+    events = []
+    for sweep in range(n_sweeps):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for f in fields:
+            run_block(f)
+            if on_step is not None:
+                on_step(sweep, f)
+            if after_block is not None:
+                after_block(f)
+                if on_step is not None:
+                    on_step(sweep, ("prior", f))
+        if after_sweep is not None:
+            after_sweep()
+            if on_step is not None:
+                on_step(sweep, tag)
+        t1.record()
+        events.append((t0, t1))
+        values.append(float(objective()))
+        if tol is not None and values[-2] - values[-1] <= float(tol) * abs(values[-2]):
+            break
+    model.params_changed()
+    torch.cuda.synchronize(model.device)
+    return {"objective": values, "sweeps": len(events), "ms": [a.elapsed_time(b) for a, b in events]}
+
+
 def exact_objective(model, X, y, kl_weight=1.0, priors=None):
-    x, y, _ = check_fit_args(model, X, y, 0, kl_weight, None, None, 1, None)
+    x, y, _ = _check_fit_exact(model, X, y, 0, kl_weight, None, None, 1, None)
     check_priors(model, priors)
     ops._need_cuda(model._flat, "the model's parameters")
     model._fresh_params()
@@ -452,7 +479,7 @@ def exact_objective(model, X, y, kl_weight=1.0, priors=None):
 def fit(model, X, y, n_sweeps=10, kl_weight=1.0, fields=None, update_scalars_=True, split_rows="auto", chunk_rows=2048,
         on_step=None, tol=None, max_workspace_bytes=MAX_WORKSPACE_BYTES, priors=None, learn_priors=False,
         learn_mean=True, prec_min=1e-4, prec_max=1e4):
-    x, y, fields = check_fit_args(model, X, y, n_sweeps, kl_weight, fields, split_rows, chunk_rows, tol)
+    x, y, fields = _check_fit_exact(model, X, y, n_sweeps, kl_weight, fields, split_rows, chunk_rows, tol)
     check_priors(model, priors)
     prec_min, prec_max = check_prec_bounds(prec_min, prec_max)
     ops._need_cuda(model._flat, "the model's parameters")
@@ -463,35 +490,16 @@ def fit(model, X, y, n_sweeps=10, kl_weight=1.0, fields=None, update_scalars_=Tr
     plans = {f: SweepPlan(model, x, y, f, split_rows, chunk_rows, max_workspace_bytes) for f in dict.fromkeys(fields)}
     seen_f = {f: plans[f].ents[plans[f].asc] for f in plans} if learn_priors else {}
     clamped = {f: torch.zeros((), dtype=torch.int64, device=x.device) for f in plans} if learn_priors else {}
-    objective = [float(objective_terms(model, x, y, seen, kl_weight, priors))]
-    events = []
-    done = 0
-    for sweep in range(n_sweeps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for f in fields:
-            plans[f].run(model, kl_weight, _prior_row(model, priors, f))
-            if on_step is not None:
-                on_step(sweep, f)
-            if learn_priors:
-                n_clamped = update_prior(model, priors, f, seen_f[f], learn_mean, prec_min, prec_max)
-                if n_clamped is not None:
-                    clamped[f] += n_clamped
-                if on_step is not None:
-                    on_step(sweep, ("prior", f))
-        if update_scalars_:
-            update_scalars(model, x, y, kl_weight)
-            if on_step is not None:
-                on_step(sweep, "scalars")
-        t1.record()
-        events.append((t0, t1))
-        objective.append(float(objective_terms(model, x, y, seen, kl_weight, priors)))
-        done += 1
-        if tol is not None and objective[-2] - objective[-1] <= float(tol) * abs(objective[-2]):
-            break
-    model.params_changed()
-    torch.cuda.synchronize(model.device)
-    out = {"objective": objective, "sweeps": done, "ms": [a.elapsed_time(b) for a, b in events]}
+
+    def learn_prior(f):
+        n_clamped = update_prior(model, priors, f, seen_f[f], learn_mean, prec_min, prec_max)
+        if n_clamped is not None:
+            clamped[f] += n_clamped
+
+    out = _sweeps(model, fields, n_sweeps, tol, on_step, lambda: objective_terms(model, x, y, seen, kl_weight, priors),
+                  lambda f: plans[f].run(model, kl_weight, _prior_row(model, priors, f)),
+                  learn_prior if learn_priors else None,
+                  (lambda: update_scalars(model, x, y, kl_weight)) if update_scalars_ else None, "scalars")
     if priors is not None:
         out["priors"] = priors
     if learn_priors:
@@ -517,7 +525,6 @@ def bound_objective_terms(model, x, y, seen, kl_weight):
     """J of fit_bound as a 0-dim fp64 tensor on the device: the rows' collapsed bound terms
     -(y - 1/2) E f + xi / 2 + log1p(e^-xi), xi = sqrt((E f)^2 + Var f), from the predictive_moments kernel's fp32
     moments, the KL of the entities `seen` (distinct ids) and of the global bias from the tables."""
-    d = model.d
     ent, bia, scal = model._views(model._flat)
     J = torch.zeros((), dtype=torch.float64, device=x.device)
     if x.shape[0]:
@@ -526,9 +533,7 @@ def bound_objective_terms(model, x, y, seen, kl_weight):
         J = J + (-(y.double() - 0.5) * m + 0.5 * xi + torch.log1p(torch.exp(-xi))).sum()
     kl = _kl64(scal[1].double(), _link64(scal[2], model.link))
     if seen.numel():
-        e, b = ent[seen], bia[seen]
-        kl = kl + _kl64(e[:, :d].double(), _link64(e[:, d:], model.link)).sum()
-        kl = kl + _kl64(b[:, 0].double(), _link64(b[:, 1], model.link)).sum()
+        kl = _add_kl64_rows(kl, ent[seen], bia[seen], model.d, model.link)
     return J + float(kl_weight) * kl
 
 
@@ -548,32 +553,8 @@ def update_bias_bound(model, x, y, kl_weight):
     scal[1:3] = torch.stack([new_m0, new_s0]).float()
 
 
-def check_fit_bound_args(model, X, y, n_sweeps, kl_weight, n_iters, fields, split_rows, chunk_rows, tol):
-    """Validate a fit_bound call (no GPU needed).  Returns (x, y, fields)."""
-    if model.output != "class":
-        raise ValueError("fit_bound needs a 'class' model (Bernoulli likelihood): a 'reg' model's blocks have their exact "
-                         "optimum; use fit_exact")
-    if isinstance(n_sweeps, bool) or not isinstance(n_sweeps, int) or n_sweeps < 0:
-        raise ValueError("n_sweeps must be an integer >= 0")
-    if fields is None:
-        fields = tuple(range(model.F))
-    else:
-        fields = tuple(fields)
-        for f in fields:
-            if isinstance(f, bool) or not isinstance(f, int) or not 0 <= f < model.F:
-                raise ValueError(f"fields must hold ints in [0, {model.F})")
-    resolve_split_rows(split_rows, model.d)
-    check_chunk_rows(chunk_rows)
-    if tol is not None and not float(tol) >= 0.0:
-        raise ValueError("tol must be None or >= 0")
-    x = yy = None
-    for f in range(model.F):                                  # (every column is some block's or a partner of one)
-        x, yy = foldin.check_args_bound(model, X, y, f, kl_weight, n_iters)
-    return x, yy, fields
-
-
 def bound_objective(model, X, y, kl_weight=1.0):
-    x, y, _ = check_fit_bound_args(model, X, y, 0, kl_weight, 1, None, None, 1, None)
+    x, y, _ = _check_fit_bound(model, X, y, 0, kl_weight, 1, None, None, 1, None)
     ops._need_cuda(model._flat, "the model's parameters")
     model._fresh_params()
     return float(bound_objective_terms(model, x, y, torch.unique(x), kl_weight))
@@ -581,32 +562,12 @@ def bound_objective(model, X, y, kl_weight=1.0):
 
 def fit_bound(model, X, y, n_sweeps=10, kl_weight=1.0, n_iters=8, fields=None, update_bias=True, split_rows="auto",
               chunk_rows=2048, on_step=None, tol=None, max_workspace_bytes=MAX_WORKSPACE_BYTES):
-    x, y, fields = check_fit_bound_args(model, X, y, n_sweeps, kl_weight, n_iters, fields, split_rows, chunk_rows, tol)
+    x, y, fields = _check_fit_bound(model, X, y, n_sweeps, kl_weight, n_iters, fields, split_rows, chunk_rows, tol)
     ops._need_cuda(model._flat, "the model's parameters")
     model._fresh_params()
     seen = torch.unique(x)
     plans = {f: SweepPlan(model, x, y, f, split_rows, chunk_rows, max_workspace_bytes, bound=True)
              for f in dict.fromkeys(fields)}
-    objective = [float(bound_objective_terms(model, x, y, seen, kl_weight))]
-    events = []
-    done = 0
-    for sweep in range(n_sweeps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for f in fields:
-            plans[f].run_bound(model, kl_weight, n_iters, False)        # (from the current rows: B = J at the start)
-            if on_step is not None:
-                on_step(sweep, f)
-        if update_bias:
-            update_bias_bound(model, x, y, kl_weight)
-            if on_step is not None:
-                on_step(sweep, "bias")
-        t1.record()
-        events.append((t0, t1))
-        objective.append(float(bound_objective_terms(model, x, y, seen, kl_weight)))
-        done += 1
-        if tol is not None and objective[-2] - objective[-1] <= float(tol) * abs(objective[-2]):
-            break
-    model.params_changed()
-    torch.cuda.synchronize(model.device)
-    return {"objective": objective, "sweeps": done, "ms": [a.elapsed_time(b) for a, b in events]}
+    return _sweeps(model, fields, n_sweeps, tol, on_step, lambda: bound_objective_terms(model, x, y, seen, kl_weight),
+                   lambda f: plans[f].run_bound(model, kl_weight, n_iters, False),     # (from the current rows: B = J at the start)
+                   after_sweep=(lambda: update_bias_bound(model, x, y, kl_weight)) if update_bias else None, tag="bias")
