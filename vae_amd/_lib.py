@@ -87,7 +87,8 @@ def _fields(ctype, *names):
 
 # ---- the fold-in solves: exact (include/vfm_foldin.h: vfm_foldin_solve_f32), split exact (include/vfm_sweep.h, the hot
 # path of VFM.fit_exact), under a learnt field prior (include/vfm_prior.h: the same structs plus the prior pointer), bound
-# for 'class' models (include/vfm_bound.h) and split bound (include/vfm_bound_sweep.h, the hot path of VFM.fit_bound)
+# for 'class' models (include/vfm_bound.h) and split bound (include/vfm_bound_sweep.h, the hot path of VFM.fit_bound), and
+# the two bound forms under a learnt field prior (include/vfm_bound_prior.h: again the same structs plus the prior pointer)
 FOLDIN_SOLVE_EXPORTS = ("vfm_foldin_solve_f32", "vfm_foldin_solve_workspace_bytes")
 FOLDIN_SOLVE_LDS_DIM = 135
 FOLDIN_SOLVE_SLABS = 256
@@ -96,6 +97,8 @@ PRIOR_EXPORTS = ("vfm_foldin_solve_prior_f32", "vfm_foldin_solve_prior_workspace
                  "vfm_foldin_solve_split_prior_f32", "vfm_foldin_split_prior_workspace_bytes")
 BOUND_EXPORTS = ("vfm_foldin_bound_f32", "vfm_foldin_bound_workspace_bytes")
 BOUND_SWEEP_EXPORTS = ("vfm_foldin_bound_split_f32", "vfm_foldin_bound_split_workspace_bytes")
+BOUND_PRIOR_EXPORTS = ("vfm_foldin_bound_prior_f32", "vfm_foldin_bound_prior_workspace_bytes",
+                       "vfm_foldin_bound_split_prior_f32", "vfm_foldin_bound_split_prior_workspace_bytes")
 
 # the runs of fields that the four structs name alike; between them the row-list forms have objective and likelihood and
 # a row_ptr, the chunk forms n_chunks and the chunk table, the bound forms n_iters and reset
@@ -142,6 +145,9 @@ _FOLD_PROTOTYPES = (
     ("vfm_foldin_solve_split_prior_f32", FoldinSplit, [C.c_void_p], "vfm_foldin_split_prior_workspace_bytes", _SPLIT_SIZES),
     ("vfm_foldin_bound_f32", FoldinBound, [], "vfm_foldin_bound_workspace_bytes", [_I64] + _SOLVE_SIZES),
     ("vfm_foldin_bound_split_f32", FoldinBoundSplit, [], "vfm_foldin_bound_split_workspace_bytes", [_I64] + _SPLIT_SIZES),
+    ("vfm_foldin_bound_prior_f32", FoldinBound, [C.c_void_p], "vfm_foldin_bound_prior_workspace_bytes", [_I64] + _SOLVE_SIZES),
+    ("vfm_foldin_bound_split_prior_f32", FoldinBoundSplit, [C.c_void_p], "vfm_foldin_bound_split_prior_workspace_bytes",
+     [_I64] + _SPLIT_SIZES),
 )
 
 

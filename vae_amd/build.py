@@ -101,10 +101,11 @@ _UNITS = [("vfm_abi.hip", "", _EXACT), ("vfm_index.hip", "", []), ("vfm_variants
           ("csrc_rank/vfm_foldin_bound_split.hip", "", _EXACT)]
 RANK_DIR = os.path.join(HERE, "csrc_rank")
 VAR_DIR = os.path.join(HERE, "csrc_var")
-# the public headers beside include/vfm_hip.h (vfm_foldin_ops.cpp holds the ops of foldin, sweep, bound_sweep, prior and
-# vfm_bound.h's fold-in; vfm_elicit_ops.cpp holds vfm_bound.h's session)
+# the public headers beside include/vfm_hip.h (vfm_foldin_ops.cpp holds the ops of foldin, sweep, bound_sweep, prior,
+# bound_prior and vfm_bound.h's fold-in; vfm_elicit_ops.cpp holds vfm_bound.h's session)
 PUBLIC_HDRS = tuple(os.path.join(ROOT, "include", f"vfm_{n}.h")
-                    for n in ("rank", "foldin", "elicit", "design", "variant_step", "sweep", "bound", "bound_sweep", "prior"))
+                    for n in ("rank", "foldin", "elicit", "design", "variant_step", "sweep", "bound", "bound_sweep", "prior",
+                              "bound_prior"))
 # the TORCH_LIBRARY fragments linked into the shim beside csrc/vfm_torch_ops.cpp, and the header they share: host C++
 # only, so it is no source of libvfm_hip.so.  One file per family
 OPS_SOURCES = tuple(os.path.join(RANK_DIR, f"vfm_{n}_ops.cpp") for n in ("rank", "foldin", "elicit", "design"))

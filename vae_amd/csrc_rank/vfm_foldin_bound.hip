@@ -24,6 +24,10 @@
 // entity's table row into LDS for it and writes the table row from its store step.
 // Every sum has a fixed order that depends on the entity's rows and d alone: no atomics, no host sync, the same bits
 // whichever other entities share the launch and wherever the triangle lives.
+//
+// vfm_foldin_bound_prior_f32 (include/vfm_bound_prior.h) is the PRIOR = true instantiation of the same kernel: the folded
+// field's prior [2, d + 1] = mean | precision is staged once per workgroup in fp64 in LDS in front of bound_body's
+// vectors; the instantiation without it is the parent's, unchanged.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -32,6 +36,7 @@
 
 #include "vfm_args.hpp"
 #include "vfm_bound.h"
+#include "vfm_bound_prior.h"
 #include "vfm_launch.hpp"            // launch_status
 
 namespace vfm {
@@ -50,15 +55,22 @@ struct BoundArgs {
   const double* cv64;                    // [n_ops]        c_var
   double* wrow;                          // [R]            w_r of the round in flight
   SolveSlabs sl;                         // the slabs and the LDS rule of the triangle
+  const float* prior;                    // [2, d + 1] mean | precision of the folded field (PRIOR instantiations only)
 };
 
-template <int W, int CPL, int LINK>
+template <int W, int CPL, int LINK, bool PRIOR>
 __global__ __launch_bounds__(FB) void k_foldin_bound(const BoundArgs s) {
 #pragma clang fp contract(on)
-  extern __shared__ double sm[];
+  extern __shared__ double sm_all[];
   const FoldArgs& a = s.f;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int d = a.d, d1 = d + 1;
+  double* sm = sm_all + (PRIOR ? 2 * d1 : 0);              // (the prior in front: lds_doubles_prior's rule)
+  const double* pr = PRIOR ? sm_all : nullptr;
+  if constexpr (PRIOR) {
+    stage_prior(s.prior, sm_all, d1);
+    __syncthreads();
+  }
   float* pf = (float*)(sm + 7 * d1);     // the fp32 parameters: mu_w, mu [d] | s_w, s [d]  (bound_body's)
   double* Hl = sm + 8 * d1;              // the triangle while it fits
   double* sg2 = Hl + tri(s.sl.cap_dim);  // sigma_w^2, sigma_k^2 [d]
@@ -87,9 +99,9 @@ __global__ __launch_bounds__(FB) void k_foldin_bound(const BoundArgs s) {
     __syncthreads();
 
     if (a.mode == VFM_FOLDIN_OBJECTIVE) {
-      if (wv == 0) bound_loss<W, CPL, LINK>(a, rows, n, pf, lane, a.loss + g);
+      if (wv == 0) bound_loss<W, CPL, LINK, PRIOR>(a, rows, n, pf, lane, a.loss + g, pr);
     } else {
-      bound_body<W, CPL, LINK>(a, s.ops64, s.cm64, s.cv64, s.wrow + r0, rows, n, a.reset != 0, sm, Hm, sg2, a.loss + g,
+      bound_body<W, CPL, LINK, PRIOR>(a, s.ops64, s.cm64, s.cv64, s.wrow + r0, rows, n, a.reset != 0, sm, Hm, sg2, a.loss + g,
                                [&](const float*) {           // the table row, rounded once
                                  for (int k = tid; k < d; k += FB) {
                                    erow[k] = pf[1 + k];
@@ -99,22 +111,25 @@ __global__ __launch_bounds__(FB) void k_foldin_bound(const BoundArgs s) {
                                    a.bias[e * 2] = pf[0];
                                    a.bias[e * 2 + 1] = pf[d1];
                                  }
-                               });
+                               }, pr);
     }
     __syncthreads();                     // (pf and the iterate are rewritten by the next entity)
   }
 }
 
+template <bool PRIOR>
 void launch(const FShape& f, bool sp, const BoundArgs& s, unsigned grid, size_t shm, hipStream_t st) {
   for_link(sp, [&](auto link) {
     for_shape(f, [&](auto w, auto c) {
-      launch_lds(k_foldin_bound<decltype(w)::value, decltype(c)::value, decltype(link)::value>, grid, shm, st, s);
+      launch_lds(k_foldin_bound<decltype(w)::value, decltype(c)::value, decltype(link)::value, PRIOR>, grid, shm, st, s);
     });
   });
 }
 
 }  // namespace
 }  // namespace vfm
+
+static int bound_call(const vfm_foldin_bound_t* p, const float* prior, void* stream);
 
 extern "C" {
 
@@ -123,7 +138,20 @@ int64_t vfm_foldin_bound_workspace_bytes(int64_t E, int64_t R, int64_t n_ops, in
   return vfm::off_bound_own(R, n_ops, d) + vfm::slabs_bytes(E, d, lds_dim);
 }
 
-int vfm_foldin_bound_f32(const vfm_foldin_bound_t* p, void* stream) {
+int64_t vfm_foldin_bound_prior_workspace_bytes(int64_t E, int64_t R, int64_t n_ops, int32_t d, int32_t lds_dim) {
+  return vfm_foldin_bound_workspace_bytes(E, R, n_ops, d, lds_dim);    // (the prior lives in LDS, not in the workspace)
+}
+
+int vfm_foldin_bound_f32(const vfm_foldin_bound_t* p, void* stream) { return bound_call(p, nullptr, stream); }
+
+int vfm_foldin_bound_prior_f32(const vfm_foldin_bound_t* p, const float* prior, void* stream) {
+  return bound_call(p, prior, stream);
+}
+
+}  // extern "C"
+
+// both entry points: prior == NULL is vfm_foldin_bound_f32
+static int bound_call(const vfm_foldin_bound_t* p, const float* prior, void* stream) {
   if (!p) return vfm::fail(VFM_E_INVALID, "vfm_foldin_bound_f32: NULL argument struct");
   const int64_t ws = vfm_foldin_bound_workspace_bytes(p->E, p->R, p->n_ops, p->d, p->lds_dim);
   const auto own = [&]() -> const char* {
@@ -146,14 +174,14 @@ int vfm_foldin_bound_f32(const vfm_foldin_bound_t* p, void* stream) {
   char* w = (char*)p->workspace;
   const unsigned grid = vfm::place_slabs(p->d, p->lds_dim, p->E, w + vfm::off_bound_own(p->R, p->n_ops, p->d),
                                          (int64_t)1 << 20, s.sl);
-  const size_t shm = (size_t)vfm::bound_lds_doubles(p->d, s.sl.cap_dim) * 8;
+  s.prior = prior;
+  const size_t shm = (size_t)(vfm::bound_lds_doubles(p->d, s.sl.cap_dim) + (prior ? 2 * (int64_t)(p->d + 1) : 0)) * 8;
 
   if (p->n_ops > 0) {
     if (int rc = vfm::launch_solve_preps(sp, s.f, p->n_ops, p->op_x, w, st)) return rc;
     if (int rc = vfm::launch_bound_prep(sp, s.f, p->n_ops, p->op_x, const_cast<double*>(s.cv64), st)) return rc;
   }
-  vfm::launch(f, sp, s, grid, shm, st);
+  if (prior) vfm::launch<true>(f, sp, s, grid, shm, st);
+  else vfm::launch<false>(f, sp, s, grid, shm, st);
   return launch_status("k_foldin_bound");
 }
-
-}  // extern "C"

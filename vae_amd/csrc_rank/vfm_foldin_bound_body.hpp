@@ -82,10 +82,11 @@ void fill_bound_args(S& s, const P* p, int mode) {
 }
 
 // phase E: B_e at the fp32 parameters pf = [mu_w, mu [d] | s_w, s [d]] (LDS), by wave 0; its 64 / W lane groups all
-// hold this entity, lane l of a group owns coordinates j W + l
-template <int W, int CPL, int LINK, class Rows>
+// hold this entity, lane l of a group owns coordinates j W + l.  PRIOR (include/vfm_bound_prior.h): the KL is to the field's
+// prior pr = m [d + 1] | lam [d + 1] (LDS, stage_prior), evaluated as solve_body's phase E evaluates it
+template <int W, int CPL, int LINK, bool PRIOR = false, class Rows>
 __device__ __forceinline__ void bound_loss(const FoldArgs& a, const Rows& rows, int64_t n, const float* pf, int lane,
-                                           float* loss) {
+                                           float* loss, const double* pr = nullptr) {
 #pragma clang fp contract(on)
   constexpr int DP = W * CPL;
   const int d = a.d, d1 = d + 1, l = lane % W;
@@ -122,9 +123,15 @@ __device__ __forceinline__ void bound_loss(const FoldArgs& a, const Rows& rows, 
   }
   float klq = 0.f;
 #pragma unroll
-  for (int j = 0; j < CPL; ++j)
-    if (vk[j]) klq += kl_std_normal(mu[j], sg[j]);
-  klq = group_sum<W>(klq) + kl_std_normal(muw, sgw);
+  for (int j = 0; j < CPL; ++j) {
+    if constexpr (PRIOR) {
+      if (vk[j]) klq += kl_prior_normal(mu[j], sg[j], (float)pr[1 + j * W + l], sqrtf((float)pr[d1 + 1 + j * W + l]));
+    } else {
+      if (vk[j]) klq += kl_std_normal(mu[j], sg[j]);
+    }
+  }
+  if constexpr (PRIOR) klq = group_sum<W>(klq) + kl_prior_normal(muw, sgw, (float)pr[0], sqrtf((float)pr[d1]));
+  else klq = group_sum<W>(klq) + kl_std_normal(muw, sgw);
   if (lane == 0) *loss = (float)(lsum + (double)a.klw * (double)klq);
 }
 
@@ -140,11 +147,16 @@ __device__ __forceinline__ void bound_loss(const FoldArgs& a, const Rows& rows, 
 // instead (pf is not read).  The iterate stays in fp64 for all rounds; put_params rounds it once into pf; after the
 // barrier that publishes pf every thread calls store(pf); then wave 0 evaluates B_e at pf into *loss.  The caller puts a
 // barrier before pf or any other LDS of the block is written again.
+// PRIOR (include/vfm_bound_prior.h): the entity's prior is N(m_c, 1 / lam_c) per coordinate, pr = m [d + 1] | lam [d + 1] in
+// LDS (stage_prior): D_c = kl lam_c + sum_r w_r A_r, b_c += kl lam_c m_c, sigma_c^2 = kl / (kl lam_c + sum_r w_r (A_r +
+// M_r^2)), prior_start is mu = m, sigma^2 = 1 / lam, and the KL of B_e is to that prior.  At m = 0, lam = 1 every
+// expression rounds as with PRIOR off.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int W, int CPL, int LINK, class Rows, class Store>
+template <int W, int CPL, int LINK, bool PRIOR = false, class Rows, class Store>
 __device__ __forceinline__ void bound_body(const FoldArgs& a, const double* ops64, const double* cm64, const double* cv64,
                                            double* wrow, const Rows& rows, int64_t n, bool prior_start, double* sm,
-                                           double* Hm, double* sg2, float* loss, Store&& store) {
+                                           double* Hm, double* sg2, float* loss, Store&& store,
+                                           const double* pr = nullptr) {
 #pragma clang fp contract(on)
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int d = a.d, d1 = d + 1;
@@ -165,6 +177,10 @@ __device__ __forceinline__ void bound_body(const FoldArgs& a, const double* ops6
   // ---- the start: xi^(0) is taken at the fp32 parameters, or at the prior
   for (int c = tid; c < d1; c += FB) {
     double t0 = 0., v0 = 1.;
+    if constexpr (PRIOR) {
+      t0 = pr[c];
+      v0 = 1.0 / pr[d1 + c];
+    }
     if (!prior_start) {
       const double sg = link_d<LINK>(pf[d1 + c]);
       t0 = pf[c];
@@ -219,7 +235,15 @@ __device__ __forceinline__ void bound_body(const FoldArgs& a, const double* ops6
           bM += t * M;
         }
       }
-      const double D = kl + SA, b = bM - 0.5 * SC;
+      double D, b;
+      if constexpr (PRIOR) {
+        const double kll = kl * pr[d1 + c], b0 = bM - 0.5 * SC;
+        D = kll + SA;
+        b = b0 + kll * pr[c];
+      } else {
+        D = kl + SA;
+        b = bM - 0.5 * SC;
+      }
       Dd[c] = D;
       Di[c] = 1.0 / D;
       bv[c] = dual ? b / D : b;
@@ -287,16 +311,24 @@ __device__ __forceinline__ void bound_body(const FoldArgs& a, const double* ops6
         t = xv[c];
       }
       th[c] = t;
-      sg2[c] = kl / (kl + SBd[c]);
+      if constexpr (PRIOR) {
+        const double kll = kl * pr[d1 + c];
+        sg2[c] = kl / (kll + SBd[c]);
+      } else {
+        sg2[c] = kl / (kl + SBd[c]);
+      }
     }
     __syncthreads();
   }
 
   // ---- D: rounded to fp32 once
-  for (int c = tid; c < d1; c += FB) put_params<LINK>(pf, d1, c, th[c], kl, 1.0, SBd[c]);
+  for (int c = tid; c < d1; c += FB) {
+    if constexpr (PRIOR) put_params<LINK, true>(pf, d1, c, th[c], kl, 1.0, SBd[c], kl * pr[d1 + c]);
+    else put_params<LINK>(pf, d1, c, th[c], kl, 1.0, SBd[c]);
+  }
   __syncthreads();
   store(pf);
 
   // ---- E: B_e at the fp32 parameters
-  if (wv == 0) bound_loss<W, CPL, LINK>(a, rows, n, pf, lane, loss);
+  if (wv == 0) bound_loss<W, CPL, LINK, PRIOR>(a, rows, n, pf, lane, loss, pr);
 }

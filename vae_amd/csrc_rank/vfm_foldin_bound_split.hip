@@ -22,6 +22,12 @@
 //   k_bsplit_loss_sum  a thread per entity: the chunks' shares in chunk order, plus kl KL
 // Rounds are separated by kernel boundaries: no atomics, no host sync, no cooperative launch, no grid-wide barrier.
 // Every sum has a fixed order that depends on the entity's rows, the chunk length and d alone.
+//
+// vfm_foldin_bound_split_prior_f32 (include/vfm_bound_prior.h) runs the PRIOR = true instantiations of k_bsplit_start (the
+// reset start mu = m, sigma^2 = 1 / lam), k_bsplit_solve (D = kl lam + SA, b += kl lam m, sigma^2 = kl / (kl lam + SB); the
+// prior [2, d + 1] = mean | precision staged once per workgroup in fp64 in LDS) and k_bsplit_loss_sum (the KL to that
+// prior).  The preps, k_bsplit_assemble and k_bsplit_loss do not read the prior; the instantiations without it are the
+// parent's, unchanged.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -30,6 +36,7 @@
 
 #include "vfm_args.hpp"
 #include "vfm_bound_sweep.h"
+#include "vfm_bound_prior.h"
 #include "vfm_launch.hpp"            // launch_status
 
 namespace vfm {
@@ -57,6 +64,7 @@ struct BSplitArgs {
   SolveSlabs sl;                         // the slabs of k_bsplit_solve's workgroups and the LDS rule of the triangle
   int64_t n_ops, n_chunks, part_elems;
   int32_t last;                          // k_bsplit_solve: the last round, the table row is written
+  const float* prior;                    // [2, d + 1] mean | precision of the folded field (PRIOR instantiations only)
 };
 
 // chunk q's rows, clamped to [0, R)
@@ -71,7 +79,7 @@ __device__ __forceinline__ void chunks_of(const BSplitArgs& s, int64_t g, int64_
   c1 = min(max(s.chunk_ptr[g + 1], c0), s.n_chunks);
 }
 
-template <int LINK>
+template <int LINK, bool PRIOR>
 __global__ __launch_bounds__(FB) void k_bsplit_start(const BSplitArgs s) {
 #pragma clang fp contract(on)
   const FoldArgs& a = s.f;
@@ -82,6 +90,10 @@ __global__ __launch_bounds__(FB) void k_bsplit_start(const BSplitArgs s) {
   const int c = (int)(i - g * d1);
   const int64_t e = a.ent[g];
   double t0 = 0., v0 = 1.;
+  if constexpr (PRIOR) {                 // (the fp32 prior read in fp64)
+    t0 = (double)s.prior[c];
+    v0 = 1.0 / (double)s.prior[d1 + c];
+  }
   if (!a.reset && e >= 0 && e < a.T) {
     const float m = c ? a.entity[e * 2 * d + c - 1] : a.bias[e * 2];
     const float sf = c ? a.entity[e * 2 * d + d + c - 1] : a.bias[e * 2 + 1];
@@ -222,13 +234,19 @@ __global__ __launch_bounds__(FB) void k_bsplit_assemble(const BSplitArgs s) {
   }
 }
 
-template <int LINK>
+template <int LINK, bool PRIOR>
 __global__ __launch_bounds__(FB) void k_bsplit_solve(const BSplitArgs s) {
 #pragma clang fp contract(on)
-  extern __shared__ double sm[];
+  extern __shared__ double sm_all[];
   const FoldArgs& a = s.f;
   const int tid = threadIdx.x;
   const int d = a.d, d1 = d + 1;
+  double* sm = sm_all + (PRIOR ? 2 * d1 : 0);              // (the prior in front: lds_doubles_prior)
+  const double* pr = sm_all;                               // (PRIOR only) m [d + 1] | lam [d + 1]
+  if constexpr (PRIOR) {
+    stage_prior(s.prior, sm_all, d1);
+    __syncthreads();
+  }
   double* Dd = sm;                       // solve_body's layout: D | . | . | right-hand side | 1 / L_jj | solution | SB | fp32
   double* yv = Dd + 3 * d1;
   double* dv = yv + d1;
@@ -255,8 +273,14 @@ __global__ __launch_bounds__(FB) void k_bsplit_solve(const BSplitArgs s) {
         bM += V[2 * d1 + c];
         if (c > 0) SC += V[3 * d1 + c - 1];
       }
-      Dd[c] = kl + SA;
-      yv[c] = bM - 0.5 * SC;
+      if constexpr (PRIOR) {
+        const double kll = kl * pr[d1 + c], b0 = bM - 0.5 * SC;
+        Dd[c] = kll + SA;
+        yv[c] = b0 + kll * pr[c];
+      } else {
+        Dd[c] = kl + SA;
+        yv[c] = bM - 0.5 * SC;
+      }
       SBd[c] = SB;
     }
     __syncthreads();
@@ -272,8 +296,14 @@ __global__ __launch_bounds__(FB) void k_bsplit_solve(const BSplitArgs s) {
     double* itg = s.iter + g * 2 * d1;
     for (int c = tid; c < d1; c += FB) {
       itg[c] = xv[c];
-      itg[d1 + c] = kl / (kl + SBd[c]);
-      if (s.last) put_params<LINK>(pf, d1, c, xv[c], kl, 1.0, SBd[c]);
+      if constexpr (PRIOR) {
+        const double kll = kl * pr[d1 + c];
+        itg[d1 + c] = kl / (kll + SBd[c]);
+        if (s.last) put_params<LINK, true>(pf, d1, c, xv[c], kl, 1.0, SBd[c], kll);
+      } else {
+        itg[d1 + c] = kl / (kl + SBd[c]);
+        if (s.last) put_params<LINK>(pf, d1, c, xv[c], kl, 1.0, SBd[c]);
+      }
     }
     __syncthreads();
     if (s.last) {                        // the table row, rounded once
@@ -350,11 +380,19 @@ __global__ __launch_bounds__(64) void k_bsplit_loss(const BSplitArgs s) {
   }
 }
 
-template <int LINK>
+template <int LINK, bool PRIOR>
 __global__ __launch_bounds__(FB) void k_bsplit_loss_sum(const BSplitArgs s) {
 #pragma clang fp contract(on)
   const FoldArgs& a = s.f;
   const int d = a.d;
+  __shared__ float prs[PRIOR ? 2 * (VFM_FOLDIN_MAX_D + 1) : 1];          // (PRIOR) m [d + 1] | sqrt(lam) [d + 1]
+  if constexpr (PRIOR) {
+    for (int c = threadIdx.x; c <= d; c += FB) {
+      prs[c] = s.prior[c];
+      prs[d + 1 + c] = sqrtf(s.prior[d + 1 + c]);
+    }
+    __syncthreads();
+  }
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= a.E) return;
   const int64_t e = a.ent[g];
@@ -366,8 +404,15 @@ __global__ __launch_bounds__(FB) void k_bsplit_loss_sum(const BSplitArgs s) {
   chunks_of(s, g, c0, c1);
   double sum = 0.;
   for (int64_t q = c0; q < c1; ++q) sum += s.lpart[q];
-  double klq = kl_std_normal(a.bias[e * 2], link_f<LINK>(a.bias[e * 2 + 1]));
-  for (int k = 0; k < d; ++k) klq += kl_std_normal(a.entity[e * 2 * d + k], link_f<LINK>(a.entity[e * 2 * d + d + k]));
+  double klq;
+  if constexpr (PRIOR) {
+    klq = kl_prior_normal(a.bias[e * 2], link_f<LINK>(a.bias[e * 2 + 1]), prs[0], prs[d + 1]);
+    for (int k = 0; k < d; ++k)
+      klq += kl_prior_normal(a.entity[e * 2 * d + k], link_f<LINK>(a.entity[e * 2 * d + d + k]), prs[1 + k], prs[d + 2 + k]);
+  } else {
+    klq = kl_std_normal(a.bias[e * 2], link_f<LINK>(a.bias[e * 2 + 1]));
+    for (int k = 0; k < d; ++k) klq += kl_std_normal(a.entity[e * 2 * d + k], link_f<LINK>(a.entity[e * 2 * d + d + k]));
+  }
   a.loss[g] = (float)(sum + (double)a.klw * klq);
 }
 
@@ -379,6 +424,8 @@ inline int64_t off_part(int64_t n_heavy, int64_t R, int64_t n_ops, int d) {
 
 }  // namespace
 }  // namespace vfm
+
+static int bsplit_call(const vfm_foldin_bound_split_t* p, const float* prior, void* stream);
 
 extern "C" {
 
@@ -392,7 +439,22 @@ int64_t vfm_foldin_bound_split_workspace_bytes(int64_t n_chunks, int64_t n_heavy
          vfm::slabs_bytes(n_heavy, d, lds_dim);
 }
 
-int vfm_foldin_bound_split_f32(const vfm_foldin_bound_split_t* p, void* stream) {
+int64_t vfm_foldin_bound_split_prior_workspace_bytes(int64_t n_chunks, int64_t n_heavy, int64_t R, int64_t n_ops,
+                                                     int32_t d, int32_t lds_dim) {
+  // (the prior lives in LDS, not in the workspace)
+  return vfm_foldin_bound_split_workspace_bytes(n_chunks, n_heavy, R, n_ops, d, lds_dim);
+}
+
+int vfm_foldin_bound_split_f32(const vfm_foldin_bound_split_t* p, void* stream) { return bsplit_call(p, nullptr, stream); }
+
+int vfm_foldin_bound_split_prior_f32(const vfm_foldin_bound_split_t* p, const float* prior, void* stream) {
+  return bsplit_call(p, prior, stream);
+}
+
+}  // extern "C"
+
+// both entry points: prior == NULL is vfm_foldin_bound_split_f32
+static int bsplit_call(const vfm_foldin_bound_split_t* p, const float* prior, void* stream) {
   if (!p) return vfm::fail(VFM_E_INVALID, "vfm_foldin_bound_split_f32: NULL argument struct");
   const int64_t ws = vfm_foldin_bound_split_workspace_bytes(p->n_chunks, p->E, p->R, p->n_ops, p->d, p->lds_dim);
   const auto own = [&]() -> const char* {
@@ -413,7 +475,8 @@ int vfm_foldin_bound_split_f32(const vfm_foldin_bound_split_t* p, void* stream) 
   char* w = (char*)p->workspace;
   s.iter = (double*)(w + vfm::off_bound_own(p->R, p->n_ops, p->d));
   const vfm::SplitGrids grid = vfm::place_split(s, p, w + vfm::off_part(p->E, p->R, p->n_ops, p->d));
-  const size_t shm = (size_t)vfm::lds_doubles(p->d, s.sl.cap_dim) * 8;
+  s.prior = prior;
+  const size_t shm = (size_t)(prior ? vfm::lds_doubles_prior(p->d, s.sl.cap_dim) : vfm::lds_doubles(p->d, s.sl.cap_dim)) * 8;
 
   if (p->n_ops > 0) {
     if (int rc = vfm::launch_solve_preps(sp, a, p->n_ops, p->op_x, w, st)) return rc;
@@ -421,8 +484,8 @@ int vfm_foldin_bound_split_f32(const vfm_foldin_bound_split_t* p, void* stream) 
   }
   const int64_t n_it = p->E * (int64_t)(p->d + 1);
   vfm::for_link(sp, [&](auto link) {
-    hipLaunchKernelGGL(vfm::k_bsplit_start<decltype(link)::value>, dim3((unsigned)((n_it + vfm::FB - 1) / vfm::FB)),
-                       dim3(vfm::FB), 0, st, s);
+    const auto k = prior ? vfm::k_bsplit_start<decltype(link)::value, true> : vfm::k_bsplit_start<decltype(link)::value, false>;
+    hipLaunchKernelGGL(k, dim3((unsigned)((n_it + vfm::FB - 1) / vfm::FB)), dim3(vfm::FB), 0, st, s);
   });
   if (int rc = launch_status("k_bsplit_start")) return rc;
   for (int it = 0; it < p->n_iters; ++it) {
@@ -432,7 +495,8 @@ int vfm_foldin_bound_split_f32(const vfm_foldin_bound_split_t* p, void* stream) 
       if (int rc = launch_status("k_bsplit_assemble")) return rc;
     }
     vfm::for_link(sp, [&](auto link) {
-      vfm::launch_lds(vfm::k_bsplit_solve<decltype(link)::value>, grid.e, shm, st, s);
+      const auto k = prior ? vfm::k_bsplit_solve<decltype(link)::value, true> : vfm::k_bsplit_solve<decltype(link)::value, false>;
+      vfm::launch_lds(k, grid.e, shm, st, s);
     });
     if (int rc = launch_status("k_bsplit_solve")) return rc;
   }
@@ -446,10 +510,8 @@ int vfm_foldin_bound_split_f32(const vfm_foldin_bound_split_t* p, void* stream) 
     if (int rc = launch_status("k_bsplit_loss")) return rc;
   }
   vfm::for_link(sp, [&](auto link) {
-    hipLaunchKernelGGL(vfm::k_bsplit_loss_sum<decltype(link)::value>, dim3((unsigned)((p->E + vfm::FB - 1) / vfm::FB)),
-                       dim3(vfm::FB), 0, st, s);
+    const auto k = prior ? vfm::k_bsplit_loss_sum<decltype(link)::value, true> : vfm::k_bsplit_loss_sum<decltype(link)::value, false>;
+    hipLaunchKernelGGL(k, dim3((unsigned)((p->E + vfm::FB - 1) / vfm::FB)), dim3(vfm::FB), 0, st, s);
   });
   return launch_status("k_bsplit_loss_sum");
 }
-
-}  // extern "C"

@@ -1,11 +1,12 @@
 // vfm_foldin_ops.cpp -- the fold-in family of torch.ops.vfm_hip: foldin (include/vfm_foldin.h), foldin_solve and
 // foldin_solve_split (vfm_foldin.h, vfm_sweep.h), their *_prior forms (vfm_prior.h), foldin_bound and foldin_bound_split
-// (vfm_bound.h, vfm_bound_sweep.h), and the five *_workspace_bytes.  Like vfm_rank_ops.cpp this TORCH_LIBRARY fragment
+// (vfm_bound.h, vfm_bound_sweep.h), their *_prior forms (vfm_bound_prior.h), and the five *_workspace_bytes.  Like vfm_rank_ops.cpp this TORCH_LIBRARY fragment
 // only validates tensors, takes the current HIP stream of the tensors' device and forwards raw pointers; all arithmetic
 // is in the HIP kernels.  Every solve is its parts (vfm_ops_common.hpp) plus its own scalars plus one call.
 #include "vfm_ops_common.hpp"
 
 #include "vfm_bound.h"
+#include "vfm_bound_prior.h"
 #include "vfm_bound_sweep.h"
 #include "vfm_foldin.h"
 #include "vfm_prior.h"
@@ -124,6 +125,19 @@ void foldin_bound(const Tensor& entities, const Tensor& row_ptr, const Tensor& y
   check(vfm_foldin_bound_f32(&p, stream_of(y)), "vfm_foldin_bound_f32");
 }
 
+void foldin_bound_prior(const Tensor& entities, const Tensor& row_ptr, const Tensor& y, const Tensor& op_x,
+                        const Tensor& row_op, Tensor entity, Tensor bias, const Tensor& scalars, Tensor workspace,
+                        Tensor loss, const Tensor& prior, int64_t col, int64_t objective, int64_t likelihood, int64_t flags,
+                        int64_t lds_dim, double kl_weight, int64_t n_iters, int64_t reset, int64_t mode) {
+  vfm_foldin_bound_t p;
+  fill_solve(p, entities, y, op_x, row_op, entity, bias, scalars, workspace, loss, col, flags, lds_dim, kl_weight);
+  fill_row_list(p, row_ptr);
+  p.objective = (int32_t)objective; p.likelihood = (int32_t)likelihood;
+  p.n_iters = (int32_t)n_iters; p.reset = (int32_t)reset; p.mode = (int32_t)mode;
+  c10::hip::HIPGuard guard(y.get_device());
+  check(vfm_foldin_bound_prior_f32(&p, prior_of(prior, p.d), stream_of(y)), "vfm_foldin_bound_prior_f32");
+}
+
 void foldin_solve_split(const Tensor& entities, const Tensor& chunk_ptr, const Tensor& chunks, const Tensor& y,
                         const Tensor& op_x, const Tensor& row_op, Tensor entity, Tensor bias, const Tensor& scalars,
                         Tensor workspace, Tensor loss, int64_t col, int64_t flags, int64_t lds_dim, double kl_weight) {
@@ -158,6 +172,19 @@ void foldin_bound_split(const Tensor& entities, const Tensor& chunk_ptr, const T
   check(vfm_foldin_bound_split_f32(&p, stream_of(y)), "vfm_foldin_bound_split_f32");
 }
 
+void foldin_bound_split_prior(const Tensor& entities, const Tensor& chunk_ptr, const Tensor& chunks, const Tensor& y,
+                              const Tensor& op_x, const Tensor& row_op, Tensor entity, Tensor bias, const Tensor& scalars,
+                              Tensor workspace, Tensor loss, const Tensor& prior, int64_t col, int64_t flags,
+                              int64_t lds_dim, double kl_weight, int64_t n_iters, int64_t reset) {
+  vfm_foldin_bound_split_t p;
+  fill_solve(p, entities, y, op_x, row_op, entity, bias, scalars, workspace, loss, col, flags, lds_dim, kl_weight);
+  fill_chunk_table(p, chunk_ptr, chunks);
+  TORCH_CHECK(n_iters >= INT32_MIN && n_iters <= INT32_MAX, "n_iters out of range");
+  p.n_iters = (int32_t)n_iters; p.reset = reset != 0;
+  c10::hip::HIPGuard guard(y.get_device());
+  check(vfm_foldin_bound_split_prior_f32(&p, prior_of(prior, p.d), stream_of(y)), "vfm_foldin_bound_split_prior_f32");
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(vfm_hip, m) {
@@ -182,6 +209,11 @@ TORCH_LIBRARY_FRAGMENT(vfm_hip, m) {
         "int col, int objective, int likelihood, int flags, int lds_dim, float kl_weight, int n_iters, int reset, "
         "int mode) -> ()",
         &foldin_bound);
+  m.def("foldin_bound_prior(Tensor entities, Tensor row_ptr, Tensor y, Tensor op_x, Tensor row_op, "
+        "Tensor(a!) entity_params, Tensor(b!) bias_params, Tensor scalars, Tensor(c!) workspace, Tensor(d!) loss, "
+        "Tensor prior, int col, int objective, int likelihood, int flags, int lds_dim, float kl_weight, int n_iters, "
+        "int reset, int mode) -> ()",
+        &foldin_bound_prior);
   m.def("foldin_split_workspace_bytes(int n_chunks, int n_heavy, int n_ops, int d, int lds_dim) -> int",
         &foldin_split_workspace_bytes);
   m.def("foldin_solve_split(Tensor entities, Tensor chunk_ptr, Tensor chunks, Tensor y, Tensor op_x, Tensor row_op, "
@@ -198,4 +230,8 @@ TORCH_LIBRARY_FRAGMENT(vfm_hip, m) {
         "Tensor(a!) entity_params, Tensor(b!) bias_params, Tensor scalars, Tensor(c!) workspace, Tensor(d!) loss, "
         "int col, int flags, int lds_dim, float kl_weight, int n_iters, int reset) -> ()",
         &foldin_bound_split);
+  m.def("foldin_bound_split_prior(Tensor entities, Tensor chunk_ptr, Tensor chunks, Tensor y, Tensor op_x, "
+        "Tensor row_op, Tensor(a!) entity_params, Tensor(b!) bias_params, Tensor scalars, Tensor(c!) workspace, "
+        "Tensor(d!) loss, Tensor prior, int col, int flags, int lds_dim, float kl_weight, int n_iters, int reset) -> ()",
+        &foldin_bound_split_prior);
 }

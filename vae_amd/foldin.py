@@ -227,16 +227,22 @@ def check_args_bound(model, X, y, field, kl_weight=1.0, n_iters=8):
     return x, y
 
 
-def run_bound(model, X, y, field=0, kl_weight=1.0, n_iters=8, reset=False, lds_dim=-1, mode=MODE_FIT):
+def run_bound(model, X, y, field=0, kl_weight=1.0, n_iters=8, reset=False, lds_dim=-1, mode=MODE_FIT, priors=None):
     """One bound fold-in launch (include/vfm_bound.h: vfm_foldin_bound_f32): n_iters rounds of the Jaakkola-Jordan
     bound's two exact block minimisers for every folded entity (mode=MODE_OBJECTIVE: B_e at the current rows, nothing
-    written; n_iters is not used).  Returns (entities [E], loss [E] = B_e, rows [E])."""
+    written; n_iters is not used).  priors (a sweep.GroupPriors): under the folded field's prior, by
+    vfm_foldin_bound_prior_f32 (include/vfm_bound_prior.h).  Returns (entities [E], loss [E] = B_e, rows [E])."""
     x, y = check_args_bound(model, X, y, field, kl_weight, n_iters)
+    if priors is not None:
+        from . import sweep
+        sweep.check_priors(model, priors)
     _check_lds_dim(lds_dim)
     d = model.d
+    mid = () if priors is None else (priors.row(int(field)).to(model.device),)
+    tail = (int(field), OBJECTIVES["closed_form"], _lib.LIK_BERNOULLI)
     return _launch(model, x, y, field,
                    lambda o, E, R, n_ops: o.foldin_bound_workspace_bytes(E, R, n_ops, d, int(lds_dim)),
-                   lambda o, a, xs, grad, flags: o.foldin_bound(
-                       *a, int(field), OBJECTIVES["closed_form"], _lib.LIK_BERNOULLI, flags, int(lds_dim),
+                   lambda o, a, xs, grad, flags: (o.foldin_bound_prior if mid else o.foldin_bound)(
+                       *a, *mid, *tail, flags, int(lds_dim),
                        float(kl_weight), int(n_iters) if mode == MODE_FIT else 0, int(bool(reset)), int(mode)),
                    writes=mode == MODE_FIT)[:3]

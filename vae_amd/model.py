@@ -1330,7 +1330,8 @@ class VFM(nn.Module):
 
     @torch.no_grad()
     def fold_in_bound(self, X_new, y_new, field: int = 0, kl_weight: float = 1.0, n_iters: int = 8,
-                      reset: bool = False, split_rows=None, chunk_rows: int = 2048, max_workspace_bytes: int = 1 << 30):
+                      reset: bool = False, split_rows=None, chunk_rows: int = 2048, max_workspace_bytes: int = 1 << 30,
+                      priors=None):
         """fold_in for a 'class' model without Adam: the entities of X_new[:, field] are fitted by n_iters rounds of
         exact solves of the Jaakkola-Jordan quadratic bound of the Bernoulli likelihood, in one launch
         (include/vfm_bound.h: vfm_foldin_bound_f32; DESIGN.md §4 "Bound fold-in").  No lr, no n_samples, no seed: each
@@ -1354,24 +1355,32 @@ class VFM(nn.Module):
         other entities get the bits they get with None; a split entity's bits depend on its rows, chunk_rows and d
         alone, and are not those of None (the chunked sums associate differently).  The chunks' shares of one call
         take at most max_workspace_bytes: the split entities are processed in as many groups as that needs, with the
-        same result."""
+        same result.
+
+        priors: None, or a sweep.GroupPriors: every round solves under the folded field's prior N(mean, 1 / prec) per
+        coordinate in place of N(0, 1) (include/vfm_bound_prior.h; DESIGN.md §4 "Hierarchical bound sweeps"), reset=True
+        starts at that prior (mu = mean, sigma^2 = 1 / prec), and the loss carries the KL to it; an entity's bits then
+        depend on the prior too.  With the standard prior (0, 1) the rows and the losses are those of priors=None, bit
+        for bit.  Non-finite values or prec <= 0: ValueError."""
         from . import foldin, sweep
         if split_rows is None:
             sweep.check_chunk_rows(chunk_rows)
-            ents, loss, rows = foldin.run_bound(self, X_new, y_new, field, kl_weight, n_iters, reset)
+            ents, loss, rows = foldin.run_bound(self, X_new, y_new, field, kl_weight, n_iters, reset, priors=priors)
         else:
             ents, loss, rows = sweep.run_bound_split(self, X_new, y_new, field, kl_weight, n_iters, reset, split_rows,
-                                                     chunk_rows, max_workspace_bytes)
+                                                     chunk_rows, max_workspace_bytes, priors=priors)
         return {"entities": ents, "loss": loss, "rows": rows}
 
     @torch.no_grad()
-    def fold_in_bound_objective(self, X, y, field: int = 0, kl_weight: float = 1.0):
+    def fold_in_bound_objective(self, X, y, field: int = 0, kl_weight: float = 1.0, priors=None):
         """fold_in_bound's objective B_e at the current rows of the entities of X[:, field], nothing written: with
         xi_r = sqrt((E f_r)^2 + Var f_r), B_e = sum_r [-(y_r - 1/2) E f_r + xi_r / 2 + log1p(e^-xi_r)] + kl_weight KL.
-        Right after fold_in_bound on the same rows it returns that call's loss, bit for bit.  Returns dict(entities
-        [E], loss [E] fp32, rows [E])."""
+        Right after fold_in_bound on the same rows it returns that call's loss, bit for bit.  priors (a
+        sweep.GroupPriors): the KL is to the folded field's N(mean, 1 / prec), as fold_in_bound(priors=) reports it.
+        Returns dict(entities [E], loss [E] fp32, rows [E])."""
         from . import foldin
-        ents, loss, rows = foldin.run_bound(self, X, y, field, kl_weight, 1, False, mode=foldin.MODE_OBJECTIVE)
+        ents, loss, rows = foldin.run_bound(self, X, y, field, kl_weight, 1, False, mode=foldin.MODE_OBJECTIVE,
+                                            priors=priors)
         return {"entities": ents, "loss": loss, "rows": rows}
 
     @torch.no_grad()
@@ -1417,28 +1426,31 @@ class VFM(nn.Module):
         collapse onto one point would ask for an infinite one); KL is unimodal in 1 / prec, so the clamped value is
         the constrained minimiser and J still does not rise.  "clamped" in the result counts, per field, the
         (sweep, coordinate) pairs at which a clamp bound.  The global bias keeps N(0, 1).  learn_priors=False with
-        priors given leaves them untouched.  Sessions, ranking, the bound paths and the Adam trainers do not read
-        priors."""
+        priors given leaves them untouched.  fit_bound and the bound fold-in take the same priors; sessions (the bound
+        session included), ranking and the Adam trainers do not read priors."""
         from . import sweep
         return sweep.fit(self, X, y, n_sweeps, kl_weight, fields, update_scalars, split_rows, chunk_rows, on_step, tol,
                          priors=priors, learn_priors=learn_priors, learn_mean=learn_mean, prec_min=prec_min,
                          prec_max=prec_max)
 
     @torch.no_grad()
-    def bound_objective(self, X, y, kl_weight: float = 1.0) -> float:
+    def bound_objective(self, X, y, kl_weight: float = 1.0, priors=None) -> float:
         """The objective J of fit_bound at the current parameters ("Bound sweeps"): over the rows of X
         the Jaakkola-Jordan bound with xi at its optimum, -(y_r - 1/2) E f_r + xi_r / 2 + log1p(e^-xi_r) with
         xi_r = sqrt((E f_r)^2 + Var f_r), plus kl_weight times the KL to N(0, 1) of the factors of every entity that
         occurs in X (embedding and first-order weight) and of the global bias: an upper bound on the expected
         Bernoulli negative log likelihood plus kl_weight KL.  The per-row moments are the predictive_moments kernel's;
-        the sums and the KL terms are taken in fp64 on the device.  'class' models only, y in {0, 1}."""
+        the sums and the KL terms are taken in fp64 on the device.  'class' models only, y in {0, 1}.  priors (a
+        sweep.GroupPriors): every entity's KL is to its field's N(mean, 1 / prec), as in exact_objective; the global bias
+        keeps N(0, 1)."""
         from . import sweep
-        return sweep.bound_objective(self, X, y, kl_weight)
+        return sweep.bound_objective(self, X, y, kl_weight, priors)
 
     @torch.no_grad()
     def fit_bound(self, X, y, n_sweeps: int = 10, kl_weight: float = 1.0, n_iters: int = 8, fields=None,
                   update_bias: bool = True, split_rows="auto", chunk_rows: int = 2048, on_step=None,
-                  tol: Optional[float] = None):
+                  tol: Optional[float] = None, priors=None, learn_priors: bool = False, learn_mean: bool = True,
+                  prec_min: float = 1e-4, prec_max: float = 1e4):
         """fit_exact's counterpart for a 'class' model: coordinate ascent on bound_objective in which each block is the
         bound's exact minimiser, no learning rate, no sampling, no seed.  One sweep runs, for each field of `fields` in
         turn (default: all, in order), fold_in_bound's n_iters rounds for every entity of that field over all rows of X
@@ -1458,10 +1470,18 @@ class VFM(nn.Module):
         Measured on an MI355X against the fp64 restatement (tests/test_gpu_fit_bound.py): every written element within
         0.498 of its bound 2^-23 |ref| + n_iters solve_abs_term (+ scale_abs_term), J within 1.3e-8 relative.
         Returns dict(objective = J before the first block and after every sweep, sweeps = the number run, ms = each
-        sweep's device time from HIP events)."""
+        sweep's device time from HIP events).
+
+        Hierarchical bound sweeps.  priors, learn_priors, learn_mean, prec_min, prec_max: as in fit_exact.
+        Every field block runs its rounds under its field's prior N(mean, 1 / prec) per coordinate
+        (include/vfm_bound_prior.h) and J is bound_objective(priors=priors); with learn_priors=True the field's prior
+        block (the same closed form: it depends on q alone, not on the likelihood) follows each entity block and
+        on_step(sweep, ("prior", field)) follows it.  The result then holds "priors" and "clamped" as fit_exact's does.
+        The global bias keeps N(0, 1).  priors=None is the path above to the bit."""
         from . import sweep
         return sweep.fit_bound(self, X, y, n_sweeps, kl_weight, n_iters, fields, update_bias, split_rows, chunk_rows,
-                               on_step, tol)
+                               on_step, tol, priors=priors, learn_priors=learn_priors, learn_mean=learn_mean,
+                               prec_min=prec_min, prec_max=prec_max)
 
     @torch.no_grad()
     def fold_in_objective(self, X, y, field: int = 0, objective: Optional[str] = None, n_samples: int = 1,

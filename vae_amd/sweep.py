@@ -16,6 +16,8 @@ workgroup per chunk of rows), the others through vfm_foldin_solve_f32, unchanged
 With a GroupPriors (include/vfm_prior.h; DESIGN.md §4, "Hierarchical sweeps") every field has a Gaussian prior
 N(m, 1 / lam) per coordinate in place of N(0, 1): the same plan solves under it (vfm_foldin_solve_prior_f32,
 vfm_foldin_solve_split_prior_f32), update_prior is the prior's own exact block minimiser, and J carries the KL to it.
+The prior's minimiser depends on q alone, so fit_bound takes the same GroupPriors (include/vfm_bound_prior.h; DESIGN.md
+§4, "Hierarchical bound sweeps"): vfm_foldin_bound_prior_f32 and vfm_foldin_bound_split_prior_f32 run the rounds under it.
 
 For a 'class' model the same plan runs the Jaakkola-Jordan bound's rounds ("Bound sweeps"): light
 entities through vfm_foldin_bound_f32, unchanged, heavy ones through vfm_foldin_bound_split_f32;
@@ -38,7 +40,7 @@ MAX_WORKSPACE_BYTES = 1 << 30
 
 
 class GroupPriors:
-    """The Gaussian prior of every field of a 'reg' model: mean [F, d + 1] and prec [F, d + 1] fp32 (column 0: the
+    """The Gaussian prior of every field of a model: mean [F, d + 1] and prec [F, d + 1] fp32 (column 0: the
     first-order weight, 1 .. d: the factors), N(mean, 1 / prec) per coordinate.  It starts at (0, 1), the N(0, 1) every
     other path of the package assumes.  Held outside the model, like a session's theta: a model file stays a model file;
     state_dict / load_state_dict keep it beside one."""
@@ -241,15 +243,18 @@ class SweepPlan:
         return self._solve(model, kl_weight, (o.foldin_solve_workspace_bytes, light),
                            (o.foldin_split_workspace_bytes, split), _lib.LIK_NORMAL, mid=mid)
 
-    def run_bound(self, model, kl_weight, n_iters, reset=False):
+    def run_bound(self, model, kl_weight, n_iters, reset=False, prior=None):
         """n_iters rounds of the bound's two block minimisers for every entity of the plan, written into the model's
-        tables: the light entities by vfm_foldin_bound_f32, the heavy ones by vfm_foldin_bound_split_f32.  Returns
-        (entities [E] ascending, loss [E] = B_e, rows [E])."""
+        tables: the light entities by vfm_foldin_bound_f32, the heavy ones by vfm_foldin_bound_split_f32.  prior: None
+        (N(0, 1), the parent entry points) or the folded field's [2, d + 1] fp32 mean | precision on the device
+        (include/vfm_bound_prior.h).  Returns (entities [E] ascending, loss [E] = B_e, rows [E])."""
         o = _lib.ops()
+        light, split, mid = ((o.foldin_bound, o.foldin_bound_split, ()) if prior is None else
+                             (o.foldin_bound_prior, o.foldin_bound_split_prior, (prior,)))
         return self._solve(model, kl_weight,
-                           (o.foldin_bound_workspace_bytes, lambda *a: o.foldin_bound(*a, foldin.MODE_FIT)),
-                           (o.foldin_bound_split_workspace_bytes, o.foldin_bound_split), _lib.LIK_BERNOULLI,
-                           rows=(self.ys.numel(),), tail=(int(n_iters), int(bool(reset))))
+                           (o.foldin_bound_workspace_bytes, lambda *a: light(*a, foldin.MODE_FIT)),
+                           (o.foldin_bound_split_workspace_bytes, split), _lib.LIK_BERNOULLI,
+                           rows=(self.ys.numel(),), mid=mid, tail=(int(n_iters), int(bool(reset))))
 
 
 def _run_split(model, x, y, field, split_rows, chunk_rows, max_workspace_bytes, lds_dim, bound, run):
@@ -264,12 +269,13 @@ def _run_split(model, x, y, field, split_rows, chunk_rows, max_workspace_bytes, 
 
 
 def run_bound_split(model, X, y, field=0, kl_weight=1.0, n_iters=8, reset=False, split_rows="auto", chunk_rows=2048,
-                    max_workspace_bytes=MAX_WORKSPACE_BYTES, lds_dim=-1):
+                    max_workspace_bytes=MAX_WORKSPACE_BYTES, lds_dim=-1, priors=None):
     """foldin.run_bound with the entities of more than max(split_rows, d + 1) rows run by the split path; the same
     output contract: (entities [E] ascending, loss [E] = B_e, rows [E])."""
     x, y = foldin.check_args_bound(model, X, y, field, kl_weight, n_iters)
+    check_priors(model, priors)
     return _run_split(model, x, y, field, split_rows, chunk_rows, max_workspace_bytes, lds_dim, True,
-                      lambda plan: plan.run_bound(model, kl_weight, n_iters, reset))
+                      lambda plan: plan.run_bound(model, kl_weight, n_iters, reset, _prior_row(model, priors, field)))
 
 
 def run_exact_split(model, X, y, field=0, kl_weight=1.0, split_rows="auto", chunk_rows=2048,
@@ -308,6 +314,15 @@ def _add_kl64_rows(kl, e, b, d, link):
     added in this order: the objectives' fp64 bits depend on it."""
     kl = kl + _kl64(e[:, :d].double(), _link64(e[:, d:], link)).sum()
     return kl + _kl64(b[:, 0].double(), _link64(b[:, 1], link)).sum()
+
+
+def _add_kl64_rows_prior(kl, e, b, d, link, m, lam):
+    """_add_kl64_rows with the KL to N(m, 1 / lam), m and lam [n, d + 1] (column 0: the weight), taken as the kernels take
+    it: KL(N(mu, sg^2) || N(m, 1 / lam)) = KL(N(sqrt(lam) (mu - m), lam sg^2) || N(0, 1)).  At m = 0, lam = 1 every
+    operation is _add_kl64_rows', so the objective's fp64 bits are those of priors=None."""
+    sl = torch.sqrt(lam)
+    kl = kl + _kl64(sl[:, 1:] * (e[:, :d].double() - m[:, 1:]), sl[:, 1:] * _link64(e[:, d:], link)).sum()
+    return kl + _kl64(sl[:, 0] * (b[:, 0].double() - m[:, 0]), sl[:, 0] * _link64(b[:, 1], link)).sum()
 
 
 def _field_of(model, ids):
@@ -521,10 +536,12 @@ def _jj_weight64(xi):
     return torch.where(small, 0.25 - xi * xi / 48.0, torch.tanh(0.5 * safe) / (2.0 * safe))
 
 
-def bound_objective_terms(model, x, y, seen, kl_weight):
+def bound_objective_terms(model, x, y, seen, kl_weight, priors=None):
     """J of fit_bound as a 0-dim fp64 tensor on the device: the rows' collapsed bound terms
     -(y - 1/2) E f + xi / 2 + log1p(e^-xi), xi = sqrt((E f)^2 + Var f), from the predictive_moments kernel's fp32
-    moments, the KL of the entities `seen` (distinct ids) and of the global bias from the tables."""
+    moments, the KL of the entities `seen` (distinct ids) and of the global bias from the tables.  priors: the
+    entities' KL is to their field's N(mean, 1 / prec) (objective_terms' branch, in the standardised form that gives
+    the bits of priors=None at the standard prior); the global bias keeps N(0, 1)."""
     ent, bia, scal = model._views(model._flat)
     J = torch.zeros((), dtype=torch.float64, device=x.device)
     if x.shape[0]:
@@ -532,7 +549,11 @@ def bound_objective_terms(model, x, y, seen, kl_weight):
         xi = _xi64(m, v)
         J = J + (-(y.double() - 0.5) * m + 0.5 * xi + torch.log1p(torch.exp(-xi))).sum()
     kl = _kl64(scal[1].double(), _link64(scal[2], model.link))
-    if seen.numel():
+    if seen.numel() and priors is not None:
+        f = _field_of(model, seen)
+        kl = _add_kl64_rows_prior(kl, ent[seen], bia[seen], model.d, model.link, priors.mean.to(x.device).double()[f],
+                                  priors.prec.to(x.device).double()[f])
+    elif seen.numel():
         kl = _add_kl64_rows(kl, ent[seen], bia[seen], model.d, model.link)
     return J + float(kl_weight) * kl
 
@@ -553,21 +574,43 @@ def update_bias_bound(model, x, y, kl_weight):
     scal[1:3] = torch.stack([new_m0, new_s0]).float()
 
 
-def bound_objective(model, X, y, kl_weight=1.0):
+def bound_objective(model, X, y, kl_weight=1.0, priors=None):
     x, y, _ = _check_fit_bound(model, X, y, 0, kl_weight, 1, None, None, 1, None)
+    check_priors(model, priors)
     ops._need_cuda(model._flat, "the model's parameters")
     model._fresh_params()
-    return float(bound_objective_terms(model, x, y, torch.unique(x), kl_weight))
+    return float(bound_objective_terms(model, x, y, torch.unique(x), kl_weight, priors))
 
 
 def fit_bound(model, X, y, n_sweeps=10, kl_weight=1.0, n_iters=8, fields=None, update_bias=True, split_rows="auto",
-              chunk_rows=2048, on_step=None, tol=None, max_workspace_bytes=MAX_WORKSPACE_BYTES):
+              chunk_rows=2048, on_step=None, tol=None, max_workspace_bytes=MAX_WORKSPACE_BYTES, priors=None,
+              learn_priors=False, learn_mean=True, prec_min=1e-4, prec_max=1e4):
     x, y, fields = _check_fit_bound(model, X, y, n_sweeps, kl_weight, n_iters, fields, split_rows, chunk_rows, tol)
+    check_priors(model, priors)
+    prec_min, prec_max = check_prec_bounds(prec_min, prec_max)
     ops._need_cuda(model._flat, "the model's parameters")
+    if learn_priors and priors is None:
+        priors = GroupPriors(model.F, model.d, model.device)          # (created at N(0, 1), returned under "priors")
     model._fresh_params()
     seen = torch.unique(x)
     plans = {f: SweepPlan(model, x, y, f, split_rows, chunk_rows, max_workspace_bytes, bound=True)
              for f in dict.fromkeys(fields)}
-    return _sweeps(model, fields, n_sweeps, tol, on_step, lambda: bound_objective_terms(model, x, y, seen, kl_weight),
-                   lambda f: plans[f].run_bound(model, kl_weight, n_iters, False),     # (from the current rows: B = J at the start)
-                   after_sweep=(lambda: update_bias_bound(model, x, y, kl_weight)) if update_bias else None, tag="bias")
+    seen_f = {f: plans[f].ents[plans[f].asc] for f in plans} if learn_priors else {}
+    clamped = {f: torch.zeros((), dtype=torch.int64, device=x.device) for f in plans} if learn_priors else {}
+
+    def learn_prior(f):
+        n_clamped = update_prior(model, priors, f, seen_f[f], learn_mean, prec_min, prec_max)
+        if n_clamped is not None:
+            clamped[f] += n_clamped
+
+    out = _sweeps(model, fields, n_sweeps, tol, on_step,
+                  lambda: bound_objective_terms(model, x, y, seen, kl_weight, priors),
+                  # (from the current rows: B = J at the start)
+                  lambda f: plans[f].run_bound(model, kl_weight, n_iters, False, _prior_row(model, priors, f)),
+                  learn_prior if learn_priors else None,
+                  (lambda: update_bias_bound(model, x, y, kl_weight)) if update_bias else None, "bias")
+    if priors is not None:
+        out["priors"] = priors
+    if learn_priors:
+        out["clamped"] = {f: int(n) for f, n in clamped.items()}
+    return out
