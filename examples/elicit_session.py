@@ -31,6 +31,13 @@ Jaakkola-Jordan bound's exact solves (`VFM.elicit_field_bound`; 8 is an untuned 
 still unasked, beside the Adam session's (200 steps on the sampled objective) on the same model.
 
     python examples/elicit_session.py --bound [questions] [epochs]
+
+With --priors the model is trained by exact coordinate ascent with a learnt Gaussian prior per field
+(`VFM.fit_exact(learn_priors=True)`; with --bound after it, `VFM.fit_bound(learn_priors=True)` on a 'class' model) and the
+cold-start questionnaire (reset=True: every student starts at the prior) runs twice: under the learnt priors
+(`priors=`) and under N(0, 1), side by side.
+
+    python examples/elicit_session.py --priors [--bound] [questions] [sweeps]
 """
 import os
 import sys
@@ -106,7 +113,33 @@ def main_bound(argv):
                                       for s in strategies))
 
 
+def main_priors(argv):
+    bound = bool(argv) and argv[0] == "--bound"
+    argv = argv[1:] if bound else argv
+    questions = int(argv[0]) if len(argv) > 0 else 15
+    sweeps = int(argv[1]) if len(argv) > 1 else 10
+    N, M, X_train, X_test, y_train, y_test = load_fraction(os.path.join(ROOT, "tests", "golden", "fraction"))
+    X_train, X_test = torch.as_tensor(X_train), torch.as_tensor(X_test)
+    y_train, y_test = torch.as_tensor(y_train).float(), torch.as_tensor(y_test).float()
+    torch.manual_seed(42)
+    model = VFM(N, M, embedding_size=5, output="class" if bound else "reg", device="cuda")
+    fit = model.fit_bound if bound else model.fit_exact
+    priors = fit(X_train, y_train, n_sweeps=sweeps, learn_priors=True)["priors"]
+    strategies = ("random", "variance")
+    curve = model.elicitation_curve_field_bound if bound else model.elicitation_curve_field_exact
+    learnt = curve(X_test, y_test, questions, 0, strategies, reset=True, seed=1, priors=priors)
+    std = curve(X_test, y_test, questions, 0, strategies, reset=True, seed=1)
+    print(f"{len(torch.unique(X_test[:, 0]))} students, {len(X_test)} questions in the pool; the students' prior precisions "
+          f"{[round(float(v), 2) for v in priors.prec[0]]}")
+    print(f"{'AUC' if bound else 'RMSE'} on the unasked, cold start: learnt priors / N(0, 1)")
+    print("asked  " + "  ".join(f"{s:>19}" for s in strategies))
+    for q in range(questions + 1):
+        print(f"{q:5d}  " + "  ".join(f"{learnt[s][q]:8.4f} / {std[s][q]:8.4f}" for s in strategies))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--priors":
+        return main_priors(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--exact":
         return main_exact(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--bound":

@@ -215,6 +215,20 @@ class ElicitDesign(_Session):
                     + _TABLES_OUTPUTS + (("out_pool_score", C.c_void_p),) + _WORKSPACE)
 
 
+# ---- the exact, bound and design sessions under a learnt field prior (include/vfm_elicit_prior.h: the same structs plus
+# the prior pointer): (entry point, struct, size function, its argument types)
+ELICIT_PRIOR_EXPORTS = ("vfm_elicit_solve_prior_f32", "vfm_elicit_solve_prior_workspace_bytes",
+                        "vfm_elicit_bound_prior_f32", "vfm_elicit_bound_prior_workspace_bytes",
+                        "vfm_design_scores_prior_f32", "vfm_design_elicit_prior_f32", "vfm_design_prior_workspace_bytes")
+_ELICIT_PRIOR_PROTOTYPES = (
+    ("vfm_elicit_solve_prior_f32", ElicitSolve, "vfm_elicit_solve_prior_workspace_bytes", [_I64, _I64, _I64, _I32, _I32]),
+    ("vfm_elicit_bound_prior_f32", ElicitBound, "vfm_elicit_bound_prior_workspace_bytes",
+     [_I64, _I64, _I64, _I64, _I32, _I32, _I32]),
+    ("vfm_design_scores_prior_f32", ElicitDesign, "vfm_design_prior_workspace_bytes", [_I64, _I64, _I64, _I32, _I32]),
+    ("vfm_design_elicit_prior_f32", ElicitDesign, "vfm_design_prior_workspace_bytes", [_I64, _I64, _I64, _I32, _I32]),
+)
+
+
 for _c in (Problem, Index, Pipe, Elicit, ElicitField, ElicitSolve, ElicitBound, ElicitDesign, FoldinSolve, FoldinSplit,
            FoldinBound, FoldinBoundSplit):
     _c._names = frozenset(n for n, _ in _c._fields_)
@@ -312,6 +326,11 @@ def load():
     lib.vfm_elicit_bound_f32.restype = C.c_int
     lib.vfm_elicit_bound_workspace_bytes.argtypes = [i64, i64, i64, i64, i32, i32, i32]
     lib.vfm_elicit_bound_workspace_bytes.restype = i64
+    for entry, struct, size, size_args in _ELICIT_PRIOR_PROTOTYPES:
+        getattr(lib, entry).argtypes = [C.POINTER(struct), vp, vp]
+        getattr(lib, entry).restype = C.c_int
+        getattr(lib, size).argtypes = size_args
+        getattr(lib, size).restype = i64
     u64 = C.c_uint64
     lib.vfm_field_moments_post_f32.argtypes = [i64, i32, i32, i64, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, u64,
                                                vp, vp, vp, vp, vp]

@@ -76,7 +76,9 @@ _UNITS = [("vfm_abi.hip", "", _EXACT), ("vfm_index.hip", "", []), ("vfm_variants
           ("csrc_rank/vfm_elicit_field.hip", "", _EXACT),
           # the exact field-form session (vfm_elicit_solve_f32): the session loop and host path of
           # csrc_rank/vfm_elicit_exact_body.hpp with the field form's scores (csrc_rank/vfm_elicit_field_score.hpp); the
-          # loop runs the exact fold-in's body (csrc_rank/vfm_foldin_solve_body.hpp), hence its flag
+          # loop runs the exact fold-in's body (csrc_rank/vfm_foldin_solve_body.hpp), hence its flag.  This unit and the
+          # next, and vfm_elicit_bound.hip below, each hold their session under a field prior as well
+          # (include/vfm_elicit_prior.h: the PRIOR = true instantiation beside the parent's, one host path for both)
           ("csrc_rank/vfm_elicit_solve.hip", "", _EXACT),
           # target-aware elicitation (include/vfm_design.h): the same session loop and host path with the score of
           # csrc_rank/vfm_design_score.hpp, which pins its own contraction expression by expression; the same flag, and a
@@ -102,10 +104,11 @@ _UNITS = [("vfm_abi.hip", "", _EXACT), ("vfm_index.hip", "", []), ("vfm_variants
 RANK_DIR = os.path.join(HERE, "csrc_rank")
 VAR_DIR = os.path.join(HERE, "csrc_var")
 # the public headers beside include/vfm_hip.h (vfm_foldin_ops.cpp holds the ops of foldin, sweep, bound_sweep, prior,
-# bound_prior and vfm_bound.h's fold-in; vfm_elicit_ops.cpp holds vfm_bound.h's session)
+# bound_prior and vfm_bound.h's fold-in; vfm_elicit_ops.cpp holds vfm_bound.h's session and, with vfm_design_ops.cpp,
+# the ops of elicit_prior)
 PUBLIC_HDRS = tuple(os.path.join(ROOT, "include", f"vfm_{n}.h")
                     for n in ("rank", "foldin", "elicit", "design", "variant_step", "sweep", "bound", "bound_sweep", "prior",
-                              "bound_prior"))
+                              "bound_prior", "elicit_prior"))
 # the TORCH_LIBRARY fragments linked into the shim beside csrc/vfm_torch_ops.cpp, and the header they share: host C++
 # only, so it is no source of libvfm_hip.so.  One file per family
 OPS_SOURCES = tuple(os.path.join(RANK_DIR, f"vfm_{n}_ops.cpp") for n in ("rank", "foldin", "elicit", "design"))

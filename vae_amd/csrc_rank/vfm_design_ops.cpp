@@ -1,10 +1,12 @@
-// vfm_design_ops.cpp -- torch.ops.vfm_hip.{design_workspace_bytes, design_scores, design_elicit}: the TORCH_LIBRARY
-// fragment over include/vfm_design.h.  Like vfm_elicit_ops.cpp it only validates tensors, takes the current HIP stream
+// vfm_design_ops.cpp -- torch.ops.vfm_hip.{design_workspace_bytes, design_scores, design_elicit, design_scores_prior,
+// design_elicit_prior}: the TORCH_LIBRARY fragment over include/vfm_design.h and its forms under a field prior
+// (include/vfm_elicit_prior.h).  Like vfm_elicit_ops.cpp it only validates tensors, takes the current HIP stream
 // of the tensors' device and forwards raw pointers; all arithmetic is in the HIP kernels.  The rows, tables, workspace,
 // outputs and history are the session parts of vfm_ops_common.hpp; the targets are this form's own.
 #include "vfm_ops_common.hpp"
 
 #include "vfm_design.h"
+#include "vfm_elicit_prior.h"
 
 namespace {
 
@@ -32,8 +34,9 @@ void fill_design(vfm_design_t& p, const Tensor& entities, const Tensor& pool_ptr
   p.field = (int32_t)field; p.flags = (int32_t)flags; p.lds_dim = (int32_t)lds_dim; p.kl_weight = (float)kl_weight;
 }
 
-// every pool row's score with R = the respondent's history
-void design_scores(const Tensor& entities, const Tensor& pool_ptr, const Tensor& pool_x, const optional<Tensor>& hist_ptr,
+// every pool row's score with R = the respondent's history; prior: NULL, or the respondents' field prior [2, d + 1]
+// (design_scores_prior)
+void design_scores_call(const Tensor* prior, const Tensor& entities, const Tensor& pool_ptr, const Tensor& pool_x, const optional<Tensor>& hist_ptr,
                    const optional<Tensor>& hist_op, const Tensor& tgt_ptr, const Tensor& tgt_op, const Tensor& op_x,
                    const Tensor& pool_op, Tensor entity, Tensor bias, const Tensor& scalars, Tensor workspace,
                    Tensor out_pool_score, int64_t field, int64_t flags, double kl_weight) {
@@ -44,11 +47,29 @@ void design_scores(const Tensor& entities, const Tensor& pool_ptr, const Tensor&
   TORCH_CHECK(dev_tensor(out_pool_score, at::kFloat, "out_pool_score").numel() >= p.P, "out_pool_score must be [P]");
   p.out_pool_score = out_pool_score.data_ptr<float>();
   c10::hip::HIPGuard guard(entities.get_device());
-  check(vfm_design_scores_f32(&p, stream_of(entities)), "vfm_design_scores_f32");
+  if (prior) check(vfm_design_scores_prior_f32(&p, prior_of(*prior, p.d), stream_of(entities)), "vfm_design_scores_prior_f32");
+  else check(vfm_design_scores_f32(&p, stream_of(entities)), "vfm_design_scores_f32");
 }
 
-// the sessions: elicit_solve's tensors without the strategy's, plus the targets
-void design_elicit(const Tensor& entities, const Tensor& pool_ptr, const Tensor& pool_x, const Tensor& pool_y,
+#define VFM_SCORES_TENSORS                                                                                               \
+  const Tensor &entities, const Tensor &pool_ptr, const Tensor &pool_x, const optional<Tensor>&hist_ptr,                 \
+      const optional<Tensor>&hist_op, const Tensor &tgt_ptr, const Tensor &tgt_op, const Tensor &op_x,                   \
+      const Tensor &pool_op, Tensor entity, Tensor bias, const Tensor &scalars, Tensor workspace, Tensor out_pool_score
+#define VFM_SCORES_TENSOR_NAMES                                                                                          \
+  entities, pool_ptr, pool_x, hist_ptr, hist_op, tgt_ptr, tgt_op, op_x, pool_op, entity, bias, scalars, workspace,       \
+      out_pool_score
+
+void design_scores(VFM_SCORES_TENSORS, int64_t field, int64_t flags, double kl_weight) {
+  design_scores_call(nullptr, VFM_SCORES_TENSOR_NAMES, field, flags, kl_weight);
+}
+
+void design_scores_prior(VFM_SCORES_TENSORS, const Tensor& prior, int64_t field, int64_t flags, double kl_weight) {
+  design_scores_call(&prior, VFM_SCORES_TENSOR_NAMES, field, flags, kl_weight);
+}
+
+// the sessions: elicit_solve's tensors without the strategy's, plus the targets; prior: as design_scores_call's
+// (design_elicit_prior)
+void design_elicit_call(const Tensor* prior, const Tensor& entities, const Tensor& pool_ptr, const Tensor& pool_x, const Tensor& pool_y,
                    const optional<Tensor>& hist_ptr, const optional<Tensor>& hist_x, const optional<Tensor>& hist_y,
                    const optional<Tensor>& hist_op, const Tensor& tgt_ptr, const Tensor& tgt_op, const Tensor& op_x,
                    const Tensor& pool_op, Tensor entity, Tensor bias, const Tensor& scalars, Tensor workspace,
@@ -62,7 +83,29 @@ void design_elicit(const Tensor& entities, const Tensor& pool_ptr, const Tensor&
   fill_field_history(p, hist_ptr, hist_x, hist_y, hist_op);
   p.reset = (int32_t)reset; p.write = (int32_t)write;
   c10::hip::HIPGuard guard(entities.get_device());
-  check(vfm_design_elicit_f32(&p, stream_of(entities)), "vfm_design_elicit_f32");
+  if (prior) check(vfm_design_elicit_prior_f32(&p, prior_of(*prior, p.d), stream_of(entities)), "vfm_design_elicit_prior_f32");
+  else check(vfm_design_elicit_f32(&p, stream_of(entities)), "vfm_design_elicit_f32");
+}
+
+#define VFM_DESIGN_TENSORS                                                                                               \
+  const Tensor &entities, const Tensor &pool_ptr, const Tensor &pool_x, const Tensor &pool_y,                            \
+      const optional<Tensor>&hist_ptr, const optional<Tensor>&hist_x, const optional<Tensor>&hist_y,                     \
+      const optional<Tensor>&hist_op, const Tensor &tgt_ptr, const Tensor &tgt_op, const Tensor &op_x,                   \
+      const Tensor &pool_op, Tensor entity, Tensor bias, const Tensor &scalars, Tensor workspace, Tensor out_row,        \
+      Tensor out_score, Tensor out_loss, const optional<Tensor>&out_theta, const optional<Tensor>&out_mean,              \
+      const optional<Tensor>&out_var
+#define VFM_DESIGN_TENSOR_NAMES                                                                                          \
+  entities, pool_ptr, pool_x, pool_y, hist_ptr, hist_x, hist_y, hist_op, tgt_ptr, tgt_op, op_x, pool_op, entity, bias,   \
+      scalars, workspace, out_row, out_score, out_loss, out_theta, out_mean, out_var
+
+void design_elicit(VFM_DESIGN_TENSORS, int64_t field, int64_t n_rounds, int64_t flags, int64_t reset, int64_t write,
+                   int64_t lds_dim, double kl_weight) {
+  design_elicit_call(nullptr, VFM_DESIGN_TENSOR_NAMES, field, n_rounds, flags, reset, write, lds_dim, kl_weight);
+}
+
+void design_elicit_prior(VFM_DESIGN_TENSORS, const Tensor& prior, int64_t field, int64_t n_rounds, int64_t flags,
+                         int64_t reset, int64_t write, int64_t lds_dim, double kl_weight) {
+  design_elicit_call(&prior, VFM_DESIGN_TENSOR_NAMES, field, n_rounds, flags, reset, write, lds_dim, kl_weight);
 }
 
 }  // namespace
@@ -79,4 +122,15 @@ TORCH_LIBRARY_FRAGMENT(vfm_hip, m) {
         "Tensor(e!) out_score, Tensor(f!) out_loss, Tensor(g!)? out_theta, Tensor(h!)? out_mean, Tensor(i!)? out_var, "
         "int field, int n_rounds, int flags, int reset, int write, int lds_dim, float kl_weight) -> ()",
         &design_elicit);
+  m.def("design_scores_prior(Tensor entities, Tensor pool_ptr, Tensor pool_x, Tensor? hist_ptr, Tensor? hist_op, "
+        "Tensor tgt_ptr, Tensor tgt_op, Tensor op_x, Tensor pool_op, Tensor entity_params, Tensor bias_params, "
+        "Tensor scalars, Tensor(a!) workspace, Tensor(b!) out_pool_score, Tensor prior, int field, int flags, "
+        "float kl_weight) -> ()",
+        &design_scores_prior);
+  m.def("design_elicit_prior(Tensor entities, Tensor pool_ptr, Tensor pool_x, Tensor pool_y, Tensor? hist_ptr, "
+        "Tensor? hist_x, Tensor? hist_y, Tensor? hist_op, Tensor tgt_ptr, Tensor tgt_op, Tensor op_x, Tensor pool_op, "
+        "Tensor(a!) entity_params, Tensor(b!) bias_params, Tensor scalars, Tensor(c!) workspace, Tensor(d!) out_row, "
+        "Tensor(e!) out_score, Tensor(f!) out_loss, Tensor(g!)? out_theta, Tensor(h!)? out_mean, Tensor(i!)? out_var, "
+        "Tensor prior, int field, int n_rounds, int flags, int reset, int write, int lds_dim, float kl_weight) -> ()",
+        &design_elicit_prior);
 }

@@ -14,12 +14,33 @@
 // to fp32 once.  Orders: S in row order, W in the target list's order, the score from the bias term on in k order.
 // Contraction: S is phase A of solve_body -- the same statement under the same pragma (`on`), so the same bits; W, v
 // and the score are under `off`.
+//
+// PRIOR (include/vfm_elicit_prior.h): under the respondents' field prior N(m_c, 1 / lam_c) the optimum's scales are
+//   sigma_k^2 = kl / (kl lam_k + prec S_k),  sigma_w^2 = kl / (kl lam_0 + prec n)
+// so v takes kll = kl lam_c as the denominator's constant; kll is formed in a statement of its own (as put_params' caller
+// and k_bsplit_solve form it), so at lam = 1 it is kl and v rounds as with PRIOR off.  lam [d + 1] (0: the weight) is the
+// second half of the prior staged in LDS (stage_prior); m is never read: the score still depends on no answer.
 #pragma once
 
-// v(S) = kl / (kl + prec S): the squared scale of the optimum of a coordinate whose rows sum to S
-__device__ __forceinline__ double design_v(double kl, double prec, double S) {
+// v(S) = kl / (kl + prec S): the squared scale of the optimum of a coordinate whose rows sum to S  (PRIOR: kl / (kll +
+// prec S))
+template <bool PRIOR = false>
+__device__ __forceinline__ double design_v(double kl, double prec, double S, double kll = 0.) {
 #pragma clang fp contract(off)
-  return kl / (kl + prec * S);
+  if constexpr (PRIOR) return kl / (kll + prec * S);
+  else return kl / (kl + prec * S);
+}
+
+// vS [d] of S [d], by the thread that wrote S[k] (the walk's own distribution); lam: as design_score's
+template <bool PRIOR = false>
+__device__ __forceinline__ void design_put_v(double kl, double prec, const double* S, int d, double* vS,
+                                             const double* lam = nullptr) {
+#pragma clang fp contract(off)
+  for (int k = threadIdx.x; k < d; k += FB) {
+    double kll = 0.;
+    if constexpr (PRIOR) kll = kl * lam[1 + k];
+    vS[k] = design_v<PRIOR>(kl, prec, S[k], kll);
+  }
 }
 
 // S [d]: thread t forms the coordinates t, t + FB, .. over the n rows of `rows` (op(i): the operand of row i) in row
@@ -64,15 +85,20 @@ __device__ __forceinline__ void design_walk_W(const double* ops64, int64_t n_ops
 }
 
 // the score of the candidate whose operand row is opq = ops64 + o * 3 d, for a respondent with n fold rows, sums S,
-// weights W and vS[k] = design_v(kl, prec, S[k])
+// weights W and vS[k] = design_v(kl, prec, S[k]) (design_put_v); PRIOR: lam [d + 1], the prior's precisions
+template <bool PRIOR = false>
 __device__ __forceinline__ float design_score(const double* S, const double* W, const double* vS, double n,
-                                              const double* opq, int d, double kl, double prec) {
+                                              const double* opq, int d, double kl, double prec,
+                                              const double* lam = nullptr) {
 #pragma clang fp contract(off)
-  double acc = design_v(kl, prec, n) - design_v(kl, prec, n + 1.0);
+  double kll = 0.;
+  if constexpr (PRIOR) kll = kl * lam[0];
+  double acc = design_v<PRIOR>(kl, prec, n, kll) - design_v<PRIOR>(kl, prec, n + 1.0, kll);
   for (int k = 0; k < d; ++k) {
     const double M = opq[k], A = opq[d + k];
     const double a = A + M * M;
-    const double drop = vS[k] - design_v(kl, prec, S[k] + a);
+    if constexpr (PRIOR) kll = kl * lam[1 + k];
+    const double drop = vS[k] - design_v<PRIOR>(kl, prec, S[k] + a, kll);
     acc += W[k] * drop;
   }
   return (float)acc;

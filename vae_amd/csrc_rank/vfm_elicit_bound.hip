@@ -9,6 +9,11 @@
 // was scored from) instead of a table row.  The scales of the iterate sit behind the LDS triangle as in k_foldin_bound;
 // respondent g's row weights at wrow[h0 + g Q + i] for fold row i, a range no other workgroup touches while hist_ptr
 // does not decrease.
+//
+// vfm_elicit_bound_prior_f32 (include/vfm_elicit_prior.h) runs k_elicit_bound_prior, the PRIOR = true instantiation of the
+// same session loop: the respondents' field prior staged in LDS in front, bound_body<.., true> as the fold (still from
+// theta_e: prior_start stays false, `reset` is the session's own prior row), one more pointer among the kernel's
+// arguments; k_elicit_bound is the instantiation without it, unchanged.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -17,6 +22,7 @@
 
 #include "vfm_args.hpp"
 #include "vfm_bound.h"
+#include "vfm_elicit_prior.h"
 #include "vfm_launch.hpp"            // launch_status
 #include "vfm_rank_tile.hpp"         // score_of, philox_uniform, link_of
 #include "vfm_field_ctx.hpp"         // ctx_valid, field_chain_moments
@@ -41,18 +47,23 @@ struct ElicitBoundArgs : ElicitSolveArgs {   // (e.f.n_steps: the rounds of the 
 // the fold of a round: n_iters rounds of the bound from theta_e
 struct BoundFold {
   __host__ __device__ static int64_t lds_doubles(int d) { return d + 1; }
-  template <int W, int CPL, int LINK, class Rows, class Store>
+  template <int W, int CPL, int LINK, bool PRIOR, class Rows, class Store>
   __device__ __forceinline__ static void run(const ElicitBoundArgs& s, const FoldArgs& f, const Rows& rows, int64_t n,
                                              int64_t g, double* sm, double* Hm, double* sg2, float, double, float* loss,
-                                             Store&& store) {
-    bound_body<W, CPL, LINK>(f, s.ops64, s.cm64, s.cv64, s.wrow + rows.h0 + g * s.e.Q, rows, n, false, sm, Hm, sg2, loss,
-                             store);
+                                             Store&& store, const double* pr) {
+    bound_body<W, CPL, LINK, PRIOR>(f, s.ops64, s.cm64, s.cv64, s.wrow + rows.h0 + g * s.e.Q, rows, n, false, sm, Hm, sg2,
+                                    loss, store, pr);
   }
 };
 
 template <int W, int CPL, int LINK>
 __global__ __launch_bounds__(FB) void k_elicit_bound(const ElicitBoundArgs s) {
   exact_session<MomentScore, W, CPL, LINK, BoundFold>(s);
+}
+
+template <int W, int CPL, int LINK>
+__global__ __launch_bounds__(FB) void k_elicit_bound_prior(const ElicitBoundArgs s, const float* __restrict__ prior) {
+  exact_session<MomentScore, W, CPL, LINK, BoundFold, true>(s, prior);
 }
 
 // workspace: [the exact session's parts up to its slabs | c_var | the row weights | the slabs]
@@ -65,6 +76,8 @@ inline int64_t off_session_slabs(int64_t U, int64_t P, int64_t H, int64_t n_ops,
 }  // namespace
 }  // namespace vfm
 
+static int elicit_bound_call(const vfm_elicit_bound_t* p, const float* prior, void* stream);
+
 extern "C" {
 
 int64_t vfm_elicit_bound_workspace_bytes(int64_t U, int64_t P, int64_t H, int64_t n_ops, int32_t d, int32_t n_rounds,
@@ -75,7 +88,21 @@ int64_t vfm_elicit_bound_workspace_bytes(int64_t U, int64_t P, int64_t H, int64_
   return vfm::off_session_slabs(U, P, H, n_ops, d, n_rounds) + vfm::slabs_bytes(U, d, lds_dim);
 }
 
-int vfm_elicit_bound_f32(const vfm_elicit_bound_t* p, void* stream) {
+int64_t vfm_elicit_bound_prior_workspace_bytes(int64_t U, int64_t P, int64_t H, int64_t n_ops, int32_t d,
+                                               int32_t n_rounds, int32_t lds_dim) {
+  return vfm_elicit_bound_workspace_bytes(U, P, H, n_ops, d, n_rounds, lds_dim);     // (the prior lives in LDS)
+}
+
+int vfm_elicit_bound_f32(const vfm_elicit_bound_t* p, void* stream) { return elicit_bound_call(p, nullptr, stream); }
+
+int vfm_elicit_bound_prior_f32(const vfm_elicit_bound_t* p, const float* prior, void* stream) {
+  return elicit_bound_call(p, prior, stream);
+}
+
+}  // extern "C"
+
+// both entry points: prior == NULL is vfm_elicit_bound_f32
+static int elicit_bound_call(const vfm_elicit_bound_t* p, const float* prior, void* stream) {
   using namespace vfm;
   if (int rc = check_session_struct(
           p, "vfm_elicit_bound_f32: NULL argument struct",
@@ -116,10 +143,14 @@ int vfm_elicit_bound_f32(const vfm_elicit_bound_t* p, void* stream) {
   if (int rc = launch_exact_session_preps(p, sp, s, st)) return rc;
   if (p->n_ops > 0)
     if (int rc = launch_bound_prep(sp, s.e.f, p->n_ops, p->op_x, cv64, st)) return rc;
-  launch_exact_session<MomentScore, BoundFold>(sp, s, grid, st, [](auto w_, auto c, auto link) {
-    return k_elicit_bound<decltype(w_)::value, decltype(c)::value, decltype(link)::value>;
-  });
+  if (prior) {
+    launch_exact_session<MomentScore, BoundFold>(sp, s, grid, st, [](auto w_, auto c, auto link) {
+      return k_elicit_bound_prior<decltype(w_)::value, decltype(c)::value, decltype(link)::value>;
+    }, 2 * (int64_t)(p->d + 1), prior);
+  } else {
+    launch_exact_session<MomentScore, BoundFold>(sp, s, grid, st, [](auto w_, auto c, auto link) {
+      return k_elicit_bound<decltype(w_)::value, decltype(c)::value, decltype(link)::value>;
+    });
+  }
   return launch_status("k_elicit_bound");
 }
-
-}  // extern "C"

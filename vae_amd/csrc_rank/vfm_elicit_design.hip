@@ -15,6 +15,11 @@
 // The operand table also holds the target contexts.  No atomics, no host synchronisation.
 //
 // LDS of a session block: k_elicit_solve's plus 2 d doubles (W, v(S)) between the triangle and the waves' winners.
+//
+// vfm_design_scores_prior_f32 and vfm_design_elicit_prior_f32 (include/vfm_elicit_prior.h) run the PRIOR = true
+// instantiations (k_design_score<LINK, true>, k_elicit_design_prior): the respondents' field prior staged in LDS in
+// front, the score's v under its precisions (vfm_design_score.hpp), one more pointer among the kernel's arguments; the
+// instantiations without it are the parents', unchanged.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -23,6 +28,7 @@
 
 #include "vfm_args.hpp"
 #include "vfm_design.h"
+#include "vfm_elicit_prior.h"
 #include "vfm_launch.hpp"            // launch_status
 #include "vfm_rank_tile.hpp"         // link_of
 #include "vfm_field_ctx.hpp"         // ctx_valid, field_chain_moments
@@ -50,14 +56,20 @@ struct HistOps {
   __device__ __forceinline__ int64_t op(int64_t i) const { return o[i]; }
 };
 
-template <int LINK>
-__global__ __launch_bounds__(FB) void k_design_score(const DesignArgs s) {
-  extern __shared__ double sm[];
+template <int LINK, bool PRIOR>
+__device__ __forceinline__ void design_score_pass(const DesignArgs& s, const float* __restrict__ prior) {
+  extern __shared__ double sm_all[];
   const ElicitFieldArgs& a = s.e;
   const FoldArgs& f = a.f;
   const int tid = threadIdx.x, d = f.d;
+  double* sm = sm_all + (PRIOR ? 2 * (d + 1) : 0);         // (the prior in front: mean | precision [2, d + 1])
+  const double* lam = PRIOR ? sm_all + (d + 1) : nullptr;
   double *S = sm, *Wt = sm + d, *vS = sm + 2 * d;
   const double prec = link_d<LINK>(f.scal[0]), kl = f.klw;
+  if constexpr (PRIOR) {
+    stage_prior(prior, sm_all, d + 1);
+    __syncthreads();
+  }
 
   for (int64_t g = blockIdx.x; g < a.U; g += gridDim.x) {
     const RespondentRanges r = respondent_ranges(a, g);
@@ -68,22 +80,33 @@ __global__ __launch_bounds__(FB) void k_design_score(const DesignArgs s) {
 
     design_walk_S(s.ops64, a.n_ops, d, HistOps{a.hist_op + r.h0}, r.nh, S);
     design_walk_W(s.ops64, a.n_ops, d, s.tgt_op + t0, nt, Wt);
-    for (int k = tid; k < d; k += FB) vS[k] = design_v(kl, prec, S[k]);       // (the thread that wrote S[k])
+    design_put_v<PRIOR>(kl, prec, S, d, vS, lam);          // (the thread that wrote S[k])
     __syncthreads();
 
     for (int64_t p = tid; p < r.np; p += FB) {
       const int64_t o = a.pool_op[r.p0 + p];
       float sc = __builtin_nanf("");
       if (pool_row_ok(a, r.p0 + p, o, eok))
-        sc = design_score(S, Wt, vS, (double)r.nh, s.ops64 + o * 3 * (int64_t)d, d, kl, prec);
+        sc = design_score<PRIOR>(S, Wt, vS, (double)r.nh, s.ops64 + o * 3 * (int64_t)d, d, kl, prec, lam);
       s.out_pool_score[r.p0 + p] = sc;
     }
     __syncthreads();                     // (S, W, v(S) are rewritten by the next respondent)
   }
 }
 
+template <int LINK>
+__global__ __launch_bounds__(FB) void k_design_score(const DesignArgs s) {
+  design_score_pass<LINK, false>(s, nullptr);
+}
+
+template <int LINK>
+__global__ __launch_bounds__(FB) void k_design_score_prior(const DesignArgs s, const float* __restrict__ prior) {
+  design_score_pass<LINK, true>(s, prior);
+}
+
 // the questions scored by the drop of the targets' variance that the respondent's scales carry
-struct DesignScore {
+template <bool PRIOR>
+struct DesignScoreT {
   using Args = DesignArgs;
   static constexpr bool THETA_OPS_EVERY_ROUND = false, ROUND_END_BARRIER = true;
   __host__ __device__ static int64_t lds_doubles(int d) { return 2 * (int64_t)d; }
@@ -91,8 +114,10 @@ struct DesignScore {
   const DesignArgs& s;
   double *Sv, *Wt, *vS;                  // S: coordinates 1 .. d of solve_body's scale sums (SBd) | [d] W | [d] v(S)
   double prec, kl;
-  __device__ __forceinline__ DesignScore(const Args& s_, double* sm, double* own, double prec_)
-      : s(s_), Sv(sm + 6 * (s_.e.f.d + 1) + 1), Wt(own), vS(own + s_.e.f.d), prec(prec_), kl(s_.e.f.klw) {}
+  const double* lam;                     // PRIOR: the prior's precisions [d + 1] in LDS
+  __device__ __forceinline__ DesignScoreT(const Args& s_, double* sm, double* own, double prec_, const double* pr)
+      : s(s_), Sv(sm + 6 * (s_.e.f.d + 1) + 1), Wt(own), vS(own + s_.e.f.d), prec(prec_), kl(s_.e.f.klw),
+        lam(PRIOR ? pr + (s_.e.f.d + 1) : nullptr) {}
 
   __device__ __forceinline__ void begin_respondent(int64_t g) const {          // the target weights, once
     int64_t t0, nt;
@@ -104,7 +129,7 @@ struct DesignScore {
     if (q == s.e.Q) return;              // S over the n fold rows so far, in row order, and v(S)
     const int d = s.e.f.d;
     design_walk_S(s.ops64, s.e.n_ops, d, rows, n, Sv);
-    for (int k = threadIdx.x; k < d; k += FB) vS[k] = design_v(kl, prec, Sv[k]);  // (the thread that wrote Sv[k])
+    design_put_v<PRIOR>(kl, prec, Sv, d, vS, lam);         // (the thread that wrote Sv[k])
   }
 
   template <int DP>
@@ -118,13 +143,19 @@ struct DesignScore {
     if (a.out_mean && ok) pool_row_moments<DP>(a, o, uth, mean, var);
     put_moments(a, q, p0, p, mean, var);
     if (was || q == a.Q || !ok) return __builtin_nanf("");
-    return design_score(Sv, Wt, vS, (double)n, s.ops64 + o * 3 * (int64_t)d, d, kl, prec);
+    return design_score<PRIOR>(Sv, Wt, vS, (double)n, s.ops64 + o * 3 * (int64_t)d, d, kl, prec, lam);
   }
 };
+using DesignScore = DesignScoreT<false>;
 
 template <int W, int CPL, int LINK>
 __global__ __launch_bounds__(FB) void k_elicit_design(const DesignArgs s) {
   exact_session<DesignScore, W, CPL, LINK>(s);
+}
+
+template <int W, int CPL, int LINK>
+__global__ __launch_bounds__(FB) void k_elicit_design_prior(const DesignArgs s, const float* __restrict__ prior) {
+  exact_session<DesignScoreT<true>, W, CPL, LINK, SolveFold, true>(s, prior);
 }
 
 // the checks of both entry points, in the order they are reported; session: vfm_design_elicit_f32
@@ -158,13 +189,35 @@ unsigned design_args(const vfm_design_t* p, bool session, DesignArgs& s) {
 }  // namespace
 }  // namespace vfm
 
+static int design_scores_call(const vfm_design_t* p, const float* prior, void* stream);
+static int design_elicit_call(const vfm_design_t* p, const float* prior, void* stream);
+
 extern "C" {
 
 int64_t vfm_design_workspace_bytes(int64_t U, int64_t P, int64_t n_ops, int32_t d, int32_t lds_dim) {
   return vfm::exact_session_workspace_bytes(U, P, n_ops, d, lds_dim);
 }
 
-int vfm_design_scores_f32(const vfm_design_t* p, void* stream) {
+int64_t vfm_design_prior_workspace_bytes(int64_t U, int64_t P, int64_t n_ops, int32_t d, int32_t lds_dim) {
+  return vfm_design_workspace_bytes(U, P, n_ops, d, lds_dim);          // (the prior lives in LDS, not in the workspace)
+}
+
+int vfm_design_scores_f32(const vfm_design_t* p, void* stream) { return design_scores_call(p, nullptr, stream); }
+
+int vfm_design_scores_prior_f32(const vfm_design_t* p, const float* prior, void* stream) {
+  return design_scores_call(p, prior, stream);
+}
+
+int vfm_design_elicit_f32(const vfm_design_t* p, void* stream) { return design_elicit_call(p, nullptr, stream); }
+
+int vfm_design_elicit_prior_f32(const vfm_design_t* p, const float* prior, void* stream) {
+  return design_elicit_call(p, prior, stream);
+}
+
+}  // extern "C"
+
+// both one-round entry points: prior == NULL is vfm_design_scores_f32
+static int design_scores_call(const vfm_design_t* p, const float* prior, void* stream) {
   using namespace vfm;
   if (int rc = check_design(p, false, "vfm_design_scores_f32: NULL argument struct")) return rc;
   if (p->U == 0 || p->P == 0) return 0;
@@ -182,13 +235,18 @@ int vfm_design_scores_f32(const vfm_design_t* p, void* stream) {
                        p->op_x, f.entity, f.bias, f.scal, (double*)s.ops64, (double*)s.cm64);
     rc = launch_status("k_foldin_solve_prep");
     if (rc) return;
-    hipLaunchKernelGGL(k_design_score<decltype(link)::value>, dim3(grid), dim3(FB), (size_t)3 * f.d * 8, st, s);
+    if (prior)
+      hipLaunchKernelGGL(k_design_score_prior<decltype(link)::value>, dim3(grid), dim3(FB),
+                         (size_t)(3 * f.d + 2 * (f.d + 1)) * 8, st, s, prior);
+    else
+      hipLaunchKernelGGL(k_design_score<decltype(link)::value>, dim3(grid), dim3(FB), (size_t)3 * f.d * 8, st, s);
     rc = launch_status("k_design_score");
   });
   return rc;
 }
 
-int vfm_design_elicit_f32(const vfm_design_t* p, void* stream) {
+// both session entry points: prior == NULL is vfm_design_elicit_f32
+static int design_elicit_call(const vfm_design_t* p, const float* prior, void* stream) {
   using namespace vfm;
   if (int rc = check_design(p, true, "vfm_design_elicit_f32: NULL argument struct")) return rc;
   if (p->U == 0) return 0;
@@ -197,10 +255,14 @@ int vfm_design_elicit_f32(const vfm_design_t* p, void* stream) {
   DesignArgs s;
   const unsigned grid = design_args(p, true, s);
   if (int rc = launch_exact_session_preps(p, sp, s, st)) return rc;
-  launch_exact_session<DesignScore>(sp, s, grid, st, [](auto w, auto c, auto link) {
-    return k_elicit_design<decltype(w)::value, decltype(c)::value, decltype(link)::value>;
-  });
+  if (prior) {
+    launch_exact_session<DesignScoreT<true>>(sp, s, grid, st, [](auto w, auto c, auto link) {
+      return k_elicit_design_prior<decltype(w)::value, decltype(c)::value, decltype(link)::value>;
+    }, 2 * (int64_t)(p->d + 1), prior);
+  } else {
+    launch_exact_session<DesignScore>(sp, s, grid, st, [](auto w, auto c, auto link) {
+      return k_elicit_design<decltype(w)::value, decltype(c)::value, decltype(link)::value>;
+    });
+  }
   return launch_status("k_elicit_design");
 }
-
-}  // extern "C"

@@ -24,7 +24,7 @@
 //   lds_doubles(d)             doubles of LDS of its own, between the triangle and the waves' winners
 //   THETA_OPS_EVERY_ROUND      are the candidate operands read by the score (else only by out_mean / out_var)?
 //   ROUND_END_BARRIER          does begin_round write LDS that solve_body reads (its contract: a barrier first)?
-//   Score(s, sm, own, prec)    sm: the block's LDS; own: its lds_doubles
+//   Score(s, sm, own, prec, pr)   sm: the block's LDS (behind the prior); own: its lds_doubles; pr: the staged prior or NULL
 //   begin_respondent(g)        before the barrier that publishes theta_e
 //   begin_round(q, rows, n)    before the barrier that publishes the round's operands; n: fold rows so far
 //   pool_row(q, p0, p, was, eok, e, n, uth)   the score of pool row p0 + p (NaN: no candidate); writes out_mean / out_var
@@ -108,22 +108,30 @@ __device__ __forceinline__ void put_moments(const ElicitFieldArgs& a, int q, int
 // (solve_body), the present one; BoundFold of vfm_elicit_bound.hip runs the Jaakkola-Jordan rounds of a 'class' model
 // (bound_body of vfm_foldin_bound_body.hpp) in its place.
 //   lds_doubles(d)             doubles of LDS of its own, between the triangle and the score's
-//   run<W, CPL, LINK>(s, f, rows, n, g, sm, Hm, own, precf, prec, loss, store)   the fold of respondent g over its n rows
-//                              from theta_e in pf; solve_body's contract: pf rewritten, store(pf) by every thread after
-//                              the barrier that publishes it, the loss by wave 0, no barrier at the end
+//   run<W, CPL, LINK, PRIOR>(s, f, rows, n, g, sm, Hm, own, precf, prec, loss, store, pr)   the fold of respondent g over
+//                              its n rows from theta_e in pf; solve_body's contract: pf rewritten, store(pf) by every
+//                              thread after the barrier that publishes it, the loss by wave 0, no barrier at the end;
+//                              pr: the staged prior of a PRIOR session (else NULL)
 struct SolveFold {
   __host__ __device__ static int64_t lds_doubles(int) { return 0; }
-  template <int W, int CPL, int LINK, class Args, class Rows, class Store>
+  template <int W, int CPL, int LINK, bool PRIOR, class Args, class Rows, class Store>
   __device__ __forceinline__ static void run(const Args& s, const FoldArgs& f, const Rows& rows, int64_t n, int64_t,
                                              double* sm, double* Hm, double*, float precf, double prec, float* loss,
-                                             Store&& store) {
-    solve_body<W, CPL, LINK>(f, s.ops64, s.cm64, rows, n, sm, Hm, precf, prec, loss, store);
+                                             Store&& store, const double* pr) {
+    solve_body<W, CPL, LINK, PRIOR>(f, s.ops64, s.cm64, rows, n, sm, Hm, precf, prec, loss, store, pr);
   }
 };
 
-template <class Score, int W, int CPL, int LINK, class Fold = SolveFold, class Args>
-__device__ __forceinline__ void exact_session(const Args& s) {
-  extern __shared__ double sm[];
+// PRIOR (include/vfm_elicit_prior.h): `prior` [2, d + 1] fp32 = mean | precision of the respondents' field is staged once
+// per workgroup, in fp64, in LDS in front of everything else (lds_doubles_prior's rule: k_foldin_solve's), so sm -- and
+// with it every LDS pointer of the session -- starts 2 (d + 1) doubles later; the fold of a round runs under it, the
+// score is constructed with it, and `reset` starts a respondent at mu = m, sigma = lam^-1/2 (prior_row_s).  Without
+// PRIOR nothing of this is compiled: sm is the block's LDS itself and the instance is the parent's.
+template <class Score, int W, int CPL, int LINK, class Fold = SolveFold, bool PRIOR = false, class Args>
+__device__ __forceinline__ void exact_session(const Args& s, const float* prior = nullptr) {
+  extern __shared__ double sm_all[];
+  double* sm = sm_all + (PRIOR ? 2 * (s.e.f.d + 1) : 0);
+  const double* pr = PRIOR ? sm_all : nullptr;
   constexpr int DP = W * CPL;
   constexpr bool SP = LINK == LINK_SOFTPLUS;
   const ElicitFieldArgs& a = s.e;
@@ -140,7 +148,11 @@ __device__ __forceinline__ void exact_session(const Args& s) {
   double* Hg = s.sl.slab ? s.sl.slab + (int64_t)blockIdx.x * s.sl.slab_elems : nullptr;
   const float precf = link_f<LINK>(f.scal[0]);
   const double prec = link_d<LINK>(f.scal[0]);
-  Score score(s, sm, own, prec);
+  Score score(s, sm, own, prec, pr);
+  if constexpr (PRIOR) {
+    stage_prior(prior, sm_all, d1);
+    __syncthreads();
+  }
 
   for (int64_t g = blockIdx.x; g < a.U; g += gridDim.x) {
     const RespondentRanges r = respondent_ranges(a, g);
@@ -155,6 +167,9 @@ __device__ __forceinline__ void exact_session(const Args& s) {
       if (eok && !f.reset) {
         m = c == 0 ? f.bias[e * 2] : f.entity[e * 2 * d + (c - 1)];
         sp = c == 0 ? f.bias[e * 2 + 1] : f.entity[e * 2 * d + d + (c - 1)];
+      } else if constexpr (PRIOR) {
+        m = (float)pr[c];
+        sp = prior_row_s<LINK>(pr[d1 + c]);
       }
       pf[c] = m;
       pf[d1 + c] = sp;
@@ -225,8 +240,8 @@ __device__ __forceinline__ void exact_session(const Args& s) {
       if (act) {
         ++n;
         const int m = solve_dim(n, d);
-        Fold::template run<W, CPL, LINK>(s, f, rows, n, g, sm, m <= s.sl.cap_dim ? Hl : Hg, fown, precf, prec,
-                                         a.out_loss + g * Q + q, [&](const float*) { put_theta(q); });
+        Fold::template run<W, CPL, LINK, PRIOR>(s, f, rows, n, g, sm, m <= s.sl.cap_dim ? Hl : Hg, fown, precf, prec,
+                                                a.out_loss + g * Q + q, [&](const float*) { put_theta(q); }, pr);
       } else {
         put_theta(q);
       }
@@ -340,16 +355,19 @@ int launch_exact_session_preps(const P* p, bool sp, const ElicitSolveArgs& s, hi
   return launch_solve_preps(sp, s.e.f, p->n_ops, p->op_x, (char*)s.e.f.ops, st);
 }
 
-// One launch of the session kernel.  kernel_of(IntC<W>, IntC<CPL>, IntC<LINK>): the unit's instance.
-template <class Score, class Fold = SolveFold, class Args, class KernelOf>
-void launch_exact_session(bool sp, const Args& s, unsigned grid, hipStream_t st, KernelOf&& kernel_of) {
+// One launch of the session kernel.  kernel_of(IntC<W>, IntC<CPL>, IntC<LINK>): the unit's instance; extra: what the
+// kernel takes behind s (the PRIOR instances: the prior, with prior_doubles = 2 (d + 1) more doubles of LDS in front).
+template <class Score, class Fold = SolveFold, class Args, class KernelOf, class... Extra>
+void launch_exact_session(bool sp, const Args& s, unsigned grid, hipStream_t st, KernelOf&& kernel_of,
+                          int64_t prior_doubles = 0, const Extra&... extra) {
   const int d = s.e.f.d;
   for_link(sp, [&](auto link) {
     for_shape(shape_of(d), [&](auto w, auto c) {
       constexpr int DP = decltype(w)::value * decltype(c)::value;
-      const size_t shm = (size_t)(lds_doubles(d, s.sl.cap_dim) + Fold::lds_doubles(d) + Score::lds_doubles(d)) * 8 +
-                         (size_t)session_tail_bytes(DP);
-      launch_lds(kernel_of(w, c, link), grid, shm, st, s);
+      const size_t shm =
+          (size_t)(prior_doubles + lds_doubles(d, s.sl.cap_dim) + Fold::lds_doubles(d) + Score::lds_doubles(d)) * 8 +
+          (size_t)session_tail_bytes(DP);
+      launch_lds(kernel_of(w, c, link), grid, shm, st, s, extra...);
     });
   });
 }

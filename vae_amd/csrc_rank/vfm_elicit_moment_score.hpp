@@ -11,7 +11,7 @@ struct MomentScore {
   __host__ __device__ static int64_t lds_doubles(int) { return 0; }
 
   const ElicitFieldArgs& a;
-  __device__ __forceinline__ MomentScore(const Args& s, double*, double*, double) : a(s.e) {}
+  __device__ __forceinline__ MomentScore(const Args& s, double*, double*, double, const double*) : a(s.e) {}
   __device__ __forceinline__ void begin_respondent(int64_t) const {}
   __device__ __forceinline__ void begin_round(int, const FieldSessionRows&, int64_t) const {}
 

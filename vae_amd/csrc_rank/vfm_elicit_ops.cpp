@@ -1,6 +1,7 @@
 // vfm_elicit_ops.cpp -- torch.ops.vfm_hip.{elicit, elicit_workspace_bytes, elicit_field, elicit_field_workspace_bytes,
-// elicit_solve, elicit_solve_workspace_bytes, elicit_bound, elicit_bound_workspace_bytes}: the TORCH_LIBRARY fragment over
-// include/vfm_elicit.h and the session of include/vfm_bound.h.  Like vfm_foldin_ops.cpp it only validates tensors, takes
+// elicit_solve, elicit_solve_workspace_bytes, elicit_bound, elicit_bound_workspace_bytes, elicit_solve_prior,
+// elicit_bound_prior}: the TORCH_LIBRARY fragment over include/vfm_elicit.h, the session of include/vfm_bound.h and their
+// forms under a field prior (include/vfm_elicit_prior.h).  Like vfm_foldin_ops.cpp it only validates tensors, takes
 // the current HIP stream of the tensors' device and forwards raw pointers; all arithmetic is in the HIP kernels.  Each
 // session op is the parts of vfm_ops_common.hpp in sequence (rows, tables, workspace, outputs, history) plus its own
 // options.
@@ -8,6 +9,7 @@
 
 #include "vfm_bound.h"
 #include "vfm_elicit.h"
+#include "vfm_elicit_prior.h"
 
 namespace {
 
@@ -122,8 +124,9 @@ int64_t elicit_solve_workspace_bytes(int64_t U, int64_t P, int64_t n_ops, int64_
   return b;
 }
 
-// the exact field-form session: elicit_field's tensors, the exact fold-in's options in place of Adam's
-void elicit_solve(const Tensor& entities, const Tensor& pool_ptr, const Tensor& pool_x, const Tensor& pool_y,
+// the exact field-form session: elicit_field's tensors, the exact fold-in's options in place of Adam's; prior: NULL, or
+// the respondents' field prior [2, d + 1] (elicit_solve_prior)
+void elicit_solve_call(const Tensor* prior, const Tensor& entities, const Tensor& pool_ptr, const Tensor& pool_x, const Tensor& pool_y,
                   const optional<Tensor>& hist_ptr, const optional<Tensor>& hist_x, const optional<Tensor>& hist_y,
                   const Tensor& op_x, const Tensor& pool_op, const optional<Tensor>& hist_op, Tensor entity, Tensor bias,
                   const Tensor& scalars, Tensor workspace, Tensor out_row, Tensor out_score, Tensor out_loss,
@@ -139,7 +142,31 @@ void elicit_solve(const Tensor& entities, const Tensor& pool_ptr, const Tensor& 
   fill_field_history(p, hist_ptr, hist_x, hist_y, hist_op);
   solve_options(p, field, key_col, strategy, flags, reset, write, lds_dim, kl_weight, seed);
   c10::hip::HIPGuard guard(entities.get_device());
-  check(vfm_elicit_solve_f32(&p, stream_of(entities)), "vfm_elicit_solve_f32");
+  if (prior) check(vfm_elicit_solve_prior_f32(&p, prior_of(*prior, p.d), stream_of(entities)), "vfm_elicit_solve_prior_f32");
+  else check(vfm_elicit_solve_f32(&p, stream_of(entities)), "vfm_elicit_solve_f32");
+}
+
+#define VFM_SESSION_TENSORS                                                                                              \
+  const Tensor &entities, const Tensor &pool_ptr, const Tensor &pool_x, const Tensor &pool_y,                            \
+      const optional<Tensor>&hist_ptr, const optional<Tensor>&hist_x, const optional<Tensor>&hist_y, const Tensor &op_x, \
+      const Tensor &pool_op, const optional<Tensor>&hist_op, Tensor entity, Tensor bias, const Tensor &scalars,          \
+      Tensor workspace, Tensor out_row, Tensor out_score, Tensor out_loss, const optional<Tensor>&out_theta,             \
+      const optional<Tensor>&out_mean, const optional<Tensor>&out_var
+#define VFM_SESSION_TENSOR_NAMES                                                                                         \
+  entities, pool_ptr, pool_x, pool_y, hist_ptr, hist_x, hist_y, op_x, pool_op, hist_op, entity, bias, scalars, workspace, \
+      out_row, out_score, out_loss, out_theta, out_mean, out_var
+
+void elicit_solve(VFM_SESSION_TENSORS, int64_t field, int64_t key_col, int64_t n_rounds, int64_t strategy, int64_t flags,
+                  int64_t reset, int64_t write, int64_t lds_dim, double kl_weight, int64_t seed) {
+  elicit_solve_call(nullptr, VFM_SESSION_TENSOR_NAMES, field, key_col, n_rounds, strategy, flags, reset, write, lds_dim,
+                    kl_weight, seed);
+}
+
+void elicit_solve_prior(VFM_SESSION_TENSORS, const Tensor& prior, int64_t field, int64_t key_col, int64_t n_rounds,
+                        int64_t strategy, int64_t flags, int64_t reset, int64_t write, int64_t lds_dim, double kl_weight,
+                        int64_t seed) {
+  elicit_solve_call(&prior, VFM_SESSION_TENSOR_NAMES, field, key_col, n_rounds, strategy, flags, reset, write, lds_dim,
+                    kl_weight, seed);
 }
 
 int64_t elicit_bound_workspace_bytes(int64_t U, int64_t P, int64_t H, int64_t n_ops, int64_t d, int64_t n_rounds,
@@ -149,8 +176,9 @@ int64_t elicit_bound_workspace_bytes(int64_t U, int64_t P, int64_t H, int64_t n_
   return b;
 }
 
-// the bound field-form session ('class' models): elicit_solve's tensors and options, and the rounds of the bound per fold
-void elicit_bound(const Tensor& entities, const Tensor& pool_ptr, const Tensor& pool_x, const Tensor& pool_y,
+// the bound field-form session ('class' models): elicit_solve's tensors and options, and the rounds of the bound per
+// fold; prior: as elicit_solve_call's (elicit_bound_prior)
+void elicit_bound_call(const Tensor* prior, const Tensor& entities, const Tensor& pool_ptr, const Tensor& pool_x, const Tensor& pool_y,
                   const optional<Tensor>& hist_ptr, const optional<Tensor>& hist_x, const optional<Tensor>& hist_y,
                   const Tensor& op_x, const Tensor& pool_op, const optional<Tensor>& hist_op, Tensor entity, Tensor bias,
                   const Tensor& scalars, Tensor workspace, Tensor out_row, Tensor out_score, Tensor out_loss,
@@ -168,7 +196,21 @@ void elicit_bound(const Tensor& entities, const Tensor& pool_ptr, const Tensor& 
   TORCH_CHECK(n_iters >= 1 && n_iters <= INT32_MAX, "n_iters must be >= 1");
   p.n_iters = (int32_t)n_iters;
   c10::hip::HIPGuard guard(entities.get_device());
-  check(vfm_elicit_bound_f32(&p, stream_of(entities)), "vfm_elicit_bound_f32");
+  if (prior) check(vfm_elicit_bound_prior_f32(&p, prior_of(*prior, p.d), stream_of(entities)), "vfm_elicit_bound_prior_f32");
+  else check(vfm_elicit_bound_f32(&p, stream_of(entities)), "vfm_elicit_bound_f32");
+}
+
+void elicit_bound(VFM_SESSION_TENSORS, int64_t field, int64_t key_col, int64_t n_rounds, int64_t strategy, int64_t flags,
+                  int64_t reset, int64_t write, int64_t lds_dim, double kl_weight, int64_t seed, int64_t n_iters) {
+  elicit_bound_call(nullptr, VFM_SESSION_TENSOR_NAMES, field, key_col, n_rounds, strategy, flags, reset, write, lds_dim,
+                    kl_weight, seed, n_iters);
+}
+
+void elicit_bound_prior(VFM_SESSION_TENSORS, const Tensor& prior, int64_t field, int64_t key_col, int64_t n_rounds,
+                        int64_t strategy, int64_t flags, int64_t reset, int64_t write, int64_t lds_dim, double kl_weight,
+                        int64_t seed, int64_t n_iters) {
+  elicit_bound_call(&prior, VFM_SESSION_TENSOR_NAMES, field, key_col, n_rounds, strategy, flags, reset, write, lds_dim,
+                    kl_weight, seed, n_iters);
 }
 
 }  // namespace
@@ -206,4 +248,18 @@ TORCH_LIBRARY_FRAGMENT(vfm_hip, m) {
         "int n_rounds, int strategy, int flags, int reset, int write, int lds_dim, float kl_weight, int seed, "
         "int n_iters) -> ()",
         &elicit_bound);
+  m.def("elicit_solve_prior(Tensor entities, Tensor pool_ptr, Tensor pool_x, Tensor pool_y, Tensor? hist_ptr, "
+        "Tensor? hist_x, Tensor? hist_y, Tensor op_x, Tensor pool_op, Tensor? hist_op, Tensor(a!) entity_params, "
+        "Tensor(b!) bias_params, Tensor scalars, Tensor(c!) workspace, Tensor(d!) out_row, Tensor(e!) out_score, "
+        "Tensor(f!) out_loss, Tensor(g!)? out_theta, Tensor(h!)? out_mean, Tensor(i!)? out_var, Tensor prior, int field, "
+        "int key_col, int n_rounds, int strategy, int flags, int reset, int write, int lds_dim, float kl_weight, "
+        "int seed) -> ()",
+        &elicit_solve_prior);
+  m.def("elicit_bound_prior(Tensor entities, Tensor pool_ptr, Tensor pool_x, Tensor pool_y, Tensor? hist_ptr, "
+        "Tensor? hist_x, Tensor? hist_y, Tensor op_x, Tensor pool_op, Tensor? hist_op, Tensor(a!) entity_params, "
+        "Tensor(b!) bias_params, Tensor scalars, Tensor(c!) workspace, Tensor(d!) out_row, Tensor(e!) out_score, "
+        "Tensor(f!) out_loss, Tensor(g!)? out_theta, Tensor(h!)? out_mean, Tensor(i!)? out_var, Tensor prior, int field, "
+        "int key_col, int n_rounds, int strategy, int flags, int reset, int write, int lds_dim, float kl_weight, "
+        "int seed, int n_iters) -> ()",
+        &elicit_bound_prior);
 }

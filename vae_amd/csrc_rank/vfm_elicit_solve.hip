@@ -6,6 +6,10 @@
 // whole by its predictive moments at theta_e (field_chain_moments / score_of / philox_uniform: vfm_elicit_field.hip's
 // scores, bit for bit), whose candidate operands are therefore refreshed every round.  The score keeps nothing in LDS
 // and writes none of solve_body's, so a round ends without a barrier.
+//
+// vfm_elicit_solve_prior_f32 (include/vfm_elicit_prior.h) runs k_elicit_solve_prior, the PRIOR = true instantiation of the
+// same session loop: the respondents' field prior staged in LDS in front, one more pointer among the kernel's
+// arguments; k_elicit_solve is the instantiation without it, unchanged.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -14,6 +18,7 @@
 
 #include "vfm_args.hpp"
 #include "vfm_elicit.h"
+#include "vfm_elicit_prior.h"
 #include "vfm_launch.hpp"            // launch_status
 #include "vfm_rank_tile.hpp"         // score_of, philox_uniform, link_of
 #include "vfm_field_ctx.hpp"         // ctx_valid, field_chain_moments
@@ -34,8 +39,15 @@ __global__ __launch_bounds__(FB) void k_elicit_solve(const ElicitSolveArgs s) {
   exact_session<MomentScore, W, CPL, LINK>(s);
 }
 
+template <int W, int CPL, int LINK>
+__global__ __launch_bounds__(FB) void k_elicit_solve_prior(const ElicitSolveArgs s, const float* __restrict__ prior) {
+  exact_session<MomentScore, W, CPL, LINK, SolveFold, true>(s, prior);
+}
+
 }  // namespace
 }  // namespace vfm
+
+static int elicit_solve_call(const vfm_elicit_solve_t* p, const float* prior, void* stream);
 
 extern "C" {
 
@@ -43,7 +55,20 @@ int64_t vfm_elicit_solve_workspace_bytes(int64_t U, int64_t P, int64_t n_ops, in
   return vfm::exact_session_workspace_bytes(U, P, n_ops, d, lds_dim);
 }
 
-int vfm_elicit_solve_f32(const vfm_elicit_solve_t* p, void* stream) {
+int64_t vfm_elicit_solve_prior_workspace_bytes(int64_t U, int64_t P, int64_t n_ops, int32_t d, int32_t lds_dim) {
+  return vfm_elicit_solve_workspace_bytes(U, P, n_ops, d, lds_dim);    // (the prior lives in LDS, not in the workspace)
+}
+
+int vfm_elicit_solve_f32(const vfm_elicit_solve_t* p, void* stream) { return elicit_solve_call(p, nullptr, stream); }
+
+int vfm_elicit_solve_prior_f32(const vfm_elicit_solve_t* p, const float* prior, void* stream) {
+  return elicit_solve_call(p, prior, stream);
+}
+
+}  // extern "C"
+
+// both entry points: prior == NULL is vfm_elicit_solve_f32
+static int elicit_solve_call(const vfm_elicit_solve_t* p, const float* prior, void* stream) {
   using namespace vfm;
   if (int rc = check_session_struct(
           p, "vfm_elicit_solve_f32: NULL argument struct",
@@ -68,10 +93,14 @@ int vfm_elicit_solve_f32(const vfm_elicit_solve_t* p, void* stream) {
   const unsigned grid = exact_session_args(p, true, p->seed, s);
   s.e.strat = p->strategy; s.e.key_col = p->key_col;
   if (int rc = launch_exact_session_preps(p, sp, s, st)) return rc;
-  launch_exact_session<MomentScore>(sp, s, grid, st, [](auto w, auto c, auto link) {
-    return k_elicit_solve<decltype(w)::value, decltype(c)::value, decltype(link)::value>;
-  });
+  if (prior) {
+    launch_exact_session<MomentScore>(sp, s, grid, st, [](auto w, auto c, auto link) {
+      return k_elicit_solve_prior<decltype(w)::value, decltype(c)::value, decltype(link)::value>;
+    }, 2 * (int64_t)(p->d + 1), prior);
+  } else {
+    launch_exact_session<MomentScore>(sp, s, grid, st, [](auto w, auto c, auto link) {
+      return k_elicit_solve<decltype(w)::value, decltype(c)::value, decltype(link)::value>;
+    });
+  }
   return launch_status("k_elicit_solve");
 }
-
-}  // extern "C"

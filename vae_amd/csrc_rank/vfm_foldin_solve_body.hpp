@@ -123,6 +123,14 @@ __device__ __forceinline__ void stage_prior(const float* __restrict__ prior, dou
   for (int c = threadIdx.x; c < 2 * d1; c += FB) pr[c] = (double)prior[c];
 }
 
+// the scale parameter of the prior's own sigma = lam^-1/2, to fp32: what a session's `reset` starts a respondent at under
+// a prior (vfm_elicit_exact_body.hpp).  At lam = 1 the bits of prior_s<LINK>().
+template <int LINK>
+__device__ __forceinline__ float prior_row_s(double lam) {
+  const double sg = sqrt(1.0 / lam);
+  return (float)(LINK == LINK_ABS ? sg : log(expm1(sg)));
+}
+
 // KL(N(mu, sg^2) || N(m, 1 / lam)) = kl_std_normal(sqrt(lam) (mu - m), sqrt(lam) sg); at m = 0, lam = 1 its bits
 __device__ __forceinline__ float kl_prior_normal(float mu, float sg, float m, float sl) {
   return kl_std_normal(sl * (mu - m), sl * sg);
@@ -427,11 +435,11 @@ void fill_solve_args(S& s, const P* p, int lik, int n_iters, int reset, int mode
 
 // a kernel of FB threads with shm bytes of dynamic LDS (more than 64 KiB: state the size first; a runtime that needs no
 // opt-in ignores it)
-template <class K, class S>
-void launch_lds(K k, unsigned grid, size_t shm, hipStream_t st, const S& s) {
+template <class K, class... S>
+void launch_lds(K k, unsigned grid, size_t shm, hipStream_t st, const S&... s) {
   (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
   (void)hipGetLastError();
-  hipLaunchKernelGGL(k, dim3(grid), dim3(FB), shm, st, s);
+  hipLaunchKernelGGL(k, dim3(grid), dim3(FB), shm, st, s...);
 }
 
 // ---- the two split units: a slab of part_doubles(d) per chunk [triangle tri(d + 1) | SA [d + 1] | SB [d + 1] |

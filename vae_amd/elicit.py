@@ -12,6 +12,12 @@ form with each round's Adam fit replaced by the exact fold-in's closed-form opti
 `run_field_bound` the same for 'class' models with the bound fold-in's rounds (include/vfm_bound.h: vfm_elicit_bound_f32).
 The field forms, design.run_field_design among them, are their argument checks and one call of `run_field_session`
 over the lists of `field_lists`; SESSION_KINDS says which of them the curves run under which strategy names.
+
+The exact, bound and design sessions take `priors` (a sweep.GroupPriors, what fit_exact / fit_bound learn with
+learn_priors=True): every round's fold then runs under the respondents' field prior, `reset` starts a respondent at it
+(foldin.prior_theta) and the design score is taken under it (include/vfm_elicit_prior.h; DESIGN.md §4 "Sessions under
+learnt priors").  priors=None is the parent op itself.  The Adam sessions (`run`, `run_field`) keep N(0, 1) and take
+no priors.
 """
 from __future__ import annotations
 
@@ -19,7 +25,7 @@ import math
 
 import torch
 
-from . import _lib, foldin, ops
+from . import _lib, foldin, ops, sweep
 from .rank import _seed64, strategy_code
 
 MAX_ROUNDS = _lib.ELICIT_MAX_ROUNDS
@@ -204,12 +210,16 @@ def link_flags(model):
 
 
 def run_field_session(model, x, y, hx, hy, field, n_questions, workspace, op, options, write, return_moments,
-                      return_theta, targets=NO_TARGETS):
+                      return_theta, targets=NO_TARGETS, priors=None):
     """One launch of a field-form session over checked arguments, whichever form: the lists, the outputs, the workspace,
     the call and the result in the caller's pool order.  workspace(o, U, P, H, n_ops, d): the form's size call on
     o = torch.ops.vfm_hip; op: the session op's name there; options: what follows out_var in its schema.  targets (as
-    field_lists'): given or None for the one form that has tgt_ptr and tgt_op, which sit where its schema has them."""
+    field_lists'): given or None for the one form that has tgt_ptr and tgt_op, which sit where its schema has them.
+    priors (checked by the caller: sweep.check_priors): None runs `op`; a GroupPriors runs `op`_prior, whose schema has
+    the field's prior row [2, d + 1] between out_var and the options."""
     ops._need_cuda(model._flat, "the model's parameters")
+    if priors is not None:
+        op, options = op + "_prior", (priors.row(int(field)).to(model.device), *options)
     dev, d, Q = model.device, model.d, int(n_questions)
     L = field_lists(x, y, hx, hy, field, targets)
     ents, px = L["ents"], L["px"]
@@ -289,17 +299,19 @@ def check_args_field_exact(model, pool, y_pool, n_questions, field, strategy, hi
 
 def run_field_exact(model, pool, y_pool, n_questions, field=0, strategy="variance", history=None, seed=0,
                     kl_weight=1.0, reset=False, write=False, return_moments=False, return_theta=False, key_field=None,
-                    lds_dim=-1):
+                    lds_dim=-1, priors=None):
     """The exact sessions of every entity of column `field` of the pool (VFM.elicit_field_exact documents the arguments
-    and the result): run_field's lists and operands, and one call of torch.ops.vfm_hip.elicit_solve."""
+    and the result): run_field's lists and operands, and one call of torch.ops.vfm_hip.elicit_solve (with priors:
+    elicit_solve_prior)."""
     x, y, hx, hy, code, field, kf = check_args_field_exact(model, pool, y_pool, n_questions, field, strategy, history,
                                                            kl_weight, key_field)
+    sweep.check_priors(model, priors)
     foldin._check_lds_dim(lds_dim)
     return run_field_session(
         model, x, y, hx, hy, field, n_questions,
         lambda o, U, P, H, n_ops, d: o.elicit_solve_workspace_bytes(U, P, n_ops, d, int(lds_dim)), "elicit_solve",
         (field, kf, int(n_questions), code, link_flags(model), int(bool(reset)), int(bool(write)), int(lds_dim),
-         float(kl_weight), _seed64(seed)), write, return_moments, return_theta)
+         float(kl_weight), _seed64(seed)), write, return_moments, return_theta, priors=priors)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -332,18 +344,20 @@ def check_args_field_bound(model, pool, y_pool, n_questions, field, strategy, hi
 
 def run_field_bound(model, pool, y_pool, n_questions, field=0, strategy="variance", history=None, seed=0, kl_weight=1.0,
                     n_iters=8, reset=False, write=False, return_moments=False, return_theta=False, key_field=None,
-                    lds_dim=-1):
+                    lds_dim=-1, priors=None):
     """The bound sessions of every entity of column `field` of the pool (VFM.elicit_field_bound documents the arguments
-    and the result): run_field's lists and operands, and one call of torch.ops.vfm_hip.elicit_bound."""
+    and the result): run_field's lists and operands, and one call of torch.ops.vfm_hip.elicit_bound (with priors:
+    elicit_bound_prior)."""
     x, y, hx, hy, code, field, kf = check_args_field_bound(model, pool, y_pool, n_questions, field, strategy, history,
                                                            kl_weight, n_iters, key_field)
+    sweep.check_priors(model, priors)
     foldin._check_lds_dim(lds_dim)
     Q = int(n_questions)
     return run_field_session(
         model, x, y, hx, hy, field, Q,
         lambda o, U, P, H, n_ops, d: o.elicit_bound_workspace_bytes(U, P, H, n_ops, d, Q, int(lds_dim)), "elicit_bound",
         (field, kf, Q, code, link_flags(model), int(bool(reset)), int(bool(write)), int(lds_dim), float(kl_weight),
-         _seed64(seed), int(n_iters)), write, return_moments, return_theta)
+         _seed64(seed), int(n_iters)), write, return_moments, return_theta, priors=priors)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -533,10 +547,8 @@ def ranking_curve(model, pool, y_pool, n_questions, field, X_test, y_test, rank_
         r = run_s(model, pool, y_pool, n_questions, field, strategy=s, write=False, return_theta=True, **kw_s)
         ents, Q = r["entities"], int(n_questions)
         U = ents.numel()
-        if session_kw.get("reset", False):
-            theta0 = torch.zeros(U, 2 * d + 2, dtype=torch.float32, device=dev)
-            theta0[:, d:2 * d] = foldin.prior_s(model.link)
-            theta0[:, 2 * d + 1] = foldin.prior_s(model.link)
+        if session_kw.get("reset", False):     # (the row the session scored round 0 from: the prior's)
+            theta0 = foldin.prior_theta(model, session_kw.get("priors"), field).to(dev).expand(U, 2 * d + 2)
         else:
             model._fresh_params()
             ent, bia, _ = model._views(model._flat)

@@ -25,6 +25,23 @@ def prior_s(link: str) -> float:
     return 1.0 if link == "abs" else math.log(math.e - 1.0)
 
 
+def prior_theta(model, priors=None, field=0):
+    """[2d + 2] fp32 = [mu | s | mu_w | s_w]: the row a session's reset=True starts a respondent of column `field` at,
+    with the kernels' bits (prior_row_s of csrc_rank/vfm_foldin_solve_body.hpp).  priors None: (0, prior_s).  A
+    sweep.GroupPriors: mu_c = mean_c, sigma_c = sqrt(1 / prec_c) in fp64 from the fp32 precision, stored as (float)
+    sigma_c for the |.| link and (float) log(expm1(sigma_c)) for softplus.  A function of the prior and the link alone."""
+    d = model.d
+    if priors is None:
+        out = torch.zeros(2 * d + 2, dtype=torch.float32)
+        out[d:2 * d] = prior_s(model.link)
+        out[2 * d + 1] = prior_s(model.link)
+        return out
+    row = priors.row(int(field)).detach().cpu()
+    sg = torch.sqrt(1.0 / row[1].double())
+    s = (sg if model.link == "abs" else torch.log(torch.expm1(sg))).float()
+    return torch.cat([row[0, 1:], s[1:], row[0, :1], s[:1]]).contiguous()
+
+
 def field_range(model, field: int):
     lo = sum(model.field_sizes[:field])
     return lo, lo + model.field_sizes[field]

@@ -1255,7 +1255,8 @@ class VFM(nn.Module):
         `exclude`, of the history and of the pool rows asked before round q (a recommender does not recommend what it
         has just asked about), matched on match_fields as rank_field matches them.  All (Q + 1) x contexts queries of a
         strategy go through ONE rank_heldout_field_posterior call.  session_kw: the session's other options (history,
-        n_steps, lr, objective, n_samples, seed, kl_weight, reset, key_field).  With exact=True the name "design" is a
+        n_steps, lr, objective, n_samples, seed, kl_weight, reset, key_field; with exact=True or bound=True also priors,
+        and round 0 under reset=True is then ranked at foldin.prior_theta).  With exact=True the name "design" is a
         strategy too: elicit_field_design, with `targets` taken from session_kw.  bound=True runs elicit_field_bound
         sessions ('class' models; session_kw then also takes n_iters, 8 being its untuned starting value; "design" is
         refused); together with exact=True it is a ValueError.
@@ -1426,8 +1427,10 @@ class VFM(nn.Module):
         collapse onto one point would ask for an infinite one); KL is unimodal in 1 / prec, so the clamped value is
         the constrained minimiser and J still does not rise.  "clamped" in the result counts, per field, the
         (sweep, coordinate) pairs at which a clamp bound.  The global bias keeps N(0, 1).  learn_priors=False with
-        priors given leaves them untouched.  fit_bound and the bound fold-in take the same priors; sessions (the bound
-        session included), ranking and the Adam trainers do not read priors."""
+        priors given leaves them untouched.  fit_bound and the bound fold-in take the same priors, and so do the
+        exact, bound and design sessions and their curves (elicit_field_exact, elicit_field_bound, elicit_field_design,
+        design_scores_field: priors=); the Adam sessions (elicit, elicit_field), fold_in, ranking and the Adam trainers
+        keep N(0, 1) and do not read priors."""
         from . import sweep
         return sweep.fit(self, X, y, n_sweeps, kl_weight, fields, update_scalars, split_rows, chunk_rows, on_step, tol,
                          priors=priors, learn_priors=learn_priors, learn_mean=learn_mean, prec_min=prec_min,
@@ -1587,7 +1590,8 @@ class VFM(nn.Module):
     @torch.no_grad()
     def elicit_field_exact(self, pool, y_pool, n_questions: int, field: int = 0, strategy: str = "variance",
                            history=None, seed: int = 0, kl_weight: float = 1.0, reset: bool = False, write: bool = False,
-                           return_moments: bool = False, return_theta: bool = False, key_field: Optional[int] = None):
+                           return_moments: bool = False, return_theta: bool = False, key_field: Optional[int] = None,
+                           priors=None):
         """elicit_field with each round's Adam fit replaced by the exact posterior: n_questions rounds of
         select_next_questions_field(n=1) followed by fold_in_exact(field=field) of the answering respondent, bitwise
         what that loop computes, for every respondent in one launch (include/vfm_elicit.h: vfm_elicit_solve_f32;
@@ -1598,10 +1602,17 @@ class VFM(nn.Module):
         'reg' models only, kl_weight > 0, F >= 2 (else ValueError, before anything needs a GPU).  pool, y_pool, history,
         field, strategy, seed, key_field, write, return_moments, return_theta: as elicit_field.  reset=True scores round
         0 from the prior instead of the respondents' rows; the optimum itself does not depend on the current rows.
-        Returns elicit_field's dict; loss [U, Q] is fold_in_exact's loss after each round."""
+        Returns elicit_field's dict; loss [U, Q] is fold_in_exact's loss after each round.
+
+        priors (a sweep.GroupPriors, e.g. fit_exact(learn_priors=True)["priors"]): the session of a model trained under
+        learnt priors -- every round is fold_in_exact(priors=priors), and reset=True starts the respondent at the
+        field's prior itself, mu = mean, sigma = prec^-1/2 (foldin.prior_theta), which is where a cold-start
+        respondent's first questions are chosen from (include/vfm_elicit_prior.h; DESIGN.md §4 "Sessions under learnt
+        priors").  At (0, 1) everything returned and written is priors=None's, bit for bit; priors=None is that path
+        itself."""
         from . import elicit
         return elicit.run_field_exact(self, pool, y_pool, n_questions, field, strategy, history, seed, kl_weight, reset,
-                                      write, return_moments, return_theta, key_field)
+                                      write, return_moments, return_theta, key_field, priors=priors)
 
     @torch.no_grad()
     def elicitation_curve_field_exact(self, pool, y_pool, n_questions: int, field: int = 0,
@@ -1618,7 +1629,7 @@ class VFM(nn.Module):
     def elicit_field_bound(self, pool, y_pool, n_questions: int, field: int = 0, strategy: str = "variance",
                            history=None, seed: int = 0, kl_weight: float = 1.0, n_iters: int = 8, reset: bool = False,
                            write: bool = False, return_moments: bool = False, return_theta: bool = False,
-                           key_field: Optional[int] = None):
+                           key_field: Optional[int] = None, priors=None):
         """elicit_field for a 'class' model without Adam: n_questions rounds of select_next_questions_field(n=1)
         followed by fold_in_bound(field=field, n_iters=n_iters, reset=False) of the answering respondent, bitwise what
         that loop computes, for every respondent in one launch (include/vfm_bound.h: vfm_elicit_bound_f32; DESIGN.md §4
@@ -1632,10 +1643,15 @@ class VFM(nn.Module):
         apply; "mean" (closest to p = 0.5) is the natural one here; "design" is refused: the scales of the optimum
         depend on the answers through xi.  reset=True starts round 0 (its scores and its fold) from the prior row
         (mu = 0, s = link^-1(1)).  pool, y_pool, history, field, seed, key_field, write, return_moments, return_theta: as
-        elicit_field.  Returns elicit_field's dict; loss [U, Q] is B_e, fold_in_bound's loss, after each round."""
+        elicit_field.  Returns elicit_field's dict; loss [U, Q] is B_e, fold_in_bound's loss, after each round.
+
+        priors (a sweep.GroupPriors, e.g. fit_bound(learn_priors=True)["priors"]): every round is
+        fold_in_bound(reset=False, priors=priors), and reset=True starts round 0 (its scores and its fold) at the
+        field's prior, mu = mean, sigma = prec^-1/2 (foldin.prior_theta; include/vfm_elicit_prior.h).  At (0, 1)
+        everything is priors=None's, bit for bit; priors=None is that path itself."""
         from . import elicit
         return elicit.run_field_bound(self, pool, y_pool, n_questions, field, strategy, history, seed, kl_weight, n_iters,
-                                      reset, write, return_moments, return_theta, key_field)
+                                      reset, write, return_moments, return_theta, key_field, priors=priors)
 
     @torch.no_grad()
     def elicitation_curve_field_bound(self, pool, y_pool, n_questions: int, field: int = 0,
@@ -1649,7 +1665,7 @@ class VFM(nn.Module):
 
     # ------------------------------------------------------------------ target-aware elicitation (vae_amd/design.py)
     @torch.no_grad()
-    def design_scores_field(self, pool, field: int, targets=None, history=None, kl_weight: float = 1.0):
+    def design_scores_field(self, pool, field: int, targets=None, history=None, kl_weight: float = 1.0, priors=None):
         """How much would each question reduce the uncertainty of the predictions that matter?  [P] fp32 in the caller's
         pool order: per pool row q of respondent e (column `field`) the drop of the mean, over e's target contexts, of
         the part of Var pred carried by e's scales if q were asked next (include/vfm_design.h; DESIGN.md §4
@@ -1662,33 +1678,38 @@ class VFM(nn.Module):
         full rows; history: (X [H, F], y [H]) as in the sessions (y is not read), rows of the pool's respondents; targets: None -- each
         respondent's own pool rows, in pool order -- or [R, F] rows whose column `field` names the respondent (grouped
         per respondent in the given order; a respondent without any gets an empty list: W = 0, and only the bias term
-        is left; rows of entities not in the pool raise)."""
+        is left; rows of entities not in the pool raise).
+
+        priors (a sweep.GroupPriors): the scales are those of fold_in_exact(priors=priors)'s optimum,
+        v_k(S) = kl_weight / (kl_weight prec_k + prec S) with prec_k the field's prior precision of coordinate k (the
+        weight's for the bias term); the prior's means are not read.  At (0, 1) the scores are priors=None's bits."""
         from . import design
-        return design.scores(self, pool, field, targets, history, kl_weight)
+        return design.scores(self, pool, field, targets, history, kl_weight, priors)
 
     @torch.no_grad()
     def select_next_questions_design_field(self, pool, field: int, n: int = 1, targets=None, history=None,
-                                           kl_weight: float = 1.0):
+                                           kl_weight: float = 1.0, priors=None):
         """select_next_questions_field by the design score: per entity of column `field` the indices of its n best
-        rows by design_scores_field (same arguments).  Ties go to the lower row; a NaN score is never chosen.  Returns
+        rows by design_scores_field (same arguments, priors among them).  Ties go to the lower row; a NaN score is never chosen.  Returns
         (entities [U'] ascending, rows [U', n] int64, -1 padded)."""
         from . import design
-        return design.select_next_questions(self, pool, field, n, targets, history, kl_weight)
+        return design.select_next_questions(self, pool, field, n, targets, history, kl_weight, priors)
 
     @torch.no_grad()
     def elicit_field_design(self, pool, y_pool, n_questions: int, field: int = 0, targets=None, history=None,
                             kl_weight: float = 1.0, reset: bool = False, write: bool = False,
-                            return_moments: bool = False, return_theta: bool = False, lds_dim: int = -1):
+                            return_moments: bool = False, return_theta: bool = False, lds_dim: int = -1, priors=None):
         """elicit_field_exact with the question chosen for what the answers are used for: n_questions rounds of
         select_next_questions_design_field(n=1, history = history + the rows asked so far) followed by
         fold_in_exact(field=field) of the answering respondent, bitwise what that loop computes, for every respondent
         in one launch (include/vfm_design.h: vfm_design_elicit_f32).  targets: as design_scores_field, fixed over the
         session (None: the respondent's whole pool, asked or not).  pool, y_pool, history, kl_weight, reset (round 0's
         moments only: the score does not read the current row), write, return_moments, return_theta: as
-        elicit_field_exact, and so is the result; score [U, Q] is the asked row's design score."""
+        elicit_field_exact, and so is the result; score [U, Q] is the asked row's design score.  priors: as
+        elicit_field_exact's for the folds and the reset row, as design_scores_field's for the score."""
         from . import design
         return design.run_field_design(self, pool, y_pool, n_questions, field, targets, history, kl_weight, reset, write,
-                                       return_moments, return_theta, lds_dim)
+                                       return_moments, return_theta, lds_dim, priors=priors)
 
     @torch.no_grad()
     def evaluate(self, X_test, y_test):
