@@ -151,6 +151,28 @@ _FOLD_PROTOTYPES = (
 )
 
 
+# ---- the implicit-feedback solves (include/vfm_implicit.h, the hot path of VFM.fit_implicit): a field's base block and
+# the solve of every (entity, partner) pair that starts from it
+IMPLICIT_EXPORTS = ("vfm_implicit_base_doubles", "vfm_implicit_base_workspace_bytes", "vfm_implicit_base_f32",
+                    "vfm_implicit_solve_workspace_bytes", "vfm_foldin_solve_implicit_f32")
+
+
+class ImplicitBase(_Strict, C.Structure):
+    """`vfm_implicit_base_t` (tests/test_fit_implicit_cpu.py checks the layout against gcc's)."""
+    _fields_ = list(_fields(C.c_int64, "T", "lo", "n", "chunk_rows") + _fields(C.c_int32, "d", "flags")
+                    + _fields(C.c_void_p, "entity_params", "bias_params", "scalars", "out_base", "workspace")
+                    + (("workspace_bytes", C.c_int64),))
+
+
+class ImplicitSolve(_Strict, C.Structure):
+    """`vfm_implicit_solve_t` (tests/test_fit_implicit_cpu.py checks the layout against gcc's)."""
+    _fields_ = list(_fields(C.c_int64, "E", "R", "T", "n_chunks", "lo", "n") + _fields(C.c_int32, "d", "flags", "lds_dim")
+                    + _fields(C.c_float, "kl_weight", "w0", "w1")
+                    + _fields(C.c_void_p, "entities", "row_ptr", "chunk_ptr", "chunks", "y", "partner", "base",
+                              "entity_params", "bias_params", "scalars", "out_loss", "workspace")
+                    + (("workspace_bytes", C.c_int64),))
+
+
 # the bound field-form session (vfm_elicit_bound_f32) is declared in vfm_bound.h too
 ELICIT_BOUND_EXPORTS = ("vfm_elicit_bound_f32", "vfm_elicit_bound_workspace_bytes")
 
@@ -230,7 +252,7 @@ _ELICIT_PRIOR_PROTOTYPES = (
 
 
 for _c in (Problem, Index, Pipe, Elicit, ElicitField, ElicitSolve, ElicitBound, ElicitDesign, FoldinSolve, FoldinSplit,
-           FoldinBound, FoldinBoundSplit):
+           FoldinBound, FoldinBoundSplit, ImplicitBase, ImplicitSolve):
     _c._names = frozenset(n for n, _ in _c._fields_)
 
 
@@ -322,6 +344,15 @@ def load():
         getattr(lib, entry).restype = C.c_int
         getattr(lib, size).argtypes = size_args
         getattr(lib, size).restype = i64
+    lib.vfm_implicit_base_doubles.argtypes = [i32]
+    lib.vfm_implicit_base_workspace_bytes.argtypes = [i64, i64, i32]
+    lib.vfm_implicit_solve_workspace_bytes.argtypes = [i64, i64, i32, i32]
+    for name in ("vfm_implicit_base_doubles", "vfm_implicit_base_workspace_bytes", "vfm_implicit_solve_workspace_bytes"):
+        getattr(lib, name).restype = i64
+    lib.vfm_implicit_base_f32.argtypes = [C.POINTER(ImplicitBase), vp]
+    lib.vfm_implicit_base_f32.restype = C.c_int
+    lib.vfm_foldin_solve_implicit_f32.argtypes = [C.POINTER(ImplicitSolve), vp]
+    lib.vfm_foldin_solve_implicit_f32.restype = C.c_int
     lib.vfm_elicit_bound_f32.argtypes = [C.POINTER(ElicitBound), vp]
     lib.vfm_elicit_bound_f32.restype = C.c_int
     lib.vfm_elicit_bound_workspace_bytes.argtypes = [i64, i64, i64, i64, i32, i32, i32]

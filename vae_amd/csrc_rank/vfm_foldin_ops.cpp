@@ -1,6 +1,7 @@
 // vfm_foldin_ops.cpp -- the fold-in family of torch.ops.vfm_hip: foldin (include/vfm_foldin.h), foldin_solve and
 // foldin_solve_split (vfm_foldin.h, vfm_sweep.h), their *_prior forms (vfm_prior.h), foldin_bound and foldin_bound_split
-// (vfm_bound.h, vfm_bound_sweep.h), their *_prior forms (vfm_bound_prior.h), and the five *_workspace_bytes.  Like vfm_rank_ops.cpp this TORCH_LIBRARY fragment
+// (vfm_bound.h, vfm_bound_sweep.h), their *_prior forms (vfm_bound_prior.h), the five *_workspace_bytes, and implicit_base
+// and foldin_solve_implicit with their size functions (vfm_implicit.h).  Like vfm_rank_ops.cpp this TORCH_LIBRARY fragment
 // only validates tensors, takes the current HIP stream of the tensors' device and forwards raw pointers; all arithmetic
 // is in the HIP kernels.  Every solve is its parts (vfm_ops_common.hpp) plus its own scalars plus one call.
 #include "vfm_ops_common.hpp"
@@ -9,6 +10,7 @@
 #include "vfm_bound_prior.h"
 #include "vfm_bound_sweep.h"
 #include "vfm_foldin.h"
+#include "vfm_implicit.h"
 #include "vfm_prior.h"
 #include "vfm_sweep.h"
 
@@ -185,6 +187,70 @@ void foldin_bound_split_prior(const Tensor& entities, const Tensor& chunk_ptr, c
   check(vfm_foldin_bound_split_prior_f32(&p, prior_of(prior, p.d), stream_of(y)), "vfm_foldin_bound_split_prior_f32");
 }
 
+int64_t implicit_base_doubles(int64_t d) {
+  return checked_bytes(vfm_implicit_base_doubles((int32_t)d), "vfm_implicit_base_doubles");
+}
+
+int64_t implicit_base_workspace_bytes(int64_t n, int64_t chunk_rows, int64_t d) {
+  return checked_bytes(vfm_implicit_base_workspace_bytes(n, chunk_rows, (int32_t)d), "vfm_implicit_base_workspace_bytes");
+}
+
+int64_t implicit_solve_workspace_bytes(int64_t E, int64_t n_chunks, int64_t d, int64_t lds_dim) {
+  return checked_bytes(vfm_implicit_solve_workspace_bytes(E, n_chunks, (int32_t)d, (int32_t)lds_dim),
+                       "vfm_implicit_solve_workspace_bytes");
+}
+
+void implicit_base(const Tensor& entity, const Tensor& bias, const Tensor& scalars, Tensor workspace, Tensor base,
+                   int64_t lo, int64_t n, int64_t chunk_rows, int64_t flags) {
+  vfm_implicit_base_t p;
+  memset(&p, 0, sizeof(p));
+  dev_tensor(entity, at::kFloat, "entity_params"); dev_tensor(bias, at::kFloat, "bias_params");
+  dev_tensor(scalars, at::kFloat, "scalars"); dev_tensor(base, at::kDouble, "base");
+  TORCH_CHECK(entity.dim() == 2 && bias.dim() == 2 && bias.size(1) == 2 && bias.size(0) == entity.size(0) &&
+              entity.size(1) % 2 == 0 && entity.size(1) >= 2 && scalars.numel() >= 3, "table shapes");
+  p.T = entity.size(0); p.d = (int32_t)(entity.size(1) / 2);
+  p.entity_params = entity.data_ptr<float>(); p.bias_params = bias.data_ptr<float>(); p.scalars = scalars.data_ptr<float>();
+  TORCH_CHECK(base.numel() >= checked_bytes(vfm_implicit_base_doubles(p.d), "vfm_implicit_base_doubles"),
+              "base [vfm_implicit_base_doubles(d)]");
+  p.out_base = base.data_ptr<double>();
+  fill_workspace(p, workspace);
+  p.lo = lo; p.n = n; p.chunk_rows = chunk_rows; p.flags = (int32_t)flags;
+  c10::hip::HIPGuard guard(entity.get_device());
+  check(vfm_implicit_base_f32(&p, stream_of(entity)), "vfm_implicit_base_f32");
+}
+
+void foldin_solve_implicit(const Tensor& entities, const optional<Tensor>& row_ptr, const optional<Tensor>& chunk_ptr,
+                           const optional<Tensor>& chunks, const Tensor& y, const Tensor& partner, const Tensor& base,
+                           Tensor entity, Tensor bias, const Tensor& scalars, Tensor workspace, Tensor loss, int64_t lo,
+                           int64_t n, int64_t flags, int64_t lds_dim, double kl_weight, double w0, double w1) {
+  vfm_implicit_solve_t p;
+  memset(&p, 0, sizeof(p));
+  dev_tensor(entities, at::kLong, "entities"); dev_tensor(y, at::kFloat, "y"); dev_tensor(partner, at::kLong, "partner");
+  dev_tensor(base, at::kDouble, "base"); dev_tensor(loss, at::kFloat, "loss");
+  TORCH_CHECK(partner.numel() == y.numel(), "partner [R] with y [R]");
+  TORCH_CHECK(loss.numel() >= entities.numel(), "loss [E]");
+  p.E = entities.numel(); p.R = y.numel();
+  p.entities = entities.data_ptr<int64_t>(); p.y = y.data_ptr<float>(); p.partner = partner.data_ptr<int64_t>();
+  p.out_loss = loss.data_ptr<float>();
+  fill_tables(p, entity, bias, scalars);
+  TORCH_CHECK(p.d >= 1 && base.numel() >= checked_bytes(vfm_implicit_base_doubles(p.d), "vfm_implicit_base_doubles"),
+              "base [vfm_implicit_base_doubles(d)]");
+  p.base = base.data_ptr<double>();
+  fill_workspace(p, workspace);
+  TORCH_CHECK(given(row_ptr) != given(chunk_ptr), "one of row_ptr and chunk_ptr");
+  if (given(row_ptr)) {
+    TORCH_CHECK(dev_tensor(*row_ptr, at::kLong, "row_ptr").numel() == p.E + 1, "row_ptr [E + 1]");
+    p.row_ptr = row_ptr->data_ptr<int64_t>();
+  } else {
+    TORCH_CHECK(given(chunks), "chunk_ptr needs chunks");
+    fill_chunk_table(p, *chunk_ptr, *chunks);
+  }
+  p.lo = lo; p.n = n; p.flags = (int32_t)flags; p.lds_dim = (int32_t)lds_dim;
+  p.kl_weight = (float)kl_weight; p.w0 = (float)w0; p.w1 = (float)w1;
+  c10::hip::HIPGuard guard(y.get_device());
+  check(vfm_foldin_solve_implicit_f32(&p, stream_of(y)), "vfm_foldin_solve_implicit_f32");
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(vfm_hip, m) {
@@ -234,4 +300,15 @@ TORCH_LIBRARY_FRAGMENT(vfm_hip, m) {
         "Tensor row_op, Tensor(a!) entity_params, Tensor(b!) bias_params, Tensor scalars, Tensor(c!) workspace, "
         "Tensor(d!) loss, Tensor prior, int col, int flags, int lds_dim, float kl_weight, int n_iters, int reset) -> ()",
         &foldin_bound_split_prior);
+  m.def("implicit_base_doubles(int d) -> int", &implicit_base_doubles);
+  m.def("implicit_base_workspace_bytes(int n, int chunk_rows, int d) -> int", &implicit_base_workspace_bytes);
+  m.def("implicit_base(Tensor entity_params, Tensor bias_params, Tensor scalars, Tensor(a!) workspace, Tensor(b!) base, "
+        "int lo, int n, int chunk_rows, int flags) -> ()",
+        &implicit_base);
+  m.def("implicit_solve_workspace_bytes(int E, int n_chunks, int d, int lds_dim) -> int", &implicit_solve_workspace_bytes);
+  m.def("foldin_solve_implicit(Tensor entities, Tensor? row_ptr, Tensor? chunk_ptr, Tensor? chunks, Tensor y, "
+        "Tensor partner, Tensor base, Tensor(a!) entity_params, Tensor(b!) bias_params, Tensor scalars, "
+        "Tensor(c!) workspace, Tensor(d!) loss, int lo, int n, int flags, int lds_dim, float kl_weight, float w0, "
+        "float w1) -> ()",
+        &foldin_solve_implicit);
 }

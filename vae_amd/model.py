@@ -1437,6 +1437,56 @@ class VFM(nn.Module):
                          prec_max=prec_max)
 
     @torch.no_grad()
+    def fold_in_implicit(self, X, y, field: int = 0, *, w0: float, w1: float = 1.0, kl_weight: float = 1.0,
+                         entities=None, split_rows="auto", chunk_rows: int = 2048, max_workspace_bytes: int = 1 << 30):
+        """fold_in_exact over EVERY (user, item) pair of a two-field 'reg' model, the implicit-feedback least-squares
+        objective (Hu, Koren & Volinsky; include/vfm_implicit.h; DESIGN.md §4 "Implicit sweeps"): the rows of X are the
+        observed pairs, with target y and weight w1; every other pair of the folded entity with the partner field has
+        target 0 and weight w0.  The sums over all partners are one Gram block of the partner field (its "base",
+        assembled once per call in fp64 over chunks of chunk_rows ids); each entity's (d + 1) x (d + 1) system starts
+        from it and is corrected at the entity's observed rows, so the call costs about a fold_in_exact over the
+        observed rows plus one pass over the partner catalog.
+
+        entities: None solves the field's whole id range, else the distinct ids given; an entity without observed rows
+        gets the base-only optimum.  split_rows, chunk_rows, max_workspace_bytes: as in fold_in_exact ("auto" =
+        4 (d + 1)); an entity's bits depend on its observed rows, the partner catalog, chunk_rows and d alone.
+        w0 has no default: nobody has measured a good one.  ValueError for a 'class' model, F != 2, kl_weight <= 0,
+        non-finite weights, w0 <= 0, w1 < w0, duplicate (user, item) pairs and ids outside their field.  Only the
+        folded rows of entity_params / bias_params change; the Adam state is not touched.
+        Returns dict(entities [E] int64 ascending, loss [E] fp32 = L_e over all partners at the returned parameters,
+        rows [E] int64 = observed rows)."""
+        from . import sweep
+        ents, loss, rows = sweep.run_implicit(self, X, y, field, w0, w1, kl_weight, entities, split_rows, chunk_rows,
+                                              max_workspace_bytes)
+        return {"entities": ents, "loss": loss, "rows": rows}
+
+    @torch.no_grad()
+    def implicit_objective(self, X, y, *, w0: float, w1: float = 1.0, kl_weight: float = 1.0) -> float:
+        """J_imp of fit_implicit at the current parameters (DESIGN.md §4 "Implicit sweeps"): over every (user, item)
+        pair w [1/2 prec ((y - E pred)^2 + Var pred) - 1/2 log prec + 1/2 log 2 pi] with (w, y) = (w1, y_r) at an
+        observed pair and (w0, 0) elsewhere, plus kl_weight times the KL to N(0, 1) of every entity of both fields and
+        of the global bias.  In fp64 on the device through the Gram form: the all-pairs sums are closed forms of the two
+        fields' Grams and first moments, corrected at the observed rows.  y None: all ones."""
+        from . import sweep
+        return sweep.implicit_objective(self, X, y, w0, w1, kl_weight)
+
+    @torch.no_grad()
+    def fit_implicit(self, X, y=None, n_sweeps: int = 10, *, w0: float, w1: float = 1.0, kl_weight: float = 1.0,
+                     update_scalars: bool = True, split_rows="auto", chunk_rows: int = 2048, on_step=None,
+                     tol: Optional[float] = None):
+        """fit_exact on the implicit-feedback objective J_imp (implicit_objective): exact coordinate ascent in which a
+        sweep solves every entity of field 0, then of field 1 (fold_in_implicit over the whole id range: entities
+        without observed rows are solved and counted too), then sets the global bias and after it the precision to
+        their exact minimisers of J_imp (update_scalars=False leaves the three scalars alone).  Each block is the
+        exact minimiser of J_imp over its variables, so J_imp never increases up to the fp32 rounding of what is
+        written.  y None: all ones (clicks).  on_step, tol and the result are fit_exact's; the plans of both fields are
+        built once.  The Adam state is not touched; rank_items, evaluate_ranking and the sessions run on the trained
+        tables as they are."""
+        from . import sweep
+        return sweep.fit_implicit(self, X, y, n_sweeps, w0, w1, kl_weight, update_scalars, split_rows, chunk_rows,
+                                  on_step, tol)
+
+    @torch.no_grad()
     def bound_objective(self, X, y, kl_weight: float = 1.0, priors=None) -> float:
         """The objective J of fit_bound at the current parameters ("Bound sweeps"): over the rows of X
         the Jaakkola-Jordan bound with xi at its optimum, -(y_r - 1/2) E f_r + xi_r / 2 + log1p(e^-xi_r) with

@@ -25,6 +25,13 @@ entities through vfm_foldin_bound_f32, unchanged, heavy ones through vfm_foldin_
   bound_objective  J of fit_bound, from the same moments
   update_bias_bound  the global bias' exact block minimiser under the bound at the current xi
   fit_bound        the sweeps
+
+For clicks or plays a two-field 'reg' model takes every (user, item) pair as a row (DESIGN.md §4, "Implicit sweeps";
+include/vfm_implicit.h): an observed pair with its target and weight w1, every other pair with target 0 and weight w0;
+
+  ImplicitPlan        a SweepPlan of the observed rows, each row's partner id and the entities without rows
+  implicit_sums       the weighted all-pairs sums, closed forms of the two fields' Grams corrected at the observed rows
+  fit_implicit        the sweeps: per field one base block of the partner field, then every entity's solve from it
 """
 from __future__ import annotations
 
@@ -156,7 +163,8 @@ class SweepPlan:
     exact solve's (run)."""
 
     def __init__(self, model, x, y, field, split_rows=None, chunk_rows=2048, max_workspace_bytes=MAX_WORKSPACE_BYTES,
-                 lds_dim=-1, bound=False):
+                 lds_dim=-1, bound=False, split_bytes=None):
+        # split_bytes(n_chunks, n_heavy, n_ops, d, lds_dim): another split form's workspace (ImplicitPlan)
         self.field, self.d, self.lds_dim = int(field), model.d, int(lds_dim)
         self.threshold = resolve_split_rows(split_rows, model.d)
         self.chunk_rows = check_chunk_rows(chunk_rows)
@@ -189,7 +197,9 @@ class SweepPlan:
             return
         first = np.concatenate([[0], np.cumsum(cnt)])[:-1]
         n_ops, nch = self.op_x.shape[0], (cnt + self.chunk_rows - 1) // self.chunk_rows
-        if bound:
+        if split_bytes is not None:
+            wsb = split_bytes
+        elif bound:
             n_rows, bsb = int(x.shape[0]), _lib.load().vfm_foldin_bound_split_workspace_bytes
             wsb = lambda n_chunks, n_heavy, n_ops, d, lds_dim: bsb(n_chunks, n_heavy, n_rows, n_ops, d, lds_dim)
         else:
@@ -614,3 +624,219 @@ def fit_bound(model, X, y, n_sweeps=10, kl_weight=1.0, n_iters=8, fields=None, u
     if learn_priors:
         out["clamped"] = {f: int(n) for f, n in clamped.items()}
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# implicit feedback: every (user, item) pair is a row ("Implicit sweeps"; include/vfm_implicit.h)
+# ---------------------------------------------------------------------------------------------------------------------
+def check_implicit_args(model, X, y, w0, w1, kl_weight):
+    """Validate the rows and weights of an implicit call (no GPU needed): a two-field 'reg' model, kl_weight > 0, finite
+    weights with w1 >= w0 > 0, ids in their fields, distinct (user, item) pairs.  y None: all ones.  Returns
+    (x [R, 2] int64, y [R] fp32, w0, w1) on the model's device."""
+    if model.output != "reg":
+        raise ValueError("the implicit solves need a 'reg' model (Gaussian likelihood): the closed form they solve has none "
+                         "for 'class'")
+    if model.F != 2:
+        raise ValueError(f"the implicit solves need a two-field model (F = 2), not F = {model.F}")
+    foldin._check_kl_positive(kl_weight)
+    w0, w1 = (float(torch.tensor(float(w), dtype=torch.float32)) for w in (w0, w1))     # (the kernels take them in fp32)
+    if not (math.isfinite(w0) and math.isfinite(w1)):
+        raise ValueError("w0 and w1 must be finite")
+    if not w0 > 0.0:
+        raise ValueError("w0 must be > 0: it is the weight of every unobserved pair")
+    if w1 < w0:
+        raise ValueError("w1 must be >= w0: an observed pair weighs at least what an unobserved one does")
+    if y is None:
+        n_rows = torch.as_tensor(X).shape[0] if torch.as_tensor(X).dim() else 0
+        y = torch.ones(n_rows, dtype=torch.float32)
+    x, y, _ = foldin.check_args(model, X, y, 0, "closed_form", 1, 0, 0.0, kl_weight)
+    if x.shape[0]:
+        key = x[:, 0] * model.T + x[:, 1]
+        if int(torch.unique(key).numel()) != x.shape[0]:
+            raise ValueError("duplicate (user, item) pairs: every pair is one row of the implicit objective")
+    return x, y, w0, w1
+
+
+def _check_entities(model, entities, field):
+    """entities= of fold_in_implicit: None, or distinct integer ids of the field's range.  Returns them sorted, on the
+    model's device."""
+    lo, hi = foldin.field_range(model, field)
+    if entities is None:
+        return None
+    e = torch.as_tensor(entities)
+    if e.numel() == 0:
+        e = e.to(torch.int64).reshape(-1)
+    if e.dtype.is_floating_point or e.dtype == torch.bool or e.dim() != 1:
+        raise ValueError("entities must be a 1-D sequence of integer ids")
+    e = e.to(model.device, torch.int64)
+    if e.numel() and (int(e.min()) < lo or int(e.max()) >= hi):
+        raise ValueError(f"entities must lie in the field's range [{lo}, {hi})")
+    e = torch.sort(e).values
+    if e.numel() > 1 and bool((e[1:] == e[:-1]).any()):
+        raise ValueError("entities must be distinct")
+    return e.contiguous()
+
+
+class ImplicitPlan:
+    """What one (X, y, field) of an implicit solve needs and that does not depend on the parameters: a SweepPlan of the
+    observed rows (its sort, its chunk table and its max_workspace_bytes grouping, the groups sized by
+    vfm_implicit_solve_workspace_bytes), each row's partner id, and the entities without observed rows.  entities: None
+    (the field's whole id range) or sorted distinct ids; rows of other entities are left out."""
+
+    def __init__(self, model, x, y, field, entities=None, split_rows="auto", chunk_rows=2048,
+                 max_workspace_bytes=MAX_WORKSPACE_BYTES, lds_dim=-1):
+        dev = x.device
+        self.field, self.d, self.lds_dim = int(field), model.d, int(lds_dim)
+        self.chunk_rows = check_chunk_rows(chunk_rows)
+        lo, hi = foldin.field_range(model, field)
+        self.partner_range = foldin.field_range(model, 1 - field)
+        if entities is None:
+            entities = torch.arange(lo, hi, dtype=torch.int64, device=dev)
+        else:
+            keep = torch.isin(x[:, field], entities)
+            x, y = x[keep].contiguous(), y[keep].contiguous()
+        size = _lib.load().vfm_implicit_solve_workspace_bytes
+        self.obs = SweepPlan(model, x, y, field, split_rows, chunk_rows, max_workspace_bytes, lds_dim,
+                             split_bytes=lambda n_chunks, n_heavy, n_ops, d, lds: size(n_heavy, n_chunks, d, lds))
+        p = self.obs
+        self.partner = (p.op_x[:, 1 - field][p.row_op].contiguous() if p.E else
+                        torch.zeros(0, dtype=torch.int64, device=dev))
+        self.ys = p.ys if p.E else torch.zeros(0, dtype=torch.float32, device=dev)
+        self.empty = entities[~torch.isin(entities, p.ents)].contiguous()
+        self.ents = torch.cat([p.ents, self.empty])
+        self.counts = torch.cat([p.counts, torch.zeros_like(self.empty)])
+        self.asc = torch.sort(self.ents).indices
+        self.E = self.ents.numel()
+
+    def base(self, model):
+        """The partner field's base block [vfm_implicit_base_doubles(d)] fp64 at the current tables."""
+        o = _lib.ops()
+        lo, hi = self.partner_range
+        out = torch.empty(o.implicit_base_doubles(self.d), dtype=torch.float64, device=model.device)
+        ws = torch.empty(o.implicit_base_workspace_bytes(hi - lo, self.chunk_rows, self.d), dtype=torch.uint8,
+                         device=model.device)
+        o.implicit_base(*model._views(model._flat), ws, out, lo, hi - lo, self.chunk_rows, foldin._link_flags(model))
+        return out
+
+    def run(self, model, kl_weight, w0, w1):
+        """Write the optimum of every entity of the plan into the model's tables: the base of the partner field, then
+        the entities with few observed rows in one call, a call per group of heavy ones, and the entities without
+        rows.  Returns (entities [E] ascending, loss [E], rows [E])."""
+        dev, p = model.device, self.obs
+        loss = torch.empty(self.E, dtype=torch.float32, device=dev)
+        if self.E == 0:
+            return self.ents, loss, self.counts
+        model._fresh_params()
+        o = _lib.ops()
+        base = self.base(model)
+        lo, hi = self.partner_range
+        tables = model._views(model._flat)
+        opts = (lo, hi - lo, foldin._link_flags(model), self.lds_dim, float(kl_weight), float(w0), float(w1))
+
+        def solve(ents, row_ptr, cptr, tab, out):
+            n = o.implicit_solve_workspace_bytes(ents.numel(), 0 if tab is None else tab.shape[0], self.d, self.lds_dim)
+            ws = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+            o.foldin_solve_implicit(ents, row_ptr, cptr, tab, self.ys, self.partner, base, *tables, ws, out, *opts)
+
+        if p.n_light:
+            nl = p.n_light
+            solve(p.ents[:nl], p.ptr[:nl + 1], None, None, loss[:nl])
+        for a, b, cptr, tab in p.groups:
+            solve(p.ents[a:b], None, cptr, tab, loss[a:b])
+        if self.empty.numel():
+            n0 = self.empty.numel()
+            solve(self.empty, torch.zeros(n0 + 1, dtype=torch.int64, device=dev), None, None, loss[p.E:])
+        model.params_changed()
+        return self.ents[self.asc], loss[self.asc], self.counts[self.asc]
+
+
+def run_implicit(model, X, y, field, w0, w1=1.0, kl_weight=1.0, entities=None, split_rows="auto", chunk_rows=2048,
+                 max_workspace_bytes=MAX_WORKSPACE_BYTES, lds_dim=-1):
+    """VFM.fold_in_implicit: (entities [E] ascending, loss [E], rows [E])."""
+    x, y, w0, w1 = check_implicit_args(model, X, y, w0, w1, kl_weight)
+    if isinstance(field, bool) or not isinstance(field, int) or not 0 <= field < 2:
+        raise ValueError("field must be 0 or 1")
+    entities = _check_entities(model, entities, field)
+    resolve_split_rows(split_rows, model.d)
+    check_chunk_rows(chunk_rows)
+    foldin._check_lds_dim(lds_dim)
+    if int(max_workspace_bytes) < 0:
+        raise ValueError("max_workspace_bytes must be >= 0")
+    ops._need_cuda(model._flat, "the model's parameters")
+    plan = ImplicitPlan(model, x, y, field, entities, split_rows, chunk_rows, int(max_workspace_bytes), lds_dim)
+    return plan.run(model, kl_weight, w0, w1)
+
+
+def implicit_sums(model, x, y, w0, w1):
+    """The three weighted sums over ALL (user, item) pairs that J_imp and its scalar blocks need, as 0-dim fp64 tensors on
+    the device: W = sum w, S1 = sum w (y - (E pred - m0)), S2 = sum w ((y - E pred)^2 + Var pred).  The all-pairs parts
+    are closed forms of the two fields' Grams and first moments (E pred_ui = p_u . q_i with p_u = (1, mu_w,u, mu_u) and
+    q_i = (m0 + mu_w,i, 1, mu_i), so sum_ui (E pred)^2 = <sum_u p p^T, sum_i q q^T>), O((N + M) d^2) in torch fp64 from
+    the tables; the observed rows correct them with the predictive_moments kernel's per-row moments."""
+    ent, bia, scal = model._views(model._flat)
+    d, link = model.d, model.link
+    N, M = model.field_sizes
+    m0, s0 = scal[1].double(), _link64(scal[2], link)
+    one = lambda n: torch.ones(n, 1, dtype=torch.float64, device=ent.device)
+    mu_u, mu_i = ent[:N, :d].double(), ent[N:N + M, :d].double()
+    su2, si2 = _link64(ent[:N, d:], link) ** 2, _link64(ent[N:N + M, d:], link) ** 2
+    P = torch.cat([one(N), bia[:N, :1].double(), mu_u], 1)
+    Q = torch.cat([m0 + bia[N:N + M, :1].double(), one(M), mu_i], 1)
+    sum_m2 = ((P.T @ P) * (Q.T @ Q)).sum()
+    sum_m = P.sum(0) @ Q.sum(0)
+    sum_v = (N * M * s0 * s0 + M * (_link64(bia[:N, 1], link) ** 2).sum() + N * (_link64(bia[N:N + M, 1], link) ** 2).sum()
+             + (mu_u * mu_u).sum(0) @ si2.sum(0) + su2.sum(0) @ (si2 + mu_i * mu_i).sum(0))
+    n = x.shape[0]
+    W = torch.tensor(w0 * N * M + (w1 - w0) * n, dtype=torch.float64, device=ent.device)
+    S1 = -w0 * (sum_m - N * M * m0)
+    S2 = w0 * (sum_m2 + sum_v)
+    if n:
+        m, v = _moments64(model, x)
+        yd = y.double()
+        S1 = S1 + (w1 * (yd - (m - m0)) + w0 * (m - m0)).sum()
+        S2 = S2 + (w1 * ((yd - m) ** 2 + v) - w0 * (m * m + v)).sum()
+    return W, S1, S2
+
+
+def implicit_objective_terms(model, x, y, w0, w1, kl_weight):
+    """J_imp as a 0-dim fp64 tensor on the device: the weighted expected negative log likelihood of every pair
+    (implicit_sums) plus kl_weight times the KL to N(0, 1) of every entity of both fields and of the global bias."""
+    ent, bia, scal = model._views(model._flat)
+    prec = _link64(scal[0], model.link)
+    W, _, S2 = implicit_sums(model, x, y, w0, w1)
+    kl = _add_kl64_rows(_kl64(scal[1].double(), _link64(scal[2], model.link)), ent, bia, model.d, model.link)
+    return 0.5 * prec * S2 + W * (LOG_2PI_HALF - 0.5 * torch.log(prec)) + float(kl_weight) * kl
+
+
+def update_scalars_implicit(model, x, y, w0, w1, kl_weight):
+    """The exact block minimisers of J_imp over the scalars, written in place: the global bias (mean and scale jointly),
+    then the precision from the sums recomputed after it.  No readback."""
+    scal = model._views(model._flat)[2]
+    kl = float(kl_weight)
+    prec = _link64(scal[0], model.link)
+    W, S1, _ = implicit_sums(model, x, y, w0, w1)
+    den = kl + prec * W
+    scal[1:3] = torch.stack([prec * S1 / den, _inv_link64(torch.sqrt(kl / den), model.link)]).float()
+    W, _, S2 = implicit_sums(model, x, y, w0, w1)
+    scal[0:1] = _inv_link64(W / S2, model.link).float().reshape(1)
+
+
+def implicit_objective(model, X, y, w0, w1=1.0, kl_weight=1.0):
+    x, y, w0, w1 = check_implicit_args(model, X, y, w0, w1, kl_weight)
+    ops._need_cuda(model._flat, "the model's parameters")
+    model._fresh_params()
+    return float(implicit_objective_terms(model, x, y, w0, w1, kl_weight))
+
+
+def fit_implicit(model, X, y=None, n_sweeps=10, w0=None, w1=1.0, kl_weight=1.0, update_scalars_=True, split_rows="auto",
+                 chunk_rows=2048, on_step=None, tol=None, max_workspace_bytes=MAX_WORKSPACE_BYTES):
+    x, y, w0, w1 = check_implicit_args(model, X, y, w0, w1, kl_weight)
+    check_fit_args(model, x, y, "reg", lambda f: (x, y), n_sweeps, None, split_rows, chunk_rows, tol)
+    ops._need_cuda(model._flat, "the model's parameters")
+    model._fresh_params()
+    plans = {f: ImplicitPlan(model, x, y, f, None, split_rows, chunk_rows, max_workspace_bytes) for f in (0, 1)}
+    return _sweeps(model, (0, 1), n_sweeps, tol, on_step,
+                   lambda: implicit_objective_terms(model, x, y, w0, w1, kl_weight),
+                   lambda f: plans[f].run(model, kl_weight, w0, w1), None,
+                   (lambda: update_scalars_implicit(model, x, y, w0, w1, kl_weight)) if update_scalars_ else None,
+                   "scalars")
