@@ -2,7 +2,10 @@
 nothing else), and the held-out clicks are ranked against the whole catalog.  fit_exact sees only the observed rows, all
 ones, and has nothing to learn; fit_implicit treats every other (user, item) pair as a row with target 0 and weight w0.
 
-    python examples/fit_implicit_synthetic.py [--w0 0.05] [--sweeps 8]
+    python examples/fit_implicit_synthetic.py [--w0 0.05] [--sweeps 8] [--learn-priors]
+
+--learn-priors: every field gets a Gaussian prior mean and precision per coordinate, set to its closed-form minimiser
+of J_imp after the field's solves over ALL of the field's entities (DESIGN.md §4 "Hierarchical implicit sweeps").
 """
 import argparse
 import os
@@ -30,6 +33,7 @@ def main():
     ap.add_argument("--d", type=int, default=16)
     ap.add_argument("--w0", type=float, default=0.05, help="weight of an unobserved pair (a starting value, not tuned)")
     ap.add_argument("--sweeps", type=int, default=8)
+    ap.add_argument("--learn-priors", action="store_true", help="learn each field's prior N(mean, 1 / prec)")
     args = ap.parse_args()
     from vae_amd.model import VFM
     dev = torch.device("cuda")
@@ -45,10 +49,15 @@ def main():
     torch.manual_seed(0)
     m = VFM(args.users, args.items, embedding_size=args.d, output="reg", device=dev)
     print("untrained: recall@10 %.4f ndcg@10 %.4f" % recall(m))
-    out = m.fit_implicit(Xtr, n_sweeps=args.sweeps, w0=args.w0,
+    out = m.fit_implicit(Xtr, n_sweeps=args.sweeps, w0=args.w0, learn_priors=args.learn_priors,
                          on_step=lambda s, w: print("  sweep %d: recall@10 %.4f ndcg@10 %.4f" % ((s,) + recall(m)))
                          if w == "scalars" else None)
     print("J_imp:", [round(v, 1) for v in out["objective"]])
+    if args.learn_priors:
+        for f, name in enumerate(("users", "items")):
+            pr = out["priors"].prec[f].cpu()
+            print("  learnt precisions of the %s: weight %.3g, factors %.3g .. %.3g (clamped coordinates: %d)"
+                  % (name, float(pr[0]), float(pr[1:].min()), float(pr[1:].max()), out["clamped"][f]))
     torch.manual_seed(0)
     e = VFM(args.users, args.items, embedding_size=args.d, output="reg", device=dev)
     e.fit_exact(Xtr, ones(Xtr), n_sweeps=args.sweeps)

@@ -155,6 +155,8 @@ _FOLD_PROTOTYPES = (
 # the solve of every (entity, partner) pair that starts from it
 IMPLICIT_EXPORTS = ("vfm_implicit_base_doubles", "vfm_implicit_base_workspace_bytes", "vfm_implicit_base_f32",
                     "vfm_implicit_solve_workspace_bytes", "vfm_foldin_solve_implicit_f32")
+# ... under a learnt field prior (include/vfm_implicit_prior.h: the same struct plus the prior pointer)
+IMPLICIT_PRIOR_EXPORTS = ("vfm_implicit_solve_prior_workspace_bytes", "vfm_foldin_solve_implicit_prior_f32")
 
 
 class ImplicitBase(_Strict, C.Structure):
@@ -353,6 +355,10 @@ def load():
     lib.vfm_implicit_base_f32.restype = C.c_int
     lib.vfm_foldin_solve_implicit_f32.argtypes = [C.POINTER(ImplicitSolve), vp]
     lib.vfm_foldin_solve_implicit_f32.restype = C.c_int
+    lib.vfm_implicit_solve_prior_workspace_bytes.argtypes = [i64, i64, i32, i32]
+    lib.vfm_implicit_solve_prior_workspace_bytes.restype = i64
+    lib.vfm_foldin_solve_implicit_prior_f32.argtypes = [C.POINTER(ImplicitSolve), vp, vp]
+    lib.vfm_foldin_solve_implicit_prior_f32.restype = C.c_int
     lib.vfm_elicit_bound_f32.argtypes = [C.POINTER(ElicitBound), vp]
     lib.vfm_elicit_bound_f32.restype = C.c_int
     lib.vfm_elicit_bound_workspace_bytes.argtypes = [i64, i64, i64, i64, i32, i32, i32]

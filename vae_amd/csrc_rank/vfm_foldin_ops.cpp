@@ -1,7 +1,8 @@
 // vfm_foldin_ops.cpp -- the fold-in family of torch.ops.vfm_hip: foldin (include/vfm_foldin.h), foldin_solve and
 // foldin_solve_split (vfm_foldin.h, vfm_sweep.h), their *_prior forms (vfm_prior.h), foldin_bound and foldin_bound_split
-// (vfm_bound.h, vfm_bound_sweep.h), their *_prior forms (vfm_bound_prior.h), the five *_workspace_bytes, and implicit_base
-// and foldin_solve_implicit with their size functions (vfm_implicit.h).  Like vfm_rank_ops.cpp this TORCH_LIBRARY fragment
+// (vfm_bound.h, vfm_bound_sweep.h), their *_prior forms (vfm_bound_prior.h), the five *_workspace_bytes, implicit_base
+// and foldin_solve_implicit with their size functions (vfm_implicit.h) and foldin_solve_implicit_prior
+// (vfm_implicit_prior.h).  Like vfm_rank_ops.cpp this TORCH_LIBRARY fragment
 // only validates tensors, takes the current HIP stream of the tensors' device and forwards raw pointers; all arithmetic
 // is in the HIP kernels.  Every solve is its parts (vfm_ops_common.hpp) plus its own scalars plus one call.
 #include "vfm_ops_common.hpp"
@@ -11,6 +12,7 @@
 #include "vfm_bound_sweep.h"
 #include "vfm_foldin.h"
 #include "vfm_implicit.h"
+#include "vfm_implicit_prior.h"
 #include "vfm_prior.h"
 #include "vfm_sweep.h"
 
@@ -219,11 +221,12 @@ void implicit_base(const Tensor& entity, const Tensor& bias, const Tensor& scala
   check(vfm_implicit_base_f32(&p, stream_of(entity)), "vfm_implicit_base_f32");
 }
 
-void foldin_solve_implicit(const Tensor& entities, const optional<Tensor>& row_ptr, const optional<Tensor>& chunk_ptr,
-                           const optional<Tensor>& chunks, const Tensor& y, const Tensor& partner, const Tensor& base,
-                           Tensor entity, Tensor bias, const Tensor& scalars, Tensor workspace, Tensor loss, int64_t lo,
-                           int64_t n, int64_t flags, int64_t lds_dim, double kl_weight, double w0, double w1) {
-  vfm_implicit_solve_t p;
+// what the implicit solve and its *_prior form name alike: everything but the prior
+void fill_implicit_solve(vfm_implicit_solve_t& p, const Tensor& entities, const optional<Tensor>& row_ptr,
+                         const optional<Tensor>& chunk_ptr, const optional<Tensor>& chunks, const Tensor& y,
+                         const Tensor& partner, const Tensor& base, const Tensor& entity, const Tensor& bias,
+                         const Tensor& scalars, const Tensor& workspace, const Tensor& loss, int64_t lo, int64_t n,
+                         int64_t flags, int64_t lds_dim, double kl_weight, double w0, double w1) {
   memset(&p, 0, sizeof(p));
   dev_tensor(entities, at::kLong, "entities"); dev_tensor(y, at::kFloat, "y"); dev_tensor(partner, at::kLong, "partner");
   dev_tensor(base, at::kDouble, "base"); dev_tensor(loss, at::kFloat, "loss");
@@ -247,8 +250,29 @@ void foldin_solve_implicit(const Tensor& entities, const optional<Tensor>& row_p
   }
   p.lo = lo; p.n = n; p.flags = (int32_t)flags; p.lds_dim = (int32_t)lds_dim;
   p.kl_weight = (float)kl_weight; p.w0 = (float)w0; p.w1 = (float)w1;
+}
+
+void foldin_solve_implicit(const Tensor& entities, const optional<Tensor>& row_ptr, const optional<Tensor>& chunk_ptr,
+                           const optional<Tensor>& chunks, const Tensor& y, const Tensor& partner, const Tensor& base,
+                           Tensor entity, Tensor bias, const Tensor& scalars, Tensor workspace, Tensor loss, int64_t lo,
+                           int64_t n, int64_t flags, int64_t lds_dim, double kl_weight, double w0, double w1) {
+  vfm_implicit_solve_t p;
+  fill_implicit_solve(p, entities, row_ptr, chunk_ptr, chunks, y, partner, base, entity, bias, scalars, workspace, loss,
+                      lo, n, flags, lds_dim, kl_weight, w0, w1);
   c10::hip::HIPGuard guard(y.get_device());
   check(vfm_foldin_solve_implicit_f32(&p, stream_of(y)), "vfm_foldin_solve_implicit_f32");
+}
+
+void foldin_solve_implicit_prior(const Tensor& entities, const optional<Tensor>& row_ptr,
+                                 const optional<Tensor>& chunk_ptr, const optional<Tensor>& chunks, const Tensor& y,
+                                 const Tensor& partner, const Tensor& base, Tensor entity, Tensor bias,
+                                 const Tensor& scalars, Tensor workspace, Tensor loss, const Tensor& prior, int64_t lo,
+                                 int64_t n, int64_t flags, int64_t lds_dim, double kl_weight, double w0, double w1) {
+  vfm_implicit_solve_t p;
+  fill_implicit_solve(p, entities, row_ptr, chunk_ptr, chunks, y, partner, base, entity, bias, scalars, workspace, loss,
+                      lo, n, flags, lds_dim, kl_weight, w0, w1);
+  c10::hip::HIPGuard guard(y.get_device());
+  check(vfm_foldin_solve_implicit_prior_f32(&p, prior_of(prior, p.d), stream_of(y)), "vfm_foldin_solve_implicit_prior_f32");
 }
 
 }  // namespace
@@ -311,4 +335,9 @@ TORCH_LIBRARY_FRAGMENT(vfm_hip, m) {
         "Tensor(c!) workspace, Tensor(d!) loss, int lo, int n, int flags, int lds_dim, float kl_weight, float w0, "
         "float w1) -> ()",
         &foldin_solve_implicit);
+  m.def("foldin_solve_implicit_prior(Tensor entities, Tensor? row_ptr, Tensor? chunk_ptr, Tensor? chunks, Tensor y, "
+        "Tensor partner, Tensor base, Tensor(a!) entity_params, Tensor(b!) bias_params, Tensor scalars, "
+        "Tensor(c!) workspace, Tensor(d!) loss, Tensor prior, int lo, int n, int flags, int lds_dim, float kl_weight, "
+        "float w0, float w1) -> ()",
+        &foldin_solve_implicit_prior);
 }

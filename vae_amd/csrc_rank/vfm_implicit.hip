@@ -19,6 +19,12 @@
 // The operands of a partner j are read from the fp32 tables where they are used (F = 2: M = mu_j, A = link(s_j)^2 in
 // fp64, C = 0, c_mean = m_0 + mu_w,j, c_var = link(s_0)^2 + link(s_w,j)^2): there is no operand block.  Every sum has a
 // fixed order that depends on the entity's rows, the catalog, chunk_rows and d alone: no atomics, no host sync.
+//
+// vfm_foldin_solve_implicit_prior_f32 (include/vfm_implicit_prior.h) is the PRIOR = true instantiation of k_implicit_solve:
+// the folded field's prior [2, d + 1] = mean | precision is staged once per workgroup in fp64 in LDS in front of the
+// vectors (lds_doubles_prior), H = kl diag(lam) + ..., b += kl lam m, sigma_c^2 = kl / (kl lam_c + prec SB'_c) and the KL
+// of the loss is to that prior; at m = 0, lam = 1 every expression rounds as with PRIOR off.  The base and the chunk pass do
+// not depend on the prior; the instantiation without it is the parent's, unchanged.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -27,6 +33,7 @@
 
 #include "vfm_args.hpp"
 #include "vfm_implicit.h"
+#include "vfm_implicit_prior.h"
 #include "vfm_launch.hpp"            // launch_status
 
 namespace vfm {
@@ -54,6 +61,7 @@ struct ImpArgs {
   const float* scal;
   float* loss;
   SolveSlabs sl;
+  const float* prior;                    // [2, d + 1] mean | precision of the folded field (PRIOR instantiation only)
 };
 
 __host__ __device__ inline int64_t imp_doubles(int d) { return tri(d + 1) + 3 * (int64_t)(d + 1) + 1; }
@@ -220,13 +228,19 @@ __global__ __launch_bounds__(FB) void k_implicit_chunks(const ImpArgs s) {
   }
 }
 
-template <int LINK>
+template <int LINK, bool PRIOR>
 __global__ __launch_bounds__(FB) void k_implicit_solve(const ImpArgs s) {
 #pragma clang fp contract(on)
-  extern __shared__ double sm[];
+  extern __shared__ double sm_all[];
   __shared__ double tts;                 // tt' of the entity
   const int tid = threadIdx.x;
   const int d = s.d, d1 = d + 1;
+  double* sm = sm_all + (PRIOR ? 2 * d1 : 0);              // (the prior in front: lds_doubles_prior)
+  const double* pr = PRIOR ? sm_all : nullptr;             // m [d + 1] | lam [d + 1]
+  if constexpr (PRIOR) {
+    stage_prior(s.prior, sm_all, d1);
+    __syncthreads();
+  }
   double* Dd = sm;                       // solve_body's layout: D | loss terms | b | right-hand side | 1 / L_jj | solution | SB' | fp32
   double* lt = Dd + d1;
   double* bs = lt + d1;
@@ -277,9 +291,15 @@ __global__ __launch_bounds__(FB) void k_implicit_solve(const ImpArgs s) {
         if (c > 0) SB = qnan;
       }
       const double b = prec * (w0 * B[nt + 2 * d1 + c] + bM);
-      Dd[c] = kl + prec * (w0 * B[nt + c] + dw * SA);
-      yv[c] = b;
-      bs[c] = b;
+      if constexpr (PRIOR) {
+        const double kll = kl * pr[d1 + c];
+        Dd[c] = kll + prec * (w0 * B[nt + c] + dw * SA);
+        yv[c] = b + kll * pr[c];
+      } else {
+        Dd[c] = kl + prec * (w0 * B[nt + c] + dw * SA);
+        yv[c] = b;
+      }
+      bs[c] = b;                         // (b of the data: the loss takes the prior's part through its KL)
       SBd[c] = w0 * B[nt + d1 + c] + dw * SB;
       if (c == 0) tts = w0 * B[nt + 3 * d1] + tt;
     }
@@ -310,7 +330,10 @@ __global__ __launch_bounds__(FB) void k_implicit_solve(const ImpArgs s) {
 
     // ---- C, D: the factorisation, the substitutions and the rounding of the exact fold-in
     chol_solve(Hm, yv, dv, xv, d1);
-    for (int c = tid; c < d1; c += FB) put_params<LINK>(pf, d1, c, xv[c], kl, prec, SBd[c]);
+    for (int c = tid; c < d1; c += FB) {
+      if constexpr (PRIOR) put_params<LINK, true>(pf, d1, c, xv[c], kl, prec, SBd[c], kl * pr[d1 + c]);
+      else put_params<LINK>(pf, d1, c, xv[c], kl, prec, SBd[c]);
+    }
     __syncthreads();
     for (int k = tid; k < d; k += FB) {
       s.entity[e * 2 * d + k] = pf[1 + k];
@@ -326,8 +349,16 @@ __global__ __launch_bounds__(FB) void k_implicit_solve(const ImpArgs s) {
       const double th = pf[c], sg = link_d<LINK>(pf[d1 + c]);
       double l = th / dv[c];
       for (int i = c + 1; i < d1; ++i) l += Hm[tri(i) + c] * (double)pf[i];
-      const double klq = 0.5 * (sg * sg + th * th - 1.0) - log(sg);
-      lt[c] = (l * l - kl * th * th) - 2.0 * th * bs[c] + prec * sg * sg * SBd[c] + 2.0 * kl * klq;
+      if constexpr (PRIOR) {
+        // KL(N(th, sg^2) || N(m, 1 / lam)) = KL(N(sqrt(lam) (th - m), lam sg^2) || N(0, 1)), as kl_prior_normal takes it
+        const double kll = kl * pr[d1 + c], sl = sqrt(pr[d1 + c]);
+        const double tm = sl * (th - pr[c]), ts = sl * sg;
+        const double klq = 0.5 * (ts * ts + tm * tm - 1.0) - log(ts);
+        lt[c] = (l * l - kll * th * th) - 2.0 * th * bs[c] + prec * sg * sg * SBd[c] + 2.0 * kl * klq;
+      } else {
+        const double klq = 0.5 * (sg * sg + th * th - 1.0) - log(sg);
+        lt[c] = (l * l - kl * th * th) - 2.0 * th * bs[c] + prec * sg * sg * SBd[c] + 2.0 * kl * klq;
+      }
     }
     __syncthreads();
     if (tid == 0) {
@@ -343,6 +374,8 @@ inline int64_t imp_part_bytes(int64_t n_chunks, int d) { return round_up(n_chunk
 
 }  // namespace
 }  // namespace vfm
+
+static int implicit_solve_call(const vfm_implicit_solve_t* p, const float* prior, void* stream);
 
 extern "C" {
 
@@ -397,7 +430,22 @@ int vfm_implicit_base_f32(const vfm_implicit_base_t* p, void* stream) {
   return launch_status("k_implicit_base_sum");
 }
 
+int64_t vfm_implicit_solve_prior_workspace_bytes(int64_t E, int64_t n_chunks, int32_t d, int32_t lds_dim) {
+  return vfm_implicit_solve_workspace_bytes(E, n_chunks, d, lds_dim);  // (the prior lives in LDS, not in the workspace)
+}
+
 int vfm_foldin_solve_implicit_f32(const vfm_implicit_solve_t* p, void* stream) {
+  return implicit_solve_call(p, nullptr, stream);
+}
+
+int vfm_foldin_solve_implicit_prior_f32(const vfm_implicit_solve_t* p, const float* prior, void* stream) {
+  return implicit_solve_call(p, prior, stream);
+}
+
+}  // extern "C"
+
+// both entry points: prior == NULL is vfm_foldin_solve_implicit_f32
+static int implicit_solve_call(const vfm_implicit_solve_t* p, const float* prior, void* stream) {
   using vfm::fail;
   if (!p) return fail(VFM_E_INVALID, "vfm_foldin_solve_implicit_f32: NULL argument struct");
   if (p->T < 1) return fail(VFM_E_INVALID, "T < 1");
@@ -434,10 +482,11 @@ int vfm_foldin_solve_implicit_f32(const vfm_implicit_solve_t* p, void* stream) {
   s.partner = p->partner; s.y = p->y; s.base = p->base;
   s.part = (double*)p->workspace; s.part_elems = vfm::imp_doubles(p->d);
   s.entity = p->entity_params; s.bias = p->bias_params; s.scal = p->scalars; s.loss = p->out_loss;
+  s.prior = prior;
   const int64_t gcap = (int64_t)1 << 20;
   const unsigned grid_e = vfm::place_slabs(p->d, p->lds_dim, p->E, (char*)p->workspace + vfm::imp_part_bytes(p->n_chunks, p->d),
                                            gcap, s.sl);
-  const size_t shm = (size_t)vfm::lds_doubles(p->d, s.sl.cap_dim) * 8;
+  const size_t shm = (size_t)(prior ? vfm::lds_doubles_prior(p->d, s.sl.cap_dim) : vfm::lds_doubles(p->d, s.sl.cap_dim)) * 8;
 
   if (p->n_chunks > 0) {
     const unsigned grid_c = (unsigned)(p->n_chunks < gcap ? p->n_chunks : gcap);
@@ -446,8 +495,9 @@ int vfm_foldin_solve_implicit_f32(const vfm_implicit_solve_t* p, void* stream) {
     });
     if (int rc = launch_status("k_implicit_chunks")) return rc;
   }
-  vfm::for_link(sp, [&](auto link) { vfm::launch_lds(vfm::k_implicit_solve<decltype(link)::value>, grid_e, shm, st, s); });
+  vfm::for_link(sp, [&](auto link) {
+    if (prior) vfm::launch_lds(vfm::k_implicit_solve<decltype(link)::value, true>, grid_e, shm, st, s);
+    else vfm::launch_lds(vfm::k_implicit_solve<decltype(link)::value, false>, grid_e, shm, st, s);
+  });
   return launch_status("k_implicit_solve");
 }
-
-}  // extern "C"

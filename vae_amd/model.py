@@ -50,6 +50,27 @@ class LikelihoodResult:
 _CHECK_WREC = bool(int(__import__("os").environ.get("VFM_CHECK_WREC", "0")))
 
 
+class _StandardPrior:
+    """The default of priors= in the implicit methods: the N(0, 1) prior of every entity, the call as it was before
+    priors= existed.  Those methods take a sweep.GroupPriors or nothing: an explicit None is a TypeError, as any other
+    argument that is no GroupPriors' place to stand in would be (the module functions of vae_amd.sweep take None)."""
+
+    def __repr__(self):
+        return "N(0, 1)"
+
+
+STANDARD_PRIOR = _StandardPrior()
+
+
+def _implicit_priors(priors):
+    """priors= of fold_in_implicit, implicit_objective and fit_implicit for vae_amd.sweep: None for the default."""
+    if priors is STANDARD_PRIOR:
+        return None
+    if priors is None:
+        raise TypeError("priors must be a sweep.GroupPriors; leave it out for the N(0, 1) prior")
+    return priors
+
+
 def _round4(n):
     return (n + 3) // 4 * 4
 
@@ -1438,7 +1459,8 @@ class VFM(nn.Module):
 
     @torch.no_grad()
     def fold_in_implicit(self, X, y, field: int = 0, *, w0: float, w1: float = 1.0, kl_weight: float = 1.0,
-                         entities=None, split_rows="auto", chunk_rows: int = 2048, max_workspace_bytes: int = 1 << 30):
+                         entities=None, split_rows="auto", chunk_rows: int = 2048, max_workspace_bytes: int = 1 << 30,
+                         priors=STANDARD_PRIOR):
         """fold_in_exact over EVERY (user, item) pair of a two-field 'reg' model, the implicit-feedback least-squares
         objective (Hu, Koren & Volinsky; include/vfm_implicit.h; DESIGN.md §4 "Implicit sweeps"): the rows of X are the
         observed pairs, with target y and weight w1; every other pair of the folded entity with the partner field has
@@ -1453,27 +1475,36 @@ class VFM(nn.Module):
         w0 has no default: nobody has measured a good one.  ValueError for a 'class' model, F != 2, kl_weight <= 0,
         non-finite weights, w0 <= 0, w1 < w0, duplicate (user, item) pairs and ids outside their field.  Only the
         folded rows of entity_params / bias_params change; the Adam state is not touched.
+        priors (a sweep.GroupPriors): every entity is solved under the folded field's N(mean, 1 / prec) per coordinate
+        in place of N(0, 1) (include/vfm_implicit_prior.h; DESIGN.md §4 "Hierarchical implicit sweeps"), and the loss
+        carries the KL to it; an entity without observed rows gets the base-only optimum under the prior.  At (0, 1)
+        the rows and losses are those of the call without priors=, bit for bit.  priors= takes a GroupPriors or is
+        left out: an explicit None is a TypeError.
         Returns dict(entities [E] int64 ascending, loss [E] fp32 = L_e over all partners at the returned parameters,
         rows [E] int64 = observed rows)."""
         from . import sweep
         ents, loss, rows = sweep.run_implicit(self, X, y, field, w0, w1, kl_weight, entities, split_rows, chunk_rows,
-                                              max_workspace_bytes)
+                                              max_workspace_bytes, priors=_implicit_priors(priors))
         return {"entities": ents, "loss": loss, "rows": rows}
 
     @torch.no_grad()
-    def implicit_objective(self, X, y, *, w0: float, w1: float = 1.0, kl_weight: float = 1.0) -> float:
+    def implicit_objective(self, X, y, *, w0: float, w1: float = 1.0, kl_weight: float = 1.0,
+                           priors=STANDARD_PRIOR) -> float:
         """J_imp of fit_implicit at the current parameters (DESIGN.md §4 "Implicit sweeps"): over every (user, item)
         pair w [1/2 prec ((y - E pred)^2 + Var pred) - 1/2 log prec + 1/2 log 2 pi] with (w, y) = (w1, y_r) at an
         observed pair and (w0, 0) elsewhere, plus kl_weight times the KL to N(0, 1) of every entity of both fields and
         of the global bias.  In fp64 on the device through the Gram form: the all-pairs sums are closed forms of the two
-        fields' Grams and first moments, corrected at the observed rows.  y None: all ones."""
+        fields' Grams and first moments, corrected at the observed rows.  y None: all ones.  priors (a
+        sweep.GroupPriors): the KL of every entity of both fields, observed or not, is to its field's prior; the global
+        bias keeps N(0, 1)."""
         from . import sweep
-        return sweep.implicit_objective(self, X, y, w0, w1, kl_weight)
+        return sweep.implicit_objective(self, X, y, w0, w1, kl_weight, _implicit_priors(priors))
 
     @torch.no_grad()
     def fit_implicit(self, X, y=None, n_sweeps: int = 10, *, w0: float, w1: float = 1.0, kl_weight: float = 1.0,
                      update_scalars: bool = True, split_rows="auto", chunk_rows: int = 2048, on_step=None,
-                     tol: Optional[float] = None):
+                     tol: Optional[float] = None, priors=STANDARD_PRIOR, learn_priors: bool = False,
+                     learn_mean: bool = True, prec_min: float = 1e-4, prec_max: float = 1e4):
         """fit_exact on the implicit-feedback objective J_imp (implicit_objective): exact coordinate ascent in which a
         sweep solves every entity of field 0, then of field 1 (fold_in_implicit over the whole id range: entities
         without observed rows are solved and counted too), then sets the global bias and after it the precision to
@@ -1481,10 +1512,20 @@ class VFM(nn.Module):
         exact minimiser of J_imp over its variables, so J_imp never increases up to the fp32 rounding of what is
         written.  y None: all ones (clicks).  on_step, tol and the result are fit_exact's; the plans of both fields are
         built once.  The Adam state is not touched; rank_items, evaluate_ranking and the sessions run on the trained
-        tables as they are."""
+        tables as they are.
+
+        priors (a sweep.GroupPriors; DESIGN.md §4 "Hierarchical implicit sweeps"): each field's entities are solved
+        under its N(mean, 1 / prec) (include/vfm_implicit_prior.h) and J_imp is implicit_objective(priors=priors).  With
+        learn_priors=True the field's prior is set to its exact minimiser of J_imp after the field's solves, over ALL
+        ids of the field -- an entity without observed rows is in J_imp through its w0 pairs, so it counts -- with
+        the mean kept when learn_mean=False and the precision clamped to [prec_min, prec_max]; on_step is then also
+        called with ("prior", f).  learn_priors=True without priors= starts them at N(0, 1).  The result then holds
+        "priors" and "clamped" ({field: coordinates at which a clamp bound, summed over the sweeps}), as fit_exact's.
+        A model trained this way interviews under the same priors= in the exact and design sessions."""
         from . import sweep
         return sweep.fit_implicit(self, X, y, n_sweeps, w0, w1, kl_weight, update_scalars, split_rows, chunk_rows,
-                                  on_step, tol)
+                                  on_step, tol, priors=_implicit_priors(priors), learn_priors=learn_priors,
+                                  learn_mean=learn_mean, prec_min=prec_min, prec_max=prec_max)
 
     @torch.no_grad()
     def bound_objective(self, X, y, kl_weight: float = 1.0, priors=None) -> float:

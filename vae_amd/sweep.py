@@ -32,6 +32,10 @@ include/vfm_implicit.h): an observed pair with its target and weight w1, every o
   ImplicitPlan        a SweepPlan of the observed rows, each row's partner id and the entities without rows
   implicit_sums       the weighted all-pairs sums, closed forms of the two fields' Grams corrected at the observed rows
   fit_implicit        the sweeps: per field one base block of the partner field, then every entity's solve from it
+
+and under a GroupPriors (include/vfm_implicit_prior.h; DESIGN.md §4, "Hierarchical implicit sweeps") the same plan solves
+under the folded field's prior (vfm_foldin_solve_implicit_prior_f32), J_imp carries every entity's KL to its field's prior
+and the prior block (update_prior) runs over the field's whole id range: an entity without observed rows is in J_imp.
 """
 from __future__ import annotations
 
@@ -718,10 +722,12 @@ class ImplicitPlan:
         o.implicit_base(*model._views(model._flat), ws, out, lo, hi - lo, self.chunk_rows, foldin._link_flags(model))
         return out
 
-    def run(self, model, kl_weight, w0, w1):
+    def run(self, model, kl_weight, w0, w1, prior=None):
         """Write the optimum of every entity of the plan into the model's tables: the base of the partner field, then
         the entities with few observed rows in one call, a call per group of heavy ones, and the entities without
-        rows.  Returns (entities [E] ascending, loss [E], rows [E])."""
+        rows.  prior: the folded field's [2, d + 1] mean | precision on the device (GroupPriors.row); every one of the
+        calls then solves under it (vfm_foldin_solve_implicit_prior_f32, include/vfm_implicit_prior.h); None: the
+        parent call itself.  Returns (entities [E] ascending, loss [E], rows [E])."""
         dev, p = model.device, self.obs
         loss = torch.empty(self.E, dtype=torch.float32, device=dev)
         if self.E == 0:
@@ -736,7 +742,11 @@ class ImplicitPlan:
         def solve(ents, row_ptr, cptr, tab, out):
             n = o.implicit_solve_workspace_bytes(ents.numel(), 0 if tab is None else tab.shape[0], self.d, self.lds_dim)
             ws = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-            o.foldin_solve_implicit(ents, row_ptr, cptr, tab, self.ys, self.partner, base, *tables, ws, out, *opts)
+            a = (ents, row_ptr, cptr, tab, self.ys, self.partner, base, *tables, ws, out)
+            if prior is None:
+                o.foldin_solve_implicit(*a, *opts)
+            else:
+                o.foldin_solve_implicit_prior(*a, prior, *opts)
 
         if p.n_light:
             nl = p.n_light
@@ -751,9 +761,10 @@ class ImplicitPlan:
 
 
 def run_implicit(model, X, y, field, w0, w1=1.0, kl_weight=1.0, entities=None, split_rows="auto", chunk_rows=2048,
-                 max_workspace_bytes=MAX_WORKSPACE_BYTES, lds_dim=-1):
-    """VFM.fold_in_implicit: (entities [E] ascending, loss [E], rows [E])."""
+                 max_workspace_bytes=MAX_WORKSPACE_BYTES, lds_dim=-1, priors=None):
+    """VFM.fold_in_implicit: (entities [E] ascending, loss [E], rows [E]).  priors: under the folded field's prior."""
     x, y, w0, w1 = check_implicit_args(model, X, y, w0, w1, kl_weight)
+    check_priors(model, priors)
     if isinstance(field, bool) or not isinstance(field, int) or not 0 <= field < 2:
         raise ValueError("field must be 0 or 1")
     entities = _check_entities(model, entities, field)
@@ -764,7 +775,7 @@ def run_implicit(model, X, y, field, w0, w1=1.0, kl_weight=1.0, entities=None, s
         raise ValueError("max_workspace_bytes must be >= 0")
     ops._need_cuda(model._flat, "the model's parameters")
     plan = ImplicitPlan(model, x, y, field, entities, split_rows, chunk_rows, int(max_workspace_bytes), lds_dim)
-    return plan.run(model, kl_weight, w0, w1)
+    return plan.run(model, kl_weight, w0, w1, _prior_row(model, priors, field))
 
 
 def implicit_sums(model, x, y, w0, w1):
@@ -798,13 +809,27 @@ def implicit_sums(model, x, y, w0, w1):
     return W, S1, S2
 
 
-def implicit_objective_terms(model, x, y, w0, w1, kl_weight):
+def _field_ids(model, field):
+    """Every id of `field`, seen in X or not, on the model's device."""
+    lo, hi = foldin.field_range(model, field)
+    return torch.arange(lo, hi, dtype=torch.int64, device=model.device)
+
+
+def implicit_objective_terms(model, x, y, w0, w1, kl_weight, priors=None):
     """J_imp as a 0-dim fp64 tensor on the device: the weighted expected negative log likelihood of every pair
-    (implicit_sums) plus kl_weight times the KL to N(0, 1) of every entity of both fields and of the global bias."""
+    (implicit_sums) plus kl_weight times the KL to N(0, 1) of every entity of both fields and of the global bias.
+    priors: every entity's KL -- observed or not: its w0 rows are in the likelihood -- is to its field's
+    N(mean, 1 / prec); the global bias keeps N(0, 1)."""
     ent, bia, scal = model._views(model._flat)
     prec = _link64(scal[0], model.link)
     W, _, S2 = implicit_sums(model, x, y, w0, w1)
-    kl = _add_kl64_rows(_kl64(scal[1].double(), _link64(scal[2], model.link)), ent, bia, model.d, model.link)
+    kl = _kl64(scal[1].double(), _link64(scal[2], model.link))
+    if priors is None:
+        kl = _add_kl64_rows(kl, ent, bia, model.d, model.link)
+    else:
+        for f in (0, 1):
+            mu, sg = _theta64(model, _field_ids(model, f))
+            kl = kl + _kl64_prior(mu, sg, priors.mean[f].to(mu.device).double(), priors.prec[f].to(mu.device).double()).sum()
     return 0.5 * prec * S2 + W * (LOG_2PI_HALF - 0.5 * torch.log(prec)) + float(kl_weight) * kl
 
 
@@ -821,22 +846,41 @@ def update_scalars_implicit(model, x, y, w0, w1, kl_weight):
     scal[0:1] = _inv_link64(W / S2, model.link).float().reshape(1)
 
 
-def implicit_objective(model, X, y, w0, w1=1.0, kl_weight=1.0):
+def implicit_objective(model, X, y, w0, w1=1.0, kl_weight=1.0, priors=None):
     x, y, w0, w1 = check_implicit_args(model, X, y, w0, w1, kl_weight)
+    check_priors(model, priors)
     ops._need_cuda(model._flat, "the model's parameters")
     model._fresh_params()
-    return float(implicit_objective_terms(model, x, y, w0, w1, kl_weight))
+    return float(implicit_objective_terms(model, x, y, w0, w1, kl_weight, priors))
 
 
 def fit_implicit(model, X, y=None, n_sweeps=10, w0=None, w1=1.0, kl_weight=1.0, update_scalars_=True, split_rows="auto",
-                 chunk_rows=2048, on_step=None, tol=None, max_workspace_bytes=MAX_WORKSPACE_BYTES):
+                 chunk_rows=2048, on_step=None, tol=None, max_workspace_bytes=MAX_WORKSPACE_BYTES, priors=None,
+                 learn_priors=False, learn_mean=True, prec_min=1e-4, prec_max=1e4):
     x, y, w0, w1 = check_implicit_args(model, X, y, w0, w1, kl_weight)
     check_fit_args(model, x, y, "reg", lambda f: (x, y), n_sweeps, None, split_rows, chunk_rows, tol)
+    check_priors(model, priors)
+    prec_min, prec_max = check_prec_bounds(prec_min, prec_max)
     ops._need_cuda(model._flat, "the model's parameters")
+    if learn_priors and priors is None:
+        priors = GroupPriors(model.F, model.d, model.device)          # (created at N(0, 1), returned under "priors")
     model._fresh_params()
     plans = {f: ImplicitPlan(model, x, y, f, None, split_rows, chunk_rows, max_workspace_bytes) for f in (0, 1)}
-    return _sweeps(model, (0, 1), n_sweeps, tol, on_step,
-                   lambda: implicit_objective_terms(model, x, y, w0, w1, kl_weight),
-                   lambda f: plans[f].run(model, kl_weight, w0, w1), None,
-                   (lambda: update_scalars_implicit(model, x, y, w0, w1, kl_weight)) if update_scalars_ else None,
-                   "scalars")
+    # the prior block is over the field's WHOLE id range: in J_imp every entity is in the KL, observed or not
+    all_f = {f: _field_ids(model, f) for f in (0, 1)} if learn_priors else {}
+    clamped = {f: torch.zeros((), dtype=torch.int64, device=x.device) for f in all_f}
+
+    def learn_prior(f):
+        clamped[f] += update_prior(model, priors, f, all_f[f], learn_mean, prec_min, prec_max)
+
+    out = _sweeps(model, (0, 1), n_sweeps, tol, on_step,
+                  lambda: implicit_objective_terms(model, x, y, w0, w1, kl_weight, priors),
+                  lambda f: plans[f].run(model, kl_weight, w0, w1, _prior_row(model, priors, f)),
+                  learn_prior if learn_priors else None,
+                  (lambda: update_scalars_implicit(model, x, y, w0, w1, kl_weight)) if update_scalars_ else None,
+                  "scalars")
+    if priors is not None:
+        out["priors"] = priors
+    if learn_priors:
+        out["clamped"] = {f: int(n) for f, n in clamped.items()}
+    return out
