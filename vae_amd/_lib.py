@@ -157,6 +157,8 @@ IMPLICIT_EXPORTS = ("vfm_implicit_base_doubles", "vfm_implicit_base_workspace_by
                     "vfm_implicit_solve_workspace_bytes", "vfm_foldin_solve_implicit_f32")
 # ... under a learnt field prior (include/vfm_implicit_prior.h: the same struct plus the prior pointer)
 IMPLICIT_PRIOR_EXPORTS = ("vfm_implicit_solve_prior_workspace_bytes", "vfm_foldin_solve_implicit_prior_f32")
+# ... with a weight per observed row (include/vfm_implicit_weights.h: the same struct, the prior and the weights pointers)
+IMPLICIT_WEIGHTS_EXPORTS = ("vfm_implicit_solve_weights_workspace_bytes", "vfm_foldin_solve_implicit_weights_f32")
 
 
 class ImplicitBase(_Strict, C.Structure):
@@ -359,6 +361,10 @@ def load():
     lib.vfm_implicit_solve_prior_workspace_bytes.restype = i64
     lib.vfm_foldin_solve_implicit_prior_f32.argtypes = [C.POINTER(ImplicitSolve), vp, vp]
     lib.vfm_foldin_solve_implicit_prior_f32.restype = C.c_int
+    lib.vfm_implicit_solve_weights_workspace_bytes.argtypes = [i64, i64, i32, i32]
+    lib.vfm_implicit_solve_weights_workspace_bytes.restype = i64
+    lib.vfm_foldin_solve_implicit_weights_f32.argtypes = [C.POINTER(ImplicitSolve), vp, vp, vp]
+    lib.vfm_foldin_solve_implicit_weights_f32.restype = C.c_int
     lib.vfm_elicit_bound_f32.argtypes = [C.POINTER(ElicitBound), vp]
     lib.vfm_elicit_bound_f32.restype = C.c_int
     lib.vfm_elicit_bound_workspace_bytes.argtypes = [i64, i64, i64, i64, i32, i32, i32]

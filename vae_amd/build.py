@@ -103,16 +103,17 @@ _UNITS = [("vfm_abi.hip", "", _EXACT), ("vfm_index.hip", "", []), ("vfm_variants
           ("csrc_rank/vfm_foldin_bound_split.hip", "", _EXACT),
           # implicit-feedback solves (include/vfm_implicit.h): the split solve's tile assembly over a field's whole
           # catalog and the exact fold-in's factorisation and rounding (csrc_rank/vfm_foldin_solve_body.hpp), hence its
-          # flag; the unit holds the solve under a field prior as well (include/vfm_implicit_prior.h)
+          # flag; the unit holds the solve under a field prior (include/vfm_implicit_prior.h) and with a weight per
+          # observed row (include/vfm_implicit_weights.h) as well
           ("csrc_rank/vfm_implicit.hip", "", _EXACT)]
 RANK_DIR = os.path.join(HERE, "csrc_rank")
 VAR_DIR = os.path.join(HERE, "csrc_var")
 # the public headers beside include/vfm_hip.h (vfm_foldin_ops.cpp holds the ops of foldin, sweep, bound_sweep, prior,
-# bound_prior, implicit, implicit_prior and vfm_bound.h's fold-in; vfm_elicit_ops.cpp holds vfm_bound.h's session and, with vfm_design_ops.cpp,
+# bound_prior, implicit, implicit_prior, implicit_weights and vfm_bound.h's fold-in; vfm_elicit_ops.cpp holds vfm_bound.h's session and, with vfm_design_ops.cpp,
 # the ops of elicit_prior)
 PUBLIC_HDRS = tuple(os.path.join(ROOT, "include", f"vfm_{n}.h")
                     for n in ("rank", "foldin", "elicit", "design", "variant_step", "sweep", "bound", "bound_sweep", "prior",
-                              "bound_prior", "elicit_prior", "implicit", "implicit_prior"))
+                              "bound_prior", "elicit_prior", "implicit", "implicit_prior", "implicit_weights"))
 # the TORCH_LIBRARY fragments linked into the shim beside csrc/vfm_torch_ops.cpp, and the header they share: host C++
 # only, so it is no source of libvfm_hip.so.  One file per family
 OPS_SOURCES = tuple(os.path.join(RANK_DIR, f"vfm_{n}_ops.cpp") for n in ("rank", "foldin", "elicit", "design"))

@@ -1,8 +1,8 @@
 // vfm_foldin_ops.cpp -- the fold-in family of torch.ops.vfm_hip: foldin (include/vfm_foldin.h), foldin_solve and
 // foldin_solve_split (vfm_foldin.h, vfm_sweep.h), their *_prior forms (vfm_prior.h), foldin_bound and foldin_bound_split
 // (vfm_bound.h, vfm_bound_sweep.h), their *_prior forms (vfm_bound_prior.h), the five *_workspace_bytes, implicit_base
-// and foldin_solve_implicit with their size functions (vfm_implicit.h) and foldin_solve_implicit_prior
-// (vfm_implicit_prior.h).  Like vfm_rank_ops.cpp this TORCH_LIBRARY fragment
+// and foldin_solve_implicit with their size functions (vfm_implicit.h), foldin_solve_implicit_prior
+// (vfm_implicit_prior.h) and foldin_solve_implicit_weights (vfm_implicit_weights.h).  Like vfm_rank_ops.cpp this TORCH_LIBRARY fragment
 // only validates tensors, takes the current HIP stream of the tensors' device and forwards raw pointers; all arithmetic
 // is in the HIP kernels.  Every solve is its parts (vfm_ops_common.hpp) plus its own scalars plus one call.
 #include "vfm_ops_common.hpp"
@@ -13,6 +13,7 @@
 #include "vfm_foldin.h"
 #include "vfm_implicit.h"
 #include "vfm_implicit_prior.h"
+#include "vfm_implicit_weights.h"
 #include "vfm_prior.h"
 #include "vfm_sweep.h"
 
@@ -275,6 +276,24 @@ void foldin_solve_implicit_prior(const Tensor& entities, const optional<Tensor>&
   check(vfm_foldin_solve_implicit_prior_f32(&p, prior_of(prior, p.d), stream_of(y)), "vfm_foldin_solve_implicit_prior_f32");
 }
 
+// prior: the folded field's, or none for N(0, 1).  weights [R]: a weight per observed row, in y's order; there is no w1
+void foldin_solve_implicit_weights(const Tensor& entities, const optional<Tensor>& row_ptr,
+                                   const optional<Tensor>& chunk_ptr, const optional<Tensor>& chunks, const Tensor& y,
+                                   const Tensor& partner, const Tensor& base, Tensor entity, Tensor bias,
+                                   const Tensor& scalars, Tensor workspace, Tensor loss, const optional<Tensor>& prior,
+                                   const Tensor& weights, int64_t lo, int64_t n, int64_t flags, int64_t lds_dim,
+                                   double kl_weight, double w0) {
+  vfm_implicit_solve_t p;
+  // (w1 = w0: a call without rows has no weights array to point at and runs the call of one w1, which reads none)
+  fill_implicit_solve(p, entities, row_ptr, chunk_ptr, chunks, y, partner, base, entity, bias, scalars, workspace, loss,
+                      lo, n, flags, lds_dim, kl_weight, w0, w0);
+  TORCH_CHECK(dev_tensor(weights, at::kFloat, "weights").numel() == y.numel(), "weights [R] with y [R]");
+  c10::hip::HIPGuard guard(y.get_device());
+  check(vfm_foldin_solve_implicit_weights_f32(&p, given(prior) ? prior_of(*prior, p.d) : nullptr,
+                                              p.R > 0 ? weights.data_ptr<float>() : nullptr, stream_of(y)),
+        "vfm_foldin_solve_implicit_weights_f32");
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(vfm_hip, m) {
@@ -340,4 +359,9 @@ TORCH_LIBRARY_FRAGMENT(vfm_hip, m) {
         "Tensor(c!) workspace, Tensor(d!) loss, Tensor prior, int lo, int n, int flags, int lds_dim, float kl_weight, "
         "float w0, float w1) -> ()",
         &foldin_solve_implicit_prior);
+  m.def("foldin_solve_implicit_weights(Tensor entities, Tensor? row_ptr, Tensor? chunk_ptr, Tensor? chunks, Tensor y, "
+        "Tensor partner, Tensor base, Tensor(a!) entity_params, Tensor(b!) bias_params, Tensor scalars, "
+        "Tensor(c!) workspace, Tensor(d!) loss, Tensor? prior, Tensor weights, int lo, int n, int flags, int lds_dim, "
+        "float kl_weight, float w0) -> ()",
+        &foldin_solve_implicit_weights);
 }

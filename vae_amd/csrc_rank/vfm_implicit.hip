@@ -25,6 +25,14 @@
 // vectors (lds_doubles_prior), H = kl diag(lam) + ..., b += kl lam m, sigma_c^2 = kl / (kl lam_c + prec SB'_c) and the KL
 // of the loss is to that prior; at m = 0, lam = 1 every expression rounds as with PRIOR off.  The base and the chunk pass do
 // not depend on the prior; the instantiation without it is the parent's, unchanged.
+//
+// vfm_foldin_solve_implicit_weights_f32 (include/vfm_implicit_weights.h) is the WROW = true instantiation of
+// k_implicit_chunks and k_implicit_solve: observed row r has the weight w[r] (read where y[r] is, under the same clamps)
+// and g_r = w[r] - w0 in fp64.  The share of the observed rows is then a weighted one -- share_of() scales the four u_i
+// of a row by g_r before the 16 products of its tile, coord_sums() adds g_r A, g_r (A + M^2) and, for coordinate 0,
+// g_r, phase B of the row-list form adds g_r, g_r M_i and g_r M_i M_j -- and the solve forms w0 base + share where it
+// forms w0 base + dw share without it.  Rows and chunks are walked in the same order.  Everything of WROW sits under
+// `if constexpr`: the instantiations without it are the parent's, unchanged, and PRIOR combines with it.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -34,6 +42,7 @@
 #include "vfm_args.hpp"
 #include "vfm_implicit.h"
 #include "vfm_implicit_prior.h"
+#include "vfm_implicit_weights.h"
 #include "vfm_launch.hpp"            // launch_status
 
 namespace vfm {
@@ -62,6 +71,7 @@ struct ImpArgs {
   float* loss;
   SolveSlabs sl;
   const float* prior;                    // [2, d + 1] mean | precision of the folded field (PRIOR instantiation only)
+  const float* w;                        // [R] weight of each observed row, >= w0 (WROW instantiations only)
 };
 
 __host__ __device__ inline int64_t imp_doubles(int d) { return tri(d + 1) + 3 * (int64_t)(d + 1) + 1; }
@@ -82,7 +92,9 @@ struct CatalogRows {
   __device__ __forceinline__ double q(int64_t, double cm, double cv) const { return cm * cm + cv; }
 };
 
-// the observed rows [r0, r0 + n) of one entity: a partner outside the base's range is -1
+// the observed rows [r0, r0 + n) of one entity: a partner outside the base's range is -1.  WROW: row r weighs s.w[r0 + r]
+// in place of s.w1, and g(r) is what it weighs above an unobserved pair
+template <bool WROW>
 struct ObservedRows {
   const ImpArgs& s;
   int64_t r0;
@@ -90,17 +102,28 @@ struct ObservedRows {
     const int64_t j = s.partner[r0 + r];
     return j >= s.lo && j < s.lo + s.n ? j : -1;
   }
+  __device__ __forceinline__ double g(int64_t r) const { return (double)s.w[r0 + r] - s.w0; }
   __device__ __forceinline__ double t(int64_t r, double cm) const {
-    return s.w1 * (double)s.y[r0 + r] - (s.w1 - s.w0) * cm;
+    if constexpr (WROW) return (double)s.w[r0 + r] * (double)s.y[r0 + r] - g(r) * cm;
+    else return s.w1 * (double)s.y[r0 + r] - (s.w1 - s.w0) * cm;
   }
   __device__ __forceinline__ double q(int64_t r, double cm, double cv) const {
     const double res = (double)s.y[r0 + r] - cm;
-    return s.w1 * res * res - s.w0 * cm * cm + (s.w1 - s.w0) * cv;
+    if constexpr (WROW) {
+      // the two squares in statements of their own: neither fuses into the difference, so a row of weight w0 and
+      // target 0 adds exactly 0 (res = -cm) and an entity of such rows is the entity without rows, bit for bit
+      const double a = (double)s.w[r0 + r] * res * res;
+      const double b = s.w0 * cm * cm;
+      return a - b + g(r) * cv;
+    } else {
+      return s.w1 * res * res - s.w0 * cm * cm + (s.w1 - s.w0) * cv;
+    }
   }
 };
 
-// coordinate c's sums over n rows in order: SA, SB, bM = sum t u_c and, for c = 0, tt = sum q; false when a row is bad
-template <int LINK, class Rows>
+// coordinate c's sums over n rows in order: SA, SB, bM = sum t u_c and, for c = 0, tt = sum q; false when a row is bad.
+// WROW: SA = sum g A, SB = sum g (A + M^2) and, for c = 0, SB = sum g over every row (bad or not, as the row count is)
+template <int LINK, bool WROW = false, class Rows>
 __device__ __forceinline__ bool coord_sums(const ImpArgs& s, const Rows& rows, int64_t n, int c, double& SA, double& SB,
                                            double& bM, double& tt) {
 #pragma clang fp contract(on)
@@ -109,6 +132,7 @@ __device__ __forceinline__ bool coord_sums(const ImpArgs& s, const Rows& rows, i
   SA = SB = bM = tt = 0.;
   if (c == 0) {
     for (int64_t r = 0; r < n; ++r) {
+      if constexpr (WROW) SB += rows.g(r);
       const int64_t j = rows.id(r);
       if (j < 0) { ok = false; continue; }
       double cm, cv;
@@ -116,7 +140,7 @@ __device__ __forceinline__ bool coord_sums(const ImpArgs& s, const Rows& rows, i
       bM += rows.t(r, cm);
       tt += rows.q(r, cm, cv);
     }
-    SB = (double)n;
+    if constexpr (!WROW) SB = (double)n;
   } else {
     for (int64_t r = 0; r < n; ++r) {
       const int64_t j = rows.id(r);
@@ -124,16 +148,23 @@ __device__ __forceinline__ bool coord_sums(const ImpArgs& s, const Rows& rows, i
       const float* row = s.entity + j * 2 * (int64_t)d;
       const double M = row[c - 1], sg = link_d<LINK>(row[d + c - 1]), A = sg * sg;
       const double cm = (double)s.scal[1] + (double)s.bias[j * 2];
-      SA += A;
-      SB += A + M * M;
+      if constexpr (WROW) {
+        const double g = rows.g(r);
+        SA += g * A;
+        SB += g * (A + M * M);
+      } else {
+        SA += A;
+        SB += A + M * M;
+      }
       bM += rows.t(r, cm) * M;
     }
   }
   return ok;
 }
 
-// the slab P of n rows, by the whole workgroup: [triangle | SA | SB | sum t u | sum q], NaN where a row is bad
-template <int LINK, class Rows>
+// the slab P of n rows, by the whole workgroup: [triangle | SA | SB | sum t u | sum q], NaN where a row is bad.
+// WROW: the triangle of sum g u u^T, the four u_i of a row scaled by g once
+template <int LINK, bool WROW = false, class Rows>
 __device__ __forceinline__ void share_of(const ImpArgs& s, const Rows& rows, int64_t n, double* P) {
 #pragma clang fp contract(on)
   const int tid = threadIdx.x;
@@ -170,6 +201,11 @@ __device__ __forceinline__ void share_of(const ImpArgs& s, const Rows& rows, int
         ui[t] = i0 + t == 0 ? 1.0 : i0 + t < d1 ? vi : 0.0;
         uj[t] = j0 + t == 0 ? 1.0 : j0 + t < d1 ? vj : 0.0;
       }
+      if constexpr (WROW) {
+        const double g = rows.g(r);
+#pragma unroll
+        for (int t = 0; t < TL; ++t) ui[t] *= g;
+      }
 #pragma unroll
       for (int u = 0; u < TL; ++u)
 #pragma unroll
@@ -187,7 +223,7 @@ __device__ __forceinline__ void share_of(const ImpArgs& s, const Rows& rows, int
   // ---- the row sums of each coordinate
   for (int c = tid; c < d1; c += FB) {
     double SA, SB, bM, tt;
-    const bool ok = coord_sums<LINK>(s, rows, n, c, SA, SB, bM, tt);
+    const bool ok = coord_sums<LINK, WROW>(s, rows, n, c, SA, SB, bM, tt);
     P[nt + c] = ok ? SA : qnan;
     P[nt + d1 + c] = ok || c == 0 ? SB : qnan;                     // (the row count stays: sigma_w is a function of it)
     P[nt + 2 * d1 + c] = ok ? bM : qnan;
@@ -219,16 +255,16 @@ __device__ __forceinline__ void chunk_rows_of(const ImpArgs& s, int64_t q, int64
   n = min(max(s.chunks[q * 3 + 2], (int64_t)0), s.R - r0);
 }
 
-template <int LINK>
+template <int LINK, bool WROW>
 __global__ __launch_bounds__(FB) void k_implicit_chunks(const ImpArgs s) {
   for (int64_t q = blockIdx.x; q < s.n_chunks; q += gridDim.x) {
     int64_t r0, n;
     chunk_rows_of(s, q, r0, n);
-    share_of<LINK>(s, ObservedRows{s, r0}, n, s.part + q * s.part_elems);
+    share_of<LINK, WROW>(s, ObservedRows<WROW>{s, r0}, n, s.part + q * s.part_elems);
   }
 }
 
-template <int LINK, bool PRIOR>
+template <int LINK, bool PRIOR, bool WROW>
 __global__ __launch_bounds__(FB) void k_implicit_solve(const ImpArgs s) {
 #pragma clang fp contract(on)
   extern __shared__ double sm_all[];
@@ -273,7 +309,7 @@ __global__ __launch_bounds__(FB) void k_implicit_solve(const ImpArgs s) {
       r0 = min(max(s.row_ptr[g], (int64_t)0), s.R);
       n = min(max(s.row_ptr[g + 1] - r0, (int64_t)0), s.R - r0);
     }
-    const ObservedRows rows{s, r0};
+    const ObservedRows<WROW> rows{s, r0};
 
     // ---- A: the sums of each coordinate, D, b and SB'
     for (int c = tid; c < d1; c += FB) {
@@ -286,12 +322,21 @@ __global__ __launch_bounds__(FB) void k_implicit_solve(const ImpArgs s) {
           bM += V[2 * d1 + c];
           if (c == 0) tt += V[3 * d1];
         }
-      } else if (!coord_sums<LINK>(s, rows, n, c, SA, SB, bM, tt)) {
+      } else if (!coord_sums<LINK, WROW>(s, rows, n, c, SA, SB, bM, tt)) {
         SA = bM = tt = qnan;
         if (c > 0) SB = qnan;
       }
       const double b = prec * (w0 * B[nt + 2 * d1 + c] + bM);
-      if constexpr (PRIOR) {
+      if constexpr (WROW) {              // (the share is weighted already: w0 base + share)
+        if constexpr (PRIOR) {
+          const double kll = kl * pr[d1 + c];
+          Dd[c] = kll + prec * (w0 * B[nt + c] + SA);
+          yv[c] = b + kll * pr[c];
+        } else {
+          Dd[c] = kl + prec * (w0 * B[nt + c] + SA);
+          yv[c] = b;
+        }
+      } else if constexpr (PRIOR) {
         const double kll = kl * pr[d1 + c];
         Dd[c] = kll + prec * (w0 * B[nt + c] + dw * SA);
         yv[c] = b + kll * pr[c];
@@ -300,7 +345,8 @@ __global__ __launch_bounds__(FB) void k_implicit_solve(const ImpArgs s) {
         yv[c] = b;
       }
       bs[c] = b;                         // (b of the data: the loss takes the prior's part through its KL)
-      SBd[c] = w0 * B[nt + d1 + c] + dw * SB;
+      if constexpr (WROW) SBd[c] = w0 * B[nt + d1 + c] + SB;
+      else SBd[c] = w0 * B[nt + d1 + c] + dw * SB;
       if (c == 0) tts = w0 * B[nt + 3 * d1] + tt;
     }
     __syncthreads();
@@ -313,18 +359,28 @@ __global__ __launch_bounds__(FB) void k_implicit_solve(const ImpArgs s) {
       if (s.chunk_ptr) {
         for (int64_t q = c0; q < c1; ++q) acc += s.part[q * s.part_elems + p];
       } else if (i == 0) {
-        acc = (double)n;
+        if constexpr (WROW) {
+          for (int64_t r = 0; r < n; ++r) acc += rows.g(r);
+        } else {
+          acc = (double)n;
+        }
       } else {
         bool bad = false;
         for (int64_t r = 0; r < n; ++r) {
           const int64_t k = rows.id(r);
           if (k < 0) { bad = true; continue; }
           const float* M = s.entity + k * 2 * (int64_t)d;
-          acc += j == 0 ? (double)M[i - 1] : (double)M[i - 1] * (double)M[j - 1];
+          if constexpr (WROW) {
+            const double gM = rows.g(r) * (double)M[i - 1];
+            acc += j == 0 ? gM : gM * (double)M[j - 1];
+          } else {
+            acc += j == 0 ? (double)M[i - 1] : (double)M[i - 1] * (double)M[j - 1];
+          }
         }
         if (bad) acc = qnan;
       }
-      Hm[p] = prec * (w0 * B[p] + dw * acc) + (i == j ? Dd[i] : 0.0);
+      if constexpr (WROW) Hm[p] = prec * (w0 * B[p] + acc) + (i == j ? Dd[i] : 0.0);
+      else Hm[p] = prec * (w0 * B[p] + dw * acc) + (i == j ? Dd[i] : 0.0);
     }
     __syncthreads();
 
@@ -375,7 +431,7 @@ inline int64_t imp_part_bytes(int64_t n_chunks, int d) { return round_up(n_chunk
 }  // namespace
 }  // namespace vfm
 
-static int implicit_solve_call(const vfm_implicit_solve_t* p, const float* prior, void* stream);
+static int implicit_solve_call(const vfm_implicit_solve_t* p, const float* prior, const float* weights, void* stream);
 
 extern "C" {
 
@@ -435,17 +491,27 @@ int64_t vfm_implicit_solve_prior_workspace_bytes(int64_t E, int64_t n_chunks, in
 }
 
 int vfm_foldin_solve_implicit_f32(const vfm_implicit_solve_t* p, void* stream) {
-  return implicit_solve_call(p, nullptr, stream);
+  return implicit_solve_call(p, nullptr, nullptr, stream);
 }
 
 int vfm_foldin_solve_implicit_prior_f32(const vfm_implicit_solve_t* p, const float* prior, void* stream) {
-  return implicit_solve_call(p, prior, stream);
+  return implicit_solve_call(p, prior, nullptr, stream);
+}
+
+int64_t vfm_implicit_solve_weights_workspace_bytes(int64_t E, int64_t n_chunks, int32_t d, int32_t lds_dim) {
+  return vfm_implicit_solve_workspace_bytes(E, n_chunks, d, lds_dim);  // (the weights are the caller's array)
+}
+
+int vfm_foldin_solve_implicit_weights_f32(const vfm_implicit_solve_t* p, const float* prior, const float* weights,
+                                          void* stream) {
+  return implicit_solve_call(p, prior, weights, stream);
 }
 
 }  // extern "C"
 
-// both entry points: prior == NULL is vfm_foldin_solve_implicit_f32
-static int implicit_solve_call(const vfm_implicit_solve_t* p, const float* prior, void* stream) {
+// the three entry points: prior == NULL is vfm_foldin_solve_implicit_f32, weights == NULL the call of one w1; with
+// weights p->w1 is neither read nor checked
+static int implicit_solve_call(const vfm_implicit_solve_t* p, const float* prior, const float* weights, void* stream) {
   using vfm::fail;
   if (!p) return fail(VFM_E_INVALID, "vfm_foldin_solve_implicit_f32: NULL argument struct");
   if (p->T < 1) return fail(VFM_E_INVALID, "T < 1");
@@ -459,7 +525,7 @@ static int implicit_solve_call(const vfm_implicit_solve_t* p, const float* prior
   if (!(p->kl_weight > 0.f) || !(p->kl_weight <= 3.0e38f))
     return fail(VFM_E_INVALID, "kl_weight must be > 0 and finite (the prior is what makes the system positive definite)");
   if (!(p->w0 > 0.f) || !(p->w0 <= 3.0e38f)) return fail(VFM_E_INVALID, "w0 must be > 0 and finite");
-  if (!(p->w1 >= p->w0) || !(p->w1 <= 3.0e38f)) return fail(VFM_E_INVALID, "w1 must be >= w0 and finite");
+  if (!weights && (!(p->w1 >= p->w0) || !(p->w1 <= 3.0e38f))) return fail(VFM_E_INVALID, "w1 must be >= w0 and finite");
   if (p->E == 0) return 0;
   if ((p->row_ptr != nullptr) == (p->chunk_ptr != nullptr))
     return fail(VFM_E_INVALID, "one of row_ptr (row-list form) and chunk_ptr (chunk form) must be given");
@@ -477,12 +543,13 @@ static int implicit_solve_call(const vfm_implicit_solve_t* p, const float* prior
   const bool sp = (p->flags & VFM_FLAG_LINK_SOFTPLUS) != 0;
   vfm::ImpArgs s = {};
   s.E = p->E; s.R = p->R; s.T = p->T; s.n_chunks = p->n_chunks; s.lo = p->lo; s.n = p->n; s.d = p->d;
-  s.kl = p->kl_weight; s.w0 = p->w0; s.w1 = p->w1;
+  s.kl = p->kl_weight; s.w0 = p->w0; s.w1 = weights ? p->w0 : p->w1;
   s.ent = p->entities; s.row_ptr = p->row_ptr; s.chunk_ptr = p->chunk_ptr; s.chunks = p->chunks;
   s.partner = p->partner; s.y = p->y; s.base = p->base;
   s.part = (double*)p->workspace; s.part_elems = vfm::imp_doubles(p->d);
   s.entity = p->entity_params; s.bias = p->bias_params; s.scal = p->scalars; s.loss = p->out_loss;
   s.prior = prior;
+  s.w = weights;
   const int64_t gcap = (int64_t)1 << 20;
   const unsigned grid_e = vfm::place_slabs(p->d, p->lds_dim, p->E, (char*)p->workspace + vfm::imp_part_bytes(p->n_chunks, p->d),
                                            gcap, s.sl);
@@ -491,13 +558,18 @@ static int implicit_solve_call(const vfm_implicit_solve_t* p, const float* prior
   if (p->n_chunks > 0) {
     const unsigned grid_c = (unsigned)(p->n_chunks < gcap ? p->n_chunks : gcap);
     vfm::for_link(sp, [&](auto link) {
-      hipLaunchKernelGGL(vfm::k_implicit_chunks<decltype(link)::value>, dim3(grid_c), dim3(vfm::FB), 0, st, s);
+      constexpr int L = decltype(link)::value;
+      if (weights) hipLaunchKernelGGL((vfm::k_implicit_chunks<L, true>), dim3(grid_c), dim3(vfm::FB), 0, st, s);
+      else hipLaunchKernelGGL((vfm::k_implicit_chunks<L, false>), dim3(grid_c), dim3(vfm::FB), 0, st, s);
     });
     if (int rc = launch_status("k_implicit_chunks")) return rc;
   }
   vfm::for_link(sp, [&](auto link) {
-    if (prior) vfm::launch_lds(vfm::k_implicit_solve<decltype(link)::value, true>, grid_e, shm, st, s);
-    else vfm::launch_lds(vfm::k_implicit_solve<decltype(link)::value, false>, grid_e, shm, st, s);
+    constexpr int L = decltype(link)::value;
+    if (prior && weights) vfm::launch_lds(vfm::k_implicit_solve<L, true, true>, grid_e, shm, st, s);
+    else if (prior) vfm::launch_lds(vfm::k_implicit_solve<L, true, false>, grid_e, shm, st, s);
+    else if (weights) vfm::launch_lds(vfm::k_implicit_solve<L, false, true>, grid_e, shm, st, s);
+    else vfm::launch_lds(vfm::k_implicit_solve<L, false, false>, grid_e, shm, st, s);
   });
   return launch_status("k_implicit_solve");
 }

@@ -1460,7 +1460,7 @@ class VFM(nn.Module):
     @torch.no_grad()
     def fold_in_implicit(self, X, y, field: int = 0, *, w0: float, w1: float = 1.0, kl_weight: float = 1.0,
                          entities=None, split_rows="auto", chunk_rows: int = 2048, max_workspace_bytes: int = 1 << 30,
-                         priors=STANDARD_PRIOR):
+                         priors=STANDARD_PRIOR, weights=None):
         """fold_in_exact over EVERY (user, item) pair of a two-field 'reg' model, the implicit-feedback least-squares
         objective (Hu, Koren & Volinsky; include/vfm_implicit.h; DESIGN.md §4 "Implicit sweeps"): the rows of X are the
         observed pairs, with target y and weight w1; every other pair of the folded entity with the partner field has
@@ -1480,31 +1480,37 @@ class VFM(nn.Module):
         carries the KL to it; an entity without observed rows gets the base-only optimum under the prior.  At (0, 1)
         the rows and losses are those of the call without priors=, bit for bit.  priors= takes a GroupPriors or is
         left out: an explicit None is a TypeError.
+        weights (a 1-D floating tensor, one per row of X, e.g. sweep.hkv_weights(counts, w0, alpha)): row r weighs
+        weights[r] in place of the one w1, the per-pair confidence of Hu, Koren & Volinsky (include/vfm_implicit_weights.h;
+        DESIGN.md §4 "Weighted implicit sweeps").  ValueError, before a GPU is needed, for another shape or dtype, a
+        weight that is not finite or below w0 once rounded to fp32, and weights= beside w1 != 1.0.  None: the call
+        as it was.  Constant weights give the optimum of the call with that w1, not its bytes.
         Returns dict(entities [E] int64 ascending, loss [E] fp32 = L_e over all partners at the returned parameters,
         rows [E] int64 = observed rows)."""
         from . import sweep
         ents, loss, rows = sweep.run_implicit(self, X, y, field, w0, w1, kl_weight, entities, split_rows, chunk_rows,
-                                              max_workspace_bytes, priors=_implicit_priors(priors))
+                                              max_workspace_bytes, priors=_implicit_priors(priors), weights=weights)
         return {"entities": ents, "loss": loss, "rows": rows}
 
     @torch.no_grad()
     def implicit_objective(self, X, y, *, w0: float, w1: float = 1.0, kl_weight: float = 1.0,
-                           priors=STANDARD_PRIOR) -> float:
+                           priors=STANDARD_PRIOR, weights=None) -> float:
         """J_imp of fit_implicit at the current parameters (DESIGN.md §4 "Implicit sweeps"): over every (user, item)
         pair w [1/2 prec ((y - E pred)^2 + Var pred) - 1/2 log prec + 1/2 log 2 pi] with (w, y) = (w1, y_r) at an
         observed pair and (w0, 0) elsewhere, plus kl_weight times the KL to N(0, 1) of every entity of both fields and
         of the global bias.  In fp64 on the device through the Gram form: the all-pairs sums are closed forms of the two
         fields' Grams and first moments, corrected at the observed rows.  y None: all ones.  priors (a
         sweep.GroupPriors): the KL of every entity of both fields, observed or not, is to its field's prior; the global
-        bias keeps N(0, 1)."""
+        bias keeps N(0, 1).  weights (one per row of X, as in fold_in_implicit): the observed pair of row r weighs
+        weights[r] in place of w1."""
         from . import sweep
-        return sweep.implicit_objective(self, X, y, w0, w1, kl_weight, _implicit_priors(priors))
+        return sweep.implicit_objective(self, X, y, w0, w1, kl_weight, _implicit_priors(priors), weights=weights)
 
     @torch.no_grad()
     def fit_implicit(self, X, y=None, n_sweeps: int = 10, *, w0: float, w1: float = 1.0, kl_weight: float = 1.0,
                      update_scalars: bool = True, split_rows="auto", chunk_rows: int = 2048, on_step=None,
                      tol: Optional[float] = None, priors=STANDARD_PRIOR, learn_priors: bool = False,
-                     learn_mean: bool = True, prec_min: float = 1e-4, prec_max: float = 1e4):
+                     learn_mean: bool = True, prec_min: float = 1e-4, prec_max: float = 1e4, weights=None):
         """fit_exact on the implicit-feedback objective J_imp (implicit_objective): exact coordinate ascent in which a
         sweep solves every entity of field 0, then of field 1 (fold_in_implicit over the whole id range: entities
         without observed rows are solved and counted too), then sets the global bias and after it the precision to
@@ -1521,11 +1527,16 @@ class VFM(nn.Module):
         the mean kept when learn_mean=False and the precision clamped to [prec_min, prec_max]; on_step is then also
         called with ("prior", f).  learn_priors=True without priors= starts them at N(0, 1).  The result then holds
         "priors" and "clamped" ({field: coordinates at which a clamp bound, summed over the sweeps}), as fit_exact's.
-        A model trained this way interviews under the same priors= in the exact and design sessions."""
+        A model trained this way interviews under the same priors= in the exact and design sessions.
+
+        weights (one per row of X, as in fold_in_implicit; DESIGN.md §4 "Weighted implicit sweeps"): every observed
+        pair carries its own confidence in place of w1 -- play counts through sweep.hkv_weights(counts, w0, alpha)
+        -- in the entity blocks, the scalar blocks and J_imp alike, so every block stays the exact minimiser of the
+        J_imp that is reported.  Repeated (user, item) pairs stay an error: add their counts up first."""
         from . import sweep
         return sweep.fit_implicit(self, X, y, n_sweeps, w0, w1, kl_weight, update_scalars, split_rows, chunk_rows,
                                   on_step, tol, priors=_implicit_priors(priors), learn_priors=learn_priors,
-                                  learn_mean=learn_mean, prec_min=prec_min, prec_max=prec_max)
+                                  learn_mean=learn_mean, prec_min=prec_min, prec_max=prec_max, weights=weights)
 
     @torch.no_grad()
     def bound_objective(self, X, y, kl_weight: float = 1.0, priors=None) -> float:

@@ -36,6 +36,10 @@ include/vfm_implicit.h): an observed pair with its target and weight w1, every o
 and under a GroupPriors (include/vfm_implicit_prior.h; DESIGN.md §4, "Hierarchical implicit sweeps") the same plan solves
 under the folded field's prior (vfm_foldin_solve_implicit_prior_f32), J_imp carries every entity's KL to its field's prior
 and the prior block (update_prior) runs over the field's whole id range: an entity without observed rows is in J_imp.
+With weights= (include/vfm_implicit_weights.h; DESIGN.md §4, "Weighted implicit sweeps") every observed row carries a
+weight of its own in place of the one w1 (hkv_weights: Hu, Koren & Volinsky's confidence from counts): the plan carries
+the weights into its row order as it carries the targets, the solves are vfm_foldin_solve_implicit_weights_f32 and
+implicit_sums corrects the all-pairs sums with each row's own weight.
 """
 from __future__ import annotations
 
@@ -181,6 +185,7 @@ class SweepPlan:
             per_id = torch.bincount(col - lo, minlength=hi - lo)
             key = col + (per_id[col - lo] > self.threshold).to(torch.int64) * model.T      # (heavy ids sort last)
         order = torch.sort(key, stable=True).indices
+        self.order = order                                    # (what else is per row follows it: ImplicitPlan's weights)
         xs, self.ys = x[order].contiguous(), y[order].contiguous()
         self.ents, counts = torch.unique_consecutive(xs[:, field], return_counts=True)
         self.ents = self.ents.contiguous()
@@ -633,10 +638,54 @@ def fit_bound(model, X, y, n_sweeps=10, kl_weight=1.0, n_iters=8, fields=None, u
 # ---------------------------------------------------------------------------------------------------------------------
 # implicit feedback: every (user, item) pair is a row ("Implicit sweeps"; include/vfm_implicit.h)
 # ---------------------------------------------------------------------------------------------------------------------
-def check_implicit_args(model, X, y, w0, w1, kl_weight):
+def hkv_weights(counts, w0, alpha, log_eps=None):
+    """The confidence of Hu, Koren & Volinsky as weights= of the implicit calls: w0 (1 + alpha counts), or with log_eps
+    w0 (1 + alpha log1p(counts / log_eps)), in fp32 (w0 rounded to fp32 first, as the calls round it, so that a count of
+    0 weighs exactly w0).  counts: non-negative play counts, dwell times, quantities, one per observed pair.  A
+    (user, item) pair that occurs twice stays an error of the implicit calls: adding up the counts of repeated pairs
+    is the caller's job.  ValueError for a negative or non-finite count, alpha < 0 and log_eps <= 0."""
+    c = torch.as_tensor(counts).to(torch.float64)
+    alpha = float(alpha)
+    w0 = float(torch.tensor(float(w0), dtype=torch.float32))
+    if not (math.isfinite(w0) and w0 > 0.0):
+        raise ValueError("w0 must be > 0 and finite")
+    if not (math.isfinite(alpha) and alpha >= 0.0):
+        raise ValueError("alpha must be >= 0 and finite")
+    if c.numel() and not (bool(torch.isfinite(c).all()) and float(c.min()) >= 0.0):
+        raise ValueError("counts must be >= 0 and finite")
+    if log_eps is not None:
+        log_eps = float(log_eps)
+        if not (math.isfinite(log_eps) and log_eps > 0.0):
+            raise ValueError("log_eps must be > 0 and finite")
+        c = torch.log1p(c / log_eps)
+    return (w0 * (1.0 + alpha * c)).float()          # (>= w0: rounding to fp32 is monotone and w0 is an fp32 value)
+
+
+def _check_weights(weights, n_rows, w0, w1):
+    """weights= of an implicit call: a 1-D floating tensor of one weight per row of X, each finite and >= w0 once
+    rounded to fp32, and no w1 beside it."""
+    w = weights if isinstance(weights, torch.Tensor) else torch.as_tensor(weights)
+    if w.dim() != 1 or not w.dtype.is_floating_point or w.shape[0] != n_rows:
+        raise ValueError(f"weights must be a 1-D floating tensor with one weight per row of X ({n_rows})")
+    if w1 != 1.0:
+        raise ValueError("weights and w1 are two sources of an observed pair's weight: give one of them")
+    w = w.detach().float()
+    if w.numel() and not bool(torch.isfinite(w).all()):
+        raise ValueError("weights must be finite (in fp32)")
+    if w.numel() and float(w.min()) < w0:
+        raise ValueError("weights must be >= w0 (in fp32): an observed pair weighs at least what an unobserved one does")
+
+
+def _row_weights(model, weights):
+    """Checked weights= as the kernels take them: [R] fp32 on the model's device, in the order of X's rows."""
+    return None if weights is None else torch.as_tensor(weights).detach().to(model.device, torch.float32).contiguous()
+
+
+def check_implicit_args(model, X, y, w0, w1, kl_weight, weights=None):
     """Validate the rows and weights of an implicit call (no GPU needed): a two-field 'reg' model, kl_weight > 0, finite
-    weights with w1 >= w0 > 0, ids in their fields, distinct (user, item) pairs.  y None: all ones.  Returns
-    (x [R, 2] int64, y [R] fp32, w0, w1) on the model's device."""
+    weights with w1 >= w0 > 0, ids in their fields, distinct (user, item) pairs.  y None: all ones.  weights: None, or a
+    1-D floating tensor with a weight per row of X, finite and >= w0 in fp32, given with w1 left at 1.0 (_check_weights;
+    _row_weights moves it to the device).  Returns (x [R, 2] int64, y [R] fp32, w0, w1) on the model's device."""
     if model.output != "reg":
         raise ValueError("the implicit solves need a 'reg' model (Gaussian likelihood): the closed form they solve has none "
                          "for 'class'")
@@ -648,12 +697,14 @@ def check_implicit_args(model, X, y, w0, w1, kl_weight):
         raise ValueError("w0 and w1 must be finite")
     if not w0 > 0.0:
         raise ValueError("w0 must be > 0: it is the weight of every unobserved pair")
-    if w1 < w0:
+    if weights is None and w1 < w0:
         raise ValueError("w1 must be >= w0: an observed pair weighs at least what an unobserved one does")
     if y is None:
         n_rows = torch.as_tensor(X).shape[0] if torch.as_tensor(X).dim() else 0
         y = torch.ones(n_rows, dtype=torch.float32)
     x, y, _ = foldin.check_args(model, X, y, 0, "closed_form", 1, 0, 0.0, kl_weight)
+    if weights is not None:
+        _check_weights(weights, x.shape[0], w0, w1)
     if x.shape[0]:
         key = x[:, 0] * model.T + x[:, 1]
         if int(torch.unique(key).numel()) != x.shape[0]:
@@ -685,10 +736,11 @@ class ImplicitPlan:
     """What one (X, y, field) of an implicit solve needs and that does not depend on the parameters: a SweepPlan of the
     observed rows (its sort, its chunk table and its max_workspace_bytes grouping, the groups sized by
     vfm_implicit_solve_workspace_bytes), each row's partner id, and the entities without observed rows.  entities: None
-    (the field's whole id range) or sorted distinct ids; rows of other entities are left out."""
+    (the field's whole id range) or sorted distinct ids; rows of other entities are left out.  weights: None, or [R]
+    fp32 beside y; it goes through the entities= filter and into the plan's row order as y does (self.ws)."""
 
     def __init__(self, model, x, y, field, entities=None, split_rows="auto", chunk_rows=2048,
-                 max_workspace_bytes=MAX_WORKSPACE_BYTES, lds_dim=-1):
+                 max_workspace_bytes=MAX_WORKSPACE_BYTES, lds_dim=-1, weights=None):
         dev = x.device
         self.field, self.d, self.lds_dim = int(field), model.d, int(lds_dim)
         self.chunk_rows = check_chunk_rows(chunk_rows)
@@ -699,6 +751,7 @@ class ImplicitPlan:
         else:
             keep = torch.isin(x[:, field], entities)
             x, y = x[keep].contiguous(), y[keep].contiguous()
+            weights = None if weights is None else weights[keep]
         size = _lib.load().vfm_implicit_solve_workspace_bytes
         self.obs = SweepPlan(model, x, y, field, split_rows, chunk_rows, max_workspace_bytes, lds_dim,
                              split_bytes=lambda n_chunks, n_heavy, n_ops, d, lds: size(n_heavy, n_chunks, d, lds))
@@ -706,6 +759,7 @@ class ImplicitPlan:
         self.partner = (p.op_x[:, 1 - field][p.row_op].contiguous() if p.E else
                         torch.zeros(0, dtype=torch.int64, device=dev))
         self.ys = p.ys if p.E else torch.zeros(0, dtype=torch.float32, device=dev)
+        self.ws = None if weights is None else weights[p.order].contiguous()
         self.empty = entities[~torch.isin(entities, p.ents)].contiguous()
         self.ents = torch.cat([p.ents, self.empty])
         self.counts = torch.cat([p.counts, torch.zeros_like(self.empty)])
@@ -722,12 +776,16 @@ class ImplicitPlan:
         o.implicit_base(*model._views(model._flat), ws, out, lo, hi - lo, self.chunk_rows, foldin._link_flags(model))
         return out
 
-    def run(self, model, kl_weight, w0, w1, prior=None):
+    def run(self, model, kl_weight, w0, w1, prior=None, weights=None):
         """Write the optimum of every entity of the plan into the model's tables: the base of the partner field, then
         the entities with few observed rows in one call, a call per group of heavy ones, and the entities without
         rows.  prior: the folded field's [2, d + 1] mean | precision on the device (GroupPriors.row); every one of the
         calls then solves under it (vfm_foldin_solve_implicit_prior_f32, include/vfm_implicit_prior.h); None: the
-        parent call itself.  Returns (entities [E] ascending, loss [E], rows [E])."""
+        parent call itself.  weights: what the plan was built with, None or the rows' weights; the plan holds them in
+        its own row order (self.ws) and every one of the calls is then vfm_foldin_solve_implicit_weights_f32
+        (include/vfm_implicit_weights.h), which has no w1.  Returns (entities [E] ascending, loss [E], rows [E])."""
+        if (weights is None) != (self.ws is None):
+            raise ValueError("weights belong to the plan: build the ImplicitPlan with the weights= that run() is given")
         dev, p = model.device, self.obs
         loss = torch.empty(self.E, dtype=torch.float32, device=dev)
         if self.E == 0:
@@ -743,7 +801,9 @@ class ImplicitPlan:
             n = o.implicit_solve_workspace_bytes(ents.numel(), 0 if tab is None else tab.shape[0], self.d, self.lds_dim)
             ws = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
             a = (ents, row_ptr, cptr, tab, self.ys, self.partner, base, *tables, ws, out)
-            if prior is None:
+            if self.ws is not None:
+                o.foldin_solve_implicit_weights(*a, prior, self.ws, *opts[:-1])
+            elif prior is None:
                 o.foldin_solve_implicit(*a, *opts)
             else:
                 o.foldin_solve_implicit_prior(*a, prior, *opts)
@@ -761,9 +821,10 @@ class ImplicitPlan:
 
 
 def run_implicit(model, X, y, field, w0, w1=1.0, kl_weight=1.0, entities=None, split_rows="auto", chunk_rows=2048,
-                 max_workspace_bytes=MAX_WORKSPACE_BYTES, lds_dim=-1, priors=None):
-    """VFM.fold_in_implicit: (entities [E] ascending, loss [E], rows [E]).  priors: under the folded field's prior."""
-    x, y, w0, w1 = check_implicit_args(model, X, y, w0, w1, kl_weight)
+                 max_workspace_bytes=MAX_WORKSPACE_BYTES, lds_dim=-1, priors=None, weights=None):
+    """VFM.fold_in_implicit: (entities [E] ascending, loss [E], rows [E]).  priors: under the folded field's prior.
+    weights: a weight per row of X in place of w1."""
+    x, y, w0, w1 = check_implicit_args(model, X, y, w0, w1, kl_weight, weights)
     check_priors(model, priors)
     if isinstance(field, bool) or not isinstance(field, int) or not 0 <= field < 2:
         raise ValueError("field must be 0 or 1")
@@ -774,16 +835,18 @@ def run_implicit(model, X, y, field, w0, w1=1.0, kl_weight=1.0, entities=None, s
     if int(max_workspace_bytes) < 0:
         raise ValueError("max_workspace_bytes must be >= 0")
     ops._need_cuda(model._flat, "the model's parameters")
-    plan = ImplicitPlan(model, x, y, field, entities, split_rows, chunk_rows, int(max_workspace_bytes), lds_dim)
-    return plan.run(model, kl_weight, w0, w1, _prior_row(model, priors, field))
+    weights = _row_weights(model, weights)
+    plan = ImplicitPlan(model, x, y, field, entities, split_rows, chunk_rows, int(max_workspace_bytes), lds_dim, weights)
+    return plan.run(model, kl_weight, w0, w1, _prior_row(model, priors, field), weights)
 
 
-def implicit_sums(model, x, y, w0, w1):
+def implicit_sums(model, x, y, w0, w1, weights=None):
     """The three weighted sums over ALL (user, item) pairs that J_imp and its scalar blocks need, as 0-dim fp64 tensors on
     the device: W = sum w, S1 = sum w (y - (E pred - m0)), S2 = sum w ((y - E pred)^2 + Var pred).  The all-pairs parts
     are closed forms of the two fields' Grams and first moments (E pred_ui = p_u . q_i with p_u = (1, mu_w,u, mu_u) and
     q_i = (m0 + mu_w,i, 1, mu_i), so sum_ui (E pred)^2 = <sum_u p p^T, sum_i q q^T>), O((N + M) d^2) in torch fp64 from
-    the tables; the observed rows correct them with the predictive_moments kernel's per-row moments."""
+    the tables; the observed rows correct them with the predictive_moments kernel's per-row moments.  weights ([R] on
+    the device, in x's row order): row r weighs weights[r] in place of w1, so W = w0 N M + sum_r (w_r - w0)."""
     ent, bia, scal = model._views(model._flat)
     d, link = model.d, model.link
     N, M = model.field_sizes
@@ -798,7 +861,11 @@ def implicit_sums(model, x, y, w0, w1):
     sum_v = (N * M * s0 * s0 + M * (_link64(bia[:N, 1], link) ** 2).sum() + N * (_link64(bia[N:N + M, 1], link) ** 2).sum()
              + (mu_u * mu_u).sum(0) @ si2.sum(0) + su2.sum(0) @ (si2 + mu_i * mu_i).sum(0))
     n = x.shape[0]
-    W = torch.tensor(w0 * N * M + (w1 - w0) * n, dtype=torch.float64, device=ent.device)
+    if weights is None:
+        W = torch.tensor(w0 * N * M + (w1 - w0) * n, dtype=torch.float64, device=ent.device)
+    else:
+        w1 = weights.double()
+        W = w0 * N * M + (w1 - w0).sum()
     S1 = -w0 * (sum_m - N * M * m0)
     S2 = w0 * (sum_m2 + sum_v)
     if n:
@@ -815,14 +882,14 @@ def _field_ids(model, field):
     return torch.arange(lo, hi, dtype=torch.int64, device=model.device)
 
 
-def implicit_objective_terms(model, x, y, w0, w1, kl_weight, priors=None):
+def implicit_objective_terms(model, x, y, w0, w1, kl_weight, priors=None, weights=None):
     """J_imp as a 0-dim fp64 tensor on the device: the weighted expected negative log likelihood of every pair
     (implicit_sums) plus kl_weight times the KL to N(0, 1) of every entity of both fields and of the global bias.
     priors: every entity's KL -- observed or not: its w0 rows are in the likelihood -- is to its field's
-    N(mean, 1 / prec); the global bias keeps N(0, 1)."""
+    N(mean, 1 / prec); the global bias keeps N(0, 1).  weights: a weight per observed row in place of w1."""
     ent, bia, scal = model._views(model._flat)
     prec = _link64(scal[0], model.link)
-    W, _, S2 = implicit_sums(model, x, y, w0, w1)
+    W, _, S2 = implicit_sums(model, x, y, w0, w1, weights)
     kl = _kl64(scal[1].double(), _link64(scal[2], model.link))
     if priors is None:
         kl = _add_kl64_rows(kl, ent, bia, model.d, model.link)
@@ -833,31 +900,31 @@ def implicit_objective_terms(model, x, y, w0, w1, kl_weight, priors=None):
     return 0.5 * prec * S2 + W * (LOG_2PI_HALF - 0.5 * torch.log(prec)) + float(kl_weight) * kl
 
 
-def update_scalars_implicit(model, x, y, w0, w1, kl_weight):
+def update_scalars_implicit(model, x, y, w0, w1, kl_weight, weights=None):
     """The exact block minimisers of J_imp over the scalars, written in place: the global bias (mean and scale jointly),
     then the precision from the sums recomputed after it.  No readback."""
     scal = model._views(model._flat)[2]
     kl = float(kl_weight)
     prec = _link64(scal[0], model.link)
-    W, S1, _ = implicit_sums(model, x, y, w0, w1)
+    W, S1, _ = implicit_sums(model, x, y, w0, w1, weights)
     den = kl + prec * W
     scal[1:3] = torch.stack([prec * S1 / den, _inv_link64(torch.sqrt(kl / den), model.link)]).float()
-    W, _, S2 = implicit_sums(model, x, y, w0, w1)
+    W, _, S2 = implicit_sums(model, x, y, w0, w1, weights)
     scal[0:1] = _inv_link64(W / S2, model.link).float().reshape(1)
 
 
-def implicit_objective(model, X, y, w0, w1=1.0, kl_weight=1.0, priors=None):
-    x, y, w0, w1 = check_implicit_args(model, X, y, w0, w1, kl_weight)
+def implicit_objective(model, X, y, w0, w1=1.0, kl_weight=1.0, priors=None, weights=None):
+    x, y, w0, w1 = check_implicit_args(model, X, y, w0, w1, kl_weight, weights)
     check_priors(model, priors)
     ops._need_cuda(model._flat, "the model's parameters")
     model._fresh_params()
-    return float(implicit_objective_terms(model, x, y, w0, w1, kl_weight, priors))
+    return float(implicit_objective_terms(model, x, y, w0, w1, kl_weight, priors, _row_weights(model, weights)))
 
 
 def fit_implicit(model, X, y=None, n_sweeps=10, w0=None, w1=1.0, kl_weight=1.0, update_scalars_=True, split_rows="auto",
                  chunk_rows=2048, on_step=None, tol=None, max_workspace_bytes=MAX_WORKSPACE_BYTES, priors=None,
-                 learn_priors=False, learn_mean=True, prec_min=1e-4, prec_max=1e4):
-    x, y, w0, w1 = check_implicit_args(model, X, y, w0, w1, kl_weight)
+                 learn_priors=False, learn_mean=True, prec_min=1e-4, prec_max=1e4, weights=None):
+    x, y, w0, w1 = check_implicit_args(model, X, y, w0, w1, kl_weight, weights)
     check_fit_args(model, x, y, "reg", lambda f: (x, y), n_sweeps, None, split_rows, chunk_rows, tol)
     check_priors(model, priors)
     prec_min, prec_max = check_prec_bounds(prec_min, prec_max)
@@ -865,7 +932,9 @@ def fit_implicit(model, X, y=None, n_sweeps=10, w0=None, w1=1.0, kl_weight=1.0, 
     if learn_priors and priors is None:
         priors = GroupPriors(model.F, model.d, model.device)          # (created at N(0, 1), returned under "priors")
     model._fresh_params()
-    plans = {f: ImplicitPlan(model, x, y, f, None, split_rows, chunk_rows, max_workspace_bytes) for f in (0, 1)}
+    weights = _row_weights(model, weights)
+    plans = {f: ImplicitPlan(model, x, y, f, None, split_rows, chunk_rows, max_workspace_bytes, weights=weights)
+             for f in (0, 1)}
     # the prior block is over the field's WHOLE id range: in J_imp every entity is in the KL, observed or not
     all_f = {f: _field_ids(model, f) for f in (0, 1)} if learn_priors else {}
     clamped = {f: torch.zeros((), dtype=torch.int64, device=x.device) for f in all_f}
@@ -874,10 +943,10 @@ def fit_implicit(model, X, y=None, n_sweeps=10, w0=None, w1=1.0, kl_weight=1.0, 
         clamped[f] += update_prior(model, priors, f, all_f[f], learn_mean, prec_min, prec_max)
 
     out = _sweeps(model, (0, 1), n_sweeps, tol, on_step,
-                  lambda: implicit_objective_terms(model, x, y, w0, w1, kl_weight, priors),
-                  lambda f: plans[f].run(model, kl_weight, w0, w1, _prior_row(model, priors, f)),
+                  lambda: implicit_objective_terms(model, x, y, w0, w1, kl_weight, priors, weights),
+                  lambda f: plans[f].run(model, kl_weight, w0, w1, _prior_row(model, priors, f), weights),
                   learn_prior if learn_priors else None,
-                  (lambda: update_scalars_implicit(model, x, y, w0, w1, kl_weight)) if update_scalars_ else None,
+                  (lambda: update_scalars_implicit(model, x, y, w0, w1, kl_weight, weights)) if update_scalars_ else None,
                   "scalars")
     if priors is not None:
         out["priors"] = priors
