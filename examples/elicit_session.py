@@ -38,6 +38,14 @@ cold-start questionnaire (reset=True: every student starts at the prior) runs tw
 (`priors=`) and under N(0, 1), side by side.
 
     python examples/elicit_session.py --priors [--bound] [questions] [sweeps]
+
+With --implicit the correct answers are clicks: a 'reg' model is trained by `VFM.fit_implicit` on the training rows
+answered correctly (every other (student, question) pair counts as target 0 with weight w0), the test students are
+cold-started by the implicit recipe -- `fold_in_implicit` without rows gives them the base-only optimum -- and interviewed
+by `VFM.elicit_field_implicit`, whose every fold is the optimum over all of a student's pairs.  Prints the NDCG@10 of the
+held-out correct answers under every round's posteriors, beside the exact session's (reset=True) on the same model.
+
+    python examples/elicit_session.py --implicit [questions] [sweeps]
 """
 import os
 import sys
@@ -94,6 +102,36 @@ def main_ranking(argv, design=False):
         print(f"{q:5d}  " + "  ".join(f"{rmse[s][q]:8.4f} / {ndcg[s]['ndcg@10'][q]:8.4f}" for s in strategies))
 
 
+def main_implicit(argv):
+    questions = int(argv[0]) if len(argv) > 0 else 10
+    sweeps = int(argv[1]) if len(argv) > 1 else 8
+    w0 = 0.1                                                 # an untuned starting value
+    N, M, X_train, X_test, y_train, y_test = load_fraction(os.path.join(ROOT, "tests", "golden", "fraction"))
+    X_train, X_test = torch.as_tensor(X_train), torch.as_tensor(X_test)
+    y_train, y_test = torch.as_tensor(y_train).float(), torch.as_tensor(y_test).float()
+    students = torch.unique(X_test[:, 0])
+    clicks = X_train[y_train == 1]                           # (the students' own rows train the questions; the recipe below forgets the students)
+    torch.manual_seed(42)
+    model = VFM(N, M, embedding_size=5, output="reg", device="cuda")
+    model.fit_implicit(clicks, n_sweeps=sweeps, w0=w0)
+    order = torch.sort(X_test[:, 0], stable=True).indices
+    nth = torch.arange(len(order)) - torch.searchsorted(X_test[order, 0].contiguous(), X_test[order, 0].contiguous())
+    ask, held = order[nth % 2 == 0], order[nth % 2 == 1]
+    strategies = ("random", "variance")
+    kw = dict(ks=(10,), strategies=strategies, threshold=0.5, ineligible="drop", seed=1)
+    exact = model.elicitation_ranking_curve_field(X_test[ask], y_test[ask], questions, 0, X_test[held], y_test[held], 1,
+                                                  exact=True, reset=True, **kw)
+    # the cold-start recipe: a student without answers sits at the base-only optimum, then reset=False
+    model.fold_in_implicit(X_test[:0], y_test[:0], 0, w0=w0, entities=students)
+    imp = model.elicitation_ranking_curve_field(X_test[ask], y_test[ask], questions, 0, X_test[held], y_test[held], 1,
+                                                implicit=True, w0=w0, **kw)
+    print(f"{len(students)} students, {len(ask)} questions in the pool, {len(held)} held out, {imp['n_queries']} ranking "
+          f"queries per strategy; NDCG@10 of the held-out: implicit session / exact session")
+    print("asked  " + "  ".join(f"{s:>19}" for s in strategies))
+    for q in range(questions + 1):
+        print(f"{q:5d}  " + "  ".join(f"{imp[s]['ndcg@10'][q]:8.4f} / {exact[s]['ndcg@10'][q]:8.4f}" for s in strategies))
+
+
 def main_bound(argv):
     questions = int(argv[0]) if len(argv) > 0 else 15
     epochs = int(argv[1]) if len(argv) > 1 else 60
@@ -142,6 +180,8 @@ def main():
         return main_priors(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--exact":
         return main_exact(sys.argv[2:])
+    if len(sys.argv) > 1 and sys.argv[1] == "--implicit":
+        return main_implicit(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--bound":
         return main_bound(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] in ("--ranking", "--design"):

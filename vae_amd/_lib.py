@@ -177,6 +177,16 @@ class ImplicitSolve(_Strict, C.Structure):
                     + (("workspace_bytes", C.c_int64),))
 
 
+# ---- the implicit field-form session (include/vfm_elicit_implicit.h): vfm_elicit_solve_t, the partner field's base
+# block with its range and the two weights in a struct of their own, and the prior pointer (NULL: N(0, 1))
+ELICIT_IMPLICIT_EXPORTS = ("vfm_elicit_implicit_f32", "vfm_elicit_implicit_workspace_bytes")
+
+
+class ElicitImplicit(_Strict, C.Structure):
+    """`vfm_elicit_implicit_t` (tests/test_elicit_implicit_cpu.py checks the layout against gcc's)."""
+    _fields_ = list(_fields(C.c_float, "w0", "w1") + _fields(C.c_int64, "lo", "n") + (("base", C.c_void_p),))
+
+
 # the bound field-form session (vfm_elicit_bound_f32) is declared in vfm_bound.h too
 ELICIT_BOUND_EXPORTS = ("vfm_elicit_bound_f32", "vfm_elicit_bound_workspace_bytes")
 
@@ -256,7 +266,7 @@ _ELICIT_PRIOR_PROTOTYPES = (
 
 
 for _c in (Problem, Index, Pipe, Elicit, ElicitField, ElicitSolve, ElicitBound, ElicitDesign, FoldinSolve, FoldinSplit,
-           FoldinBound, FoldinBoundSplit, ImplicitBase, ImplicitSolve):
+           FoldinBound, FoldinBoundSplit, ImplicitBase, ImplicitSolve, ElicitImplicit):
     _c._names = frozenset(n for n, _ in _c._fields_)
 
 
@@ -365,6 +375,10 @@ def load():
     lib.vfm_implicit_solve_weights_workspace_bytes.restype = i64
     lib.vfm_foldin_solve_implicit_weights_f32.argtypes = [C.POINTER(ImplicitSolve), vp, vp, vp]
     lib.vfm_foldin_solve_implicit_weights_f32.restype = C.c_int
+    lib.vfm_elicit_implicit_f32.argtypes = [C.POINTER(ElicitSolve), C.POINTER(ElicitImplicit), vp, vp]
+    lib.vfm_elicit_implicit_f32.restype = C.c_int
+    lib.vfm_elicit_implicit_workspace_bytes.argtypes = [i64, i64, i64, i32, i32]
+    lib.vfm_elicit_implicit_workspace_bytes.restype = i64
     lib.vfm_elicit_bound_f32.argtypes = [C.POINTER(ElicitBound), vp]
     lib.vfm_elicit_bound_f32.restype = C.c_int
     lib.vfm_elicit_bound_workspace_bytes.argtypes = [i64, i64, i64, i64, i32, i32, i32]

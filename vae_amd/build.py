@@ -105,15 +105,20 @@ _UNITS = [("vfm_abi.hip", "", _EXACT), ("vfm_index.hip", "", []), ("vfm_variants
           # catalog and the exact fold-in's factorisation and rounding (csrc_rank/vfm_foldin_solve_body.hpp), hence its
           # flag; the unit holds the solve under a field prior (include/vfm_implicit_prior.h) and with a weight per
           # observed row (include/vfm_implicit_weights.h) as well
-          ("csrc_rank/vfm_implicit.hip", "", _EXACT)]
+          ("csrc_rank/vfm_implicit.hip", "", _EXACT),
+          # implicit elicitation session (include/vfm_elicit_implicit.h): the exact sessions' loop and host path
+          # (csrc_rank/vfm_elicit_exact_body.hpp) with the implicit solve's per-entity body
+          # (csrc_rank/vfm_implicit_body.hpp) as the fold of a round, hence their flag; the unit holds the session under a
+          # field prior as well
+          ("csrc_rank/vfm_elicit_implicit.hip", "", _EXACT)]
 RANK_DIR = os.path.join(HERE, "csrc_rank")
 VAR_DIR = os.path.join(HERE, "csrc_var")
 # the public headers beside include/vfm_hip.h (vfm_foldin_ops.cpp holds the ops of foldin, sweep, bound_sweep, prior,
-# bound_prior, implicit, implicit_prior, implicit_weights and vfm_bound.h's fold-in; vfm_elicit_ops.cpp holds vfm_bound.h's session and, with vfm_design_ops.cpp,
-# the ops of elicit_prior)
+# bound_prior, implicit, implicit_prior, implicit_weights and vfm_bound.h's fold-in; vfm_elicit_ops.cpp holds vfm_bound.h's session, the
+# session of elicit_implicit and, with vfm_design_ops.cpp, the ops of elicit_prior)
 PUBLIC_HDRS = tuple(os.path.join(ROOT, "include", f"vfm_{n}.h")
                     for n in ("rank", "foldin", "elicit", "design", "variant_step", "sweep", "bound", "bound_sweep", "prior",
-                              "bound_prior", "elicit_prior", "implicit", "implicit_prior", "implicit_weights"))
+                              "bound_prior", "elicit_prior", "implicit", "implicit_prior", "implicit_weights", "elicit_implicit"))
 # the TORCH_LIBRARY fragments linked into the shim beside csrc/vfm_torch_ops.cpp, and the header they share: host C++
 # only, so it is no source of libvfm_hip.so.  One file per family
 OPS_SOURCES = tuple(os.path.join(RANK_DIR, f"vfm_{n}_ops.cpp") for n in ("rank", "foldin", "elicit", "design"))

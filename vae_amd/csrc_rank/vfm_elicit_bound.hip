@@ -46,6 +46,7 @@ struct ElicitBoundArgs : ElicitSolveArgs {   // (e.f.n_steps: the rounds of the 
 
 // the fold of a round: n_iters rounds of the bound from theta_e
 struct BoundFold {
+  static constexpr bool ALL_PAIRS = false;
   __host__ __device__ static int64_t lds_doubles(int d) { return d + 1; }
   template <int W, int CPL, int LINK, bool PRIOR, class Rows, class Store>
   __device__ __forceinline__ static void run(const ElicitBoundArgs& s, const FoldArgs& f, const Rows& rows, int64_t n,

@@ -112,7 +112,11 @@ __device__ __forceinline__ void put_moments(const ElicitFieldArgs& a, int q, int
 //                              its n rows from theta_e in pf; solve_body's contract: pf rewritten, store(pf) by every
 //                              thread after the barrier that publishes it, the loss by wave 0, no barrier at the end;
 //                              pr: the staged prior of a PRIOR session (else NULL)
+//   ALL_PAIRS                  does the fold run over every (respondent, partner) pair of a two-field model (ImplicitFold of
+//                              vfm_elicit_implicit.hip)?  Then its system is always the primal (d + 1) x (d + 1) one, and
+//                              pool_ok(s, row) says whether pool row `row` names a partner the fold's base block covers
 struct SolveFold {
+  static constexpr bool ALL_PAIRS = false;
   __host__ __device__ static int64_t lds_doubles(int) { return 0; }
   template <int W, int CPL, int LINK, bool PRIOR, class Args, class Rows, class Store>
   __device__ __forceinline__ static void run(const Args& s, const FoldArgs& f, const Rows& rows, int64_t n, int64_t,
@@ -209,7 +213,10 @@ __device__ __forceinline__ void exact_session(const Args& s, const float* prior 
       for (int64_t p = tid; p < np; p += FB) {
         const bool was = a.asked[p0 + p] != 0;
         if (was && !a.out_mean) continue;
-        const float sc = score.template pool_row<DP>(q, p0, p, was, eok, e, n, uth);
+        float sc = score.template pool_row<DP>(q, p0, p, was, eok, e, n, uth);
+        if constexpr (Fold::ALL_PAIRS) {   // (a partner outside the base's range is never a candidate)
+          if (!Fold::pool_ok(s, p0 + p)) sc = __builtin_nanf("");
+        }
         if (!was && sc == sc && (bp < 0 || sc > bs)) { bs = sc; bp = p; }
       }
       if (q == Q) break;
@@ -239,7 +246,9 @@ __device__ __forceinline__ void exact_session(const Args& s, const float* prior 
       // ---- fold in: the optimum over the history and the rows asked so far, from the rows themselves
       if (act) {
         ++n;
-        const int m = solve_dim(n, d);
+        int m;
+        if constexpr (Fold::ALL_PAIRS) m = d1;              // (the base has full rank: always the primal system)
+        else m = solve_dim(n, d);
         Fold::template run<W, CPL, LINK, PRIOR>(s, f, rows, n, g, sm, m <= s.sl.cap_dim ? Hl : Hg, fown, precf, prec,
                                                 a.out_loss + g * Q + q, [&](const float*) { put_theta(q); }, pr);
       } else {
@@ -311,9 +320,11 @@ int check_exact_operands(const P* p, bool need_op_x, const char* small_msg) {
 
 // The workspace carved up and the kernel arguments both forms name alike, from p.  A: ElicitSolveArgs or a struct
 // derived from it; session: rounds, `reset`, `write` and the session's outputs count (else one round, nothing written);
-// seed: of the random strategy.  Returns the grid of the session kernel; the unit adds its score's own fields.
+// seed: of the random strategy.  operand_block false (the implicit session, whose fold reads the tables): the fold-in's
+// operand block is absent -- its four pointers stay NULL -- and the slabs follow the score's constants directly.
+// Returns the grid of the session kernel; the unit adds its score's own fields.
 template <class A, class P>
-unsigned exact_session_args(const P* p, bool session, uint64_t seed, A& s) {
+unsigned exact_session_args(const P* p, bool session, uint64_t seed, A& s, bool operand_block = true) {
   const int64_t n_ops = p->n_ops;
   char* w = (char*)p->workspace + flags_bytes(p->P);
   float* sop = (float*)w;
@@ -336,6 +347,7 @@ unsigned exact_session_args(const P* p, bool session, uint64_t seed, A& s) {
     a.out_mean = p->out_mean; a.out_var = p->out_var;
   }
   a.asked = (uint8_t*)p->workspace;
+  if (!operand_block) return place_slabs(p->d, p->lds_dim, p->U, w, (int64_t)1 << 20, s.sl);
   a.f.ops = (const float*)w;
   a.f.opc = (const float*)(w + ops_off_opc(n_ops, p->d));
   s.ops64 = (const double*)(w + off_ops64(n_ops, p->d));

@@ -1,7 +1,8 @@
 // vfm_elicit_ops.cpp -- torch.ops.vfm_hip.{elicit, elicit_workspace_bytes, elicit_field, elicit_field_workspace_bytes,
 // elicit_solve, elicit_solve_workspace_bytes, elicit_bound, elicit_bound_workspace_bytes, elicit_solve_prior,
-// elicit_bound_prior}: the TORCH_LIBRARY fragment over include/vfm_elicit.h, the session of include/vfm_bound.h and their
-// forms under a field prior (include/vfm_elicit_prior.h).  Like vfm_foldin_ops.cpp it only validates tensors, takes
+// elicit_bound_prior, elicit_implicit, elicit_implicit_prior, elicit_implicit_workspace_bytes}: the TORCH_LIBRARY fragment
+// over include/vfm_elicit.h, the session of include/vfm_bound.h, their forms under a field prior
+// (include/vfm_elicit_prior.h) and the implicit session (include/vfm_elicit_implicit.h).  Like vfm_foldin_ops.cpp it only validates tensors, takes
 // the current HIP stream of the tensors' device and forwards raw pointers; all arithmetic is in the HIP kernels.  Each
 // session op is the parts of vfm_ops_common.hpp in sequence (rows, tables, workspace, outputs, history) plus its own
 // options.
@@ -9,6 +10,7 @@
 
 #include "vfm_bound.h"
 #include "vfm_elicit.h"
+#include "vfm_elicit_implicit.h"
 #include "vfm_elicit_prior.h"
 
 namespace {
@@ -213,6 +215,49 @@ void elicit_bound_prior(VFM_SESSION_TENSORS, const Tensor& prior, int64_t field,
                     kl_weight, seed, n_iters);
 }
 
+int64_t elicit_implicit_workspace_bytes(int64_t U, int64_t P, int64_t n_ops, int64_t d, int64_t lds_dim) {
+  const int64_t b = vfm_elicit_implicit_workspace_bytes(U, P, n_ops, (int32_t)d, (int32_t)lds_dim);
+  TORCH_CHECK(b >= 0, "vfm_elicit_implicit_workspace_bytes: bad arguments");
+  return b;
+}
+
+// the implicit field-form session (two-field 'reg' models): elicit_solve's tensors and options, the partner field's base
+// block, its id range and the two weights; prior: as elicit_solve_call's (elicit_implicit_prior)
+void elicit_implicit_call(const Tensor* prior, VFM_SESSION_TENSORS, const Tensor& base, int64_t field, int64_t key_col,
+                          int64_t n_rounds, int64_t strategy, int64_t flags, int64_t reset, int64_t write, int64_t lds_dim,
+                          double kl_weight, int64_t seed, int64_t lo, int64_t n, double w0, double w1) {
+  vfm_elicit_solve_t p;
+  VFM_STRUCT_INIT(p);
+  fill_field_rows(p, entities, pool_ptr, pool_x, &pool_y, op_x, pool_op);
+  fill_tables(p, entity, bias, scalars);
+  fill_workspace(p, workspace);
+  fill_session_outputs(p, n_rounds, out_row, out_score, out_loss, out_theta, out_mean, out_var);
+  fill_field_history(p, hist_ptr, hist_x, hist_y, hist_op);
+  solve_options(p, field, key_col, strategy, flags, reset, write, lds_dim, kl_weight, seed);
+  dev_tensor(base, at::kDouble, "base");
+  TORCH_CHECK(p.d >= 1 && p.d <= VFM_FOLDIN_MAX_D && base.numel() >= vfm_implicit_base_doubles(p.d),
+              "base [vfm_implicit_base_doubles(d)]");
+  vfm_elicit_implicit_t imp;
+  imp.w0 = (float)w0; imp.w1 = (float)w1; imp.lo = lo; imp.n = n; imp.base = base.data_ptr<double>();
+  c10::hip::HIPGuard guard(entities.get_device());
+  check(vfm_elicit_implicit_f32(&p, &imp, prior ? prior_of(*prior, p.d) : nullptr, stream_of(entities)),
+        "vfm_elicit_implicit_f32");
+}
+
+void elicit_implicit(VFM_SESSION_TENSORS, const Tensor& base, int64_t field, int64_t key_col, int64_t n_rounds,
+                     int64_t strategy, int64_t flags, int64_t reset, int64_t write, int64_t lds_dim, double kl_weight,
+                     int64_t seed, int64_t lo, int64_t n, double w0, double w1) {
+  elicit_implicit_call(nullptr, VFM_SESSION_TENSOR_NAMES, base, field, key_col, n_rounds, strategy, flags, reset, write,
+                       lds_dim, kl_weight, seed, lo, n, w0, w1);
+}
+
+void elicit_implicit_prior(VFM_SESSION_TENSORS, const Tensor& prior, const Tensor& base, int64_t field, int64_t key_col,
+                           int64_t n_rounds, int64_t strategy, int64_t flags, int64_t reset, int64_t write,
+                           int64_t lds_dim, double kl_weight, int64_t seed, int64_t lo, int64_t n, double w0, double w1) {
+  elicit_implicit_call(&prior, VFM_SESSION_TENSOR_NAMES, base, field, key_col, n_rounds, strategy, flags, reset, write,
+                       lds_dim, kl_weight, seed, lo, n, w0, w1);
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(vfm_hip, m) {
@@ -262,4 +307,20 @@ TORCH_LIBRARY_FRAGMENT(vfm_hip, m) {
         "int key_col, int n_rounds, int strategy, int flags, int reset, int write, int lds_dim, float kl_weight, "
         "int seed, int n_iters) -> ()",
         &elicit_bound_prior);
+  m.def("elicit_implicit_workspace_bytes(int U, int P, int n_ops, int d, int lds_dim) -> int",
+        &elicit_implicit_workspace_bytes);
+  m.def("elicit_implicit(Tensor entities, Tensor pool_ptr, Tensor pool_x, Tensor pool_y, Tensor? hist_ptr, Tensor? hist_x, "
+        "Tensor? hist_y, Tensor op_x, Tensor pool_op, Tensor? hist_op, Tensor(a!) entity_params, "
+        "Tensor(b!) bias_params, Tensor scalars, Tensor(c!) workspace, Tensor(d!) out_row, Tensor(e!) out_score, "
+        "Tensor(f!) out_loss, Tensor(g!)? out_theta, Tensor(h!)? out_mean, Tensor(i!)? out_var, Tensor base, int field, "
+        "int key_col, int n_rounds, int strategy, int flags, int reset, int write, int lds_dim, float kl_weight, "
+        "int seed, int lo, int n, float w0, float w1) -> ()",
+        &elicit_implicit);
+  m.def("elicit_implicit_prior(Tensor entities, Tensor pool_ptr, Tensor pool_x, Tensor pool_y, Tensor? hist_ptr, "
+        "Tensor? hist_x, Tensor? hist_y, Tensor op_x, Tensor pool_op, Tensor? hist_op, Tensor(a!) entity_params, "
+        "Tensor(b!) bias_params, Tensor scalars, Tensor(c!) workspace, Tensor(d!) out_row, Tensor(e!) out_score, "
+        "Tensor(f!) out_loss, Tensor(g!)? out_theta, Tensor(h!)? out_mean, Tensor(i!)? out_var, Tensor prior, Tensor base, "
+        "int field, int key_col, int n_rounds, int strategy, int flags, int reset, int write, int lds_dim, "
+        "float kl_weight, int seed, int lo, int n, float w0, float w1) -> ()",
+        &elicit_implicit_prior);
 }

@@ -52,6 +52,7 @@ namespace {
 
 #include "vfm_foldin_body.hpp"       // FB, for_link, round_up, softplus_d, LOG_2PI_HALF
 #include "vfm_foldin_solve_body.hpp" // tri, tri_decode, link_d, chol_solve, put_params, the slab rule, launch_lds
+#include "vfm_implicit_body.hpp"     // partner_consts, coord_sums, list_elem, implicit_body: the per-entity text of the solve
 
 constexpr int TL = 4;                    // edge of a register tile of the triangle
 
@@ -76,14 +77,6 @@ struct ImpArgs {
 
 __host__ __device__ inline int64_t imp_doubles(int d) { return tri(d + 1) + 3 * (int64_t)(d + 1) + 1; }
 
-// c_mean and c_var of partner j
-template <int LINK>
-__device__ __forceinline__ void partner_consts(const ImpArgs& s, int64_t j, double& cm, double& cv) {
-  const double s0 = link_d<LINK>(s.scal[2]), sw = link_d<LINK>(s.bias[j * 2 + 1]);
-  cm = (double)s.scal[1] + (double)s.bias[j * 2];
-  cv = s0 * s0 + sw * sw;
-}
-
 // the ids [first, first + n) of the catalog: y = 0, weight 1
 struct CatalogRows {
   int64_t first;
@@ -105,62 +98,21 @@ struct ObservedRows {
   __device__ __forceinline__ double g(int64_t r) const { return (double)s.w[r0 + r] - s.w0; }
   __device__ __forceinline__ double t(int64_t r, double cm) const {
     if constexpr (WROW) return (double)s.w[r0 + r] * (double)s.y[r0 + r] - g(r) * cm;
-    else return s.w1 * (double)s.y[r0 + r] - (s.w1 - s.w0) * cm;
+    else return obs_t(s.w0, s.w1, (double)s.y[r0 + r], cm);
   }
   __device__ __forceinline__ double q(int64_t r, double cm, double cv) const {
-    const double res = (double)s.y[r0 + r] - cm;
     if constexpr (WROW) {
+      const double res = (double)s.y[r0 + r] - cm;
       // the two squares in statements of their own: neither fuses into the difference, so a row of weight w0 and
       // target 0 adds exactly 0 (res = -cm) and an entity of such rows is the entity without rows, bit for bit
       const double a = (double)s.w[r0 + r] * res * res;
       const double b = s.w0 * cm * cm;
       return a - b + g(r) * cv;
     } else {
-      return s.w1 * res * res - s.w0 * cm * cm + (s.w1 - s.w0) * cv;
+      return obs_q(s.w0, s.w1, (double)s.y[r0 + r], cm, cv);
     }
   }
 };
-
-// coordinate c's sums over n rows in order: SA, SB, bM = sum t u_c and, for c = 0, tt = sum q; false when a row is bad.
-// WROW: SA = sum g A, SB = sum g (A + M^2) and, for c = 0, SB = sum g over every row (bad or not, as the row count is)
-template <int LINK, bool WROW = false, class Rows>
-__device__ __forceinline__ bool coord_sums(const ImpArgs& s, const Rows& rows, int64_t n, int c, double& SA, double& SB,
-                                           double& bM, double& tt) {
-#pragma clang fp contract(on)
-  const int d = s.d;
-  bool ok = true;
-  SA = SB = bM = tt = 0.;
-  if (c == 0) {
-    for (int64_t r = 0; r < n; ++r) {
-      if constexpr (WROW) SB += rows.g(r);
-      const int64_t j = rows.id(r);
-      if (j < 0) { ok = false; continue; }
-      double cm, cv;
-      partner_consts<LINK>(s, j, cm, cv);
-      bM += rows.t(r, cm);
-      tt += rows.q(r, cm, cv);
-    }
-    if constexpr (!WROW) SB = (double)n;
-  } else {
-    for (int64_t r = 0; r < n; ++r) {
-      const int64_t j = rows.id(r);
-      if (j < 0) { ok = false; continue; }
-      const float* row = s.entity + j * 2 * (int64_t)d;
-      const double M = row[c - 1], sg = link_d<LINK>(row[d + c - 1]), A = sg * sg;
-      const double cm = (double)s.scal[1] + (double)s.bias[j * 2];
-      if constexpr (WROW) {
-        const double g = rows.g(r);
-        SA += g * A;
-        SB += g * (A + M * M);
-      } else {
-        SA += A;
-        SB += A + M * M;
-      }
-      bM += rows.t(r, cm) * M;
-    }
-  }
-  return ok;
-}
 
 // the slab P of n rows, by the whole workgroup: [triangle | SA | SB | sum t u | sum q], NaN where a row is bad.
 // WROW: the triangle of sum g u u^T, the four u_i of a row scaled by g once
@@ -264,11 +216,43 @@ __global__ __launch_bounds__(FB) void k_implicit_chunks(const ImpArgs s) {
   }
 }
 
+// the share of entity g's observed rows for implicit_body: its chunks' slabs [c0, c1) added in chunk order (chunk form),
+// or its row list accumulated where it is used (row-list form: ListShare's two calls)
+template <int LINK, bool WROW>
+struct EntityShare {
+  const ImpArgs& s;
+  const ObservedRows<WROW>& rows;
+  int64_t c0, c1, n;
+  __device__ __forceinline__ void coord(int c, double& SA, double& SB, double& bM, double& tt) const {
+#pragma clang fp contract(on)
+    if (s.chunk_ptr) {
+      const int d1 = s.d + 1;
+      for (int64_t q = c0; q < c1; ++q) {
+        const double* V = s.part + q * s.part_elems + tri(d1);
+        SA += V[c];
+        SB += V[d1 + c];
+        bM += V[2 * d1 + c];
+        if (c == 0) tt += V[3 * d1];
+      }
+    } else {
+      ListShare<LINK, WROW, ImpArgs, ObservedRows<WROW>>{s, rows, n}.coord(c, SA, SB, bM, tt);
+    }
+  }
+  __device__ __forceinline__ double elem(int64_t p, int i, int j) const {
+#pragma clang fp contract(on)
+    if (s.chunk_ptr) {
+      double acc = 0.;
+      for (int64_t q = c0; q < c1; ++q) acc += s.part[q * s.part_elems + p];
+      return acc;
+    }
+    return list_elem<WROW>(s, rows, n, i, j);
+  }
+};
+
 template <int LINK, bool PRIOR, bool WROW>
 __global__ __launch_bounds__(FB) void k_implicit_solve(const ImpArgs s) {
 #pragma clang fp contract(on)
   extern __shared__ double sm_all[];
-  __shared__ double tts;                 // tt' of the entity
   const int tid = threadIdx.x;
   const int d = s.d, d1 = d + 1;
   double* sm = sm_all + (PRIOR ? 2 * d1 : 0);              // (the prior in front: lds_doubles_prior)
@@ -277,22 +261,11 @@ __global__ __launch_bounds__(FB) void k_implicit_solve(const ImpArgs s) {
     stage_prior(s.prior, sm_all, d1);
     __syncthreads();
   }
-  double* Dd = sm;                       // solve_body's layout: D | loss terms | b | right-hand side | 1 / L_jj | solution | SB' | fp32
-  double* lt = Dd + d1;
-  double* bs = lt + d1;
-  double* yv = bs + d1;
-  double* dv = yv + d1;
-  double* xv = dv + d1;
-  double* SBd = xv + d1;
-  float* pf = (float*)(SBd + d1);
   double* Hl = sm + 8 * d1;
   double* Hg = s.sl.slab ? s.sl.slab + (int64_t)blockIdx.x * s.sl.slab_elems : nullptr;
   double* Hm = d1 <= s.sl.cap_dim ? Hl : Hg;
   const double prec = link_d<LINK>(s.scal[0]);
   const double kl = s.kl, w0 = s.w0, dw = s.w1 - s.w0;
-  const int64_t nt = tri(d1);
-  const double* B = s.base;
-  const double qnan = __builtin_nan("");
 
   for (int64_t g = blockIdx.x; g < s.E; g += gridDim.x) {
     const int64_t e = s.ent[g];
@@ -310,118 +283,18 @@ __global__ __launch_bounds__(FB) void k_implicit_solve(const ImpArgs s) {
       n = min(max(s.row_ptr[g + 1] - r0, (int64_t)0), s.R - r0);
     }
     const ObservedRows<WROW> rows{s, r0};
-
-    // ---- A: the sums of each coordinate, D, b and SB'
-    for (int c = tid; c < d1; c += FB) {
-      double SA = 0., SB = 0., bM = 0., tt = 0.;
-      if (s.chunk_ptr) {
-        for (int64_t q = c0; q < c1; ++q) {
-          const double* V = s.part + q * s.part_elems + nt;
-          SA += V[c];
-          SB += V[d1 + c];
-          bM += V[2 * d1 + c];
-          if (c == 0) tt += V[3 * d1];
-        }
-      } else if (!coord_sums<LINK, WROW>(s, rows, n, c, SA, SB, bM, tt)) {
-        SA = bM = tt = qnan;
-        if (c > 0) SB = qnan;
+    // phases A-E (vfm_implicit_body.hpp); the row is written where the fp32 parameters are published
+    implicit_body<LINK, PRIOR, WROW>(EntityShare<LINK, WROW>{s, rows, c0, c1, n}, d, s.base, kl, w0, dw, prec, sm, Hm,
+                                     s.loss + g, [&](const float* pf) {
+      for (int k = tid; k < d; k += FB) {
+        s.entity[e * 2 * d + k] = pf[1 + k];
+        s.entity[e * 2 * d + d + k] = pf[d1 + 1 + k];
       }
-      const double b = prec * (w0 * B[nt + 2 * d1 + c] + bM);
-      if constexpr (WROW) {              // (the share is weighted already: w0 base + share)
-        if constexpr (PRIOR) {
-          const double kll = kl * pr[d1 + c];
-          Dd[c] = kll + prec * (w0 * B[nt + c] + SA);
-          yv[c] = b + kll * pr[c];
-        } else {
-          Dd[c] = kl + prec * (w0 * B[nt + c] + SA);
-          yv[c] = b;
-        }
-      } else if constexpr (PRIOR) {
-        const double kll = kl * pr[d1 + c];
-        Dd[c] = kll + prec * (w0 * B[nt + c] + dw * SA);
-        yv[c] = b + kll * pr[c];
-      } else {
-        Dd[c] = kl + prec * (w0 * B[nt + c] + dw * SA);
-        yv[c] = b;
+      if (tid == 0) {
+        s.bias[e * 2] = pf[0];
+        s.bias[e * 2 + 1] = pf[d1];
       }
-      bs[c] = b;                         // (b of the data: the loss takes the prior's part through its KL)
-      if constexpr (WROW) SBd[c] = w0 * B[nt + d1 + c] + SB;
-      else SBd[c] = w0 * B[nt + d1 + c] + dw * SB;
-      if (c == 0) tts = w0 * B[nt + 3 * d1] + tt;
-    }
-    __syncthreads();
-
-    // ---- B: the system
-    for (int64_t p = tid; p < nt; p += FB) {
-      int i, j;
-      tri_decode(p, i, j);
-      double acc = 0.;
-      if (s.chunk_ptr) {
-        for (int64_t q = c0; q < c1; ++q) acc += s.part[q * s.part_elems + p];
-      } else if (i == 0) {
-        if constexpr (WROW) {
-          for (int64_t r = 0; r < n; ++r) acc += rows.g(r);
-        } else {
-          acc = (double)n;
-        }
-      } else {
-        bool bad = false;
-        for (int64_t r = 0; r < n; ++r) {
-          const int64_t k = rows.id(r);
-          if (k < 0) { bad = true; continue; }
-          const float* M = s.entity + k * 2 * (int64_t)d;
-          if constexpr (WROW) {
-            const double gM = rows.g(r) * (double)M[i - 1];
-            acc += j == 0 ? gM : gM * (double)M[j - 1];
-          } else {
-            acc += j == 0 ? (double)M[i - 1] : (double)M[i - 1] * (double)M[j - 1];
-          }
-        }
-        if (bad) acc = qnan;
-      }
-      if constexpr (WROW) Hm[p] = prec * (w0 * B[p] + acc) + (i == j ? Dd[i] : 0.0);
-      else Hm[p] = prec * (w0 * B[p] + dw * acc) + (i == j ? Dd[i] : 0.0);
-    }
-    __syncthreads();
-
-    // ---- C, D: the factorisation, the substitutions and the rounding of the exact fold-in
-    chol_solve(Hm, yv, dv, xv, d1);
-    for (int c = tid; c < d1; c += FB) {
-      if constexpr (PRIOR) put_params<LINK, true>(pf, d1, c, xv[c], kl, prec, SBd[c], kl * pr[d1 + c]);
-      else put_params<LINK>(pf, d1, c, xv[c], kl, prec, SBd[c]);
-    }
-    __syncthreads();
-    for (int k = tid; k < d; k += FB) {
-      s.entity[e * 2 * d + k] = pf[1 + k];
-      s.entity[e * 2 * d + d + k] = pf[d1 + 1 + k];
-    }
-    if (tid == 0) {
-      s.bias[e * 2] = pf[0];
-      s.bias[e * 2 + 1] = pf[d1];
-    }
-
-    // ---- E: L_e at the written parameters from the system; column c of L^T theta, the diagonal of L is 1 / dv
-    for (int c = tid; c < d1; c += FB) {
-      const double th = pf[c], sg = link_d<LINK>(pf[d1 + c]);
-      double l = th / dv[c];
-      for (int i = c + 1; i < d1; ++i) l += Hm[tri(i) + c] * (double)pf[i];
-      if constexpr (PRIOR) {
-        // KL(N(th, sg^2) || N(m, 1 / lam)) = KL(N(sqrt(lam) (th - m), lam sg^2) || N(0, 1)), as kl_prior_normal takes it
-        const double kll = kl * pr[d1 + c], sl = sqrt(pr[d1 + c]);
-        const double tm = sl * (th - pr[c]), ts = sl * sg;
-        const double klq = 0.5 * (ts * ts + tm * tm - 1.0) - log(ts);
-        lt[c] = (l * l - kll * th * th) - 2.0 * th * bs[c] + prec * sg * sg * SBd[c] + 2.0 * kl * klq;
-      } else {
-        const double klq = 0.5 * (sg * sg + th * th - 1.0) - log(sg);
-        lt[c] = (l * l - kl * th * th) - 2.0 * th * bs[c] + prec * sg * sg * SBd[c] + 2.0 * kl * klq;
-      }
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double sum = prec * tts;
-      for (int c = 0; c < d1; ++c) sum += lt[c];
-      s.loss[g] = (float)(0.5 * sum + SBd[0] * ((double)LOG_2PI_HALF - 0.5 * log(prec)));
-    }
+    }, pr);
     __syncthreads();                     // (the vectors and pf are rewritten by the next entity)
   }
 }

@@ -10,6 +10,8 @@ through torch.ops.vfm_hip.elicit.  `run_field` is the same for the entities of a
 number of fields (vfm_elicit_field_f32): full rows, one operand per distinct context.  `run_field_exact` is the field
 form with each round's Adam fit replaced by the exact fold-in's closed-form optimum (vfm_elicit_solve_f32), and
 `run_field_bound` the same for 'class' models with the bound fold-in's rounds (include/vfm_bound.h: vfm_elicit_bound_f32).
+`run_field_implicit` is the exact form for a two-field click model: each round's fold is the optimum over EVERY
+(respondent, partner) pair, the objective fit_implicit trains under (include/vfm_elicit_implicit.h).
 The field forms, design.run_field_design among them, are their argument checks and one call of `run_field_session`
 over the lists of `field_lists`; SESSION_KINDS says which of them the curves run under which strategy names.
 
@@ -361,6 +363,71 @@ def run_field_bound(model, pool, y_pool, n_questions, field=0, strategy="varianc
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the implicit field form (two-field 'reg' models): each round's fold is the optimum over every (respondent, partner)
+# pair, fold_in_implicit's (vfm_elicit_implicit_f32)
+# ---------------------------------------------------------------------------------------------------------------------
+DESIGN_NEEDS_ROWS = ("strategy 'design' is not available for the implicit sessions: its score is the drop of the optimum's "
+                     "scales over the rows asked alone; under J_imp the scales carry the w0 mass of every partner, and "
+                     "that target-aware score is not built")
+
+
+def check_args_field_implicit(model, pool, y_pool, n_questions, field, strategy, history, kl_weight, w0, w1):
+    """Validate an implicit field-form session call (no GPU needed): the implicit solves' conditions (a two-field 'reg'
+    model, kl_weight > 0 and finite, finite weights with w1 >= w0 > 0 once rounded to fp32), no "mean" / "design"
+    strategy, check_args_field's pool and history checks, and no partner named twice for a respondent by pool and history
+    together.  Returns (x, y, hx, hy, strategy code, field, key column, w0, w1)."""
+    if model.output != "reg":
+        raise ValueError("the implicit session needs a 'reg' model (Gaussian likelihood): the closed form it solves has "
+                         "none for 'class'; use elicit_field_bound")
+    if model.F != 2:
+        raise ValueError(f"the implicit session needs a two-field model (F = 2), not F = {model.F}")
+    foldin._check_kl_positive(kl_weight)
+    w0, w1 = (float(torch.tensor(float(w), dtype=torch.float32)) for w in (w0, w1))     # (the kernels take them in fp32)
+    if not (math.isfinite(w0) and math.isfinite(w1)):
+        raise ValueError("w0 and w1 must be finite")
+    if not w0 > 0.0:
+        raise ValueError("w0 must be > 0: it is the weight of every unobserved pair")
+    if w1 < w0:
+        raise ValueError("w1 must be >= w0: an observed pair weighs at least what an unobserved one does")
+    if strategy == "design":
+        raise ValueError(DESIGN_NEEDS_ROWS)
+    x, y, hx, hy, _, code, field, kf = check_args_field(model, pool, y_pool, n_questions, field, strategy, history, 0,
+                                                        0.0, "closed_form", 1, kl_weight, None)
+    rows = x if hx is None else torch.cat([x, hx])
+    if rows.shape[0]:
+        key = rows[:, 0] * model.T + rows[:, 1]
+        if int(torch.unique(key).numel()) != rows.shape[0]:
+            raise ValueError("duplicate (user, item) pairs in pool and history: every pair is one row of the implicit "
+                             "objective")
+    return x, y, hx, hy, code, field, kf, w0, w1
+
+
+def run_field_implicit(model, pool, y_pool, n_questions, field=0, w0=None, w1=1.0, strategy="variance", history=None,
+                       seed=0, kl_weight=1.0, reset=False, write=False, return_moments=False, return_theta=False,
+                       chunk_rows=2048, lds_dim=-1, priors=None):
+    """The implicit sessions of every entity of column `field` of the pool (VFM.elicit_field_implicit documents the
+    arguments and the result): run_field's lists and operands, one base block of the partner field
+    (sweep.implicit_base at chunk_rows: fold_in_implicit's bits) and one call of torch.ops.vfm_hip.elicit_implicit (with
+    priors: elicit_implicit_prior)."""
+    if w0 is None:
+        raise TypeError("run_field_implicit needs w0, the weight of an unobserved pair")
+    x, y, hx, hy, code, field, kf, w0, w1 = check_args_field_implicit(model, pool, y_pool, n_questions, field, strategy,
+                                                                      history, kl_weight, w0, w1)
+    sweep.check_priors(model, priors)
+    foldin._check_lds_dim(lds_dim)
+    sweep.check_chunk_rows(chunk_rows)
+    ops._need_cuda(model._flat, "the model's parameters")
+    model._fresh_params()
+    lo, hi = foldin.field_range(model, 1 - field)
+    base = sweep.implicit_base(model, lo, hi, chunk_rows)      # (the partner field is frozen over the session)
+    return run_field_session(
+        model, x, y, hx, hy, field, n_questions,
+        lambda o, U, P, H, n_ops, d: o.elicit_implicit_workspace_bytes(U, P, n_ops, d, int(lds_dim)), "elicit_implicit",
+        (base, field, kf, int(n_questions), code, link_flags(model), int(bool(reset)), int(bool(write)), int(lds_dim),
+         float(kl_weight), _seed64(seed), lo, hi - lo, w0, w1), write, return_moments, return_theta, priors=priors)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # the curve of quality against questions asked (torch; any device)
 # ---------------------------------------------------------------------------------------------------------------------
 def asked_round(rows, P):
@@ -405,6 +472,7 @@ SESSION_KINDS = {
     "adam": dict(runner="run_field", accepts=(), refuses={}),
     "exact": dict(runner="run_field_exact", accepts=("design",), refuses={}),
     "bound": dict(runner="run_field_bound", accepts=(), refuses={"design": DESIGN_NEEDS_REG}),
+    "implicit": dict(runner="run_field_implicit", accepts=(), refuses={"design": DESIGN_NEEDS_ROWS}),
 }
 
 
@@ -510,7 +578,7 @@ def round_posteriors(theta0, theta, resp, rnd):
 
 def ranking_curve(model, pool, y_pool, n_questions, field, X_test, y_test, rank_field, ks=(10,),
                   strategies=("random", "variance"), exact=False, exclude=None, match_fields=None, threshold=None,
-                  ineligible="raise", bound=False, **session_kw):
+                  ineligible="raise", bound=False, implicit=False, **session_kw):
     """VFM.elicitation_ranking_curve_field (which documents the arguments and the result)."""
     from . import rank
     for key in ("write", "return_moments", "return_theta", "strategy"):
@@ -518,7 +586,13 @@ def ranking_curve(model, pool, y_pool, n_questions, field, X_test, y_test, rank_
             raise ValueError(f"elicitation_ranking_curve_field sets {key} itself")
     if bound and exact:
         raise ValueError("bound=True and exact=True: the exact sessions are for 'reg' models, the bound ones for 'class'")
-    kind, strategies = "bound" if bound else "exact" if exact else "adam", list(strategies)
+    if implicit and (exact or bound):
+        raise ValueError("implicit=True excludes exact=True and bound=True: a session has one fold")
+    if implicit and session_kw.get("w0") is None:
+        raise ValueError("implicit=True needs w0, the weight of an unobserved pair")
+    if not implicit and any(k in session_kw for k in ("w0", "w1")):
+        raise ValueError("w0 and w1 are options of the implicit sessions: implicit=True")
+    kind, strategies = "implicit" if implicit else "bound" if bound else "exact" if exact else "adam", list(strategies)
     for s in strategies:
         _curve_strategy(s, kind)
     field = rank._field_arg(model, field)

@@ -1264,7 +1264,7 @@ class VFM(nn.Module):
                                         rank_field: int, ks=(10,), strategies=("random", "variance"),
                                         exact: bool = False, exclude=None, match_fields=None,
                                         threshold: Optional[float] = None, ineligible: str = "raise",
-                                        bound: bool = False, **session_kw):
+                                        bound: bool = False, implicit: bool = False, **session_kw):
         """How good are the recommendations after q questions?  For each strategy one session over the pool --
         elicit_field, or elicit_field_exact with exact=True, run with write=False, return_theta=True -- and, per round
         q = 0 .. n_questions, the held-out ranking metrics of the `rank_field` catalog (evaluate_ranking_field's:
@@ -1280,12 +1280,17 @@ class VFM(nn.Module):
         and round 0 under reset=True is then ranked at foldin.prior_theta).  With exact=True the name "design" is a
         strategy too: elicit_field_design, with `targets` taken from session_kw.  bound=True runs elicit_field_bound
         sessions ('class' models; session_kw then also takes n_iters, 8 being its untuned starting value; "design" is
-        refused); together with exact=True it is a ValueError.
+        refused); together with exact=True it is a ValueError.  implicit=True runs elicit_field_implicit sessions
+        (two-field 'reg' click models; session_kw then holds w0 -- required -- and takes w1, chunk_rows and priors;
+        "design" is refused); it excludes exact and bound, and theta0 is formed as for them.  Recall / NDCG under each
+        round's posteriors is the metric an implicit model is judged by.
         Returns {strategy: {metric: [Q + 1 floats]}, "n_queries": queries ranked per strategy}.  The model is left
         untouched, bit for bit."""
         from . import elicit
         return elicit.ranking_curve(self, pool, y_pool, n_questions, field, X_test, y_test, rank_field, ks, strategies,
-                                    exact, exclude, match_fields, threshold, ineligible, bound, **session_kw)
+                                    exact, exclude, match_fields, threshold, ineligible, bound, implicit,
+                                    **{k: (_implicit_priors(v) if implicit and k == "priors" else v)
+                                       for k, v in session_kw.items()})
 
     # ------------------------------------------------------------------ fold-in (vae_amd/foldin.py)
     @torch.no_grad()
@@ -1715,6 +1720,43 @@ class VFM(nn.Module):
         from . import elicit
         return elicit.run_field_exact(self, pool, y_pool, n_questions, field, strategy, history, seed, kl_weight, reset,
                                       write, return_moments, return_theta, key_field, priors=priors)
+
+    @torch.no_grad()
+    def elicit_field_implicit(self, pool, y_pool, n_questions: int, field: int = 0, *, w0: float, w1: float = 1.0,
+                              strategy: str = "variance", history=None, seed: int = 0, kl_weight: float = 1.0,
+                              reset: bool = False, write: bool = False, return_moments: bool = False,
+                              return_theta: bool = False, chunk_rows: int = 2048, lds_dim: int = -1,
+                              priors=STANDARD_PRIOR):
+        """elicit_field_exact for a model trained by fit_implicit: n_questions rounds of
+        select_next_questions_field(n=1) followed by fold_in_implicit(rows so far, field, w0=w0, w1=w1,
+        entities=respondents) in its row-list form, bitwise what that loop computes, for every respondent in one launch
+        (include/vfm_elicit_implicit.h: vfm_elicit_implicit_f32; DESIGN.md §4 "Implicit sessions").  After every answer
+        the respondent's posterior is the optimum of its share of J_imp (implicit_objective): the history followed by
+        the rows asked so far are its observed pairs (their targets, the weight w1), every other id of the partner field
+        a pair of target 0 and weight w0 -- the objective every user of the table was fitted under, so the scores that
+        choose the next question and the ranking under the posterior are on the scale of the model's own users.
+
+        A two-field 'reg' model, kl_weight > 0, finite weights with w1 >= w0 > 0 (in fp32), ids inside their fields, no
+        partner named twice for a respondent by pool and history together (a pair is one row of J_imp), strategy "top",
+        "variance" or "random" ("mean" needs a 'class' model, "design" is not built) -- else ValueError, before anything
+        needs a GPU.  w0 has no default.  pool, y_pool, history, field, strategy, seed, write, return_moments,
+        return_theta: as elicit_field.  chunk_rows: of the partner field's base block, assembled once before the
+        session (the partner field is frozen); it gives the bits of fold_in_implicit at the same chunk_rows.  lds_dim:
+        as in fold_in_exact's solve (tests).
+
+        reset keeps the exact session's meaning: round 0 is SCORED from the prior row (mu = 0, sigma = 1; with priors=
+        from the learnt field prior) instead of the respondents' table rows.  The no-answer posterior under J_imp is not
+        the prior but the base-only optimum -- every partner a pair of target 0 -- so the cold-start recipe is
+        m.fold_in_implicit(X[:0], y[:0], field, w0=w0, entities=respondents) followed by a session with reset=False.
+
+        priors (a sweep.GroupPriors, e.g. fit_implicit(learn_priors=True)["priors"]; leave it out for N(0, 1), an
+        explicit None is a TypeError): every round is fold_in_implicit(priors=priors).  At (0, 1) everything returned
+        and written is the call without priors=, bit for bit.
+        Returns elicit_field's dict; loss [U, Q] is fold_in_implicit's loss after each round."""
+        from . import elicit
+        return elicit.run_field_implicit(self, pool, y_pool, n_questions, field, w0, w1, strategy, history, seed,
+                                         kl_weight, reset, write, return_moments, return_theta, chunk_rows, lds_dim,
+                                         priors=_implicit_priors(priors))
 
     @torch.no_grad()
     def elicitation_curve_field_exact(self, pool, y_pool, n_questions: int, field: int = 0,

@@ -732,6 +732,17 @@ def _check_entities(model, entities, field):
     return e.contiguous()
 
 
+def implicit_base(model, lo, hi, chunk_rows):
+    """The base block [vfm_implicit_base_doubles(d)] fp64 of the id range [lo, hi) at the current tables
+    (vfm_implicit_base_f32): its bits depend on the range, chunk_rows and d alone."""
+    o = _lib.ops()
+    out = torch.empty(o.implicit_base_doubles(model.d), dtype=torch.float64, device=model.device)
+    ws = torch.empty(o.implicit_base_workspace_bytes(hi - lo, int(chunk_rows), model.d), dtype=torch.uint8,
+                     device=model.device)
+    o.implicit_base(*model._views(model._flat), ws, out, lo, hi - lo, int(chunk_rows), foldin._link_flags(model))
+    return out
+
+
 class ImplicitPlan:
     """What one (X, y, field) of an implicit solve needs and that does not depend on the parameters: a SweepPlan of the
     observed rows (its sort, its chunk table and its max_workspace_bytes grouping, the groups sized by
@@ -768,13 +779,7 @@ class ImplicitPlan:
 
     def base(self, model):
         """The partner field's base block [vfm_implicit_base_doubles(d)] fp64 at the current tables."""
-        o = _lib.ops()
-        lo, hi = self.partner_range
-        out = torch.empty(o.implicit_base_doubles(self.d), dtype=torch.float64, device=model.device)
-        ws = torch.empty(o.implicit_base_workspace_bytes(hi - lo, self.chunk_rows, self.d), dtype=torch.uint8,
-                         device=model.device)
-        o.implicit_base(*model._views(model._flat), ws, out, lo, hi - lo, self.chunk_rows, foldin._link_flags(model))
-        return out
+        return implicit_base(model, *self.partner_range, self.chunk_rows)
 
     def run(self, model, kl_weight, w0, w1, prior=None, weights=None):
         """Write the optimum of every entity of the plan into the model's tables: the base of the partner field, then
